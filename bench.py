@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/sec of 256x256 class-conditional HQ-Transformer sampling on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]            (N > 1: launched by torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]     (N > 1: launched by torch.distributed.run)
 
 One "step" = one pass of the hot path over one batch per GPU: the 64-position hierarchical AR loop
 (`sampling_ihqgpt`) followed by the HQ-VAE decode of the sampled code grids and clamp(0.5x+0.5) -- exactly
@@ -12,9 +12,11 @@ step; top_k = top_p = None, temperatures [1, 1]).  Weak scaling: every rank samp
 weights replicated, no collective inside the path (every image is an independent chain); `--gather pixels|codes`
 adds an optional RCCL gather of each step's result to rank 0.
 
-The JSON line also carries `roofline` (dominant kernel family, measured live with HIP events on the
-launch stream by libhqt's per-launch timers in a separate un-graphed pass) and `cpu_baseline` (the numpy
-oracle = a port of the reference's CPU path, timed on this box's host cores on a bounded sample).
+A plain run sets up, warms up, times the K steps and prints the line.  With `--full` the line also carries what takes runs of its
+own: `serial` / `like_for_like` (the same steps one at a time), `exact_mode` (the fp32-accurate AR loops), `roofline` (dominant
+kernel family, measured live with HIP events on the launch stream by libhqt's per-launch timers in a separate un-graphed pass),
+`cpu_baseline` (a port of the reference's CPU path, timed on this box's host cores on a bounded sample) and
+`host_ms_per_step_unthrottled`.  `--dump-outputs DIR` writes the codes and pixels of the last timed step as float32 .npy files.
 """
 from __future__ import annotations
 
@@ -45,7 +47,8 @@ def parse():
     p = argparse.ArgumentParser()
     p.add_argument('--gpus', type=int, default=1)
     p.add_argument('--steps', type=int, default=96, help='timed steps; the default keeps the timed region above 5 s (a multiple of --merge: whole passes)')
-    p.add_argument('--warmup', type=int, default=6)
+    p.add_argument('--warmup', type=int, default=6, help='untimed steps before the timed region, rounded up to whole passes of the timed '
+                   'schedule; every lane runs at least one pass (and the shorter last pass, if any)')
     p.add_argument('--sampler', choices=['harness', 'quality'], default='harness',
                    help='harness: top_k = top_p = None, T = [1, 1] (measure_throughput/__main__.py:93-101, the headline); quality: top_k = 2048, '
                         'top_p = 1.0, T = 0.95 on every level (checkpoints/README.md:6, the defaults of sampling_hqmodel.py:27-31) -- exercises the '
@@ -62,10 +65,15 @@ def parse():
                    help='RCCL gather of every step\'s result to rank 0 (BASELINE.json configs[2]: "RCCL gather over xGMI").  Default: pixels when '
                         'N > 1 (the finished images of every rank land on rank 0 inside the timed region), n/a at N = 1; none = no collective at all '
                         '(the path itself has no exchange step)')
-    p.add_argument('--no-cpu-baseline', action='store_true')
-    p.add_argument('--no-roofline', action='store_true')
+    p.add_argument('--full', action='store_true', help='also measure what the headline does not need, after the timed steps: the '
+                   'one-step-at-a-time record (serial / like_for_like), exact_mode, roofline, cpu_baseline and the unthrottled host cost per step')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write what the last timed step returned -- codes of every level and the clamped pixels (rank 0 with several GPUs) -- '
+                        'to DIR/<name>.npy in float32; above DUMP_BYTES in all, the same fixed, seeded sample of images from every array')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the `cpu_baseline` record')
+    p.add_argument('--no-roofline', action='store_true', help='with --full: skip the `roofline` record')
     p.add_argument('--no-graph', action='store_true')
-    p.add_argument('--no-exact-mode', action='store_true', help='skip the `exact_mode` record (fp32 AR loop: a few seconds)')
+    p.add_argument('--no-exact-mode', action='store_true', help='with --full: skip the `exact_mode` record (fp32 AR loop: a few seconds)')
     p.add_argument('--inflight', type=int, default=None, help='passes in flight per GPU: consecutive passes are round-robined over this many '
                    'lanes (own HIP stream, KV cache and activations; shared weights).  1 = one pass at a time.  Default: see --merge')
     p.add_argument('--merge', type=int, default=None, help='execute this many queued steps as ONE device pass of merge x batch rows (every step keeps its own class id, '
@@ -243,6 +251,27 @@ def pmc_traffic(family, rows=None):
 
 
 DEFAULT_AR_PRIORITY = False      # measured: profiles/r05_ar_priority.txt
+DUMP_BYTES = 64_000_000          # --dump-outputs: bytes of array data in all (a batch of 64 images at 256 x 256 with its codes: 50.4 MB)
+
+
+def dump_outputs(path, ct, cb, px):
+    """What a caller of the timed path receives for one step -- the codes of every level and the pixels -- as float32 .npy files
+    (codes < 2^24: exact).  More than DUMP_BYTES: the rows (images) of a fixed, seeded sample, the same rows from every array."""
+    arrays = {'codes_top': ct}
+    if isinstance(cb, (list, tuple)):
+        arrays.update({f'codes_level{i + 1}': c for i, c in enumerate(cb)})
+    else:
+        arrays['codes_bot'] = cb
+    arrays['pixels'] = px
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    n = ct.shape[0]
+    keep = min(n, (DUMP_BYTES - 1024 * len(arrays)) // sum(a[0].nbytes for a in arrays.values()))     # 1024: room for each .npy header
+    if keep < n:
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f'{k}.npy'), a)
 
 
 def default_schedule(steps, merge=None, inflight=None, wide=False):
@@ -428,8 +457,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    for i in range(args.warmup):
-        step(i)
+    # one step at a time: the order the --full records and a --positions run time (the pipelined timed region is warmed below)
+    if args.full or n_pos < n_full:
+        for i in range(args.warmup):
+            step(i)
     barrier()
     # Optional pipeline experiment (--overlap): decode (+gather) of batch k on a second, lower-priority stream underneath
     # the AR loop of batch k+1.  Measured on MI355X: AR 101 -> 129 ms under contention, net 494 -> 473 images/s, so the
@@ -440,7 +471,7 @@ def main():
     s_dec = torch.cuda.Stream(device=dev, priority=lo_prio) if overlap else s_ar
     # ---- the timed region: K steps, round-robined over `inflight` lanes (hqtransformer_amd/pipeline.py).  Every step is
     #      one complete batch-B pass (64-position AR loop + decode + clamp [+ gather]); lanes only change the schedule.
-    from hqtransformer_amd.pipeline import InflightSampler
+    from hqtransformer_amd.pipeline import InflightSampler, Pending
     inflight, merge = default_schedule(args.steps, args.merge, args.inflight, txt_cond or three)
     if args.positions:
         merge = 1                                  # debug runs (counter collection) sample a few positions of one pass
@@ -452,7 +483,8 @@ def main():
         gather_step(ct, px)
 
     debug_short = n_pos < n_full            # --positions (counter collection): the padded decode of step(), one lane, no pipeline
-    for li in range(0 if debug_short else max(inflight, args.warmup) * merge):  # every lane at least once: workspace, graph capture
+    # warm-up: W steps in whole passes, every lane at least once (workspace, graph capture)
+    for li in range(0 if debug_short else max(inflight, -(-args.warmup // merge)) * merge):
         pipe.submit(B, cond_of(li), seed=1000 + li, max_seq_len=n_pos, use_fp16=fast, sample_offset=rank * B,
                     use_graph=not args.no_graph, after=after, precision=dec_prec, **samp_kw)
     pipe.flush()
@@ -479,11 +511,14 @@ def main():
         dist.all_gather(allt, t)
         elapsed_ranks = [float(x.item()) for x in allt]
         elapsed_lanes = max(elapsed_ranks)         # the contract's MAX over ranks
+    if args.dump_outputs and rank == 0:
+        last = kept[-1].get() if isinstance(kept[-1], Pending) else kept[-1]      # merged steps: a Pending, filled by the drain above
+        dump_outputs(args.dump_outputs, *last[:3])
     # what the host itself spends per step: one more pass submitted into EMPTY queues (untimed), so that nothing throttles the submitting thread
     # (at most 8 steps: a pass of 32 steps is > 4000 launches, more than the HIP queues take without blocking the submitter -- measured 26 ms
     # "per step" that way, all of it waiting; the first, untimed round captures the graph of that row count)
     host_free_s, host_free_steps = 0.0, min(merge, 8)
-    if not debug_short:
+    if args.full and not debug_short:
         for timed_round in (False, True):
             t1 = time.perf_counter()
             for j in range(host_free_steps):
@@ -499,8 +534,9 @@ def main():
         dist.all_gather(allt, t)
         host_ms_ranks = [round(1000 * float(x.item()) / args.steps, 3) for x in allt]
     del kept
-    pipe.release(B, n_pos)            # lane 0 back to the latency-oriented kernels for the one-at-a-time reference pass
-    sample_codes(0, not args.no_graph)  # untimed: the policy change re-captures lane 0's graph; keep that out of the pass below
+    if args.full:
+        pipe.release(B, n_pos)            # lane 0 back to the latency-oriented kernels for the one-at-a-time reference pass
+        sample_codes(0, not args.no_graph)  # untimed: the policy change re-captures lane 0's graph; keep that out of the pass below
 
     # ---- reference pass: the same steps one at a time on one lane (the reference harness's order), with per-phase events
     def one_at_a_time(n, ar_prec, prec, gather=True):
@@ -540,14 +576,16 @@ def main():
         return {'value': round(world * B * n / el, 2), 'ms_per_step': round(1000 * el / n, 3), 'steps': n,
                 'phase_ms': {'ar': round(a_ms, 3), 'decode': round(d_ms, 3)}}
 
-    n_serial = args.steps if (inflight == 1 and merge == 1) else min(args.steps, 3)
-    serial = one_at_a_time(n_serial, args.precision, dec_prec)
-    serial['note'] = 'the same steps one at a time on one lane (the reference harness order: measure_throughput/__main__.py:84-116)'
-    ar_ms, dec_ms = serial['phase_ms']['ar'], serial['phase_ms']['decode']
+    serial = None
+    if args.full:
+        n_serial = args.steps if (inflight == 1 and merge == 1) else min(args.steps, 3)
+        serial = one_at_a_time(n_serial, args.precision, dec_prec)
+        serial['note'] = 'the same steps one at a time on one lane (the reference harness order: measure_throughput/__main__.py:84-116)'
+        ar_ms, dec_ms = serial['phase_ms']['ar'], serial['phase_ms']['decode']
     # ---- the arithmetic whose code sequences are BIT-EXACT against the reference's CPU path (fp32 AR loop; the decode stays fp32-accurate):
     #      the same workload, one step at a time and as one merged pass of the timed region's row count
     exact_mode = None
-    if fast and not args.no_exact_mode and not args.positions:
+    if args.full and fast and not args.no_exact_mode and not args.positions:
         xprec = dec_prec if dec_prec != 'fast' else 'split'
         what = {'exact': 'EXACT: fp32 weights / activations / accumulation -- every nn.Linear of up to 256 rows on the fp32 MATRIX instructions (exact_mfma_gemm_kernel: v_mfma_f32_16x16x4_f32, '
                          'bitwise an fmaf chain), larger ones on the vector ALUs (gemm_tile_kernel) -- codes bit-identical to the oracle (tests/test_gpu_timed_schedule.py)',
@@ -598,7 +636,7 @@ def main():
             'config': {'workload': (f'text-to-image ({s2.ctx_len_txt}-token synthetic prompts, prefill + ' if txt_cond else 'imagenet256-classcond (') + f'hq-vae({"8x8+16x16+32x32, three code levels" if three else "8x8+16x16"})+hq-transformer {s2.n_layers}L/{s2.embed_dim}d), '
                                    f'{args.steps} steps of batch {B}/GPU, {n_pos} top positions, ' + (f'top_k={tk}, top_p={tp}, T={T} (quality-mode sampler)' if quality else 'top_k=top_p=None, T=[1,1]') +
                                    (f'; SCHEDULE: {args.steps} x {B}-row steps merged into {merge * B}-row passes ({merge} steps per pass, {inflight} passes in flight) -- the one-step-at-a-time order of the '
-                                    f'reference harness is the top-level `like_for_like` record' if (merge > 1 or inflight > 1) else '; one step at a time (the reference harness order)'),
+                                    f'reference harness is the top-level `like_for_like` record of --full' if (merge > 1 or inflight > 1) else '; one step at a time (the reference harness order)'),
                        'global_batch': world * B, 'per_gpu_batch': B, 'steps_per_pass': merge, 'parallelism': f'dp{world} (sample-sharded, weights replicated)',
                        # the schedule, in numbers: a device pass executes `merge` steps at once, `inflight` passes are resident per GPU
                        'schedule': (('chosen from K: the timed steps are split over 3 lanes in passes of up to 16 steps (merge = min(16, ceil(K / 3)))' if (txt_cond or three) else
@@ -607,7 +645,7 @@ def main():
                        'rows_per_pass': merge * B, 'images_in_flight_per_gpu': merge * B * inflight,
                        'step_latency_ms': round(1000 * elapsed / args.steps * merge * inflight, 1),
                        'step_latency_note': 'time from a step entering its pass to its pixels: one pass per lane, lanes share the GPU (ms_per_step x merge x lanes); '
-                                            'serial.ms_per_step is the latency of the unmerged one-step-at-a-time order',
+                                            'serial.ms_per_step (--full) is the latency of the unmerged one-step-at-a-time order',
                        'precision': {'ar': 'FAST: bf16 weights + MFMA, fp32 accumulate / LayerNorm / softmax / sampler (the reference harness samples under fp16 autocast)' if fast else 'EXACT: fp32',
                                      'decode': {'split': 'SPLIT: fp32-accurate on the matrix cores (fp16 hi/lo operands, 3 MFMAs per term, fp32 accumulate); pixels within 1e-4 of the fp32 oracle '
                                                          '(the reference harness decodes in fp32, outside autocast)',
@@ -619,29 +657,31 @@ def main():
                        'merge': (f'{merge} consecutive batch-{B} steps execute as ONE device pass of {merge * B} rows (own class id, Philox seed and global row indices per step).  In EXACT (fp32) arithmetic '
                                  f'the draws of a step do not depend on what it is merged with (bit-identical to the unmerged call); in FAST (bf16, this line) the GEMM / attention / sampler kernels are chosen by the row '
                                  f'count of the pass, so draws are reproducible per (seed, schedule) and agree with the unmerged call only within the FAST gates (tests/test_gpu_timed_schedule.py).  '
-                                 f'The reference harness runs one batch-{B} step at a time -- that order is the `like_for_like` (= `serial`) record') if merge > 1 else 'none'},
+                                 f'The reference harness runs one batch-{B} step at a time -- that order is the `like_for_like` (= `serial`) record of --full') if merge > 1 else 'none'},
             # bit-exactness against the reference's CPU path holds for the fp32 AR loop (--precision exact, the `exact_mode` record) only; the timed arithmetic is tolerance-gated
             'bit_exact_codes': (not fast),
             'gather_ok': (None if dist is None else (args.gather == gather_requested)),
             # per rank: wall time of the timed region between the two barriers and the images/s of that rank alone; `value` is world * B * K / max(elapsed_s_ranks)
             'elapsed_s_ranks': [round(v, 4) for v in elapsed_ranks], 'value_ranks': [round(B * args.steps / v, 2) for v in elapsed_ranks],
             'host_ms_per_step': max(host_ms_ranks), 'host_ms_per_step_ranks': host_ms_ranks,
-            'host_ms_per_step_unthrottled': round(1000 * host_free_s, 3),
             'host_ms_note': 'host_ms_per_step = wall time until the last step of the timed region was handed to HIP / steps -- the runtime blocks (spins) the submitting thread '
-                            'when its queues are full, so a value close to ms_per_step means the DEVICE paces the run; host_ms_per_step_unthrottled = the same submission '
-                            f'into empty queues (one untimed pass of {host_free_steps} steps, rank 0): what the host itself costs per step',
+                            'when its queues are full, so a value close to ms_per_step means the DEVICE paces the run' +
+                            (f'; host_ms_per_step_unthrottled = the same submission into empty queues (one untimed pass of {host_free_steps} steps, rank 0): '
+                             'what the host itself costs per step' if args.full else ''),
             'env_switches': {k: v for k, v in sorted(os.environ.items()) if k.startswith('HQT_')},
-            'serial': serial,
-            # the SAME record under the name VERDICT r03 asked for: BASELINE configs[1] ("batch 64") taken literally, one step at a time
-            'like_for_like': dict(serial, images_in_flight_per_gpu=B),
         }
+        if args.full:
+            out['host_ms_per_step_unthrottled'] = round(1000 * host_free_s, 3)
+            out['serial'] = serial
+            # the SAME record under the name VERDICT r03 asked for: BASELINE configs[1] ("batch 64") taken literally, one step at a time
+            out['like_for_like'] = dict(serial, images_in_flight_per_gpu=B)
         if exact_mode is not None:
             out['exact_mode'] = exact_mode
         if n_pos < n_full or args.skip_decode:
             out['INVALID'] = f'debug run: {n_pos} of {n_full} top positions sampled' + (', decode skipped' if args.skip_decode else '')
 
     # ---- roofline: per-launch HIP-event timers inside libhqt, un-graphed pass, rank 0 only
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # One pass of the timed region = `merge` steps = Bm rows: time the kernels of THAT pass (one lane, un-graphed, per-launch events).
         Bm = merge * B
         e2, e1 = model.stage2.engine(Bm, n_pos), model.stage1.engine(Bm)
@@ -743,7 +783,7 @@ def main():
         out['kernel_ms_per_pass'] = {k: [v[0], round(v[1], 3)] for k, v in sorted(rep.items(), key=lambda kv: -kv[1][1])}
         out['kernel_ms_per_pass_note'] = f'[launches, ms] per pass of {Bm} images ({merge} steps), un-graphed, one lane'
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(cfg, s2, s1, B)
         if not txt_cond and not three and s2.n_layers == 12:
             # the reference ITSELF (PyTorch CPU, fp32, 8 threads) as measured once in the build container, BASELINE.md section 2 -- it cannot

@@ -4,6 +4,8 @@ import glob
 import json
 import os
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -124,3 +126,58 @@ def test_round4_records_of_the_committed_driver_line():
     # the 640-row tile geometry: 59.1 -> 55.7 MB per launch)
     assert gemm['traffic'] is None or (want is not None and abs(gemm['traffic'] - want) / want < 0.10)
     assert d['cpu_baseline']['kind'] == 'native-port' and d['cpu_baseline']['cores'] >= 1
+
+
+def _bench_module(name):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, 'bench.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_outputs_names_dtype_and_size_cap(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per array a caller receives; above the byte cap the same seeded rows of every array."""
+    import numpy as np
+    import torch
+    mod = _bench_module('bench_mod3')
+    ct = torch.arange(8 * 4, dtype=torch.int64).reshape(8, 4)
+    cb = torch.arange(8 * 4 * 4, dtype=torch.int64).reshape(8, 4, 4)
+    px = torch.rand(8, 3, 16, 16)
+    mod.dump_outputs(str(tmp_path / 'all'), ct, cb, px)
+    got = {f[:-4]: np.load(tmp_path / 'all' / f) for f in os.listdir(tmp_path / 'all')}
+    assert sorted(got) == ['codes_bot', 'codes_top', 'pixels'] and all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got['codes_top'], ct.numpy()) and np.array_equal(got['codes_bot'], cb.numpy()) and np.array_equal(got['pixels'], px.numpy())
+    per_image = 4 * (4 + 16 + 3 * 16 * 16)
+    monkeypatch.setattr(mod, 'DUMP_BYTES', 3 * per_image + 1024 * 3)
+    for d in ('a', 'b'):
+        mod.dump_outputs(str(tmp_path / d), ct, [cb, cb[:, :2]], px)
+    a = {f[:-4]: np.load(tmp_path / 'a' / f) for f in os.listdir(tmp_path / 'a')}
+    b = {f[:-4]: np.load(tmp_path / 'b' / f) for f in os.listdir(tmp_path / 'b')}
+    assert sorted(a) == ['codes_level1', 'codes_level2', 'codes_top', 'pixels'] and all(np.array_equal(a[k], b[k]) for k in a)
+    rows = (a['codes_top'][:, 0] / 4).astype(int)
+    assert len(rows) == 2 and np.all(np.diff(rows) > 0)        # codes_level2 makes an image larger than per_image: 2 rows fit, sorted
+    assert np.array_equal(a['pixels'], px.numpy()[rows]) and np.array_equal(a['codes_level2'], cb[:, :2].numpy()[rows])
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full) times the steps and prints the headline keys without the records that need runs of their own; with the same
+    arguments, --dump-outputs writes the same arrays from run to run."""
+    import numpy as np
+    lines = []
+    for d in ('a', 'b'):
+        r = _run_bench(['--gpus', '1', '--steps', '3', '--warmup', '1', '--merge', '2', '--inflight', '2', '--config',
+                        os.path.join(ROOT, 'configs', 'tiny-cls.yaml'), '--dump-outputs', str(tmp_path / d)], {})
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1]))
+    d = lines[0]
+    assert d['steps'] == 3 and d['ms_per_step'] > 0 and abs(d['value'] - 64 * 1000.0 / d['ms_per_step']) / d['value'] < 0.01
+    assert not {'serial', 'like_for_like', 'exact_mode', 'roofline', 'cpu_baseline', 'host_ms_per_step_unthrottled'} & set(d)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['codes_bot.npy', 'codes_top.npy', 'pixels.npy'] and names == sorted(os.listdir(tmp_path / 'b'))
+    for n in names:
+        a, b = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert a.dtype == np.float32 and a.shape[0] == 64 and np.array_equal(a, b), n
+    px = np.load(tmp_path / 'a' / 'pixels.npy')
+    assert px.shape == (64, 3, 64, 64) and 0.0 <= px.min() and px.max() <= 1.0

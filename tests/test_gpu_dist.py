@@ -98,7 +98,7 @@ def _bench_two_ranks(extra_env, gpus_needed, world=2):
     s.close()
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(world), '--master-addr', '127.0.0.1', '--master-port', str(port),
            os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--steps', '6', '--warmup', '2', '--merge', '2', '--inflight', '2',
-           '--config', os.path.join(ROOT, 'configs', 'tiny-cls.yaml'), '--no-cpu-baseline', '--no-roofline']
+           '--config', os.path.join(ROOT, 'configs', 'tiny-cls.yaml'), '--full', '--no-cpu-baseline', '--no-roofline']
     r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', **extra_env), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     line = [l for l in r.stdout.splitlines() if l.startswith('{')][-1]
@@ -143,7 +143,7 @@ def test_bench_two_gpus_over_rccl():
 
 def _bench_direct(args, extra_env):
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py')] + args + ['--steps', '6', '--warmup', '2', '--merge', '2', '--inflight', '2',
-           '--config', os.path.join(ROOT, 'configs', 'tiny-cls.yaml'), '--no-cpu-baseline', '--no-roofline', '--no-exact-mode']
+           '--config', os.path.join(ROOT, 'configs', 'tiny-cls.yaml'), '--full', '--no-cpu-baseline', '--no-roofline', '--no-exact-mode']
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
     r = subprocess.run(cmd, cwd=ROOT, env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY='0', **extra_env), capture_output=True, text=True, timeout=900)
     return r

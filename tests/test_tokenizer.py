@@ -1,27 +1,24 @@
 """Text front-end against fixture G10 = ids the reference's own `create_tokenizer('bpe16k_huggingface')` + dataset padding /
 truncation produced for 20 captions (tools/gen_golden_tokenizer.py; hqvae/tokenizers/__init__.py:15-39,
-hqvae/datasets/__init__.py:145-151).  The 16k vocabulary is a data file of the reference that this repository does not copy:
-the comparison runs wherever a reference checkout is present (HQT_REFERENCE or /root/reference -- the build container) and is
-skipped elsewhere; the fixture's self-consistency checks run everywhere."""
+hqvae/datasets/__init__.py:145-151).  The 16k vocabulary is a data file of the reference that this repository does not copy; the
+fixture carries the part of it those captions use (every merge that fires on them and the tokens it reads or writes, under their
+original ids), which encodes them exactly as the full vocabulary does (checked when the fixture is generated)."""
 import os
 
 import numpy as np
-import pytest
 import torch
 
 from hqtransformer_amd import text
-from tests.helpers import load
-
-REF = os.environ.get('HQT_REFERENCE', '/root/reference')
+from tests.helpers import GOLDEN, load
 
 
 def vocab_pair():
-    """HQT_BPE16K_VOCAB / HQT_BPE16K_MERGES name the two files directly (any host that has them: the test then RUNS, and fails if they are
-    unreadable); otherwise the reference checkout under HQT_REFERENCE or /root/reference; None = neither is present."""
+    """HQT_BPE16K_VOCAB / HQT_BPE16K_MERGES name a full vocabulary pair (the test then reads it, and fails if it is unreadable);
+    otherwise the committed subset of fixture G10."""
     v, m = os.environ.get('HQT_BPE16K_VOCAB'), os.environ.get('HQT_BPE16K_MERGES')
     if v or m:
         return (v or '', m or '')
-    return text.find_reference_vocab(REF)
+    return tuple(os.path.join(GOLDEN, f'g10_bpe16k_subset_{n}') for n in ('vocab.json', 'merges.txt'))
 
 
 def test_fixture_is_self_consistent():
@@ -37,7 +34,6 @@ def test_fixture_is_self_consistent():
     assert (fx['ids_64'][:, :32] == fx['ids_32'])[fx['ids_32'][:, -1] == int(fx['pad_id_32'])].all()   # short captions: the 32-id form is a prefix
 
 
-@pytest.mark.skipif(vocab_pair() is None, reason='neither HQT_BPE16K_VOCAB / HQT_BPE16K_MERGES nor a reference checkout (bpe-16k vocabulary) is present')
 def test_build_tokenizer_reproduces_the_reference_ids():
     fx = load('g10_tokenizer.npz')
     vocab, merges = vocab_pair()
