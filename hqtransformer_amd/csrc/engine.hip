@@ -376,8 +376,12 @@ extern "C" int hqt_create(const hqt_config* cfg, int device, hqt_handle** out) {
         const int hs = c.embed_dim / c.n_heads;
         if (hs % 8 || hs > 256 || (hs & (hs - 1))) return fail(HQT_ERR_INVALID, "head_dim %d unsupported (power of two in [8, 256])", hs);
         if (c.vocab_top != c.vocab_bot) return fail(HQT_ERR_INVALID, "vocab_top != vocab_bot");
-        if (c.depth_decoding < 0 || c.depth_decoding > HQT_DEPTH_TOP2MID2BOT || (c.depth_decoding && c.code_levels != 3))
-            return fail(HQT_ERR_INVALID, "depth_decoding %d: 0 'parallel-add', 1 'parallel', 2 'parallel-reduce', 3 'top2mid2bot' (three code levels only)", c.depth_decoding);
+        const bool bidir = c.depth_decoding == HQT_DEPTH_BIDIRECTIONAL;
+        if (c.depth_decoding < 0 || c.depth_decoding > HQT_DEPTH_BIDIRECTIONAL || (c.depth_decoding && !bidir && c.code_levels != 3) || (bidir && c.code_levels == 3))
+            return fail(HQT_ERR_INVALID, "depth_decoding %d: 0 'parallel-add', 1 'parallel', 2 'parallel-reduce', 3 'top2mid2bot' (three code levels only), "
+                        "4 'bidirectional' (two code levels only)", c.depth_decoding);
+        if (bidir && c.cond_type == HQT_COND_TEXT)       // the reference's bidirectional step does not pick the last text token (hierarchical_ar.py:808)
+            return fail(HQT_ERR_INVALID, "depth_decoding 4 'bidirectional' with text conditioning is not built");
         if (c.vocab_top > HQT_MAX_V || c.vocab_top % 4) return fail(HQT_ERR_INVALID, "vocab size %d unsupported", c.vocab_top);
         if (c.cond_type == HQT_COND_CLASS && c.n_classes < 1) return fail(HQT_ERR_INVALID, "n_classes");
         if (c.max_steps < 1 || c.max_steps > c.ctx_len_img) return fail(HQT_ERR_INVALID, "max_steps must be in [1, ctx_len_img]");
@@ -423,7 +427,7 @@ static int alloc_workspace(hqt_handle* hp) {
         const size_t D = c.embed_dim;
         const int Tp = c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : 1;    // rows of the widest body pass
         h->Tmax = (c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : 0) + c.max_steps;
-        const int Tdepth = c.code_levels == 3 ? 16 : 4;      // rows per sample of the widest depth sub-step
+        const int Tdepth = c.code_levels == 3 ? 16 : (c.depth_decoding == HQT_DEPTH_BIDIRECTIONAL ? 5 : 4);      // rows per sample of the widest depth sub-step
         const int Kdepth = c.code_levels == 3 ? 21 : 5;      // keys of the depth cache
         const size_t rows = (B * (size_t)std::max(Tp, Tdepth) + 31) / 32 * 32;
         CHK(dev_alloc(h.get(), (void**)&h->x, rows * D * 4, true));
@@ -1106,8 +1110,8 @@ static int persist_build(hqt_handle* h) {
     for (auto& b : h->depth) if (!b.qkv.bias_ln || !b.fc1.bias_ln) return HQT_OK;
     std::vector<PackSrc> src;
     int k4 = 0;
-    if (c.code_levels != 3 && h->head_top.bias_ln) {
-        // two levels: body -> ln_f + sos_depth (a phase on the residual stream itself) -> the four single-key blocks of depth sub-step 0 -> head_top
+    if (c.code_levels != 3 && c.depth_decoding != HQT_DEPTH_BIDIRECTIONAL && h->head_top.bias_ln) {
+        // two levels, 'parallel': body -> ln_f + sos_depth (a phase on the residual stream itself) -> the four single-key blocks of depth sub-step 0 -> head_top
         PersistProg& pr = h->pfull;
         for (auto& b : h->body) persist_block_shapes(h, b, false, h->Tmax, &k4, pr.phases, src);
         PersistPhase ph{};
@@ -1128,7 +1132,7 @@ static int persist_build(hqt_handle* h) {
             HIPCHK(hipMemcpy(h->lnf_shift, beta.data(), (size_t)D * 4, hipMemcpyHostToDevice));
         }
     }
-    if (!h->pfull.ok) {                          // three code levels (or no folded head): the body alone
+    if (!h->pfull.ok) {                          // three code levels, 'bidirectional' (or no folded head): the body alone
         src.clear(); k4 = 0;
         for (auto& b : h->body) persist_block_shapes(h, b, false, h->Tmax, &k4, h->pbody.phases, src);
         CHK(persist_build_one(h, h->pbody, src));
@@ -1310,6 +1314,65 @@ static int run_block_dln(hqt_handle* h, const SampleCtx& c, const BlockW& bw, fl
     return HQT_OK;
 }
 
+// The 'bidirectional' depth head (hierarchical_ar.py:791-878; its Blocks have causal_attn = False: layers.py:290-330, no mask at all):
+// ONE pass of the depth blocks over five rows per sample, [ln_f(h) + sos_depth, pos_emb_depth[0..3]], with full 5 x 5 attention and no
+// cache carried to the next position.  Top logits from row 0 (ln_top, head_top), bottom logits from rows 1..4 (ln_bot, head_bot).  All five
+// draws use temperature_top, top_k_bot and top_p_bot, as the reference does (:866-873); the noise / logits_out slots are the parallel head's.
+static int run_depth_bidir(hqt_handle* h, const SampleCtx& c, int Tq_body) {
+    const hqt_config& cf = h->cfg;
+    const int D = cf.embed_dim, B = c.B, V = cf.vocab_top, M = 5 * B;
+    const int adt = c.md.act_dt();
+    const size_t dkv_layer = (size_t)cf.max_batch * 5 * D * c.md.act_sz();
+    const bool dln = dln_ok(h, c, h->depth[0], M);
+    {
+        Timed t(h, "bidir_depth_input", c.st);
+        LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, B, D, Tq_body, Tq_body - 1, 1e-5f, DT_F32, 0,
+                  h->pend.slabs, h->pend.S, h->pend.rows, h->pend.bias, dln ? h->xdpk : nullptr, dln ? packed_mb(M) : 0, h->partsd};
+        ln.fill = W(h, "pos_emb_depth.weight");
+        h->pend.slabs = nullptr; h->pend.S = 0;
+        HIPCHK(launch_bidir_depth_input(ln, c.st));
+        h->npartsd = 1;
+    }
+    for (int l = 0; l < cf.n_layers_depth; ++l) {     // Tq = 5 > 1: never the single-key shortcut of run_block_dln
+        void* kc = (char*)h->dk + l * dkv_layer;
+        void* vc = (char*)h->dv + l * dkv_layer;
+        if (dln) CHK(run_block_dln(h, c, h->depth[l], h->xd, h->xdpk, h->partsd, &h->npartsd, 5, kc, vc, 5, 0, nullptr, 0));
+        else CHK(run_block(h, c, h->depth[l], h->xd, 5, kc, vc, 5, 0, nullptr, 0));
+    }
+    // ln_top / ln_bot of the interleaved rows into two compact operands: [B, D] (hbuf) and [4 B, D] (abuf)
+    const int pk1 = (c.md.fast && B <= PACKED_MAX_ROWS && h->head_top.wpk) ? packed_mb(B) : 0;
+    const int pk4 = (c.md.fast && 4 * B <= PACKED_MAX_ROWS && h->head_bot.wpk) ? packed_mb(4 * B) : 0;
+    {
+        Timed t(h, "bidir_head_ln", c.st);
+        LNArgs ln{h->xd, W(h, "ln_top.weight"), W(h, "ln_top.bias"), nullptr, h->hbuf, M, D, 1, 0, 1e-5f, adt, pk1,
+                  h->pend.slabs, h->pend.S, h->pend.rows, h->pend.bias, nullptr, 0, nullptr};
+        ln.gamma2 = W(h, "ln_bot.weight"); ln.beta2 = W(h, "ln_bot.bias"); ln.y2 = h->abuf; ln.out2_packed_mb = pk4;
+        h->pend.slabs = nullptr; h->pend.S = 0;
+        HIPCHK(launch_bidir_head_ln(ln, c.st));
+    }
+    GemmArgs g{};
+    g.A = h->hbuf; g.a_packed_mb = pk1; g.M = B; g.batch = 1; g.C = h->logits; g.ldc = V; g.store = STORE_ROWS;
+    CHK(run_linear(h, c.md, g, h->head_top, adt, DT_F32, c.st, "gemm_head"));
+    {
+        Timed t(h, "bidir_sampler_top", c.st);
+        SamplerArgs s{h->logits, B, V, 1, B, c.o.temperature_top, c.o.top_k_bot, c.o.top_p_bot, c.noise, 0,
+                      h->state, h->rows, c.o.n_steps, c.out_top, c.logits_out};
+        s.fast_math = c.md.fast ? 1 : 0;
+        HIPCHK(launch_sampler(s, c.st));
+    }
+    g = GemmArgs{};
+    g.A = h->abuf; g.a_packed_mb = pk4; g.M = 4 * B; g.batch = 1; g.C = h->logits; g.ldc = V; g.store = STORE_ROWS;
+    CHK(run_linear(h, c.md, g, h->head_bot, adt, DT_F32, c.st, "gemm_head"));
+    {
+        Timed t(h, "bidir_sampler_bot", c.st);
+        SamplerArgs s{h->logits, 4 * B, V, 4, B, c.o.temperature_top, c.o.top_k_bot, c.o.top_p_bot, c.noise, 1,
+                      h->state, h->rows, c.o.n_steps, c.out_bot, c.logits_out};
+        s.fast_math = c.md.fast ? 1 : 0;
+        HIPCHK(launch_sampler(s, c.st));
+    }
+    return HQT_OK;
+}
+
 // Everything of one top position after the body input x is ready (hierarchical_ar.py:482-563,667-789)
 static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_base, bool body_tbase_from_state) {
     const hqt_config& cf = h->cfg;
@@ -1326,7 +1389,8 @@ static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body
     const bool dln4 = dln_ok(h, c, h->depth[0], 4 * B) && h->head_bot.wpk_ln;
     const bool body_persistable = dln_body && body_tbase_from_state && body_t_base == 0;
     // ... up to the top logits: body, ln_f + sos_depth, depth sub-step 0, head_top as ONE persistent launch
-    const bool pfull = body_persistable && dln1 && h->single_key && persist_on(h, c, h->pfull);
+    const bool bidir = cf.depth_decoding == HQT_DEPTH_BIDIRECTIONAL;
+    const bool pfull = !bidir && body_persistable && dln1 && h->single_key && persist_on(h, c, h->pfull);
     const bool pbody = !pfull && body_persistable && persist_on(h, c, h->pbody);
     if (pfull) CHK(run_persist(h, c, h->pfull, h->x, 0, tb_dev, "persist_position"));
     if (pbody) CHK(run_persist(h, c, h->pbody, h->x, 1, tb_dev, "persist_body"));
@@ -1336,6 +1400,7 @@ static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body
         if (dln_body) CHK(run_block_dln(h, c, h->body[l], h->x, h->xpk, h->parts, &h->nparts, Tq_body, kc, vc, h->Tmax, body_t_base, tb_dev, 1));
         else CHK(run_block(h, c, h->body[l], h->x, Tq_body, kc, vc, h->Tmax, body_t_base, tb_dev, 1));
     }
+    if (bidir) return run_depth_bidir(h, c, Tq_body);
     // ln_f on the last token of each sample, + sos_depth (hierarchical_ar.py:561,684-686) -> depth-head input
     if (!pfull) {
         Timed t(h, "layernorm", c.st);

@@ -66,8 +66,19 @@ struct LNArgs {
     bf16_t* ypk;
     int ypk_mb;
     float* yparts;
+    // bidirectional depth head only (launch_bidir_*)
+    const float* fill;           // [4, D] rows 1..4 of every sample's depth input (pos_emb_depth)
+    const float* gamma2;         // ln_bot affine of rows 1..4
+    const float* beta2;
+    void* y2;                    // [4 B, D] bottom-head operand
+    int out2_packed_mb;
 };
 hipError_t launch_layernorm(const LNArgs& a, hipStream_t st);
+// bidirectional depth head (hierarchical_ar.py:803-826): x[b] = last body row of sample b (in_rows_per_group / in_row_offset) ->
+// y rows [5 b] = ln_f(x[b]) + add, [5 b + 1 .. 5 b + 4] = fill[0..3]; fp32 y, optional packed copy + row statistics (ypk)
+hipError_t launch_bidir_depth_input(const LNArgs& a, hipStream_t st);
+// M = 5 B depth rows: row 5 b -> ln_top into row b of y, row 5 b + 1 + s -> ln_bot into row 4 b + s of y2
+hipError_t launch_bidir_head_ln(const LNArgs& a, hipStream_t st);
 
 struct AttnArgs {
     const void* q;               // [B*Tq, D]

@@ -194,12 +194,28 @@ hipError_t launch_depth_embed_causal(const int64_t* codes, int stride, int slot,
 // ---------------------------------------------------------------------------------------------
 // One wave per row (4 rows per workgroup): the row lives in registers as float4 vectors (coalesced 1-KiB
 // wave loads), mean and variance are two shuffle reductions, no LDS and no barrier.
-template <typename TO>
+// MODE selects where a row goes (the bidirectional depth head, [B, 5, D] depth rows):
+//   LN_PLAIN:       output row m.
+//   LN_BIDIR_INPUT: output row 5 m (ln_f + sos_depth of sample m), and rows 5 m + 1 .. 5 m + 4 = a.fill rows 0..3 (pos_emb_depth).
+//   LN_BIDIR_HEADS: input row m = 5 b + s; s == 0 -> ln_top (gamma / beta) into row b of y, s > 0 -> ln_bot (gamma2 / beta2) into
+//                   row 4 b + s - 1 of y2 (each with its own packed layout).
+enum { LN_PLAIN = 0, LN_BIDIR_INPUT = 1, LN_BIDIR_HEADS = 2 };
+template <typename TO, int MODE = LN_PLAIN>
 __global__ __launch_bounds__(256) void layernorm_kernel(LNArgs a) {
     const int lane = threadIdx.x & 63;
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= a.M) return;
     const int D = a.D;
+    int om = m, opk = a.out_packed_mb;
+    const float* gamma = a.gamma;
+    const float* beta = a.beta;
+    void* y = a.y;
+    if (MODE == LN_BIDIR_INPUT) om = 5 * m;
+    if (MODE == LN_BIDIR_HEADS) {
+        const int b = m / 5, s = m - 5 * b;
+        om = s ? 4 * b + s - 1 : b;
+        if (s) { gamma = a.gamma2; beta = a.beta2; y = a.y2; opk = a.out2_packed_mb; }
+    }
     const long long in_row = (long long)m * a.in_rows_per_group + a.in_row_offset;      // ln_f of the prefill reads the last token of each sample
     float* x = a.x + in_row * D;
     constexpr int MAXV = 8;                       // D <= 2048 in registers; wider rows fall back to re-reading
@@ -212,8 +228,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LNArgs a) {
         v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         gmv[i] = v[i]; btv[i] = v[i];
         if (vi < nvec) {
-            gmv[i] = *reinterpret_cast<const float4*>(a.gamma + vi * 4);
-            btv[i] = *reinterpret_cast<const float4*>(a.beta + vi * 4);
+            gmv[i] = *reinterpret_cast<const float4*>(gamma + vi * 4);
+            btv[i] = *reinterpret_cast<const float4*>(beta + vi * 4);
             if (a.add) { const float4 ad = *reinterpret_cast<const float4*>(a.add + vi * 4); btv[i].x += ad.x; btv[i].y += ad.y; btv[i].z += ad.z; btv[i].w += ad.w; }
             float4 t = *reinterpret_cast<const float4*>(x + vi * 4);
             if (a.n_slabs > 0) {                  // fold in the split-K partial sums (+bias) of the previous GEMM
@@ -249,8 +265,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LNArgs a) {
         const int d = vi * 4;
         float o[4] = {(t.x - mean) * rstd * gm.x + bt.x, (t.y - mean) * rstd * gm.y + bt.y, (t.z - mean) * rstd * gm.z + bt.z,
                       (t.w - mean) * rstd * gm.w + bt.w};
-        TO* dst = a.out_packed_mb ? reinterpret_cast<TO*>(a.y) + packed_off(m, d, a.out_packed_mb)      // 4 consecutive k stay contiguous
-                                  : reinterpret_cast<TO*>(a.y) + (long long)m * D + d;
+        TO* dst = opk ? reinterpret_cast<TO*>(y) + packed_off(om, d, opk)      // 4 consecutive k stay contiguous
+                              : reinterpret_cast<TO*>(y) + (long long)om * D + d;
         if (sizeof(TO) == 2) {
             uint2 pk;
             pk.x = (unsigned)f32_to_bf16(o[0]) | ((unsigned)f32_to_bf16(o[1]) << 16);
@@ -263,7 +279,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LNArgs a) {
             uint2 pk;
             pk.x = (unsigned)f32_to_bf16(o[0]) | ((unsigned)f32_to_bf16(o[1]) << 16);
             pk.y = (unsigned)f32_to_bf16(o[2]) | ((unsigned)f32_to_bf16(o[3]) << 16);
-            *reinterpret_cast<uint2*>(a.ypk + packed_off(m, d, a.ypk_mb)) = pk;
+            *reinterpret_cast<uint2*>(a.ypk + packed_off(om, d, a.ypk_mb)) = pk;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const float r = bf16_to_f32(f32_to_bf16(o[e])); ys += r; yq += r * r; }
         }
@@ -271,20 +287,55 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LNArgs a) {
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) if (lane + i * 64 < nvec) emit(lane + i * 64, v[i], gmv[i], btv[i]);
     for (int vi = lane + MAXV * 64; vi < nvec; vi += 64) {
-        float4 bt = *reinterpret_cast<const float4*>(a.beta + vi * 4);
+        float4 bt = *reinterpret_cast<const float4*>(beta + vi * 4);
         if (a.add) { const float4 ad = *reinterpret_cast<const float4*>(a.add + vi * 4); bt.x += ad.x; bt.y += ad.y; bt.z += ad.z; bt.w += ad.w; }
-        emit(vi, *reinterpret_cast<const float4*>(x + vi * 4), *reinterpret_cast<const float4*>(a.gamma + vi * 4), bt);
+        emit(vi, *reinterpret_cast<const float4*>(x + vi * 4), *reinterpret_cast<const float4*>(gamma + vi * 4), bt);
     }
     if (a.ypk) {
         ys = wave_reduce(ys, OpAdd());
         yq = wave_reduce(yq, OpAdd());
-        if (lane == 0) { a.yparts[2 * m] = ys; a.yparts[2 * m + 1] = yq; }
+        if (lane == 0) { a.yparts[2 * om] = ys; a.yparts[2 * om + 1] = yq; }
+    }
+    if (MODE == LN_BIDIR_INPUT) {                 // the four bottom query rows: pos_emb_depth[0..3], no code embedding (hierarchical_ar.py:815-818)
+        for (int j = 1; j <= 4; ++j) {
+            const int r = om + j;
+            float ps = 0.0f, pq = 0.0f;
+            for (int vi = lane; vi < nvec; vi += 64) {
+                const float4 t = *reinterpret_cast<const float4*>(a.fill + (long long)(j - 1) * D + vi * 4);
+                *reinterpret_cast<float4*>(reinterpret_cast<float*>(y) + (long long)r * D + vi * 4) = t;
+                if (a.ypk) {
+                    const float o[4] = {t.x, t.y, t.z, t.w};
+                    uint2 pk;
+                    pk.x = (unsigned)f32_to_bf16(o[0]) | ((unsigned)f32_to_bf16(o[1]) << 16);
+                    pk.y = (unsigned)f32_to_bf16(o[2]) | ((unsigned)f32_to_bf16(o[3]) << 16);
+                    *reinterpret_cast<uint2*>(a.ypk + packed_off(r, vi * 4, a.ypk_mb)) = pk;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { const float r4 = bf16_to_f32(f32_to_bf16(o[e])); ps += r4; pq += r4 * r4; }
+                }
+            }
+            if (a.ypk) {
+                ps = wave_reduce(ps, OpAdd());
+                pq = wave_reduce(pq, OpAdd());
+                if (lane == 0) { a.yparts[2 * r] = ps; a.yparts[2 * r + 1] = pq; }
+            }
+        }
     }
 }
 hipError_t launch_layernorm(const LNArgs& a, hipStream_t st) {
     if (a.D % 4 != 0) return hipErrorInvalidValue;
     if (a.out_dtype == DT_BF16) layernorm_kernel<bf16_t><<<(a.M + 3) / 4, 256, 0, st>>>(a);
     else layernorm_kernel<float><<<(a.M + 3) / 4, 256, 0, st>>>(a);
+    return hipGetLastError();
+}
+hipError_t launch_bidir_depth_input(const LNArgs& a, hipStream_t st) {
+    if (a.D % 4 != 0 || a.out_dtype != DT_F32 || a.out_packed_mb || !a.fill) return hipErrorInvalidValue;
+    layernorm_kernel<float, LN_BIDIR_INPUT><<<(a.M + 3) / 4, 256, 0, st>>>(a);
+    return hipGetLastError();
+}
+hipError_t launch_bidir_head_ln(const LNArgs& a, hipStream_t st) {
+    if (a.D % 4 != 0 || a.M % 5 != 0 || a.add || a.ypk || !a.y2 || !a.gamma2 || !a.beta2) return hipErrorInvalidValue;
+    if (a.out_dtype == DT_BF16) layernorm_kernel<bf16_t, LN_BIDIR_HEADS><<<(a.M + 3) / 4, 256, 0, st>>>(a);
+    else layernorm_kernel<float, LN_BIDIR_HEADS><<<(a.M + 3) / 4, 256, 0, st>>>(a);
     return hipGetLastError();
 }
 

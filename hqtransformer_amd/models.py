@@ -122,7 +122,8 @@ class _Stage:
 
 
 class HQTransformerStage2(_Stage):
-    """Counterpart of ``iHQGPT`` (``hqvae/models/stage2/hierarchical_ar.py:23-216``) for model_type 'parallel' and, with
+    """Counterpart of ``iHQGPT`` (``hqvae/models/stage2/hierarchical_ar.py:23-216``) for model_type 'parallel' and 'bidirectional4'
+    (``spec.depth_decoding == 'bidirectional'``) and, with
     ``spec.levels == 3``, of the three-level ``HQTransformer`` ('parallel-add', 'parallel', 'parallel-reduce': ``spec.depth_decoding``; ``hqvae/models/stage2/hqtransformer.py``)."""
 
     def __init__(self, spec: Stage2Spec, seed: int = 0):
@@ -134,7 +135,7 @@ class HQTransformerStage2(_Stage):
         self.ctx_len_img = spec.ctx_len_img
         self.n_layers = spec.n_layers
         self.n_layers_depth = spec.n_layers_depth
-        self.model_type = 'parallel'
+        self.model_type = 'bidirectional' if spec.depth_decoding == 'bidirectional' else 'parallel'
         self.code_level = spec.levels               # HQTransformer.code_level (hqtransformer.py:185)
 
     # attributes sampling.py:183-192 and the notebook read

@@ -88,6 +88,9 @@ def sampling_ihqgpt(model,
         else:
             cond = None
     force_top = None
+    if given_top_code is not None and getattr(spec, 'depth_decoding', '') == 'bidirectional':
+        # the reference passes given_top_code to the 'parallel' head only and silently ignores it here (hierarchical_ar.py:451-479)
+        raise ValueError("given_top_code is not supported by the 'bidirectional' depth head (the reference ignores it)")
     if given_top_code is not None:
         force_top = torch.as_tensor(given_top_code)
         if force_top.dim() == 1:

@@ -13,8 +13,10 @@ from typing import Dict, List, Tuple
 
 COND_NONE, COND_CLS, COND_TXT = 0, 1, 2
 EMB_TRANSFORMER1, EMB_REDUCE = 0, 1
-# HQTransformer.decoding_type values whose three-level SAMPLING works in the reference and is built here (index = hqt_config.depth_decoding)
-DEPTH_DECODINGS = ('parallel-add', 'parallel', 'parallel-reduce', 'top2mid2bot')
+# Depth heads built here (index = hqt_config.depth_decoding).  Three levels: the HQTransformer.decoding_type values whose SAMPLING works
+# in the reference (0..3).  Two levels: 0 is iHQGPT 'parallel'; 'bidirectional' (4) is iHQGPT model_type 'bidirectional4'.
+DEPTH_DECODINGS = ('parallel-add', 'parallel', 'parallel-reduce', 'top2mid2bot', 'bidirectional')
+DEPTH_DECODINGS_L3 = DEPTH_DECODINGS[:4]
 
 
 @dataclass
@@ -34,7 +36,8 @@ class Stage2Spec:
     gelu_approx: bool = False
     ratio_bot2top: int = 4
     levels: int = 2           # code levels: 2 = iHQGPT (1 + 4 codes per position), 3 = HQTransformer 'parallel*' (1 + 4 + 16)
-    depth_decoding: str = 'parallel-add'      # three levels: HQTransformer.decoding_type, one of DEPTH_DECODINGS (hqtransformer.py:105-157,526-551)
+    depth_decoding: str = 'parallel-add'      # three levels: HQTransformer.decoding_type, one of DEPTH_DECODINGS_L3 (hqtransformer.py:105-157,526-551);
+                                              # two levels: 'parallel-add' (= iHQGPT 'parallel') or 'bidirectional' (hierarchical_ar.py:791-878)
 
     @property
     def codes_per_pos(self) -> int:  # hqtransformer.py:187-194
@@ -75,12 +78,13 @@ def stage2_spec_from_config(cfg) -> Stage2Spec:
     """Mirrors the argument plumbing of ``ImageGPT2.__init__`` (``hqvae/models/__init__.py:123-137``)."""
     s2 = cfg.stage2
     levels = 2
+    depth_decoding = 'parallel-add'
     if 'multilevel-hq' in s2.type:          # HQTransformer (hqvae/models/__init__.py:138-145)
         vs = list(s2.vocab_sizes_img)
         if len(vs) != 3 or len(set(vs)) != 1:
             raise NotImplementedError('multilevel-hq: three levels with one vocabulary size are built')
-        if s2.decoding_type not in DEPTH_DECODINGS:
-            raise NotImplementedError(f"decoding_type '{s2.decoding_type}': {', '.join(DEPTH_DECODINGS)} are built ('parallel-add' is the released "
+        if s2.decoding_type not in DEPTH_DECODINGS_L3:
+            raise NotImplementedError(f"decoding_type '{s2.decoding_type}': {', '.join(DEPTH_DECODINGS_L3)} are built ('parallel-add' is the released "
                                       "level-3 config; 'tree', 'old-parallel' and 'parallel-add-reduce' cannot sample three levels in the "
                                       "reference either: hqtransformer.py:537-549)")
         levels = 3
@@ -88,8 +92,10 @@ def stage2_spec_from_config(cfg) -> Stage2Spec:
         raise ValueError(f"stage2.type '{s2.type}' is not on the HQ-Transformer sampling path")
     else:
         model_type = s2.type.split('/')[-1] if '/' in s2.type else 'top2bot'
-        if model_type != 'parallel':
-            raise NotImplementedError(f"model_type '{model_type}': only 'parallel' is built (SURVEY.md §0 item 2)")
+        if model_type in ('bidirectional', 'bidirectional4'):       # bot_win = 2: one top + 2 x 2 bottom codes (hierarchical_ar.py:48-54)
+            depth_decoding = 'bidirectional'
+        elif model_type != 'parallel':
+            raise NotImplementedError(f"model_type '{model_type}': 'parallel' and 'bidirectional4' are built (SURVEY.md §0 item 2)")
     hp = s2.hparams
     hp_dec = s2.hparams_dec
     if hp_dec is None:  # hierarchical_ar.py:150-153
@@ -111,13 +117,16 @@ def stage2_spec_from_config(cfg) -> Stage2Spec:
     if not (hp.mlp_bias and hp.attn_bias):
         raise NotImplementedError('bias-free blocks')
     cond = COND_CLS if s2.use_cls_cond else (COND_TXT if s2.use_txt_cond else COND_NONE)
+    if depth_decoding == 'bidirectional' and cond == COND_TXT:
+        raise NotImplementedError("model_type 'bidirectional4' with text conditioning: the reference's bidirectional step runs its depth pass "
+                                  "over every text token at position 0 (hierarchical_ar.py:808) instead of the last one; not built")
     vocab = list(s2.vocab_sizes_img)[0] if levels == 3 else s2.vocab_size_img
     return Stage2Spec(levels=levels, embed_dim=hp.embed_dim, n_layers=hp.n_layers, n_heads=hp.n_heads,
                       n_layers_depth=n_layers_depth, vocab_top=vocab, vocab_bot=vocab,
                       vocab_txt=s2.vocab_size_txt, ctx_len_img=hp.ctx_len_img, ctx_len_txt=hp.ctx_len_txt,
                       n_classes=(hp.n_classes or 0), cond=cond, embedding=emb,
                       gelu_approx=bool(hp.gelu_use_approx), ratio_bot2top=(s2.ratio_bot2top or 4),
-                      depth_decoding=(s2.decoding_type if levels == 3 else 'parallel-add'))
+                      depth_decoding=(s2.decoding_type if levels == 3 else depth_decoding))
 
 
 def stage1_spec_from_config(cfg) -> Stage1Spec:
@@ -204,7 +213,7 @@ def stage2_param_shapes(s: Stage2Spec) -> 'OrderedDict[str, Tuple[int, ...]]':
     out['ln_f.weight'] = (D,)
     out['ln_f.bias'] = (D,)
     out['tok_emb_top_depth.weight'] = (s.vocab_top, D)
-    out['tok_emb_bot_depth.weight'] = (s.vocab_bot, D)       # present in checkpoints, unused by 'parallel'
+    out['tok_emb_bot_depth.weight'] = (s.vocab_bot, D)       # present in checkpoints, unused by 'parallel' and 'bidirectional'
     out['pos_emb_depth.weight'] = (max(1 + 1, 5), D)          # hierarchical_ar.py:167 (len_seq_depth = 2)
     for j in range(s.n_layers_depth):
         _block_shapes(f'depths.{j}', D, out)

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define HQT_ABI_VERSION 7
+#define HQT_ABI_VERSION 8
 
 typedef enum {
     HQT_OK = 0,
@@ -90,7 +90,11 @@ typedef struct {
      * code's embedding), 2 'parallel-reduce' (tok_emb_depth_levels.{0,1} are [V, 4 D]: child position c of a code takes slice c).
      * 3 'top2mid2bot': a causal head of 21 sequential one-token sub-steps (hqtransformer.py:700-800; pos_emb_depths.0 is [21, D],
      * the sub-step inputs come from tok_emb_levels).  The other values of the reference ('tree', 'old-parallel',
-     * 'parallel-add-reduce') cannot sample three levels there either. */
+     * 'parallel-add-reduce') cannot sample three levels there either.
+     * Two levels: 0 = iHQGPT 'parallel' (the released checkpoints), or 4 'bidirectional' (stage2.type hq-transformer/bidirectional4,
+     * hierarchical_ar.py:791-878, since ABI version 8): one unmasked pass of the depth blocks over [ln_f(h) + sos_depth,
+     * pos_emb_depth[0..3]] per position, all five codes drawn from it.  As in the reference, all five draws use
+     * temperature_top, top_k_bot and top_p_bot.  Not with text conditioning. */
     int32_t depth_decoding;
     /* Which derived layouts of the AR loop's nn.Linear weights hqt_finalize_weights builds (bit mask of HQT_LAYOUT_*; 0 = all of them,
      * what ABI <= 6 always did: 9.6 GiB measured for the 2.1 GB ImageNet-12L model and its batch-64 workspace).  The fp32 tensors as received are always kept: they are
@@ -107,6 +111,7 @@ typedef struct {
 #define HQT_DEPTH_PARALLEL 1
 #define HQT_DEPTH_PARALLEL_REDUCE 2
 #define HQT_DEPTH_TOP2MID2BOT 3
+#define HQT_DEPTH_BIDIRECTIONAL 4
 
 /* Sampling options = the keyword arguments of sampling_ihqgpt (hqvae/utils/sampling.py:164-177).
  * top_k <= 0 means None (no cut-off), top_p <= 0 means None. */
