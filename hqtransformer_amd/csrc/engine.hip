@@ -121,6 +121,7 @@ struct hqt_handle {
     std::vector<BlockW> body, depth;
     Lin head_top, head_bot;
     int Tmax = 0;
+    int depth_rows = 0;                       // keys of the depth cache: 5 (two code levels) or 21 (three)
     float *x = nullptr, *xd = nullptr, *logits = nullptr;
     void *hbuf = nullptr, *qbuf = nullptr, *abuf = nullptr, *mbuf = nullptr;    // fp32-sized, reused as bf16 in FAST
     void *kcache = nullptr, *vcache = nullptr, *dk = nullptr, *dv = nullptr;
@@ -428,7 +429,7 @@ static int alloc_workspace(hqt_handle* hp) {
         const int Tp = c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : 1;    // rows of the widest body pass
         h->Tmax = (c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : 0) + c.max_steps;
         const int Tdepth = c.code_levels == 3 ? 16 : (c.depth_decoding == HQT_DEPTH_BIDIRECTIONAL ? 5 : 4);      // rows per sample of the widest depth sub-step
-        const int Kdepth = c.code_levels == 3 ? 21 : 5;      // keys of the depth cache
+        h->depth_rows = c.code_levels == 3 ? 21 : 5;
         const size_t rows = (B * (size_t)std::max(Tp, Tdepth) + 31) / 32 * 32;
         CHK(dev_alloc(h.get(), (void**)&h->x, rows * D * 4, true));
         CHK(dev_alloc(h.get(), (void**)&h->xd, B * Tdepth * D * 4, true));
@@ -440,7 +441,7 @@ static int alloc_workspace(hqt_handle* hp) {
         const size_t kv = (size_t)c.n_layers * B * h->Tmax * D * 4;
         CHK(dev_alloc(h.get(), &h->kcache, kv, true));
         CHK(dev_alloc(h.get(), &h->vcache, kv, true));
-        const size_t dkv = (size_t)c.n_layers_depth * B * Kdepth * D * 4;
+        const size_t dkv = (size_t)c.n_layers_depth * B * h->depth_rows * D * 4;
         CHK(dev_alloc(h.get(), &h->dk, dkv, true));
         CHK(dev_alloc(h.get(), &h->dv, dkv, true));
         h->splitk_elems = (size_t)16 * rows * (size_t)std::max<size_t>(4 * D, (size_t)c.vocab_top);
@@ -1013,22 +1014,23 @@ static int run_linear(hqt_handle* h, const Mode& md, GemmArgs g, const Lin& l, i
 }
 
 // ------------------------------------------------------------------------------------------ stage 2
+struct SamplerSet { float temperature = 1.f; int top_k = 0; float top_p = 0.f; };   // one code level's sampler settings
 struct SampleCtx {
     int B;
     const int64_t* cond;
-    hqt_sample_opts o;
+    int levels;                                  // code levels: 2 (hqt_sample) or 3 (hqt_sample_l3)
+    int precision, n_steps, use_graph;
+    uint64_t seed;
+    int64_t sample_offset;
+    const uint64_t* row_seeds;
+    const int64_t* row_offsets;
+    SamplerSet lv[3];
     const float* noise;
-    const int64_t *feed_top, *feed_bot;
+    const int64_t* feed[3] = {nullptr, nullptr, nullptr};   // codes each level's embeddings read: the drawn ones (out) or the forced ones
+    int64_t* out[3] = {nullptr, nullptr, nullptr};
     float* logits_out;
-    int64_t *out_top, *out_bot;
     hipStream_t st;
     Mode md;
-    // three-level calls (hqt_sample_l3): per-level sampler settings and the third level's code buffers
-    int levels = 2;
-    int top_k[3] = {0, 0, 0};
-    float top_p[3] = {0.f, 0.f, 0.f}, temperature[3] = {1.f, 1.f, 1.f};
-    const int64_t* feed_l2 = nullptr;
-    int64_t* out_l2 = nullptr;
 };
 
 // State-dict key of a stage-2 tensor: the code below names tensors as iHQGPT does; the three-level HQTransformer keeps
@@ -1117,7 +1119,7 @@ static int persist_build(hqt_handle* h) {
         PersistPhase ph{};
         ph.type = PP_LNF; ph.N = c.embed_dim; ph.K = c.embed_dim; ph.map = PP_MAP_QUAD; ph.dln = 1;
         pr.phases.push_back(ph); src.push_back({nullptr, nullptr});
-        for (auto& b : h->depth) persist_block_shapes(h, b, true, 5, &k4, pr.phases, src);
+        for (auto& b : h->depth) persist_block_shapes(h, b, true, h->depth_rows, &k4, pr.phases, src);
         ph = PersistPhase{};
         ph.type = PP_ROWS; ph.N = c.vocab_top; ph.K = c.embed_dim; ph.dln = 1;
         pr.phases.push_back(ph); src.push_back({h->head_top.w32, h->w[key2(h, "ln_top.weight")].d});
@@ -1176,7 +1178,7 @@ static int persist_bind(hqt_handle* h) {
         size_t p = bind_body(h->pfull);
         PersistPhase& lf = h->pfull.phases[p++];
         lf.A = h->xpk; lf.bias = h->lnf_shift; lf.colsum = W(h, "ln_f.weight"); lf.out = h->xdpk;
-        const size_t dkv_layer = (size_t)c.max_batch * 5 * D;
+        const size_t dkv_layer = (size_t)c.max_batch * h->depth_rows * D;
         for (int l = 0; l < c.n_layers_depth; ++l) {
             const BlockW& bw = h->depth[l];
             PersistPhase* ph = &h->pfull.phases[p];
@@ -1314,257 +1316,187 @@ static int run_block_dln(hqt_handle* h, const SampleCtx& c, const BlockW& bw, fl
     return HQT_OK;
 }
 
-// The 'bidirectional' depth head (hierarchical_ar.py:791-878; its Blocks have causal_attn = False: layers.py:290-330, no mask at all):
-// ONE pass of the depth blocks over five rows per sample, [ln_f(h) + sos_depth, pos_emb_depth[0..3]], with full 5 x 5 attention and no
-// cache carried to the next position.  Top logits from row 0 (ln_top, head_top), bottom logits from rows 1..4 (ln_bot, head_bot).  All five
-// draws use temperature_top, top_k_bot and top_p_bot, as the reference does (:866-873); the noise / logits_out slots are the parallel head's.
-static int run_depth_bidir(hqt_handle* h, const SampleCtx& c, int Tq_body) {
+// The body blocks of one position over Tq_body rows: as ONE persistent launch up to the top logits (pfull: two code levels, 'parallel' -- persist_build
+// makes that program for no other head; dln0: sub-step 0 of the depth head takes the deferred-LayerNorm path), as one persistent launch of the body
+// alone (pbody), or as the launch chain.  *pfull: the whole-position launch ran.
+static int run_body(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_base, bool body_tbase_from_state, bool dln0, bool* pfull) {
     const hqt_config& cf = h->cfg;
-    const int D = cf.embed_dim, B = c.B, V = cf.vocab_top, M = 5 * B;
-    const int adt = c.md.act_dt();
-    const size_t dkv_layer = (size_t)cf.max_batch * 5 * D * c.md.act_sz();
-    const bool dln = dln_ok(h, c, h->depth[0], M);
-    {
-        Timed t(h, "bidir_depth_input", c.st);
-        LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, B, D, Tq_body, Tq_body - 1, 1e-5f, DT_F32, 0,
-                  h->pend.slabs, h->pend.S, h->pend.rows, h->pend.bias, dln ? h->xdpk : nullptr, dln ? packed_mb(M) : 0, h->partsd};
-        ln.fill = W(h, "pos_emb_depth.weight");
-        h->pend.slabs = nullptr; h->pend.S = 0;
-        HIPCHK(launch_bidir_depth_input(ln, c.st));
-        h->npartsd = 1;
-    }
-    for (int l = 0; l < cf.n_layers_depth; ++l) {     // Tq = 5 > 1: never the single-key shortcut of run_block_dln
-        void* kc = (char*)h->dk + l * dkv_layer;
-        void* vc = (char*)h->dv + l * dkv_layer;
-        if (dln) CHK(run_block_dln(h, c, h->depth[l], h->xd, h->xdpk, h->partsd, &h->npartsd, 5, kc, vc, 5, 0, nullptr, 0));
-        else CHK(run_block(h, c, h->depth[l], h->xd, 5, kc, vc, 5, 0, nullptr, 0));
-    }
-    // ln_top / ln_bot of the interleaved rows into two compact operands: [B, D] (hbuf) and [4 B, D] (abuf)
-    const int pk1 = (c.md.fast && B <= PACKED_MAX_ROWS && h->head_top.wpk) ? packed_mb(B) : 0;
-    const int pk4 = (c.md.fast && 4 * B <= PACKED_MAX_ROWS && h->head_bot.wpk) ? packed_mb(4 * B) : 0;
-    {
-        Timed t(h, "bidir_head_ln", c.st);
-        LNArgs ln{h->xd, W(h, "ln_top.weight"), W(h, "ln_top.bias"), nullptr, h->hbuf, M, D, 1, 0, 1e-5f, adt, pk1,
-                  h->pend.slabs, h->pend.S, h->pend.rows, h->pend.bias, nullptr, 0, nullptr};
-        ln.gamma2 = W(h, "ln_bot.weight"); ln.beta2 = W(h, "ln_bot.bias"); ln.y2 = h->abuf; ln.out2_packed_mb = pk4;
-        h->pend.slabs = nullptr; h->pend.S = 0;
-        HIPCHK(launch_bidir_head_ln(ln, c.st));
-    }
-    GemmArgs g{};
-    g.A = h->hbuf; g.a_packed_mb = pk1; g.M = B; g.batch = 1; g.C = h->logits; g.ldc = V; g.store = STORE_ROWS;
-    CHK(run_linear(h, c.md, g, h->head_top, adt, DT_F32, c.st, "gemm_head"));
-    {
-        Timed t(h, "bidir_sampler_top", c.st);
-        SamplerArgs s{h->logits, B, V, 1, B, c.o.temperature_top, c.o.top_k_bot, c.o.top_p_bot, c.noise, 0,
-                      h->state, h->rows, c.o.n_steps, c.out_top, c.logits_out};
-        s.fast_math = c.md.fast ? 1 : 0;
-        HIPCHK(launch_sampler(s, c.st));
-    }
-    g = GemmArgs{};
-    g.A = h->abuf; g.a_packed_mb = pk4; g.M = 4 * B; g.batch = 1; g.C = h->logits; g.ldc = V; g.store = STORE_ROWS;
-    CHK(run_linear(h, c.md, g, h->head_bot, adt, DT_F32, c.st, "gemm_head"));
-    {
-        Timed t(h, "bidir_sampler_bot", c.st);
-        SamplerArgs s{h->logits, 4 * B, V, 4, B, c.o.temperature_top, c.o.top_k_bot, c.o.top_p_bot, c.noise, 1,
-                      h->state, h->rows, c.o.n_steps, c.out_bot, c.logits_out};
-        s.fast_math = c.md.fast ? 1 : 0;
-        HIPCHK(launch_sampler(s, c.st));
-    }
-    return HQT_OK;
-}
-
-// Everything of one top position after the body input x is ready (hierarchical_ar.py:482-563,667-789)
-static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_base, bool body_tbase_from_state) {
-    const hqt_config& cf = h->cfg;
-    const int D = cf.embed_dim, B = c.B, V = cf.vocab_top;
-    const int adt = c.md.act_dt();
-    const size_t esz = c.md.act_sz();
-    const size_t kv_layer = (size_t)cf.max_batch * h->Tmax * D * esz;
+    const size_t kv_layer = (size_t)cf.max_batch * h->Tmax * cf.embed_dim * c.md.act_sz();
     const int* tb_dev = body_tbase_from_state ? &h->state->t_base : nullptr;
     // deferred LayerNorm needs the packed copy + row statistics of x from the caller's embedding kernel: embed_step emits
     // them (decode steps, Tq = 1); the text prefill's embed_text does not, so the prefill pass takes the classic path
-    const bool dln_body = Tq_body == 1 && dln_ok(h, c, h->body[0], B * Tq_body);
+    const bool dln_body = Tq_body == 1 && dln_ok(h, c, h->body[0], c.B * Tq_body);
     // the twelve body blocks as ONE persistent launch (persist.h): decode steps of up to 64 samples
-    const bool dln1 = dln_ok(h, c, h->depth[0], B) && h->head_top.wpk_ln;
-    const bool dln4 = dln_ok(h, c, h->depth[0], 4 * B) && h->head_bot.wpk_ln;
     const bool body_persistable = dln_body && body_tbase_from_state && body_t_base == 0;
-    // ... up to the top logits: body, ln_f + sos_depth, depth sub-step 0, head_top as ONE persistent launch
-    const bool bidir = cf.depth_decoding == HQT_DEPTH_BIDIRECTIONAL;
-    const bool pfull = !bidir && body_persistable && dln1 && h->single_key && persist_on(h, c, h->pfull);
-    const bool pbody = !pfull && body_persistable && persist_on(h, c, h->pbody);
-    if (pfull) CHK(run_persist(h, c, h->pfull, h->x, 0, tb_dev, "persist_position"));
+    *pfull = body_persistable && dln0 && h->single_key && persist_on(h, c, h->pfull);
+    const bool pbody = !*pfull && body_persistable && persist_on(h, c, h->pbody);
+    if (*pfull) CHK(run_persist(h, c, h->pfull, h->x, 0, tb_dev, "persist_position"));
     if (pbody) CHK(run_persist(h, c, h->pbody, h->x, 1, tb_dev, "persist_body"));
-    for (int l = 0; l < (pbody || pfull ? 0 : cf.n_layers); ++l) {
+    for (int l = 0; l < (pbody || *pfull ? 0 : cf.n_layers); ++l) {
         void* kc = (char*)h->kcache + l * kv_layer;
         void* vc = (char*)h->vcache + l * kv_layer;
         if (dln_body) CHK(run_block_dln(h, c, h->body[l], h->x, h->xpk, h->parts, &h->nparts, Tq_body, kc, vc, h->Tmax, body_t_base, tb_dev, 1));
         else CHK(run_block(h, c, h->body[l], h->x, Tq_body, kc, vc, h->Tmax, body_t_base, tb_dev, 1));
-    }
-    if (bidir) return run_depth_bidir(h, c, Tq_body);
-    // ln_f on the last token of each sample, + sos_depth (hierarchical_ar.py:561,684-686) -> depth-head input
-    if (!pfull) {
-        Timed t(h, "layernorm", c.st);
-        LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, B, D, Tq_body, Tq_body - 1, 1e-5f, DT_F32, 0,
-                  h->pend.slabs, h->pend.S, h->pend.rows, h->pend.bias, dln1 ? h->xdpk : nullptr, dln1 ? packed_mb(B) : 0, h->partsd};
-        h->pend.slabs = nullptr; h->pend.S = 0;
-        HIPCHK(launch_layernorm(ln, c.st));
-        h->npartsd = 1;
-    }
-    const size_t dkv_layer = (size_t)cf.max_batch * 5 * D * esz;
-    const int pk1 = (c.md.fast && B <= PACKED_MAX_ROWS && h->head_top.wpk) ? packed_mb(B) : 0;
-    const int pk4 = (c.md.fast && 4 * B <= PACKED_MAX_ROWS && h->head_bot.wpk) ? packed_mb(4 * B) : 0;
-    // ---- depth sub-step 0: top code
-    for (int l = 0; l < (pfull ? 0 : cf.n_layers_depth); ++l) {
-        void* kc = (char*)h->dk + l * dkv_layer;
-        void* vc = (char*)h->dv + l * dkv_layer;
-        if (dln1) CHK(run_block_dln(h, c, h->depth[l], h->xd, h->xdpk, h->partsd, &h->npartsd, 1, kc, vc, 5, 0, nullptr, 0));
-        else CHK(run_block(h, c, h->depth[l], h->xd, 1, kc, vc, 5, 0, nullptr, 0));
-    }
-    GemmArgs g{};
-    if (dln1) {                                  // ln_top folded into head_top
-        g.A = h->xdpk; g.a_packed_mb = pk1; g.ln_parts = h->partsd; g.ln_nparts = h->npartsd; g.ln_colsum = h->head_top.colsum; g.ln_eps = 1e-5f;
-    } else {
-        CHK(run_ln(h, c.st, h->xd, W(h, "ln_top.weight"), W(h, "ln_top.bias"), nullptr, h->hbuf, B, D, 1, 0, adt, pk1));
-        g.A = h->hbuf; g.a_packed_mb = pk1;
-    }
-    g.M = B; g.batch = 1; g.C = h->logits; g.ldc = V; g.store = STORE_ROWS;
-    if (!pfull) CHK(run_linear(h, c.md, g, h->head_top, adt, DT_F32, c.st, "gemm_head"));
-    {
-        Timed t(h, "sampler", c.st);
-        SamplerArgs s{h->logits, B, V, 1, B, c.o.temperature_top, c.o.top_k_top, c.o.top_p_top, c.noise, 0,
-                      h->state, h->rows, c.o.n_steps, c.out_top, c.logits_out};
-        s.fast_math = c.md.fast ? 1 : 0;
-        // the draw and the embedding lookup of the drawn code in one kernel: the sampler's workgroup of sample b also writes the
-        // four input rows of depth sub-step 1 (HQT_NO_FUSED_EMBED=1: separate depth_embed_kernel, for A/B runs)
-        static const bool fuse = !getenv("HQT_NO_FUSED_EMBED");
-        if (fuse) {
-            s.emb_tok = W(h, "tok_emb_top_depth.weight"); s.emb_pos = W(h, "pos_emb_depth.weight");
-            s.emb_feed = c.feed_top != c.out_top ? c.feed_top : nullptr;
-            s.emb_x = h->xd; s.emb_D = D;
-            s.emb_xpk = dln4 ? h->xdpk : nullptr; s.emb_pk_mb = dln4 ? packed_mb(4 * B) : 0; s.emb_parts = h->partsd;
-        }
-        HIPCHK(launch_sampler(s, c.st));
-        if (!fuse) {
-            Timed t2(h, "embed", c.st);
-            HIPCHK(launch_depth_embed(c.feed_top, c.o.n_steps, h->state, W(h, "tok_emb_top_depth.weight"), W(h, "pos_emb_depth.weight"),
-                                      h->xd, B, D, dln4 ? h->xdpk : nullptr, dln4 ? packed_mb(4 * B) : 0, h->partsd, c.st, V));
-        }
-        h->npartsd = 1;
-    }
-    // ---- depth sub-step 1: four bottom codes in one pass
-    for (int l = 0; l < cf.n_layers_depth; ++l) {
-        void* kc = (char*)h->dk + l * dkv_layer;
-        void* vc = (char*)h->dv + l * dkv_layer;
-        if (dln4) CHK(run_block_dln(h, c, h->depth[l], h->xd, h->xdpk, h->partsd, &h->npartsd, 4, kc, vc, 5, 1, nullptr, 0));
-        else CHK(run_block(h, c, h->depth[l], h->xd, 4, kc, vc, 5, 1, nullptr, 0));
-    }
-    g = GemmArgs{};
-    if (dln4) {
-        g.A = h->xdpk; g.a_packed_mb = pk4; g.ln_parts = h->partsd; g.ln_nparts = h->npartsd; g.ln_colsum = h->head_bot.colsum; g.ln_eps = 1e-5f;
-    } else {
-        CHK(run_ln(h, c.st, h->xd, W(h, "ln_bot.weight"), W(h, "ln_bot.bias"), nullptr, h->hbuf, 4 * B, D, 1, 0, adt, pk4));
-        g.A = h->hbuf; g.a_packed_mb = pk4;
-    }
-    g.M = 4 * B; g.batch = 1; g.C = h->logits; g.ldc = V; g.store = STORE_ROWS;
-    CHK(run_linear(h, c.md, g, h->head_bot, adt, DT_F32, c.st, "gemm_head"));
-    {
-        Timed t(h, "sampler", c.st);
-        SamplerArgs s{h->logits, 4 * B, V, 4, B, c.o.temperature_bot, c.o.top_k_bot, c.o.top_p_bot, c.noise, 1,
-                      h->state, h->rows, c.o.n_steps, c.out_bot, c.logits_out};
-        s.fast_math = c.md.fast ? 1 : 0;
-        HIPCHK(launch_sampler(s, c.st));
     }
     return HQT_OK;
 }
 
-// One top position of the three-level HQTransformer after the body input x is ready (hqtransformer.py:409-635): body
-// blocks, ln_f, then three depth sub-steps over 1, 4 and 16 tokens.  Every sub-step's tokens see all earlier and current
-// depth tokens (the 'parallel' mask of layers.py:154-178 restricted to the rows being evaluated is all-ones), so the
-// attention kernel runs non-causally over t_base + Tq keys of a 21-row cache.
-static int run_position_l3(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_base, bool body_tbase_from_state) {
+// The depth blocks over the Tq tokens per sample in xd, at offset tbase of the depth cache
+static int run_depth(hqt_handle* h, const SampleCtx& c, bool dln, int Tq, int tbase) {
+    const hqt_config& cf = h->cfg;
+    const size_t dkv_layer = (size_t)cf.max_batch * h->depth_rows * cf.embed_dim * c.md.act_sz();
+    for (int l = 0; l < cf.n_layers_depth; ++l) {
+        void* kc = (char*)h->dk + l * dkv_layer;
+        void* vc = (char*)h->dv + l * dkv_layer;
+        if (dln) CHK(run_block_dln(h, c, h->depth[l], h->xd, h->xdpk, h->partsd, &h->npartsd, Tq, kc, vc, h->depth_rows, tbase, nullptr, 0));
+        else CHK(run_block(h, c, h->depth[l], h->xd, Tq, kc, vc, h->depth_rows, tbase, nullptr, 0));
+    }
+    return HQT_OK;
+}
+
+static int head_pk(const SampleCtx& c, const Lin& head, int M) {      // FAST: the head GEMM's operand travels packed when the streaming GEMM serves it
+    return (c.md.fast && M <= PACKED_MAX_ROWS && head.wpk) ? packed_mb(M) : 0;
+}
+
+// Logits of the M depth rows of code level lv into h->logits: ln_levels[lv] folded into the head GEMM (dln: the deferred-LayerNorm operand), or
+// the LayerNorm of xd into hbuf and then the GEMM.  `normed` non-null: the operand is already normalised there (the bidirectional head).
+static int run_head(hqt_handle* h, const SampleCtx& c, const Lin& head, int lv, int M, bool dln, void* normed) {
+    static const char* const ln_names[3][2] = {{"ln_top.weight", "ln_top.bias"}, {"ln_bot.weight", "ln_bot.bias"}, {"ln_levels.2.weight", "ln_levels.2.bias"}};
+    const int adt = c.md.act_dt(), pk = head_pk(c, head, M);
+    GemmArgs g{};
+    if (dln) {
+        g.A = h->xdpk; g.ln_parts = h->partsd; g.ln_nparts = h->npartsd; g.ln_colsum = head.colsum; g.ln_eps = 1e-5f;
+    } else {
+        if (!normed) {
+            normed = h->hbuf;
+            CHK(run_ln(h, c.st, h->xd, W(h, ln_names[lv][0]), W(h, ln_names[lv][1]), nullptr, normed, M, h->cfg.embed_dim, 1, 0, adt, pk));
+        }
+        g.A = normed;
+    }
+    g.a_packed_mb = pk; g.M = M; g.batch = 1; g.C = h->logits; g.ldc = h->cfg.vocab_top; g.store = STORE_ROWS;
+    return run_linear(h, c.md, g, head, adt, DT_F32, c.st, "gemm_head");
+}
+
+// One depth sub-step: code level lv, Tq tokens per sample at offset tbase of the depth sequence (which is also the first draw index of the
+// sampler); out_stride > 0: each token writes slot out_slot of an out_stride-wide code group (the 21-step causal head)
+struct SubStep { int lv, Tq, tbase, out_stride, out_slot; };
+static SubStep sub_step(const hqt_config& cf, int sub) {
+    static const int first[3] = {0, 1, 5}, width[3] = {1, 4, 16};
+    if (cf.depth_decoding != HQT_DEPTH_TOP2MID2BOT) return {sub, width[sub], first[sub], 0, 0};
+    const int lv = sub == 0 ? 0 : (sub < 5 ? 1 : 2);
+    return {lv, 1, sub, lv ? width[lv] : 0, sub - first[lv]};
+}
+
+// The input rows of depth sub-step `sub` in xd (dln: with their packed copy and row statistics)
+static int run_depth_input(hqt_handle* h, const SampleCtx& c, int sub, bool dln, int Tq_body, bool fuse) {
     const hqt_config& cf = h->cfg;
     const int D = cf.embed_dim, B = c.B, V = cf.vocab_top;
-    const int adt = c.md.act_dt();
-    const size_t esz = c.md.act_sz();
-    const size_t kv_layer = (size_t)cf.max_batch * h->Tmax * D * esz;
-    const int* tb_dev = body_tbase_from_state ? &h->state->t_base : nullptr;
-    const bool dln_body = Tq_body == 1 && dln_ok(h, c, h->body[0], B * Tq_body);
-    const bool pbody = dln_body && body_tbase_from_state && body_t_base == 0 && persist_on(h, c, h->pbody);      // the body is the two-level model's: one persistent launch
-    if (pbody) CHK(run_persist(h, c, h->pbody, h->x, 1, tb_dev, "persist_body"));
-    for (int l = 0; l < (pbody ? 0 : cf.n_layers); ++l) {
-        void* kc = (char*)h->kcache + l * kv_layer;
-        void* vc = (char*)h->vcache + l * kv_layer;
-        if (dln_body) CHK(run_block_dln(h, c, h->body[l], h->x, h->xpk, h->parts, &h->nparts, Tq_body, kc, vc, h->Tmax, body_t_base, tb_dev, 1));
-        else CHK(run_block(h, c, h->body[l], h->x, Tq_body, kc, vc, h->Tmax, body_t_base, tb_dev, 1));
+    const SubStep s = sub_step(cf, sub);
+    const int M = B * s.Tq, pk = dln ? packed_mb(M) : 0, dmul = cf.depth_decoding == HQT_DEPTH_PARALLEL_REDUCE ? 4 : 1;
+    bf16_t* xpk = dln ? h->xdpk : nullptr;
+    if (sub == 0) {           // ln_f on the last token of each sample, + sos_depth (hierarchical_ar.py:561,684-686) -> depth input of level 0
+        Timed t(h, "layernorm", c.st);
+        LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, B, D, Tq_body, Tq_body - 1, 1e-5f, DT_F32, 0,
+                  h->pend.slabs, h->pend.S, h->pend.rows, h->pend.bias, xpk, pk, h->partsd};
+        h->pend.slabs = nullptr; h->pend.S = 0;
+        HIPCHK(launch_layernorm(ln, c.st));
+    } else if (cf.depth_decoding == HQT_DEPTH_TOP2MID2BOT) {   // the previous sub-step's code, embedded by the spatial tables, + its position in the 21-token sequence
+        Timed t(h, "embed", c.st);
+        const SubStep p = sub_step(cf, sub - 1);
+        const int tbl = sub == 1 ? 0 : (sub < 5 ? 1 : 2);
+        const float* tok = tbl == 0 ? W(h, "tok_emb_top.weight") : (tbl == 1 ? W(h, "tok_emb_bot.weight") : W(h, "tok_emb_levels.2.weight"));
+        HIPCHK(launch_depth_embed_causal(c.feed[p.lv], p.lv ? p.out_stride : 1, p.out_slot, c.n_steps, h->state, tok,
+                                         W(h, "pos_emb_depth.weight") + (size_t)p.tbase * D, h->xd, B, D, xpk, pk, h->partsd, c.st, V));
+    } else if (s.lv == 1) {   // emb(top code) + positions 0..3 (fuse: the top sampler wrote them)
+        if (fuse) return HQT_OK;
+        Timed t(h, "embed", c.st);
+        HIPCHK(launch_depth_embed(c.feed[0], c.n_steps, h->state, W(h, "tok_emb_top_depth.weight"), W(h, "pos_emb_depth.weight"),
+                                  h->xd, B, D, xpk, pk, h->partsd, c.st, V, dmul * D));
+    } else {                  // parent's level-1 embedding + position i (+ emb(top code): 'add'), 16 tokens
+        Timed t(h, "embed", c.st);
+        HIPCHK(launch_depth_embed_l2(c.feed[0], c.feed[1], c.n_steps, h->state,
+                                     cf.depth_decoding == HQT_DEPTH_PARALLEL_ADD ? W(h, "tok_emb_top_depth.weight") : nullptr,
+                                     W(h, "tok_emb_depth_levels.1.weight"), W(h, "pos_emb_depths.1.weight"),
+                                     h->xd, B, D, xpk, pk, h->partsd, c.st, V, dmul * D));
     }
+    return HQT_OK;
+}
+
+// Everything of one top position after the body input x is ready (hierarchical_ar.py:482-563,667-789; three code levels:
+// hqtransformer.py:409-635): the body blocks, ln_f, then the depth sub-steps, each an input step, the depth blocks, a head and its draws.
+//  - 'parallel' (two levels; three: 'parallel-add', 'parallel-reduce'): one sub-step per level over 1, 4 (and 16) tokens.  Every sub-step's
+//    tokens see all earlier and current depth tokens (the 'parallel' mask of layers.py:154-178 restricted to the rows being evaluated is
+//    all-ones), so the attention runs non-causally over tbase + Tq keys of the depth cache.
+//  - 'top2mid2bot' (hqtransformer.py:700-800): 21 causal sub-steps of ONE token -- sub-step cnt >= 1 is fed the code drawn by cnt - 1
+//    through tok_emb_levels[cnt == 1 ? 0 : (cnt < 5 ? 1 : 2)] (:718-723: the table follows the sub-step being computed, so the last middle
+//    code is embedded with the level-2 table, as there) + pos_emb_depths.0[cnt - 1]; head of level (cnt == 0 ? 0 : cnt < 5 ? 1 : 2)
+//  - 'bidirectional' (hierarchical_ar.py:791-878; its Blocks have causal_attn = False: layers.py:290-330, no mask at all): ONE pass of the
+//    depth blocks over five rows per sample, [ln_f(h) + sos_depth, pos_emb_depth[0..3]], with full 5 x 5 attention and no cache carried to
+//    the next position; then the two 'parallel' sub-steps' heads and draws, top logits from row 0 (ln_top, head_top), bottom from rows 1..4
+//    (ln_bot, head_bot).  All five draws use temperature_top, top_k_bot and top_p_bot, as the reference does (:866-873).
+static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_base, bool body_tbase_from_state) {
+    const hqt_config& cf = h->cfg;
+    const int D = cf.embed_dim, B = c.B, V = cf.vocab_top;
     const Lin* heads[3] = {&h->head_top, &h->head_bot, &h->head_l2};
-    const char* ln_names[3][2] = {{"ln_top.weight", "ln_top.bias"}, {"ln_bot.weight", "ln_bot.bias"}, {"ln_levels.2.weight", "ln_levels.2.bias"}};
-    const int dmul = cf.depth_decoding == HQT_DEPTH_PARALLEL_REDUCE ? 4 : 1;
-    // 'top2mid2bot' (hqtransformer.py:700-800): 21 causal sub-steps of ONE token -- sub-step cnt >= 1 is fed the code drawn by cnt - 1
-    // through tok_emb_levels[cnt == 1 ? 0 : (cnt < 5 ? 1 : 2)] (:718-723: the table follows the sub-step being computed, so the last middle
-    // code is embedded with the level-2 table, as there) + pos_emb_depths.0[cnt - 1]; head of level (cnt == 0 ? 0 : cnt < 5 ? 1 : 2)
-    const bool causal_head = cf.depth_decoding == HQT_DEPTH_TOP2MID2BOT;
-    const int nsub = causal_head ? 21 : 3;
-    int64_t* outs[3] = {c.out_top, c.out_bot, c.out_l2};
-    const int64_t* feeds[3] = {c.feed_top, c.feed_bot, c.feed_l2};
-    const size_t dkv_layer = (size_t)cf.max_batch * 21 * D * esz;
-    for (int sub = 0; sub < nsub; ++sub) {
-        const int lv = causal_head ? (sub == 0 ? 0 : (sub < 5 ? 1 : 2)) : sub;
-        const int Tq = causal_head ? 1 : (lv == 0 ? 1 : (lv == 1 ? 4 : 16));
-        const int tbase = causal_head ? sub : (lv == 0 ? 0 : (lv == 1 ? 1 : 5));
-        const int draw0 = tbase;
-        const int M = B * Tq;
-        const bool dln = dln_ok(h, c, h->depth[0], M) && heads[lv]->wpk_ln;
-        const int pk = (c.md.fast && M <= PACKED_MAX_ROWS && heads[lv]->wpk) ? packed_mb(M) : 0;
-        if (sub == 0) {           // ln_f on the last token of each sample, + sos_depth -> depth input of level 0
-            Timed t(h, "layernorm", c.st);
-            LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, B, D, Tq_body, Tq_body - 1, 1e-5f, DT_F32, 0,
-                      h->pend.slabs, h->pend.S, h->pend.rows, h->pend.bias, dln ? h->xdpk : nullptr, dln ? packed_mb(B) : 0, h->partsd};
-            h->pend.slabs = nullptr; h->pend.S = 0;
-            HIPCHK(launch_layernorm(ln, c.st));
-        } else if (causal_head) { // the previous sub-step's code, embedded by the spatial tables, + its position in the 21-token sequence
-            Timed t(h, "embed", c.st);
-            const int prev = sub - 1, plv = prev == 0 ? 0 : (prev < 5 ? 1 : 2);
-            const int tbl = sub == 1 ? 0 : (sub < 5 ? 1 : 2);
-            const float* tok = tbl == 0 ? W(h, "tok_emb_top.weight") : (tbl == 1 ? W(h, "tok_emb_bot.weight") : h->w["stage2.tok_emb_levels.2.weight"].d);
-            HIPCHK(launch_depth_embed_causal(feeds[plv], plv == 0 ? 1 : (plv == 1 ? 4 : 16), plv == 0 ? 0 : (plv == 1 ? prev - 1 : prev - 5), c.o.n_steps,
-                                             h->state, tok, W(h, "pos_emb_depth.weight") + (size_t)prev * D, h->xd, B, D,
-                                             dln ? h->xdpk : nullptr, dln ? packed_mb(M) : 0, h->partsd, c.st, V));
-        } else if (lv == 1) {     // emb(top code) + positions 0..3
-            Timed t(h, "embed", c.st);
-            HIPCHK(launch_depth_embed(c.feed_top, c.o.n_steps, h->state, W(h, "tok_emb_top_depth.weight"), W(h, "pos_emb_depth.weight"),
-                                      h->xd, B, D, dln ? h->xdpk : nullptr, dln ? packed_mb(M) : 0, h->partsd, c.st, V, dmul * D));
-        } else {                  // parent's level-1 embedding + position i (+ emb(top code): 'add'), 16 tokens
-            Timed t(h, "embed", c.st);
-            HIPCHK(launch_depth_embed_l2(c.feed_top, c.feed_bot, c.o.n_steps, h->state,
-                                         cf.depth_decoding == HQT_DEPTH_PARALLEL_ADD ? W(h, "tok_emb_top_depth.weight") : nullptr,
-                                         h->w["stage2.tok_emb_depth_levels.1.weight"].d, h->w["stage2.pos_emb_depths.1.weight"].d,
-                                         h->xd, B, D, dln ? h->xdpk : nullptr, dln ? packed_mb(M) : 0, h->partsd, c.st, V, dmul * D));
-        }
-        h->npartsd = 1;
-        for (int l = 0; l < cf.n_layers_depth; ++l) {
-            void* kc = (char*)h->dk + l * dkv_layer;
-            void* vc = (char*)h->dv + l * dkv_layer;
-            if (dln) CHK(run_block_dln(h, c, h->depth[l], h->xd, h->xdpk, h->partsd, &h->npartsd, Tq, kc, vc, 21, tbase, nullptr, 0));
-            else CHK(run_block(h, c, h->depth[l], h->xd, Tq, kc, vc, 21, tbase, nullptr, 0));
-        }
-        GemmArgs g{};
-        if (dln) {                // ln_levels[lv] folded into head_levels[lv]
-            g.A = h->xdpk; g.a_packed_mb = pk; g.ln_parts = h->partsd; g.ln_nparts = h->npartsd; g.ln_colsum = heads[lv]->colsum; g.ln_eps = 1e-5f;
-        } else {
-            const float* lg = lv < 2 ? W(h, ln_names[lv][0]) : h->w["stage2.ln_levels.2.weight"].d;
-            const float* lb = lv < 2 ? W(h, ln_names[lv][1]) : h->w["stage2.ln_levels.2.bias"].d;
-            CHK(run_ln(h, c.st, h->xd, lg, lb, nullptr, h->hbuf, M, D, 1, 0, adt, pk));
-            g.A = h->hbuf; g.a_packed_mb = pk;
-        }
-        g.M = M; g.batch = 1; g.C = h->logits; g.ldc = V; g.store = STORE_ROWS;
-        CHK(run_linear(h, c.md, g, *heads[lv], adt, DT_F32, c.st, "gemm_head"));
+    const bool bidir = cf.depth_decoding == HQT_DEPTH_BIDIRECTIONAL, causal_head = cf.depth_decoding == HQT_DEPTH_TOP2MID2BOT;
+    const int nsub = causal_head ? h->depth_rows : c.levels;       // 'top2mid2bot': one sub-step per depth token
+    auto dln_of = [&](const SubStep& s) { return !bidir && dln_ok(h, c, h->depth[0], B * s.Tq) && heads[s.lv]->wpk_ln; };
+    bool pfull = false;
+    CHK(run_body(h, c, Tq_body, body_t_base, body_tbase_from_state, dln_of(sub_step(cf, 0)), &pfull));
+    // the draw and the embedding lookup of the drawn code in one kernel: the two-level top sampler's workgroup of sample b also writes the
+    // four input rows of depth sub-step 1 (HQT_NO_FUSED_EMBED=1: separate depth_embed_kernel, for A/B runs)
+    static const bool fuse_env = !getenv("HQT_NO_FUSED_EMBED");
+    const bool fuse = fuse_env && c.levels == 2 && !bidir;
+    void* normed[3] = {nullptr, nullptr, nullptr};
+    SamplerSet bidir_set;
+    if (bidir) {                  // one pass over all depth rows
+        const int M = B * h->depth_rows;
+        const bool dln = dln_ok(h, c, h->depth[0], M);
         {
-            Timed t(h, "sampler", c.st);
-            SamplerArgs sa{h->logits, M, V, Tq, B, c.temperature[lv], c.top_k[lv], c.top_p[lv], c.noise, draw0,
-                           h->state, h->rows, c.o.n_steps, outs[lv], c.logits_out, 21};
-            if (causal_head && lv > 0) { sa.out_stride = lv == 1 ? 4 : 16; sa.out_slot = lv == 1 ? sub - 1 : sub - 5; }
+            Timed t(h, "bidir_depth_input", c.st);
+            LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, B, D, Tq_body, Tq_body - 1, 1e-5f, DT_F32, 0,
+                      h->pend.slabs, h->pend.S, h->pend.rows, h->pend.bias, dln ? h->xdpk : nullptr, dln ? packed_mb(M) : 0, h->partsd};
+            ln.fill = W(h, "pos_emb_depth.weight");
+            h->pend.slabs = nullptr; h->pend.S = 0;
+            HIPCHK(launch_bidir_depth_input(ln, c.st));
+            h->npartsd = 1;
+        }
+        CHK(run_depth(h, c, dln, h->depth_rows, 0));      // Tq = 5 > 1: never the single-key shortcut of run_block_dln
+        {   // ln_top / ln_bot of the interleaved rows into two compact operands: [B, D] (hbuf) and [4 B, D] (abuf)
+            Timed t(h, "bidir_head_ln", c.st);
+            LNArgs ln{h->xd, W(h, "ln_top.weight"), W(h, "ln_top.bias"), nullptr, h->hbuf, M, D, 1, 0, 1e-5f, c.md.act_dt(), head_pk(c, h->head_top, B),
+                      h->pend.slabs, h->pend.S, h->pend.rows, h->pend.bias, nullptr, 0, nullptr};
+            ln.gamma2 = W(h, "ln_bot.weight"); ln.beta2 = W(h, "ln_bot.bias"); ln.y2 = h->abuf; ln.out2_packed_mb = head_pk(c, h->head_bot, 4 * B);
+            h->pend.slabs = nullptr; h->pend.S = 0;
+            HIPCHK(launch_bidir_head_ln(ln, c.st));
+        }
+        normed[0] = h->hbuf; normed[1] = h->abuf;
+        bidir_set = {c.lv[0].temperature, c.lv[1].top_k, c.lv[1].top_p};
+    }
+    for (int sub = 0; sub < nsub; ++sub) {
+        const SubStep s = sub_step(cf, sub);
+        const int M = B * s.Tq;
+        const bool dln = dln_of(s), in_pfull = pfull && sub == 0;      // the whole-position launch computed sub-step 0 up to its logits
+        if (!bidir && !in_pfull) {    // the bidirectional pass ran its depth blocks above
+            CHK(run_depth_input(h, c, sub, dln, Tq_body, fuse));
+            h->npartsd = 1;
+            CHK(run_depth(h, c, dln, s.Tq, s.tbase));
+        }
+        if (!in_pfull) CHK(run_head(h, c, *heads[s.lv], s.lv, M, dln, normed[s.lv]));
+        {
+            Timed t(h, bidir ? (s.lv ? "bidir_sampler_bot" : "bidir_sampler_top") : "sampler", c.st);
+            const SamplerSet& set = bidir ? bidir_set : c.lv[s.lv];
+            SamplerArgs sa{h->logits, M, V, s.Tq, B, set.temperature, set.top_k, set.top_p, c.noise, s.tbase,
+                           h->state, h->rows, c.n_steps, c.out[s.lv], c.logits_out, h->depth_rows};
+            sa.out_stride = s.out_stride; sa.out_slot = s.out_slot;
             sa.fast_math = c.md.fast ? 1 : 0;
+            if (fuse && sub == 0) {
+                const bool dln_next = dln_of(sub_step(cf, 1));
+                sa.emb_tok = W(h, "tok_emb_top_depth.weight"); sa.emb_pos = W(h, "pos_emb_depth.weight");
+                sa.emb_feed = c.feed[0] != c.out[0] ? c.feed[0] : nullptr;
+                sa.emb_x = h->xd; sa.emb_D = D;
+                sa.emb_xpk = dln_next ? h->xdpk : nullptr; sa.emb_pk_mb = dln_next ? packed_mb(4 * B) : 0; sa.emb_parts = h->partsd;
+            }
             HIPCHK(launch_sampler(sa, c.st));
         }
     }
@@ -1582,97 +1514,92 @@ static int run_decode_step(hqt_handle* h, const SampleCtx& c) {      // one KV-c
     const hqt_config& cf = h->cfg;
     {
         Timed t(h, "embed", c.st);
-        EmbedArgs e{c.B, cf.embed_dim, c.o.n_steps, cf.embedding_type, cf.cond_type, h->state, c.cond,
+        EmbedArgs e{c.B, cf.embed_dim, c.n_steps, cf.embedding_type, cf.cond_type, h->state, c.cond,
                     cf.cond_type == HQT_COND_CLASS ? W(h, "sos.weight") : (cf.cond_type == HQT_COND_NONE ? W(h, "sos") : nullptr),
                     W(h, "tok_emb_top.weight"), W(h, "tok_emb_bot.weight"), W(h, "pos_emb_top.weight"),
                     cf.embedding_type == HQT_EMB_TRANSFORMER1 ? W(h, "pos_emb_emb.weight") : nullptr,
-                    c.feed_top, c.feed_bot, h->x, nullptr, 0, h->parts};
+                    c.feed[0], c.feed[1], h->x, nullptr, 0, h->parts};
         if (dln_ok(h, c, h->body[0], c.B)) { e.xpk = h->xpk; e.pk_mb = packed_mb(c.B); h->nparts = 1; }
-        if (c.levels == 3) { e.levels = 3; e.tok_l2 = h->w["stage2.tok_emb_levels.2.weight"].d; e.codes_l2 = c.feed_l2; }
+        if (c.levels == 3) { e.levels = 3; e.tok_l2 = W(h, "tok_emb_levels.2.weight"); e.codes_l2 = c.feed[2]; }
         e.V = cf.vocab_top; e.n_classes = cf.n_classes;
         HIPCHK(launch_embed_step(e, c.st));
     }
-    if (c.levels == 3) CHK(run_position_l3(h, c, 1, 0, true));
-    else CHK(run_position(h, c, 1, 0, true));
+    CHK(run_position(h, c, 1, 0, true));
     HIPCHK(launch_advance_step(h->state, 1, c.st));
     return HQT_OK;
 }
 
 static int sample_run(hqt_handle* h, const SampleCtx& c);
 
-extern "C" int hqt_sample(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts* opts, const float* noise,
-                          const int64_t* force_top, const int64_t* force_bot, float* logits_out, int64_t* out_top,
-                          int64_t* out_bot, void* stream) {
-    if (!h || !opts || !out_top || !out_bot) return fail(HQT_ERR_INVALID, "null argument");
+// hqt_sample / hqt_sample_l3 after their null checks: `c` holds the call's options, sampler settings and forced codes (feed); validates them,
+// runs the call and copies the drawn codes of every level out
+static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t* const* out, void* stream) {
     if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
     const hqt_config& cf = h->cfg;
-    if (!cf.has_stage2) return fail(HQT_ERR_STATE, "handle was created without stage 2");
-    if (cf.code_levels == 3) return fail(HQT_ERR_STATE, "three-level model: use hqt_sample_l3");
+    if (c.levels == 2 && !cf.has_stage2) return fail(HQT_ERR_STATE, "handle was created without stage 2");
+    if (c.levels == 2 && cf.code_levels == 3) return fail(HQT_ERR_STATE, "three-level model: use hqt_sample_l3");
+    if (c.levels == 3 && (!cf.has_stage2 || cf.code_levels != 3)) return fail(HQT_ERR_STATE, "handle does not hold a three-level stage 2");
+    const int B = c.B;
     if (B < 1 || B > cf.max_batch) return fail(HQT_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cf.max_batch);
-    if (opts->n_steps < 1 || opts->n_steps > cf.max_steps) return fail(HQT_ERR_INVALID, "n_steps=%d outside [1, %d]", opts->n_steps, cf.max_steps);
+    if (c.n_steps < 1 || c.n_steps > cf.max_steps) return fail(HQT_ERR_INVALID, "n_steps=%d outside [1, %d]", c.n_steps, cf.max_steps);
     if (cf.cond_type != HQT_COND_NONE && !cond) return fail(HQT_ERR_INVALID, "cond is required for class/text conditioning");
-    if (!(opts->temperature_top > 0.f) || !(opts->temperature_bot > 0.f)) return fail(HQT_ERR_INVALID, "temperatures must be > 0");
-    if ((opts->top_p_top > 0.f || opts->top_p_bot > 0.f) && cf.vocab_top > 8192) return fail(HQT_ERR_INVALID, "top-p needs vocab <= 8192");
+    bool top_p = false;
+    for (int i = 0; i < c.levels; ++i) {
+        if (!(c.lv[i].temperature > 0.f)) return fail(HQT_ERR_INVALID, "temperatures must be > 0");
+        top_p = top_p || c.lv[i].top_p > 0.f;
+    }
+    if (top_p && cf.vocab_top > 8192) return fail(HQT_ERR_INVALID, "top-p needs vocab <= 8192");
     ON_DEVICE(h);
     // The launch sequence reads cond and writes the drawn codes in buffers owned by the handle, and takes the Philox seed
     // and the global row offset from device memory: nothing that changes from call to call is baked into the captured
     // graph, so a steady stream of batches replays ONE graph (no re-capture, no exec destroyed under pending launches).
-    SampleCtx c;
-    c.B = B; c.cond = cond ? h->cond_buf : nullptr; c.o = *opts; c.noise = noise;
-    c.feed_top = force_top ? force_top : h->codes_top;
-    c.feed_bot = force_bot ? force_bot : h->codes_bot;
-    c.logits_out = logits_out; c.out_top = h->codes_top; c.out_bot = h->codes_bot;
+    int64_t* codes[3] = {h->codes_top, h->codes_bot, h->codes_l2};
+    for (int i = 0; i < c.levels; ++i) {
+        if (!c.feed[i]) c.feed[i] = codes[i];
+        c.out[i] = codes[i];
+    }
+    c.cond = cond ? h->cond_buf : nullptr;
     c.st = (hipStream_t)stream;
-    CHK(mode_of(opts->precision, false, &c.md));
+    CHK(mode_of(c.precision, false, &c.md));
     CHK(layout_check(h, c.md));
     if (cond) HIPCHK(hipMemcpyAsync(h->cond_buf, cond, (size_t)B * (cf.cond_type == HQT_COND_TEXT ? cf.ctx_len_txt : 1) * 8, hipMemcpyDefault, c.st));
-    const int rc_run = sample_run(h, c);
-    if (rc_run != HQT_OK) return rc_run;
-    HIPCHK(hipMemcpyAsync(out_top, h->codes_top, (size_t)B * opts->n_steps * 8, hipMemcpyDeviceToDevice, c.st));
-    HIPCHK(hipMemcpyAsync(out_bot, h->codes_bot, (size_t)B * opts->n_steps * 4 * 8, hipMemcpyDeviceToDevice, c.st));
+    CHK(sample_run(h, c));
+    static const size_t width[3] = {1, 4, 16};
+    for (int i = 0; i < c.levels; ++i)
+        HIPCHK(hipMemcpyAsync(out[i], codes[i], (size_t)B * c.n_steps * width[i] * 8, hipMemcpyDeviceToDevice, c.st));
     return HQT_OK;
+}
+
+// the options both entry points share
+template <class Opts> static SampleCtx sample_ctx(int levels, int B, const Opts* o, const float* noise, float* logits_out) {
+    SampleCtx c{};
+    c.levels = levels; c.B = B; c.noise = noise; c.logits_out = logits_out;
+    c.precision = o->precision; c.n_steps = o->n_steps; c.use_graph = o->use_graph;
+    c.seed = o->seed; c.sample_offset = o->sample_offset; c.row_seeds = o->row_seeds; c.row_offsets = o->row_offsets;
+    return c;
+}
+
+extern "C" int hqt_sample(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts* opts, const float* noise,
+                          const int64_t* force_top, const int64_t* force_bot, float* logits_out, int64_t* out_top,
+                          int64_t* out_bot, void* stream) {
+    if (!h || !opts || !out_top || !out_bot) return fail(HQT_ERR_INVALID, "null argument");
+    SampleCtx c = sample_ctx(2, B, opts, noise, logits_out);
+    c.lv[0] = {opts->temperature_top, opts->top_k_top, opts->top_p_top};
+    c.lv[1] = {opts->temperature_bot, opts->top_k_bot, opts->top_p_bot};
+    c.feed[0] = force_top; c.feed[1] = force_bot;
+    int64_t* const out[2] = {out_top, out_bot};
+    return sample_call(h, c, cond, out, stream);
 }
 
 extern "C" int hqt_sample_l3(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts_l3* opts, const float* noise,
                              const int64_t* force0, const int64_t* force1, const int64_t* force2, float* logits_out,
                              int64_t* out0, int64_t* out1, int64_t* out2, void* stream) {
     if (!h || !opts || !out0 || !out1 || !out2) return fail(HQT_ERR_INVALID, "null argument");
-    if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
-    const hqt_config& cf = h->cfg;
-    if (!cf.has_stage2 || cf.code_levels != 3) return fail(HQT_ERR_STATE, "handle does not hold a three-level stage 2");
-    if (B < 1 || B > cf.max_batch) return fail(HQT_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cf.max_batch);
-    if (opts->n_steps < 1 || opts->n_steps > cf.max_steps) return fail(HQT_ERR_INVALID, "n_steps=%d outside [1, %d]", opts->n_steps, cf.max_steps);
-    if (cf.cond_type != HQT_COND_NONE && !cond) return fail(HQT_ERR_INVALID, "cond is required for class/text conditioning");
-    float pmax = 0.f;
-    for (int i = 0; i < 3; ++i) {
-        if (!(opts->temperature[i] > 0.f)) return fail(HQT_ERR_INVALID, "temperatures must be > 0");
-        pmax = std::max(pmax, opts->top_p[i]);
-    }
-    if (pmax > 0.f && cf.vocab_top > 8192) return fail(HQT_ERR_INVALID, "top-p needs vocab <= 8192");
-    ON_DEVICE(h);
-    SampleCtx c;
-    c.levels = 3;
-    c.B = B; c.cond = cond ? h->cond_buf : nullptr; c.noise = noise;
-    c.o = hqt_sample_opts{};                        // the shared loop reads n_steps / seed / offsets / graph flag from here
-    c.o.precision = opts->precision; c.o.n_steps = opts->n_steps; c.o.seed = opts->seed; c.o.sample_offset = opts->sample_offset;
-    c.o.use_graph = opts->use_graph; c.o.row_seeds = opts->row_seeds; c.o.row_offsets = opts->row_offsets;
-    c.o.top_k_top = opts->top_k[0]; c.o.top_k_bot = opts->top_k[1]; c.o.top_p_top = opts->top_p[0]; c.o.top_p_bot = std::max(opts->top_p[1], opts->top_p[2]);
-    c.o.temperature_top = opts->temperature[0]; c.o.temperature_bot = opts->temperature[1];
-    for (int i = 0; i < 3; ++i) { c.top_k[i] = opts->top_k[i]; c.top_p[i] = opts->top_p[i]; c.temperature[i] = opts->temperature[i]; }
-    c.feed_top = force0 ? force0 : h->codes_top;
-    c.feed_bot = force1 ? force1 : h->codes_bot;
-    c.feed_l2 = force2 ? force2 : h->codes_l2;
-    c.logits_out = logits_out; c.out_top = h->codes_top; c.out_bot = h->codes_bot; c.out_l2 = h->codes_l2;
-    c.st = (hipStream_t)stream;
-    CHK(mode_of(opts->precision, false, &c.md));
-    CHK(layout_check(h, c.md));
-    if (cond) HIPCHK(hipMemcpyAsync(h->cond_buf, cond, (size_t)B * (cf.cond_type == HQT_COND_TEXT ? cf.ctx_len_txt : 1) * 8, hipMemcpyDefault, c.st));
-    const int rc_run = sample_run(h, c);
-    if (rc_run != HQT_OK) return rc_run;
-    HIPCHK(hipMemcpyAsync(out0, h->codes_top, (size_t)B * opts->n_steps * 8, hipMemcpyDeviceToDevice, c.st));
-    HIPCHK(hipMemcpyAsync(out1, h->codes_bot, (size_t)B * opts->n_steps * 4 * 8, hipMemcpyDeviceToDevice, c.st));
-    HIPCHK(hipMemcpyAsync(out2, h->codes_l2, (size_t)B * opts->n_steps * 16 * 8, hipMemcpyDeviceToDevice, c.st));
-    return HQT_OK;
+    SampleCtx c = sample_ctx(3, B, opts, noise, logits_out);
+    for (int i = 0; i < 3; ++i) c.lv[i] = {opts->temperature[i], opts->top_k[i], opts->top_p[i]};
+    c.feed[0] = force0; c.feed[1] = force1; c.feed[2] = force2;
+    int64_t* const out[3] = {out0, out1, out2};
+    return sample_call(h, c, cond, out, stream);
 }
 
 // Persistent launches need every compute unit of the device: two of them in flight at once (two root handles sampling on two streams)
@@ -1704,16 +1631,14 @@ struct PersistOrder {
 
 static int sample_run(hqt_handle* h, const SampleCtx& c) {
     const hqt_config& cf = h->cfg;
-    const hqt_sample_opts* opts = &c.o;
     const int B = c.B;
-    const int64_t* cond = c.cond;
-    const float* noise = c.noise;
-    float* logits_out = c.logits_out;
-    HIPCHK(sampler_configure(cf.vocab_top, opts->top_p_top > 0.f || opts->top_p_bot > 0.f));
+    bool top_p = false;
+    for (int i = 0; i < c.levels; ++i) top_p = top_p || c.lv[i].top_p > 0.f;
+    HIPCHK(sampler_configure(cf.vocab_top, top_p));
     CHK(persist_bind(h));
     HIPCHK(launch_set_step(h->state, 0, 0, c.st));
-    if (opts->row_seeds || opts->row_offsets) {      // merged steps: per-row Philox keys (host arrays, staged through pinned-free pageable copies: B <= max_batch entries)
-        if (!opts->row_seeds || !opts->row_offsets) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
+    if (c.row_seeds || c.row_offsets) {      // merged steps: per-row Philox keys (host arrays, staged through pinned-free pageable copies: B <= max_batch entries)
+        if (!c.row_seeds || !c.row_offsets) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
         const int slot = h->rows_next;
         h->rows_next = (slot + 1) % hqt_handle::ROWS_RING;
         if (!h->rows_pinned[slot]) {
@@ -1722,40 +1647,38 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         }
         if (h->rows_busy[slot]) HIPCHK(hipEventSynchronize(h->rows_ev[slot]));       // the copy that last read this buffer (4 calls ago) is done
         RowKey* rk = h->rows_pinned[slot];
-        for (int b = 0; b < B; ++b) { rk[b].seed = opts->row_seeds[b]; rk[b].global_row = opts->row_offsets[b]; }
+        for (int b = 0; b < B; ++b) { rk[b].seed = c.row_seeds[b]; rk[b].global_row = c.row_offsets[b]; }
         HIPCHK(hipMemcpyAsync(h->rows, rk, (size_t)B * sizeof(RowKey), hipMemcpyHostToDevice, c.st));
         HIPCHK(hipEventRecord(h->rows_ev[slot], c.st));
         h->rows_busy[slot] = true;
     } else {
-        HIPCHK(launch_set_rows(h->rows, B, opts->seed, opts->sample_offset, c.st));
+        HIPCHK(launch_set_rows(h->rows, B, c.seed, c.sample_offset, c.st));
     }
     int first = 0;
     if (cf.cond_type == HQT_COND_TEXT) {     // 64-token causal prefill (sampling.py:187-190, layers.py:107-111)
         const int T = cf.ctx_len_txt;
-        HIPCHK(launch_embed_text(cond, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, B, T, cf.embed_dim, c.st, cf.vocab_txt));
-        if (c.levels == 3) CHK(run_position_l3(h, c, T, 0, false));
-        else CHK(run_position(h, c, T, 0, false));
+        HIPCHK(launch_embed_text(c.cond, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, B, T, cf.embed_dim, c.st, cf.vocab_txt));
+        CHK(run_position(h, c, T, 0, false));
         HIPCHK(launch_advance_step(h->state, T, c.st));
         first = 1;
     }
-    const int remaining = opts->n_steps - first;
+    const int remaining = c.n_steps - first;
     if (remaining <= 0) return HQT_OK;
-    if (opts->use_graph && !h->timing) {
+    if (c.use_graph && !h->timing) {
         // positions per captured graph: the largest divisor of the remaining positions up to HQT_GRAPH_POSITIONS (default 16):
         // one graph launch then covers G positions (fewer host launches and graph-to-graph hand-overs on the device)
         static const int gmax = getenv("HQT_GRAPH_POSITIONS") ? std::max(1, atoi(getenv("HQT_GRAPH_POSITIONS"))) : 16;
         int G = 1;
         for (int d = std::min(gmax, remaining); d >= 1; --d) if (remaining % d == 0) { G = d; break; }
-        std::vector<uint64_t> key = {(uint64_t)G, (uint64_t)B, (uint64_t)(cond != nullptr), (uint64_t)noise, (uint64_t)c.feed_top, (uint64_t)c.feed_bot,
-                                     (uint64_t)logits_out, (uint64_t)opts->precision,
-                                     (uint64_t)opts->n_steps, (uint64_t)opts->top_k_top, (uint64_t)opts->top_k_bot,
-                                     (uint64_t)c.levels, (uint64_t)c.feed_l2, (uint64_t)c.top_k[2], (uint64_t)h->policy,
+        std::vector<uint64_t> key = {(uint64_t)G, (uint64_t)B, (uint64_t)(c.cond != nullptr), (uint64_t)c.noise, (uint64_t)c.logits_out,
+                                     (uint64_t)c.precision, (uint64_t)c.n_steps, (uint64_t)c.levels, (uint64_t)h->policy,
                                      (uint64_t)((h->persist_enabled && !h->persist_tripped ? 1 : 0) + (h->single_key ? 0 : 4) + (h->split_kslices ? 0 : 8))};
-        { uint32_t f3[2]; memcpy(f3, &c.top_p[2], 4); memcpy(f3 + 1, &c.temperature[2], 4); key.push_back(f3[0]); key.push_back(f3[1]); }
-        uint32_t f[4];
-        memcpy(f, &opts->top_p_top, 4); memcpy(f + 1, &opts->top_p_bot, 4);
-        memcpy(f + 2, &opts->temperature_top, 4); memcpy(f + 3, &opts->temperature_bot, 4);
-        for (int i = 0; i < 4; ++i) key.push_back(f[i]);
+        for (const int64_t* f : c.feed) key.push_back((uint64_t)f);
+        for (const SamplerSet& l : c.lv) {
+            uint32_t f[2];
+            memcpy(f, &l.top_p, 4); memcpy(f + 1, &l.temperature, 4);
+            key.push_back((uint64_t)l.top_k); key.push_back(f[0]); key.push_back(f[1]);
+        }
         if (!h->graph_exec || key != h->graph_key) {
             if (h->graph_exec) {                         // rare (options or test-only buffers changed): drain before destroying
                 HIPCHK(hipStreamSynchronize(c.st));

@@ -225,6 +225,24 @@ class Engine:
         o.row_seeds, o.row_offsets = C.cast(rs, C.c_void_p), C.cast(ro, C.c_void_p)
         return rs, ro
 
+    def _prep(self, t, shape, dtype, what: str, table: int = 0) -> Optional[torch.Tensor]:
+        """A sampling input checked for its shape (and, ``table`` > 0, for ids inside a table of that many rows), on the device; None stays None."""
+        if t is None:
+            return None
+        t = torch.as_tensor(t)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f'{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}')
+        if table:
+            self._check_index(t, table, what)
+        return t.to(device=self.device, dtype=dtype).contiguous()
+
+    def _prep_cond(self, cond, B: int) -> Optional[torch.Tensor]:
+        if self.s2.cond == 1:
+            return self._prep(cond, (B,), torch.int64, 'cond (class ids)', self.s2.n_classes)
+        if self.s2.cond == 2:
+            return self._prep(cond, (B, self.s2.ctx_len_txt), torch.int64, 'cond (text token ids)', self.s2.vocab_txt)
+        return None
+
     # ------------------------------------------------------------------ stage 2
     def sample(self, batch: int, cond: Optional[torch.Tensor], n_steps: int, *, precision: int = PRECISION_FAST,
                top_k: Sequence[Optional[int]] = (None, None), top_p: Sequence[Optional[float]] = (None, None),
@@ -246,25 +264,10 @@ class Engine:
         o.temperature_top, o.temperature_bot = float(temperature[0]), float(temperature[1])
         o.seed, o.sample_offset, o.use_graph = int(seed) & (2 ** 64 - 1), int(sample_offset), int(bool(use_graph))
         rows = self._row_keys(o, B, row_seeds, row_offsets)
-
-        def prep(t, shape, dtype, what, table=0):
-            if t is None:
-                return None
-            t = torch.as_tensor(t)
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f'{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}')
-            if table:
-                self._check_index(t, table, what)
-            return t.to(device=dev, dtype=dtype).contiguous()
-        if self.s2.cond == 1:
-            cond = prep(cond, (B,), torch.int64, 'cond (class ids)', self.s2.n_classes)
-        elif self.s2.cond == 2:
-            cond = prep(cond, (B, self.s2.ctx_len_txt), torch.int64, 'cond (text token ids)', self.s2.vocab_txt)
-        else:
-            cond = None
-        noise = prep(noise, (n_steps, 5, B, V), torch.float32, 'noise')
-        force_top = prep(force_top, (B, n_steps), torch.int64, 'force_top', V)
-        force_bot = prep(force_bot, (B, n_steps, 4), torch.int64, 'force_bot', V)
+        cond = self._prep_cond(cond, B)
+        noise = self._prep(noise, (n_steps, 5, B, V), torch.float32, 'noise')
+        force_top = self._prep(force_top, (B, n_steps), torch.int64, 'force_top', V)
+        force_bot = self._prep(force_bot, (B, n_steps, 4), torch.int64, 'force_bot', V)
         if out is None:
             out_top = torch.empty((B, n_steps), dtype=torch.int64, device=dev)
             out_bot = torch.empty((B, n_steps, 4), dtype=torch.int64, device=dev)
@@ -303,34 +306,19 @@ class Engine:
             o.temperature[i] = float(temperature[i])
         o.seed, o.sample_offset, o.use_graph = int(seed) & (2 ** 64 - 1), int(sample_offset), int(bool(use_graph))
         rows = self._row_keys(o, B, row_seeds, row_offsets)
-
-        def prep(t, shape, dtype, what, table=0):
-            if t is None:
-                return None
-            t = torch.as_tensor(t)
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f'{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}')
-            if table:
-                self._check_index(t, table, what)
-            return t.to(device=dev, dtype=dtype).contiguous()
-        if self.s2.cond == 1:
-            cond = prep(cond, (B,), torch.int64, 'cond (class ids)', self.s2.n_classes)
-        elif self.s2.cond == 2:
-            cond = prep(cond, (B, self.s2.ctx_len_txt), torch.int64, 'cond (text token ids)', self.s2.vocab_txt)
-        else:
-            cond = None
-        noise = prep(noise, (n_steps, 21, B, V), torch.float32, 'noise')
+        cond = self._prep_cond(cond, B)
+        noise = self._prep(noise, (n_steps, 21, B, V), torch.float32, 'noise')
         f = [None, None, None]
         if force is not None:
-            f = [prep(force[0], (B, n_steps), torch.int64, 'force[0]', V), prep(force[1], (B, n_steps, 4), torch.int64, 'force[1]', V),
-                 prep(force[2], (B, n_steps, 16), torch.int64, 'force[2]', V)]
+            f = [self._prep(force[0], (B, n_steps), torch.int64, 'force[0]', V), self._prep(force[1], (B, n_steps, 4), torch.int64, 'force[1]', V),
+                 self._prep(force[2], (B, n_steps, 16), torch.int64, 'force[2]', V)]
         outs = [torch.empty(shp, dtype=torch.int64, device=dev) for shp in ((B, n_steps), (B, n_steps, 4), (B, n_steps, 16))]
         logits = torch.empty((n_steps, 21, B, V), dtype=torch.float32, device=dev) if return_logits else None
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
             _lib.check(self.lib.hqt_sample_l3(self.h, B, _ptr(cond), C.byref(o), _ptr(noise), _ptr(f[0]), _ptr(f[1]), _ptr(f[2]),
                                               _ptr(logits), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), C.c_void_p(stream)))
-            self._note_split(precision, stream, ar_rows=B)        # the three-level body runs persistently too (run_position_l3)
+            self._note_split(precision, stream, ar_rows=B)        # the three-level body runs persistently too (run_position)
         self._keep = (cond, noise, f, rows)
         self._trust(*outs, bound=max(self.s2.vocab_top, self.s2.vocab_bot))
         return (outs[0], outs[1], outs[2], logits) if return_logits else tuple(outs)
