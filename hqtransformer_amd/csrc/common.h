@@ -183,7 +183,7 @@ struct GemmArgs {
     int* range_flag;         // a_f32 / b_f32: where an element outside the fp16 range is reported (hqt_range_check)
     int out_split;           // conv3x3_split_ring16_kernel: store the output as fp16 hi / lo operand planes [pixel][2][N] (range-checked: range_flag) instead of the
                              // fp32 tensor -- the consumer is another SPLIT conv with nothing in between (resblock -> upsampling conv): no operand pass
-    int k_quarters;          // fp32 nn.Linear of the AR loop (set by run_linear for its gemm_* launches): the four-quarter summation order shared by
+    int k_quarters;          // fp32 nn.Linear of the AR loop (set by ar_linear, the AR loop's dispatcher in engine.hip): the four-quarter summation order shared by
                              //   exact_mfma_gemm_kernel (<= 256 rows) and gemm_tile_kernel<..., QUARTERS>; every other fp32 GEMM keeps one chain per output
     int b_tile16;            // exact_mfma_gemm_kernel only: Bw is the fragment-ordered fp32 copy [n / 16][k / 32][chunk][lane][4] (pack_exact_tiles_kernel)
     int k_slices;            // split_gemm_kernel<fp32 A> only (plain fp32 rows out, one batch): > 1 = blockIdx.z takes a slice of K and leaves its raw partial as

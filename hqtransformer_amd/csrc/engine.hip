@@ -129,7 +129,6 @@ struct hqt_handle {
     float *parts = nullptr, *partsd = nullptr; // their partial row statistics [D/32][Mpad][2]
     int nparts = 0, npartsd = 0;
     float* fold_tmp = nullptr;
-    int resid_nparts = 0;                     // partial row statistics the last STORE_RESID GEMM left per row (run_linear)
     bool tile_gemm = true;                    // merged passes through the LDS-tiled MFMA kernels (HQT_NO_TILE_GEMM=1: streaming kernels at every row count)
     float* splitk = nullptr;                  // split-K partial slabs of the streaming GEMM
     size_t splitk_elems = 0;
@@ -157,8 +156,7 @@ struct hqt_handle {
     unsigned long long* vq_best = nullptr;
     void* act[4] = {nullptr, nullptr, nullptr, nullptr};   // 3 rotating activation buffers + the normalised/activated copy (FAST)
     double* gn_partial = nullptr;
-    float* gn_tiles = nullptr;                // per-tile output statistics of the last halo conv ([image][tile][32][2])
-    struct { const void* tensor; int tiles; bool dbl; } gn_ready = {nullptr, 0, false};   // dbl: double partials (SPLIT conv)
+    float* gn_tiles = nullptr;                // per-tile output statistics of the last halo conv ([image][tile][32][2]); S1Ctx::gn_ready says of which tensor
     void* zero_page = nullptr;
     int* range_flag = nullptr;                // set by the SPLIT operand pass when an activation leaves the fp16 range (hqt_range_check)
     size_t act_elems = 0;
@@ -904,51 +902,51 @@ static int mode_of(int precision, bool stage1, Mode* md) {
     return HQT_OK;
 }
 
-// y = x W^T (+b)(act)(+resid): picks the MFMA kernels in FAST mode when the shape allows
-static int run_linear(hqt_handle* h, const Mode& md, GemmArgs g, const Lin& l, int a_dt, int c_dt, hipStream_t st,
-                      const char* tag, bool defer_residual = false) {
+// What every launch of filter bank `l` takes from it and from the handle (both dispatchers, and the shape probes of stage 1);
+// split_planes: the filters are the fp16 hi / lo planes (and their fragment-packed copies) of the SPLIT kernels
+static void lin_args(const hqt_handle* h, GemmArgs& g, const Lin& l, bool split_planes) {
     g.N = l.N; g.K = l.K; g.ldb = l.K;
     g.bias = l.b32;
     g.zero_page = h->zero_page;
     g.tune = h->policy;
     if (g.alpha == 0.0f) g.alpha = 1.0f;
     if (g.lda == 0) g.lda = l.K;
-    // tools/ar_pass_time.py --by-rows: one timing slot per (GEMM, row count) instead of per GEMM
-    static const bool by_rows = getenv("HQT_TIMING_BY_ROWS") != nullptr;
-    char slot_name[64];
-    snprintf(slot_name, sizeof slot_name, by_rows ? "%s@%d" : "%s", tag, g.M);
-    Timed t(h, slot_name, st);
-    if (g.Bw_lo) {                              // SPLIT: the caller packed the operand planes (s1_operand) after checking the shape
-        g.Bw = l.w16h; g.Bw_lo = l.w16l; g.Bw_frag16 = l.wfrag16; g.Bw_up16 = l.wup16;
-        if (h->gn_ready.tensor == g.C) h->gn_ready.tensor = nullptr;
-        if (g.conv_taps == 9) {
-            if (g.store == STORE_ROWS && h->gn_tiles && conv_halo_stats_ok(g.N, 32)) {   // every such output is normalised next
-                g.gn_part_out_d = reinterpret_cast<double*>(h->gn_tiles); g.gn_out_groups = 32;
-                h->gn_ready.tensor = g.C; h->gn_ready.tiles = split_conv3_tiles_per_image(g); h->gn_ready.dbl = true;
-            }
-            HIPCHK(launch_split_conv3(g, st));
-        } else {
-            HIPCHK(launch_split_gemm(g, st));
-        }
-        return HQT_OK;
+    if (split_planes) { g.Bw = l.w16h; g.Bw_lo = l.w16l; g.Bw_frag16 = l.wfrag16; g.Bw_up16 = l.wup16; }
+}
+
+// Timing slot of a dispatched launch: `tag`, or `tag@rows` under HQT_TIMING_BY_ROWS (tools/ar_pass_time.py --by-rows: one slot per
+// (GEMM, row count) instead of per GEMM)
+struct SlotName {
+    char s[64];
+    SlotName(const char* tag, int rows) {
+        static const bool by_rows = getenv("HQT_TIMING_BY_ROWS") != nullptr;
+        snprintf(s, sizeof s, by_rows ? "%s@%d" : "%s", tag, rows);
     }
+};
+
+// Stage 2, y = x W^T (+b)(act)(+resid) of one nn.Linear of the AR loop.  FAST: the LDS-tiled, the weight-streaming or the plain MFMA kernel;
+// SPLIT: fp16 hi / lo planes above 256 rows; otherwise fp32.  defer_residual: a split-K launch may leave its slabs in h->pend for the next
+// LayerNorm.  resid_nparts (STORE_RESID launches): the partial row statistics the producer leaves per row.
+static int ar_linear(hqt_handle* h, const Mode& md, GemmArgs g, const Lin& l, int a_dt, int c_dt, hipStream_t st,
+                     const char* tag, bool defer_residual = false, int* resid_nparts = nullptr) {
+    lin_args(h, g, l, false);
+    g.k_quarters = 1;                           // every caller is the AR loop: see GemmArgs.k_quarters
+    const SlotName slot(tag, g.M);
+    Timed t(h, slot.s, st);
     if (md.fast) {
-        if (g.store == STORE_RESID) h->resid_nparts = g.N / 32;          // partial row statistics the producer leaves (streaming GEMM: one per 32 columns)
+        if (resid_nparts) *resid_nparts = g.N / 32;          // streaming GEMM: one per 32 columns
         // merged passes (512+ rows): the LDS-tiled MFMA kernels (tile_gemm.hip); same operands, same store modes
         if ((g.ln_parts ? l.wpk_ln : l.wpk) && h->tile_gemm && tile_gemm_ok(g, a_dt, c_dt)) {
             const TilePlan tp = tile_gemm_plan(g);
             if (tp.geom >= 0 && (size_t)tp.S * 32 * g.a_packed_mb * g.N <= h->splitk_elems) {
                 if (g.ln_parts) g.bias = l.bias_ln;
                 HIPCHK(launch_tile_gemm(g, g.ln_parts ? l.wpk_ln : l.wpk, a_dt, c_dt, tp, h->splitk, st));
-                if (tp.S > 1) count_variant(h, "variant:tile_gemm_%dx%d_splitk%d:%s%s", tp.bm, tp.bn, tp.S, tag, by_rows ? slot_name + strlen(tag) : "");
-                else count_variant(h, "variant:tile_gemm_%dx%d%s:%s%s", tp.bm, tp.bn, g.ln_parts ? "_dln" : "", tag, by_rows ? slot_name + strlen(tag) : "");
                 if (tp.S > 1) {
-                    char cn[64];
-                    snprintf(cn, sizeof cn, by_rows ? "gemm_combine@%d" : "gemm_combine", g.M);
-                    t.next(cn);
+                    count_variant(h, "variant:tile_gemm_%dx%d_splitk%d:%s", tp.bm, tp.bn, tp.S, slot.s);
+                    t.next(SlotName("gemm_combine", g.M).s);
                     HIPCHK(launch_resid_combine(g, h->splitk, tp.S, st));
-                }
-                if (g.store == STORE_RESID) h->resid_nparts = tp.S > 1 ? 1 : g.N / tp.bn;
+                } else count_variant(h, "variant:tile_gemm_%dx%d%s:%s", tp.bm, tp.bn, g.ln_parts ? "_dln" : "", slot.s);
+                if (resid_nparts) *resid_nparts = tp.S > 1 ? 1 : g.N / tp.bn;
                 return HQT_OK;
             }
         }
@@ -959,36 +957,25 @@ static int run_linear(hqt_handle* h, const Mode& md, GemmArgs g, const Lin& l, i
             count_variant(h, "variant:stream_gemm_dln:%s", tag);
             return HQT_OK;
         }
-        if (l.wpk && !g.conv_taps && stream_gemm_ok(g, a_dt, c_dt)) {
+        if (l.wpk && stream_gemm_ok(g, a_dt, c_dt)) {
             int S = (defer_residual && g.store != STORE_RESID) ? stream_gemm_splitk(g) : 1;
             if ((size_t)S * 32 * g.a_packed_mb * g.N > h->splitk_elems) S = 1;
             HIPCHK(launch_stream_gemm(g, l.wpk, a_dt, c_dt, S, h->splitk, st));
             count_variant(h, "variant:stream_gemm:%s", tag);
-            if (S > 1) { h->pend.slabs = h->splitk; h->pend.S = S; h->pend.rows = 32 * g.a_packed_mb; h->pend.bias = l.b32; }
+            if (S > 1) h->pend = {h->splitk, S, 32 * g.a_packed_mb, l.b32};
             return HQT_OK;
         }
         g.Bw = l.w16;
-        if (mfma_gemm_ok(g, a_dt, DT_BF16, c_dt)) {
-            // a 3x3 halo conv also leaves per-tile GroupNorm statistics of its output (every such output is normalised next)
-            if (g.conv_taps == 9 && g.store == STORE_ROWS && h->gn_tiles && conv_halo_ok(g, c_dt) && conv_halo_stats_ok(g.N, 32) &&
-                !getenv("HQT_NO_FUSED_GN")) {
-                g.gn_part_out = h->gn_tiles; g.gn_out_groups = 32;
-                h->gn_ready.tensor = g.C; h->gn_ready.tiles = conv_halo_tiles_per_image(g); h->gn_ready.dbl = false;
-            } else if (h->gn_ready.tensor == g.C) {
-                h->gn_ready.tensor = nullptr;                           // the tensor is being overwritten by something else
-            }
-            HIPCHK(launch_mfma_gemm(g, a_dt, DT_BF16, c_dt, st));
-            return HQT_OK;
-        }
-        if (h->gn_ready.tensor == g.C) h->gn_ready.tensor = nullptr;
-        HIPCHK(launch_gemm_generic(g, a_dt, DT_BF16, c_dt, st));
+        if (mfma_gemm_ok(g, a_dt, DT_BF16, c_dt)) HIPCHK(launch_mfma_gemm(g, a_dt, DT_BF16, c_dt, st));
+        else HIPCHK(launch_gemm_generic(g, a_dt, DT_BF16, c_dt, st));
         return HQT_OK;
     }
     // (up to 256 rows the fp32 matrix instructions of exact_gemm.hip are faster than three fp16 MFMAs on 128 x 128 tiles that are mostly padding:
     //  249 vs 483 ms of AR loop per batch-64 step -- SPLIT takes them there, and is bit-identical to EXACT on those launches)
-    if (md.split_ar && l.w16h && l.w16l && !g.conv_taps && !g.a_packed_mb && g.M > 256) {
+    if (md.split_ar && l.w16h && l.w16l && !g.a_packed_mb && g.M > 256) {
         GemmArgs sg = g;
-        sg.a_f32 = 1; sg.Bw = l.w16h; sg.Bw_lo = l.w16l; sg.range_flag = h->range_flag;
+        lin_args(h, sg, l, true);
+        sg.a_f32 = 1; sg.range_flag = h->range_flag;
         if (split_gemm_ok(sg)) {
             // few tiles (fc2 / proj at 640 rows: 60): K slices into the split-K workspace, summed in index order by the combine launch
             const int S = h->split_kslices ? split_gemm_slices(sg) : 1;
@@ -1000,9 +987,7 @@ static int run_linear(hqt_handle* h, const Mode& md, GemmArgs g, const Lin& l, i
         }
     }
     g.Bw = l.w32;
-    g.k_quarters = strncmp(tag, "gemm_", 5) == 0;          // the AR loop's nn.Linear launches (gemm_qkv / proj / fc1 / fc2 / head): see GemmArgs.k_quarters
-    if (h->gn_ready.tensor == g.C) h->gn_ready.tensor = nullptr;
-    if (exact_mfma_ok(g)) {                      // plain fp32 nn.Linear (the AR loop): the fp32 matrix instructions, one tile per wave
+    if (exact_mfma_ok(g)) {                      // the fp32 matrix instructions, one tile per wave
         if (l.w32t && g.N % 16 == 0) { g.Bw = l.w32t; g.b_tile16 = 1; }
         HIPCHK(launch_exact_mfma_gemm(g, st));
         count_variant(h, "variant:exact_mfma:%s", tag);
@@ -1061,7 +1046,7 @@ struct PackSrc { const float* w; const float* gamma; };
 static void persist_block_shapes(hqt_handle* h, const BlockW& bw, bool single_key, int cache_T, int* k4, std::vector<PersistPhase>& out, std::vector<PackSrc>& src) {
     const int D = h->cfg.embed_dim;
     PersistPhase ph{};
-    if (single_key) {        // depth sub-step 0: one query over one key -- the attention output IS the value row (run_block_dln); only [key; value] is computed
+    if (single_key) {        // depth sub-step 0: one query over one key -- the attention output IS the value row (run_block); only [key; value] is computed
         ph.type = PP_KV1; ph.N = 2 * D; ph.K = D; ph.dln = 1; ph.cache_T = cache_T; ph.kv_row = 0;
         out.push_back(ph); src.push_back({bw.qkv.w32 + (size_t)D * D, bw.ln1_g});
     } else {
@@ -1218,71 +1203,66 @@ static int run_persist(hqt_handle* h, const SampleCtx& c, const PersistProg& pr,
     return HQT_OK;
 }
 
+// The split-K slabs the last GEMM left pending go to this LayerNorm, which folds them into x before normalising
+static void take_pend(hqt_handle* h, LNArgs& ln) {
+    ln.slabs = h->pend.slabs; ln.n_slabs = h->pend.S; ln.slab_rows = h->pend.rows; ln.slab_bias = h->pend.bias;
+    h->pend = {nullptr, 0, 0, nullptr};
+}
+
 static int run_ln(hqt_handle* h, hipStream_t st, float* x, const float* g, const float* b, const float* add, void* y, int M,
                   int D, int in_rpg, int in_off, int out_dt, int out_pk) {
     Timed t(h, "layernorm", st);
-    LNArgs ln{x, g, b, add, y, M, D, in_rpg, in_off, 1e-5f, out_dt, out_pk, h->pend.slabs, h->pend.S, h->pend.rows, h->pend.bias, nullptr, 0, nullptr};
-    h->pend.slabs = nullptr; h->pend.S = 0;
+    LNArgs ln{x, g, b, add, y, M, D, in_rpg, in_off, 1e-5f, out_dt, out_pk};
+    take_pend(h, ln);
     HIPCHK(launch_layernorm(ln, st));
     return HQT_OK;
 }
 
-// One transformer block over M = B*Tq rows (stage2/layers.py:324-328,371-375)
-static int run_block(hqt_handle* h, const SampleCtx& c, const BlockW& bw, float* x, int Tq, void* kc, void* vc, int Tcache,
-                     int t_base, const int* t_base_dev, int causal) {
-    const int D = h->cfg.embed_dim, M = c.B * Tq;
-    const int adt = c.md.act_dt();
-    // FAST: GEMM A operands travel in the MFMA-fragment-packed layout when the streaming GEMM serves them
-    const int pk = (c.md.fast && M <= PACKED_MAX_ROWS && bw.qkv.wpk && bw.proj.wpk && bw.fc1.wpk && bw.fc2.wpk) ? packed_mb(M) : 0;
-    CHK(run_ln(h, c.st, x, bw.ln1_g, bw.ln1_b, nullptr, h->hbuf, M, D, 1, 0, adt, pk));
-    GemmArgs g{};
-    g.A = h->hbuf; g.M = M; g.batch = 1; g.a_packed_mb = pk;
-    g.C = h->qbuf; g.C2 = kc; g.C3 = vc; g.ldc = D; g.qkv_D = D; g.store = STORE_QKV;
-    g.rows_per_group = Tq; g.group_stride = Tcache; g.row_offset = t_base; g.row_offset_dev = t_base_dev;
-    CHK(run_linear(h, c.md, g, bw.qkv, adt, adt, c.st, "gemm_qkv"));
-    {
-        Timed t(h, "attention", c.st);
-        AttnArgs a{h->qbuf, kc, vc, h->abuf, c.B, Tq, h->cfg.n_heads, D / h->cfg.n_heads, Tcache, t_base, t_base_dev, causal, adt, pk, nullptr};
-        HIPCHK(launch_attention(a, c.st));
-    }
-    g = GemmArgs{};
-    g.A = h->abuf; g.M = M; g.batch = 1; g.a_packed_mb = pk; g.C = x; g.ldc = D; g.resid = x; g.store = STORE_ROWS;
-    CHK(run_linear(h, c.md, g, bw.proj, adt, DT_F32, c.st, "gemm_proj", true));
-    CHK(run_ln(h, c.st, x, bw.ln2_g, bw.ln2_b, nullptr, h->hbuf, M, D, 1, 0, adt, pk));
-    g = GemmArgs{};
-    g.A = h->hbuf; g.M = M; g.batch = 1; g.a_packed_mb = pk; g.C = h->mbuf; g.ldc = 4 * D;
-    g.store = pk ? STORE_PACKED : STORE_ROWS; g.c_packed_mb = pk;
-    g.act = h->cfg.gelu_approx ? ACT_GELU_SIGMOID : ACT_GELU_ERF;
-    CHK(run_linear(h, c.md, g, bw.fc1, adt, adt, c.st, "gemm_fc1"));
-    g = GemmArgs{};
-    g.A = h->mbuf; g.M = M; g.batch = 1; g.a_packed_mb = pk; g.C = x; g.ldc = D; g.resid = x; g.store = STORE_ROWS;
-    CHK(run_linear(h, c.md, g, bw.fc2, adt, DT_F32, c.st, "gemm_fc2", true));
-    return HQT_OK;
-}
+// One residual stream of the AR loop: fp32 master rows.  xpk non-null: FAST deferred LayerNorm -- the stream also keeps a bf16 packed
+// copy with *nparts partial row statistics per row in `parts`; null: classic LayerNorm launches.
+struct Resid { float* x; bf16_t* xpk; float* parts; int* nparts; };
 
-// FAST block with deferred LayerNorm (5 launches instead of 7): the residual stream is kept as an fp32 master row plus
-// a bf16 packed copy with partial row statistics; qkv / fc1 consume the copy with gamma-folded weights and normalise in
-// their epilogue, proj / fc2 update all three in theirs.  (Round 4's ninth "prefetch" wave, which touched the NEXT launch's weights
-// from inside this one, bought nothing -- profiles/r04_micro_weight_prefetch.txt -- and left with its switch in round 5.)
 static bool dln_ok(hqt_handle* h, const SampleCtx& c, const BlockW& bw, int M) {
     static const bool off = getenv("HQT_NO_DLN") != nullptr;      // debugging / A-B switch: classic LayerNorm kernels
     if (off) return false;
     return c.md.fast && M <= PACKED_MAX_ROWS && bw.qkv.wpk_ln && bw.fc1.wpk_ln && bw.proj.wpk && bw.fc2.wpk && h->cfg.embed_dim % 32 == 0;
 }
-static int run_block_dln(hqt_handle* h, const SampleCtx& c, const BlockW& bw, float* x32, bf16_t* xpk, float* parts, int* nparts,
-                         int Tq, void* kc, void* vc, int Tcache, int t_base, const int* t_base_dev, int causal) {
-    const int D = h->cfg.embed_dim, M = c.B * Tq, pk = packed_mb(M);
+
+// One transformer block over M = B*Tq rows (stage2/layers.py:324-328,371-375): qkv, attention, proj, fc1, fc2.
+// Classic: a LayerNorm launch in front of qkv and of fc1 (7 launches).  Deferred LayerNorm (5 launches): qkv / fc1 consume the packed copy of
+// the stream with gamma-folded weights and normalise in their epilogue, proj / fc2 update master rows, copy and statistics in theirs.
+// (Round 4's ninth "prefetch" wave, which touched the NEXT launch's weights from inside this one, bought nothing --
+// profiles/r04_micro_weight_prefetch.txt -- and left with its switch in round 5.)
+static int run_block(hqt_handle* h, const SampleCtx& c, const BlockW& bw, const Resid& r, int Tq, void* kc, void* vc, int Tcache,
+                     int t_base, const int* t_base_dev, int causal) {
+    const int D = h->cfg.embed_dim, M = c.B * Tq, adt = c.md.act_dt();
+    const bool dln = r.xpk != nullptr;
+    // FAST: GEMM A operands travel in the MFMA-fragment-packed layout when the streaming GEMM serves them
+    const int pk = (dln || (c.md.fast && M <= PACKED_MAX_ROWS && bw.qkv.wpk && bw.proj.wpk && bw.fc1.wpk && bw.fc2.wpk)) ? packed_mb(M) : 0;
+    // the A operand of qkv / fc1: the normalised stream
+    auto normed = [&](GemmArgs& g, const float* gamma, const float* beta, const Lin& l) -> int {
+        g.M = M; g.batch = 1; g.a_packed_mb = pk;
+        if (dln) { g.A = r.xpk; g.ln_parts = r.parts; g.ln_nparts = *r.nparts; g.ln_colsum = l.colsum; g.ln_eps = 1e-5f; return HQT_OK; }
+        g.A = h->hbuf;
+        return run_ln(h, c.st, r.x, gamma, beta, nullptr, h->hbuf, M, D, 1, 0, adt, pk);
+    };
+    // proj / fc2: x += A W^T + b
+    auto residual = [&](const void* A, const Lin& l, const char* tag) -> int {
+        GemmArgs g{};
+        g.A = A; g.M = M; g.batch = 1; g.a_packed_mb = pk; g.C = r.x; g.ldc = D;
+        if (dln) { g.store = STORE_RESID; g.resid_pk = r.xpk; g.resid_parts = r.parts; g.c_packed_mb = pk; }
+        else { g.store = STORE_ROWS; g.resid = r.x; }
+        return ar_linear(h, c.md, g, l, adt, DT_F32, c.st, tag, true, dln ? r.nparts : nullptr);
+    };
     GemmArgs g{};
-    g.A = xpk; g.M = M; g.batch = 1; g.a_packed_mb = pk;
-    g.ln_parts = parts; g.ln_nparts = *nparts; g.ln_colsum = bw.qkv.colsum; g.ln_eps = 1e-5f;
+    CHK(normed(g, bw.ln1_g, bw.ln1_b, bw.qkv));
     g.C = h->qbuf; g.C2 = kc; g.C3 = vc; g.ldc = D; g.qkv_D = D; g.store = STORE_QKV;
     g.rows_per_group = Tq; g.group_stride = Tcache; g.row_offset = t_base; g.row_offset_dev = t_base_dev;
     // One query over one key (depth sub-step 0: hierarchical_ar.py:690-702 with an empty cache): softmax of a single
     // score is exactly 1, so the attention output is the value row itself.  The GEMM then skips the query third of
     // the fused weight (rows [D, 3D) only), appends K/V to the cache for sub-step 1 and writes V straight into the
     // projection's operand; no attention launch.
-    const bool single_key = Tq == 1 && t_base == 0 && !t_base_dev && h->single_key;
-    if (single_key) {
+    if (dln && Tq == 1 && t_base == 0 && !t_base_dev && h->single_key) {
         g.qkv_first = 1; g.qkv_v_pk = reinterpret_cast<bf16_t*>(h->abuf); g.c_packed_mb = pk;
         Lin kv = bw.qkv;
         kv.N = 2 * D;
@@ -1290,30 +1270,21 @@ static int run_block_dln(hqt_handle* h, const SampleCtx& c, const BlockW& bw, fl
         kv.bias_ln = bw.qkv.bias_ln + D;
         kv.colsum = bw.qkv.colsum + D;
         g.ln_colsum = kv.colsum;
-        CHK(run_linear(h, c.md, g, kv, DT_BF16, DT_BF16, c.st, "gemm_qkv"));
+        CHK(ar_linear(h, c.md, g, kv, adt, adt, c.st, "gemm_qkv"));
     } else {
-        CHK(run_linear(h, c.md, g, bw.qkv, DT_BF16, DT_BF16, c.st, "gemm_qkv"));
+        CHK(ar_linear(h, c.md, g, bw.qkv, adt, adt, c.st, "gemm_qkv"));
         Timed t(h, "attention", c.st);
-        AttnArgs a{h->qbuf, kc, vc, h->abuf, c.B, Tq, h->cfg.n_heads, D / h->cfg.n_heads, Tcache, t_base, t_base_dev, causal, DT_BF16, pk, nullptr};
+        AttnArgs a{h->qbuf, kc, vc, h->abuf, c.B, Tq, h->cfg.n_heads, D / h->cfg.n_heads, Tcache, t_base, t_base_dev, causal, adt, pk, nullptr};
         HIPCHK(launch_attention(a, c.st));
     }
+    CHK(residual(h->abuf, bw.proj, "gemm_proj"));
     g = GemmArgs{};
-    g.A = h->abuf; g.M = M; g.batch = 1; g.a_packed_mb = pk;
-    g.C = x32; g.ldc = D; g.store = STORE_RESID; g.resid_pk = xpk; g.resid_parts = parts; g.c_packed_mb = pk;
-    CHK(run_linear(h, c.md, g, bw.proj, DT_BF16, DT_F32, c.st, "gemm_proj"));
-    *nparts = h->resid_nparts;
-    g = GemmArgs{};
-    g.A = xpk; g.M = M; g.batch = 1; g.a_packed_mb = pk;
-    g.ln_parts = parts; g.ln_nparts = *nparts; g.ln_colsum = bw.fc1.colsum; g.ln_eps = 1e-5f;
-    g.C = h->mbuf; g.ldc = 4 * D; g.store = STORE_PACKED; g.c_packed_mb = pk;
+    CHK(normed(g, bw.ln2_g, bw.ln2_b, bw.fc1));
+    g.C = h->mbuf; g.ldc = 4 * D;
+    g.store = pk ? STORE_PACKED : STORE_ROWS; g.c_packed_mb = pk;
     g.act = h->cfg.gelu_approx ? ACT_GELU_SIGMOID : ACT_GELU_ERF;
-    CHK(run_linear(h, c.md, g, bw.fc1, DT_BF16, DT_BF16, c.st, "gemm_fc1"));
-    g = GemmArgs{};
-    g.A = h->mbuf; g.M = M; g.batch = 1; g.a_packed_mb = pk;
-    g.C = x32; g.ldc = D; g.store = STORE_RESID; g.resid_pk = xpk; g.resid_parts = parts; g.c_packed_mb = pk;
-    CHK(run_linear(h, c.md, g, bw.fc2, DT_BF16, DT_F32, c.st, "gemm_fc2"));
-    *nparts = h->resid_nparts;
-    return HQT_OK;
+    CHK(ar_linear(h, c.md, g, bw.fc1, adt, adt, c.st, "gemm_fc1"));
+    return residual(h->mbuf, bw.fc2, "gemm_fc2");
 }
 
 // The body blocks of one position over Tq_body rows: as ONE persistent launch up to the top logits (pfull: two code levels, 'parallel' -- persist_build
@@ -1332,12 +1303,9 @@ static int run_body(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_b
     const bool pbody = !*pfull && body_persistable && persist_on(h, c, h->pbody);
     if (*pfull) CHK(run_persist(h, c, h->pfull, h->x, 0, tb_dev, "persist_position"));
     if (pbody) CHK(run_persist(h, c, h->pbody, h->x, 1, tb_dev, "persist_body"));
-    for (int l = 0; l < (pbody || *pfull ? 0 : cf.n_layers); ++l) {
-        void* kc = (char*)h->kcache + l * kv_layer;
-        void* vc = (char*)h->vcache + l * kv_layer;
-        if (dln_body) CHK(run_block_dln(h, c, h->body[l], h->x, h->xpk, h->parts, &h->nparts, Tq_body, kc, vc, h->Tmax, body_t_base, tb_dev, 1));
-        else CHK(run_block(h, c, h->body[l], h->x, Tq_body, kc, vc, h->Tmax, body_t_base, tb_dev, 1));
-    }
+    const Resid r{h->x, dln_body ? h->xpk : nullptr, h->parts, &h->nparts};
+    for (int l = 0; l < (pbody || *pfull ? 0 : cf.n_layers); ++l)
+        CHK(run_block(h, c, h->body[l], r, Tq_body, (char*)h->kcache + l * kv_layer, (char*)h->vcache + l * kv_layer, h->Tmax, body_t_base, tb_dev, 1));
     return HQT_OK;
 }
 
@@ -1345,12 +1313,9 @@ static int run_body(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_b
 static int run_depth(hqt_handle* h, const SampleCtx& c, bool dln, int Tq, int tbase) {
     const hqt_config& cf = h->cfg;
     const size_t dkv_layer = (size_t)cf.max_batch * h->depth_rows * cf.embed_dim * c.md.act_sz();
-    for (int l = 0; l < cf.n_layers_depth; ++l) {
-        void* kc = (char*)h->dk + l * dkv_layer;
-        void* vc = (char*)h->dv + l * dkv_layer;
-        if (dln) CHK(run_block_dln(h, c, h->depth[l], h->xd, h->xdpk, h->partsd, &h->npartsd, Tq, kc, vc, h->depth_rows, tbase, nullptr, 0));
-        else CHK(run_block(h, c, h->depth[l], h->xd, Tq, kc, vc, h->depth_rows, tbase, nullptr, 0));
-    }
+    const Resid r{h->xd, dln ? h->xdpk : nullptr, h->partsd, &h->npartsd};
+    for (int l = 0; l < cf.n_layers_depth; ++l)
+        CHK(run_block(h, c, h->depth[l], r, Tq, (char*)h->dk + l * dkv_layer, (char*)h->dv + l * dkv_layer, h->depth_rows, tbase, nullptr, 0));
     return HQT_OK;
 }
 
@@ -1374,7 +1339,7 @@ static int run_head(hqt_handle* h, const SampleCtx& c, const Lin& head, int lv, 
         g.A = normed;
     }
     g.a_packed_mb = pk; g.M = M; g.batch = 1; g.C = h->logits; g.ldc = h->cfg.vocab_top; g.store = STORE_ROWS;
-    return run_linear(h, c.md, g, head, adt, DT_F32, c.st, "gemm_head");
+    return ar_linear(h, c.md, g, head, adt, DT_F32, c.st, "gemm_head");
 }
 
 // One depth sub-step: code level lv, Tq tokens per sample at offset tbase of the depth sequence (which is also the first draw index of the
@@ -1397,8 +1362,8 @@ static int run_depth_input(hqt_handle* h, const SampleCtx& c, int sub, bool dln,
     if (sub == 0) {           // ln_f on the last token of each sample, + sos_depth (hierarchical_ar.py:561,684-686) -> depth input of level 0
         Timed t(h, "layernorm", c.st);
         LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, B, D, Tq_body, Tq_body - 1, 1e-5f, DT_F32, 0,
-                  h->pend.slabs, h->pend.S, h->pend.rows, h->pend.bias, xpk, pk, h->partsd};
-        h->pend.slabs = nullptr; h->pend.S = 0;
+                  nullptr, 0, 0, nullptr, xpk, pk, h->partsd};
+        take_pend(h, ln);
         HIPCHK(launch_layernorm(ln, c.st));
     } else if (cf.depth_decoding == HQT_DEPTH_TOP2MID2BOT) {   // the previous sub-step's code, embedded by the spatial tables, + its position in the 21-token sequence
         Timed t(h, "embed", c.st);
@@ -1455,19 +1420,18 @@ static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body
         {
             Timed t(h, "bidir_depth_input", c.st);
             LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, B, D, Tq_body, Tq_body - 1, 1e-5f, DT_F32, 0,
-                      h->pend.slabs, h->pend.S, h->pend.rows, h->pend.bias, dln ? h->xdpk : nullptr, dln ? packed_mb(M) : 0, h->partsd};
+                      nullptr, 0, 0, nullptr, dln ? h->xdpk : nullptr, dln ? packed_mb(M) : 0, h->partsd};
             ln.fill = W(h, "pos_emb_depth.weight");
-            h->pend.slabs = nullptr; h->pend.S = 0;
+            take_pend(h, ln);
             HIPCHK(launch_bidir_depth_input(ln, c.st));
             h->npartsd = 1;
         }
-        CHK(run_depth(h, c, dln, h->depth_rows, 0));      // Tq = 5 > 1: never the single-key shortcut of run_block_dln
+        CHK(run_depth(h, c, dln, h->depth_rows, 0));      // Tq = 5 > 1: never the single-key shortcut of run_block
         {   // ln_top / ln_bot of the interleaved rows into two compact operands: [B, D] (hbuf) and [4 B, D] (abuf)
             Timed t(h, "bidir_head_ln", c.st);
-            LNArgs ln{h->xd, W(h, "ln_top.weight"), W(h, "ln_top.bias"), nullptr, h->hbuf, M, D, 1, 0, 1e-5f, c.md.act_dt(), head_pk(c, h->head_top, B),
-                      h->pend.slabs, h->pend.S, h->pend.rows, h->pend.bias, nullptr, 0, nullptr};
+            LNArgs ln{h->xd, W(h, "ln_top.weight"), W(h, "ln_top.bias"), nullptr, h->hbuf, M, D, 1, 0, 1e-5f, c.md.act_dt(), head_pk(c, h->head_top, B)};
             ln.gamma2 = W(h, "ln_bot.weight"); ln.beta2 = W(h, "ln_bot.bias"); ln.y2 = h->abuf; ln.out2_packed_mb = head_pk(c, h->head_bot, 4 * B);
-            h->pend.slabs = nullptr; h->pend.S = 0;
+            take_pend(h, ln);
             HIPCHK(launch_bidir_head_ln(ln, c.st));
         }
         normed[0] = h->hbuf; normed[1] = h->abuf;
@@ -1740,15 +1704,20 @@ struct S1Ctx {
     void *cur, *t1, *t2, *tn;
     float *gn1, *gn2;
     bool cur_planes = false;   // SPLIT: `cur` already holds fp16 hi / lo operand planes (the producing conv's epilogue emitted them: GemmArgs::out_split)
+    // per-tile output statistics a 3x3 conv of this chunk left in h->gn_tiles for the GroupNorm of `tensor` (dbl: double partials, SPLIT conv)
+    struct { const void* tensor; int tiles; bool dbl; } gn_ready = {nullptr, 0, false};
 };
+
+// How the A operand of a stage-1 conv arrives: the tensor as the layer before left it (fp32, or bf16 in FAST), fp16 hi / lo planes
+// (an operand pass or the producing conv wrote them), or the fp32 tensor split by the SPLIT GEMM while it stages its tiles
+enum S1Operand { S1_TENSOR, S1_PLANES, S1_SPLIT_IN_KERNEL };
 
 // SPLIT: can conv / GEMM `g` (A = an fp32 NHWC tensor) with filters `l` run on the matrix cores?  Shapes the split kernels do
 // not take (strided taps, channel counts that are not multiples of 64, ...) fall back to the fp32 vector-ALU kernel.
 static bool split_shape_ok(const hqt_handle* h, const GemmArgs& g, const Lin& l) {
     if (!l.w16h) return false;
     GemmArgs t = g;
-    t.N = l.N; t.K = l.K; t.ldb = l.K; t.zero_page = h->zero_page; t.Bw_lo = l.w16l; t.Bw_frag16 = l.wfrag16; t.Bw_up16 = l.wup16;
-    if (t.lda == 0) t.lda = l.K;
+    lin_args(h, t, l, true);
     return t.conv_taps == 9 ? split_conv3_ok(t) : split_gemm_ok(t);
 }
 // SPLIT operand pass: fp16 hi / lo planes of (GroupNorm + swish of) the fp32 tensor g->A into `tn`; the conv then reads `tn`.
@@ -1760,8 +1729,17 @@ static int s1_split_pack(S1Ctx& c, GemmArgs* g, const float* stats, const float*
     Timed t(h, "split_pack", c.st);
     HIPCHK(launch_split_pack(reinterpret_cast<const float*>(g->A), reinterpret_cast<half_t*>(c.tn), stats, gamma, beta, rows, per, C, 32, swish, h->range_flag, c.st));
     g->A = c.tn;
-    g->Bw_lo = c.tn;                         // non-NULL marks the operand as split planes; run_linear substitutes the filter planes
     if (!g->conv_taps) g->lda = 2 * C;
+    return HQT_OK;
+}
+
+// SPLIT: GroupNorm statistics of the fp32 tensor `src`, from the per-tile sums its producing conv left or by a pass over it
+static int s1_split_stats(S1Ctx& c, const void* src, int C, int hw, float* stats) {
+    Timed t(c.h, "gn_stats", c.st);
+    if (c.gn_ready.tensor == src && c.gn_ready.dbl)
+        HIPCHK(launch_gn_finalize_tiles_d(reinterpret_cast<const double*>(c.h->gn_tiles), stats, c.n, c.gn_ready.tiles, hw, C, 32, 1e-6f, c.st));
+    else
+        HIPCHK(launch_gn_stats_fast(src, stats, c.h->gn_partial, c.n, hw, C, 32, 1e-6f, c.st, DT_F32));
     return HQT_OK;
 }
 
@@ -1771,28 +1749,24 @@ static int s1_split_pack(S1Ctx& c, GemmArgs* g, const float* stats, const float*
 // operand pass writes the normalised tensor as fp16 hi / lo planes into `tn`; shapes the split kernels do not take run
 // the EXACT way.  Sets the tensor the conv must read / fills the loader's GN fields.
 static int s1_norm(S1Ctx& c, const void* src, int C, int hw, float* stats, const float* gamma, const float* beta, int swish, GemmArgs* g,
-                   const Lin* l = nullptr) {
+                   const Lin& l, S1Operand* a) {
     hqt_handle* h = c.h;
     hipStream_t st = c.st;
+    *a = S1_TENSOR;
     if (c.md.fast) {
-        if (h->gn_ready.tensor == src && !h->gn_ready.dbl) {     // the producing conv already reduced its tiles: only the fixed-order finalize is left
+        {
             Timed t(h, "gn_stats", st);
-            HIPCHK(launch_gn_finalize_tiles(h->gn_tiles, stats, c.n, h->gn_ready.tiles, hw, C, 32, 1e-6f, st));
-        } else {
-            Timed t(h, "gn_stats", st);
-            HIPCHK(launch_gn_stats_fast(src, stats, h->gn_partial, c.n, hw, C, 32, 1e-6f, st));
+            if (c.gn_ready.tensor == src && !c.gn_ready.dbl)       // the producing conv already reduced its tiles: only the fixed-order finalize is left
+                HIPCHK(launch_gn_finalize_tiles(h->gn_tiles, stats, c.n, c.gn_ready.tiles, hw, C, 32, 1e-6f, st));
+            else
+                HIPCHK(launch_gn_stats_fast(src, stats, h->gn_partial, c.n, hw, C, 32, 1e-6f, st));
         }
         { Timed t(h, "gn_apply", st); HIPCHK(launch_gn_apply(src, c.tn, stats, gamma, beta, c.n, hw, C, 32, swish, st)); }
         g->A = c.tn;
-    } else if (c.md.split && l && split_shape_ok(h, *g, *l)) {
-        {
-            Timed t(h, "gn_stats", st);
-            if (h->gn_ready.tensor == src && h->gn_ready.dbl)
-                HIPCHK(launch_gn_finalize_tiles_d(reinterpret_cast<const double*>(h->gn_tiles), stats, c.n, h->gn_ready.tiles, hw, C, 32, 1e-6f, st));
-            else
-                HIPCHK(launch_gn_stats_fast(src, stats, h->gn_partial, c.n, hw, C, 32, 1e-6f, st, DT_F32));
-        }
+    } else if (c.md.split && split_shape_ok(h, *g, l)) {
+        CHK(s1_split_stats(c, src, C, hw, stats));
         CHK(s1_split_pack(c, g, stats, gamma, beta, swish));
+        *a = S1_PLANES;
     } else {
         { Timed t(h, "gn_stats", st); HIPCHK(launch_gn_stats(src, c.adt, stats, c.n, hw, C, 32, 1e-6f, st)); }
         with_gn(*g, stats, gamma, beta, swish);
@@ -1801,18 +1775,53 @@ static int s1_norm(S1Ctx& c, const void* src, int C, int hw, float* stats, const
 }
 // a conv without GroupNorm in front (conv_in, upsample conv, nin_shortcut, proj_out, the 1x1 convs around the quantiser): SPLIT
 // needs the operand planes, the other modes read the tensor as it is
-static int s1_plain(S1Ctx& c, GemmArgs* g, const Lin& l) {
+static int s1_plain(S1Ctx& c, GemmArgs* g, const Lin& l, S1Operand* a) {
+    *a = S1_TENSOR;
     if (!c.md.split) return HQT_OK;
     if (g->conv_taps == 1) {                 // 1x1: the GEMM kernel splits the fp32 tensor while it stages the tile -- no operand pass
         GemmArgs t = *g;
         t.a_f32 = 1;
         if (split_shape_ok(c.h, t, l)) {
-            g->a_f32 = 1; g->range_flag = c.h->range_flag;
-            g->Bw_lo = g->A;                 // non-NULL marks a SPLIT launch; run_linear substitutes the filter planes
+            g->a_f32 = 1; g->range_flag = c.h->range_flag; *a = S1_SPLIT_IN_KERNEL;
             return HQT_OK;
         }
     }
-    if (split_shape_ok(c.h, *g, l)) CHK(s1_split_pack(c, g, nullptr, nullptr, nullptr, 0));
+    if (!split_shape_ok(c.h, *g, l)) return HQT_OK;
+    *a = S1_PLANES;
+    return s1_split_pack(c, g, nullptr, nullptr, nullptr, 0);
+}
+
+// Stage 1, one convolution (or the 1x1 conv as a GEMM) of filter bank `l` over the chunk; `a`: how its A operand arrives (s1_norm / s1_plain
+// checked the shape before they chose anything but S1_TENSOR).  SPLIT kernels for planes, FAST: the MFMA / halo kernels, otherwise the fp32
+// vector-ALU kernel.  A 3x3 conv whose output is normalised next also leaves per-tile GroupNorm statistics (c.gn_ready).
+static int s1_conv(S1Ctx& c, GemmArgs g, S1Operand a, const Lin& l, int c_dt, const char* tag) {
+    hqt_handle* h = c.h;
+    lin_args(h, g, l, a != S1_TENSOR);
+    Timed t(h, SlotName(tag, g.M).s, c.st);
+    if (c.gn_ready.tensor == g.C) c.gn_ready.tensor = nullptr;          // the tensor is being overwritten
+    if (a != S1_TENSOR) {
+        if (g.conv_taps != 9) { HIPCHK(launch_split_gemm(g, c.st)); return HQT_OK; }
+        if (g.store == STORE_ROWS && h->gn_tiles && conv_halo_stats_ok(g.N, 32)) {   // every such output is normalised next
+            g.gn_part_out_d = reinterpret_cast<double*>(h->gn_tiles); g.gn_out_groups = 32;
+            c.gn_ready = {g.C, split_conv3_tiles_per_image(g), true};
+        }
+        HIPCHK(launch_split_conv3(g, c.st));
+        return HQT_OK;
+    }
+    if (c.md.fast) {
+        g.Bw = l.w16;
+        if (!mfma_gemm_ok(g, c.adt, DT_BF16, c_dt)) { HIPCHK(launch_gemm_generic(g, c.adt, DT_BF16, c_dt, c.st)); return HQT_OK; }
+        // a 3x3 halo conv also leaves per-tile GroupNorm statistics of its output
+        if (g.conv_taps == 9 && g.store == STORE_ROWS && h->gn_tiles && conv_halo_ok(g, c_dt) && conv_halo_stats_ok(g.N, 32) &&
+            !getenv("HQT_NO_FUSED_GN")) {
+            g.gn_part_out = h->gn_tiles; g.gn_out_groups = 32;
+            c.gn_ready = {g.C, conv_halo_tiles_per_image(g), false};
+        }
+        HIPCHK(launch_mfma_gemm(g, c.adt, DT_BF16, c_dt, c.st));
+        return HQT_OK;
+    }
+    g.Bw = l.w32;                                // (k_quarters stays 0: the summation order of the AR loop's nn.Linear is not a convolution's)
+    HIPCHK(launch_gemm_generic(g, DT_F32, DT_F32, DT_F32, c.st));
     return HQT_OK;
 }
 
@@ -1830,7 +1839,6 @@ static bool s1_split_product(hqt_handle* h, const Mode& md, GemmArgs& sg) {
 // kinds 0 conv3, 1 ResnetBlock, 2 AttnBlock, 3 upsample conv, 5 Downsample conv (shared by Decoder.forward and Encoder.forward)
 static int s1_layer(S1Ctx& c, const DecLayer& l, const DecLayer* next = nullptr) {
     hqt_handle* h = c.h;
-    const Mode& md = c.md;
     hipStream_t st = c.st;
     const int adt = c.adt, n = c.n;
     void *&cur = c.cur, *&t1 = c.t1, *&t2 = c.t2;
@@ -1838,85 +1846,80 @@ static int s1_layer(S1Ctx& c, const DecLayer& l, const DecLayer* next = nullptr)
     if (l.kind == 0 || l.kind == 3) {
         const int ro = l.kind == 3 ? 2 * res : res;
         GemmArgs g = conv_args(cur, n, ro, l.cin, 9, l.kind == 3, t1, l.cout);
-        if (c.cur_planes) { g.Bw_lo = g.A; c.cur_planes = false; }   // the planes are there (non-NULL Bw_lo marks a SPLIT launch; run_linear substitutes the filters)
-        else CHK(s1_plain(c, &g, l.conv1));
-        CHK(run_linear(h, md, g, l.conv1, adt, adt, st, "conv3x3"));
+        S1Operand a = S1_PLANES;
+        if (c.cur_planes) c.cur_planes = false;                      // the producing conv wrote the planes
+        else CHK(s1_plain(c, &g, l.conv1, &a));
+        CHK(s1_conv(c, g, a, l.conv1, adt, "conv3x3"));
         std::swap(cur, t1);
     } else if (l.kind == 5) {               // Downsample (stage1/modules/layers.py:56-76): pad right / bottom by one, 3x3 stride 2
         GemmArgs g = conv_args(cur, n, res / 2, l.cin, 9, 0, t1, l.cout);
         g.conv_stride2 = 1; g.conv_nopad = 1;
-        CHK(run_linear(h, md, g, l.conv1, adt, adt, st, "conv_down"));
+        CHK(s1_conv(c, g, S1_TENSOR, l.conv1, adt, "conv_down"));
         std::swap(cur, t1);
     } else if (l.kind == 1) {               // ResnetBlock (stage1/modules/layers.py:115-133)
         GemmArgs g = conv_args(cur, n, res, l.cin, 9, 0, t1, l.cout);
-        CHK(s1_norm(c, cur, l.cin, hw, c.gn1, l.n1_g, l.n1_b, 1, &g, &l.conv1));
-        CHK(run_linear(h, md, g, l.conv1, adt, adt, st, "conv3x3"));
+        S1Operand a;
+        CHK(s1_norm(c, cur, l.cin, hw, c.gn1, l.n1_g, l.n1_b, 1, &g, l.conv1, &a));
+        CHK(s1_conv(c, g, a, l.conv1, adt, "conv3x3"));
         const void* shortcut = cur;
         void* outbuf = t2;
         if (l.cin != l.cout) {
             GemmArgs sc = conv_args(cur, n, res, l.cin, 1, 0, t2, l.cout);
-            CHK(s1_plain(c, &sc, l.nin));
-            CHK(run_linear(h, md, sc, l.nin, adt, adt, st, "conv1x1"));
+            CHK(s1_plain(c, &sc, l.nin, &a));
+            CHK(s1_conv(c, sc, a, l.nin, adt, "conv1x1"));
             shortcut = t2;
             outbuf = cur;                   // x is dead once the shortcut is computed
         }
         g = conv_args(t1, n, res, l.cout, 9, 0, outbuf, l.cout);
         g.resid = shortcut;
-        CHK(s1_norm(c, t1, l.cout, hw, c.gn2, l.n2_g, l.n2_b, 1, &g, &l.conv2));
+        CHK(s1_norm(c, t1, l.cout, hw, c.gn2, l.n2_g, l.n2_b, 1, &g, l.conv2, &a));
         // SPLIT: when the block's only consumer is an upsampling conv (no GroupNorm in between) whose operand would be split by a separate pass, this conv's epilogue
         // writes the operand planes instead of the fp32 tensor (same bytes, one pass over the tensor less)
         bool planes = false;
-        if (md.split && g.Bw_lo && next && next->kind == 3 && next->cin == l.cout) {
+        if (a == S1_PLANES && next && next->kind == 3 && next->cin == l.cout) {
             GemmArgs up = conv_args(outbuf, n, 2 * res, next->cin, 9, 1, t1, next->cout);
             GemmArgs me = g;
-            me.N = l.conv2.N; me.K = l.conv2.K; me.ldb = l.conv2.K; me.zero_page = h->zero_page; me.Bw = l.conv2.w16h; me.Bw_lo = l.conv2.w16l; me.Bw_frag16 = l.conv2.wfrag16;
+            lin_args(h, me, l.conv2, true);
             planes = split_shape_ok(h, up, next->conv1) && split_conv3_emits_planes(me);
         }
         if (planes) { g.out_split = 1; g.range_flag = h->range_flag; }
-        CHK(run_linear(h, md, g, l.conv2, adt, adt, st, "conv3x3"));
+        CHK(s1_conv(c, g, a, l.conv2, adt, "conv3x3"));
         if (outbuf == t2) std::swap(cur, t2);
         c.cur_planes = planes;
         if (planes) count_variant(h, "variant:conv3x3_planes_out:conv3x3");
     } else if (l.kind == 2) {               // AttnBlock (stage1/modules/layers.py:163-186)
         const int C = l.cin;
         GemmArgs g = conv_args(cur, n, res, C, 1, 0, h->aq, C);
-        CHK(s1_norm(c, cur, C, hw, c.gn1, l.n1_g, l.n1_b, 0, &g, &l.q));
+        S1Operand a;
+        CHK(s1_norm(c, cur, C, hw, c.gn1, l.n1_g, l.n1_b, 0, &g, l.q, &a));
         const GemmArgs normed = g;           // same normalised input for q, k, v
-        CHK(run_linear(h, md, g, l.q, adt, adt, st, "conv1x1"));
+        CHK(s1_conv(c, g, a, l.q, adt, "conv1x1"));
         g = normed; g.C = h->ak;
-        CHK(run_linear(h, md, g, l.k, adt, adt, st, "conv1x1"));
+        CHK(s1_conv(c, g, a, l.k, adt, "conv1x1"));
         g = normed; g.C = h->av;
         g.store = STORE_NCHW; g.rows_per_image = hw;                 // V^T per image: [C][hw]
-        CHK(run_linear(h, md, g, l.v, adt, adt, st, "conv1x1"));
-        {   // S[i, j] = q_i . k_j * C^-0.5
+        CHK(s1_conv(c, g, a, l.v, adt, "conv1x1"));
+        // one product of two activation tensors per image: [M, K] x [N, K]^T
+        auto product = [&](const void* A, const void* B, void* out, int M, int N, int K, float alpha) -> int {
             Timed t(h, "attn_gemm", st);
             GemmArgs sg{};
-            sg.A = h->aq; sg.lda = C; sg.a_batch_stride = (long long)hw * C;
-            sg.Bw = h->ak; sg.ldb = C; sg.b_batch_stride = (long long)hw * C;
-            sg.C = h->as; sg.ldc = hw; sg.c_batch_stride = (long long)hw * hw;
-            sg.M = hw; sg.N = hw; sg.K = C; sg.batch = n; sg.alpha = 1.0f / sqrtf((float)C); sg.store = STORE_ROWS;
+            sg.A = A; sg.lda = K; sg.a_batch_stride = (long long)M * K;
+            sg.Bw = B; sg.ldb = K; sg.b_batch_stride = (long long)N * K;
+            sg.C = out; sg.ldc = N; sg.c_batch_stride = (long long)M * N;
+            sg.M = M; sg.N = N; sg.K = K; sg.batch = n; sg.alpha = alpha; sg.store = STORE_ROWS;
             sg.zero_page = h->zero_page;          // lets the LDS-DMA kernel take the batched product
-            if (md.fast && mfma_gemm_ok(sg, adt, adt, adt)) HIPCHK(launch_mfma_gemm(sg, adt, adt, adt, st));
-            else if (s1_split_product(h, md, sg)) HIPCHK(launch_split_gemm(sg, st));
+            if (c.md.fast && mfma_gemm_ok(sg, adt, adt, adt)) HIPCHK(launch_mfma_gemm(sg, adt, adt, adt, st));
+            else if (s1_split_product(h, c.md, sg)) HIPCHK(launch_split_gemm(sg, st));
             else HIPCHK(launch_gemm_generic(sg, adt, adt, adt, st));
-        }
+            return HQT_OK;
+        };
+        CHK(product(h->aq, h->ak, h->as, hw, hw, C, 1.0f / sqrtf((float)C)));      // S[i, j] = q_i . k_j * C^-0.5
         { Timed t(h, "softmax", st); HIPCHK(launch_softmax_rows(h->as, adt, n * hw, hw, st)); }
-        {   // o[i, c] = sum_j w[i, j] v[c, j]
-            Timed t(h, "attn_gemm", st);
-            GemmArgs sg{};
-            sg.A = h->as; sg.lda = hw; sg.a_batch_stride = (long long)hw * hw;
-            sg.Bw = h->av; sg.ldb = hw; sg.b_batch_stride = (long long)hw * C;
-            sg.C = h->ao; sg.ldc = C; sg.c_batch_stride = (long long)hw * C;
-            sg.M = hw; sg.N = C; sg.K = hw; sg.batch = n; sg.alpha = 1.0f; sg.store = STORE_ROWS;
-            sg.zero_page = h->zero_page;
-            if (md.fast && mfma_gemm_ok(sg, adt, adt, adt)) HIPCHK(launch_mfma_gemm(sg, adt, adt, adt, st));
-            else if (s1_split_product(h, md, sg)) HIPCHK(launch_split_gemm(sg, st));
-            else HIPCHK(launch_gemm_generic(sg, adt, adt, adt, st));
-        }
+        CHK(product(h->as, h->av, h->ao, hw, C, hw, 1.0f));                         // o[i, c] = sum_j w[i, j] v[c, j]
         g = conv_args(h->ao, n, res, C, 1, 0, t1, C);
         g.resid = cur;
-        CHK(s1_plain(c, &g, l.proj));
-        CHK(run_linear(h, md, g, l.proj, adt, adt, st, "conv1x1"));
+        CHK(s1_plain(c, &g, l.proj, &a));
+        CHK(s1_conv(c, g, a, l.proj, adt, "conv1x1"));
         std::swap(cur, t1);
     } else {
         return fail(HQT_ERR_INVALID, "s1_layer: kind %d", l.kind);
@@ -1929,7 +1932,6 @@ static int decode_chunk(hqt_handle* h, int n, const int64_t* code_t, const int64
     const hqt_config& cf = h->cfg;
     const int adt = md.act_dt();
     const int r = h->dec.front().res, E = cf.s1_embed_dim;
-    h->gn_ready.tensor = nullptr;
     const bool l3 = cf.code_levels == 3;
     {
         Timed t(h, "quant_gather", st);
@@ -1945,8 +1947,9 @@ static int decode_chunk(hqt_handle* h, int n, const int64_t* code_t, const int64
     S1Ctx c{h, n, md, st, adt, h->act[0], h->act[1], h->act[2], h->act[3], h->gn, h->gn + (size_t)h->dec_chunk * 64};
     {
         GemmArgs g = conv_args(h->quant, n, r, l3 ? E : 2 * E, 1, 0, c.cur, cf.s1_z_channels);
-        CHK(s1_plain(c, &g, h->post_quant));
-        CHK(run_linear(h, md, g, h->post_quant, adt, adt, st, "conv1x1"));
+        S1Operand a;
+        CHK(s1_plain(c, &g, h->post_quant, &a));
+        CHK(s1_conv(c, g, a, h->post_quant, adt, "conv1x1"));
     }
     for (size_t li = 0; li < h->dec.size(); ++li) {
         const DecLayer& l = h->dec[li];
@@ -1960,21 +1963,16 @@ static int decode_chunk(hqt_handle* h, int n, const int64_t* code_t, const int64
             d.N = l.conv1.N; d.K = l.conv1.K; d.Bw = l.conv1.w32; d.bias = l.conv1.b32; d.alpha = 1.0f;
             with_gn(d, c.gn1, l.n1_g, l.n1_b, 1);
             if (conv_out_direct_ok(d)) {
-                {
-                    Timed t(h, "gn_stats", st);
-                    if (h->gn_ready.tensor == c.cur && h->gn_ready.dbl)
-                        HIPCHK(launch_gn_finalize_tiles_d(reinterpret_cast<const double*>(h->gn_tiles), c.gn1, n, h->gn_ready.tiles, hw, l.cin, 32, 1e-6f, st));
-                    else
-                        HIPCHK(launch_gn_stats_fast(c.cur, c.gn1, h->gn_partial, n, hw, l.cin, 32, 1e-6f, st, DT_F32));
-                }
+                CHK(s1_split_stats(c, c.cur, l.cin, hw, c.gn1));
                 Timed t(h, "conv_out", st);
                 HIPCHK(launch_conv_out_direct(d, st));
                 count_variant(h, "variant:conv_out_direct:conv_out");
                 continue;
             }
         }
-        CHK(s1_norm(c, c.cur, l.cin, hw, c.gn1, l.n1_g, l.n1_b, 1, &g, &l.conv1));
-        CHK(run_linear(h, md, g, l.conv1, adt, DT_F32, st, "conv_out"));
+        S1Operand a;
+        CHK(s1_norm(c, c.cur, l.cin, hw, c.gn1, l.n1_g, l.n1_b, 1, &g, l.conv1, &a));
+        CHK(s1_conv(c, g, a, l.conv1, DT_F32, "conv_out"));
     }
     return HQT_OK;
 }
@@ -2024,7 +2022,6 @@ extern "C" int hqt_decode_seq_l3(hqt_handle* h, int B, const int64_t* codes0, co
 static int encode_chunk(hqt_handle* h, int n, const float* pixels, float* h_rows, const Mode& md, hipStream_t st) {
     const hqt_config& cf = h->cfg;
     const int adt = md.act_dt();
-    h->gn_ready.tensor = nullptr;
     S1Ctx c{h, n, md, st, adt, h->act[0], h->act[1], h->act[2], h->act[3], h->gn, h->gn + (size_t)h->dec_chunk * 64};
     for (auto& l : h->enc) {
         if (l.kind == 6) {                  // conv_in (layers.py:212-216): 3x3 stride 1, or 4x4 stride 2 with use_init_downsample
@@ -2032,16 +2029,17 @@ static int encode_chunk(hqt_handle* h, int n, const float* pixels, float* h_rows
             { Timed t(h, "image_layout", st); HIPCHK(launch_image_to_nhwc(pixels, c.t2, adt, n, l.res, cp, st)); }
             GemmArgs g = conv_args(c.t2, n, l.res >> down, cp, down ? 16 : 9, 0, c.t1, l.cout);
             g.conv_stride2 = down;
-            CHK(run_linear(h, md, g, l.conv1, adt, adt, st, "conv_in"));
+            CHK(s1_conv(c, g, S1_TENSOR, l.conv1, adt, "conv_in"));
             std::swap(c.cur, c.t1);
         } else if (l.kind == 7) {           // norm_out -> swish -> conv_out (layers.py:289-292), then quant_conv_b (generator.py:299) in fp32 rows
             const int hw = l.res * l.res;
             GemmArgs g = conv_args(c.cur, n, l.res, l.cin, 9, 0, c.t1, l.cout);
-            CHK(s1_norm(c, c.cur, l.cin, hw, c.gn1, l.n1_g, l.n1_b, 1, &g, &l.conv1));
-            CHK(run_linear(h, md, g, l.conv1, adt, adt, st, "conv3x3"));
+            S1Operand a;
+            CHK(s1_norm(c, c.cur, l.cin, hw, c.gn1, l.n1_g, l.n1_b, 1, &g, l.conv1, &a));
+            CHK(s1_conv(c, g, a, l.conv1, adt, "conv3x3"));
             GemmArgs q = conv_args(c.t1, n, l.res, l.cout, 1, 0, h_rows, cf.s1_embed_dim);
-            CHK(s1_plain(c, &q, h->quant_conv));
-            CHK(run_linear(h, md, q, h->quant_conv, adt, DT_F32, st, "conv1x1"));
+            CHK(s1_plain(c, &q, h->quant_conv, &a));
+            CHK(s1_conv(c, q, a, h->quant_conv, DT_F32, "conv1x1"));
         } else {
             CHK(s1_layer(c, l));
         }

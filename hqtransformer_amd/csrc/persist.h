@@ -2,7 +2,7 @@
 // (hierarchical_ar.py:561,684-686), the single-key blocks of depth sub-step 0 and head_top (three code levels: the body blocks).
 //
 // Replaces, for a batch of up to 64 samples, the launch chain of hierarchical_ar.py:554-563 / layers.py:324-328,61-195
-// (qkv -> attention -> proj -> fc1 -> fc2 per block; 5 dependent launches per block in run_block_dln) with one
+// (qkv -> attention -> proj -> fc1 -> fc2 per block; 5 dependent launches per block in run_block with deferred LayerNorm) with one
 // workgroup per CU that walks a PROGRAM of phases.  What the launch chain cannot do and this kernel does:
 //   * every CU owns a fixed column slice of every nn.Linear, and its slice of ALL weights of the program is one
 //     contiguous stream in HBM that a loader wave DMAs into an LDS ring (buffer_load ... lds), running ahead of
