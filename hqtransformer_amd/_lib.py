@@ -14,13 +14,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libhqt.so')
 CSRC = os.path.join(HERE, 'csrc')
 SOURCES = ['engine.hip', 'kernels.hip', 'fast_kernels.hip', 'persist.hip', 'tile_gemm.hip', 'exact_gemm.hip', 'mfma_gemm.hip', 'split_conv.hip', 'split_stream_conv.hip']
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 PRECISION_EXACT, PRECISION_FAST, PRECISION_SPLIT = 0, 1, 2
 PRECISIONS = {'exact': PRECISION_EXACT, 'fast': PRECISION_FAST, 'split': PRECISION_SPLIT}
 POLICY_LATENCY, POLICY_THROUGHPUT = 0, 1
 SWITCH_PERSIST, SWITCH_SINGLE_KEY, SWITCH_PERSIST_FAULT, SWITCH_SPLIT_KSLICES = 0, 1, 2, 3
 LAYOUT_FAST, LAYOUT_EXACT, LAYOUT_SPLIT, LAYOUT_ALL = 1, 2, 4, 7
+RESAMPLE_PIXELSHUFFLE, RESAMPLE_NEAREST, RESAMPLE_CONV2 = 0, 1, 2
 
 
 class HqtLibraryError(RuntimeError):
@@ -52,6 +53,7 @@ class hqt_config(C.Structure):
         ('code_levels', C.c_int32),
         ('depth_decoding', C.c_int32),
         ('ar_layouts', C.c_int32),
+        ('s1_resample', C.c_int32),
     ]
 
 

@@ -154,6 +154,10 @@ struct hqt_handle {
     float *vq_h = nullptr, *vq_recon = nullptr, *vq_zz = nullptr, *vq_err = nullptr;
     void* vq_z = nullptr;
     unsigned long long* vq_best = nullptr;
+    // ---- E-wide top level (hqt_config.s1_resample != 0: 'nearest', 'conv2')
+    float* up_table = nullptr;                // conv2: upsample_t folded over the top codebook, [n_embed][2][2][E] (launch_fold_upsample_t)
+    Lin up_lin, down_lin;                     // conv2, encode side: upsample_t as a Linear [4E, E] (launch_repack_upsample_t), down_t as a Linear [E, 4E]
+    float *vq_t = nullptr, *vq_q = nullptr;   // encode workspace: the top quantiser's input rows h_t and its straight-through rows, [B (r/2)^2, E] each
     void* act[4] = {nullptr, nullptr, nullptr, nullptr};   // 3 rotating activation buffers + the normalised/activated copy (FAST)
     double* gn_partial = nullptr;
     float* gn_tiles = nullptr;                // per-tile output statistics of the last halo conv ([image][tile][32][2]); S1Ctx::gn_ready says of which tensor
@@ -389,6 +393,9 @@ extern "C" int hqt_create(const hqt_config* cfg, int device, hqt_handle** out) {
         if (c.s1_n_mult < 1 || c.s1_n_mult > 8) return fail(HQT_ERR_INVALID, "s1_n_mult");
         if (c.s1_ch % 32) return fail(HQT_ERR_INVALID, "GroupNorm(32) needs ch %% 32 == 0");
         if (c.s1_z_channels % 16 || (2 * c.s1_embed_dim) % 16) return fail(HQT_ERR_INVALID, "z_channels and 2*embed_dim must be multiples of 16");
+        if (c.s1_resample < 0 || c.s1_resample > HQT_RESAMPLE_CONV2) return fail(HQT_ERR_INVALID, "s1_resample %d: 0 pixelshuffle, 1 nearest, 2 conv2", c.s1_resample);
+        if (c.s1_resample && c.code_levels == 3) return fail(HQT_ERR_INVALID, "s1_resample %d with three code levels: the three-level HQ-VAE is built with pixelshuffle only", c.s1_resample);
+        if (c.s1_resample == HQT_RESAMPLE_CONV2 && c.s1_embed_dim % 16) return fail(HQT_ERR_INVALID, "s1_resample 2 (conv2) needs embed_dim %% 16 == 0");
         build_decoder_plan(h.get());
         build_encoder_plan(h.get());
     }
@@ -409,6 +416,10 @@ static int alloc_encode_workspace(hqt_handle* h) {
     CHK(dev_alloc(h, (void**)&h->vq_zz, rows * 4, true));
     CHK(dev_alloc(h, (void**)&h->vq_best, rows * 8, true));
     CHK(dev_alloc(h, (void**)&h->vq_err, rows * 4 * 3, true));
+    if (c.s1_resample) {
+        CHK(dev_alloc(h, (void**)&h->vq_t, elems / 4 * 4, true));
+        CHK(dev_alloc(h, (void**)&h->vq_q, elems / 4 * 4, true));
+    }
     return HQT_OK;
 }
 
@@ -736,8 +747,15 @@ static int load_encoder(hqt_handle* h) {
     }
     const int E = c.s1_embed_dim, L = c.code_levels == 3 ? 3 : 2;
     CHK(load_conv(h, "quant_conv_b", E, c.s1_z_channels, 1, h->quant_conv));
+    if (c.s1_resample == HQT_RESAMPLE_CONV2) {     // Conv2d(E, E, 2, stride 2): [co][ci][a][b] is already the Linear [E, 4E] over pixel-unshuffled rows (k = ci * 4 + 2 a + b)
+        const float *w, *b;
+        CHK(get_w(h, "stage1.down_t.weight", {E, E, 2, 2}, &w));
+        CHK(get_w(h, "stage1.down_t.bias", {E}, &b));
+        h->down_lin = Lin();
+        h->down_lin.w32 = w; h->down_lin.b32 = b; h->down_lin.N = E; h->down_lin.K = 4 * E;
+    }
     for (int l = 0; l < L; ++l) {
-        const int dim = E << (2 * (L - 1 - l));
+        const int dim = c.s1_resample ? E : E << (2 * (L - 1 - l));
         const std::string name = L == 3 ? "stage1.quantizers." + std::to_string(l) + ".embedding"
                                         : (l == 0 ? "stage1.quantize_t.embedding" : "stage1.quantize_b.embedding");
         const float* e = h->w[name].d;
@@ -773,6 +791,7 @@ extern "C" int hqt_finalize_weights(hqt_handle* h) {
         for (auto& l : h->enc) { l.conv1 = l.conv2 = l.nin = l.q = l.k = l.v = l.proj = Lin(); }
         for (auto& p : h->cb_norm) p = nullptr;
         h->vq_h = h->vq_recon = h->vq_zz = h->vq_err = nullptr; h->vq_z = nullptr; h->vq_best = nullptr;
+        h->vq_t = h->vq_q = nullptr; h->up_table = nullptr; h->up_lin = h->down_lin = Lin();
         h->has_encoder = false;
     }
     return rc;
@@ -846,7 +865,22 @@ static int finalize_impl(hqt_handle* h) {
             CHK(get_w(h, "stage1.quantizers.2.embedding", {c.s1_n_embed, E}, &t));
             CHK(load_conv(h, "post_quant_conv_b", c.s1_z_channels, E, 1, h->post_quant));
         } else {
-            CHK(get_w(h, "stage1.quantize_t.embedding", {c.s1_n_embed, 4 * E}, &t));
+            CHK(get_w(h, "stage1.quantize_t.embedding", {c.s1_n_embed, c.s1_resample ? E : 4 * E}, &t));      // generator.py:214,231,242
+            if (c.s1_resample == HQT_RESAMPLE_CONV2) {
+                const float *uw, *ub;
+                CHK(get_w(h, "stage1.upsample_t.weight", {E, E, 2, 2}, &uw));
+                CHK(get_w(h, "stage1.upsample_t.bias", {E}, &ub));
+                // decode: q_t is always a codebook row, so the transposed conv folds into a table the size of the pixelshuffle top codebook
+                CHK(dev_alloc(h, (void**)&h->up_table, (size_t)c.s1_n_embed * 4 * E * 4, false));
+                HIPCHK(launch_fold_upsample_t(t, uw, ub, h->up_table, c.s1_n_embed, E, 0));
+                // encode: the straight-through rows are not codebook rows; there the transposed conv is a Linear [4E, E] + bias
+                float *wt, *b4;
+                CHK(dev_alloc(h, (void**)&wt, (size_t)4 * E * E * 4, false));
+                CHK(dev_alloc(h, (void**)&b4, (size_t)4 * E * 4, false));
+                HIPCHK(launch_repack_upsample_t(uw, ub, wt, b4, E, 0));
+                h->up_lin = Lin();
+                h->up_lin.w32 = wt; h->up_lin.b32 = b4; h->up_lin.N = 4 * E; h->up_lin.K = E;
+            }
             CHK(get_w(h, "stage1.quantize_b.embedding", {c.s1_n_embed, E}, &t));
             CHK(load_conv(h, "post_quant_conv_b", c.s1_z_channels, 2 * E, 1, h->post_quant));
         }
@@ -874,7 +908,9 @@ static int finalize_impl(hqt_handle* h) {
             }
         }
     }
-    if (c.has_stage1 && h->w.count("stage1.encoder.conv_in.weight")) CHK(load_encoder(h));
+    // the encode side is optional as a whole: the encoder tensors and, for conv2, down_t (decode needs neither)
+    if (c.has_stage1 && h->w.count("stage1.encoder.conv_in.weight") && (c.s1_resample != HQT_RESAMPLE_CONV2 || h->w.count("stage1.down_t.weight")))
+        CHK(load_encoder(h));
     HIPCHK(stream_gemm_configure());
     HIPCHK(tile_gemm_configure());
     HIPCHK(mfma_gemm_configure());
@@ -1939,6 +1975,11 @@ static int decode_chunk(hqt_handle* h, int n, const int64_t* code_t, const int64
             QuantArgs3 q{code_t, code_m, code_b, seq_layout, W1(h, "quantizers.0.embedding"), W1(h, "quantizers.1.embedding"),
                          W1(h, "quantizers.2.embedding"), h->quant, n, r, E, adt, cf.s1_n_embed};
             HIPCHK(launch_quant_gather3(q, st));
+        } else if (cf.s1_resample) {     // E-wide top level: the codebook itself (nearest x2) or the folded upsample_t table; a missing top level of conv2 is its bias
+            const bool conv2 = cf.s1_resample == HQT_RESAMPLE_CONV2;
+            QuantRowsArgs q{code_t, code_b, seq_layout, conv2 ? h->up_table : W1(h, "quantize_t.embedding"), conv2 ? 4 : 1,
+                            conv2 ? W1(h, "upsample_t.bias") : nullptr, W1(h, "quantize_b.embedding"), h->quant, n, r, E, adt, cf.s1_n_embed};
+            HIPCHK(launch_quant_gather_rows(q, st));
         } else {
             QuantArgs q{code_t, code_b, seq_layout, W1(h, "quantize_t.embedding"), W1(h, "quantize_b.embedding"), h->quant, n, r, E, adt, cf.s1_n_embed};
             HIPCHK(launch_quant_gather(q, st));
@@ -2047,13 +2088,61 @@ static int encode_chunk(hqt_handle* h, int n, const float* pixels, float* h_rows
     return HQT_OK;
 }
 
+// Top level of the 'nearest' / 'conv2' variants (generator.py:300-302): h_t = down_t(h_b), nearest code of the E-wide top codebook,
+// vq_recon = upsample_t(z + (e - z)) in the bottom layout.  Every product here is fp32 in every precision, like the distance GEMM:
+// they decide the codes and are under 0.1 % of an encode's FLOPs.
+static int encode_top_resampled(hqt_handle* h, int B, const hqt_encode_out* out, hipStream_t st) {
+    const hqt_config& cf = h->cfg;
+    const int r = h->dec.front().res, E = cf.s1_embed_dim, rq = r / 2, M = B * rq * rq;
+    const bool conv2 = cf.s1_resample == HQT_RESAMPLE_CONV2;
+    auto linear = [&](const float* A, const Lin& l, float* C, const char* slot) -> int {        // C[M, N] = A[M, K] W^T + b
+        Timed t(h, slot, st);
+        GemmArgs g{};
+        g.A = A; g.lda = l.K; g.M = M; g.N = l.N; g.K = l.K; g.batch = 1; g.Bw = l.w32; g.ldb = l.K; g.bias = l.b32; g.alpha = 1.0f;
+        g.C = C; g.ldc = l.N; g.store = STORE_ROWS; g.zero_page = h->zero_page;
+        HIPCHK(launch_gemm_generic(g, DT_F32, DT_F32, DT_F32, st));
+        return HQT_OK;
+    };
+    if (conv2) {      // Conv2d(k 2, stride 2) = a Linear over the pixel-unshuffled rows: the k = 1 gather of vq_rows gives exactly that column order
+        VqArgs u{};
+        u.h = h->vq_h; u.recon = nullptr; u.B = B; u.r = r; u.E = E; u.k = 1; u.z = h->vq_z; u.z_dtype = DT_F32; u.zz = h->vq_zz;
+        { Timed t(h, "vq_rows", st); HIPCHK(launch_vq_rows(u, st)); }
+        CHK(linear((const float*)h->vq_z, h->down_lin, h->vq_t, "vq_down_t"));
+    } else {
+        Timed t(h, "vq_rows", st);
+        HIPCHK(launch_vq_avgpool_rows(h->vq_h, h->vq_t, B, r, E, st));
+    }
+    HIPCHK(launch_row_sumsq(h->vq_t, DT_F32, h->vq_zz, M, E, st));
+    if (out->resid[0]) HIPCHK(launch_nhwc_to_nchw_f32(h->vq_t, out->resid[0], B, rq * rq, E, st));
+    HIPCHK(hipMemsetAsync(h->vq_best, 0xff, (size_t)M * 8, st));
+    const float* emb = W1(h, "quantize_t.embedding");
+    {
+        Timed t(h, "vq_distance", st);
+        GemmArgs g{};
+        g.A = h->vq_t; g.lda = E; g.M = M; g.N = cf.s1_n_embed; g.K = E; g.batch = 1; g.ldb = E; g.alpha = 1.0f;
+        g.store = STORE_ARGMIN; g.am_rownorm = h->vq_zz; g.am_best = h->vq_best; g.zero_page = h->zero_page;
+        g.Bw = emb; g.am_colnorm = h->cb_norm[0];
+        HIPCHK(launch_gemm_generic(g, DT_F32, DT_F32, DT_F32, st));
+    }
+    VqTopArgs a{h->vq_t, h->vq_best, emb, B, r, E, out->codes[0], out->quant[0], conv2 ? h->vq_q : nullptr, conv2 ? nullptr : h->vq_recon, h->vq_err};
+    { Timed t(h, "vq_finish", st); HIPCHK(launch_vq_finish_top(a, st)); }
+    if (conv2) {      // the straight-through rows are not codebook rows: a real [M, E] x [E, 4E] product + bias, then the 2x2 scatter (every recon element is written)
+        CHK(linear(h->vq_q, h->up_lin, (float*)h->vq_z, "vq_upsample_t"));
+        Timed t(h, "vq_finish", st);
+        HIPCHK(launch_vq_scatter_up((const float*)h->vq_z, h->vq_recon, B, r, E, st));
+    }
+    if (out->diff) HIPCHK(launch_vq_diff(h->vq_err, M, 0.25f / ((float)M * (float)E), out->diff, st));
+    return HQT_OK;
+}
+
 extern "C" int hqt_has_encoder(const hqt_handle* h) { return h ? (h->has_encoder ? 1 : 0) : -1; }
 
 extern "C" int hqt_encode(hqt_handle* h, int B, const float* pixels, int precision, const hqt_encode_out* out, void* stream) {
     if (!h || !pixels || !out) return fail(HQT_ERR_INVALID, "null argument");
     if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
     if (!h->cfg.has_stage1) return fail(HQT_ERR_STATE, "handle was created without stage 1");
-    if (!h->has_encoder) return fail(HQT_ERR_STATE, "the encoder tensors (stage1.encoder.*, stage1.quant_conv_b.*) were not set before hqt_finalize_weights");
+    if (!h->has_encoder) return fail(HQT_ERR_STATE, "the encoder tensors (stage1.encoder.*, stage1.quant_conv_b.*%s) were not set before hqt_finalize_weights",
+                                     h->cfg.s1_resample == HQT_RESAMPLE_CONV2 ? ", stage1.down_t.*" : "");
     if (B < 1 || B > h->cfg.max_batch) return fail(HQT_ERR_INVALID, "B must be in [1, max_batch = %d]", h->cfg.max_batch);
     const hqt_config& cf = h->cfg;
     const int L = cf.code_levels == 3 ? 3 : 2;
@@ -2070,6 +2159,7 @@ extern "C" int hqt_encode(hqt_handle* h, int B, const float* pixels, int precisi
     // residual quantisation, coarse -> fine, over the whole batch (generator.py:300-309 / 541-560)
     const size_t elems = (size_t)B * r * r * E;
     for (int l = 0; l < L; ++l) {
+        if (l == 0 && cf.s1_resample) { CHK(encode_top_resampled(h, B, out, st)); continue; }
         const int k = L - 1 - l, rq = r >> k, dim = E << (2 * k), M = B * rq * rq;
         const std::string name = L == 3 ? "quantizers." + std::to_string(l) + ".embedding" : (l == 0 ? "quantize_t.embedding" : "quantize_b.embedding");
         VqArgs a{};

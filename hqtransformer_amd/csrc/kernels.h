@@ -170,6 +170,30 @@ struct QuantArgs3 {
     int n_embed;
 };
 hipError_t launch_quant_gather3(const QuantArgs3& a, hipStream_t st);
+// Two-level models whose top level is E wide (hqt_config.s1_resample: 'nearest', 'conv2'; generator.py:214-219,233-242,316-318).  Both
+// halves of an output pixel are whole rows of a table:  quant[b, Y, X, 0:E] = top[(code_t[Y/2, X/2] * top_sub + sub) * E ...],
+// quant[b, Y, X, E:2E] = emb_b[code_b[Y, X] * E ...].  'nearest': top = the codebook, top_sub = 1 (every pixel of the 2x2 block reads
+// the same row).  'conv2': top = the folded table of launch_fold_upsample_t, top_sub = 4, sub = 2 (Y % 2) + X % 2.
+// A NULL code_t reads top_null (upsample_t.bias: the reference runs upsample_t over a zero quant_t) or, top_null == NULL, zeros.
+struct QuantRowsArgs {
+    const int64_t* code_t;       // grid [B, r/2, r/2] or seq [B, (r/2)^2]; NULL = top_null
+    const int64_t* code_b;       // grid [B, r, r] or seq [B, (r/2)^2, 4]; NULL = zeros
+    int seq_layout;
+    const float* top;            // [n_embed, top_sub, E]
+    int top_sub;                 // 1 or 4
+    const float* top_null;       // [E] or NULL
+    const float* emb_b;          // [n_embed, E]
+    void* quant;                 // NHWC [B, r, r, 2E]
+    int B, r, E;                 // E % 4 == 0
+    int out_dtype;
+    int n_embed;
+};
+hipError_t launch_quant_gather_rows(const QuantRowsArgs& a, hipStream_t st);
+// table[n][a][b][co] = bias[co] + sum_ci emb[n][ci] * w[ci][co][a][b]: ConvTranspose2d(E, E, 2, stride 2) (weight [in, out, kh, kw]) applied
+// to codebook row n, i.e. the four output pixels a top code expands to.  One fp32 FMA chain per entry, ci ascending, starting from the bias.
+hipError_t launch_fold_upsample_t(const float* emb, const float* w, const float* bias, float* table, int n_embed, int E, hipStream_t st);
+// wt[(a * 2 + b) * E + co][ci] = w[ci][co][a][b], bias4[(a * 2 + b) * E + co] = bias[co]: the transposed conv as a Linear with N = 4 E, K = E
+hipError_t launch_repack_upsample_t(const float* w, const float* bias, float* wt, float* bias4, int E, hipStream_t st);
 
 // GroupNorm statistics over NHWC x: stats[b][g] = (mean, rstd)
 hipError_t launch_gn_stats(const void* x, int dtype, float* stats, int B, int HW, int C, int groups, float eps,
@@ -218,6 +242,25 @@ struct VqArgs {
 };
 hipError_t launch_vq_rows(const VqArgs& a, hipStream_t st);
 hipError_t launch_vq_finish(const VqArgs& a, hipStream_t st);
+// ---- top level of the 'nearest' / 'conv2' variants (E wide; hqt_config.s1_resample).  Top rows m = (b, y, x) at resolution r / 2.
+// AvgPool2d(2) while gathering: rows[m][c] = ((h[2y, 2x] + h[2y, 2x+1]) + h[2y+1, 2x]) + h[2y+1, 2x+1]) * 0.25 (generator.py:215, 300)
+hipError_t launch_vq_avgpool_rows(const float* h, float* rows, int B, int r, int E, hipStream_t st);
+// finish pass over E-wide top rows z: codes, err_rows, quant_nchw as launch_vq_finish; the straight-through rows q = z + (e - z) go to
+// q_rows [M, E] (may be NULL) and, recon != NULL, to the four bottom pixels of the block (nearest x2: generator.py:216-219, 302)
+struct VqTopArgs {
+    const float* z;          // [M, E] the quantiser's input rows (h_t)
+    const unsigned long long* best;
+    const float* emb;        // [n_embed, E]
+    int B, r, E;             // r = bottom grid
+    int64_t* codes;          // [B, r/2, r/2]
+    float* quant_nchw;       // optional [B, E, r/2, r/2]
+    float* q_rows;           // optional [M, E]
+    float* recon;            // optional NHWC [B, r, r, E]: q replicated over the 2x2 block
+    float* err_rows;         // [M]
+};
+hipError_t launch_vq_finish_top(const VqTopArgs& a, hipStream_t st);
+// recon[b, 2y+a, 2x+b', co] = up[m][(a * 2 + b') * E + co]: the 2x2 scatter of the transposed conv's GEMM output ([M, 4E], launch_repack_upsample_t order)
+hipError_t launch_vq_scatter_up(const float* up, float* recon, int B, int r, int E, hipStream_t st);
 // diff[0] = scale * sum(err_rows[0..M)) in a fixed order (one workgroup)
 hipError_t launch_vq_diff(const float* err_rows, int M, float scale, float* diff, hipStream_t st);
 // fp32 NHWC [B, r, r, E] -> fp32 NCHW

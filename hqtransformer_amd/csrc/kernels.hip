@@ -1565,6 +1565,82 @@ hipError_t launch_quant_gather3(const QuantArgs3& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+// 'nearest' / 'conv2' top level: both halves of a pixel are contiguous E-float rows, so one lane moves one 16-byte segment
+// (4 channels) of one pixel; consecutive lanes cover consecutive segments of the 2E-channel output row.
+template <typename TO>
+__global__ __launch_bounds__(256) void quant_gather_rows_kernel(QuantRowsArgs a) {
+    const int r = a.r, rt = r / 2, E = a.E, segs = 2 * E / 4;
+    const long long n = (long long)a.B * r * r * segs;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long pix = i / segs;
+        const int c = (int)(i - pix * segs) * 4;         // first channel of this segment in [0, 2E)
+        const int b = (int)(pix / (r * r)), Y = (int)((pix / r) % r), X = (int)(pix % r);
+        const float* src = nullptr;
+        if (c < E) {
+            if (a.code_t) {
+                const long long ct = clamp_idx(a.code_t[((long long)b * rt + (Y >> 1)) * rt + (X >> 1)], a.n_embed);
+                const int sub = a.top_sub == 4 ? (Y & 1) * 2 + (X & 1) : 0;
+                src = a.top + (ct * a.top_sub + sub) * E + c;
+            } else if (a.top_null) src = a.top_null + c;
+        } else if (a.code_b) {
+            long long cb;
+            if (a.seq_layout) cb = a.code_b[(((long long)b * rt + (Y >> 1)) * rt + (X >> 1)) * 4 + (Y & 1) * 2 + (X & 1)];
+            else cb = a.code_b[((long long)b * r + Y) * r + X];
+            src = a.emb_b + clamp_idx(cb, a.n_embed) * E + (c - E);
+        }
+        const float4 v = src ? *reinterpret_cast<const float4*>(src) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        TO* out = reinterpret_cast<TO*>(a.quant) + pix * 2 * E + c;
+        if constexpr (sizeof(TO) == 4) *reinterpret_cast<float4*>(out) = v;
+        else {
+            uint2 pk;
+            pk.x = (unsigned)f32_to_bf16(v.x) | ((unsigned)f32_to_bf16(v.y) << 16);
+            pk.y = (unsigned)f32_to_bf16(v.z) | ((unsigned)f32_to_bf16(v.w) << 16);
+            *reinterpret_cast<uint2*>(out) = pk;
+        }
+    }
+}
+hipError_t launch_quant_gather_rows(const QuantRowsArgs& a, hipStream_t st) {
+    if (a.E % 4 || (a.top_sub != 1 && a.top_sub != 4)) return hipErrorInvalidValue;
+    const long long n = (long long)a.B * a.r * a.r * (2 * a.E / 4);
+    const int grid = (int)std::min<long long>((n + 255) / 256, 8192);
+    if (a.out_dtype == DT_BF16) quant_gather_rows_kernel<bf16_t><<<grid, 256, 0, st>>>(a);
+    else quant_gather_rows_kernel<float><<<grid, 256, 0, st>>>(a);
+    return hipGetLastError();
+}
+
+// ConvTranspose2d(E, E, 2, stride 2) of a codebook row (stride == kernel: every output pixel has exactly one input pixel).
+// Summation order of an entry: acc = bias[co]; for ci = 0 .. E-1: acc = fma(emb[n][ci], w[ci][co][a][b], acc)  (fp32, ci ascending).
+__global__ __launch_bounds__(256) void fold_upsample_t_kernel(const float* __restrict__ emb, const float* __restrict__ w, const float* __restrict__ bias,
+                                                              float* __restrict__ table, int n_embed, int E) {
+    const long long n = (long long)n_embed * 4 * E;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int co = (int)(i % E), ab = (int)((i / E) & 3);
+        const long long row = i / (4 * E);
+        const float* e = emb + row * E;
+        float acc = bias[co];
+        for (int ci = 0; ci < E; ++ci) acc = fmaf(e[ci], w[((long long)ci * E + co) * 4 + ab], acc);
+        table[i] = acc;
+    }
+}
+hipError_t launch_fold_upsample_t(const float* emb, const float* w, const float* bias, float* table, int n_embed, int E, hipStream_t st) {
+    const long long n = (long long)n_embed * 4 * E;
+    fold_upsample_t_kernel<<<(int)std::min<long long>((n + 255) / 256, 8192), 256, 0, st>>>(emb, w, bias, table, n_embed, E);
+    return hipGetLastError();
+}
+
+__global__ void repack_upsample_t_kernel(const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ wt, float* __restrict__ bias4, int E) {
+    const int n = 4 * E * E;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int ci = i % E, row = i / E, co = row % E, ab = row / E;       // wt[(ab * E + co)][ci]
+        wt[i] = w[((long long)ci * E + co) * 4 + ab];
+        if (ci == 0) bias4[row] = bias[co];
+    }
+}
+hipError_t launch_repack_upsample_t(const float* w, const float* bias, float* wt, float* bias4, int E, hipStream_t st) {
+    repack_upsample_t_kernel<<<std::min((4 * E * E + 255) / 256, 4096), 256, 0, st>>>(w, bias, wt, bias4, E);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------
 // GroupNorm statistics (32 groups, eps 1e-6; stage1/modules/layers.py:17-21), NHWC input.
 // One workgroup per (sample, group); sums in double.
@@ -1971,6 +2047,84 @@ __global__ __launch_bounds__(256) void vq_finish_kernel(VqArgs a) {
 hipError_t launch_vq_finish(const VqArgs& a, hipStream_t st) {
     const int rq = a.r >> a.k, M = a.B * rq * rq;
     vq_finish_kernel<<<M, 256, 0, st>>>(a);
+    return hipGetLastError();
+}
+
+// AvgPool2d(2) over the bottom-layout feature map, one 16-byte channel segment of one top row per lane.  Order of the four terms:
+// ((h[2y][2x] + h[2y][2x+1]) + h[2y+1][2x]) + h[2y+1][2x+1], then * 0.25 (exact): the window order of torch's avg_pool2d.
+__global__ __launch_bounds__(256) void vq_avgpool_rows_kernel(const float* __restrict__ h, float* __restrict__ rows, int B, int r, int E) {
+    const int rq = r / 2, segs = E / 4;
+    const long long n = (long long)B * rq * rq * segs;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long m = i / segs;
+        const int c = (int)(i - m * segs) * 4;
+        const int b = (int)(m / (rq * rq)), y = (int)((m / rq) % rq), x = (int)(m % rq);
+        const float* p = h + (((long long)b * r + 2 * y) * r + 2 * x) * E + c;
+        const float4 v00 = *reinterpret_cast<const float4*>(p), v01 = *reinterpret_cast<const float4*>(p + E);
+        const float4 v10 = *reinterpret_cast<const float4*>(p + (long long)r * E), v11 = *reinterpret_cast<const float4*>(p + (long long)r * E + E);
+        float4 o;
+        o.x = (((v00.x + v01.x) + v10.x) + v11.x) * 0.25f;
+        o.y = (((v00.y + v01.y) + v10.y) + v11.y) * 0.25f;
+        o.z = (((v00.z + v01.z) + v10.z) + v11.z) * 0.25f;
+        o.w = (((v00.w + v01.w) + v10.w) + v11.w) * 0.25f;
+        *reinterpret_cast<float4*>(rows + m * E + c) = o;
+    }
+}
+hipError_t launch_vq_avgpool_rows(const float* h, float* rows, int B, int r, int E, hipStream_t st) {
+    if (E % 4 || r % 2) return hipErrorInvalidValue;
+    const long long n = (long long)B * (r / 2) * (r / 2) * (E / 4);
+    vq_avgpool_rows_kernel<<<(int)std::min<long long>((n + 255) / 256, 8192), 256, 0, st>>>(h, rows, B, r, E);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void vq_finish_top_kernel(VqTopArgs a) {
+    __shared__ float sh[4];
+    const int rq = a.r / 2, E = a.E;
+    const int m = blockIdx.x;
+    const int b = m / (rq * rq), pix = m - b * rq * rq, y = pix / rq, x = pix - y * rq;
+    const long long code = (long long)(a.best[m] & 0xffffffffull);
+    if (threadIdx.x == 0) a.codes[m] = code;
+    const float* e = a.emb + code * E;
+    const float* zrow = a.z + (long long)m * E;
+    float acc = 0.0f;
+    for (int c = threadIdx.x; c < E; c += 256) {
+        const float z = zrow[c];
+        const float d = e[c] - z;
+        acc += d * d;                                        // quantizer.py:130
+        const float q = z + d;                               // quantizer.py:131: z + (z_q - z).detach()
+        if (a.quant_nchw) a.quant_nchw[((long long)b * E + c) * rq * rq + pix] = q;
+        if (a.q_rows) a.q_rows[(long long)m * E + c] = q;
+        if (a.recon) {                                       // nearest x2: bottom pixel (Y, X) reads top entry (Y / 2, X / 2)
+            float* o = a.recon + (((long long)b * a.r + 2 * y) * a.r + 2 * x) * E + c;
+            o[0] = q; o[E] = q; o[(long long)a.r * E] = q; o[(long long)a.r * E + E] = q;
+        }
+    }
+    acc = block_sum_256(acc, sh);
+    if (threadIdx.x == 0) a.err_rows[m] = acc;
+}
+hipError_t launch_vq_finish_top(const VqTopArgs& a, hipStream_t st) {
+    const int rq = a.r / 2;
+    vq_finish_top_kernel<<<a.B * rq * rq, 256, 0, st>>>(a);
+    return hipGetLastError();
+}
+
+// one 16-byte segment per lane on both sides: up row m = (b, y, x) holds the four output pixels (a, b') of its block as E-float runs
+__global__ __launch_bounds__(256) void vq_scatter_up_kernel(const float* __restrict__ up, float* __restrict__ recon, int B, int r, int E) {
+    const int rq = r / 2, segs = 4 * E / 4;
+    const long long n = (long long)B * rq * rq * segs;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long m = i / segs;
+        const int col = (int)(i - m * segs) * 4;             // (a * 2 + b') * E + co
+        const int ab = col / E, co = col - ab * E;
+        const int b = (int)(m / (rq * rq)), y = (int)((m / rq) % rq), x = (int)(m % rq);
+        const float4 v = *reinterpret_cast<const float4*>(up + m * 4 * E + col);
+        *reinterpret_cast<float4*>(recon + (((long long)b * r + 2 * y + (ab >> 1)) * r + 2 * x + (ab & 1)) * E + co) = v;
+    }
+}
+hipError_t launch_vq_scatter_up(const float* up, float* recon, int B, int r, int E, hipStream_t st) {
+    if (E % 4 || r % 2) return hipErrorInvalidValue;
+    const long long n = (long long)B * (r / 2) * (r / 2) * E;
+    vq_scatter_up_kernel<<<(int)std::min<long long>((n + 255) / 256, 8192), 256, 0, st>>>(up, recon, B, r, E);
     return hipGetLastError();
 }
 

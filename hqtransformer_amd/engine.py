@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import PRECISION_EXACT, PRECISION_FAST, hqt_config, hqt_encode_out, hqt_sample_opts, hqt_sample_opts_l3
-from .spec import DEPTH_DECODINGS, Stage1Spec, Stage2Spec
+from .spec import DEPTH_DECODINGS, STAGE1_RESAMPLES, Stage1Spec, Stage2Spec
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -48,6 +48,7 @@ def make_config(s2: Optional[Stage2Spec], s1: Optional[Stage1Spec], max_batch: i
         c.s1_n_embed, c.s1_out_ch = s1.n_embed, s1.out_ch
         c.s1_use_init_downsample, c.s1_use_mid_block, c.s1_use_attn = (int(s1.use_init_downsample), int(s1.use_mid_block),
                                                                         int(s1.use_attn))
+        c.s1_resample = STAGE1_RESAMPLES.index(getattr(s1, 'resample', 'pixelshuffle'))
     return c
 
 
@@ -372,9 +373,10 @@ class Engine:
         r, E = s1.z_res, s1.embed_dim
         o = hqt_encode_out()
         res: Dict[str, object] = {'codes': [], 'quant': [], 'resid': []}
+        wide = getattr(s1, 'resample', 'pixelshuffle') == 'pixelshuffle'      # 'nearest' / 'conv2': every level is E wide
         for l in range(L):
             k = L - 1 - l
-            rq, dim = r >> k, E * 4 ** k
+            rq, dim = r >> k, (E * 4 ** k if wide else E)
             c = torch.empty((B, rq, rq), dtype=torch.int64, device=dev)
             res['codes'].append(c)
             o.codes[l] = _ptr(c)

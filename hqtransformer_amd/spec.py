@@ -17,6 +17,9 @@ EMB_TRANSFORMER1, EMB_REDUCE = 0, 1
 # in the reference (0..3).  Two levels: 0 is iHQGPT 'parallel'; 'bidirectional' (4) is iHQGPT model_type 'bidirectional4'.
 DEPTH_DECODINGS = ('parallel-add', 'parallel', 'parallel-reduce', 'top2mid2bot', 'bidirectional')
 DEPTH_DECODINGS_L3 = DEPTH_DECODINGS[:4]
+# down_t / upsample_t pairs of the two-level HQ-VAE built here (index = hqt_config.s1_resample; generator.py:193-242, kernel size 2):
+# PixelUnshuffle / PixelShuffle, AvgPool2d / nearest x2, Conv2d(k 2, s 2) / ConvTranspose2d(k 2, s 2)
+STAGE1_RESAMPLES = ('pixelshuffle', 'nearest', 'conv2')
 
 
 @dataclass
@@ -60,13 +63,14 @@ class Stage1Spec:
     attn_resolutions: List[int]
     resolution: int
     z_channels: int
-    embed_dim: int            # bottom codebook dim; top codebook dim = 4 * embed_dim (pixelshuffle 2)
+    embed_dim: int            # bottom codebook dim; top codebook dim = 4 * embed_dim (pixelshuffle 2) or embed_dim ('nearest', 'conv2')
     n_embed: int
     out_ch: int = 3
     use_init_downsample: bool = True
     use_mid_block: bool = True
     use_attn: bool = True
     code_levels: int = 2      # 2 = SimRQGAN2Generator (concat), 3 = HQVAEGenerator (additive pixel-shuffle pyramid)
+    resample: str = 'pixelshuffle'   # down_t / upsample_t of the top level (generator.py:193-242), one of STAGE1_RESAMPLES; index = hqt_config.s1_resample
 
     @property
     def z_res(self) -> int:   # layers.py:330-331
@@ -134,8 +138,15 @@ def stage1_spec_from_config(cfg) -> Stage1Spec:
     if s1.type not in ('simrqgan2', 'hqvae'):
         raise NotImplementedError(f"stage1.type '{s1.type}': 'simrqgan2' and 'hqvae' are built")
     aux = s1.hparams_aux
-    if aux is None or aux.upsample != 'pixelshuffle' or aux.decoding_type != 'concat':
-        raise NotImplementedError('only upsample=pixelshuffle (kernel 2), decoding_type=concat is built')
+    built = "upsample = pixelshuffle, nearest (= nearest2) or conv2 (kernel size 2) with decoding_type = concat is built"
+    if aux is None or aux.upsample is None:  # the reference itself raises TypeError there (generator.py:203)
+        raise NotImplementedError(f'stage1.hparams_aux.upsample is not set: {built}')
+    resample = {'pixelshuffle': 'pixelshuffle', 'nearest': 'nearest', 'nearest2': 'nearest', 'conv2': 'conv2'}.get(aux.upsample)
+    if resample is None or aux.decoding_type != 'concat':
+        raise NotImplementedError(f"upsample '{aux.upsample}', decoding_type '{aux.decoding_type}': {built}")
+    if s1.type == 'hqvae' and resample != 'pixelshuffle':
+        raise NotImplementedError(f"stage1.type 'hqvae' (three code levels) with upsample '{aux.upsample}': three levels are built with pixelshuffle; "
+                                  "nearest and conv2 are built for 'simrqgan2'")
     code_levels = 2
     if s1.type == 'hqvae':                  # HQVAEGenerator (generator.py:451-515): additive pyramid, decoding_type is not read by decode
         code_levels = int(aux.code_levels or 2)
@@ -146,7 +157,7 @@ def stage1_spec_from_config(cfg) -> Stage1Spec:
                       attn_resolutions=list(hp.attn_resolutions), resolution=hp.resolution,
                       z_channels=hp.z_channels, embed_dim=s1.embed_dim, n_embed=s1.n_embed, out_ch=hp.out_ch,
                       use_init_downsample=bool(hp.use_init_downsample), use_mid_block=bool(hp.use_mid_block),
-                      use_attn=bool(hp.use_attn), code_levels=code_levels)
+                      use_attn=bool(hp.use_attn), code_levels=code_levels, resample=resample)
 
 
 def _block_shapes(prefix: str, D: int, out: Dict[str, Tuple[int, ...]]) -> None:
@@ -273,14 +284,19 @@ def decoder_plan(s: Stage1Spec) -> List[DecoderLayer]:
 
 
 def stage1_param_shapes(s: Stage1Spec) -> 'OrderedDict[str, Tuple[int, ...]]':
-    """Tensors ``decode_code`` reads (generator.py:312-367): two codebooks, the 1x1 post-quant conv, the decoder."""
+    """Tensors ``decode_code`` reads (generator.py:312-367): two codebooks, ``upsample_t`` where it has weights ('conv2'), the 1x1
+    post-quant conv, the decoder."""
     out: 'OrderedDict[str, Tuple[int, ...]]' = OrderedDict()
     if s.code_levels == 3:                  # HQVAEGenerator (generator.py:478-506): dims E*16, E*4, E; 1x1 conv from E channels
         for ci in range(3):
             out[f'quantizers.{ci}.embedding'] = (s.n_embed, s.embed_dim * 4 ** (2 - ci))
         out['post_quant_conv_b.weight'] = (s.z_channels, s.embed_dim, 1, 1)
     else:
-        out['quantize_t.embedding'] = (s.n_embed, s.embed_dim * 4)
+        resample = getattr(s, 'resample', 'pixelshuffle')
+        if resample == 'conv2':             # ConvTranspose2d(E, E, 2, stride 2): weight [in, out, kh, kw] (generator.py:236-240)
+            out['upsample_t.weight'] = (s.embed_dim, s.embed_dim, 2, 2)
+            out['upsample_t.bias'] = (s.embed_dim,)
+        out['quantize_t.embedding'] = (s.n_embed, s.embed_dim * (4 if resample == 'pixelshuffle' else 1))    # generator.py:214,231,242
         out['quantize_b.embedding'] = (s.n_embed, s.embed_dim)
         out['post_quant_conv_b.weight'] = (s.z_channels, 2 * s.embed_dim, 1, 1)
     out['post_quant_conv_b.bias'] = (s.z_channels,)
@@ -383,13 +399,16 @@ def stage1_encoder_param_shapes(s: Stage1Spec) -> 'OrderedDict[str, Tuple[int, .
             out['encoder.conv_out.bias'] = (l.cout,)
         else:
             _layer_shapes(l, out)
+    if getattr(s, 'resample', 'pixelshuffle') == 'conv2':     # Conv2d(E, E, 2, stride 2) (generator.py:235); upsample_t is on the decode side
+        out['down_t.weight'] = (s.embed_dim, s.embed_dim, 2, 2)
+        out['down_t.bias'] = (s.embed_dim,)
     out['quant_conv_b.weight'] = (s.embed_dim, s.z_channels, 1, 1)
     out['quant_conv_b.bias'] = (s.embed_dim,)
     return out
 
 
 def stage1_is_encoder_key(key: str) -> bool:
-    return key.startswith('encoder.') or key.startswith('quant_conv_b.')
+    return key.startswith('encoder.') or key.startswith('quant_conv_b.') or key.startswith('down_t.')
 
 
 def stage1_is_ignored(key: str) -> bool:

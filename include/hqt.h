@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define HQT_ABI_VERSION 8
+#define HQT_ABI_VERSION 9
 
 typedef enum {
     HQT_OK = 0,
@@ -71,7 +71,7 @@ typedef struct {
     int32_t cond_type;              /* HQT_COND_*  */
     int32_t embedding_type;         /* HQT_EMB_*   */
     int32_t gelu_approx;            /* hparams.gelu_use_approx */
-    /* stage 1: 'simrqgan2', upsample = pixelshuffle(2), decoding_type = concat */
+    /* stage 1: 'simrqgan2', decoding_type = concat, upsample = pixelshuffle(2) unless s1_resample (last field) says otherwise */
     int32_t has_stage1;
     int32_t s1_ch, s1_n_mult, s1_ch_mult[8];
     int32_t s1_num_res_blocks;
@@ -102,7 +102,25 @@ typedef struct {
      * hqt_sample_l3 call in a precision whose layout the handle was built without fails with HQT_ERR_STATE (EXACT without
      * HQT_LAYOUT_EXACT still runs, on the row-major fp32 weights: same results, slower below 257 rows).  Stage 1 is not affected. */
     int32_t ar_layouts;
+    /* Two-level stage 1 only (since ABI version 9): the down_t / upsample_t pair between the top and the bottom grid
+     * (hparams_aux.upsample, kernel size 2; generator.py:193-242).  0 is what every earlier version built.
+     *   HQT_RESAMPLE_PIXELSHUFFLE 0  PixelUnshuffle(2) / PixelShuffle(2); stage1.quantize_t.embedding is [n_embed, 4 E].
+     *   HQT_RESAMPLE_NEAREST      1  AvgPool2d(2) / nearest x2 ('nearest', 'nearest2'); stage1.quantize_t.embedding is [n_embed, E];
+     *                                a NULL code_t contributes zero.
+     *   HQT_RESAMPLE_CONV2        2  Conv2d(E, E, 2, stride 2) / ConvTranspose2d(E, E, 2, stride 2), both with bias ('conv2');
+     *                                stage1.quantize_t.embedding is [n_embed, E].  Further tensors: stage1.upsample_t.weight
+     *                                [E in, E out, 2, 2] and stage1.upsample_t.bias [E], needed by decode and encode (without them
+     *                                hqt_finalize_weights fails with HQT_ERR_MISSING_WEIGHT); stage1.down_t.weight [E, E, 2, 2] and
+     *                                stage1.down_t.bias [E], encode side only and optional like the encoder tensors (without them
+     *                                hqt_encode fails with HQT_ERR_STATE).  A NULL code_t is a ZERO quant_t that still passes
+     *                                through upsample_t (generator.py:339-342, 316): it contributes upsample_t.bias, not zero.
+     * With 1 and 2 both levels of hqt_encode are E wide: quant[0] / resid[0] are [B, E, r/2, r/2], resid[0] = h_t = down_t(h_b),
+     * and recon = quant_b + upsample_t(quant_t).  Three code levels take 0 only. */
+    int32_t s1_resample;
 } hqt_config;
+#define HQT_RESAMPLE_PIXELSHUFFLE 0
+#define HQT_RESAMPLE_NEAREST 1
+#define HQT_RESAMPLE_CONV2 2
 #define HQT_LAYOUT_FAST 1   /* bf16 MFMA-fragment packing (+ the LayerNorm-folded copies, the persistent chain's per-CU stream) */
 #define HQT_LAYOUT_EXACT 2  /* fragment-ordered fp32 copy (v_mfma_f32_16x16x4_f32 kernel of passes up to 256 rows) */
 #define HQT_LAYOUT_SPLIT 4  /* fp16 hi / lo planes (SPLIT precision on the stage-2 entry points) */
@@ -234,7 +252,9 @@ int hqt_decode_seq_l3(hqt_handle* h, int B, const int64_t* codes0, const int64_t
  * without them the call fails with HQT_ERR_STATE.
  *   pixels   fp32 [B, 3, R, R] NCHW (device)
  * Level index l runs coarse -> fine (two levels: 0 = top, 1 = bottom); r_l = r >> (levels - 1 - l),
- * dim_l = embed_dim * 4^(levels - 1 - l).  Every pointer of hqt_encode_out except codes[] may be NULL.
+ * dim_l = embed_dim * 4^(levels - 1 - l) (s1_resample != 0: dim_l = embed_dim on both levels, the top quantiser's input is
+ * down_t(h) and the reconstruction of the top level is upsample_t(quant_t): see hqt_config.s1_resample).  Every pointer of
+ * hqt_encode_out except codes[] may be NULL.
  *   codes[l]  int64 [B, r_l, r_l]                 (the reference returns them flattened)
  *   quant[l]  fp32 [B, dim_l, r_l, r_l]           the straight-through quantised tensor of level l (quant_t / quant_b)
  *   resid[l]  fp32 [B, dim_l, r_l, r_l]           the quantiser's input of level l (resid[1] of a two-level model is
@@ -257,7 +277,8 @@ int hqt_has_encoder(const hqt_handle* h);
 
 /* hqt_decode -- replaces SimRQGAN2Generator.decode_code (generator.py:323-367: codebook lookup
  * quantizer.py:179-186, PixelShuffle, concat, post_quant_conv_b, Decoder.forward layers.py:385-410).
- *   code_t      int64 [B, r/2, r/2] or NULL (that level contributes a zero quant, generator.py:328-358)
+ *   code_t      int64 [B, r/2, r/2] or NULL (that level contributes a zero quant, generator.py:328-358; with
+ *               s1_resample = HQT_RESAMPLE_CONV2 the zero quant still collects upsample_t.bias)
  *   code_b      int64 [B, r, r] or NULL          (r = bottom grid = resolution / 2^n_levels)
  *   out_pixels  fp32 [B, out_ch, H, W] NCHW; clamp01 != 0 fuses clamp(0.5 x + 0.5, 0, 1)
  *               (measure_throughput/__main__.py:113) into the last kernel, else raw decoder output
