@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import weakref
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -32,8 +32,8 @@ def make_config(s2: Optional[Stage2Spec], s1: Optional[Stage1Spec], max_batch: i
         c.vocab_top, c.vocab_bot, c.vocab_txt = s2.vocab_top, s2.vocab_bot, s2.vocab_txt
         c.ctx_len_img, c.ctx_len_txt, c.n_classes = s2.ctx_len_img, s2.ctx_len_txt, s2.n_classes
         c.cond_type, c.embedding_type, c.gelu_approx = s2.cond, s2.embedding, int(s2.gelu_approx)
-        c.depth_decoding = DEPTH_DECODINGS.index(getattr(s2, 'depth_decoding', 'parallel-add'))
-    if (s2 is not None and getattr(s2, 'levels', 2) == 3) or (s1 is not None and getattr(s1, 'code_levels', 2) == 3):
+        c.depth_decoding = DEPTH_DECODINGS.index(s2.depth_decoding)
+    if (s2 is not None and s2.levels == 3) or (s1 is not None and s1.code_levels == 3):
         c.code_levels = 3
     if s1 is not None:
         c.has_stage1 = 1
@@ -48,13 +48,17 @@ def make_config(s2: Optional[Stage2Spec], s1: Optional[Stage1Spec], max_batch: i
         c.s1_n_embed, c.s1_out_ch = s1.n_embed, s1.out_ch
         c.s1_use_init_downsample, c.s1_use_mid_block, c.s1_use_attn = (int(s1.use_init_downsample), int(s1.use_mid_block),
                                                                         int(s1.use_attn))
-        c.s1_resample = STAGE1_RESAMPLES.index(getattr(s1, 'resample', 'pixelshuffle'))
+        c.s1_resample = STAGE1_RESAMPLES.index(s1.resample)
     return c
 
 
 # (data_ptr, numel) -> tensor version of device tensors whose indices are known to be in range: produced by a sampler of this
 # process (any engine: the stage-2 engine's codes go to the stage-1 engine's decode) or already validated once
 _TRUSTED: Dict[tuple, tuple] = {}       # (data_ptr, shape, stride, dtype) -> (tensor version, weakref to its storage, largest valid id + 1)
+
+# what the two- and the three-level surface call their levels in messages
+_FORCE_NAMES = {2: ('force_top', 'force_bot'), 3: ('force[0]', 'force[1]', 'force[2]')}
+_CODE_NAMES = {2: ('code_t', 'code_b'), 3: ('code grid',) * 3}
 
 
 class Engine:
@@ -245,6 +249,44 @@ class Engine:
         return None
 
     # ------------------------------------------------------------------ stage 2
+    # Code levels are lists, coarse to fine; their number (2: hqt_sample, 3: hqt_sample_l3) is all that differs below.
+    def _sample_levels(self, levels: int, batch: int, cond, n_steps: int, *, precision, top_k, top_p, temperature, noise, seed, sample_offset,
+                       force: Sequence[Optional[torch.Tensor]], out: Optional[Sequence[torch.Tensor]], return_logits, use_graph,
+                       row_seeds, row_offsets) -> Tuple[List[torch.Tensor], Optional[torch.Tensor]]:
+        """Returns (codes [B, n], [B, n, 4][, [B, n, 16]], logits [n, draws, B, V] or None)."""
+        dev = self.device
+        B, V, L = int(batch), self.s2.vocab_top, int(levels)
+        draws = (4 ** L - 1) // 3                   # one draw per code of a position: 1 + 4 (+ 16)
+        shapes = [(B, n_steps) + ((4 ** l,) if l else ()) for l in range(L)]
+        o = hqt_sample_opts() if L == 2 else hqt_sample_opts_l3()
+        o.precision, o.n_steps = int(precision), int(n_steps)
+        for i in range(L):
+            k, p, t = int(top_k[i]) if top_k[i] else 0, float(top_p[i]) if top_p[i] else 0.0, float(temperature[i])
+            if L == 2:                              # hqt_sample_opts names its two levels: top_k_top, top_k_bot, ...
+                for field, v in (('top_k', k), ('top_p', p), ('temperature', t)):
+                    setattr(o, f'{field}_{("top", "bot")[i]}', v)
+            else:
+                o.top_k[i], o.top_p[i], o.temperature[i] = k, p, t
+        o.seed, o.sample_offset, o.use_graph = int(seed) & (2 ** 64 - 1), int(sample_offset), int(bool(use_graph))
+        rows = self._row_keys(o, B, row_seeds, row_offsets)
+        cond = self._prep_cond(cond, B)
+        noise = self._prep(noise, (n_steps, draws, B, V), torch.float32, 'noise')
+        force = [self._prep(f, shp, torch.int64, what, V) for f, shp, what in zip(force, shapes, _FORCE_NAMES[L])]
+        if out is None:
+            outs = [torch.empty(shp, dtype=torch.int64, device=dev) for shp in shapes]
+        else:
+            outs = [self._check_out(t, shp, torch.int64, dev, f'out[{i}]') for i, (t, shp) in enumerate(zip(out, shapes))]
+        logits = torch.empty((n_steps, draws, B, V), dtype=torch.float32, device=dev) if return_logits else None
+        fn = self.lib.hqt_sample if L == 2 else self.lib.hqt_sample_l3
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            _lib.check(fn(self.h, B, _ptr(cond), C.byref(o), _ptr(noise), *map(_ptr, force), _ptr(logits), *map(_ptr, outs), C.c_void_p(stream)))
+            self._note_split(precision, stream, ar_rows=B)        # every head runs persistently (run_position)
+        # inputs must outlive the asynchronous launches
+        self._keep = (cond, noise, force, rows)
+        self._trust(*outs, bound=max(self.s2.vocab_top, self.s2.vocab_bot))     # the sampler only writes ids inside the vocabulary
+        return outs, logits
+
     def sample(self, batch: int, cond: Optional[torch.Tensor], n_steps: int, *, precision: int = PRECISION_FAST,
                top_k: Sequence[Optional[int]] = (None, None), top_p: Sequence[Optional[float]] = (None, None),
                temperature: Sequence[float] = (1.0, 1.0), noise: Optional[torch.Tensor] = None, seed: int = 0,
@@ -252,106 +294,26 @@ class Engine:
                return_logits: bool = False, use_graph: bool = True,
                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None):
-        """``row_seeds`` / ``row_offsets`` (both or neither, ``batch`` entries): merged steps -- row b draws what the row with
+        """Two-level sampling: returns (codes_top [B, n], codes_bot [B, n, 4][, logits [n, 5, B, V]]).
+        ``row_seeds`` / ``row_offsets`` (both or neither, ``batch`` entries): merged steps -- row b draws what the row with
         global index ``row_offsets[b]`` of a call seeded ``row_seeds[b]`` draws (``hqt_sample_opts.row_seeds``)."""
-        dev = self.device
-        B, V = int(batch), self.s2.vocab_top
-        o = hqt_sample_opts()
-        o.precision, o.n_steps = int(precision), int(n_steps)
-        o.top_k_top = int(top_k[0]) if top_k[0] else 0
-        o.top_k_bot = int(top_k[1]) if top_k[1] else 0
-        o.top_p_top = float(top_p[0]) if top_p[0] else 0.0
-        o.top_p_bot = float(top_p[1]) if top_p[1] else 0.0
-        o.temperature_top, o.temperature_bot = float(temperature[0]), float(temperature[1])
-        o.seed, o.sample_offset, o.use_graph = int(seed) & (2 ** 64 - 1), int(sample_offset), int(bool(use_graph))
-        rows = self._row_keys(o, B, row_seeds, row_offsets)
-        cond = self._prep_cond(cond, B)
-        noise = self._prep(noise, (n_steps, 5, B, V), torch.float32, 'noise')
-        force_top = self._prep(force_top, (B, n_steps), torch.int64, 'force_top', V)
-        force_bot = self._prep(force_bot, (B, n_steps, 4), torch.int64, 'force_bot', V)
-        if out is None:
-            out_top = torch.empty((B, n_steps), dtype=torch.int64, device=dev)
-            out_bot = torch.empty((B, n_steps, 4), dtype=torch.int64, device=dev)
-        else:
-            if not isinstance(out, (tuple, list)) or len(out) != 2:
-                raise ValueError('out: expected a pair (codes_top [B, n_steps], codes_bot [B, n_steps, 4])')
-            out_top = self._check_out(out[0], (B, n_steps), torch.int64, dev, 'out[0]')
-            out_bot = self._check_out(out[1], (B, n_steps, 4), torch.int64, dev, 'out[1]')
-        logits = torch.empty((n_steps, 5, B, V), dtype=torch.float32, device=dev) if return_logits else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            _lib.check(self.lib.hqt_sample(self.h, B, _ptr(cond), C.byref(o), _ptr(noise), _ptr(force_top), _ptr(force_bot),
-                                           _ptr(logits), _ptr(out_top), _ptr(out_bot), C.c_void_p(stream)))
-            self._note_split(precision, stream, ar_rows=B)
-        # inputs must outlive the asynchronous launches
-        self._keep = (cond, noise, force_top, force_bot, rows)
-        self._trust(out_top, out_bot, bound=max(self.s2.vocab_top, self.s2.vocab_bot))     # the sampler only writes ids inside the vocabulary
-        if return_logits:
-            return out_top, out_bot, logits
-        return out_top, out_bot
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError('out: expected a pair (codes_top [B, n_steps], codes_bot [B, n_steps, 4])')
+        outs, logits = self._sample_levels(2, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
+                                           noise=noise, seed=seed, sample_offset=sample_offset, force=(force_top, force_bot), out=out,
+                                           return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets)
+        return (outs[0], outs[1], logits) if return_logits else (outs[0], outs[1])
 
-    # ------------------------------------------------------------------ three code levels (hqt_sample_l3 / hqt_decode_l3)
     def sample3(self, batch: int, cond: Optional[torch.Tensor], n_steps: int, *, precision: int = PRECISION_FAST,
                 top_k: Sequence[Optional[int]] = (None, None, None), top_p: Sequence[Optional[float]] = (None, None, None),
                 temperature: Sequence[float] = (1.0, 1.0, 1.0), noise: Optional[torch.Tensor] = None, seed: int = 0,
                 sample_offset: int = 0, force: Optional[Sequence[torch.Tensor]] = None, return_logits: bool = False,
                 use_graph: bool = True, row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None):
         """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]])."""
-        dev = self.device
-        B, V = int(batch), self.s2.vocab_top
-        o = hqt_sample_opts_l3()
-        o.precision, o.n_steps = int(precision), int(n_steps)
-        for i in range(3):
-            o.top_k[i] = int(top_k[i]) if top_k[i] else 0
-            o.top_p[i] = float(top_p[i]) if top_p[i] else 0.0
-            o.temperature[i] = float(temperature[i])
-        o.seed, o.sample_offset, o.use_graph = int(seed) & (2 ** 64 - 1), int(sample_offset), int(bool(use_graph))
-        rows = self._row_keys(o, B, row_seeds, row_offsets)
-        cond = self._prep_cond(cond, B)
-        noise = self._prep(noise, (n_steps, 21, B, V), torch.float32, 'noise')
-        f = [None, None, None]
-        if force is not None:
-            f = [self._prep(force[0], (B, n_steps), torch.int64, 'force[0]', V), self._prep(force[1], (B, n_steps, 4), torch.int64, 'force[1]', V),
-                 self._prep(force[2], (B, n_steps, 16), torch.int64, 'force[2]', V)]
-        outs = [torch.empty(shp, dtype=torch.int64, device=dev) for shp in ((B, n_steps), (B, n_steps, 4), (B, n_steps, 16))]
-        logits = torch.empty((n_steps, 21, B, V), dtype=torch.float32, device=dev) if return_logits else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            _lib.check(self.lib.hqt_sample_l3(self.h, B, _ptr(cond), C.byref(o), _ptr(noise), _ptr(f[0]), _ptr(f[1]), _ptr(f[2]),
-                                              _ptr(logits), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), C.c_void_p(stream)))
-            self._note_split(precision, stream, ar_rows=B)        # the three-level body runs persistently too (run_position)
-        self._keep = (cond, noise, f, rows)
-        self._trust(*outs, bound=max(self.s2.vocab_top, self.s2.vocab_bot))
-        return (outs[0], outs[1], outs[2], logits) if return_logits else tuple(outs)
-
-    def decode3(self, codes: Sequence[Optional[torch.Tensor]], *, precision: int = PRECISION_EXACT, clamp01: bool = False,
-                seq_layout: bool = False) -> torch.Tensor:
-        """``HQVAEGenerator.decode_code([t, m, b])``; ``seq_layout``: the sampler's [B, n], [B, n, 4], [B, n, 16]."""
-        dev = self.device
-        ref = next((c for c in codes if c is not None), None)
-        if ref is None or len(codes) != 3:
-            raise ValueError('decode3 takes three code tensors, at least one not None')
-        B = int(ref.shape[0])
-        r = self.s1.z_res
-        n = (r // 4) ** 2
-        want = ((B, n), (B, n, 4), (B, n, 16)) if seq_layout else ((B, r // 4, r // 4), (B, r // 2, r // 2), (B, r, r))
-        cs = []
-        for c, w in zip(codes, want):
-            if c is not None:
-                if tuple(c.shape) != w:
-                    raise ValueError(f'code grid: expected {w}, got {tuple(c.shape)}')
-                self._check_index(c, self.s1.n_embed, 'code grid')
-                c = c.to(device=dev, dtype=torch.int64).contiguous()
-            cs.append(c)
-        H = self.s1.resolution
-        out = torch.empty((B, self.s1.out_ch, H, H), dtype=torch.float32, device=dev)
-        fn = self.lib.hqt_decode_seq_l3 if seq_layout else self.lib.hqt_decode_l3
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            _lib.check(fn(self.h, B, _ptr(cs[0]), _ptr(cs[1]), _ptr(cs[2]), _ptr(out), int(clamp01), int(precision), C.c_void_p(stream)))
-            self._note_split(precision, stream)
-        self._keep_dec = cs
-        return out
+        outs, logits = self._sample_levels(3, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
+                                           noise=noise, seed=seed, sample_offset=sample_offset, force=(None,) * 3 if force is None else force,
+                                           out=None, return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets)
+        return (*outs, logits) if return_logits else tuple(outs)
 
     # ------------------------------------------------------------------ stage 1, encode side
     @property
@@ -373,7 +335,7 @@ class Engine:
         r, E = s1.z_res, s1.embed_dim
         o = hqt_encode_out()
         res: Dict[str, object] = {'codes': [], 'quant': [], 'resid': []}
-        wide = getattr(s1, 'resample', 'pixelshuffle') == 'pixelshuffle'      # 'nearest' / 'conv2': every level is E wide
+        wide = s1.resample == 'pixelshuffle'      # 'nearest' / 'conv2': every level is E wide
         for l in range(L):
             k = L - 1 - l
             rq, dim = r >> k, (E * 4 ** k if wide else E)
@@ -402,38 +364,50 @@ class Engine:
         return res
 
     # ------------------------------------------------------------------ stage 1
-    def decode(self, code_t: Optional[torch.Tensor], code_b: Optional[torch.Tensor], *, precision: int = PRECISION_EXACT,
-               clamp01: bool = False, seq_layout: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _decode_levels(self, codes: Sequence[Optional[torch.Tensor]], *, precision: int, clamp01: bool, seq_layout: bool,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Code tensors, coarse to fine (2: hqt_decode[_seq], 3: hqt_decode[_seq]_l3), at least one not None (a missing level = zero quant):
+        grids [B, r_l, r_l] or, ``seq_layout``, the sampler's [B, n], [B, n, 4][, [B, n, 16]]."""
         dev = self.device
-        ref = code_t if code_t is not None else code_b
-        if ref is None:
-            raise ValueError('code_t and code_b are both None')
-        B = int(ref.shape[0])
-        r = self.s1.z_res
+        L, r = len(codes), self.s1.z_res
+        if L not in _CODE_NAMES:
+            raise ValueError(f'two or three code levels are built, got {L}')
+        B = int(next(c for c in codes if c is not None).shape[0])
         if seq_layout:
-            want_t, want_b = (B, (r // 2) ** 2), (B, (r // 2) ** 2, 4)
+            want = [(B, (r >> (L - 1)) ** 2) + ((4 ** l,) if l else ()) for l in range(L)]
         else:
-            want_t, want_b = (B, r // 2, r // 2), (B, r, r)
-        if code_t is not None and tuple(code_t.shape) != want_t:
-            raise ValueError(f'code_t: expected {want_t}, got {tuple(code_t.shape)}')
-        if code_b is not None and tuple(code_b.shape) != want_b:
-            raise ValueError(f'code_b: expected {want_b}, got {tuple(code_b.shape)}')
-        self._check_index(code_t, self.s1.n_embed, 'code_t')
-        self._check_index(code_b, self.s1.n_embed, 'code_b')
-        code_t = None if code_t is None else code_t.to(device=dev, dtype=torch.int64).contiguous()
-        code_b = None if code_b is None else code_b.to(device=dev, dtype=torch.int64).contiguous()
+            want = [(B, r >> (L - 1 - l), r >> (L - 1 - l)) for l in range(L)]
+        for c, w, what in zip(codes, want, _CODE_NAMES[L]):
+            if c is not None and tuple(c.shape) != w:
+                raise ValueError(f'{what}: expected {w}, got {tuple(c.shape)}')
+        for c, what in zip(codes, _CODE_NAMES[L]):
+            self._check_index(c, self.s1.n_embed, what)
+        cs = [None if c is None else c.to(device=dev, dtype=torch.int64).contiguous() for c in codes]
         H = self.s1.resolution
         if out is None:
             out = torch.empty((B, self.s1.out_ch, H, H), dtype=torch.float32, device=dev)
         else:
             self._check_out(out, (B, self.s1.out_ch, H, H), torch.float32, dev, 'out')
-        fn = self.lib.hqt_decode_seq if seq_layout else self.lib.hqt_decode
+        fn = getattr(self.lib, 'hqt_decode' + ('_seq' if seq_layout else '') + ('_l3' if L == 3 else ''))
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
-            _lib.check(fn(self.h, B, _ptr(code_t), _ptr(code_b), _ptr(out), int(clamp01), int(precision), C.c_void_p(stream)))
+            _lib.check(fn(self.h, B, *map(_ptr, cs), _ptr(out), int(clamp01), int(precision), C.c_void_p(stream)))
             self._note_split(precision, stream)
-        self._keep_dec = (code_t, code_b)
+        self._keep_dec = cs
         return out
+
+    def decode(self, code_t: Optional[torch.Tensor], code_b: Optional[torch.Tensor], *, precision: int = PRECISION_EXACT,
+               clamp01: bool = False, seq_layout: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if code_t is None and code_b is None:
+            raise ValueError('code_t and code_b are both None')
+        return self._decode_levels((code_t, code_b), precision=precision, clamp01=clamp01, seq_layout=seq_layout, out=out)
+
+    def decode3(self, codes: Sequence[Optional[torch.Tensor]], *, precision: int = PRECISION_EXACT, clamp01: bool = False,
+                seq_layout: bool = False) -> torch.Tensor:
+        """``HQVAEGenerator.decode_code([t, m, b])``; ``seq_layout``: the sampler's [B, n], [B, n, 4], [B, n, 16]."""
+        if len(codes) != 3 or all(c is None for c in codes):
+            raise ValueError('decode3 takes three code tensors, at least one not None')
+        return self._decode_levels(codes, precision=precision, clamp01=clamp01, seq_layout=seq_layout)
 
     # ------------------------------------------------------------------ timing (bench.py roofline numerator)
     def timing(self, on: bool) -> None:

@@ -27,14 +27,14 @@ import torch
 
 from .config import load_config, parse_dotlist
 from .models import ImageGPT2
-from .sampling import rearrange_codes, rearrange_codes3, sampling_hqtransformer, sampling_ihqgpt
+from .pipeline import InflightSampler, decode_codes, sample_codes
 
 EXPERIMENT_DEFAULTS = dict(f=32, model='huge', d=4, c=16384, batch_size=50, n_loop=6, warmup=1, model_path='',
                            top_resolution=8, code_levels=2, decode_batch=0, decode_precision='split', seed=0, inflight=1, merge=1)
 
 
 def iterations_per_loop(batch_size: int) -> int:
-    """``n_iter_per_loop = (1000 + batch_size - 1) // batch_size`` (measure_throughput/__main__.py:76)."""
+    """``n_iter_per_loop = (1000 + batch_size - 1) // batch_size`` (measure_throughput/__main__.py:76, measure_throughput_txt/__main__.py:103)."""
     return (1000 + batch_size - 1) // batch_size
 
 
@@ -42,12 +42,28 @@ def load_model(result_path: str) -> ImageGPT2:
     return ImageGPT2(load_config(result_path))
 
 
-def main(args) -> dict:
-    torch.set_grad_enabled(False)
-    if args.code_levels not in (2, 3):
-        raise NotImplementedError('code_levels must be 2 or 3')
-    random.seed(args.seed)
-    model_ar = load_model(args.model_path)
+def report_loop(tag: str, wall_s: float, phase_s, images: int) -> tuple:
+    """The two lines of one loop; returns (whole iteration, AR loop, decode) in ms per sample."""
+    print(f'{tag} | {wall_s:.1f} s/loop (ar: {phase_s[0]:.1f}, decode: {phase_s[1]:.1f})')
+    per_image_ms = tuple(1000.0 * t / images for t in (wall_s, *phase_s))
+    print(f'{tag} | {per_image_ms[0]:.1f} ms/sample (ar: {per_image_ms[1]:.1f}, decode: {per_image_ms[2]:.1f})')
+    return per_image_ms
+
+
+def summarize(title: str, per_loop: list, warmup: int) -> dict:
+    """The summary line over the loops after the first ``warmup`` (run and dropped), and the harness's result."""
+    kept = per_loop[warmup:]
+    print('-' * 80)
+    mean_ms, mean_ar_ms, mean_dec_ms = (sum(col) / len(kept) for col in zip(*kept))
+    print(f'{title} | {mean_ms:.4f} ms/sample (ar: {mean_ar_ms:.4f}, decode: {mean_dec_ms:.4f})')
+    print('=' * 80)
+    return dict(ms_per_sample=mean_ms, ms_ar=mean_ar_ms, ms_decode=mean_dec_ms, images_per_s=1000.0 / mean_ms)
+
+
+def run_loops(args, model_ar: ImageGPT2, next_cond, sampler: dict, num_candidates: int) -> dict:
+    """The harness loop of both counterparts (measure_throughput/__main__.py:84-180, measure_throughput_txt/__main__.py:106-188).
+    ``next_cond()`` draws the next iteration's class id / prompt batch, ``sampler`` holds the sampler's keywords, ``num_candidates`` is
+    what a direct sampler call gets (a queued step always carries ``batch_size`` rows)."""
     device = torch.device('cuda')
     model_ar = model_ar.to(device)
     model_ar.eval()
@@ -57,82 +73,57 @@ def main(args) -> dict:
                                                       torch.cuda.get_device_name(device)))
     ar_size = sum(p.numel() for p in model_ar.stage2.parameters()) / (10 ** 6)
     print(f'transformer size: {ar_size:.1f}M')
-    batch_size = args.batch_size
+    batch_size, n_loop = int(args.batch_size), int(args.n_loop)
     n_iter_per_loop = iterations_per_loop(batch_size)
-    n_loop = args.n_loop
-
-    pipe = None
+    n_pos = int(args.top_resolution) * int(args.top_resolution)
     merge = max(1, int(args.merge))
+    pipe = None
     if int(args.inflight) > 1 or merge > 1:
-        from .pipeline import InflightSampler
         pipe = InflightSampler(model_ar, lanes=int(args.inflight), device=device, merge=merge, record_phases=merge > 1)
 
+    def iteration(marks):                              # marks: (AR start, AR end, decode end) events of this iteration
+        cond = next_cond()
+        if pipe is not None:
+            pipe.submit(batch_size, cond, max_seq_len=n_pos, use_fp16=True, precision=args.decode_precision, clamp01=True,
+                        phase_events=None if merge > 1 else marks, **sampler)
+            return
+        marks[0].record()
+        codes = sample_codes(model_ar.stage2, num_candidates, cond, use_fp16=True, max_seq_len=n_pos, model_stage1=None, **sampler)
+        marks[1].record()
+        _ = decode_codes(model_ar.stage1, codes, args.decode_precision, int(args.decode_batch), int(args.top_resolution))
+        marks[2].record()
+
     def loop(loop_idx: int):
-        starts = [torch.cuda.Event(enable_timing=True) for _ in range(n_iter_per_loop)]
-        middles = [torch.cuda.Event(enable_timing=True) for _ in range(n_iter_per_loop)]
-        ends = [torch.cuda.Event(enable_timing=True) for _ in range(n_iter_per_loop)]
+        marks = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) for _ in range(n_iter_per_loop)]
         torch.cuda.synchronize(device)
         t_begin = time.time()
-        for i in range(n_iter_per_loop if pipe is not None else 0):
-            pipe.submit(batch_size, random.randint(0, 999), max_seq_len=args.top_resolution * args.top_resolution, use_fp16=True,
-                        precision=args.decode_precision, clamp01=True, softmax_temperature=[1.0 for _ in range(args.code_levels)],
-                        phase_events=None if merge > 1 else (starts[i], middles[i], ends[i]))
+        for m in marks:
+            iteration(m)
         if pipe is not None:
             pipe.drain()
-        for i in range(n_iter_per_loop if (pipe is None and args.code_levels == 3) else 0):     # measure_throughput/__main__.py:116-138
-            starts[i].record()
-            codes_levels = sampling_hqtransformer(model_ar.stage2, num_candidates=batch_size, cond=random.randint(0, 999),
-                                                  top_k=[None] * 3, top_p=[None] * 3, softmax_temperature=[1.0] * 3, use_fp16=True,
-                                                  is_tqdm=False, max_seq_len=args.top_resolution * args.top_resolution, model_stage1=None)
-            middles[i].record()
-            if args.decode_batch and args.decode_batch < batch_size:
-                grids = rearrange_codes3(codes_levels, args.top_resolution)
-                pixels = torch.cat([model_ar.stage1.decode_code([g[j:j + args.decode_batch] for g in grids], precision=args.decode_precision)
-                                    for j in range(0, batch_size, args.decode_batch)], dim=0)
-                _ = (0.5 * pixels + 0.5).clamp(0, 1)
-            else:
-                _ = model_ar.stage1.decode_sequences(codes_levels, precision=args.decode_precision, clamp01=True)
-            ends[i].record()
-        for i in range(n_iter_per_loop if (pipe is None and args.code_levels == 2) else 0):
-            starts[i].record()
-            codes_t, codes_b = sampling_ihqgpt(model_ar.stage2, cond=random.randint(0, 999), num_candidates=batch_size,
-                                               top_k_top=None, top_p_top=None, top_k_bot=None, top_p_bot=None,
-                                               softmax_temperature=[1.0 for _ in range(args.code_levels)], use_fp16=True,
-                                               is_tqdm=False, max_seq_len=args.top_resolution * args.top_resolution,
-                                               model_stage1=None)
-            middles[i].record()
-            if args.decode_batch and args.decode_batch < batch_size:
-                grid_t, grid_b = rearrange_codes(codes_t, codes_b, args.top_resolution)
-                pixels = torch.cat([model_ar.stage1.decode_code(ct, cb, precision=args.decode_precision)
-                                    for ct, cb in zip(grid_t.split(args.decode_batch), grid_b.split(args.decode_batch))], dim=0)
-                _ = (0.5 * pixels + 0.5).clamp(0, 1)
-            else:      # rearranges and the clamp are folded into the decode kernels
-                _ = model_ar.stage1.decode_sequences(codes_t, codes_b, precision=args.decode_precision, clamp01=True)
-            ends[i].record()
         torch.cuda.synchronize(device)
         wall_s = time.time() - t_begin
-        model_ar.stage1.range_check()                      # SPLIT decode: raises if an activation left the fp16 range
+        model_ar.stage1.range_check()          # SPLIT decode: raises if an activation left the fp16 range
         model_ar.stage2.range_check()          # FAST AR sampling of up to 64 rows: raises if a persistent launch gave up (hqt_range_check)
-        if pipe is not None and merge > 1:                 # per pass: (AR start, AR end, decode end) on the pass's lane
-            log, pipe.phase_log = pipe.phase_log, []
-            phase_s = [sum(ev[a].elapsed_time(ev[a + 1]) for ev, _ in log) / 1000 for a in (0, 1)]
-        else:
-            marks = (starts, middles, ends)
-            phase_s = [sum(marks[a][i].elapsed_time(marks[a + 1][i]) for i in range(n_iter_per_loop)) / 1000 for a in (0, 1)]
-        tag = f'{loop_idx + 1}/{n_loop}'
-        print(f'{tag} | {wall_s:.1f} s/loop (ar: {phase_s[0]:.1f}, decode: {phase_s[1]:.1f})')
-        images = n_iter_per_loop * batch_size
-        per_image_ms = tuple(1000.0 * t / images for t in (wall_s, *phase_s))        # (whole iteration, AR loop, decode) per sample
-        print(f'{tag} | {per_image_ms[0]:.1f} ms/sample (ar: {per_image_ms[1]:.1f}, decode: {per_image_ms[2]:.1f})')
-        return per_image_ms
+        if pipe is not None and merge > 1:     # per pass: (AR start, AR end, decode end) on the pass's lane
+            marks, pipe.phase_log = [ev for ev, _ in pipe.phase_log], []
+        phase_s = [sum(m[a].elapsed_time(m[a + 1]) for m in marks) / 1000 for a in (0, 1)]
+        return report_loop(f'{loop_idx + 1}/{n_loop}', wall_s, phase_s, n_iter_per_loop * batch_size)
 
     print('-' * 80)
-    kept = [loop(k) for k in range(args.n_loop)][args.warmup:]                   # the first `warmup` loops are run and dropped
-    print('-' * 80)
-    mean_ms, mean_ar_ms, mean_dec_ms = (sum(col) / len(kept) for col in zip(*kept))
-    print(f'{title} | {mean_ms:.4f} ms/sample (ar: {mean_ar_ms:.4f}, decode: {mean_dec_ms:.4f})')
-    print('=' * 80)
-    return dict(ms_per_sample=mean_ms, ms_ar=mean_ar_ms, ms_decode=mean_dec_ms, images_per_s=1000.0 / mean_ms)
+    return summarize(title, [loop(k) for k in range(n_loop)], int(args.warmup))
+
+
+def main(args) -> dict:
+    torch.set_grad_enabled(False)
+    if args.code_levels not in (2, 3):
+        raise NotImplementedError('code_levels must be 2 or 3')
+    random.seed(args.seed)
+    model_ar = load_model(args.model_path)
+    if model_ar.stage2.spec.levels != args.code_levels:
+        raise ValueError(f'{args.model_path} has {model_ar.stage2.spec.levels} code levels, code_levels={args.code_levels}')
+    # random class, top_k = top_p = None, temperatures 1.0 (measure_throughput/__main__.py:92-104, 116-126)
+    return run_loops(args, model_ar, lambda: random.randint(0, 999), dict(softmax_temperature=[1.0] * args.code_levels), num_candidates=args.batch_size)
 
 
 if __name__ == '__main__':

@@ -23,6 +23,11 @@ from .spec import (COND_CLS, COND_TXT, stage2_unused, Stage1Spec, Stage2Spec, st
                    stage1_spec_from_config, stage2_param_shapes, stage2_spec_from_config)
 
 
+def _levels(first, second) -> list:
+    """The two public argument forms -- ``(code_t, code_b)`` and ``([t, m, b])`` (HQVAEGenerator.decode_code, generator.py:577-599) -- as one list, coarse to fine."""
+    return list(first) if isinstance(first, (list, tuple)) else [first, second]
+
+
 class _Table:
     """Stand-in for an nn.Embedding the drivers only inspect (``.weight.shape``)."""
 
@@ -211,20 +216,13 @@ class HQVAEStage1(_Stage):
         ``check_range`` (SPLIT only): True = wait for the call and raise HqtError if an activation left the fp16 range (a stream
         synchronisation: the call is then NOT asynchronous); False = stay asynchronous, the caller runs ``range_check()`` itself
         once its pipeline drains (what ``decode_sequences`` always does)."""
-        if isinstance(code_t, (list, tuple)):        # HQVAEGenerator.decode_code([t, m, b]) (generator.py:577-599)
-            codes = list(code_t)
-            ref = next(c for c in codes if c is not None)
-            prec = self._prec(precision)
-            eng = self.engine(int(ref.shape[0]), lane)
-            px = eng.decode3(codes, precision=prec, clamp01=clamp01)
-            if check_range:
-                eng.range_check()
-            return px
-        assert code_t is not None or code_b is not None
-        ref = code_t if code_t is not None else code_b
+        return self._decode(_levels(code_t, code_b), precision, clamp01, lane, seq_layout=False, check_range=check_range)
+
+    def _decode(self, codes, precision: Optional[str], clamp01: bool, lane: int, seq_layout: bool, check_range: bool) -> torch.Tensor:
+        assert any(c is not None for c in codes)
         prec = self._prec(precision)
-        eng = self.engine(int(ref.shape[0]), lane)
-        px = eng.decode(code_t, code_b, precision=prec, clamp01=clamp01)
+        eng = self.engine(int(next(c for c in codes if c is not None).shape[0]), lane)
+        px = eng._decode_levels(codes, precision=prec, clamp01=clamp01, seq_layout=seq_layout)
         if check_range:
             eng.range_check()
         return px
@@ -264,20 +262,15 @@ class HQVAEStage1(_Stage):
         """Reconstruction ``decode(encode(x))`` (the ``dec`` of ``SimRQGAN2Generator.forward`` in eval mode, generator.py:262-280;
         eval_stage1.py reads only this output)."""
         grids = self.code_grids(x, precision, lane, check_range=False)        # one check below covers both halves (same engine, same stream)
-        if self.spec.code_levels == 3:
-            return self.decode_code(list(grids), precision=precision, lane=lane, check_range=check_range)
-        return self.decode_code(grids[0], grids[1], precision=precision, lane=lane, check_range=check_range)
+        return self.decode_code(list(grids), precision=precision, lane=lane, check_range=check_range)
 
     __call__ = forward
 
     def decode_sequences(self, codes_top, codes_bot: Optional[torch.Tensor] = None, precision: Optional[str] = None,
                          clamp01: bool = False, lane: int = 0) -> torch.Tensor:
         """Decode the sampler's own outputs ([B, HW], [B, HW, 4]); the two rearranges of
-        sampling_hqmodel.py:119-120 are folded into the codebook-gather addressing."""
-        prec = self._prec(precision)
-        if isinstance(codes_top, (list, tuple)):     # three levels: [B, L], [B, L, 4], [B, L, 16]
-            return self.engine(int(codes_top[0].shape[0]), lane).decode3(list(codes_top), precision=prec, clamp01=clamp01, seq_layout=True)
-        return self.engine(int(codes_top.shape[0]), lane).decode(codes_top, codes_bot, precision=prec, clamp01=clamp01, seq_layout=True)
+        sampling_hqmodel.py:119-120 are folded into the codebook-gather addressing; three levels: one list [B, L], [B, L, 4], [B, L, 16]."""
+        return self._decode(_levels(codes_top, codes_bot), precision, clamp01, lane, seq_layout=True, check_range=False)     # never synchronises
 
 
 class ImageGPT2:

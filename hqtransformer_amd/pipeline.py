@@ -14,12 +14,51 @@ once for all of them instead of once per step.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import Any, Callable, List, NamedTuple, Optional, Tuple
 
 import torch
 
 from ._lib import POLICY_LATENCY, POLICY_THROUGHPUT
-from .sampling import sampling_hqtransformer, sampling_ihqgpt
+from .sampling import rearrange_levels, sampling_hqtransformer, sampling_ihqgpt
+
+
+# Code levels travel as one list, coarse to fine.  These are the only places that tell two levels from three: the sampler call, and the
+# (codes_top, codes_bot) shape of a result, whose second entry is a tensor (two levels) or the list of the finer levels (three).
+def sample_codes(stage2, num_candidates: int, cond, **kw) -> list:
+    """One ``sampling_ihqgpt`` / ``sampling_hqtransformer`` call (keywords of that sampler) -> its codes as a list."""
+    sampler = sampling_hqtransformer if stage2.spec.levels == 3 else sampling_ihqgpt
+    return list(sampler(stage2, num_candidates=num_candidates, cond=cond, is_tqdm=False, **kw))
+
+
+def sampler_cutoffs(levels: int, top_k, top_p) -> dict:
+    """One top-k / top-p for every level (what the reference's drivers pass), in the keywords of that level count's sampler."""
+    if levels == 3:
+        return dict(top_k=[top_k] * 3, top_p=[top_p] * 3)
+    return dict(top_k_top=top_k, top_p_top=top_p, top_k_bot=top_k, top_p_bot=top_p)
+
+
+def decode_codes(stage1, codes: list, precision: Optional[str] = None, decode_batch: int = 0, top_resolution: int = 0) -> torch.Tensor:
+    """Sampled codes -> pixels in [0, 1]: rearrange + ``decode_code`` + ``clamp(0.5 x + 0.5, 0, 1)`` of the reference's drivers, folded into
+    the decode kernels; ``decode_batch`` < B restores the reference's chunked decode of ``decode_batch`` images per call."""
+    B = int(codes[0].shape[0])
+    if decode_batch and decode_batch < B:
+        grids = rearrange_levels(codes, top_resolution)
+        pixels = torch.cat([stage1.decode_code([g[j:j + decode_batch] for g in grids], precision=precision) for j in range(0, B, decode_batch)], dim=0)
+        return (0.5 * pixels + 0.5).clamp(0, 1)
+    return stage1.decode_sequences(codes, precision=precision, clamp01=True)
+
+
+def _public(codes: list) -> tuple:
+    return codes[0], (codes[1] if len(codes) == 2 else codes[1:])
+
+
+def _levels_of(ct, cb) -> list:
+    return [ct, *cb] if isinstance(cb, (list, tuple)) else [ct, cb]
+
+
+def _rows(ct, cb, px, lo: int, n: int) -> tuple:
+    """Rows [lo, lo + n) of a pass's (codes_top, codes_bot, pixels): one step of a merged pass."""
+    return (*_public([c[lo:lo + n] for c in _levels_of(ct, cb)]), None if px is None else px[lo:lo + n])
 
 
 def _same(a, b) -> bool:
@@ -33,9 +72,25 @@ def _same(a, b) -> bool:
     return a == b
 
 
-def _settings(entry) -> tuple:
-    """What the steps of one merged pass must share: max_seq_len, use_fp16, precision, clamp01, use_graph, sampler settings."""
-    return (entry[4], entry[5], entry[6], entry[7], entry[8], {k: v for k, v in entry[11].items() if k != 'sample_offset'})
+class _Step(NamedTuple):
+    """One queued step of a merging sampler: ``submit``'s arguments and the Pending handed out for it."""
+    pending: 'Pending'
+    num_candidates: int
+    cond: Any
+    seed: Optional[int]
+    max_seq_len: int
+    use_fp16: bool
+    precision: Optional[str]
+    clamp01: bool
+    use_graph: bool
+    after: Optional[Callable]
+    order_after_current: bool
+    sample_kw: dict
+
+    def settings(self) -> tuple:
+        """What the steps of one merged pass must share."""
+        return (self.max_seq_len, self.use_fp16, self.precision, self.clamp01, self.use_graph,
+                {k: v for k, v in self.sample_kw.items() if k != 'sample_offset'})
 
 
 class Pending:
@@ -85,11 +140,11 @@ class InflightSampler:
             if decode is False or phase_events is not None or sample_kw.get('noise') is not None:
                 raise ValueError('merged steps support the plain sample + decode step only (no explicit noise, no phase events)')
             p = Pending()
-            entry = (p, num_candidates, cond, seed, max_seq_len, use_fp16, precision, clamp01, use_graph, after, order_after_current, sample_kw)
+            step = _Step(p, num_candidates, cond, seed, max_seq_len, use_fp16, precision, clamp01, use_graph, after, order_after_current, sample_kw)
             # checked HERE, before the step is queued: a mismatch raises without touching the queue (every Pending already handed out stays valid)
-            if self._queue and not _same(_settings(entry), _settings(self._queue[0])):
+            if self._queue and not _same(step.settings(), self._queue[0].settings()):
                 raise ValueError('steps merged into one pass must share max_seq_len, precision and sampler settings (flush() first to start a new pass)')
-            self._queue.append(entry)
+            self._queue.append(step)
             if len(self._queue) >= self.merge:
                 self.flush()
             return p
@@ -99,49 +154,41 @@ class InflightSampler:
 
     def flush(self) -> None:
         """Launch the queued steps (merge > 1) as one pass; their Pending objects receive (codes_top, codes_bot, pixels, done_event)."""
-        q = self._queue
+        q, self._queue = self._queue, []
         if not q:
             return
         ref = q[0]
-
-        self._queue = []
-        sizes = [e[1] for e in q]
-        kw = dict(ref[11])
-        offs = [int(e[11].get('sample_offset', 0)) for e in q]
-        kw.pop('sample_offset', None)
-        cls = getattr(self.model.stage2, 'use_cls_cond', False)
+        sizes = [e.num_candidates for e in q]
+        los = [sum(sizes[:i]) for i in range(len(q))]
+        kw = {k: v for k, v in ref.sample_kw.items() if k != 'sample_offset'}
+        offs = [int(e.sample_kw.get('sample_offset', 0)) for e in q]
         cond = None
-        if getattr(self.model.stage2, 'use_txt_cond', False):           # [n, ctx_len_txt] token ids per step
-            cond = torch.cat([torch.as_tensor(e[2]).reshape(n, -1).to('cpu', torch.int64) for e, n in zip(q, sizes)])
-        elif cls:
+        if self.model.stage2.use_txt_cond:           # [n, ctx_len_txt] token ids per step
+            cond = torch.cat([torch.as_tensor(e.cond).reshape(e.num_candidates, -1).to('cpu', torch.int64) for e in q])
+        elif self.model.stage2.use_cls_cond:
             parts = []
-            for e, n in zip(q, sizes):
-                c = torch.as_tensor(e[2]).reshape(-1).to('cpu', torch.int64)
-                parts.append(c.expand(n) if c.numel() == 1 else c)
+            for e in q:
+                c = torch.as_tensor(e.cond).reshape(-1).to('cpu', torch.int64)
+                parts.append(c.expand(e.num_candidates) if c.numel() == 1 else c)
             cond = torch.cat(parts)
-        seeds = [int(e[3]) if e[3] is not None else int(torch.randint(0, 2 ** 62, (1,)).item()) for e in q]
+        seeds = [int(e.seed) if e.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()) for e in q]
         row_seeds = [s for s, n in zip(seeds, sizes) for _ in range(n)]
         row_offsets = [o + i for o, n in zip(offs, sizes) for i in range(n)]
-        afters = [e[9] for e in q]
 
         def split_after(ct, cb, px):
-            lo = 0
-            for n, a in zip(sizes, afters):
-                if a is not None:
-                    a(ct[lo:lo + n], [c[lo:lo + n] for c in cb] if isinstance(cb, (list, tuple)) else cb[lo:lo + n], None if px is None else px[lo:lo + n])
-                lo += n
+            for e, lo in zip(q, los):
+                if e.after is not None:
+                    e.after(*_rows(ct, cb, px, lo, e.num_candidates))
         phases = None
         if self.record_phases:
             phases = tuple(torch.cuda.Event(enable_timing=True) for _ in range(3))
             self.phase_log.append((phases, sum(sizes)))
-        ct, cb, px, ev = self._launch(sum(sizes), cond, seed=seeds[0], max_seq_len=ref[4], use_fp16=ref[5], decode=True, precision=ref[6], clamp01=ref[7],
-                                      use_graph=ref[8], after=split_after if any(a is not None for a in afters) else None, phase_events=phases,
-                                      order_after_current=any(e[10] for e in q), row_seeds=row_seeds, row_offsets=row_offsets, **kw)
-        lo = 0
-        for e, n in zip(q, sizes):
-            e[0].value = (ct[lo:lo + n], [c[lo:lo + n] for c in cb] if isinstance(cb, (list, tuple)) else cb[lo:lo + n],
-                          None if px is None else px[lo:lo + n], ev)
-            lo += n
+        ct, cb, px, ev = self._launch(sum(sizes), cond, seed=seeds[0], max_seq_len=ref.max_seq_len, use_fp16=ref.use_fp16, decode=True,
+                                      precision=ref.precision, clamp01=ref.clamp01, use_graph=ref.use_graph,
+                                      after=split_after if any(e.after is not None for e in q) else None, phase_events=phases,
+                                      order_after_current=any(e.order_after_current for e in q), row_seeds=row_seeds, row_offsets=row_offsets, **kw)
+        for e, lo in zip(q, los):
+            e.pending.value = (*_rows(ct, cb, px, lo, e.num_candidates), ev)
 
     def _launch(self, num_candidates: int, cond, *, seed: Optional[int] = None, max_seq_len: int = 64, use_fp16: bool = True,
                 decode: bool = True, precision: Optional[str] = None, clamp01: bool = True, use_graph: bool = True,
@@ -164,30 +211,24 @@ class InflightSampler:
             if eng.policy != POLICY_THROUGHPUT:
                 eng.set_policy(POLICY_THROUGHPUT)
         ast = self.ar_streams[lane] if self.ar_streams else st
-        three = getattr(self.model.stage2.spec, 'levels', 2) == 3
         if ast is not st:
             ast.wait_stream(st)                      # the lane stays one in-order sequence: AR of this pass behind the lane's previous decode
         with torch.cuda.stream(ast):
             if phase_events is not None:
                 phase_events[0].record(ast)
-            if three:                                # HQTransformer: (codes0, [codes1, codes2]) keeps the 4-tuple shape of the result
-                codes = sampling_hqtransformer(self.model.stage2, num_candidates=num_candidates, cond=cond, seed=seed, max_seq_len=max_seq_len,
-                                               use_fp16=use_fp16, is_tqdm=False, use_graph=use_graph, lane=lane, precision=ar_precision, **sample_kw)
-                ct, cb = codes[0], codes[1:]
-            else:
-                ct, cb = sampling_ihqgpt(self.model.stage2, num_candidates=num_candidates, cond=cond, seed=seed, max_seq_len=max_seq_len,
-                                         use_fp16=use_fp16, is_tqdm=False, use_graph=use_graph, lane=lane, precision=ar_precision, **sample_kw)
+            codes = sample_codes(self.model.stage2, num_candidates, cond, seed=seed, max_seq_len=max_seq_len, use_fp16=use_fp16,
+                                 use_graph=use_graph, lane=lane, precision=ar_precision, **sample_kw)
             if phase_events is not None:
                 phase_events[1].record(ast)
         if ast is not st:
             st.wait_stream(ast)
-            for t in (ct, *(cb if isinstance(cb, (list, tuple)) else (cb,))):
+            for t in codes:
                 t.record_stream(st)
+        ct, cb = _public(codes)                      # the 4-tuple shape of the result, whatever the level count
         with torch.cuda.stream(st):
             px = None
             if decode:
-                px = self.model.stage1.decode_sequences([ct] + list(cb) if three else ct, None if three else cb,
-                                                        precision=precision or ('fast' if use_fp16 else 'exact'), clamp01=clamp01, lane=lane)
+                px = self.model.stage1.decode_sequences(codes, precision=precision or ('fast' if use_fp16 else 'exact'), clamp01=clamp01, lane=lane)
             if phase_events is not None:
                 phase_events[2].record(st)
             if after is not None:
@@ -196,7 +237,7 @@ class InflightSampler:
             ev.record(st)
         # the results were allocated on the lane's stream and will be read (and eventually freed) on the caller's: tell the
         # caching allocator, or it may hand the memory to the lane again while the caller's stream still reads it
-        for t in (ct, px, *(cb if isinstance(cb, (list, tuple)) else (cb,))):
+        for t in (*codes, px):
             if t is not None:
                 t.record_stream(caller)
         return ct, cb, px, ev

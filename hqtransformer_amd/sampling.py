@@ -26,6 +26,30 @@ def _precision(precision: Optional[str], use_fp16: bool) -> int:
     return PRECISIONS[precision]
 
 
+def _batch_and_cond(model, num_candidates: int, cond):
+    """``(num_candidates, cond)`` of the reference's samplers -> (B, cond tensor or None): text prompts [B, ctx_len_txt] set B themselves
+    (sampling.py:187-190); a class id is an int, one id or B ids; anything else is unconditional."""
+    if model.use_txt_cond:
+        cond = torch.as_tensor(cond)
+        if cond.dim() != 2:
+            raise ValueError('text conditioning expects cond of shape [B, ctx_len_txt]')
+        B = int(cond.shape[0])
+    else:
+        B = int(num_candidates)
+        if model.use_cls_cond:
+            if isinstance(cond, int):
+                cond = torch.full((B,), int(cond), dtype=torch.int64)
+            else:
+                cond = torch.as_tensor(cond).reshape(-1)
+                if cond.numel() == 1:
+                    cond = cond.repeat(B)
+            if int(cond.min()) < 0 or int(cond.max()) >= model.spec.n_classes:
+                raise IndexError('index out of range in self')          # what nn.Embedding raises in the reference
+        else:
+            cond = None
+    return B, cond
+
+
 @torch.no_grad()
 def sampling_ihqgpt(model,
                     num_candidates: int,
@@ -69,26 +93,9 @@ def sampling_ihqgpt(model,
     ``model.range_check()`` (``hqt_range_check``: raises ``HqtError``) once the codes are needed, as ``InflightSampler.drain`` and ``bench.py`` do.
     """
     spec = model.spec
-    if model.use_txt_cond:
-        cond = torch.as_tensor(cond)
-        if cond.dim() != 2:
-            raise ValueError('text conditioning expects cond of shape [B, ctx_len_txt]')
-        B = int(cond.shape[0])
-    else:
-        B = int(num_candidates)
-        if model.use_cls_cond:
-            if isinstance(cond, int):
-                cond = torch.full((B,), int(cond), dtype=torch.int64)
-            else:
-                cond = torch.as_tensor(cond).reshape(-1)
-                if cond.numel() == 1:
-                    cond = cond.repeat(B)
-            if int(cond.min()) < 0 or int(cond.max()) >= spec.n_classes:
-                raise IndexError('index out of range in self')          # what nn.Embedding raises in the reference
-        else:
-            cond = None
+    B, cond = _batch_and_cond(model, num_candidates, cond)
     force_top = None
-    if given_top_code is not None and getattr(spec, 'depth_decoding', '') == 'bidirectional':
+    if given_top_code is not None and spec.depth_decoding == 'bidirectional':
         # the reference passes given_top_code to the 'parallel' head only and silently ignores it here (hierarchical_ar.py:451-479)
         raise ValueError("given_top_code is not supported by the 'bidirectional' depth head (the reference ignores it)")
     if given_top_code is not None:
@@ -132,24 +139,7 @@ def sampling_hqtransformer(model,
     spec = model.spec
     if spec.levels != 3:
         raise ValueError('sampling_hqtransformer needs the three-level HQTransformer (stage2.type multilevel-hq)')
-    if model.use_txt_cond:
-        cond = torch.as_tensor(cond)
-        if cond.dim() != 2:
-            raise ValueError('text conditioning expects cond of shape [B, ctx_len_txt]')
-        B = int(cond.shape[0])
-    else:
-        B = int(num_candidates)
-        if model.use_cls_cond:
-            if isinstance(cond, int):
-                cond = torch.full((B,), int(cond), dtype=torch.int64)
-            else:
-                cond = torch.as_tensor(cond).reshape(-1)
-                if cond.numel() == 1:
-                    cond = cond.repeat(B)
-            if int(cond.min()) < 0 or int(cond.max()) >= spec.n_classes:
-                raise IndexError('index out of range in self')
-        else:
-            cond = None
+    B, cond = _batch_and_cond(model, num_candidates, cond)
     top_k = list(top_k) if top_k is not None else [None, None, None]
     top_p = list(top_p) if top_p is not None else [None, None, None]
     eng = model.engine(B, max_seq_len, lane)
@@ -160,19 +150,17 @@ def sampling_hqtransformer(model,
                             row_seeds=row_seeds, row_offsets=row_offsets))
 
 
-def rearrange_codes3(codes: List[torch.Tensor], top_resolution: int):
-    """'B (H W) -> B H W' and 'B (H W) (kerH kerW) -> B (H kerH) (W kerW)' with kerH = 2 and 4
-    (``sampling_hqmodel.py:150-153``, ``measure_throughput/__main__.py:128-130``)."""
+def rearrange_levels(codes: List[torch.Tensor], top_resolution: int) -> tuple:
+    """'B (H W) -> B H W' and, level l, 'B (H W) (kerH kerW) -> B (H kerH) (W kerW)' with kerH = kerW = 2 ** l, as pure views."""
     B, K = codes[0].shape[0], top_resolution
-    return (codes[0].reshape(B, K, K),
-            codes[1].reshape(B, K, K, 2, 2).permute(0, 1, 3, 2, 4).reshape(B, 2 * K, 2 * K),
-            codes[2].reshape(B, K, K, 4, 4).permute(0, 1, 3, 2, 4).reshape(B, 4 * K, 4 * K))
+    return tuple(c.reshape(B, K, K, 2 ** l, 2 ** l).permute(0, 1, 3, 2, 4).reshape(B, K << l, K << l) for l, c in enumerate(codes))
+
+
+def rearrange_codes3(codes: List[torch.Tensor], top_resolution: int):
+    """The three rearranges of ``sampling_hqmodel.py:150-153``, ``measure_throughput/__main__.py:128-130``."""
+    return rearrange_levels(list(codes[:3]), top_resolution)
 
 
 def rearrange_codes(codes_top: torch.Tensor, codes_bot: torch.Tensor, top_resolution: int):
-    """'B (H W) -> B H W' and 'B (H W) (kerH kerW) -> B (H kerH) (W kerW)' with kerH = kerW = 2
-    (``sampling_hqmodel.py:119-120``, ``measure_throughput/__main__.py:106-107``) as pure views."""
-    B, H = codes_top.shape[0], top_resolution
-    ct = codes_top.reshape(B, H, H)
-    cb = codes_bot.reshape(B, H, H, 2, 2).permute(0, 1, 3, 2, 4).reshape(B, 2 * H, 2 * H)
-    return ct, cb
+    """The two rearranges of ``sampling_hqmodel.py:119-120``, ``measure_throughput/__main__.py:106-107``."""
+    return rearrange_levels([codes_top, codes_bot], top_resolution)

@@ -20,27 +20,32 @@ import torch
 
 from .config import load_config
 from .models import ImageGPT2
-from .sampling import sampling_hqtransformer, sampling_ihqgpt
+from .pipeline import decode_codes, sample_codes, sampler_cutoffs
 from .utils import set_seed
 
 
-def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser()
+def common_arguments(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
+    """The arguments this driver shares with the text-to-image one (sampling_hqmodel.py:24-42, sampling_hqmodel_txt2img.py:27-42)."""
     p.add_argument('-r', '--result-path', type=str, required=True)
     p.add_argument('-m', '--model-path', type=str, default='', required=True)
     p.add_argument('--top-k', type=int, default=2048)
     p.add_argument('--top-p', type=float, default=1.0)
     p.add_argument('--temperature', type=float, default=1.0)
     p.add_argument('--temperature-decay', type=float, default=1.0)
-    p.add_argument('--batch-size', type=int, default=50)
     p.add_argument('--code-level', type=int, default=2)
     p.add_argument('--top-resolution', type=int, default=8)
     p.add_argument('--bot-resolution', type=int, default=16)
     p.add_argument('--seed', type=int, default=0)
-    p.add_argument('--num-classes', type=int, default=1000)
-    p.add_argument('--samples-per-class', type=int, default=None, help='default 50000 // num_classes')
     p.add_argument('--decode-precision', choices=['split', 'exact', 'fast'], default='split',
                    help='the reference decodes in fp32: split = fp32-accurate on the matrix cores (default), exact = fp32 vector ALUs, fast = bf16')
+    return p
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = common_arguments(argparse.ArgumentParser())
+    p.add_argument('--batch-size', type=int, default=50)
+    p.add_argument('--num-classes', type=int, default=1000)
+    p.add_argument('--samples-per-class', type=int, default=None, help='default 50000 // num_classes')
     return p
 
 
@@ -93,6 +98,18 @@ def save_pickle(fname, data):
         pickle.dump(data, fp, pickle.HIGHEST_PROTOCOL)
 
 
+def sample_pixels(model: ImageGPT2, args, num_candidates: int, cond) -> np.ndarray:
+    """One batch of either driver (sampling_hqmodel.py:101-153,201-214): ``top_k`` / ``top_p`` shared by the levels, temperatures
+    ``T * decay^level``, decode + ``clamp(0.5 x + 0.5, 0, 1)``; float32 [B, 3, H, W] in [0, 1] on the host."""
+    temps = [args.temperature * (args.temperature_decay ** i) for i in range(args.code_level)]
+    codes = sample_codes(model.stage2, num_candidates, cond, softmax_temperature=temps, use_fp16=True, max_seq_len=args.top_resolution * args.top_resolution,
+                         model_stage1=model.stage1, **sampler_cutoffs(args.code_level, args.top_k, args.top_p))
+    pixels = decode_codes(model.stage1, codes, args.decode_precision)
+    model.stage1.range_check()          # SPLIT decode: raises if an activation left the fp16 range
+    model.stage2.range_check()          # FAST AR sampling of up to 64 rows: raises if a persistent launch gave up (hqt_range_check)
+    return pixels.cpu().numpy()
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.code_level not in (2, 3):
@@ -105,25 +122,8 @@ def main(argv=None):
     for cls_idx in range(args.num_classes):
         for num_batches in range(per_class // n):
             targets = torch.ones(n, dtype=torch.long) * cls_idx
-            temps = [args.temperature * (args.temperature_decay ** i) for i in range(args.code_level)]
-            if args.code_level == 3:                 # sampling_hqmodel.py:131-153,201-214
-                codes = sampling_hqtransformer(model.stage2, cond=cls_idx, num_candidates=n, top_k=[args.top_k] * 3, top_p=[args.top_p] * 3,
-                                               softmax_temperature=temps, use_fp16=True, is_tqdm=False,
-                                               max_seq_len=args.top_resolution * args.top_resolution, model_stage1=model.stage1)
-                pixels = model.stage1.decode_sequences(codes, precision=args.decode_precision, clamp01=True)
-                model.stage1.range_check()                                  # SPLIT decode: raises if an activation left the fp16 range
-                model.stage2.range_check()          # FAST AR sampling of up to 64 rows: raises if a persistent launch gave up (hqt_range_check)
-                save_pickle(os.path.join(args.result_path, f'samples_({cls_idx + 1}_{num_batches}).pkl'), pixels.cpu().numpy())
-                np.savez(os.path.join(args.result_path, f'targets_({cls_idx + 1}_{num_batches}).npz'), targets=targets.cpu().numpy())
-                continue
-            codes_t, codes_b = sampling_ihqgpt(model.stage2, cond=cls_idx, num_candidates=n, top_k_top=args.top_k,
-                                               top_p_top=args.top_p, top_k_bot=args.top_k, top_p_bot=args.top_p,
-                                               softmax_temperature=temps, use_fp16=True, is_tqdm=False,
-                                               max_seq_len=args.top_resolution * args.top_resolution, model_stage1=model.stage1)
-            pixels = model.stage1.decode_sequences(codes_t, codes_b, precision=args.decode_precision, clamp01=True)
-            model.stage1.range_check()                                  # SPLIT decode: raises if an activation left the fp16 range
-            model.stage2.range_check()          # FAST AR sampling of up to 64 rows: raises if a persistent launch gave up (hqt_range_check)
-            save_pickle(os.path.join(args.result_path, f'samples_({cls_idx + 1}_{num_batches}).pkl'), pixels.cpu().numpy())
+            pixels = sample_pixels(model, args, n, cls_idx)
+            save_pickle(os.path.join(args.result_path, f'samples_({cls_idx + 1}_{num_batches}).pkl'), pixels)
             np.savez(os.path.join(args.result_path, f'targets_({cls_idx + 1}_{num_batches}).npz'), targets=targets.cpu().numpy())
 
 

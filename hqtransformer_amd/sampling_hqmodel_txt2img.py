@@ -16,28 +16,16 @@ from __future__ import annotations
 import argparse
 import os
 
-import numpy as np
 import torch
 
 from . import text as T
-from .sampling import sampling_ihqgpt
-from .sampling_hqmodel import load_model, save_pickle
+from .sampling_hqmodel import common_arguments, load_model, sample_pixels, save_pickle
 from .utils import set_seed
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser()
-    p.add_argument('-r', '--result-path', type=str, required=True)
-    p.add_argument('-m', '--model-path', type=str, default='', required=True)
-    p.add_argument('--top-k', type=int, default=2048)
-    p.add_argument('--top-p', type=float, default=1.0)
-    p.add_argument('--temperature', type=float, default=1.0)
-    p.add_argument('--temperature-decay', type=float, default=1.0)
-    p.add_argument('--code-level', type=int, default=2)
+    p = common_arguments(argparse.ArgumentParser())
     p.add_argument('--batch_size', type=int, default=32)
-    p.add_argument('--top-resolution', type=int, default=8)
-    p.add_argument('--bot-resolution', type=int, default=16)
-    p.add_argument('--seed', type=int, default=0)
     p.add_argument('--dataset', type=str, default='cc3m', choices=['cc3m'])
     # where the reference reads a fixed dataset directory and its bundled vocabulary
     p.add_argument('--captions', type=str, default=None, help='val_list.txt ("<image>\t<caption>" lines) or one caption per line')
@@ -46,8 +34,6 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--reference-root', type=str, default=os.environ.get('HQT_REFERENCE_ROOT'),
                    help='checkout of kakaobrain/hqtransformer to take the bundled bpe-16k vocabulary from')
     p.add_argument('--synthetic-prompts', type=int, default=0, help='N random-id prompts instead of captions (smoke runs)')
-    p.add_argument('--decode-precision', choices=['split', 'exact', 'fast'], default='split',
-                   help='the reference decodes in fp32: split = fp32-accurate on the matrix cores (default), exact = fp32 vector ALUs, fast = bf16')
     return p
 
 
@@ -79,16 +65,9 @@ def main(argv=None):
         raise SystemExit('the model is not text-conditional (stage2.use_txt_cond)')
     spec = model.stage2.spec
     ids = prompt_ids(args, spec.ctx_len_txt, spec.vocab_txt)
-    temps = [args.temperature * (args.temperature_decay ** i) for i in range(args.code_level)]
     n = args.batch_size
-    for batch_idx, txts in enumerate(ids.split(n)):
-        codes_t, codes_b = sampling_ihqgpt(model.stage2, cond=txts.cuda(), num_candidates=1, top_k_top=args.top_k, top_p_top=args.top_p,
-                                           top_k_bot=args.top_k, top_p_bot=args.top_p, softmax_temperature=temps, use_fp16=True,
-                                           is_tqdm=False, max_seq_len=args.top_resolution * args.top_resolution, model_stage1=model.stage1)
-        pixels = model.stage1.decode_sequences(codes_t, codes_b, precision=args.decode_precision, clamp01=True)
-        model.stage1.range_check()                                  # SPLIT decode: raises if an activation left the fp16 range
-        model.stage2.range_check()          # FAST AR sampling of up to 64 rows: raises if a persistent launch gave up (hqt_range_check)
-        save_pickle(os.path.join(args.result_path, f'samples_({batch_idx + 1}_{n}).pkl'), pixels.cpu().numpy().astype(np.float32))
+    for batch_idx, txts in enumerate(ids.split(n)):     # one image per prompt (num_candidates=1: B = number of prompts, sampling.py:187-190)
+        save_pickle(os.path.join(args.result_path, f'samples_({batch_idx + 1}_{n}).pkl'), sample_pixels(model, args, 1, txts.cuda()))
 
 
 if __name__ == '__main__':

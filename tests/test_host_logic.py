@@ -182,3 +182,18 @@ def test_measure_throughput_txt_host_logic(tmp_path):
     import pytest
     with pytest.raises(ValueError):
         next(mtt.prompt_batches(parse_dotlist([f'captions={tmp_path / "caps.txt"}'], mtt.EXPERIMENT_DEFAULTS), spec))
+
+
+def test_harness_loop_accounting_lines_and_warmup_drop(capsys):
+    """The accounting both harnesses share, without a GPU: the two lines of a loop (measure_throughput/__main__.py:150-160), per-sample
+    figures = loop seconds / images, and the summary over the loops after the first ``warmup`` ones (:168-178)."""
+    from hqtransformer_amd import measure_throughput as mt, measure_throughput_txt as mtt
+    assert mtt.iterations_per_loop is mt.iterations_per_loop
+    a = mt.report_loop('1/3', 4.0, [3.0, 1.0], 1000)
+    assert a == (4.0, 3.0, 1.0)
+    assert capsys.readouterr().out == '1/3 | 4.0 s/loop (ar: 3.0, decode: 1.0)\n1/3 | 4.0 ms/sample (ar: 3.0, decode: 1.0)\n'
+    b, c = mt.report_loop('2/3', 2.0, [1.5, 0.5], 1000), mt.report_loop('3/3', 1.0, [0.5, 0.25], 500)
+    capsys.readouterr()
+    out = mt.summarize('bs50, sampling loops 2-3', [a, b, c], 1)
+    assert out == dict(ms_per_sample=2.0, ms_ar=1.25, ms_decode=0.5, images_per_s=500.0)
+    assert capsys.readouterr().out == '-' * 80 + '\nbs50, sampling loops 2-3 | 2.0000 ms/sample (ar: 1.2500, decode: 0.5000)\n' + '=' * 80 + '\n'

@@ -13,6 +13,11 @@ Cases: tiny class-conditional, text (prefill), three-level ('parallel-add', 'top
 sample / sample3 in EXACT, SPLIT and FAST, persist on and off, eager and graph; one merged pass of 640 rows under the throughput
 policy (tiled GEMM, split-K combine, K-sliced SPLIT GEMM); decode and encode in the three precisions on a stage 1 with attention, an
 upsampling conv and a nin_shortcut (planes-out, conv_out-direct, the halo conv's fused statistics), one decode with HQT_NO_FUSED_GN=1.
+
+The ``surface/*`` cases record hashes only, with fixed seeds, of what the Python surface above the engine returns on the tiny configs:
+``sampling_ihqgpt`` (class / text / bidirectional; every form of ``cond``, ``given_top_code``, ``row_seeds``, 'split', a seed drawn from
+torch's generator), ``sampling_hqtransformer``, ``decode_code`` / ``decode_sequences`` (two and three levels, a level missing) and
+``InflightSampler`` (3 lanes unmerged, 2 lanes x merge 4; every step's codes and pixels).  A refactor of that surface must leave them unchanged.
 """
 import argparse
 import hashlib
@@ -114,6 +119,71 @@ def stage1_cases(rec):
     eng.close()
 
 
+def surface_cases(rec):
+    import torch
+    from hqtransformer_amd import synth
+    from hqtransformer_amd.config import load_config
+    from hqtransformer_amd.models import ImageGPT2
+    from hqtransformer_amd.pipeline import InflightSampler
+    from hqtransformer_amd.sampling import rearrange_codes, rearrange_codes3, sampling_hqtransformer, sampling_ihqgpt
+
+    def model(name, *overrides, seed):
+        return ImageGPT2(load_config(os.path.join(ROOT, 'configs', name), list(overrides)), seed=seed).to('cuda').eval()
+
+    def put(case, tensors):
+        torch.cuda.synchronize()
+        rec['surface/' + case] = {'hashes': [None if t is None else digest(t) for t in tensors]}
+
+    B = 3
+    cls, txt, l3 = model('tiny-cls.yaml', seed=3), model('tiny-txt.yaml', seed=4), model('tiny-l3.yaml', seed=9)
+    bidir = model('tiny-cls.yaml', 'stage2.type=hq-transformer/bidirectional4', seed=5)
+    prompts = torch.from_numpy(synth.text_ids(6, B, txt.stage2.spec.ctx_len_txt, txt.stage2.spec.vocab_txt))
+    quality = dict(top_k_top=100, top_p_top=0.9, top_k_bot=50, top_p_bot=None, softmax_temperature=[1.0, 0.9])
+    for name, m, cond in (('class', cls, 7), ('text', txt, prompts), ('bidirectional', bidir, 7)):
+        for fp16 in (False, True):
+            put(f'ihqgpt/{name}/fp16={int(fp16)}', sampling_ihqgpt(m.stage2, B, cond, use_fp16=fp16, is_tqdm=False, max_seq_len=64, seed=21, **quality))
+        put(f'ihqgpt/{name}/split', sampling_ihqgpt(m.stage2, B, cond, is_tqdm=False, max_seq_len=16, seed=22, precision='split'))
+        torch.manual_seed(23)                     # seed=None: one draw from torch's generator per call
+        put(f'ihqgpt/{name}/torch_seed', [*sampling_ihqgpt(m.stage2, B, cond, is_tqdm=False, max_seq_len=16),
+                                          *sampling_ihqgpt(m.stage2, B, cond, is_tqdm=False, max_seq_len=16), torch.randint(0, 2 ** 62, (1,))])
+    for form, cond in (('one', torch.tensor([7])), ('each', torch.tensor([1, 5, 9]))):
+        put(f'ihqgpt/class/cond={form}', sampling_ihqgpt(cls.stage2, B, cond, use_fp16=False, is_tqdm=False, max_seq_len=16, seed=24))
+    given = torch.arange(16).reshape(1, 16) % 7
+    put('ihqgpt/class/given_top_code', sampling_ihqgpt(cls.stage2, B, 7, use_fp16=False, is_tqdm=False, max_seq_len=16, seed=25, given_top_code=given))
+    put('ihqgpt/class/row_seeds', sampling_ihqgpt(cls.stage2, B, torch.tensor([1, 5, 9]), use_fp16=False, is_tqdm=False, max_seq_len=16,
+                                                 seed=29, row_seeds=[31, 32, 31], row_offsets=[0, 4, 2]))
+    codes2 = sampling_ihqgpt(cls.stage2, B, 7, use_fp16=False, is_tqdm=False, max_seq_len=64, seed=26)
+    for fp16 in (False, True):
+        put(f'hqtransformer/fp16={int(fp16)}', sampling_hqtransformer(l3.stage2, B, 123, top_k=[100, 50, None], top_p=[0.9, None, None],
+                                                                     softmax_temperature=[1.0, 0.9, 0.8], use_fp16=fp16, is_tqdm=False, max_seq_len=16, seed=27))
+    codes3 = sampling_hqtransformer(l3.stage2, B, 123, use_fp16=False, is_tqdm=False, max_seq_len=16, seed=28)
+    grids2, grids3 = rearrange_codes(*codes2, 8), list(rearrange_codes3(codes3, 4))
+    for prec in PRECISIONS:
+        put(f'decode/l2/{prec}', [cls.stage1.decode_code(*grids2, precision=prec), cls.stage1.decode_code(None, grids2[1], precision=prec),
+                                  cls.stage1.decode_code(grids2[0], None, precision=prec, clamp01=True),
+                                  cls.stage1.decode_sequences(*codes2, precision=prec), cls.stage1.decode_sequences(codes2[0], None, precision=prec, clamp01=True)])
+        put(f'decode/l3/{prec}', [l3.stage1.decode_code(grids3, precision=prec), l3.stage1.decode_code([None, grids3[1], grids3[2]], precision=prec),
+                                  l3.stage1.decode_code([grids3[0], None, None], precision=prec, clamp01=True),
+                                  l3.stage1.decode_sequences(codes3, precision=prec), l3.stage1.decode_sequences([codes3[0], codes3[1], None], precision=prec, clamp01=True)])
+        cls.stage1.range_check()
+        l3.stage1.range_check()
+    l3_quality = dict(top_k=[100, 50, None], top_p=[0.9, None, None], softmax_temperature=[1.0, 0.9, 0.8])
+    for name, m, n_pos, conds, kw in (('class', cls, 64, [3, torch.tensor([4]), torch.tensor([1, 5, 9]), 6, 8], quality),
+                                      ('l3', l3, 16, [3, torch.tensor([4]), torch.tensor([1, 5, 9]), 6, 8], l3_quality),
+                                      ('text', txt, 64, [prompts.roll(k, 0) for k in range(5)], quality)):
+        for lanes, merge in ((3, 1), (2, 4)):
+            for fp16 in (False, True):
+                pipe = InflightSampler(m, lanes=lanes, merge=merge)
+                steps = [pipe.submit(B, c, seed=40 + k, max_seq_len=n_pos, use_fp16=fp16, sample_offset=k, **kw) for k, c in enumerate(conds)]
+                pipe.drain()
+                out = []
+                for st in steps:
+                    ct, cb, px, _ = st.get() if merge > 1 else st
+                    out += [ct, *(cb if isinstance(cb, (list, tuple)) else [cb]), px]
+                put(f'inflight/{name}/lanes={lanes}/merge={merge}/fp16={int(fp16)}', out)
+                pipe.release(B, n_pos)
+
+
 def record() -> dict:
     from hqtransformer_amd import _lib
     from hqtransformer_amd.spec import Stage2Spec
@@ -129,6 +199,7 @@ def record() -> dict:
                       ctx_len_img=64, ctx_len_txt=16, n_classes=1000, cond=1, embedding=0)
     sample_cases(rec, 'merged640', wide, 31, 640, 2, policy=_lib.POLICY_THROUGHPUT, persist=(True,))
     stage1_cases(rec)
+    surface_cases(rec)
     return rec
 
 
