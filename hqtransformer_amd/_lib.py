@@ -79,6 +79,10 @@ class hqt_sample_opts_l3(C.Structure):
     ]
 
 
+class hqt_row_sampler(C.Structure):
+    _fields_ = [('temperature', C.c_float * 3), ('top_k', C.c_int32 * 3), ('top_p', C.c_float * 3)]
+
+
 class hqt_encode_out(C.Structure):
     _fields_ = [
         ('codes', C.c_void_p * 3), ('quant', C.c_void_p * 3), ('resid', C.c_void_p * 3),
@@ -97,6 +101,7 @@ SYMBOLS = {
     'hqt_clone': (C.c_int, [_VP, C.POINTER(_VP)]),
     'hqt_set_policy': (C.c_int, [_VP, C.c_int]),
     'hqt_set_switch': (C.c_int, [_VP, C.c_int, C.c_int]),
+    'hqt_set_row_samplers': (C.c_int, [_VP, C.c_int, C.POINTER(hqt_row_sampler)]),
     'hqt_sample': (C.c_int, [_VP, C.c_int, _I64P, C.POINTER(hqt_sample_opts), _F32P, _I64P, _I64P, _F32P, _I64P, _I64P, _VP]),
     'hqt_decode': (C.c_int, [_VP, C.c_int, _I64P, _I64P, _F32P, C.c_int, C.c_int, _VP]),
     'hqt_decode_seq': (C.c_int, [_VP, C.c_int, _I64P, _I64P, _F32P, C.c_int, C.c_int, _VP]),

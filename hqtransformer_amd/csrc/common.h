@@ -200,6 +200,11 @@ struct RowKey {              // per batch row, device memory owned by the handle
     unsigned long long seed;
     long long global_row;
 };
+struct RowSampler {          // per batch row, device memory owned by the handle: the row's sampler settings per code level (= hqt_row_sampler of hqt.h)
+    float temperature[3];
+    int top_k[3];            // <= 0: none
+    float top_p[3];          // <= 0: none
+};
 
 #define HQT_MAX_V 16384
 

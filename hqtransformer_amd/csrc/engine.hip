@@ -138,10 +138,12 @@ struct hqt_handle {
     // per-row keys of merged steps travel through a ring of PINNED staging buffers (an asynchronous copy from pinned memory reads its
     // source when the stream gets there: a buffer is rewritten only after the copy that last read it has completed, hipEventSynchronize)
     static constexpr int ROWS_RING = 4;
-    RowKey* rows_pinned[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};
+    RowKey* rows_pinned[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};       // each: RowKey[max_batch], then RowSampler[max_batch]
     hipEvent_t rows_ev[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};
     bool rows_busy[ROWS_RING] = {false, false, false, false};
     int rows_next = 0;
+    RowSampler* row_set = nullptr;            // [max_batch] per-row sampler settings of the current call (hqt_set_row_samplers)
+    std::vector<hqt_row_sampler> row_set_staged;   // host table waiting for the next hqt_sample / hqt_sample_l3 of this handle, which takes it
     int64_t *cond_buf = nullptr, *codes_top = nullptr, *codes_bot = nullptr;   // call-independent homes of cond / the drawn codes
     int64_t* codes_l2 = nullptr;              // third level: [B, max_steps, 16]
     Lin head_l2;                              // head_levels.2 (three-level models; head_top / head_bot hold levels 0 / 1)
@@ -457,6 +459,7 @@ static int alloc_workspace(hqt_handle* hp) {
         CHK(dev_alloc(h.get(), (void**)&h->splitk, h->splitk_elems * 4, true));
         CHK(dev_alloc(h.get(), (void**)&h->state, sizeof(StepState), true));
         CHK(dev_alloc(h.get(), (void**)&h->rows, B * sizeof(RowKey), true));
+        CHK(dev_alloc(h.get(), (void**)&h->row_set, B * sizeof(RowSampler), true));
         CHK(dev_alloc(h.get(), (void**)&h->cond_buf, B * (size_t)std::max(1, c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : 1) * 8, true));
         CHK(dev_alloc(h.get(), (void**)&h->codes_top, B * (size_t)c.max_steps * 8, true));
         CHK(dev_alloc(h.get(), (void**)&h->codes_bot, B * (size_t)c.max_steps * 4 * 8, true));
@@ -545,6 +548,7 @@ extern "C" int hqt_clone(hqt_handle* src, hqt_handle** out) {
     h->pend = {nullptr, 0, 0, nullptr};
     for (int i = 0; i < hqt_handle::ROWS_RING; ++i) { h->rows_pinned[i] = nullptr; h->rows_ev[i] = nullptr; h->rows_busy[i] = false; }
     h->rows_next = 0;
+    h->row_set_staged.clear();                   // a lane has its own table
     h->nparts = h->npartsd = 0;
     h->pbody.d_phases = nullptr; h->pfull.d_phases = nullptr;      // phase tables hold workspace pointers: bound per handle (persist_bind)
     h->persist_used = false; h->persist_tripped = false; h->capture_persist = false; h->graph_has_persist = false;
@@ -1046,6 +1050,8 @@ struct SampleCtx {
     const uint64_t* row_seeds;
     const int64_t* row_offsets;
     SamplerSet lv[3];
+    const hqt_row_sampler* row_set = nullptr;    // host table of B rows staged by hqt_set_row_samplers: in place of lv[] (which then holds defaults)
+    bool row_top_p = false;                      // some row of it uses top-p
     const float* noise;
     const int64_t* feed[3] = {nullptr, nullptr, nullptr};   // codes each level's embeddings read: the drawn ones (out) or the forced ones
     int64_t* out[3] = {nullptr, nullptr, nullptr};
@@ -1490,6 +1496,10 @@ static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body
                            h->state, h->rows, c.n_steps, c.out[s.lv], c.logits_out, h->depth_rows};
             sa.out_stride = s.out_stride; sa.out_slot = s.out_slot;
             sa.fast_math = c.md.fast ? 1 : 0;
+            if (c.row_set) {      // the bidirectional head keeps its mapping per row: every draw with temperature[0], top_k[1], top_p[1]
+                sa.row_set = h->row_set; sa.row_top_p = c.row_top_p ? 1 : 0;
+                sa.row_lv_t = bidir ? 0 : s.lv; sa.row_lv_k = bidir ? 1 : s.lv;
+            }
             if (fuse && sub == 0) {
                 const bool dln_next = dln_of(sub_step(cf, 1));
                 sa.emb_tok = W(h, "tok_emb_top_depth.weight"); sa.emb_pos = W(h, "pos_emb_depth.weight");
@@ -1534,6 +1544,11 @@ static int sample_run(hqt_handle* h, const SampleCtx& c);
 // hqt_sample / hqt_sample_l3 after their null checks: `c` holds the call's options, sampler settings and forced codes (feed); validates them,
 // runs the call and copies the drawn codes of every level out
 static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t* const* out, void* stream) {
+    // the staged row table belongs to THIS call and to no later one, whatever becomes of the call
+    std::vector<hqt_row_sampler> staged;
+    staged.swap(h->row_set_staged);
+    const size_t staged_rows = staged.size();
+    c.row_set = staged_rows ? staged.data() : nullptr;
     if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
     const hqt_config& cf = h->cfg;
     if (c.levels == 2 && !cf.has_stage2) return fail(HQT_ERR_STATE, "handle was created without stage 2");
@@ -1543,12 +1558,19 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     if (B < 1 || B > cf.max_batch) return fail(HQT_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cf.max_batch);
     if (c.n_steps < 1 || c.n_steps > cf.max_steps) return fail(HQT_ERR_INVALID, "n_steps=%d outside [1, %d]", c.n_steps, cf.max_steps);
     if (cf.cond_type != HQT_COND_NONE && !cond) return fail(HQT_ERR_INVALID, "cond is required for class/text conditioning");
-    bool top_p = false;
-    for (int i = 0; i < c.levels; ++i) {
-        if (!(c.lv[i].temperature > 0.f)) return fail(HQT_ERR_INVALID, "temperatures must be > 0");
-        top_p = top_p || c.lv[i].top_p > 0.f;
+    if (c.row_set) {                             // per-row settings replace the scalars of `opts`: those are neither checked nor part of the graph key
+        if ((int)staged_rows != B) return fail(HQT_ERR_INVALID, "hqt_set_row_samplers staged %d rows, this call has B=%d", (int)staged_rows, B);
+        for (int i = 0; i < 3; ++i) c.lv[i] = SamplerSet();
     }
+    bool top_p = false;
+    for (int b = 0; b < (c.row_set ? B : 1); ++b)
+        for (int i = 0; i < c.levels; ++i) {
+            const SamplerSet l = c.row_set ? SamplerSet{c.row_set[b].temperature[i], c.row_set[b].top_k[i], c.row_set[b].top_p[i]} : c.lv[i];
+            if (!(l.temperature > 0.f)) return fail(HQT_ERR_INVALID, "temperatures must be > 0");
+            top_p = top_p || l.top_p > 0.f;
+        }
     if (top_p && cf.vocab_top > 8192) return fail(HQT_ERR_INVALID, "top-p needs vocab <= 8192");
+    c.row_top_p = c.row_set && top_p;
     ON_DEVICE(h);
     // The launch sequence reads cond and writes the drawn codes in buffers owned by the handle, and takes the Philox seed
     // and the global row offset from device memory: nothing that changes from call to call is baked into the captured
@@ -1579,9 +1601,21 @@ template <class Opts> static SampleCtx sample_ctx(int levels, int B, const Opts*
     return c;
 }
 
+static_assert(sizeof(hqt_row_sampler) == 36 && sizeof(RowSampler) == sizeof(hqt_row_sampler), "hqt_row_sampler is copied to the device as RowSampler");
+
+extern "C" int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler* rows) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    h->row_set_staged.clear();
+    if (n == 0 || !rows) return HQT_OK;
+    if (n < 0 || n > h->cfg.max_batch) return fail(HQT_ERR_INVALID, "n=%d outside [0, max_batch=%d]", n, h->cfg.max_batch);
+    h->row_set_staged.assign(rows, rows + n);    // checked against B, the levels and the vocabulary by the call that takes it
+    return HQT_OK;
+}
+
 extern "C" int hqt_sample(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts* opts, const float* noise,
                           const int64_t* force_top, const int64_t* force_bot, float* logits_out, int64_t* out_top,
                           int64_t* out_bot, void* stream) {
+    if (h && (!opts || !out_top || !out_bot)) h->row_set_staged.clear();
     if (!h || !opts || !out_top || !out_bot) return fail(HQT_ERR_INVALID, "null argument");
     SampleCtx c = sample_ctx(2, B, opts, noise, logits_out);
     c.lv[0] = {opts->temperature_top, opts->top_k_top, opts->top_p_top};
@@ -1594,6 +1628,7 @@ extern "C" int hqt_sample(hqt_handle* h, int B, const int64_t* cond, const hqt_s
 extern "C" int hqt_sample_l3(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts_l3* opts, const float* noise,
                              const int64_t* force0, const int64_t* force1, const int64_t* force2, float* logits_out,
                              int64_t* out0, int64_t* out1, int64_t* out2, void* stream) {
+    if (h && (!opts || !out0 || !out1 || !out2)) h->row_set_staged.clear();
     if (!h || !opts || !out0 || !out1 || !out2) return fail(HQT_ERR_INVALID, "null argument");
     SampleCtx c = sample_ctx(3, B, opts, noise, logits_out);
     for (int i = 0; i < 3; ++i) c.lv[i] = {opts->temperature[i], opts->top_k[i], opts->top_p[i]};
@@ -1634,26 +1669,32 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
     const int B = c.B;
     bool top_p = false;
     for (int i = 0; i < c.levels; ++i) top_p = top_p || c.lv[i].top_p > 0.f;
-    HIPCHK(sampler_configure(cf.vocab_top, top_p));
+    HIPCHK(sampler_configure(cf.vocab_top, top_p || c.row_top_p));
     CHK(persist_bind(h));
     HIPCHK(launch_set_step(h->state, 0, 0, c.st));
-    if (c.row_seeds || c.row_offsets) {      // merged steps: per-row Philox keys (host arrays, staged through pinned-free pageable copies: B <= max_batch entries)
-        if (!c.row_seeds || !c.row_offsets) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
+    if ((c.row_seeds || c.row_offsets) && (!c.row_seeds || !c.row_offsets)) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
+    if (c.row_seeds || c.row_set) {          // merged steps: per-row Philox keys and / or sampler settings (host arrays of B <= max_batch entries, through the pinned ring)
         const int slot = h->rows_next;
         h->rows_next = (slot + 1) % hqt_handle::ROWS_RING;
         if (!h->rows_pinned[slot]) {
-            HIPCHK(hipHostMalloc((void**)&h->rows_pinned[slot], (size_t)h->cfg.max_batch * sizeof(RowKey), hipHostMallocDefault));
+            HIPCHK(hipHostMalloc((void**)&h->rows_pinned[slot], (size_t)h->cfg.max_batch * (sizeof(RowKey) + sizeof(RowSampler)), hipHostMallocDefault));
             HIPCHK(hipEventCreateWithFlags(&h->rows_ev[slot], hipEventDisableTiming));
         }
         if (h->rows_busy[slot]) HIPCHK(hipEventSynchronize(h->rows_ev[slot]));       // the copy that last read this buffer (4 calls ago) is done
         RowKey* rk = h->rows_pinned[slot];
-        for (int b = 0; b < B; ++b) { rk[b].seed = c.row_seeds[b]; rk[b].global_row = c.row_offsets[b]; }
-        HIPCHK(hipMemcpyAsync(h->rows, rk, (size_t)B * sizeof(RowKey), hipMemcpyHostToDevice, c.st));
+        if (c.row_seeds) {
+            for (int b = 0; b < B; ++b) { rk[b].seed = c.row_seeds[b]; rk[b].global_row = c.row_offsets[b]; }
+            HIPCHK(hipMemcpyAsync(h->rows, rk, (size_t)B * sizeof(RowKey), hipMemcpyHostToDevice, c.st));
+        }
+        if (c.row_set) {
+            RowSampler* rs = reinterpret_cast<RowSampler*>(rk + h->cfg.max_batch);
+            memcpy(rs, c.row_set, (size_t)B * sizeof(RowSampler));
+            HIPCHK(hipMemcpyAsync(h->row_set, rs, (size_t)B * sizeof(RowSampler), hipMemcpyHostToDevice, c.st));
+        }
         HIPCHK(hipEventRecord(h->rows_ev[slot], c.st));
         h->rows_busy[slot] = true;
-    } else {
-        HIPCHK(launch_set_rows(h->rows, B, c.seed, c.sample_offset, c.st));
     }
+    if (!c.row_seeds) HIPCHK(launch_set_rows(h->rows, B, c.seed, c.sample_offset, c.st));
     int first = 0;
     if (cf.cond_type == HQT_COND_TEXT) {     // 64-token causal prefill (sampling.py:187-190, layers.py:107-111)
         const int T = cf.ctx_len_txt;
@@ -1679,6 +1720,9 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
             memcpy(f, &l.top_p, 4); memcpy(f + 1, &l.temperature, 4);
             key.push_back((uint64_t)l.top_k); key.push_back(f[0]); key.push_back(f[1]);
         }
+        // a row table: that there is one (two sampler launches per draw where the pass dispatches) and whether a row uses top-p (the LDS of the general
+        // kernel) -- never its values, which the kernels read from device memory: a changed table replays the same graph
+        key.push_back((uint64_t)((c.row_set ? 1 : 0) + (c.row_top_p ? 2 : 0)));
         if (!h->graph_exec || key != h->graph_key) {
             if (h->graph_exec) {                         // rare (options or test-only buffers changed): drain before destroying
                 HIPCHK(hipStreamSynchronize(c.st));

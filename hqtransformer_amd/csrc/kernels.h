@@ -123,7 +123,15 @@ struct SamplerArgs {
     int out_stride, out_slot;    // out_stride > 0: the drawn code goes to out[(b * n_steps + step) * out_stride + out_slot] (slots == 1: one sub-step of the
                                  // 21-step causal head writes ONE slot of a 4- or 16-wide code group)
     int fast_math;               // FAST-precision calls: v_exp / v_log / v_rcp forms of exp, log and the divisions (1-2 ulp each; EXACT keeps the IEEE forms: its draws are the parity gate, compared bit for bit)
+    // ---- per-row settings (hqt_set_row_samplers): row b draws with temperature[row_lv_t], top_k[row_lv_k], top_p[row_lv_k] of row_set[b] in place of the three
+    //      scalars above (the two indices differ under the bidirectional head only).  NULL: the scalars, for every row.
+    const RowSampler* row_set;   // [B], device
+    int row_lv_t, row_lv_k;
+    int row_top_p;               // some row of the table uses top-p: the general kernel's LDS is sized for it (a launch-time choice, so a host-side one)
+    int row_dispatch;            // set by launch_sampler: both kernels run over the pass and a workgroup leaves at once when its row belongs to the other one
 };
+// Uniform call: one launch.  With a row table in a FAST pass whose vocabulary the register-resident kernel takes: that kernel, then the general one, each over
+// every row -- which rows are in which class is read on the device, so the launch sequence does not depend on the table's values.
 hipError_t launch_sampler(const SamplerArgs& a, hipStream_t st);
 // depth sub-step 2 of the three-level model (hqtransformer.py:537-551): token i (raster (H1 H2 W1 W2)) =
 // tok1[codes1[b, step, parent(i)]] + pos[i] (+ tok0[codes0[b, step]]: 'add', tok0 non-NULL), 16 rows per sample; tok1_ld = 4 D:

@@ -1031,6 +1031,11 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// Which kernel draws a row of a FAST pass whose vocabulary sampler_plain_fast_kernel takes: the rows without a cut-off go there, the others to sampler_kernel --
+// the choice launch_sampler makes for a uniform call, made per row when the settings come from a row table (the two kernels differ in the last bit of a ratio,
+// so a row must stay with the kernel it would get alone)
+__host__ __device__ __forceinline__ bool sampler_row_plain(int top_k, float top_p, int V) { return !(top_k > 0 && top_k < V) && !(top_p > 0.0f); }
+
 // NT threads per logits row: 1024 (16 waves, 4 per SIMD) hides the latency of the exp / log / divide / Philox chains that a
 // lone 4-wave workgroup per CU exposes (25 -> ~10 us per launch at V = 8192); 256 for small vocabularies.
 // FM: fast-math forms for FAST-precision calls.  The plain path (no top-k / top-p) is bound by the IEEE expf / logf / divisions of its
@@ -1052,6 +1057,15 @@ __global__ __launch_bounds__(NT, 8) void sampler_kernel(SamplerArgs a, int n2) {
     unsigned char* keep = reinterpret_cast<unsigned char*>(sidx + n2);
 
     const int r = blockIdx.x, b = r / a.slots, slot = r % a.slots;
+    // the row's own settings when the call carries a row table (workgroup-uniform: scalar loads); under dispatch a row without a cut-off belongs to
+    // sampler_plain_fast_kernel, and this workgroup leaves before it touches anything
+    float temperature = a.temperature, top_p = a.top_p;
+    int top_k = a.top_k;
+    if (a.row_set) {
+        const RowSampler& rs = a.row_set[b];
+        temperature = rs.temperature[a.row_lv_t]; top_k = rs.top_k[a.row_lv_k]; top_p = rs.top_p[a.row_lv_k];
+        if (a.row_dispatch && sampler_row_plain(top_k, top_p, V)) return;
+    }
     const int step = a.state->step;
     const int draw = a.draw0 + slot;
     const float* lg = a.logits + (long long)r * V;
@@ -1059,18 +1073,18 @@ __global__ __launch_bounds__(NT, 8) void sampler_kernel(SamplerArgs a, int n2) {
     const long long nidx = (((long long)step * draws + draw) * a.B + b) * V;
 
     // ---- temperature (logits /= T, hierarchical_ar.py:763,779) and raw-logit dump
-    const float inv_t = FM ? __builtin_amdgcn_rcpf(a.temperature) : 0.0f;
+    const float inv_t = FM ? __builtin_amdgcn_rcpf(temperature) : 0.0f;
     for (int i = tid; i < V; i += NT) {
         const float v = lg[i];
         if (a.logits_out) a.logits_out[nidx + i] = v;
-        lp[i] = FM ? v * inv_t : v / a.temperature;
+        lp[i] = FM ? v * inv_t : v / temperature;
     }
     __syncthreads();
 
     // ---- top-k: exact k-th largest by 4-pass radix select, keep >= threshold (sampling.py:12-19)
-    if (a.top_k > 0 && a.top_k < V) {
+    if (top_k > 0 && top_k < V) {
         uint32_t prefix = 0;
-        int remaining = a.top_k;
+        int remaining = top_k;
         for (int shift = 24; shift >= 0; shift -= 8) {
             if (tid < 256) hist[tid] = 0;
             __syncthreads();
@@ -1128,7 +1142,7 @@ __global__ __launch_bounds__(NT, 8) void sampler_kernel(SamplerArgs a, int n2) {
     // ---- top-p (sampling.py:22-37): descending sort, prefix sums accumulated in double and rounded
     //      to fp32 per element (what torch.cumsum does on the CPU), cut after the first prefix >= p
     float renorm = 1.0f;
-    const bool use_p = a.top_p > 0.0f;
+    const bool use_p = top_p > 0.0f;
     if (use_p) {
         // Only entries with p > 0 can matter (zeros -- everything top-k masked -- sort last, add nothing to the prefix sums and stay zero
         // whether kept or not), so they alone are compacted, sorted and scanned: with top_k = 2048 of V = 8192 the bitonic network
@@ -1237,7 +1251,7 @@ __global__ __launch_bounds__(NT, 8) void sampler_kernel(SamplerArgs a, int n2) {
             const int j = tid * chunk + c;
             if (j < cnt) {
                 run += (double)skey[j];
-                if ((float)run >= a.top_p && j < first) first = j;
+                if ((float)run >= top_p && j < first) first = j;
             }
         }
         first = block_reduce(first, OpMin(), redi);
@@ -1346,12 +1360,18 @@ __global__ __launch_bounds__(256) void sampler_plain_fast_kernel(SamplerArgs a) 
     __shared__ int redi[4];
     const int V = a.V, tid = threadIdx.x;
     const int r = blockIdx.x, b = r / a.slots, slot = r % a.slots;
+    float temperature = a.temperature;
+    if (a.row_set) {             // row table: this kernel takes the rows without a cut-off, sampler_kernel (launched over the same rows) the others
+        const RowSampler& rs = a.row_set[b];
+        temperature = rs.temperature[a.row_lv_t];
+        if (!sampler_row_plain(rs.top_k[a.row_lv_k], rs.top_p[a.row_lv_k], V)) return;      // workgroup-uniform
+    }
     const int step = a.state->step;
     const int draw = a.draw0 + slot;
     const float* lg = a.logits + (long long)r * V;
     const int draws = a.draws > 0 ? a.draws : 5;
     const long long nidx = (((long long)step * draws + draw) * a.B + b) * V;
-    const float inv_t = __builtin_amdgcn_rcpf(a.temperature);
+    const float inv_t = __builtin_amdgcn_rcpf(temperature);
     float4 v[G4];
     float m = -INFINITY;
 #pragma unroll
@@ -1481,17 +1501,23 @@ hipError_t sampler_configure(int V, bool use_top_p) {
     if (e == hipSuccess && dev >= 0 && dev < 64) limit[dev] = smem;
     return e;
 }
-hipError_t launch_sampler(const SamplerArgs& a, hipStream_t st) {
+hipError_t launch_sampler(const SamplerArgs& args, hipStream_t st) {
+    SamplerArgs a = args;
+    const bool table = a.row_set != nullptr;
     int n2;
-    const size_t smem = sampler_smem(a.V, a.top_p > 0.0f, n2);
+    const size_t smem = sampler_smem(a.V, table ? a.row_top_p != 0 : a.top_p > 0.0f, n2);
     if (smem > 160 * 1024) return hipErrorInvalidValue;               // sampler_configure(V, top_p) ran in sample_run for this call's options
-    // FAST, no cut-offs, V <= 8192: the register-resident kernel (HQT_NO_PLAIN_SAMPLER=1: A/B switch)
+    // FAST, no cut-offs, V <= 8192: the register-resident kernel (HQT_NO_PLAIN_SAMPLER=1: A/B switch).  With a row table it runs over every row in front of the
+    // general kernel and each of the two leaves the other one's rows alone (row_dispatch): two launches whatever the table holds.
     static const bool no_plain = getenv("HQT_NO_PLAIN_SAMPLER") != nullptr;
-    if (!no_plain && a.fast_math && !(a.top_k > 0 && a.top_k < a.V) && !(a.top_p > 0.0f) && a.V % 4 == 0 && a.V <= 8192 && a.V >= 1024) {
+    const bool plain_v = !no_plain && a.fast_math && a.V % 4 == 0 && a.V <= 8192 && a.V >= 1024;
+    a.row_dispatch = table && plain_v ? 1 : 0;
+    if (plain_v && (table || sampler_row_plain(a.top_k, a.top_p, a.V))) {
         if (a.V <= 2048) sampler_plain_fast_kernel<2><<<a.R, 256, 0, st>>>(a);
         else if (a.V <= 4096) sampler_plain_fast_kernel<4><<<a.R, 256, 0, st>>>(a);
         else sampler_plain_fast_kernel<8><<<a.R, 256, 0, st>>>(a);
-        return hipGetLastError();
+        const hipError_t e = hipGetLastError();
+        if (!table || e != hipSuccess) return e;
     }
     if (a.V >= 4096) { if (a.fast_math) sampler_kernel<1024, true><<<a.R, 1024, smem, st>>>(a, n2); else sampler_kernel<1024, false><<<a.R, 1024, smem, st>>>(a, n2); }
     else { if (a.fast_math) sampler_kernel<256, true><<<a.R, 256, smem, st>>>(a, n2); else sampler_kernel<256, false><<<a.R, 256, smem, st>>>(a, n2); }

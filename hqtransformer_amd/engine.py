@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import PRECISION_EXACT, PRECISION_FAST, hqt_config, hqt_encode_out, hqt_sample_opts, hqt_sample_opts_l3
+from ._lib import PRECISION_EXACT, PRECISION_FAST, hqt_config, hqt_encode_out, hqt_row_sampler, hqt_sample_opts, hqt_sample_opts_l3
 from .spec import DEPTH_DECODINGS, STAGE1_RESAMPLES, Stage1Spec, Stage2Spec
 
 
@@ -55,6 +55,32 @@ def make_config(s2: Optional[Stage2Spec], s1: Optional[Stage1Spec], max_batch: i
 # (data_ptr, numel) -> tensor version of device tensors whose indices are known to be in range: produced by a sampler of this
 # process (any engine: the stage-2 engine's codes go to the stage-1 engine's decode) or already validated once
 _TRUSTED: Dict[tuple, tuple] = {}       # (data_ptr, shape, stride, dtype) -> (tensor version, weakref to its storage, largest valid id + 1)
+
+def row_sampler_table(levels: int, row_samplers) -> np.ndarray:
+    """Per-row sampler settings -> the ``hqt_row_sampler`` array ``hqt_set_row_samplers`` takes, as uint32 [B, 9] (three fp32 temperatures, three
+    int32 top-k, three fp32 top-p; index = code level, levels the model lacks stay at temperature 1 / no cut-off).  Each entry is
+    ``(temperature per level, top_k per level, top_p per level)``; ``None`` for a cut-off, or for all cut-offs of a kind, means none."""
+    L = int(levels)
+    rows = np.zeros((len(row_samplers), 9), dtype=np.uint32)
+    done: Dict[tuple, np.ndarray] = {}           # by value: a merged step repeats one entry for all of its rows
+    for b, entry in enumerate(row_samplers):
+        if len(entry) != 3:
+            raise ValueError(f'row_samplers[{b}]: expected (temperature, top_k, top_p), each per level')
+        t, k, p = (tuple(v) if v is not None else (None,) * L for v in entry)
+        if not (len(t) == len(k) == len(p) == L):
+            raise ValueError(f'row_samplers[{b}]: expected {L} levels in each of temperature, top_k and top_p')
+        row = done.get((t, k, p))
+        if row is None:
+            tf = np.ones(3, dtype=np.float32)
+            tf[:L] = [1.0 if v is None else float(v) for v in t]
+            ki = np.zeros(3, dtype=np.int32)
+            ki[:L] = [int(v) if v else 0 for v in k]
+            pf = np.zeros(3, dtype=np.float32)
+            pf[:L] = [float(v) if v else 0.0 for v in p]
+            row = done[(t, k, p)] = np.concatenate([tf.view(np.uint32), ki.view(np.uint32), pf.view(np.uint32)])
+        rows[b] = row
+    return rows
+
 
 # what the two- and the three-level surface call their levels in messages
 _FORCE_NAMES = {2: ('force_top', 'force_bot'), 3: ('force[0]', 'force[1]', 'force[2]')}
@@ -252,7 +278,7 @@ class Engine:
     # Code levels are lists, coarse to fine; their number (2: hqt_sample, 3: hqt_sample_l3) is all that differs below.
     def _sample_levels(self, levels: int, batch: int, cond, n_steps: int, *, precision, top_k, top_p, temperature, noise, seed, sample_offset,
                        force: Sequence[Optional[torch.Tensor]], out: Optional[Sequence[torch.Tensor]], return_logits, use_graph,
-                       row_seeds, row_offsets) -> Tuple[List[torch.Tensor], Optional[torch.Tensor]]:
+                       row_seeds, row_offsets, row_samplers=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor]]:
         """Returns (codes [B, n], [B, n, 4][, [B, n, 16]], logits [n, draws, B, V] or None)."""
         dev = self.device
         B, V, L = int(batch), self.s2.vocab_top, int(levels)
@@ -269,6 +295,7 @@ class Engine:
                 o.top_k[i], o.top_p[i], o.temperature[i] = k, p, t
         o.seed, o.sample_offset, o.use_graph = int(seed) & (2 ** 64 - 1), int(sample_offset), int(bool(use_graph))
         rows = self._row_keys(o, B, row_seeds, row_offsets)
+        table = None if row_samplers is None else row_sampler_table(L, row_samplers)     # its length is checked against B by the library
         cond = self._prep_cond(cond, B)
         noise = self._prep(noise, (n_steps, draws, B, V), torch.float32, 'noise')
         force = [self._prep(f, shp, torch.int64, what, V) for f, shp, what in zip(force, shapes, _FORCE_NAMES[L])]
@@ -280,10 +307,12 @@ class Engine:
         fn = self.lib.hqt_sample if L == 2 else self.lib.hqt_sample_l3
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
+            if table is not None:                   # staged on the handle; the call below takes it (and clears it even when it fails)
+                _lib.check(self.lib.hqt_set_row_samplers(self.h, len(table), table.ctypes.data_as(C.POINTER(hqt_row_sampler))))
             _lib.check(fn(self.h, B, _ptr(cond), C.byref(o), _ptr(noise), *map(_ptr, force), _ptr(logits), *map(_ptr, outs), C.c_void_p(stream)))
             self._note_split(precision, stream, ar_rows=B)        # every head runs persistently (run_position)
         # inputs must outlive the asynchronous launches
-        self._keep = (cond, noise, force, rows)
+        self._keep = (cond, noise, force, rows)     # (the row-sampler table was copied by hqt_set_row_samplers)
         self._trust(*outs, bound=max(self.s2.vocab_top, self.s2.vocab_bot))     # the sampler only writes ids inside the vocabulary
         return outs, logits
 
@@ -293,26 +322,33 @@ class Engine:
                sample_offset: int = 0, force_top: Optional[torch.Tensor] = None, force_bot: Optional[torch.Tensor] = None,
                return_logits: bool = False, use_graph: bool = True,
                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-               row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None):
+               row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
+               row_samplers: Optional[Sequence[tuple]] = None):
         """Two-level sampling: returns (codes_top [B, n], codes_bot [B, n, 4][, logits [n, 5, B, V]]).
         ``row_seeds`` / ``row_offsets`` (both or neither, ``batch`` entries): merged steps -- row b draws what the row with
-        global index ``row_offsets[b]`` of a call seeded ``row_seeds[b]`` draws (``hqt_sample_opts.row_seeds``)."""
+        global index ``row_offsets[b]`` of a call seeded ``row_seeds[b]`` draws (``hqt_sample_opts.row_seeds``).
+        ``row_samplers`` (``batch`` entries ``(temperature per level, top_k per level, top_p per level)``, see ``row_sampler_table``): row b
+        draws with its own settings in place of ``top_k`` / ``top_p`` / ``temperature`` -- bit for bit what it draws in a call that has
+        those settings for every row (``hqt_set_row_samplers``)."""
         if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
             raise ValueError('out: expected a pair (codes_top [B, n_steps], codes_bot [B, n_steps, 4])')
         outs, logits = self._sample_levels(2, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(force_top, force_bot), out=out,
-                                           return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets)
+                                           return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
+                                           row_samplers=row_samplers)
         return (outs[0], outs[1], logits) if return_logits else (outs[0], outs[1])
 
     def sample3(self, batch: int, cond: Optional[torch.Tensor], n_steps: int, *, precision: int = PRECISION_FAST,
                 top_k: Sequence[Optional[int]] = (None, None, None), top_p: Sequence[Optional[float]] = (None, None, None),
                 temperature: Sequence[float] = (1.0, 1.0, 1.0), noise: Optional[torch.Tensor] = None, seed: int = 0,
                 sample_offset: int = 0, force: Optional[Sequence[torch.Tensor]] = None, return_logits: bool = False,
-                use_graph: bool = True, row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None):
-        """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]])."""
+                use_graph: bool = True, row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
+                row_samplers: Optional[Sequence[tuple]] = None):
+        """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]]); ``row_samplers`` as in ``sample``."""
         outs, logits = self._sample_levels(3, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(None,) * 3 if force is None else force,
-                                           out=None, return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets)
+                                           out=None, return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
+                                           row_samplers=row_samplers)
         return (*outs, logits) if return_logits else tuple(outs)
 
     # ------------------------------------------------------------------ stage 1, encode side

@@ -10,7 +10,8 @@ of the configured batch size, and results do not depend on the lane (bit-identic
 ``merge=k`` additionally executes k queued steps as ONE pass of k x B rows (class-conditional, unconditional, text-conditional; two or
 three code levels): the steps stay independent -- every row keeps the class id / prompt, the Philox seed and the global row index of its own step (``hqt_sample_opts.row_seeds`` / ``row_offsets``), so in EXACT
 arithmetic each step's codes are bit-identical to the unmerged call (tests/test_gpu_surface.py) -- but the weights are streamed
-once for all of them instead of once per step.
+once for all of them instead of once per step.  ``mixed_samplers=True`` lets the steps of a pass differ in temperature, top-k and top-p as well:
+every row then carries the sampler settings of its own step (``hqt_set_row_samplers``) and draws what it draws in that step's separate call.
 """
 from __future__ import annotations
 
@@ -35,6 +36,29 @@ def sampler_cutoffs(levels: int, top_k, top_p) -> dict:
     if levels == 3:
         return dict(top_k=[top_k] * 3, top_p=[top_p] * 3)
     return dict(top_k_top=top_k, top_p_top=top_p, top_k_bot=top_k, top_p_bot=top_p)
+
+
+# the sampler keywords of sampling_ihqgpt (two levels) and sampling_hqtransformer (three): what the steps of a mixed pass may differ in
+SAMPLER_KEYS = ('top_k_top', 'top_p_top', 'top_k_bot', 'top_p_bot', 'top_k', 'top_p', 'softmax_temperature')
+
+
+def step_row_samplers(levels: int, sizes, sample_kws) -> list:
+    """Steps of a mixed pass -> its row table: step i's sampler keywords (``sample_kws[i]``: those of ``sampling_ihqgpt`` for two levels, of
+    ``sampling_hqtransformer`` for three; missing = the sampler's default) as one ``(temperature, top_k, top_p)`` entry, each per level, repeated
+    for the step's ``sizes[i]`` rows.  The result is ``row_samplers=`` of the samplers (``Engine.sample``)."""
+    L = int(levels)
+    rows: list = []
+    for n, kw in zip(sizes, sample_kws):
+        if L == 3:
+            top_k, top_p = (tuple(kw[k]) if kw.get(k) is not None else (None,) * 3 for k in ('top_k', 'top_p'))
+        else:
+            top_k, top_p = (kw.get('top_k_top'), kw.get('top_k_bot')), (kw.get('top_p_top'), kw.get('top_p_bot'))
+        t = kw.get('softmax_temperature')
+        temperature = tuple(float(v) for v in t) if t is not None else (1.0,) * L
+        if not (len(temperature) == len(top_k) == len(top_p) == L):
+            raise ValueError(f'sampler settings of a {L}-level step need {L} entries each, got {kw}')
+        rows.extend([(temperature, top_k, top_p)] * int(n))
+    return rows
 
 
 def decode_codes(stage1, codes: list, precision: Optional[str] = None, decode_batch: int = 0, top_resolution: int = 0) -> torch.Tensor:
@@ -87,10 +111,11 @@ class _Step(NamedTuple):
     order_after_current: bool
     sample_kw: dict
 
-    def settings(self) -> tuple:
-        """What the steps of one merged pass must share."""
+    def settings(self, mixed_samplers: bool = False) -> tuple:
+        """What the steps of one merged pass must share (``mixed_samplers``: all but the sampler settings, which then travel per row)."""
+        free = ('sample_offset',) + (SAMPLER_KEYS if mixed_samplers else ())
         return (self.max_seq_len, self.use_fp16, self.precision, self.clamp01, self.use_graph,
-                {k: v for k, v in self.sample_kw.items() if k != 'sample_offset'})
+                {k: v for k, v in self.sample_kw.items() if k not in free})
 
 
 class Pending:
@@ -108,11 +133,14 @@ class Pending:
 
 class InflightSampler:
     def __init__(self, model, lanes: int = 3, device: Optional[torch.device] = None, merge: int = 1, record_phases: bool = False,
-                 ar_high_priority: bool = False):
+                 ar_high_priority: bool = False, mixed_samplers: bool = False):
         if lanes < 1 or merge < 1:
             raise ValueError('lanes and merge must be >= 1')
         self.model = model
         self.merge = int(merge)
+        # merged steps may differ in top_k* / top_p* / softmax_temperature: every pass stages a row table on its lane (always, also when its steps
+        # happen to agree: the launch sequence, hence the captured graph, then never depends on what was queued)
+        self.mixed_samplers = bool(mixed_samplers)
         self.record_phases = bool(record_phases)     # merged passes: (AR start, AR end, decode end) events per pass, appended to phase_log
         self.phase_log: list = []
         self._queue: list = []
@@ -142,7 +170,10 @@ class InflightSampler:
             p = Pending()
             step = _Step(p, num_candidates, cond, seed, max_seq_len, use_fp16, precision, clamp01, use_graph, after, order_after_current, sample_kw)
             # checked HERE, before the step is queued: a mismatch raises without touching the queue (every Pending already handed out stays valid)
-            if self._queue and not _same(step.settings(), self._queue[0].settings()):
+            if self._queue and not _same(step.settings(self.mixed_samplers), self._queue[0].settings(self.mixed_samplers)):
+                if self.mixed_samplers:
+                    raise ValueError('steps of a mixed pass may differ in temperature, top-k and top-p only: max_seq_len, precision and every other '
+                                     'setting must match (flush() first to start a new pass)')
                 raise ValueError('steps merged into one pass must share max_seq_len, precision and sampler settings (flush() first to start a new pass)')
             self._queue.append(step)
             if len(self._queue) >= self.merge:
@@ -161,6 +192,9 @@ class InflightSampler:
         sizes = [e.num_candidates for e in q]
         los = [sum(sizes[:i]) for i in range(len(q))]
         kw = {k: v for k, v in ref.sample_kw.items() if k != 'sample_offset'}
+        if self.mixed_samplers:                      # every row keeps the sampler settings of its own step
+            kw = {k: v for k, v in kw.items() if k not in SAMPLER_KEYS}
+            kw['row_samplers'] = step_row_samplers(self.model.stage2.spec.levels, sizes, [e.sample_kw for e in q])
         offs = [int(e.sample_kw.get('sample_offset', 0)) for e in q]
         cond = None
         if self.model.stage2.use_txt_cond:           # [n, ctx_len_txt] token ids per step

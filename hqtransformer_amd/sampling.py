@@ -71,7 +71,8 @@ def sampling_ihqgpt(model,
                     lane: int = 0,
                     row_seeds=None,
                     row_offsets=None,
-                    precision: Optional[str] = None):
+                    precision: Optional[str] = None,
+                    row_samplers=None):
     """Returns ``(codes_top int64 [B, max_seq_len], codes_bot int64 [B, max_seq_len, 4])`` on the model's GPU.
 
     ``model`` is ``ImageGPT2.stage2``.  ``cond``: python int (class id, repeated for every candidate), an
@@ -84,6 +85,8 @@ def sampling_ihqgpt(model,
     several workspaces over the same weights (one per batch in flight, see ``hqtransformer_amd.pipeline``);
     ``row_seeds`` / ``row_offsets`` (B entries each): merged steps -- row b draws what global row ``row_offsets[b]`` of a call
     seeded ``row_seeds[b]`` would draw, so several independent calls can share one pass over the weights;
+    ``row_samplers`` (B entries ``(temperature per level, top_k per level, top_p per level)``, None = no cut-off): row b draws with its own
+    settings in place of ``top_k_*`` / ``top_p_*`` / ``softmax_temperature``, bit for bit as in a call that has them for every row;
     ``precision`` ('exact' | 'fast' | 'split') overrides ``use_fp16``: 'split' = the fp32 launch sequence with every nn.Linear on the
     matrix cores (fp16 hi / lo operands, three MFMAs per term, fp32 accumulation): code sequences bit-identical to 'exact' wherever the
     draw is well-conditioned, at several times its speed.
@@ -111,7 +114,7 @@ def sampling_ihqgpt(model,
     return eng.sample(B, cond, max_seq_len, precision=_precision(precision, use_fp16),
                       top_k=(top_k_top, top_k_bot), top_p=(top_p_top, top_p_bot), temperature=softmax_temperature,
                       noise=noise, seed=seed or 0, sample_offset=sample_offset, force_top=force_top, use_graph=use_graph,
-                      row_seeds=row_seeds, row_offsets=row_offsets)
+                      row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers)
 
 
 def sampling_hqtransformer(model,
@@ -131,11 +134,13 @@ def sampling_hqtransformer(model,
                            lane: int = 0,
                            row_seeds=None,
                            row_offsets=None,
-                           precision: Optional[str] = None):
+                           precision: Optional[str] = None,
+                           row_samplers=None):
     """Counterpart of ``hqvae.utils.sampling.sampling_hqtransformer`` (sampling.py:240-307) for the three-level
     HQTransformer: returns ``[codes0 int64 [B, L], codes1 [B, L, 4], codes2 [B, L, 16]]`` on the model's GPU.
     ``top_k`` / ``top_p`` / ``softmax_temperature`` are per-level lists (None = no cut-off); ``cond`` as in
-    ``sampling_ihqgpt``.  Extensions: ``noise`` fp32 [L, 21, B, V], ``seed`` / ``sample_offset``, ``lane``."""
+    ``sampling_ihqgpt``.  Extensions: ``noise`` fp32 [L, 21, B, V], ``seed`` / ``sample_offset``, ``lane``,
+    ``row_samplers`` (per-row settings, as in ``sampling_ihqgpt``)."""
     spec = model.spec
     if spec.levels != 3:
         raise ValueError('sampling_hqtransformer needs the three-level HQTransformer (stage2.type multilevel-hq)')
@@ -147,7 +152,7 @@ def sampling_hqtransformer(model,
         seed = _seed_from_torch()
     return list(eng.sample3(B, cond, max_seq_len, precision=_precision(precision, use_fp16), top_k=top_k, top_p=top_p,
                             temperature=softmax_temperature, noise=noise, seed=seed or 0, sample_offset=sample_offset, use_graph=use_graph,
-                            row_seeds=row_seeds, row_offsets=row_offsets))
+                            row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers))
 
 
 def rearrange_levels(codes: List[torch.Tensor], top_resolution: int) -> tuple:

@@ -200,6 +200,19 @@ int hqt_set_policy(hqt_handle* h, int policy);
 enum { HQT_SWITCH_PERSIST = 0, HQT_SWITCH_SINGLE_KEY = 1, HQT_SWITCH_PERSIST_FAULT = 2, HQT_SWITCH_SPLIT_KSLICES = 3 };
 int hqt_set_switch(hqt_handle* h, int which, int on);
 
+/* hqt_set_row_samplers -- no reference counterpart as a call: the reference filters and draws every row on its own (hqvae/utils/sampling.py:12-37 cut each
+ * row of the logits separately; hierarchical_ar.py:762-785, 866-873 apply one temperature / top-k / top-p triple per code level to the whole batch), so rows of
+ * ONE pass may carry the settings of different calls without changing what any of them draws.  Merged steps (row_seeds / row_offsets above) need exactly that
+ * when their calls differ in sampler settings.  `rows` is a HOST array of n entries, index = code level (a two-level model ignores index 2), copied before
+ * return; n = 0 or rows = NULL clears.  The table is STAGED on the handle (a lane from hqt_clone has its own): the next hqt_sample / hqt_sample_l3 on that
+ * handle takes it and clears it, whether that call succeeds or not.  That call then fails with HQT_ERR_INVALID unless n equals its B, every temperature it
+ * uses is > 0 and no row asks for top-p on a vocabulary above 8192; row b draws with rows[b] in place of the scalars of `opts` (which are ignored), through
+ * the same arithmetic as in a call whose scalars are rows[b]: bit-identical codes.  top_k <= 0 / top_p <= 0 mean None, as in hqt_sample_opts.  The
+ * bidirectional head keeps the reference's mapping per row: all five draws use temperature[0], top_k[1], top_p[1].  The values live in device memory, not in
+ * the captured graph: calls that differ only in the table replay one graph. */
+typedef struct { float temperature[3]; int32_t top_k[3]; float top_p[3]; } hqt_row_sampler;   /* 36 bytes */
+int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler* rows);
+
 /* hqt_sample -- replaces sampling_ihqgpt + iHQGPT.sampling_step (hqvae/utils/sampling.py:164-237,
  * hierarchical_ar.py:428-480, 482-563, 667-789) for a batch of B independent images.
  *   cond        int64 [B] class ids (HQT_COND_CLASS), int64 [B, ctx_len_txt] token ids
