@@ -121,6 +121,9 @@ struct hqt_handle {
     std::vector<BlockW> body, depth;
     Lin head_top, head_bot;
     int Tmax = 0;
+    int max_prefix = 0;                       // hqt_set_max_prefix: longest code prefix a call may pass (0: none); lanes inherit it
+    static constexpr int BODY_BUFS = 10;
+    size_t body_bytes[BODY_BUFS] = {};        // what alloc_body_rows allocated, in its order
     int depth_rows = 0;                       // keys of the depth cache: 5 (two code levels) or 21 (three)
     float *x = nullptr, *xd = nullptr, *logits = nullptr;
     void *hbuf = nullptr, *qbuf = nullptr, *abuf = nullptr, *mbuf = nullptr;    // fp32-sized, reused as bf16 in FAST
@@ -425,6 +428,51 @@ static int alloc_encode_workspace(hqt_handle* h) {
     return HQT_OK;
 }
 
+// The stage-2 buffers sized by the rows of the widest pass: the body's text prompt or prefix prefill (max_prefix + 1 rows per sample; 0: one
+// row) and the widest depth sub-step.  release_old (hqt_set_max_prefix): the handle's own earlier set goes first.
+static int alloc_body_rows(hqt_handle* h, bool release_old) {
+    const hqt_config& c = h->cfg;
+    const size_t B = (size_t)c.max_batch, D = c.embed_dim;
+    const int Tp = c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : (h->max_prefix > 0 ? h->max_prefix + 1 : 1);    // rows per sample of the widest body pass
+    const int Tdepth = c.code_levels == 3 ? 16 : (c.depth_decoding == HQT_DEPTH_BIDIRECTIONAL ? 5 : 4);
+    const size_t rows = (B * (size_t)std::max(Tp, Tdepth) + 31) / 32 * 32;
+    // packed_off() buffers are addressed with a row stride of 32 * packed_mb(M) (32 / 64 / ... / 4096 rows), which can
+    // exceed round32(M): size them for the widest padded block any M <= PACKED_MAX_ROWS pass can use
+    size_t rows_pk = 256;
+    while (rows_pk < rows && rows_pk < (size_t)PACKED_MAX_ROWS) rows_pk *= 2;
+    rows_pk = std::max(rows_pk, rows);
+    h->splitk_elems = (size_t)16 * rows * (size_t)std::max<size_t>(4 * D, (size_t)c.vocab_top);
+    void** const bufs[hqt_handle::BODY_BUFS] = {(void**)&h->x, &h->hbuf, &h->qbuf, &h->abuf, &h->mbuf, (void**)&h->splitk,
+                                                (void**)&h->xpk, (void**)&h->xdpk, (void**)&h->parts, (void**)&h->partsd};
+    const size_t bytes[hqt_handle::BODY_BUFS] = {rows * D * 4, rows * D * 4, rows * D * 4, rows * D * 4, rows * 4 * D * 4, h->splitk_elems * 4,
+                                                 rows_pk * D * 2, rows_pk * D * 2, (D / 32 + 1) * rows_pk * 2 * 4, (D / 32 + 1) * rows_pk * 2 * 4};
+    for (int i = 0; i < hqt_handle::BODY_BUFS; ++i) {
+        if (release_old && *bufs[i]) {
+            HIPCHK(hipFree(*bufs[i]));
+            h->owned.erase(std::remove(h->owned.begin(), h->owned.end(), *bufs[i]), h->owned.end());
+            h->workspace_bytes -= h->body_bytes[i];
+            *bufs[i] = nullptr;
+        }
+        CHK(dev_alloc(h, bufs[i], bytes[i], true));
+        h->body_bytes[i] = bytes[i];
+    }
+    return HQT_OK;
+}
+
+extern "C" int hqt_set_max_prefix(hqt_handle* h, int max_prefix) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    const hqt_config& c = h->cfg;
+    if (!c.has_stage2) return fail(HQT_ERR_INVALID, "hqt_set_max_prefix: the handle was created without stage 2");
+    if (h->finalized || h->parent) return fail(HQT_ERR_STATE, "hqt_set_max_prefix comes between hqt_create and hqt_finalize_weights (lanes inherit the value)");
+    if (max_prefix < 0 || max_prefix > c.max_steps - 1) return fail(HQT_ERR_INVALID, "max_prefix=%d outside [0, max_steps - 1 = %d]", max_prefix, c.max_steps - 1);
+    // the MFMA prefill kernel has been shown to take the text prompt alone (up to 64 rows per sample): prompt + prefix is not built
+    if (max_prefix && c.cond_type == HQT_COND_TEXT) return fail(HQT_ERR_INVALID, "max_prefix with text conditioning is not built");
+    if (max_prefix == h->max_prefix) return HQT_OK;
+    ON_DEVICE(h);
+    h->max_prefix = max_prefix;
+    return alloc_body_rows(h, true);
+}
+
 static int alloc_workspace(hqt_handle* hp) {
     struct { hqt_handle* p; hqt_handle* get() const { return p; } hqt_handle* operator->() const { return p; } } h{hp};
     const hqt_config& c = h->cfg;
@@ -437,17 +485,11 @@ static int alloc_workspace(hqt_handle* hp) {
     HIPCHK(hipMemset(h->range_flag, 0, 256));
     if (c.has_stage2) {
         const size_t D = c.embed_dim;
-        const int Tp = c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : 1;    // rows of the widest body pass
         h->Tmax = (c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : 0) + c.max_steps;
         const int Tdepth = c.code_levels == 3 ? 16 : (c.depth_decoding == HQT_DEPTH_BIDIRECTIONAL ? 5 : 4);      // rows per sample of the widest depth sub-step
         h->depth_rows = c.code_levels == 3 ? 21 : 5;
-        const size_t rows = (B * (size_t)std::max(Tp, Tdepth) + 31) / 32 * 32;
-        CHK(dev_alloc(h.get(), (void**)&h->x, rows * D * 4, true));
+        CHK(alloc_body_rows(h.get(), false));
         CHK(dev_alloc(h.get(), (void**)&h->xd, B * Tdepth * D * 4, true));
-        CHK(dev_alloc(h.get(), &h->hbuf, rows * D * 4, true));
-        CHK(dev_alloc(h.get(), &h->qbuf, rows * D * 4, true));
-        CHK(dev_alloc(h.get(), &h->abuf, rows * D * 4, true));
-        CHK(dev_alloc(h.get(), &h->mbuf, rows * 4 * D * 4, true));
         CHK(dev_alloc(h.get(), (void**)&h->logits, B * Tdepth * (size_t)c.vocab_top * 4, true));
         const size_t kv = (size_t)c.n_layers * B * h->Tmax * D * 4;
         CHK(dev_alloc(h.get(), &h->kcache, kv, true));
@@ -455,8 +497,6 @@ static int alloc_workspace(hqt_handle* hp) {
         const size_t dkv = (size_t)c.n_layers_depth * B * h->depth_rows * D * 4;
         CHK(dev_alloc(h.get(), &h->dk, dkv, true));
         CHK(dev_alloc(h.get(), &h->dv, dkv, true));
-        h->splitk_elems = (size_t)16 * rows * (size_t)std::max<size_t>(4 * D, (size_t)c.vocab_top);
-        CHK(dev_alloc(h.get(), (void**)&h->splitk, h->splitk_elems * 4, true));
         CHK(dev_alloc(h.get(), (void**)&h->state, sizeof(StepState), true));
         CHK(dev_alloc(h.get(), (void**)&h->rows, B * sizeof(RowKey), true));
         CHK(dev_alloc(h.get(), (void**)&h->row_set, B * sizeof(RowSampler), true));
@@ -464,15 +504,6 @@ static int alloc_workspace(hqt_handle* hp) {
         CHK(dev_alloc(h.get(), (void**)&h->codes_top, B * (size_t)c.max_steps * 8, true));
         CHK(dev_alloc(h.get(), (void**)&h->codes_bot, B * (size_t)c.max_steps * 4 * 8, true));
         if (c.code_levels == 3) CHK(dev_alloc(h.get(), (void**)&h->codes_l2, B * (size_t)c.max_steps * 16 * 8, true));
-        // packed_off() buffers are addressed with a row stride of 32 * packed_mb(M) (32 / 64 / ... / 4096 rows), which can
-        // exceed round32(M): size them for the widest padded block any M <= PACKED_MAX_ROWS pass can use
-        size_t rows_pk = 256;
-        while (rows_pk < rows && rows_pk < (size_t)PACKED_MAX_ROWS) rows_pk *= 2;
-        rows_pk = std::max(rows_pk, rows);
-        CHK(dev_alloc(h.get(), (void**)&h->xpk, rows_pk * D * 2, true));
-        CHK(dev_alloc(h.get(), (void**)&h->xdpk, rows_pk * D * 2, true));
-        CHK(dev_alloc(h.get(), (void**)&h->parts, (D / 32 + 1) * rows_pk * 2 * 4, true));
-        CHK(dev_alloc(h.get(), (void**)&h->partsd, (D / 32 + 1) * rows_pk * 2 * 4, true));
         if (!h->parent) {                        // the persistent chain runs on root handles only (persist_on)
             CHK(dev_alloc(h.get(), (void**)&h->persist_counters, PERSIST_COUNTER_BYTES, true));
             CHK(dev_alloc(h.get(), (void**)&h->persist_err, 256, true));
@@ -1055,6 +1086,9 @@ struct SampleCtx {
     const float* noise;
     const int64_t* feed[3] = {nullptr, nullptr, nullptr};   // codes each level's embeddings read: the drawn ones (out) or the forced ones
     int64_t* out[3] = {nullptr, nullptr, nullptr};
+    int prefix_len = 0;                          // hqt_sample_prefix: positions [0, prefix_len) are given ...
+    const int64_t* prefix[3] = {nullptr, nullptr, nullptr};   // ... as [B, prefix_len], [B, prefix_len, 4][, [B, prefix_len, 16]]
+    bool with_prefix = false;                    // the call came through a prefix entry point (prefix_len is then validated)
     float* logits_out;
     hipStream_t st;
     Mode md;
@@ -1520,18 +1554,24 @@ static int layout_check(const hqt_handle* h, const Mode& md) {
     return HQT_OK;
 }
 
-static int run_decode_step(hqt_handle* h, const SampleCtx& c) {      // one KV-cached position, Tq = 1
+// What the body-input embedding reads: the tables, cond and the codes of every level in `codes` ([B, n_steps(, 4 | 16)])
+static EmbedArgs embed_args(hqt_handle* h, const SampleCtx& c, const int64_t* const* codes) {
     const hqt_config& cf = h->cfg;
+    EmbedArgs e{c.B, cf.embed_dim, c.n_steps, cf.embedding_type, cf.cond_type, h->state, c.cond,
+                cf.cond_type == HQT_COND_CLASS ? W(h, "sos.weight") : (cf.cond_type == HQT_COND_NONE ? W(h, "sos") : nullptr),
+                W(h, "tok_emb_top.weight"), W(h, "tok_emb_bot.weight"), W(h, "pos_emb_top.weight"),
+                cf.embedding_type == HQT_EMB_TRANSFORMER1 ? W(h, "pos_emb_emb.weight") : nullptr,
+                codes[0], codes[1], h->x, nullptr, 0, h->parts};
+    if (c.levels == 3) { e.levels = 3; e.tok_l2 = W(h, "tok_emb_levels.2.weight"); e.codes_l2 = codes[2]; }
+    e.V = cf.vocab_top; e.n_classes = cf.n_classes;
+    return e;
+}
+
+static int run_decode_step(hqt_handle* h, const SampleCtx& c) {      // one KV-cached position, Tq = 1
     {
         Timed t(h, "embed", c.st);
-        EmbedArgs e{c.B, cf.embed_dim, c.n_steps, cf.embedding_type, cf.cond_type, h->state, c.cond,
-                    cf.cond_type == HQT_COND_CLASS ? W(h, "sos.weight") : (cf.cond_type == HQT_COND_NONE ? W(h, "sos") : nullptr),
-                    W(h, "tok_emb_top.weight"), W(h, "tok_emb_bot.weight"), W(h, "pos_emb_top.weight"),
-                    cf.embedding_type == HQT_EMB_TRANSFORMER1 ? W(h, "pos_emb_emb.weight") : nullptr,
-                    c.feed[0], c.feed[1], h->x, nullptr, 0, h->parts};
+        EmbedArgs e = embed_args(h, c, c.feed);
         if (dln_ok(h, c, h->body[0], c.B)) { e.xpk = h->xpk; e.pk_mb = packed_mb(c.B); h->nparts = 1; }
-        if (c.levels == 3) { e.levels = 3; e.tok_l2 = W(h, "tok_emb_levels.2.weight"); e.codes_l2 = c.feed[2]; }
-        e.V = cf.vocab_top; e.n_classes = cf.n_classes;
         HIPCHK(launch_embed_step(e, c.st));
     }
     CHK(run_position(h, c, 1, 0, true));
@@ -1558,6 +1598,14 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     if (B < 1 || B > cf.max_batch) return fail(HQT_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cf.max_batch);
     if (c.n_steps < 1 || c.n_steps > cf.max_steps) return fail(HQT_ERR_INVALID, "n_steps=%d outside [1, %d]", c.n_steps, cf.max_steps);
     if (cf.cond_type != HQT_COND_NONE && !cond) return fail(HQT_ERR_INVALID, "cond is required for class/text conditioning");
+    if (c.with_prefix) {
+        if (cf.cond_type == HQT_COND_TEXT) return fail(HQT_ERR_INVALID, "a code prefix with text conditioning is not built");
+        if (c.prefix_len < 1 || c.prefix_len >= c.n_steps)
+            return fail(HQT_ERR_INVALID, "prefix_len=%d outside [1, n_steps - 1 = %d]: at least one position must be left to draw", c.prefix_len, c.n_steps - 1);
+        if (c.prefix_len > h->max_prefix)
+            return fail(HQT_ERR_INVALID, "prefix_len=%d exceeds max_prefix=%d of this handle (hqt_set_max_prefix sizes the body workspace for max_prefix + 1 rows per sample)", c.prefix_len, h->max_prefix);
+        for (int i = 0; i < c.levels; ++i) if (!c.prefix[i]) return fail(HQT_ERR_INVALID, "prefix codes of level %d are NULL", i);
+    }
     if (c.row_set) {                             // per-row settings replace the scalars of `opts`: those are neither checked nor part of the graph key
         if ((int)staged_rows != B) return fail(HQT_ERR_INVALID, "hqt_set_row_samplers staged %d rows, this call has B=%d", (int)staged_rows, B);
         for (int i = 0; i < 3; ++i) c.lv[i] = SamplerSet();
@@ -1585,8 +1633,12 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     CHK(mode_of(c.precision, false, &c.md));
     CHK(layout_check(h, c.md));
     if (cond) HIPCHK(hipMemcpyAsync(h->cond_buf, cond, (size_t)B * (cf.cond_type == HQT_COND_TEXT ? cf.ctx_len_txt : 1) * 8, hipMemcpyDefault, c.st));
-    CHK(sample_run(h, c));
     static const size_t width[3] = {1, 4, 16};
+    // the prefix goes into the handle's code buffers (outside any captured graph): the prefill's embedding, the embedding of position
+    // prefix_len + 1 and the copies below read it there
+    for (int i = 0; i < (c.prefix_len ? c.levels : 0); ++i)
+        HIPCHK(launch_copy_prefix(c.prefix[i], codes[i], B, c.prefix_len, c.n_steps, (int)width[i], cf.vocab_top, c.st));
+    CHK(sample_run(h, c));
     for (int i = 0; i < c.levels; ++i)
         HIPCHK(hipMemcpyAsync(out[i], codes[i], (size_t)B * c.n_steps * width[i] * 8, hipMemcpyDeviceToDevice, c.st));
     return HQT_OK;
@@ -1612,29 +1664,59 @@ extern "C" int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler*
     return HQT_OK;
 }
 
-extern "C" int hqt_sample(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts* opts, const float* noise,
-                          const int64_t* force_top, const int64_t* force_bot, float* logits_out, int64_t* out_top,
-                          int64_t* out_bot, void* stream) {
+// prefix_len < 0: no prefix (hqt_sample / hqt_sample_l3); otherwise the call came through a prefix entry point and prefix_len is validated
+static int sample2(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts* opts, const float* noise, int prefix_len,
+                   const int64_t* prefix_top, const int64_t* prefix_bot, const int64_t* force_top, const int64_t* force_bot,
+                   float* logits_out, int64_t* out_top, int64_t* out_bot, void* stream) {
     if (h && (!opts || !out_top || !out_bot)) h->row_set_staged.clear();
     if (!h || !opts || !out_top || !out_bot) return fail(HQT_ERR_INVALID, "null argument");
     SampleCtx c = sample_ctx(2, B, opts, noise, logits_out);
     c.lv[0] = {opts->temperature_top, opts->top_k_top, opts->top_p_top};
     c.lv[1] = {opts->temperature_bot, opts->top_k_bot, opts->top_p_bot};
     c.feed[0] = force_top; c.feed[1] = force_bot;
+    if (prefix_len >= 0) { c.with_prefix = true; c.prefix_len = prefix_len; c.prefix[0] = prefix_top; c.prefix[1] = prefix_bot; }
     int64_t* const out[2] = {out_top, out_bot};
     return sample_call(h, c, cond, out, stream);
 }
 
-extern "C" int hqt_sample_l3(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts_l3* opts, const float* noise,
-                             const int64_t* force0, const int64_t* force1, const int64_t* force2, float* logits_out,
-                             int64_t* out0, int64_t* out1, int64_t* out2, void* stream) {
+static int sample3(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts_l3* opts, const float* noise, int prefix_len,
+                   const int64_t* const* prefix, const int64_t* force0, const int64_t* force1, const int64_t* force2, float* logits_out,
+                   int64_t* out0, int64_t* out1, int64_t* out2, void* stream) {
     if (h && (!opts || !out0 || !out1 || !out2)) h->row_set_staged.clear();
     if (!h || !opts || !out0 || !out1 || !out2) return fail(HQT_ERR_INVALID, "null argument");
     SampleCtx c = sample_ctx(3, B, opts, noise, logits_out);
     for (int i = 0; i < 3; ++i) c.lv[i] = {opts->temperature[i], opts->top_k[i], opts->top_p[i]};
     c.feed[0] = force0; c.feed[1] = force1; c.feed[2] = force2;
+    if (prefix_len >= 0) { c.with_prefix = true; c.prefix_len = prefix_len; for (int i = 0; i < 3; ++i) c.prefix[i] = prefix[i]; }
     int64_t* const out[3] = {out0, out1, out2};
     return sample_call(h, c, cond, out, stream);
+}
+
+extern "C" int hqt_sample(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts* opts, const float* noise,
+                          const int64_t* force_top, const int64_t* force_bot, float* logits_out, int64_t* out_top,
+                          int64_t* out_bot, void* stream) {
+    return sample2(h, B, cond, opts, noise, -1, nullptr, nullptr, force_top, force_bot, logits_out, out_top, out_bot, stream);
+}
+
+extern "C" int hqt_sample_prefix(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts* opts, const float* noise,
+                                 int prefix_len, const int64_t* prefix_top, const int64_t* prefix_bot,
+                                 const int64_t* force_top, const int64_t* force_bot, float* logits_out,
+                                 int64_t* out_top, int64_t* out_bot, void* stream) {
+    return sample2(h, B, cond, opts, noise, std::max(prefix_len, 0), prefix_top, prefix_bot, force_top, force_bot, logits_out, out_top, out_bot, stream);
+}
+
+extern "C" int hqt_sample_l3(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts_l3* opts, const float* noise,
+                             const int64_t* force0, const int64_t* force1, const int64_t* force2, float* logits_out,
+                             int64_t* out0, int64_t* out1, int64_t* out2, void* stream) {
+    return sample3(h, B, cond, opts, noise, -1, nullptr, force0, force1, force2, logits_out, out0, out1, out2, stream);
+}
+
+extern "C" int hqt_sample_prefix_l3(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts_l3* opts, const float* noise,
+                                    int prefix_len, const int64_t* prefix0, const int64_t* prefix1, const int64_t* prefix2,
+                                    const int64_t* force0, const int64_t* force1, const int64_t* force2, float* logits_out,
+                                    int64_t* out0, int64_t* out1, int64_t* out2, void* stream) {
+    const int64_t* const prefix[3] = {prefix0, prefix1, prefix2};
+    return sample3(h, B, cond, opts, noise, std::max(prefix_len, 0), prefix, force0, force1, force2, logits_out, out0, out1, out2, stream);
 }
 
 // Persistent launches need every compute unit of the device: two of them in flight at once (two root handles sampling on two streams)
@@ -1702,6 +1784,23 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         CHK(run_position(h, c, T, 0, false));
         HIPCHK(launch_advance_step(h->state, T, c.st));
         first = 1;
+    }
+    if (c.prefix_len) {
+        // Prefix prefill: the P + 1 body input rows of every sample (sos, then the embeddings of positions 0 .. P - 1, read from the
+        // handle's code buffers) in one launch, all body blocks causally over them -- K/V of all rows go to the cache --, the depth
+        // head on the last row, which draws position P: the step state says P while that pass runs (sampler keys, noise slice, where
+        // the codes go), and P + 1 over P + 1 keys afterwards.  Like the text prefill the pass takes the classic path (Tq_body > 1:
+        // run_body); the persistent chain first reads the step state in the decode steps below, behind the advance.
+        const int P = c.prefix_len;
+        const int64_t* const own[3] = {h->codes_top, h->codes_bot, h->codes_l2};
+        HIPCHK(launch_set_step(h->state, P, 0, c.st));
+        {
+            Timed t(h, "embed_prefix", c.st);
+            HIPCHK(launch_embed_prefix(embed_args(h, c, own), P + 1, c.st));
+        }
+        CHK(run_position(h, c, P + 1, 0, false));
+        HIPCHK(launch_advance_step(h->state, P + 1, c.st));
+        first = P + 1;
     }
     const int remaining = c.n_steps - first;
     if (remaining <= 0) return HQT_OK;

@@ -36,6 +36,11 @@ struct EmbedArgs {
     int V, n_classes;            // table sizes for the index clamp (0: unchecked)
 };
 hipError_t launch_embed_step(const EmbedArgs& a, hipStream_t st);
+// prefix prefill: x[b * rows_per_sample + j] = body input row j of sample b (row 0: sos; row j: position j - 1's codes), the arithmetic of
+// launch_embed_step; `state` is not read and no packed copy is written
+hipError_t launch_embed_prefix(const EmbedArgs& a, int rows_per_sample, hipStream_t st);
+// dst[b, p < P, :] = src[b, p, :] for one code level (dst [B, n_steps, width], src [B, P, width]), clamped into [0, V)
+hipError_t launch_copy_prefix(const int64_t* src, int64_t* dst, int B, int P, int n_steps, int width, int V, hipStream_t st);
 
 // text prefix: x[b, t, :] = tok_emb_txt[cond[b, t]] + pos_emb_txt[t]
 hipError_t launch_embed_text(const int64_t* cond, const float* tok, const float* pos, float* x, int B, int T, int D,

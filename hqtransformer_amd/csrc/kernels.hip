@@ -69,15 +69,13 @@ hipError_t launch_set_step(StepState* s, int step, int t_base, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------
 // A3/K1: input embedding of one top position (hierarchical_ar.py:493-544)
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void embed_step_kernel(EmbedArgs a) {
-    __shared__ float red[4];
-    const int b = blockIdx.x, D = a.D;
-    const int step = a.state->step;
-    float* x = a.x + (long long)b * D;
+// Body input row `step` of sample b: the sos row (step 0), else the embedding of position step - 1's codes with pos_emb_top[step - 1].
+// The ONE place that does this arithmetic: the decode step and the prefix prefill both call it, so a row is bit-identical whichever wrote it.
+__device__ __forceinline__ void embed_row(const EmbedArgs& a, int b, int step, float* x) {
+    const int D = a.D;
     if (step == 0) {
         const float* src = a.cond_type == 1 ? a.sos + clamp_idx(a.cond[b], a.n_classes) * (long long)D : a.sos;
         for (int d = threadIdx.x; d < D; d += blockDim.x) x[d] = src[d];
-        if (a.xpk) { __syncthreads(); emit_packed_row(x, b, D, a.xpk, a.pk_mb, a.parts, red); }
         return;
     }
     const int p = step - 1;
@@ -111,10 +109,45 @@ __global__ __launch_bounds__(256) void embed_step_kernel(EmbedArgs a) {
             x[d] = s / 5.0f;
         }
     }
-    if (a.xpk) { __syncthreads(); emit_packed_row(x, b, D, a.xpk, a.pk_mb, a.parts, red); }
+}
+
+__global__ __launch_bounds__(256) void embed_step_kernel(EmbedArgs a) {
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    float* x = a.x + (long long)b * a.D;
+    embed_row(a, b, a.state->step, x);
+    if (a.xpk) { __syncthreads(); emit_packed_row(x, b, a.D, a.xpk, a.pk_mb, a.parts, red); }
 }
 hipError_t launch_embed_step(const EmbedArgs& a, hipStream_t st) {
     embed_step_kernel<<<a.B, 256, 0, st>>>(a);
+    return hipGetLastError();
+}
+
+// Prefix prefill: the rows_per_sample = P + 1 body input rows of every sample in one launch, x[b * (P + 1) + j] = embed_row(b, j) -- row 0 the
+// sos row, row j the input the decode step at position j would have computed from the codes of position j - 1 (a.codes_*: the handle's
+// code buffers, which hold the prefix).  One workgroup per row; no packed copy (the prefill pass takes the classic LayerNorm path).
+__global__ __launch_bounds__(256) void embed_prefix_kernel(EmbedArgs a, int rows_per_sample) {
+    const int row = blockIdx.x, b = row / rows_per_sample, j = row - b * rows_per_sample;
+    embed_row(a, b, j, a.x + (long long)row * a.D);
+}
+hipError_t launch_embed_prefix(const EmbedArgs& a, int rows_per_sample, hipStream_t st) {
+    if (rows_per_sample < 2 || rows_per_sample > a.n_steps || a.xpk) return hipErrorInvalidValue;
+    embed_prefix_kernel<<<a.B * rows_per_sample, 256, 0, st>>>(a, rows_per_sample);
+    return hipGetLastError();
+}
+
+// The prefix codes of one level, [B, P, width], into the first P positions of the handle's [B, n_steps, width] code buffer (clamped into
+// the vocabulary like every index that arrives from the caller)
+__global__ __launch_bounds__(256) void copy_prefix_kernel(const int64_t* src, int64_t* dst, long long n, int per_sample, int dst_per_sample, int V) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long b = i / per_sample, r = i - b * per_sample;
+    dst[b * dst_per_sample + r] = clamp_idx(src[i], V);
+}
+hipError_t launch_copy_prefix(const int64_t* src, int64_t* dst, int B, int P, int n_steps, int width, int V, hipStream_t st) {
+    if (P < 1 || P > n_steps) return hipErrorInvalidValue;
+    const long long n = (long long)B * P * width;
+    copy_prefix_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(src, dst, n, P * width, n_steps * width, V);
     return hipGetLastError();
 }
 

@@ -87,14 +87,48 @@ _FORCE_NAMES = {2: ('force_top', 'force_bot'), 3: ('force[0]', 'force[1]', 'forc
 _CODE_NAMES = {2: ('code_t', 'code_b'), 3: ('code grid',) * 3}
 
 
+def check_prefix(s2: Stage2Spec, batch: int, n_steps: int, prefix, max_prefix: Optional[int] = None) -> Optional[list]:
+    """A code prefix checked on the host, before any engine is built or touched: ``prefix`` is the list of code levels, coarse to fine,
+    int64 [B, P], [B, P, 4][, [B, P, 16]] with 1 <= P <= n_steps - 1 (and P <= ``max_prefix`` when given); every code inside the vocabulary
+    (IndexError otherwise, as nn.Embedding raises in the reference).  Returns the levels as tensors; None stays None."""
+    if prefix is None:
+        return None
+    if s2.cond == 2:
+        raise ValueError('a code prefix with text conditioning is not built (the prompt and the prefix would share one prefill)')
+    L = s2.levels
+    if not isinstance(prefix, (list, tuple)) or len(prefix) != L:
+        raise ValueError(f'prefix: expected the {L} code levels as one list, coarse to fine')
+    levels = [torch.as_tensor(p) for p in prefix]
+    if levels[0].dim() != 2 or int(levels[0].shape[0]) != int(batch):
+        raise ValueError(f'prefix[0]: expected shape ({int(batch)}, P), got {tuple(levels[0].shape)}')
+    P = int(levels[0].shape[1])
+    if P < 1 or P >= int(n_steps):
+        raise ValueError(f'prefix of P={P} positions: P must lie in [1, n_steps - 1 = {int(n_steps) - 1}] (at least one position is left to draw)')
+    if max_prefix is not None and P > int(max_prefix):
+        raise ValueError(f'prefix of P={P} positions exceeds max_prefix={int(max_prefix)} of this engine')
+    for l, t in enumerate(levels):
+        want = (int(batch), P) + ((4 ** l,) if l else ())
+        if tuple(t.shape) != want:
+            raise ValueError(f'prefix[{l}]: expected shape {want}, got {tuple(t.shape)}')
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError(f'prefix[{l}]: expected integer codes, got {t.dtype}')
+        if not t.is_cuda:                            # device tensors are checked (once) by the engine: Engine._check_index
+            lo, hi = int(t.min()), int(t.max())
+            if lo < 0 or hi >= s2.vocab_top:
+                raise IndexError(f'prefix[{l}]: index out of range (values span [{lo}, {hi}], table has {s2.vocab_top} rows)')
+    return levels
+
+
 class Engine:
     """One libhqt handle on one GPU.  Not thread-safe; asynchronous on torch's current stream."""
 
     def __init__(self, s2: Optional[Stage2Spec], s1: Optional[Stage1Spec], device: torch.device, max_batch: int,
-                 max_steps: Optional[int] = None, ar_layouts: int = 0):
+                 max_steps: Optional[int] = None, ar_layouts: int = 0, max_prefix: int = 0):
         """``ar_layouts``: bit mask of ``_lib.LAYOUT_*`` -- which derived layouts of the AR loop's weights ``finalize`` builds
         (``hqt_config.ar_layouts``; 0 = all).  A FAST-only replica passes ``_lib.LAYOUT_FAST`` and holds 5.2 instead of 9.1 GB for the
-        ImageNet-12L model; a call in a precision the engine was built without raises HqtError (HQT_ERR_STATE)."""
+        ImageNet-12L model; a call in a precision the engine was built without raises HqtError (HQT_ERR_STATE).
+        ``max_prefix``: longest code prefix ``sample(..., prefix=...)`` may pass (``hqt_set_max_prefix``, called right after ``hqt_create``; 0 = none, and the workspace
+        is exactly what it is without the feature)."""
         self.lib = _lib.load()                      # raises HqtLibraryError when the HIP library is absent
         self.s2, self.s1 = s2, s1
         self.device = torch.device(device)
@@ -102,11 +136,15 @@ class Engine:
             raise _lib.HqtLibraryError(f'libhqt runs on an MI355X only; got device {self.device} (no CPU fallback)')
         self.max_batch = int(max_batch)
         self.max_steps = int(max_steps if max_steps is not None else (s2.ctx_len_img if s2 else 1))
+        self.max_prefix = int(max_prefix)
         self.cfg = make_config(s2, s1, self.max_batch, self.max_steps, ar_layouts)
         h = C.c_void_p()
         _lib.check(self.lib.hqt_create(C.byref(self.cfg), self.device.index or 0, C.byref(h)))
         self.h = h
         self.finalized = False
+        if self.max_prefix:
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.hqt_set_max_prefix(self.h, self.max_prefix))
         self.policy = _lib.POLICY_LATENCY
 
     def clone(self) -> 'Engine':
@@ -116,7 +154,7 @@ class Engine:
             raise _lib.HqtError(-1, 'clone() needs a finalized engine')
         e = Engine.__new__(Engine)
         e.lib, e.s2, e.s1, e.device = self.lib, self.s2, self.s1, self.device
-        e.max_batch, e.max_steps, e.cfg = self.max_batch, self.max_steps, self.cfg
+        e.max_batch, e.max_steps, e.max_prefix, e.cfg = self.max_batch, self.max_steps, self.max_prefix, self.cfg
         h = C.c_void_p()
         _lib.check(self.lib.hqt_clone(self.h, C.byref(h)))
         e.h, e.finalized = h, True
@@ -278,10 +316,12 @@ class Engine:
     # Code levels are lists, coarse to fine; their number (2: hqt_sample, 3: hqt_sample_l3) is all that differs below.
     def _sample_levels(self, levels: int, batch: int, cond, n_steps: int, *, precision, top_k, top_p, temperature, noise, seed, sample_offset,
                        force: Sequence[Optional[torch.Tensor]], out: Optional[Sequence[torch.Tensor]], return_logits, use_graph,
-                       row_seeds, row_offsets, row_samplers=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor]]:
+                       row_seeds, row_offsets, row_samplers=None, prefix=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor]]:
         """Returns (codes [B, n], [B, n, 4][, [B, n, 16]], logits [n, draws, B, V] or None)."""
         dev = self.device
         B, V, L = int(batch), self.s2.vocab_top, int(levels)
+        prefix = check_prefix(self.s2, B, n_steps, prefix, self.max_prefix)
+        P = 0 if prefix is None else int(prefix[0].shape[1])
         draws = (4 ** L - 1) // 3                   # one draw per code of a position: 1 + 4 (+ 16)
         shapes = [(B, n_steps) + ((4 ** l,) if l else ()) for l in range(L)]
         o = hqt_sample_opts() if L == 2 else hqt_sample_opts_l3()
@@ -299,12 +339,21 @@ class Engine:
         cond = self._prep_cond(cond, B)
         noise = self._prep(noise, (n_steps, draws, B, V), torch.float32, 'noise')
         force = [self._prep(f, shp, torch.int64, what, V) for f, shp, what in zip(force, shapes, _FORCE_NAMES[L])]
+        if prefix is not None:
+            prefix = [self._prep(p, (B, P) + shp[2:], torch.int64, f'prefix[{l}]', V) for l, (p, shp) in enumerate(zip(prefix, shapes))]
         if out is None:
             outs = [torch.empty(shp, dtype=torch.int64, device=dev) for shp in shapes]
         else:
             outs = [self._check_out(t, shp, torch.int64, dev, f'out[{i}]') for i, (t, shp) in enumerate(zip(out, shapes))]
-        logits = torch.empty((n_steps, draws, B, V), dtype=torch.float32, device=dev) if return_logits else None
-        fn = self.lib.hqt_sample if L == 2 else self.lib.hqt_sample_l3
+        # (with a prefix the rows of positions < P are not written: zeros)
+        logits = (torch.zeros if P else torch.empty)((n_steps, draws, B, V), dtype=torch.float32, device=dev) if return_logits else None
+        if P:
+            entry = self.lib.hqt_sample_prefix if L == 2 else self.lib.hqt_sample_prefix_l3
+
+            def fn(h, b, cnd, opts, nz, *rest):
+                return entry(h, b, cnd, opts, nz, P, *map(_ptr, prefix), *rest)
+        else:
+            fn = self.lib.hqt_sample if L == 2 else self.lib.hqt_sample_l3
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
             if table is not None:                   # staged on the handle; the call below takes it (and clears it even when it fails)
@@ -312,7 +361,7 @@ class Engine:
             _lib.check(fn(self.h, B, _ptr(cond), C.byref(o), _ptr(noise), *map(_ptr, force), _ptr(logits), *map(_ptr, outs), C.c_void_p(stream)))
             self._note_split(precision, stream, ar_rows=B)        # every head runs persistently (run_position)
         # inputs must outlive the asynchronous launches
-        self._keep = (cond, noise, force, rows)     # (the row-sampler table was copied by hqt_set_row_samplers)
+        self._keep = (cond, noise, force, rows, prefix)     # (the row-sampler table was copied by hqt_set_row_samplers)
         self._trust(*outs, bound=max(self.s2.vocab_top, self.s2.vocab_bot))     # the sampler only writes ids inside the vocabulary
         return outs, logits
 
@@ -323,8 +372,11 @@ class Engine:
                return_logits: bool = False, use_graph: bool = True,
                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
-               row_samplers: Optional[Sequence[tuple]] = None):
+               row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None):
         """Two-level sampling: returns (codes_top [B, n], codes_bot [B, n, 4][, logits [n, 5, B, V]]).
+        ``prefix`` = [top [B, P], bot [B, P, 4]], 1 <= P <= min(n - 1, max_prefix of this engine): completion (``hqt_sample_prefix``) -- the
+        returned codes hold the prefix at positions < P, and positions >= P are drawn as a free run would draw them had its first P positions
+        produced these codes (same Philox keys, same slice of ``noise``, same sampler settings); the prefix runs through the body in ONE pass.
         ``row_seeds`` / ``row_offsets`` (both or neither, ``batch`` entries): merged steps -- row b draws what the row with
         global index ``row_offsets[b]`` of a call seeded ``row_seeds[b]`` draws (``hqt_sample_opts.row_seeds``).
         ``row_samplers`` (``batch`` entries ``(temperature per level, top_k per level, top_p per level)``, see ``row_sampler_table``): row b
@@ -335,7 +387,7 @@ class Engine:
         outs, logits = self._sample_levels(2, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(force_top, force_bot), out=out,
                                            return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
-                                           row_samplers=row_samplers)
+                                           row_samplers=row_samplers, prefix=prefix)
         return (outs[0], outs[1], logits) if return_logits else (outs[0], outs[1])
 
     def sample3(self, batch: int, cond: Optional[torch.Tensor], n_steps: int, *, precision: int = PRECISION_FAST,
@@ -343,12 +395,13 @@ class Engine:
                 temperature: Sequence[float] = (1.0, 1.0, 1.0), noise: Optional[torch.Tensor] = None, seed: int = 0,
                 sample_offset: int = 0, force: Optional[Sequence[torch.Tensor]] = None, return_logits: bool = False,
                 use_graph: bool = True, row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
-                row_samplers: Optional[Sequence[tuple]] = None):
-        """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]]); ``row_samplers`` as in ``sample``."""
+                row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None):
+        """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]]); ``row_samplers`` as in ``sample``;
+        ``prefix`` = [[B, P], [B, P, 4], [B, P, 16]]: completion, as in ``sample`` (``hqt_sample_prefix_l3``)."""
         outs, logits = self._sample_levels(3, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(None,) * 3 if force is None else force,
                                            out=None, return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
-                                           row_samplers=row_samplers)
+                                           row_samplers=row_samplers, prefix=prefix)
         return (*outs, logits) if return_logits else tuple(outs)
 
     # ------------------------------------------------------------------ stage 1, encode side

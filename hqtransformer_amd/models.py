@@ -156,12 +156,15 @@ class HQTransformerStage2(_Stage):
     def pos_emb_txt(self):
         return _Table(self._w['pos_emb_txt.weight'])
 
-    def engine(self, batch: int, n_steps: int, lane: int = 0) -> Engine:
+    def engine(self, batch: int, n_steps: int, lane: int = 0, max_prefix: int = 0) -> Engine:
+        """``max_prefix`` > 0: the engine must take code prefixes of that many positions (``hqt_set_max_prefix``); like ``batch`` it only
+        ever grows, and a model that never completes a prefix keeps the workspace it always had."""
         self._need_gpu()
         e = self._engine
-        if e is None or batch > e.max_batch or n_steps > e.max_steps:
+        if e is None or batch > e.max_batch or n_steps > e.max_steps or max_prefix > e.max_prefix:
             self._drop_engine()
-            e = Engine(self.spec, None, self._device, max(batch, e.max_batch if e else 0), self.spec.ctx_len_img)
+            e = Engine(self.spec, None, self._device, max(batch, e.max_batch if e else 0), self.spec.ctx_len_img,
+                       max_prefix=max(int(max_prefix), e.max_prefix if e else 0))
             unused = stage2_unused(self.spec)
             e.load(stage2={k: v for k, v in self._w.items() if k not in unused})
             e.finalize()

@@ -72,6 +72,36 @@ def decode_codes(stage1, codes: list, precision: Optional[str] = None, decode_ba
     return stage1.decode_sequences(codes, precision=precision, clamp01=True)
 
 
+def grids_to_sequences(grids: list) -> list:
+    """Code grids [B, K << l, K << l], coarse to fine, -> the sampler's layout [B, K K], [B, K K, 4][, [B, K K, 16]]: the inverse of
+    ``rearrange_levels`` ('B (H kerH) (W kerW) -> B (H W) (kerH kerW)')."""
+    B, K = int(grids[0].shape[0]), int(grids[0].shape[-1])
+    out = []
+    for l, g in enumerate(grids):
+        k = 2 ** l
+        s = g.reshape(B, K, k, K, k).permute(0, 1, 3, 2, 4).reshape(B, K * K, k * k)
+        out.append(s.reshape(B, K * K) if l == 0 else s.contiguous())
+    return out
+
+
+def complete_images(model, images: torch.Tensor, keep_rows: int, cond=None, encode_precision: Optional[str] = None,
+                    decode_precision: Optional[str] = None, **sampler) -> Tuple[torch.Tensor, list]:
+    """Keep the first ``keep_rows`` rows of every image's top code grid and sample the rest: ``images`` fp32 [B, 3, R, R] in [-1, 1] (what
+    ``stage1.get_codes`` takes) -> ``stage1`` codes -> the codes of the first ``P = keep_rows * top_resolution`` positions on every level (the
+    bottom / middle grids cut at the matching rows) as ``prefix_codes`` of one sampler call over all ``top_resolution ** 2`` positions ->
+    ``decode_codes``.  ``cond``: class ids as in ``sampling_ihqgpt``; ``sampler``: further keywords of that sampler (cut-offs, temperatures,
+    seed, precision ...).  Returns ``(pixels fp32 [B, 3, R, R] in [0, 1], codes)`` with ``codes`` the full-length code list, coarse to fine;
+    its positions < P are the image's own codes."""
+    grids = list(model.stage1.code_grids(images, precision=encode_precision))
+    K = int(grids[0].shape[-1])
+    if not 1 <= int(keep_rows) < K:
+        raise ValueError(f'keep_rows={keep_rows} outside [1, {K - 1}]: at least one row of the {K} x {K} top grid is kept and one is left to sample')
+    P = int(keep_rows) * K
+    prefix = [s[:, :P].contiguous() for s in grids_to_sequences(grids)]
+    codes = sample_codes(model.stage2, int(images.shape[0]), cond, max_seq_len=K * K, prefix_codes=prefix, **sampler)
+    return decode_codes(model.stage1, codes, decode_precision), codes
+
+
 def _public(codes: list) -> tuple:
     return codes[0], (codes[1] if len(codes) == 2 else codes[1:])
 
@@ -111,11 +141,29 @@ class _Step(NamedTuple):
     order_after_current: bool
     sample_kw: dict
 
+    def prefix_len(self) -> int:
+        """P of the step's ``prefix_codes`` (0: none)."""
+        prefix = self.sample_kw.get('prefix_codes')
+        return 0 if prefix is None else int(torch.as_tensor(prefix[0]).shape[-1])
+
     def settings(self, mixed_samplers: bool = False) -> tuple:
-        """What the steps of one merged pass must share (``mixed_samplers``: all but the sampler settings, which then travel per row)."""
-        free = ('sample_offset',) + (SAMPLER_KEYS if mixed_samplers else ())
-        return (self.max_seq_len, self.use_fp16, self.precision, self.clamp01, self.use_graph,
+        """What the steps of one merged pass must share (``mixed_samplers``: all but the sampler settings, which then travel per row).
+        Prefix codes belong to a step's rows like its class ids; their LENGTH is shared (a pass has one prefill)."""
+        free = ('sample_offset', 'prefix_codes') + (SAMPLER_KEYS if mixed_samplers else ())
+        return (self.max_seq_len, self.use_fp16, self.precision, self.clamp01, self.use_graph, self.prefix_len(),
                 {k: v for k, v in self.sample_kw.items() if k not in free})
+
+
+def check_mergeable(step: _Step, first: _Step, mixed_samplers: bool = False) -> None:
+    """ValueError unless ``step`` can join the pass that ``first`` opened."""
+    if step.prefix_len() != first.prefix_len():
+        raise ValueError(f'steps merged into one pass must share the prefix length: this step has P={step.prefix_len()}, the pass P={first.prefix_len()} '
+                         '(a merged pass has one prefill; flush() first to start a new pass)')
+    if not _same(step.settings(mixed_samplers), first.settings(mixed_samplers)):
+        if mixed_samplers:
+            raise ValueError('steps of a mixed pass may differ in temperature, top-k and top-p only: max_seq_len, precision and every other '
+                             'setting must match (flush() first to start a new pass)')
+        raise ValueError('steps merged into one pass must share max_seq_len, precision and sampler settings (flush() first to start a new pass)')
 
 
 class Pending:
@@ -170,11 +218,8 @@ class InflightSampler:
             p = Pending()
             step = _Step(p, num_candidates, cond, seed, max_seq_len, use_fp16, precision, clamp01, use_graph, after, order_after_current, sample_kw)
             # checked HERE, before the step is queued: a mismatch raises without touching the queue (every Pending already handed out stays valid)
-            if self._queue and not _same(step.settings(self.mixed_samplers), self._queue[0].settings(self.mixed_samplers)):
-                if self.mixed_samplers:
-                    raise ValueError('steps of a mixed pass may differ in temperature, top-k and top-p only: max_seq_len, precision and every other '
-                                     'setting must match (flush() first to start a new pass)')
-                raise ValueError('steps merged into one pass must share max_seq_len, precision and sampler settings (flush() first to start a new pass)')
+            if self._queue:
+                check_mergeable(step, self._queue[0], self.mixed_samplers)
             self._queue.append(step)
             if len(self._queue) >= self.merge:
                 self.flush()
@@ -191,7 +236,11 @@ class InflightSampler:
         ref = q[0]
         sizes = [e.num_candidates for e in q]
         los = [sum(sizes[:i]) for i in range(len(q))]
-        kw = {k: v for k, v in ref.sample_kw.items() if k != 'sample_offset'}
+        kw = {k: v for k, v in ref.sample_kw.items() if k not in ('sample_offset', 'prefix_codes')}
+        if ref.prefix_len():                         # every step's own prefix rows, in step order (one P: check_mergeable)
+            where = torch.as_tensor(ref.sample_kw['prefix_codes'][0]).device       # device prefixes stay there: no copy back to the host
+            kw['prefix_codes'] = [torch.cat([torch.as_tensor(e.sample_kw['prefix_codes'][l]).to(where, torch.int64) for e in q])
+                                  for l in range(len(ref.sample_kw['prefix_codes']))]
         if self.mixed_samplers:                      # every row keeps the sampler settings of its own step
             kw = {k: v for k, v in kw.items() if k not in SAMPLER_KEYS}
             kw['row_samplers'] = step_row_samplers(self.model.stage2.spec.levels, sizes, [e.sample_kw for e in q])

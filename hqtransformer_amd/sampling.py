@@ -10,6 +10,7 @@ from typing import List, Optional
 import torch
 
 from ._lib import PRECISION_EXACT, PRECISION_FAST, PRECISIONS
+from .engine import check_prefix
 
 
 def _seed_from_torch() -> int:
@@ -72,7 +73,8 @@ def sampling_ihqgpt(model,
                     row_seeds=None,
                     row_offsets=None,
                     precision: Optional[str] = None,
-                    row_samplers=None):
+                    row_samplers=None,
+                    prefix_codes=None):
     """Returns ``(codes_top int64 [B, max_seq_len], codes_bot int64 [B, max_seq_len, 4])`` on the model's GPU.
 
     ``model`` is ``ImageGPT2.stage2``.  ``cond``: python int (class id, repeated for every candidate), an
@@ -89,7 +91,11 @@ def sampling_ihqgpt(model,
     settings in place of ``top_k_*`` / ``top_p_*`` / ``softmax_temperature``, bit for bit as in a call that has them for every row;
     ``precision`` ('exact' | 'fast' | 'split') overrides ``use_fp16``: 'split' = the fp32 launch sequence with every nn.Linear on the
     matrix cores (fp16 hi / lo operands, three MFMAs per term, fp32 accumulation): code sequences bit-identical to 'exact' wherever the
-    draw is well-conditioned, at several times its speed.
+    draw is well-conditioned, at several times its speed;
+    ``prefix_codes`` = ``[top [B, P], bot [B, P, 4]]``, 1 <= P <= max_seq_len - 1: completion -- the first P positions of the returned codes are
+    these, the rest is drawn as a free run would draw it had its first P positions produced them (same Philox keys / ``noise`` slice per absolute
+    position; ``given_top_code`` keeps its meaning for positions >= P).  The prefix goes through the body in one causal pass, not P decode steps.
+    Not with text conditioning.
 
     The call is asynchronous and does not read the device's flags: 'split' passes above 256 rows SATURATE activations outside the fp16 range and
     only flag them, and a persistent FAST launch (up to 64 samples) that could not finish on a shared GPU only marks the handle -- call
@@ -97,6 +103,7 @@ def sampling_ihqgpt(model,
     """
     spec = model.spec
     B, cond = _batch_and_cond(model, num_candidates, cond)
+    prefix = check_prefix(spec, B, max_seq_len, prefix_codes)       # refused here, before an engine is built
     force_top = None
     if given_top_code is not None and spec.depth_decoding == 'bidirectional':
         # the reference passes given_top_code to the 'parallel' head only and silently ignores it here (hierarchical_ar.py:451-479)
@@ -108,13 +115,22 @@ def sampling_ihqgpt(model,
         if force_top.shape[0] != B:
             force_top = force_top.repeat(B, 1)
         force_top = force_top[:, :max_seq_len]
-    eng = model.engine(B, max_seq_len, lane)
+    eng = model.engine(B, max_seq_len, lane, max_prefix=_prefix_room(spec, prefix))
     if seed is None and noise is None:
         seed = _seed_from_torch()
     return eng.sample(B, cond, max_seq_len, precision=_precision(precision, use_fp16),
                       top_k=(top_k_top, top_k_bot), top_p=(top_p_top, top_p_bot), temperature=softmax_temperature,
                       noise=noise, seed=seed or 0, sample_offset=sample_offset, force_top=force_top, use_graph=use_graph,
-                      row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers)
+                      row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix)
+
+
+def _prefix_room(spec, prefix) -> int:
+    """``max_prefix`` of the engine a call with this prefix needs: none without one, else the length of this prefix.  The prefill's buffers
+    grow with max_batch * (max_prefix + 1) rows (the split-K slab alone is 16 * rows * max(4 D, V) * 4 bytes: 1 GiB at 64 samples of the
+    ImageNet-12L model with 32 positions, 2 GiB with 63), so room is taken for what is asked, not for every prefix the model could take.  Like the batch,
+    the room only grows: a longer prefix later rebuilds the engine (weights are loaded and finalized again), and a caller who knows its
+    longest prefix asks for it once with ``model.engine(batch, n_steps, max_prefix=...)``."""
+    return 0 if prefix is None else int(prefix[0].shape[1])
 
 
 def sampling_hqtransformer(model,
@@ -135,24 +151,27 @@ def sampling_hqtransformer(model,
                            row_seeds=None,
                            row_offsets=None,
                            precision: Optional[str] = None,
-                           row_samplers=None):
+                           row_samplers=None,
+                           prefix_codes=None):
     """Counterpart of ``hqvae.utils.sampling.sampling_hqtransformer`` (sampling.py:240-307) for the three-level
     HQTransformer: returns ``[codes0 int64 [B, L], codes1 [B, L, 4], codes2 [B, L, 16]]`` on the model's GPU.
     ``top_k`` / ``top_p`` / ``softmax_temperature`` are per-level lists (None = no cut-off); ``cond`` as in
     ``sampling_ihqgpt``.  Extensions: ``noise`` fp32 [L, 21, B, V], ``seed`` / ``sample_offset``, ``lane``,
-    ``row_samplers`` (per-row settings, as in ``sampling_ihqgpt``)."""
+    ``row_samplers`` (per-row settings, as in ``sampling_ihqgpt``), ``prefix_codes`` = ``[t [B, P], m [B, P, 4], b [B, P, 16]]`` (completion,
+    as in ``sampling_ihqgpt``)."""
     spec = model.spec
     if spec.levels != 3:
         raise ValueError('sampling_hqtransformer needs the three-level HQTransformer (stage2.type multilevel-hq)')
     B, cond = _batch_and_cond(model, num_candidates, cond)
+    prefix = check_prefix(spec, B, max_seq_len, prefix_codes)
     top_k = list(top_k) if top_k is not None else [None, None, None]
     top_p = list(top_p) if top_p is not None else [None, None, None]
-    eng = model.engine(B, max_seq_len, lane)
+    eng = model.engine(B, max_seq_len, lane, max_prefix=_prefix_room(spec, prefix))
     if seed is None and noise is None:
         seed = _seed_from_torch()
     return list(eng.sample3(B, cond, max_seq_len, precision=_precision(precision, use_fp16), top_k=top_k, top_p=top_p,
                             temperature=softmax_temperature, noise=noise, seed=seed or 0, sample_offset=sample_offset, use_graph=use_graph,
-                            row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers))
+                            row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix))
 
 
 def rearrange_levels(codes: List[torch.Tensor], top_resolution: int) -> tuple:

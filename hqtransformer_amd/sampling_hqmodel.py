@@ -20,7 +20,7 @@ import torch
 
 from .config import load_config
 from .models import ImageGPT2
-from .pipeline import decode_codes, sample_codes, sampler_cutoffs
+from .pipeline import complete_images, decode_codes, sample_codes, sampler_cutoffs
 from .utils import set_seed
 
 
@@ -46,6 +46,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--batch-size', type=int, default=50)
     p.add_argument('--num-classes', type=int, default=1000)
     p.add_argument('--samples-per-class', type=int, default=None, help='default 50000 // num_classes')
+    p.add_argument('--complete-from', type=str, default=None, metavar='FILE.npy',
+                   help='complete images instead of sampling from scratch: float32 [N, 3, H, W] in [0, 1] (the layout of the samples this driver writes); '
+                        'row i of a batch completes image (batch index * batch size + i) mod N.  Needs --keep-rows')
+    p.add_argument('--keep-rows', type=int, default=None, help='with --complete-from: rows of the top code grid kept from the image (1 .. top_resolution - 1)')
     return p
 
 
@@ -102,6 +106,16 @@ def sample_pixels(model: ImageGPT2, args, num_candidates: int, cond) -> np.ndarr
     """One batch of either driver (sampling_hqmodel.py:101-153,201-214): ``top_k`` / ``top_p`` shared by the levels, temperatures
     ``T * decay^level``, decode + ``clamp(0.5 x + 0.5, 0, 1)``; float32 [B, 3, H, W] in [0, 1] on the host."""
     temps = [args.temperature * (args.temperature_decay ** i) for i in range(args.code_level)]
+    images = getattr(args, 'complete_images', None)
+    if images is not None:               # --complete-from: the same sampler settings, the first rows of every image kept
+        first = getattr(args, 'complete_next', 0)
+        args.complete_next = first + num_candidates
+        rows = torch.from_numpy(images[np.arange(first, first + num_candidates) % len(images)])
+        pixels, _ = complete_images(model, 2.0 * rows - 1.0, args.keep_rows, cond=cond, decode_precision=args.decode_precision, softmax_temperature=temps,
+                                    use_fp16=True, **sampler_cutoffs(args.code_level, args.top_k, args.top_p))
+        model.stage1.range_check()
+        model.stage2.range_check()
+        return pixels.cpu().numpy()
     codes = sample_codes(model.stage2, num_candidates, cond, softmax_temperature=temps, use_fp16=True, max_seq_len=args.top_resolution * args.top_resolution,
                          model_stage1=model.stage1, **sampler_cutoffs(args.code_level, args.top_k, args.top_p))
     pixels = decode_codes(model.stage1, codes, args.decode_precision)
@@ -114,6 +128,14 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.code_level not in (2, 3):
         raise NotImplementedError('--code-level must be 2 or 3')
+    if (args.complete_from is None) != (args.keep_rows is None):
+        raise SystemExit('--complete-from and --keep-rows come together')
+    if args.complete_from is not None:
+        args.complete_images = np.ascontiguousarray(np.load(args.complete_from), dtype=np.float32)
+        if args.complete_images.ndim != 4 or args.complete_images.shape[1] != 3 or len(args.complete_images) < 1:
+            raise SystemExit(f'--complete-from: expected float32 [N, 3, H, W], got {args.complete_images.shape}')
+        if not 1 <= args.keep_rows < args.top_resolution:
+            raise SystemExit(f'--keep-rows must lie in [1, top_resolution - 1 = {args.top_resolution - 1}]')
     set_seed(args.seed)
     os.makedirs(args.result_path, exist_ok=True)
     model = load_model(args.model_path).eval()

@@ -252,6 +252,42 @@ typedef struct {
 int hqt_sample_l3(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts_l3* opts, const float* noise,
                   const int64_t* force0, const int64_t* force1, const int64_t* force2, float* logits_out,
                   int64_t* out0, int64_t* out1, int64_t* out2, void* stream);
+/* hqt_set_max_prefix -- no reference counterpart.  Largest code prefix a later hqt_sample_prefix / hqt_sample_prefix_l3 call on this handle
+ * may pass.  A handle starts with max_prefix = 0: such calls are refused and the workspace is what hqt_create has always allocated.  The
+ * prefix prefill runs all body blocks over max_batch * (max_prefix + 1) rows at once; this call re-sizes the body workspace (activations,
+ * split-K slabs, packed copies -- not the KV cache, which max_steps already covers) for that pass.  An entry point and not a field of
+ * hqt_config, so that the struct, and with it ABI version 9, stay what they are (as with hqt_set_row_samplers).  Call it between hqt_create
+ * and hqt_finalize_weights (HQT_ERR_STATE afterwards: lanes, captured graphs and the persistent chain's phase tables hold workspace pointers);
+ * lanes made by hqt_clone inherit the value.  HQT_ERR_INVALID: max_prefix outside [0, max_steps - 1], a handle without stage 2, text
+ * conditioning. */
+int hqt_set_max_prefix(hqt_handle* h, int max_prefix);
+
+/* hqt_sample_prefix / hqt_sample_prefix_l3 -- completion (no reference counterpart as a call: the reference can only
+ * teacher-force a whole run position by position): the codes of positions 0 .. prefix_len - 1 are given, positions prefix_len .. n_steps - 1
+ * are drawn exactly as hqt_sample / hqt_sample_l3 would draw them had its first prefix_len positions produced these codes -- same Philox keys
+ * (seed, global row, ABSOLUTE position, draw, chunk), same slice of `noise` (indexed by absolute position), same sampler settings and row
+ * tables.  The prefix is not fed through the model one position at a time: its prefix_len + 1 body input rows per sample (the sos / class row,
+ * then the input embedding of every prefix position) are written by one kernel and all body blocks run causally over them in ONE pass that
+ * fills the KV cache; the depth head runs on the last row only and draws position prefix_len.  The remaining positions are ordinary decode steps.
+ *   prefix_len   1 .. min(n_steps - 1, max_prefix of the handle: hqt_set_max_prefix)
+ *   prefix_top   int64 [B, prefix_len]; prefix_bot int64 [B, prefix_len, 4]   (l3: prefix0 [B, P], prefix1 [B, P, 4], prefix2 [B, P, 16]);
+ *                values outside the vocabulary are clamped into it on the device, as every id that arrives from the caller (cond,
+ *                force_*): device pointers cannot be checked on the host, so such input is NOT an error here and hqt_range_check
+ *                does not report it -- a caller that cannot vouch for its codes checks them first (the Python surface raises IndexError)
+ *   out_*        full length, as in hqt_sample: positions < prefix_len hold the prefix verbatim -- for a prefix inside the
+ *                vocabulary; a clamped value comes back clamped
+ *   force_*      [B, n_steps] ... as in hqt_sample; entries of positions < prefix_len are not read
+ *   logits_out   as in hqt_sample; the rows of positions < prefix_len are not written
+ * Every other argument as in hqt_sample / hqt_sample_l3.  HQT_ERR_INVALID: prefix_len < 1, prefix_len >= n_steps, prefix_len >
+ * the handle's max_prefix (the message names hqt_set_max_prefix), a NULL prefix pointer, a text-conditional model. */
+int hqt_sample_prefix(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts* opts, const float* noise,
+                      int prefix_len, const int64_t* prefix_top, const int64_t* prefix_bot,
+                      const int64_t* force_top, const int64_t* force_bot, float* logits_out,
+                      int64_t* out_top, int64_t* out_bot, void* stream);
+int hqt_sample_prefix_l3(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts_l3* opts, const float* noise,
+                         int prefix_len, const int64_t* prefix0, const int64_t* prefix1, const int64_t* prefix2,
+                         const int64_t* force0, const int64_t* force1, const int64_t* force2, float* logits_out,
+                         int64_t* out0, int64_t* out1, int64_t* out2, void* stream);
 int hqt_decode_l3(hqt_handle* h, int B, const int64_t* code_t, const int64_t* code_m, const int64_t* code_b, float* out_pixels,
                   int clamp01, int precision, void* stream);
 int hqt_decode_seq_l3(hqt_handle* h, int B, const int64_t* codes0, const int64_t* codes1, const int64_t* codes2, float* out_pixels,
