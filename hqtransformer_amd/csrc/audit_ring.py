@@ -1,17 +1,20 @@
 #!/usr/bin/env python3
-"""Audit of the hand-scheduled loop of conv3x3_split_ring_kernel in the compiler's output.
+"""Audit of a hand-scheduled SPLIT conv loop in the compiler's output.
 
-The kernel keeps asm-issued loads in flight across its loop's back edge; that is only safe if (a) the loop body is ONE basic block and
+The kernels keep asm-issued loads in flight across their loop's back edge; that is only safe if (a) the loop body is ONE basic block and
 (b) hipcc never touches a destination register of such a load except in the MFMAs / ds_writes that consume it after the counted wait.
 This script checks both on the generated ISA:   hipcc -O3 --offload-arch=gfx950 -S --cuda-device-only split_stream_conv.hip -o x.s;
-                                                 python hqtransformer_amd/csrc/audit_ring.py x.s [mangled kernel name]
-(both hand-scheduled kernels: _Z25conv3x3_split_ring_kernelILi0EEv8GemmArgs, _Z27conv3x3_split_ring16_kernelILi0EEv8GemmArgs)
+                                                 python hqtransformer_amd/csrc/audit_ring.py x.s <mangled kernel name>
+_lib.build() runs it on every instantiation of the three hand-scheduled kernels the ISA holds:
+    _Z27conv3x3_split_ring16_kernelILi0EEv8GemmArgs, _Z25conv2x2_split_up16_kernelILi0EEv8GemmArgs, _Z26conv3x3_split_out16_kernel8GemmArgs
 """
 import re
 import sys
 
+if len(sys.argv) != 3:
+    sys.exit(__doc__)
 src = open(sys.argv[1]).read().split('\n')
-name = (sys.argv[2] if len(sys.argv) > 2 else '_Z25conv3x3_split_ring_kernelILi0EEv8GemmArgs') + ':'        # mangled kernel name
+name = sys.argv[2] + ':'                # mangled kernel name
 i0 = next(i for i, l in enumerate(src) if l.startswith(name))
 i1 = next(i for i in range(i0, len(src)) if 's_endpgm' in src[i])
 body = src[i0:i1]

@@ -1,17 +1,11 @@
 // SPLIT precision kernels (see split_kernels.h): fp32-accurate 3x3 convolutions and GEMMs on the gfx950 matrix cores,
 // fp16 hi/lo operand planes, three v_mfma_f32_32x32x16_f16 per fragment pair, fp32 accumulation.
 #include "split_kernels.h"
+#include "split_ring.h"
 #include "gemm_generic.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-#include "split_device.h"
 
 namespace {
 __device__ __forceinline__ unsigned pack_h2(half_t a, half_t b) {
@@ -160,7 +154,7 @@ constexpr int S_TY = 8, S_TX = 16, S_PITCH = S_TX + 2;
 constexpr int S_ROWS = (S_TY + 2) * S_PITCH;                    // 180 patch rows (pixels) of 128 B per plane
 constexpr int S_PIECES = (S_ROWS + 7) / 8;                      // 23 DMA pieces of 8 rows
 constexpr int S_PATCH_BYTES = S_PIECES * 1024;                  // per plane
-constexpr int S_CPITCH = 128 * 4 + 16;                          // fp32 staging row (bytes)
+constexpr int S_CPITCH = R_CPITCH;                              // fp32 staging row (bytes): read back by ring_store_rows (split_ring.h)
 constexpr int split_conv3_lds(int BN) { return 4 * S_PATCH_BYTES + 4 * BN * 128; }
 static_assert(128 * S_CPITCH <= split_conv3_lds(32), "epilogue staging must fit in the operand buffers");
 static_assert(split_conv3_lds(128) <= 160 * 1024, "LDS budget");
@@ -315,9 +309,8 @@ __global__ __launch_bounds__(PC ? 512 : 256, 1) void conv3x3_split_kernel(GemmAr
 #undef HQT_RETIRE
     };
 
-    float bv[8];                                        // epilogue bias of this thread's 8 channels, fetched under the main loop
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bv[e] = (BN == 128 && g.bias && n0 + (tid & 15) * 8 + e < g.N) ? g.bias[n0 + (tid & 15) * 8 + e] : 0.0f;
+    float bv[8] = {};                                   // epilogue bias of this thread's 8 channels, fetched under the main loop
+    if constexpr (BN == 128) ring_bias8(g, n0 + (tid & 15) * 8, bv);
     const int NC = g.Cin / 64, KT = NC * 9;
     if (PC && consumer) __builtin_amdgcn_s_setprio(2);      // the matrix stream wins issue arbitration against its SIMD's producer wave
     if (!PC || producer) {
@@ -343,17 +336,7 @@ __global__ __launch_bounds__(PC ? 512 : 256, 1) void conv3x3_split_kernel(GemmAr
         }
     }
     if (PC && consumer) __builtin_amdgcn_s_setprio(0);
-    if (ABL == 1) {                                    // no epilogue: keep the accumulators alive, one store per wave at most
-        float sacc = 0.0f;
-#pragma unroll
-        for (int i = 0; i < FI; ++i)
-#pragma unroll
-            for (int j = 0; j < FJ; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sacc += accm[i][j][r] + accx[i][j][r];
-        if (sacc == 12345.678f) reinterpret_cast<float*>(g.C)[0] = sacc;
-        return;
-    }
+    if (ABL == 1) { ring_sink_acc(g, accm, accx); return; }
     // ---- epilogue.  D map: col = lane & 31 -> pixel fr of block i; row = (r & 3) + 8 (r >> 2) + 4 fh -> channel
     if (NCHW) {                                        // conv_out: fp32 NCHW (+clamp); lanes = consecutive pixels of a row
         if (!consumer) return;
@@ -379,11 +362,7 @@ __global__ __launch_bounds__(PC ? 512 : 256, 1) void conv3x3_split_kernel(GemmAr
     if constexpr (BN == 128) {
         const long long pix0 = ((long long)img * g.H + ty0) * g.W + tx0;         // NHWC row of tile pixel (0, 0)
         char* stage = lds_raw;                              // [128 pixels][S_CPITCH] fp32; every operand read is behind the last barrier
-        float* Cb = reinterpret_cast<float*>(g.C);
-        const float* Rb = reinterpret_cast<const float*>(g.resid);
-        const int c8 = (tid & 15) * 8;                      // 8 consecutive channels per thread, 16 threads per pixel row
-        const int nn = n0 + c8;
-        float gs[8], gq[8];                                 // GroupNorm statistics of this thread's channels
+        float gs[8], gq[8];                                 // GroupNorm statistics of this thread's 8 channels
 #pragma unroll
         for (int e = 0; e < 8; ++e) { gs[e] = 0.0f; gq[e] = 0.0f; }
         if (consumer) {
@@ -403,61 +382,9 @@ __global__ __launch_bounds__(PC ? 512 : 256, 1) void conv3x3_split_kernel(GemmAr
         }
         }
         __syncthreads();
-        if (consumer && nn < g.N) {                                 // split_conv3_ok(): N % 8 == 0, so a thread's 8 channels are all in or all out
-            long long moff[8];
-            f32x4 r0[8], r1[8];
-#pragma unroll
-            for (int pass = 0; pass < 8; ++pass) {      // residual rows first: sixteen 16-B loads in flight
-                const int r = pass * 16 + (tid >> 4);
-                moff[pass] = (pix0 + (long long)(r >> 4) * g.W + (r & 15)) * g.ldc + nn;
-                if (Rb) { r0[pass] = *reinterpret_cast<const f32x4*>(Rb + moff[pass]); r1[pass] = *reinterpret_cast<const f32x4*>(Rb + moff[pass] + 4); }
-            }
-#pragma unroll
-            for (int pass = 0; pass < 8; ++pass) {
-                const int r = pass * 16 + (tid >> 4);
-                const f32x4 lo = *reinterpret_cast<const f32x4*>(stage + r * S_CPITCH + c8 * 4);
-                const f32x4 hi = *reinterpret_cast<const f32x4*>(stage + r * S_CPITCH + c8 * 4 + 16);
-                float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = v[e] * g.alpha + bv[e];
-                if (Rb) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { v[e] += r0[pass][e]; v[4 + e] += r1[pass][e]; }
-                }
-                const f32x4 o0 = {v[0], v[1], v[2], v[3]}, o1 = {v[4], v[5], v[6], v[7]};
-                *reinterpret_cast<f32x4*>(Cb + moff[pass]) = o0;
-                *reinterpret_cast<f32x4*>(Cb + moff[pass] + 4) = o1;
-                if (g.gn_part_out_d) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { gs[e] += v[e]; gq[e] += v[e] * v[e]; }
-                }
-            }
-        }
-        if (g.gn_part_out_d) {                              // uniform branch (kernel argument): barriers are safe here
-            __syncthreads();                                // every staged value has been read
-            float* redw = reinterpret_cast<float*>(lds_raw);                    // [16 pixel rows][128 channels][2]; zeros from idle threads
-            if (consumer) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                redw[(((tid >> 4) * 128) + c8 + e) * 2] = gs[e];
-                redw[(((tid >> 4) * 128) + c8 + e) * 2 + 1] = gq[e];
-            }
-            }
-            __syncthreads();
-            const float* red = reinterpret_cast<const float*>(lds_raw);
-            if (consumer && tid < 128) {                                // one channel per thread, then its group (cpg consecutive channels = lanes)
-                double sa = 0.0, sq = 0.0;
-#pragma unroll
-                for (int rg = 0; rg < 16; ++rg) { sa += (double)red[((rg * 128) + tid) * 2]; sq += (double)red[((rg * 128) + tid) * 2 + 1]; }
-                const int cpg = g.N / g.gn_out_groups;
-                for (int off = cpg >> 1; off > 0; off >>= 1) { sa += __shfl_xor(sa, off, 64); sq += __shfl_xor(sq, off, 64); }
-                const int ch = n0 + tid;
-                if (ch < g.N && (tid & (cpg - 1)) == 0) {
-                    double* pp = g.gn_part_out_d + (((long long)img * (tiles_x * tiles_y) + trem) * g.gn_out_groups + ch / cpg) * 2;
-                    pp[0] = sa; pp[1] = sq;
-                }
-            }
-        }
+        // whole NHWC rows, bias, residual and the GroupNorm partial of the tile: split_ring.h, 8 passes of 16 staged pixels
+        ring_store_rows<8>(g, stage, tid, n0, bv, consumer, [&](int r) { return pix0 + (long long)(r >> 4) * g.W + (r & 15); }, gs, gq);
+        ring_reduce_gn(g, lds_raw, tid, gs, gq, n0, consumer, (long long)img * (tiles_x * tiles_y) + trem);
     }
 }
 

@@ -1,5 +1,5 @@
 // SPLIT precision: the device-side hi / lo split shared by the operand pass, the GEMM / conv kernels that split while they stage a tile
-// (split_conv.hip) and the conv epilogue that emits operand planes (split_stream_conv.hip).  See split_kernels.h for the arithmetic.
+// (split_conv.hip) and the conv epilogue that emits operand planes (split_ring.h).  See split_kernels.h for the arithmetic.
 #pragma once
 #include "split_kernels.h"
 

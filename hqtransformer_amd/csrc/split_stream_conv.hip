@@ -18,61 +18,21 @@
 //     ONE workgroup barrier per 32-channel chunk;
 //   * the main loop is one basic block of straight-line code with asm loads in flight across its back edge; _lib.build() audits the
 //     generated ISA (csrc/audit_ring.py) and refuses to link a library whose loops the compiler has touched.
+// The three kernels differ in their hand-scheduled main loops only (which read, load or store goes at which tap, and every counted wait).
+// What surrounds the loops -- geometry, tile decode, patch-piece addressing, the asm wrappers the loops call, the staged row epilogue and
+// the GroupNorm partials -- is defined once, in split_ring.h.
 #include "split_kernels.h"
-#include "split_device.h"
+#include "split_ring.h"
 #include "gemm_generic.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-namespace {
-constexpr float R_INV = 1.0f / 2048.0f;
-constexpr int R_TY = 8, R_TX = 16, R_PITCH = R_TX + 2;
-constexpr int R_ROWS = (R_TY + 2) * R_PITCH;                    // 180 patch rows (pixels) of 64 B per plane
-constexpr int R_PIECES = (R_ROWS + 15) / 16;                    // 12 DMA pieces of 16 rows per plane
-constexpr int R_PLANE = R_PIECES * 1024;
-constexpr int R_CPITCH = 128 * 4 + 16;                          // fp32 staging row of the epilogue (bytes)
-constexpr int R_LDS = 4 * R_PLANE;                              // two buffers x two planes = 48 KiB
-static_assert(64 * R_CPITCH <= R_LDS, "epilogue staging (64 pixels at a time) must fit in the patch buffers");
-
-__device__ __forceinline__ void r_xcd_tile(int& tile_m, int& tile_n, int panel) {
-    const int nx = gridDim.x, total = gridDim.x * gridDim.y;
-    int id = blockIdx.x + nx * blockIdx.y;
-    if ((total & 7) == 0) id = (id & 7) * (total >> 3) + (id >> 3);
-    if (panel > 0) {
-        // panels of `panel` pixel tiles x all n-tiles; inside a panel the pixel tile runs fastest: the workgroups an XCD holds at one
-        // time walk ONE filter stream together (L2 hits) and each its own patch
-        const int per = panel * nx, p = id / per, r = id - p * per;
-        const int rows = min(panel, (int)gridDim.y - p * panel);
-        tile_n = r / rows;
-        tile_m = p * panel + (r - tile_n * rows);
-        return;
-    }
-    tile_m = id / nx;
-    tile_n = id - tile_m * nx;
-}
-}  // namespace
 
 // ---------------------------------------------------------------------------------------------
 // Size of a fragment-packed 3x3 filter bank (hi + lo): ceil(N / 32) channel groups x Cin / 32 chunks x 9 taps x 4 KiB
 // (+ three k-tiles of padding: the kernels prefetch the filters of up to five k-steps past the end of the last n-tile's stream, and drop them)
 constexpr size_t R_FRAG_PAD = 3 * 4 * 512;
 size_t split_frag_elems(int N, int Cin) { return (size_t)((N + 31) / 32) * (Cin / 32) * 9 * 4 * 512 + R_FRAG_PAD; }
-
-namespace {
-// Patch rows are 64 B of data on an 80-B pitch: 8 consecutive pixels then start in 8 different 16-B bank groups (5 q mod 8), so the
-// fragment reads need no XOR swizzle -- and without one a fragment address is  base(fragment) + constant(buffer, tap, plane), i.e. an
-// immediate offset: ZERO vector instructions per read (a swizzled layout cost ~7 each, and vector instructions are not hidden behind
-// this wave's or its SIMD neighbour's MFMAs).
-constexpr int G_PITCH = 80, G_PLANE = 16 * R_PIECES * G_PITCH, G_LDS = 4 * G_PLANE;       // 15 KiB per plane, 60 KiB per workgroup
-static_assert(64 * R_CPITCH <= G_LDS, "epilogue staging (64 pixels at a time) must fit in the patch buffers");
-static_assert(3 * G_PLANE + 38 * G_PITCH + 32 < 65536, "ds_read immediate offsets");
-}  // namespace
 
 // ---------------------------------------------------------------------------------------------
 // conv3x3_split_ring16_kernel (fifth generation): the ring structure on v_mfma_f32_16x16x32_f16.  The ring kernel keeps the matrix pipe busy 85 % of the
@@ -107,14 +67,22 @@ hipError_t launch_pack_split_frag16(const float* w_tapmajor, half_t* out, int N,
 }
 
 namespace {
-constexpr int H_RING = 3, H_AHEAD = H_RING - 1, H_STEPS = 18;         // ring slots (taps), prefetch distance, taps per loop body (two chunks)
-static_assert(H_STEPS % H_RING == 0, "static ring slots");
-constexpr bool h_piece_at(int u) { u = ((u % H_STEPS) + H_STEPS) % H_STEPS; return (u % 9) < 6; }
-// loads issued after the filters of body step s (fetched during step s - 2, first hook) and before step s begins
-constexpr int h_younger(int s) {
-    int n = 4 * (H_AHEAD - 1);
-    for (int u = s - H_AHEAD; u < s; ++u) n += h_piece_at(u) ? 1 : 0;
-    return n;
+// Epilogue staging of the kernels on 8 x 2 blocks of v_mfma_f32_16x16x32_f16 per wave (ring16, up16): main + cross / 2^11 of tile rows
+// 4 half .. 4 half + 3 into the staging rows.  D map: col = lane & 15 -> pixel fx of tile row i; row = 4 (lane >> 4) + r -> channel
+// 16 j + 4 fk + r of the wave's 32.
+__device__ __forceinline__ void h_stage_half(char* stage, const f32x4 (&accm)[8][2], const f32x4 (&accx)[8][2], int half, int wave, int fx, int fk) {
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii) {
+        const int i = half * 4 + ii, r = ii * 16 + fx;          // pixel within the staged 64
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int nl = wave * 32 + j * 16 + 4 * fk;
+            f32x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = accm[i][j][e] + accx[i][j][e] * R_INV;
+            *reinterpret_cast<f32x4*>(stage + r * R_CPITCH + nl * 4) = v;
+        }
+    }
 }
 }  // namespace
 
@@ -129,45 +97,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_ring16_kernel(GemmArgs g
     int tile_m, tile_n;
     r_xcd_tile(tile_m, tile_n, g.tile_panel);
     const int n0 = tile_n * 128;
-    const int tiles_x = g.W / R_TX, tiles_y = g.H / R_TY;
-    const int img = tile_m / (tiles_x * tiles_y);
-    const int trem = tile_m - img * (tiles_x * tiles_y);
-    const int ty0 = (trem / tiles_x) * R_TY, tx0 = (trem % tiles_x) * R_TX;
+    int img, trem, ty0, tx0, tiles_x, tiles_y;
+    ring_tile(tile_m, g.H, g.W, img, trem, ty0, tx0, tiles_x, tiles_y);
     const int Hin = g.H >> g.upsample, Win = g.W >> g.upsample;
-    const half_t* Abase = reinterpret_cast<const half_t*>(g.A);                 // [pixel][hi Cin | lo Cin]
     const int NC = g.Cin / 32;
 
-    // ---- patch pieces: exactly as in the ring kernel
-    constexpr int PPW = 2 * R_PIECES / 4;
-    static_assert(PPW == 6, "one piece per wave at taps 0..5");
-    typedef int rsrc_t __attribute__((ext_vector_type(4)));
-    rsrc_t img_rsrc;
-    {
-        const unsigned long long ib = (unsigned long long)(size_t)(Abase + (long long)img * Hin * Win * (2 * g.Cin));
-        img_rsrc[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)ib);
-        img_rsrc[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(ib >> 32) & 0xffff);      // stride 0
-        img_rsrc[2] = __builtin_amdgcn_readfirstlane(Hin * Win * 2 * g.Cin * 2);               // bytes
-        img_rsrc[3] = 0x00020000;                                                              // raw buffer, 32-bit data format (gfx9)
-    }
-    unsigned poff[3];                                               // hi-plane source offset of pieces wave + 4 (u % 3); the lo plane is + Cin halves (scalar offset)
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-        const int plane = 0, piece = wave + 4 * u;
-        const int q = piece * 16 + (lane >> 2);
-        const int qy = (q * 3641) >> 16, qx = q - qy * R_PITCH;                 // q / 18 for q < 192
-        const int iy = ty0 + qy - 1, ix = tx0 + qx - 1;
-        const bool in = (q < R_ROWS) & ((unsigned)iy < (unsigned)g.H) & ((unsigned)ix < (unsigned)g.W);
-        const unsigned off = (unsigned)((((iy >> g.upsample) * Win + (ix >> g.upsample)) * (2 * g.Cin) + (lane & 3) * 8 + plane * g.Cin) * 2);
-        poff[u] = in ? off : 0x80000000u;
-    }
+    // ---- patch pieces: this wave's pieces wave + 4 u of either plane, fetched through registers (split_ring.h)
+    const ring_rsrc_t img_rsrc = ring_image_rsrc(g.A, img, Hin, Win, g.Cin);
+    unsigned poff[3];
+    ring_piece_offsets(poff, wave, lane, ty0, tx0, g.H, g.W, Win, g.upsample, g.Cin);
     u32x4 pst[2];                                                   // pieces in flight: loaded at tap t, written to LDS at tap t + 2
-    unsigned piece_base = lds_base + wave * (16 * G_PITCH) + (lane >> 2) * G_PITCH + (lane & 3) * 16;
-    auto load_piece = [&](int c, int u, int r) {
-        asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(pst[r]) : "v"(poff[u % 3]), "s"(img_rsrc), "s"(c * 64 + (u / 3) * g.Cin * 2));
-    };
-#define HQT_STORE_PIECE(buf, u, r)                                                                                             \
-    asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(piece_base), "v"(pst[r]),                                            \
-                 "n"(((buf) * 2 + (u) / 3) * G_PLANE + 4 * ((u) % 3) * 16 * G_PITCH) : "memory")
+    unsigned piece_base = ring_piece_base(lds_base, wave, lane);
 
     // this wave's filter stream: 4 KiB per tap ([block 0 hi][block 0 lo][block 1 hi][block 1 lo])
     const char* bfrag = reinterpret_cast<const char*>(reinterpret_cast<const half_t*>(g.Bw_frag16) + (size_t)(n0 / 32 + wave) * ((size_t)NC * 9 * 2048));
@@ -181,33 +121,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_ring16_kernel(GemmArgs g
 #pragma unroll
             for (int r = 0; r < 4; ++r) { accm[i][j][r] = 0.0f; accx[i][j][r] = 0.0f; }
     // fragment of pixel block i at tap (dy, dx): patch row (i + dy) * 18 + fx + dx, 16-B group fk -- one base + immediates
-    const unsigned abase = lds_base + fx * G_PITCH + fk * 16;
+    const unsigned abase = ring_frag_base(lds_base, fx, fk);
     half8 ah[4], al[4];                                             // pixel blocks in flight: slot = block % 4
     half8 wh[H_RING][2], wl[H_RING][2];                             // filter fragments [tap % 3][channel block]
-#define HQT_READ_A16(ps, tapoff, i)                                                                                            \
-    do {                                                                                                                       \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ah[(i) % 4]) : "v"(abase), "n"((ps) * 2 * G_PLANE + ((i) * R_PITCH + (tapoff)) * G_PITCH));            \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(al[(i) % 4]) : "v"(abase), "n"((ps) * 2 * G_PLANE + ((i) * R_PITCH + (tapoff)) * G_PITCH + G_PLANE));  \
-    } while (0)
-    auto load_b = [&](long long S, int slot) {
-        const char* p = bfrag + S * 4096;
-        asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(wh[slot][0]) : "v"(lane16), "s"(p));
-        asm volatile("global_load_dwordx4 %0, %1, %2 offset:1024" : "=v"(wl[slot][0]) : "v"(lane16), "s"(p));
-        asm volatile("global_load_dwordx4 %0, %1, %2 offset:2048" : "=v"(wh[slot][1]) : "v"(lane16), "s"(p));
-        asm volatile("global_load_dwordx4 %0, %1, %2 offset:3072" : "=v"(wl[slot][1]) : "v"(lane16), "s"(p));
-    };
 
-    // ---- prologue (as the ring kernel): first patch through the piece registers, filters of taps 0 and 1; everything lands first
+    // ---- prologue: first patch through the piece registers, filters of taps 0 and 1; everything lands first
 #pragma unroll
     for (int rnd = 0; rnd < 3; ++rnd) {
-        load_piece(0, 2 * rnd, 0); load_piece(0, 2 * rnd + 1, 1);
+        ring_load_piece(pst[0], poff, img_rsrc, 0, 2 * rnd, g.Cin); ring_load_piece(pst[1], poff, img_rsrc, 0, 2 * rnd + 1, g.Cin);
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(pst[0]), "+v"(pst[1]));
-        if (rnd == 0) { HQT_STORE_PIECE(0, 0, 0); HQT_STORE_PIECE(0, 1, 1); }
-        else if (rnd == 1) { HQT_STORE_PIECE(0, 2, 0); HQT_STORE_PIECE(0, 3, 1); }
-        else { HQT_STORE_PIECE(0, 4, 0); HQT_STORE_PIECE(0, 5, 1); }
+        ring_store_piece(piece_base, pst[0], 0, 2 * rnd); ring_store_piece(piece_base, pst[1], 0, 2 * rnd + 1);
     }
 #pragma unroll
-    for (int s = 0; s < H_AHEAD; ++s) load_b(s, s);
+    for (int s = 0; s < H_AHEAD; ++s) ring_load_b4(wh[s], wl[s], lane16, bfrag, s);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
     // ---- main loop: one iteration = two chunks = 18 taps of straight-line code
@@ -218,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_ring16_kernel(GemmArgs g
             const int c = c0 + cc, cn = min(c + 1, NC - 1);
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
-            if (ABL != 4) { HQT_READ_A16(cc, 0, 0); HQT_READ_A16(cc, 0, 1); HQT_READ_A16(cc, 0, 2); HQT_READ_A16(cc, 0, 3); }
+            if (ABL != 4) { ring_read_a16(ah, al, abase, cc, 0, 0); ring_read_a16(ah, al, abase, cc, 0, 1); ring_read_a16(ah, al, abase, cc, 0, 2); ring_read_a16(ah, al, abase, cc, 0, 3); }
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
                 const int s = cc * 9 + tap, slot = s % H_RING, nslot = (s + H_AHEAD) % H_RING;
@@ -253,135 +179,48 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_ring16_kernel(GemmArgs g
                     if (ABL == 4) continue;
                     // refill the two slots: blocks (i0 + 4, i1 + 4) of this tap, or blocks (i0 - 4, i1 - 4) of the next tap
                     if (pr < 2) {
-                        if (pr == 0) { HQT_READ_A16(cc, tapoff, 4); HQT_READ_A16(cc, tapoff, 5); }
-                        else { HQT_READ_A16(cc, tapoff, 6); HQT_READ_A16(cc, tapoff, 7); }
+                        if (pr == 0) { ring_read_a16(ah, al, abase, cc, tapoff, 4); ring_read_a16(ah, al, abase, cc, tapoff, 5); }
+                        else { ring_read_a16(ah, al, abase, cc, tapoff, 6); ring_read_a16(ah, al, abase, cc, tapoff, 7); }
                     } else if (tap < 8) {
-                        if (pr == 2) { HQT_READ_A16(cc, ntapoff, 0); HQT_READ_A16(cc, ntapoff, 1); }
-                        else { HQT_READ_A16(cc, ntapoff, 2); HQT_READ_A16(cc, ntapoff, 3); }
+                        if (pr == 2) { ring_read_a16(ah, al, abase, cc, ntapoff, 0); ring_read_a16(ah, al, abase, cc, ntapoff, 1); }
+                        else { ring_read_a16(ah, al, abase, cc, ntapoff, 2); ring_read_a16(ah, al, abase, cc, ntapoff, 3); }
                     }
-                    if (pr == 0 && ABL != 5) load_b(S + H_AHEAD, nslot);            // the slot tap s - 1 released takes the filters of tap s + 2
+                    if (pr == 0 && ABL != 5) ring_load_b4(wh[nslot], wl[nslot], lane16, bfrag, S + H_AHEAD);            // the slot tap s - 1 released takes the filters of tap s + 2
                     if (pr == 1 && ABL != 2) {
                         // the piece of tap - 2: behind it were issued the filters of tap + 1 (4), the piece of tap - 1 and the filters of tap + 2 (4)
-                        if (tap >= 2 && tap - 2 < PPW) {
-                            if (tap - 1 < PPW) asm volatile("s_waitcnt vmcnt(9)" : "+v"(pst[tap % 2]));
+                        if (tap >= 2 && tap - 2 < R_PPW) {
+                            if (tap - 1 < R_PPW) asm volatile("s_waitcnt vmcnt(9)" : "+v"(pst[tap % 2]));
                             else asm volatile("s_waitcnt vmcnt(8)" : "+v"(pst[tap % 2]));
-                            HQT_STORE_PIECE(cc ^ 1, tap - 2, tap % 2);
+                            ring_store_piece(piece_base, pst[tap % 2], cc ^ 1, tap - 2);
                         }
-                        if (tap < PPW) load_piece(cn, tap, tap % 2);
+                        if (tap < R_PPW) ring_load_piece(pst[tap % 2], poff, img_rsrc, cn, tap, g.Cin);
                     }
                 }
             }
         }
     }
-#undef HQT_READ_A16
-#undef HQT_STORE_PIECE
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                       // the patch buffers become the epilogue's staging area
     __builtin_amdgcn_sched_barrier(0);
-    if (ABL == 1) {
-        float sacc = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) sacc += accm[i][j][r] + accx[i][j][r];
-        if (sacc == 12345.678f) reinterpret_cast<float*>(g.C)[0] = sacc;
-        return;
-    }
+    if (ABL == 1) { ring_sink_acc(g, accm, accx); return; }
     // ---- epilogue.  D map: col = lane & 15 -> pixel fx of tile row i; row = 4 (lane >> 4) + r -> channel 16 j + 4 fk + r of the wave's 32.
-    //      Staged store, 64 pixels (tile rows 4 half .. 4 half + 3) at a time, then as the ring kernel.
+    //      Staged store, 64 pixels (tile rows 4 half .. 4 half + 3) at a time, then whole NHWC rows (split_ring.h).
     const long long pix0 = ((long long)img * g.H + ty0) * g.W + tx0;
     char* stage = lds_raw;
-    float* Cb = reinterpret_cast<float*>(g.C);
-    const float* Rb = reinterpret_cast<const float*>(g.resid);
-    const int c8 = (tid & 15) * 8, nn = n0 + c8;
-    float bv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bv[e] = (g.bias && nn + e < g.N) ? g.bias[nn + e] : 0.0f;
+    float bv[8], gs[8], gq[8];
+    ring_bias8(g, n0 + (tid & 15) * 8, bv);
     bool bad = false;
-    float gs[8], gq[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { gs[e] = 0.0f; gq[e] = 0.0f; }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         if (half > 0) __syncthreads();                  // the previous half has been read back
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) {
-            const int i = half * 4 + ii, r = ii * 16 + fx;      // pixel within the staged 64
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int nl = wave * 32 + j * 16 + 4 * fk;
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = accm[i][j][e] + accx[i][j][e] * R_INV;
-                *reinterpret_cast<f32x4*>(stage + r * R_CPITCH + nl * 4) = v;
-            }
-        }
+        h_stage_half(stage, accm, accx, half, wave, fx, fk);
         __syncthreads();
-        if (nn < g.N) {                                 // N % 8 == 0
-            long long moff[4];
-            f32x4 r0[4], r1[4];
-#pragma unroll
-            for (int p4 = 0; p4 < 4; ++p4) {            // the residual rows of the four passes are fetched together
-                const int r = p4 * 16 + (tid >> 4);
-                moff[p4] = (pix0 + (long long)(half * 4 + (r >> 4)) * g.W + (r & 15)) * g.ldc + nn;
-                if (Rb) { r0[p4] = *reinterpret_cast<const f32x4*>(Rb + moff[p4]); r1[p4] = *reinterpret_cast<const f32x4*>(Rb + moff[p4] + 4); }
-            }
-#pragma unroll
-            for (int p4 = 0; p4 < 4; ++p4) {
-                const int r = p4 * 16 + (tid >> 4);
-                const f32x4 lo = *reinterpret_cast<const f32x4*>(stage + r * R_CPITCH + c8 * 4);
-                const f32x4 hi = *reinterpret_cast<const f32x4*>(stage + r * R_CPITCH + c8 * 4 + 16);
-                float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = v[e] * g.alpha + bv[e];
-                if (Rb) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { v[e] += r0[p4][e]; v[4 + e] += r1[p4][e]; }
-                }
-                if (g.out_split) {                      // uniform: the consumer is a SPLIT conv with no GroupNorm in front -- its operand planes leave from here
-                    unsigned hi[4], lo[4];
-                    split8_checked(v, hi, lo, bad);
-                    half_t* P = reinterpret_cast<half_t*>(g.C) + 2 * moff[p4] - nn;         // pixel * 2 N + channel (ldc == N)
-                    *reinterpret_cast<u32x4*>(P) = u32x4{hi[0], hi[1], hi[2], hi[3]};
-                    *reinterpret_cast<u32x4*>(P + g.N) = u32x4{lo[0], lo[1], lo[2], lo[3]};
-                } else {
-                    const f32x4 o0 = {v[0], v[1], v[2], v[3]}, o1 = {v[4], v[5], v[6], v[7]};
-                    *reinterpret_cast<f32x4*>(Cb + moff[p4]) = o0;
-                    *reinterpret_cast<f32x4*>(Cb + moff[p4] + 4) = o1;
-                }
-                if (g.gn_part_out_d) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { gs[e] += v[e]; gq[e] += v[e] * v[e]; }
-                }
-            }
-        }
+        ring_store_rows<4, true>(g, stage, tid, n0, bv, true, [&](int r) { return pix0 + (long long)(half * 4 + (r >> 4)) * g.W + (r & 15); }, gs, gq, bad);
     }
     if (bad && g.range_flag) atomicOr(g.range_flag, 1);
-    if (g.gn_part_out_d) {                              // uniform branch (kernel argument): barriers are safe here
-        __syncthreads();
-        float* redw = reinterpret_cast<float*>(lds_raw);                    // [16 pixel rows][128 channels][2]; zeros from idle threads
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            redw[(((tid >> 4) * 128) + c8 + e) * 2] = gs[e];
-            redw[(((tid >> 4) * 128) + c8 + e) * 2 + 1] = gq[e];
-        }
-        __syncthreads();
-        const float* red = reinterpret_cast<const float*>(lds_raw);
-        if (tid < 128) {
-            double sa = 0.0, sq = 0.0;
-#pragma unroll
-            for (int rg = 0; rg < 16; ++rg) { sa += (double)red[((rg * 128) + tid) * 2]; sq += (double)red[((rg * 128) + tid) * 2 + 1]; }
-            const int cpg = g.N / g.gn_out_groups;
-            for (int off = cpg >> 1; off > 0; off >>= 1) { sa += __shfl_xor(sa, off, 64); sq += __shfl_xor(sq, off, 64); }
-            const int ch = n0 + tid;
-            if (ch < g.N && (tid & (cpg - 1)) == 0) {
-                double* pp = g.gn_part_out_d + (((long long)img * (tiles_x * tiles_y) + trem) * g.gn_out_groups + ch / cpg) * 2;
-                pp[0] = sa; pp[1] = sq;
-            }
-        }
-    }
+    ring_reduce_gn(g, lds_raw, tid, gs, gq, n0, true, (long long)img * (tiles_x * tiles_y) + trem);
 }
 
 
@@ -445,44 +284,16 @@ __global__ __launch_bounds__(256, 2) void conv2x2_split_up16_kernel(GemmArgs g) 
     const int phase = tile_v / NT, pa = phase >> 1, pb = phase & 1;
     const int n0 = (tile_v - phase * NT) * 128;
     const int Hin = g.H >> 1, Win = g.W >> 1;                       // g.H / g.W: the OUTPUT
-    const int tiles_x = Win / R_TX, tiles_y = Hin / R_TY;
-    const int img = tile_m / (tiles_x * tiles_y);
-    const int trem = tile_m - img * (tiles_x * tiles_y);
-    const int ty0 = (trem / tiles_x) * R_TY, tx0 = (trem % tiles_x) * R_TX;     // low-resolution pixels
-    const half_t* Abase = reinterpret_cast<const half_t*>(g.A);                 // [pixel][hi Cin | lo Cin]
+    int img, trem, ty0, tx0, tiles_x, tiles_y;                      // ty0 / tx0: low-resolution pixels
+    ring_tile(tile_m, Hin, Win, img, trem, ty0, tx0, tiles_x, tiles_y);
     const int NC = g.Cin / 32;
 
-    // ---- patch pieces: the (8 + 2) x (16 + 2) low-resolution neighbourhood, as in the ring kernels
-    constexpr int PPW = 2 * R_PIECES / 4;
-    static_assert(PPW == 6, "six pieces per wave and chunk");
-    typedef int rsrc_t __attribute__((ext_vector_type(4)));
-    rsrc_t img_rsrc;
-    {
-        const unsigned long long ib = (unsigned long long)(size_t)(Abase + (long long)img * Hin * Win * (2 * g.Cin));
-        img_rsrc[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)ib);
-        img_rsrc[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(ib >> 32) & 0xffff);      // stride 0
-        img_rsrc[2] = __builtin_amdgcn_readfirstlane(Hin * Win * 2 * g.Cin * 2);               // bytes
-        img_rsrc[3] = 0x00020000;                                                              // raw buffer, 32-bit data format (gfx9)
-    }
+    // ---- patch pieces: the (8 + 2) x (16 + 2) low-resolution neighbourhood (split_ring.h)
+    const ring_rsrc_t img_rsrc = ring_image_rsrc(g.A, img, Hin, Win, g.Cin);
     unsigned poff[3];
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-        const int piece = wave + 4 * u;
-        const int q = piece * 16 + (lane >> 2);
-        const int qy = (q * 3641) >> 16, qx = q - qy * R_PITCH;                 // q / 18 for q < 192
-        const int iy = ty0 + qy - 1, ix = tx0 + qx - 1;
-        const bool in = (q < R_ROWS) & ((unsigned)iy < (unsigned)Hin) & ((unsigned)ix < (unsigned)Win);
-        const unsigned off = (unsigned)(((iy * Win + ix) * (2 * g.Cin) + (lane & 3) * 8) * 2);
-        poff[u] = in ? off : 0x80000000u;
-    }
-    u32x4 pst[PPW];                                                 // the six pieces of the next chunk: loaded at taps 0 / 1, written at taps 2 / 3
-    unsigned piece_base = lds_base + wave * (16 * G_PITCH) + (lane >> 2) * G_PITCH + (lane & 3) * 16;
-    auto load_piece = [&](int c, int u) {
-        asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(pst[u]) : "v"(poff[u % 3]), "s"(img_rsrc), "s"(c * 64 + (u / 3) * g.Cin * 2));
-    };
-#define HQT_STORE_PIECE(buf, u)                                                                                                \
-    asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(piece_base), "v"(pst[u]),                                            \
-                 "n"(((buf) * 2 + (u) / 3) * G_PLANE + 4 * ((u) % 3) * 16 * G_PITCH) : "memory")
+    ring_piece_offsets(poff, wave, lane, ty0, tx0, Hin, Win, Win, 0, g.Cin);
+    u32x4 pst[R_PPW];                                               // the six pieces of the next chunk: loaded at taps 0 / 1, written at taps 2 / 3
+    unsigned piece_base = ring_piece_base(lds_base, wave, lane);
 
     // this wave's filter stream: 4 KiB per tap ([block 0 hi][block 0 lo][block 1 hi][block 1 lo]), 4 taps per chunk
     const char* bfrag = reinterpret_cast<const char*>(reinterpret_cast<const half_t*>(g.Bw_up16) +
@@ -497,28 +308,17 @@ __global__ __launch_bounds__(256, 2) void conv2x2_split_up16_kernel(GemmArgs g) 
 #pragma unroll
             for (int r = 0; r < 4; ++r) { accm[i][j][r] = 0.0f; accx[i][j][r] = 0.0f; }
     // fragment of pixel block i at tap (ty, tx) of phase (pa, pb): patch row (i + pa + ty) * 18 + fx + pb + tx -- the phase goes into the base
-    const unsigned abase = lds_base + (fx + pa * R_PITCH + pb) * G_PITCH + fk * 16;
+    const unsigned abase = ring_frag_base(lds_base, fx + pa * R_PITCH + pb, fk);
     half8 ah[4], al[4];                                             // pixel blocks in flight: slot = block % 4
     half8 wh[2][2], wl[2][2];                                       // filter fragments [tap % 2][channel block]
-#define HQT_READ_A16(ps, tapoff, i)                                                                                            \
-    do {                                                                                                                       \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ah[(i) % 4]) : "v"(abase), "n"((ps) * 2 * G_PLANE + ((i) * R_PITCH + (tapoff)) * G_PITCH));            \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(al[(i) % 4]) : "v"(abase), "n"((ps) * 2 * G_PLANE + ((i) * R_PITCH + (tapoff)) * G_PITCH + G_PLANE));  \
-    } while (0)
-    auto load_b = [&](long long S, int slot) {
-        const char* p = bfrag + S * 4096;
-        asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(wh[slot][0]) : "v"(lane16), "s"(p));
-        asm volatile("global_load_dwordx4 %0, %1, %2 offset:1024" : "=v"(wl[slot][0]) : "v"(lane16), "s"(p));
-        asm volatile("global_load_dwordx4 %0, %1, %2 offset:2048" : "=v"(wh[slot][1]) : "v"(lane16), "s"(p));
-        asm volatile("global_load_dwordx4 %0, %1, %2 offset:3072" : "=v"(wl[slot][1]) : "v"(lane16), "s"(p));
-    };
 
     // ---- prologue: the first patch through the piece registers, the filters of tap 0; everything lands first
 #pragma unroll
-    for (int u = 0; u < PPW; ++u) load_piece(0, u);
+    for (int u = 0; u < R_PPW; ++u) ring_load_piece(pst[u], poff, img_rsrc, 0, u, g.Cin);
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(pst[0]), "+v"(pst[1]), "+v"(pst[2]), "+v"(pst[3]), "+v"(pst[4]), "+v"(pst[5]));
-    HQT_STORE_PIECE(0, 0); HQT_STORE_PIECE(0, 1); HQT_STORE_PIECE(0, 2); HQT_STORE_PIECE(0, 3); HQT_STORE_PIECE(0, 4); HQT_STORE_PIECE(0, 5);
-    load_b(0, 0);
+#pragma unroll
+    for (int u = 0; u < R_PPW; ++u) ring_store_piece(piece_base, pst[u], 0, u);
+    ring_load_b4(wh[0], wl[0], lane16, bfrag, 0);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
     // ---- main loop: one iteration = two chunks = 8 taps of straight-line code.  Vector-memory operations in issue order per tap t:
@@ -532,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void conv2x2_split_up16_kernel(GemmArgs g) 
             const int c = c0 + cc, cn = min(c + 1, NC - 1);
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
-            if (ABL != 4) { HQT_READ_A16(cc, 0, 0); HQT_READ_A16(cc, 0, 1); HQT_READ_A16(cc, 0, 2); HQT_READ_A16(cc, 0, 3); }
+            if (ABL != 4) { ring_read_a16(ah, al, abase, cc, 0, 0); ring_read_a16(ah, al, abase, cc, 0, 1); ring_read_a16(ah, al, abase, cc, 0, 2); ring_read_a16(ah, al, abase, cc, 0, 3); }
 #pragma unroll
             for (int tap = 0; tap < TAPS; ++tap) {
                 const int s = cc * TAPS + tap, slot = s % 2, nslot = (s + 1) % 2;
@@ -541,7 +341,7 @@ __global__ __launch_bounds__(256, 2) void conv2x2_split_up16_kernel(GemmArgs g) 
                 if (ABL != 4) {
                     if (tap == 1 || tap == 2) asm volatile("s_waitcnt vmcnt(3)" : "+v"(wh[slot][0]), "+v"(wl[slot][0]), "+v"(wh[slot][1]), "+v"(wl[slot][1]));
                     else asm volatile("s_waitcnt vmcnt(0)" : "+v"(wh[slot][0]), "+v"(wl[slot][0]), "+v"(wh[slot][1]), "+v"(wl[slot][1]));
-                    if (ABL != 5) load_b(S + 1, nslot);                               // the slot tap s - 1 released takes the filters of tap s + 1: a whole tap of MFMAs ahead
+                    if (ABL != 5) ring_load_b4(wh[nslot], wl[nslot], lane16, bfrag, S + 1);                               // the slot tap s - 1 released takes the filters of tap s + 1: a whole tap of MFMAs ahead
                 }
 #pragma unroll
                 for (int pr = 0; pr < 4; ++pr) {
@@ -573,120 +373,43 @@ __global__ __launch_bounds__(256, 2) void conv2x2_split_up16_kernel(GemmArgs g) 
                         // (already landed: see above; the count only has to be loose enough not to wait for anything younger -- the
                         //  filters of the next tap, and at tap 2 the three pieces tap 1 fetched)
                         if (tap == 2) asm volatile("s_waitcnt vmcnt(7)" : "+v"(pst[u])); else asm volatile("s_waitcnt vmcnt(4)" : "+v"(pst[u]));
-                        if (u == 0) HQT_STORE_PIECE(cc ^ 1, 0); else if (u == 1) HQT_STORE_PIECE(cc ^ 1, 1); else if (u == 2) HQT_STORE_PIECE(cc ^ 1, 2);
-                        else if (u == 3) HQT_STORE_PIECE(cc ^ 1, 3); else if (u == 4) HQT_STORE_PIECE(cc ^ 1, 4); else HQT_STORE_PIECE(cc ^ 1, 5);
+                        ring_store_piece(piece_base, pst[u], cc ^ 1, u);
                     }
                     // refill the two slots: blocks (i0 + 4, i1 + 4) of this tap, or blocks (i0 - 4, i1 - 4) of the next tap
                     if (pr < 2) {
-                        if (pr == 0) { HQT_READ_A16(cc, tapoff, 4); HQT_READ_A16(cc, tapoff, 5); }
-                        else { HQT_READ_A16(cc, tapoff, 6); HQT_READ_A16(cc, tapoff, 7); }
+                        if (pr == 0) { ring_read_a16(ah, al, abase, cc, tapoff, 4); ring_read_a16(ah, al, abase, cc, tapoff, 5); }
+                        else { ring_read_a16(ah, al, abase, cc, tapoff, 6); ring_read_a16(ah, al, abase, cc, tapoff, 7); }
                     } else if (tap < TAPS - 1) {
-                        if (pr == 2) { HQT_READ_A16(cc, ntapoff, 0); HQT_READ_A16(cc, ntapoff, 1); }
-                        else { HQT_READ_A16(cc, ntapoff, 2); HQT_READ_A16(cc, ntapoff, 3); }
+                        if (pr == 2) { ring_read_a16(ah, al, abase, cc, ntapoff, 0); ring_read_a16(ah, al, abase, cc, ntapoff, 1); }
+                        else { ring_read_a16(ah, al, abase, cc, ntapoff, 2); ring_read_a16(ah, al, abase, cc, ntapoff, 3); }
                     }
-                    if (pr >= 1 && tap < 2 && ABL != 2) load_piece(cn, 3 * tap + pr - 1);
+                    if (pr >= 1 && tap < 2 && ABL != 2) ring_load_piece(pst[3 * tap + pr - 1], poff, img_rsrc, cn, 3 * tap + pr - 1, g.Cin);
                 }
             }
         }
     }
-#undef HQT_READ_A16
-#undef HQT_STORE_PIECE
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                       // the patch buffers become the epilogue's staging area
     __builtin_amdgcn_sched_barrier(0);
-    if (ABL == 1) {
-        float sacc = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) sacc += accm[i][j][r] + accx[i][j][r];
-        if (sacc == 12345.678f) reinterpret_cast<float*>(g.C)[0] = sacc;
-        return;
-    }
+    if (ABL == 1) { ring_sink_acc(g, accm, accx); return; }
     // ---- epilogue: as the ring16 kernel, with low-resolution tile pixel (row, col) stored at output pixel (2 (ty0 + row) + pa, 2 (tx0 + col) + pb)
     char* stage = lds_raw;
-    float* Cb = reinterpret_cast<float*>(g.C);
-    const float* Rb = reinterpret_cast<const float*>(g.resid);
-    const int c8 = (tid & 15) * 8, nn = n0 + c8;
-    float bv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bv[e] = (g.bias && nn + e < g.N) ? g.bias[nn + e] : 0.0f;
-    float gs[8], gq[8];
+    float bv[8], gs[8], gq[8];
+    ring_bias8(g, n0 + (tid & 15) * 8, bv);
 #pragma unroll
     for (int e = 0; e < 8; ++e) { gs[e] = 0.0f; gq[e] = 0.0f; }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         if (half > 0) __syncthreads();                  // the previous half has been read back
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) {
-            const int i = half * 4 + ii, r = ii * 16 + fx;      // pixel within the staged 64
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int nl = wave * 32 + j * 16 + 4 * fk;
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = accm[i][j][e] + accx[i][j][e] * R_INV;
-                *reinterpret_cast<f32x4*>(stage + r * R_CPITCH + nl * 4) = v;
-            }
-        }
+        h_stage_half(stage, accm, accx, half, wave, fx, fk);
         __syncthreads();
-        if (nn < g.N) {                                 // N % 8 == 0
-            long long moff[4];
-            f32x4 r0[4], r1[4];
-#pragma unroll
-            for (int p4 = 0; p4 < 4; ++p4) {
-                const int r = p4 * 16 + (tid >> 4);
-                const long long oy = 2 * (ty0 + half * 4 + (r >> 4)) + pa, ox = 2 * (tx0 + (r & 15)) + pb;
-                moff[p4] = (((long long)img * g.H + oy) * g.W + ox) * g.ldc + nn;
-                if (Rb) { r0[p4] = *reinterpret_cast<const f32x4*>(Rb + moff[p4]); r1[p4] = *reinterpret_cast<const f32x4*>(Rb + moff[p4] + 4); }
-            }
-#pragma unroll
-            for (int p4 = 0; p4 < 4; ++p4) {
-                const int r = p4 * 16 + (tid >> 4);
-                const f32x4 lo = *reinterpret_cast<const f32x4*>(stage + r * R_CPITCH + c8 * 4);
-                const f32x4 hi = *reinterpret_cast<const f32x4*>(stage + r * R_CPITCH + c8 * 4 + 16);
-                float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = v[e] * g.alpha + bv[e];
-                if (Rb) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { v[e] += r0[p4][e]; v[4 + e] += r1[p4][e]; }
-                }
-                const f32x4 o0 = {v[0], v[1], v[2], v[3]}, o1 = {v[4], v[5], v[6], v[7]};
-                *reinterpret_cast<f32x4*>(Cb + moff[p4]) = o0;
-                *reinterpret_cast<f32x4*>(Cb + moff[p4] + 4) = o1;
-                if (g.gn_part_out_d) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { gs[e] += v[e]; gq[e] += v[e] * v[e]; }
-                }
-            }
-        }
+        ring_store_rows<4>(g, stage, tid, n0, bv, true, [&](int r) {
+            const long long oy = 2 * (ty0 + half * 4 + (r >> 4)) + pa, ox = 2 * (tx0 + (r & 15)) + pb;
+            return ((long long)img * g.H + oy) * g.W + ox;
+        }, gs, gq);
     }
-    if (g.gn_part_out_d) {                              // uniform branch (kernel argument): barriers are safe here
-        __syncthreads();
-        float* redw = reinterpret_cast<float*>(lds_raw);                    // [16 pixel rows][128 channels][2]; zeros from idle threads
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            redw[(((tid >> 4) * 128) + c8 + e) * 2] = gs[e];
-            redw[(((tid >> 4) * 128) + c8 + e) * 2 + 1] = gq[e];
-        }
-        __syncthreads();
-        const float* red = reinterpret_cast<const float*>(lds_raw);
-        if (tid < 128) {
-            double sa = 0.0, sq = 0.0;
-#pragma unroll
-            for (int rg = 0; rg < 16; ++rg) { sa += (double)red[((rg * 128) + tid) * 2]; sq += (double)red[((rg * 128) + tid) * 2 + 1]; }
-            const int cpg = g.N / g.gn_out_groups;
-            for (int off = cpg >> 1; off > 0; off >>= 1) { sa += __shfl_xor(sa, off, 64); sq += __shfl_xor(sq, off, 64); }
-            const int ch = n0 + tid;
-            if (ch < g.N && (tid & (cpg - 1)) == 0) {       // one partial per (low-resolution tile, phase): 4 tiles_x tiles_y per image
-                double* pp = g.gn_part_out_d + ((((long long)img * (tiles_x * tiles_y) + trem) * 4 + phase) * g.gn_out_groups + ch / cpg) * 2;
-                pp[0] = sa; pp[1] = sq;
-            }
-        }
-    }
+    // one partial per (low-resolution tile, phase): 4 tiles_x tiles_y per image
+    ring_reduce_gn(g, lds_raw, tid, gs, gq, n0, true, ((long long)img * (tiles_x * tiles_y) + trem) * 4 + phase);
 }
 
 
@@ -704,43 +427,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_out16_kernel(GemmArgs g)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fx = lane & 15, fk = lane >> 4;
     const int tile_m = blockIdx.y;
-    const int tiles_x = g.W / R_TX, tiles_y = g.H / R_TY;
-    const int img = tile_m / (tiles_x * tiles_y);
-    const int trem = tile_m - img * (tiles_x * tiles_y);
-    const int ty0 = (trem / tiles_x) * R_TY, tx0 = (trem % tiles_x) * R_TX;
+    int img, trem, ty0, tx0, tiles_x, tiles_y;
+    ring_tile(tile_m, g.H, g.W, img, trem, ty0, tx0, tiles_x, tiles_y);
     const int Hin = g.H >> g.upsample, Win = g.W >> g.upsample;
-    const half_t* Abase = reinterpret_cast<const half_t*>(g.A);
     const int NC = g.Cin / 32;
 
-    constexpr int PPW = 2 * R_PIECES / 4;
-    typedef int rsrc_t __attribute__((ext_vector_type(4)));
-    rsrc_t img_rsrc;
-    {
-        const unsigned long long ib = (unsigned long long)(size_t)(Abase + (long long)img * Hin * Win * (2 * g.Cin));
-        img_rsrc[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)ib);
-        img_rsrc[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(ib >> 32) & 0xffff);
-        img_rsrc[2] = __builtin_amdgcn_readfirstlane(Hin * Win * 2 * g.Cin * 2);
-        img_rsrc[3] = 0x00020000;
-    }
+    const ring_rsrc_t img_rsrc = ring_image_rsrc(g.A, img, Hin, Win, g.Cin);
     unsigned poff[3];
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-        const int piece = wave + 4 * u;
-        const int q = piece * 16 + (lane >> 2);
-        const int qy = (q * 3641) >> 16, qx = q - qy * R_PITCH;
-        const int iy = ty0 + qy - 1, ix = tx0 + qx - 1;
-        const bool in = (q < R_ROWS) & ((unsigned)iy < (unsigned)g.H) & ((unsigned)ix < (unsigned)g.W);
-        const unsigned off = (unsigned)((((iy >> g.upsample) * Win + (ix >> g.upsample)) * (2 * g.Cin) + (lane & 3) * 8) * 2);
-        poff[u] = in ? off : 0x80000000u;
-    }
+    ring_piece_offsets(poff, wave, lane, ty0, tx0, g.H, g.W, Win, g.upsample, g.Cin);
     u32x4 pst[2];
-    unsigned piece_base = lds_base + wave * (16 * G_PITCH) + (lane >> 2) * G_PITCH + (lane & 3) * 16;
-    auto load_piece = [&](int c, int u, int r) {
-        asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(pst[r]) : "v"(poff[u % 3]), "s"(img_rsrc), "s"(c * 64 + (u / 3) * g.Cin * 2));
-    };
-#define HQT_STORE_PIECE(buf, u, r)                                                                                             \
-    asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(piece_base), "v"(pst[r]),                                            \
-                 "n"(((buf) * 2 + (u) / 3) * G_PLANE + 4 * ((u) % 3) * 16 * G_PITCH) : "memory")
+    unsigned piece_base = ring_piece_base(lds_base, wave, lane);
 
     // one filter stream for the whole tile: 4 KiB per tap in the 16-channel-block packing, block 0 only ([hi][lo])
     const char* bfrag = reinterpret_cast<const char*>(g.Bw_frag16);
@@ -752,32 +448,18 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_out16_kernel(GemmArgs g)
 #pragma unroll
         for (int r = 0; r < 4; ++r) { accm[i][r] = 0.0f; accx[i][r] = 0.0f; }
     // this wave's pixel blocks = tile rows 2 wave, 2 wave + 1
-    const unsigned abase = lds_base + (2 * wave * R_PITCH + fx) * G_PITCH + fk * 16;
+    const unsigned abase = ring_frag_base(lds_base, 2 * wave * R_PITCH + fx, fk);
     half8 ah[4], al[4];                                             // [tap parity * 2 + block]
     half8 wh[H_RING], wl[H_RING];
-#define HQT_READ_A16(ps, tapoff, i, slot)                                                                                      \
-    do {                                                                                                                       \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ah[slot]) : "v"(abase), "n"((ps) * 2 * G_PLANE + ((i) * R_PITCH + (tapoff)) * G_PITCH));            \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(al[slot]) : "v"(abase), "n"((ps) * 2 * G_PLANE + ((i) * R_PITCH + (tapoff)) * G_PITCH + G_PLANE));  \
-    } while (0)
-    auto load_b = [&](long long S, int slot) {
-        const char* p = bfrag + S * 4096;
-        asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(wh[slot]) : "v"(lane16), "s"(p));
-        asm volatile("global_load_dwordx4 %0, %1, %2 offset:1024" : "=v"(wl[slot]) : "v"(lane16), "s"(p));
-    };
-    // loads issued after the filters of body step s (2 loads, fetched during step s - 2) and before step s begins
-#define HQT_YOUNGER(s) (2 * (H_AHEAD - 1) + (h_piece_at((s) - 2) ? 1 : 0) + (h_piece_at((s) - 1) ? 1 : 0))
 
 #pragma unroll
     for (int rnd = 0; rnd < 3; ++rnd) {
-        load_piece(0, 2 * rnd, 0); load_piece(0, 2 * rnd + 1, 1);
+        ring_load_piece(pst[0], poff, img_rsrc, 0, 2 * rnd, g.Cin); ring_load_piece(pst[1], poff, img_rsrc, 0, 2 * rnd + 1, g.Cin);
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(pst[0]), "+v"(pst[1]));
-        if (rnd == 0) { HQT_STORE_PIECE(0, 0, 0); HQT_STORE_PIECE(0, 1, 1); }
-        else if (rnd == 1) { HQT_STORE_PIECE(0, 2, 0); HQT_STORE_PIECE(0, 3, 1); }
-        else { HQT_STORE_PIECE(0, 4, 0); HQT_STORE_PIECE(0, 5, 1); }
+        ring_store_piece(piece_base, pst[0], 0, 2 * rnd); ring_store_piece(piece_base, pst[1], 0, 2 * rnd + 1);
     }
 #pragma unroll
-    for (int s = 0; s < H_AHEAD; ++s) load_b(s, s);
+    for (int s = 0; s < H_AHEAD; ++s) ring_load_b2(wh[s], wl[s], lane16, bfrag, s);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
 #pragma unroll 1
@@ -787,7 +469,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_out16_kernel(GemmArgs g)
             const int c = c0 + cc, cn = min(c + 1, NC - 1);
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
-            HQT_READ_A16(cc, 0, 0, 0); HQT_READ_A16(cc, 0, 1, 1);       // tap 0 -> parity 0
+            ring_read_a16(ah, al, abase, cc, 0, 0, 0); ring_read_a16(ah, al, abase, cc, 0, 1, 1);       // tap 0 -> parity 0
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
                 const int s = cc * 9 + tap, slot = s % H_RING, nslot = (s + H_AHEAD) % H_RING;
@@ -796,10 +478,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_out16_kernel(GemmArgs g)
                 const int ntapoff = ((tap + 1) / 3) * R_PITCH + (tap + 1) % 3;
                 // the next tap's fragments first (read one tap ahead into the other parity's slots), then this tap's MFMAs
                 if (tap < 8) {
-                    if (par == 0) { HQT_READ_A16(cc, ntapoff, 0, 2); HQT_READ_A16(cc, ntapoff, 1, 3); }
-                    else { HQT_READ_A16(cc, ntapoff, 0, 0); HQT_READ_A16(cc, ntapoff, 1, 1); }
+                    if (par == 0) { ring_read_a16(ah, al, abase, cc, ntapoff, 0, 2); ring_read_a16(ah, al, abase, cc, ntapoff, 1, 3); }
+                    else { ring_read_a16(ah, al, abase, cc, ntapoff, 0, 0); ring_read_a16(ah, al, abase, cc, ntapoff, 1, 1); }
                 }
-                asm volatile("s_waitcnt vmcnt(%2)" : "+v"(wh[slot]), "+v"(wl[slot]) : "n"(HQT_YOUNGER(s)));
+                asm volatile("s_waitcnt vmcnt(%2)" : "+v"(wh[slot]), "+v"(wl[slot]) : "n"(h_younger(s, 2)));
                 if (tap < 8) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(ah[2 * par]), "+v"(al[2 * par]), "+v"(ah[2 * par + 1]), "+v"(al[2 * par + 1]));
                 else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ah[2 * par]), "+v"(al[2 * par]), "+v"(ah[2 * par + 1]), "+v"(al[2 * par + 1]));
                 accm[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[slot], ah[2 * par], accm[0], 0, 0, 0);
@@ -808,19 +490,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_out16_kernel(GemmArgs g)
                 accx[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[slot], al[2 * par + 1], accx[1], 0, 0, 0);
                 accx[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[slot], ah[2 * par], accx[0], 0, 0, 0);
                 accx[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[slot], ah[2 * par + 1], accx[1], 0, 0, 0);
-                load_b(S + H_AHEAD, nslot);
-                if (tap >= 2 && tap - 2 < PPW) {
-                    if (tap - 1 < PPW) asm volatile("s_waitcnt vmcnt(5)" : "+v"(pst[tap % 2]));     // behind the piece: filters of tap + 1 (2), piece of tap - 1, filters of tap + 2 (2)
+                ring_load_b2(wh[nslot], wl[nslot], lane16, bfrag, S + H_AHEAD);
+                if (tap >= 2 && tap - 2 < R_PPW) {
+                    if (tap - 1 < R_PPW) asm volatile("s_waitcnt vmcnt(5)" : "+v"(pst[tap % 2]));     // behind the piece: filters of tap + 1 (2), piece of tap - 1, filters of tap + 2 (2)
                     else asm volatile("s_waitcnt vmcnt(4)" : "+v"(pst[tap % 2]));
-                    HQT_STORE_PIECE(cc ^ 1, tap - 2, tap % 2);
+                    ring_store_piece(piece_base, pst[tap % 2], cc ^ 1, tap - 2);
                 }
-                if (tap < PPW) load_piece(cn, tap, tap % 2);
+                if (tap < R_PPW) ring_load_piece(pst[tap % 2], poff, img_rsrc, cn, tap, g.Cin);
             }
         }
     }
-#undef HQT_READ_A16
-#undef HQT_STORE_PIECE
-#undef HQT_YOUNGER
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     // ---- epilogue: D col = lane & 15 -> pixel fx of tile row 2 wave + i; row = 4 fk + r -> channel (< N <= 16)
     float* Cb = reinterpret_cast<float*>(g.C);
