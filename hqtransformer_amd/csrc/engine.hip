@@ -428,12 +428,13 @@ static int alloc_encode_workspace(hqt_handle* h) {
     return HQT_OK;
 }
 
-// The stage-2 buffers sized by the rows of the widest pass: the body's text prompt or prefix prefill (max_prefix + 1 rows per sample; 0: one
-// row) and the widest depth sub-step.  release_old (hqt_set_max_prefix): the handle's own earlier set goes first.
+// The stage-2 buffers sized by the rows of the widest pass: the body's text prompt (followed by max_prefix rows of a code prefix) or prefix
+// prefill (max_prefix + 1 rows per sample; 0: one row) and the widest depth sub-step.  release_old (hqt_set_max_prefix): the handle's own
+// earlier set goes first.
 static int alloc_body_rows(hqt_handle* h, bool release_old) {
     const hqt_config& c = h->cfg;
     const size_t B = (size_t)c.max_batch, D = c.embed_dim;
-    const int Tp = c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : (h->max_prefix > 0 ? h->max_prefix + 1 : 1);    // rows per sample of the widest body pass
+    const int Tp = c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt + h->max_prefix : (h->max_prefix > 0 ? h->max_prefix + 1 : 1);    // rows per sample of the widest body pass
     const int Tdepth = c.code_levels == 3 ? 16 : (c.depth_decoding == HQT_DEPTH_BIDIRECTIONAL ? 5 : 4);
     const size_t rows = (B * (size_t)std::max(Tp, Tdepth) + 31) / 32 * 32;
     // packed_off() buffers are addressed with a row stride of 32 * packed_mb(M) (32 / 64 / ... / 4096 rows), which can
@@ -465,8 +466,12 @@ extern "C" int hqt_set_max_prefix(hqt_handle* h, int max_prefix) {
     if (!c.has_stage2) return fail(HQT_ERR_INVALID, "hqt_set_max_prefix: the handle was created without stage 2");
     if (h->finalized || h->parent) return fail(HQT_ERR_STATE, "hqt_set_max_prefix comes between hqt_create and hqt_finalize_weights (lanes inherit the value)");
     if (max_prefix < 0 || max_prefix > c.max_steps - 1) return fail(HQT_ERR_INVALID, "max_prefix=%d outside [0, max_steps - 1 = %d]", max_prefix, c.max_steps - 1);
-    // the MFMA prefill kernel has been shown to take the text prompt alone (up to 64 rows per sample): prompt + prefix is not built
-    if (max_prefix && c.cond_type == HQT_COND_TEXT) return fail(HQT_ERR_INVALID, "max_prefix with text conditioning is not built");
+    if (max_prefix && c.cond_type == HQT_COND_TEXT) {     // the prompt and the prefix share one prefill of ctx_len_txt + prefix_len rows per sample
+        // (the two-level 'bidirectional' head with text conditioning is refused by hqt_create)
+        if (c.code_levels == 3) return fail(HQT_ERR_INVALID, "max_prefix with text conditioning and three code levels is not built (two code levels are)");
+        if ((long long)c.max_batch * (c.ctx_len_txt + max_prefix) > PACKED_MAX_ROWS)
+            return fail(HQT_ERR_INVALID, "max_batch * (ctx_len_txt + max_prefix) = %d * (%d + %d) exceeds the %d rows of one pass", c.max_batch, c.ctx_len_txt, max_prefix, PACKED_MAX_ROWS);
+    }
     if (max_prefix == h->max_prefix) return HQT_OK;
     ON_DEVICE(h);
     h->max_prefix = max_prefix;
@@ -1599,11 +1604,12 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     if (c.n_steps < 1 || c.n_steps > cf.max_steps) return fail(HQT_ERR_INVALID, "n_steps=%d outside [1, %d]", c.n_steps, cf.max_steps);
     if (cf.cond_type != HQT_COND_NONE && !cond) return fail(HQT_ERR_INVALID, "cond is required for class/text conditioning");
     if (c.with_prefix) {
-        if (cf.cond_type == HQT_COND_TEXT) return fail(HQT_ERR_INVALID, "a code prefix with text conditioning is not built");
+        if (cf.cond_type == HQT_COND_TEXT && c.levels == 3)
+            return fail(HQT_ERR_INVALID, "a code prefix with text conditioning and three code levels is not built (two code levels are)");
         if (c.prefix_len < 1 || c.prefix_len >= c.n_steps)
             return fail(HQT_ERR_INVALID, "prefix_len=%d outside [1, n_steps - 1 = %d]: at least one position must be left to draw", c.prefix_len, c.n_steps - 1);
         if (c.prefix_len > h->max_prefix)
-            return fail(HQT_ERR_INVALID, "prefix_len=%d exceeds max_prefix=%d of this handle (hqt_set_max_prefix sizes the body workspace for max_prefix + 1 rows per sample)", c.prefix_len, h->max_prefix);
+            return fail(HQT_ERR_INVALID, "prefix_len=%d exceeds max_prefix=%d of this handle (hqt_set_max_prefix sizes the body workspace for the prefill's rows)", c.prefix_len, h->max_prefix);
         for (int i = 0; i < c.levels; ++i) if (!c.prefix[i]) return fail(HQT_ERR_INVALID, "prefix codes of level %d are NULL", i);
     }
     if (c.row_set) {                             // per-row settings replace the scalars of `opts`: those are neither checked nor part of the graph key
@@ -1778,25 +1784,33 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
     }
     if (!c.row_seeds) HIPCHK(launch_set_rows(h->rows, B, c.seed, c.sample_offset, c.st));
     int first = 0;
+    const int64_t* const own[3] = {h->codes_top, h->codes_bot, h->codes_l2};
     if (cf.cond_type == HQT_COND_TEXT) {     // 64-token causal prefill (sampling.py:187-190, layers.py:107-111)
-        const int T = cf.ctx_len_txt;
-        HIPCHK(launch_embed_text(c.cond, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, B, T, cf.embed_dim, c.st, cf.vocab_txt));
-        CHK(run_position(h, c, T, 0, false));
-        HIPCHK(launch_advance_step(h->state, T, c.st));
-        first = 1;
-    }
-    if (c.prefix_len) {
+        // With a code prefix of P positions the prompt and the prefix are ONE pass of T + P rows per sample: rows 0 .. T - 1 the prompt rows,
+        // row T + j the input the decode step at position j + 1 computes from the codes of position j (embed_row, read from the handle's
+        // code buffers).  K/V of all rows go to the cache; ln_f and the depth head run on the last row and draw position P: the step state
+        // says (P, 0) while the pass runs and (P + 1, T + P) afterwards.  P = 0: the launches of before, unchanged.
+        const int T = cf.ctx_len_txt, P = c.prefix_len;
+        if (P) HIPCHK(launch_set_step(h->state, P, 0, c.st));
+        HIPCHK(launch_embed_text(c.cond, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, B, T, cf.embed_dim, c.st, cf.vocab_txt, T + P));
+        if (P) {
+            Timed t(h, "embed_prefix", c.st);
+            HIPCHK(launch_embed_prefix(embed_args(h, c, own), P, T + P, T, 1, c.st));
+        }
+        CHK(run_position(h, c, T + P, 0, false));
+        HIPCHK(launch_advance_step(h->state, T + P, c.st));
+        first = P + 1;
+    } else if (c.prefix_len) {
         // Prefix prefill: the P + 1 body input rows of every sample (sos, then the embeddings of positions 0 .. P - 1, read from the
         // handle's code buffers) in one launch, all body blocks causally over them -- K/V of all rows go to the cache --, the depth
         // head on the last row, which draws position P: the step state says P while that pass runs (sampler keys, noise slice, where
         // the codes go), and P + 1 over P + 1 keys afterwards.  Like the text prefill the pass takes the classic path (Tq_body > 1:
         // run_body); the persistent chain first reads the step state in the decode steps below, behind the advance.
         const int P = c.prefix_len;
-        const int64_t* const own[3] = {h->codes_top, h->codes_bot, h->codes_l2};
         HIPCHK(launch_set_step(h->state, P, 0, c.st));
         {
             Timed t(h, "embed_prefix", c.st);
-            HIPCHK(launch_embed_prefix(embed_args(h, c, own), P + 1, c.st));
+            HIPCHK(launch_embed_prefix(embed_args(h, c, own), P + 1, P + 1, 0, 0, c.st));
         }
         CHK(run_position(h, c, P + 1, 0, false));
         HIPCHK(launch_advance_step(h->state, P + 1, c.st));

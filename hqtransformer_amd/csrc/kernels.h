@@ -36,15 +36,15 @@ struct EmbedArgs {
     int V, n_classes;            // table sizes for the index clamp (0: unchecked)
 };
 hipError_t launch_embed_step(const EmbedArgs& a, hipStream_t st);
-// prefix prefill: x[b * rows_per_sample + j] = body input row j of sample b (row 0: sos; row j: position j - 1's codes), the arithmetic of
-// launch_embed_step; `state` is not read and no packed copy is written
-hipError_t launch_embed_prefix(const EmbedArgs& a, int rows_per_sample, hipStream_t st);
+// prefix prefill: x[b * stride + row_off + j] = body input row step_off + j of sample b, j < rows (row 0: sos; row s: position s - 1's codes),
+// the arithmetic of launch_embed_step; `state` is not read and no packed copy is written
+hipError_t launch_embed_prefix(const EmbedArgs& a, int rows, int stride, int row_off, int step_off, hipStream_t st);
 // dst[b, p < P, :] = src[b, p, :] for one code level (dst [B, n_steps, width], src [B, P, width]), clamped into [0, V)
 hipError_t launch_copy_prefix(const int64_t* src, int64_t* dst, int B, int P, int n_steps, int width, int V, hipStream_t st);
 
-// text prefix: x[b, t, :] = tok_emb_txt[cond[b, t]] + pos_emb_txt[t]
+// text prompt: x[b * rows_per_sample + t, :] = tok_emb_txt[cond[b, t]] + pos_emb_txt[t]
 hipError_t launch_embed_text(const int64_t* cond, const float* tok, const float* pos, float* x, int B, int T, int D,
-                             hipStream_t st, int vocab = 0);
+                             hipStream_t st, int vocab = 0, int rows_per_sample = 0);      // rows_per_sample 0: T
 
 // depth sub-step 1 input: x[b*4+s, :] = tok_top_depth[top[b, step]] + pos_depth[s]
 hipError_t launch_depth_embed(const int64_t* codes_top, int n_steps, const StepState* state, const float* tok,

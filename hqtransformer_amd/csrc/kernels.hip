@@ -123,16 +123,19 @@ hipError_t launch_embed_step(const EmbedArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-// Prefix prefill: the rows_per_sample = P + 1 body input rows of every sample in one launch, x[b * (P + 1) + j] = embed_row(b, j) -- row 0 the
-// sos row, row j the input the decode step at position j would have computed from the codes of position j - 1 (a.codes_*: the handle's
-// code buffers, which hold the prefix).  One workgroup per row; no packed copy (the prefill pass takes the classic LayerNorm path).
-__global__ __launch_bounds__(256) void embed_prefix_kernel(EmbedArgs a, int rows_per_sample) {
-    const int row = blockIdx.x, b = row / rows_per_sample, j = row - b * rows_per_sample;
-    embed_row(a, b, j, a.x + (long long)row * a.D);
+// Prefix prefill: `rows` body input rows of every sample in one launch, x[b * stride + row_off + j] = embed_row(b, step_off + j), j < rows.
+// Class-conditional / unconditional (stride = rows = P + 1, no offsets): row 0 the sos row, row j the input the decode step at position j
+// would have computed from the codes of position j - 1 (a.codes_*: the handle's code buffers, which hold the prefix).  Text (stride = T + P,
+// row_off = T, step_off = 1, rows = P): the rows behind the prompt rows embed_text_kernel wrote.  One workgroup per row; no packed copy
+// (the prefill pass takes the classic LayerNorm path).
+__global__ __launch_bounds__(256) void embed_prefix_kernel(EmbedArgs a, int rows, int stride, int row_off, int step_off) {
+    const int b = blockIdx.x / rows, j = blockIdx.x - b * rows;
+    embed_row(a, b, step_off + j, a.x + ((long long)b * stride + row_off + j) * a.D);
 }
-hipError_t launch_embed_prefix(const EmbedArgs& a, int rows_per_sample, hipStream_t st) {
-    if (rows_per_sample < 2 || rows_per_sample > a.n_steps || a.xpk) return hipErrorInvalidValue;
-    embed_prefix_kernel<<<a.B * rows_per_sample, 256, 0, st>>>(a, rows_per_sample);
+hipError_t launch_embed_prefix(const EmbedArgs& a, int rows, int stride, int row_off, int step_off, hipStream_t st) {
+    // (embed_row reads the codes of position step - 1 < n_steps)
+    if (rows < 1 || row_off < 0 || step_off < 0 || row_off + rows > stride || step_off + rows > a.n_steps || a.xpk) return hipErrorInvalidValue;
+    embed_prefix_kernel<<<a.B * rows, 256, 0, st>>>(a, rows, stride, row_off, step_off);
     return hipGetLastError();
 }
 
@@ -151,15 +154,18 @@ hipError_t launch_copy_prefix(const int64_t* src, int64_t* dst, int B, int P, in
     return hipGetLastError();
 }
 
+// The T prompt rows of every sample, x[b * rows_per_sample + t] (rows_per_sample > T: a code prefix's rows follow, embed_prefix_kernel)
 __global__ __launch_bounds__(256) void embed_text_kernel(const int64_t* cond, const float* tok, const float* pos,
-                                                         float* x, int T, int D, int vocab) {
-    const int row = blockIdx.x, t = row % T;
-    const long long id = clamp_idx(cond[row], vocab);
-    for (int d = threadIdx.x; d < D; d += blockDim.x) x[(long long)row * D + d] = tok[id * D + d] + pos[(long long)t * D + d];
+                                                         float* x, int T, int D, int vocab, int rows_per_sample) {
+    const int b = blockIdx.x / T, t = blockIdx.x % T;
+    const long long id = clamp_idx(cond[blockIdx.x], vocab), row = (long long)b * rows_per_sample + t;
+    for (int d = threadIdx.x; d < D; d += blockDim.x) x[row * D + d] = tok[id * D + d] + pos[(long long)t * D + d];
 }
 hipError_t launch_embed_text(const int64_t* cond, const float* tok, const float* pos, float* x, int B, int T, int D,
-                             hipStream_t st, int vocab) {
-    embed_text_kernel<<<B * T, 256, 0, st>>>(cond, tok, pos, x, T, D, vocab);
+                             hipStream_t st, int vocab, int rows_per_sample) {
+    if (rows_per_sample == 0) rows_per_sample = T;
+    if (rows_per_sample < T) return hipErrorInvalidValue;
+    embed_text_kernel<<<B * T, 256, 0, st>>>(cond, tok, pos, x, T, D, vocab, rows_per_sample);
     return hipGetLastError();
 }
 
@@ -758,6 +764,119 @@ __global__ __launch_bounds__(256) void attention_prefill_mfma_kernel(AttnArgs a)
 #endif
 }
 
+// Causal prefill of any row count (the text prompt followed by a code prefix: more than 64 rows per sample), FAST precision, head size 64,
+// nothing cached before it: ONE wave per (sample, head, 32-query tile) walks the key tiles kt = 0 .. qt with the two products and operand
+// orders of attention_prefill_mfma_kernel -- S^T = K Q^T leaves a query's scores in one lane, O^T = V^T P^T takes the probabilities,
+// converted in place, as its B operand -- and an online softmax: running maximum and (per lane half) running sum of each query, the two O
+// accumulator tiles rescaled per key tile.  A lane's column of S^T and of O^T is its query, so the rescale is lane-local.  What a wave holds
+// does not depend on T: one Q tile, one K tile, one V tile pair (strided 2-byte loads, issued before the scores are computed), two
+// accumulators.  Rows beyond T are clamped on load (they repeat the last row), masked in the scores of every valid query (key <= query < T)
+// and never stored; key tiles above the diagonal are never visited; the diagonal tile is masked element-wise.
+__global__ __launch_bounds__(256) void attention_prefill_tiled_kernel(AttnArgs a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+    typedef __attribute__((ext_vector_type(8))) unsigned short u16x8_t;
+    typedef __attribute__((ext_vector_type(16))) float f32x16_t;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int T = a.Tq, nqt = (T + 31) / 32;
+    const int gid = blockIdx.x * 4 + wave;
+    if (gid >= a.B * a.n_heads * nqt) return;                         // idle waves of the last workgroup (no workgroup-wide step follows)
+    const int qt = nqt - 1 - gid % nqt, bh = gid / nqt;               // the longest walks of a (sample, head) first
+    const int h = bh % a.n_heads, b = bh / a.n_heads;
+    const int D = a.n_heads * 64;
+    const int r = lane & 31, hf = lane >> 5;
+    const bf16_t* qb = reinterpret_cast<const bf16_t*>(a.q) + (long long)b * T * D + h * 64;
+    const bf16_t* kb = reinterpret_cast<const bf16_t*>(a.kcache) + (long long)b * a.Tmax * D + h * 64;
+    const bf16_t* vb = reinterpret_cast<const bf16_t*>(a.vcache) + (long long)b * a.Tmax * D + h * 64;
+    const int q = 32 * qt + r;
+    bf16x8_t qf[4];
+    {
+        const long long row = min(q, T - 1);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8_t*>(qb + row * D + 16 * ks + 8 * hf);
+    }
+    const float scale = 1.0f / sqrtf(64.0f);
+    f32x16_t o[2];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[dt][i] = 0.0f;
+    float m = -INFINITY, sum = 0.0f;                                  // m: over all keys of the query (both lane halves agree); sum: this half's keys
+    for (int kt = 0; kt <= qt; ++kt) {
+        bf16x8_t kf[4];
+        {
+            const long long row = min(32 * kt + r, T - 1);
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) kf[ks] = *reinterpret_cast<const bf16x8_t*>(kb + row * D + 16 * ks + 8 * hf);
+        }
+        // V^T fragments: element j <- V[key(kt, s2, hf, j)][32 dt + r], the order in which the accumulator registers hold P
+        u16x8_t vraw[2][2];
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const long long key = min(32 * kt + 16 * s2 + 8 * (j >> 2) + 4 * hf + (j & 3), T - 1);
+                    vraw[dt][s2][j] = vb[key * D + 32 * dt + r];
+                }
+        f32x16_t sc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sc[i] = 0.0f;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], sc, 0, 0, 0);
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int key = 32 * kt + (i & 3) + 8 * (i >> 2) + 4 * hf;
+            const float v = key <= q ? sc[i] * scale : -INFINITY;     // masks only in the diagonal tile
+            sc[i] = v;
+            tmax = fmaxf(tmax, v);
+        }
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));                 // the other half of this tile's keys; finite: key 32 kt <= q is visible
+        const float m_new = fmaxf(m, tmax);
+        const float alpha = __expf(m - m_new);                        // 0 in the first tile (m = -inf)
+        m = m_new;
+        sum *= alpha;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
+        bf16x8_t pf[2];
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float e = __expf(sc[8 * s2 + j] - m);           // 0 for masked keys
+                sum += e;
+                pf[s2][j] = (__bf16)e;
+            }
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2)
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, vraw[dt][s2]), pf[s2], o[dt], 0, 0, 0);
+    }
+    sum += __shfl_xor(sum, 32, 64);
+    const float inv_sum = 1.0f / sum;
+    if (q < T) {
+        const int row = b * T + q;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const int col = h * 64 + 32 * dt + 8 * g4 + 4 * hf;
+                bf16_t* dst = a.out_packed_mb ? reinterpret_cast<bf16_t*>(a.out) + packed_off(row, col, a.out_packed_mb)
+                                              : reinterpret_cast<bf16_t*>(a.out) + (long long)row * D + col;
+                uint2 pk;
+                pk.x = (unsigned)f32_to_bf16(o[dt][4 * g4] * inv_sum) | ((unsigned)f32_to_bf16(o[dt][4 * g4 + 1] * inv_sum) << 16);
+                pk.y = (unsigned)f32_to_bf16(o[dt][4 * g4 + 2] * inv_sum) | ((unsigned)f32_to_bf16(o[dt][4 * g4 + 3] * inv_sum) << 16);
+                *reinterpret_cast<uint2*>(dst) = pk;
+            }
+    }
+#endif
+}
+
 // The same few-query case with head size 64 and at most 8 keys (depth sub-step 1: 4 queries x 5 keys), from 64 samples: EIGHT heads per
 // wave.  A head is the 8 lanes that cover one 128-byte key / value row, and all its keys sit in that group's registers, so a wave holds
 // 8 x (NK keys + NK values + Tq queries) x 16 bytes in flight instead of one head's, an eighth of the waves are dispatched (at 2048
@@ -1018,7 +1137,16 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t st) {
             return hipGetLastError();
         }
     }
-    // causal prefill of a whole prompt (bf16, head size 64, nothing cached before it): the matrix-core kernel, one wave per (sample, head)
+    // causal prefill of a whole prompt (bf16, head size 64, nothing cached before it) on the matrix cores: up to 64 rows per sample one wave
+    // per (sample, head) with the whole problem in registers, above that one wave per 32-query tile (attention_prefill_tiled_kernel).
+    // HQT_PREFILL_TILED=1 (test hook, read per launch so that one process can compare the two): the tiled kernel from 5 rows on
+    if (a.causal && a.dtype == DT_BF16 && a.head_dim == 64 && a.Tq > 4 && a.t_base == 0 && !a.t_base_dev && !a.dbg &&
+        (a.n_heads * 64) % 8 == 0 && (a.Tq > 64 || getenv("HQT_PREFILL_TILED") != nullptr)) {
+        if (a.Tq > a.Tmax) return hipErrorInvalidValue;
+        const long long waves = (long long)a.B * a.n_heads * ((a.Tq + 31) / 32);
+        attention_prefill_tiled_kernel<<<(unsigned)((waves + 3) / 4), 256, 0, st>>>(a);
+        return hipGetLastError();
+    }
     if (a.causal && a.dtype == DT_BF16 && a.head_dim == 64 && a.Tq > 4 && a.Tq <= 64 && a.t_base == 0 && !a.t_base_dev && !a.dbg &&
         (a.n_heads * 64) % 8 == 0) {
         const int g2 = (a.B * a.n_heads + 3) / 4;

@@ -87,14 +87,24 @@ _FORCE_NAMES = {2: ('force_top', 'force_bot'), 3: ('force[0]', 'force[1]', 'forc
 _CODE_NAMES = {2: ('code_t', 'code_b'), 3: ('code grid',) * 3}
 
 
-def check_prefix(s2: Stage2Spec, batch: int, n_steps: int, prefix, max_prefix: Optional[int] = None) -> Optional[list]:
+def check_prefix(s2: Stage2Spec, batch: int, n_steps: int, prefix, max_prefix: Optional[int] = None, text_prefix: bool = False) -> Optional[list]:
     """A code prefix checked on the host, before any engine is built or touched: ``prefix`` is the list of code levels, coarse to fine,
     int64 [B, P], [B, P, 4][, [B, P, 16]] with 1 <= P <= n_steps - 1 (and P <= ``max_prefix`` when given); every code inside the vocabulary
-    (IndexError otherwise, as nn.Embedding raises in the reference).  Returns the levels as tensors; None stays None."""
+    (IndexError otherwise, as nn.Embedding raises in the reference).  Returns the levels as tensors; None stays None.
+    ``text_prefix``: a text-conditional model takes the prefix (two code levels with the causal 'parallel' depth head: the prompt and the prefix
+    share one prefill of ctx_len_txt + P rows per sample); a caller asks for it explicitly, because of the row workspace it costs."""
     if prefix is None:
         return None
     if s2.cond == 2:
-        raise ValueError('a code prefix with text conditioning is not built (the prompt and the prefix would share one prefill)')
+        if not text_prefix:
+            raise ValueError('a code prefix with text conditioning shares one prefill with the prompt (ctx_len_txt + P rows per sample) and is '
+                             'run on request only: pass text_prefix=True')
+        if s2.depth_decoding == 'bidirectional':
+            raise ValueError("a code prefix with text conditioning is built for the two-level 'parallel' depth head; the 'bidirectional' head "
+                             "with text conditioning is not built at all (the reference's own step does not pick the last text token)")
+        if s2.levels == 3:
+            raise ValueError("a code prefix with text conditioning is built for two code levels (the 'parallel' depth head); three code levels "
+                             'with text conditioning are not')
     L = s2.levels
     if not isinstance(prefix, (list, tuple)) or len(prefix) != L:
         raise ValueError(f'prefix: expected the {L} code levels as one list, coarse to fine')
@@ -320,7 +330,8 @@ class Engine:
         """Returns (codes [B, n], [B, n, 4][, [B, n, 16]], logits [n, draws, B, V] or None)."""
         dev = self.device
         B, V, L = int(batch), self.s2.vocab_top, int(levels)
-        prefix = check_prefix(self.s2, B, n_steps, prefix, self.max_prefix)
+        # (a text engine was asked for the shared prompt + prefix prefill when it was built with max_prefix; without it P > max_prefix = 0 refuses)
+        prefix = check_prefix(self.s2, B, n_steps, prefix, self.max_prefix, text_prefix=True)
         P = 0 if prefix is None else int(prefix[0].shape[1])
         draws = (4 ** L - 1) // 3                   # one draw per code of a position: 1 + 4 (+ 16)
         shapes = [(B, n_steps) + ((4 ** l,) if l else ()) for l in range(L)]
@@ -376,7 +387,8 @@ class Engine:
         """Two-level sampling: returns (codes_top [B, n], codes_bot [B, n, 4][, logits [n, 5, B, V]]).
         ``prefix`` = [top [B, P], bot [B, P, 4]], 1 <= P <= min(n - 1, max_prefix of this engine): completion (``hqt_sample_prefix``) -- the
         returned codes hold the prefix at positions < P, and positions >= P are drawn as a free run would draw them had its first P positions
-        produced these codes (same Philox keys, same slice of ``noise``, same sampler settings); the prefix runs through the body in ONE pass.
+        produced these codes (same Philox keys, same slice of ``noise``, same sampler settings); the prefix runs through the body in ONE pass
+        (text conditioning: together with the prompt, ctx_len_txt + P rows per sample).
         ``row_seeds`` / ``row_offsets`` (both or neither, ``batch`` entries): merged steps -- row b draws what the row with
         global index ``row_offsets[b]`` of a call seeded ``row_seeds[b]`` draws (``hqt_sample_opts.row_seeds``).
         ``row_samplers`` (``batch`` entries ``(temperature per level, top_k per level, top_p per level)``, see ``row_sampler_table``): row b

@@ -89,8 +89,9 @@ def complete_images(model, images: torch.Tensor, keep_rows: int, cond=None, enco
     """Keep the first ``keep_rows`` rows of every image's top code grid and sample the rest: ``images`` fp32 [B, 3, R, R] in [-1, 1] (what
     ``stage1.get_codes`` takes) -> ``stage1`` codes -> the codes of the first ``P = keep_rows * top_resolution`` positions on every level (the
     bottom / middle grids cut at the matching rows) as ``prefix_codes`` of one sampler call over all ``top_resolution ** 2`` positions ->
-    ``decode_codes``.  ``cond``: class ids as in ``sampling_ihqgpt``; ``sampler``: further keywords of that sampler (cut-offs, temperatures,
-    seed, precision ...).  Returns ``(pixels fp32 [B, 3, R, R] in [0, 1], codes)`` with ``codes`` the full-length code list, coarse to fine;
+    ``decode_codes``.  ``cond``: class ids as in ``sampling_ihqgpt``, or text prompts [B, ctx_len_txt] (two code levels: the prompt and the
+    prefix then share one prefill, ``text_prefix=True`` of ``sampling_ihqgpt``); ``sampler``: further keywords of that sampler (cut-offs,
+    temperatures, seed, precision ...).  Returns ``(pixels fp32 [B, 3, R, R] in [0, 1], codes)`` with ``codes`` the full-length code list, coarse to fine;
     its positions < P are the image's own codes."""
     grids = list(model.stage1.code_grids(images, precision=encode_precision))
     K = int(grids[0].shape[-1])
@@ -98,6 +99,8 @@ def complete_images(model, images: torch.Tensor, keep_rows: int, cond=None, enco
         raise ValueError(f'keep_rows={keep_rows} outside [1, {K - 1}]: at least one row of the {K} x {K} top grid is kept and one is left to sample')
     P = int(keep_rows) * K
     prefix = [s[:, :P].contiguous() for s in grids_to_sequences(grids)]
+    if model.stage2.use_txt_cond and model.stage2.spec.levels == 2:
+        sampler['text_prefix'] = True
     codes = sample_codes(model.stage2, int(images.shape[0]), cond, max_seq_len=K * K, prefix_codes=prefix, **sampler)
     return decode_codes(model.stage1, codes, decode_precision), codes
 

@@ -74,7 +74,8 @@ def sampling_ihqgpt(model,
                     row_offsets=None,
                     precision: Optional[str] = None,
                     row_samplers=None,
-                    prefix_codes=None):
+                    prefix_codes=None,
+                    text_prefix: bool = False):
     """Returns ``(codes_top int64 [B, max_seq_len], codes_bot int64 [B, max_seq_len, 4])`` on the model's GPU.
 
     ``model`` is ``ImageGPT2.stage2``.  ``cond``: python int (class id, repeated for every candidate), an
@@ -95,7 +96,9 @@ def sampling_ihqgpt(model,
     ``prefix_codes`` = ``[top [B, P], bot [B, P, 4]]``, 1 <= P <= max_seq_len - 1: completion -- the first P positions of the returned codes are
     these, the rest is drawn as a free run would draw it had its first P positions produced them (same Philox keys / ``noise`` slice per absolute
     position; ``given_top_code`` keeps its meaning for positions >= P).  The prefix goes through the body in one causal pass, not P decode steps.
-    Not with text conditioning.
+    With text conditioning only on request, ``text_prefix=True``: the prompt and the prefix then share ONE prefill of ctx_len_txt + P rows per
+    sample, and the engine's row workspace is sized for it (about twice the row buffers at the CC-15M shape: DESIGN §5.4); without the flag a
+    text model refuses ``prefix_codes`` with ValueError before any engine is built.
 
     The call is asynchronous and does not read the device's flags: 'split' passes above 256 rows SATURATE activations outside the fp16 range and
     only flag them, and a persistent FAST launch (up to 64 samples) that could not finish on a shared GPU only marks the handle -- call
@@ -103,7 +106,7 @@ def sampling_ihqgpt(model,
     """
     spec = model.spec
     B, cond = _batch_and_cond(model, num_candidates, cond)
-    prefix = check_prefix(spec, B, max_seq_len, prefix_codes)       # refused here, before an engine is built
+    prefix = check_prefix(spec, B, max_seq_len, prefix_codes, text_prefix=text_prefix)       # refused here, before an engine is built
     force_top = None
     if given_top_code is not None and spec.depth_decoding == 'bidirectional':
         # the reference passes given_top_code to the 'parallel' head only and silently ignores it here (hierarchical_ar.py:451-479)

@@ -38,6 +38,10 @@ def common_arguments(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--decode-precision', choices=['split', 'exact', 'fast'], default='split',
                    help='the reference decodes in fp32: split = fp32-accurate on the matrix cores (default), exact = fp32 vector ALUs, fast = bf16')
+    p.add_argument('--complete-from', type=str, default=None, metavar='FILE.npy',
+                   help='complete images instead of sampling from scratch: float32 [N, 3, H, W] in [0, 1] (the layout of the samples this driver writes); '
+                        'row i of a batch completes image (batch index * batch size + i) mod N.  Needs --keep-rows')
+    p.add_argument('--keep-rows', type=int, default=None, help='with --complete-from: rows of the top code grid kept from the image (1 .. top_resolution - 1)')
     return p
 
 
@@ -46,10 +50,6 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--batch-size', type=int, default=50)
     p.add_argument('--num-classes', type=int, default=1000)
     p.add_argument('--samples-per-class', type=int, default=None, help='default 50000 // num_classes')
-    p.add_argument('--complete-from', type=str, default=None, metavar='FILE.npy',
-                   help='complete images instead of sampling from scratch: float32 [N, 3, H, W] in [0, 1] (the layout of the samples this driver writes); '
-                        'row i of a batch completes image (batch index * batch size + i) mod N.  Needs --keep-rows')
-    p.add_argument('--keep-rows', type=int, default=None, help='with --complete-from: rows of the top code grid kept from the image (1 .. top_resolution - 1)')
     return p
 
 
@@ -109,8 +109,9 @@ def sample_pixels(model: ImageGPT2, args, num_candidates: int, cond) -> np.ndarr
     images = getattr(args, 'complete_images', None)
     if images is not None:               # --complete-from: the same sampler settings, the first rows of every image kept
         first = getattr(args, 'complete_next', 0)
-        args.complete_next = first + num_candidates
-        rows = torch.from_numpy(images[np.arange(first, first + num_candidates) % len(images)])
+        count = int(cond.shape[0]) if model.stage2.use_txt_cond else num_candidates      # text: one image per prompt
+        args.complete_next = first + count
+        rows = torch.from_numpy(images[np.arange(first, first + count) % len(images)])
         pixels, _ = complete_images(model, 2.0 * rows - 1.0, args.keep_rows, cond=cond, decode_precision=args.decode_precision, softmax_temperature=temps,
                                     use_fp16=True, **sampler_cutoffs(args.code_level, args.top_k, args.top_p))
         model.stage1.range_check()
@@ -124,10 +125,8 @@ def sample_pixels(model: ImageGPT2, args, num_candidates: int, cond) -> np.ndarr
     return pixels.cpu().numpy()
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
-    if args.code_level not in (2, 3):
-        raise NotImplementedError('--code-level must be 2 or 3')
+def load_completion(args) -> None:
+    """``--complete-from`` / ``--keep-rows`` of either driver, checked; the images go to ``args.complete_images``."""
     if (args.complete_from is None) != (args.keep_rows is None):
         raise SystemExit('--complete-from and --keep-rows come together')
     if args.complete_from is not None:
@@ -136,6 +135,13 @@ def main(argv=None):
             raise SystemExit(f'--complete-from: expected float32 [N, 3, H, W], got {args.complete_images.shape}')
         if not 1 <= args.keep_rows < args.top_resolution:
             raise SystemExit(f'--keep-rows must lie in [1, top_resolution - 1 = {args.top_resolution - 1}]')
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.code_level not in (2, 3):
+        raise NotImplementedError('--code-level must be 2 or 3')
+    load_completion(args)
     set_seed(args.seed)
     os.makedirs(args.result_path, exist_ok=True)
     model = load_model(args.model_path).eval()

@@ -10,6 +10,8 @@ one ``samples_({batch+1}_{batch_size}).pkl`` per batch = pickle of a float32 num
 (:213-216).  The caption source replaces the hard-wired CC3M directory of the reference's ``CC3MTextOnly``
 (``--captions``: its ``val_list.txt`` format or one caption per line); ``--synthetic-prompts N`` draws random token ids
 instead (no tokenizer files needed: smoke runs).  The last, shorter batch is kept (the reference's DataLoader does the same).
+``--complete-from FILE.npy --keep-rows R`` (no reference counterpart): meaning and file formats of ``sampling_hqmodel --complete-from`` -- prompt i
+completes image i mod N to its caption, the first R rows of its top code grid kept.
 """
 from __future__ import annotations
 
@@ -19,7 +21,7 @@ import os
 import torch
 
 from . import text as T
-from .sampling_hqmodel import common_arguments, load_model, sample_pixels, save_pickle
+from .sampling_hqmodel import common_arguments, load_completion, load_model, sample_pixels, save_pickle
 from .utils import set_seed
 
 
@@ -58,6 +60,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.code_level != 2:
         raise NotImplementedError('--code-level 3 (HQTransformer 3-level path) is not built yet (SURVEY.md §8f rank 1)')
+    load_completion(args)
     set_seed(args.seed)
     os.makedirs(args.result_path, exist_ok=True)
     model = load_model(args.model_path).eval()

@@ -254,12 +254,13 @@ int hqt_sample_l3(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_op
                   int64_t* out0, int64_t* out1, int64_t* out2, void* stream);
 /* hqt_set_max_prefix -- no reference counterpart.  Largest code prefix a later hqt_sample_prefix / hqt_sample_prefix_l3 call on this handle
  * may pass.  A handle starts with max_prefix = 0: such calls are refused and the workspace is what hqt_create has always allocated.  The
- * prefix prefill runs all body blocks over max_batch * (max_prefix + 1) rows at once; this call re-sizes the body workspace (activations,
+ * prefix prefill runs all body blocks over max_batch * (max_prefix + 1) rows at once (text conditioning: the prompt and the prefix share
+ * one pass of max_batch * (ctx_len_txt + max_prefix) rows); this call re-sizes the body workspace (activations,
  * split-K slabs, packed copies -- not the KV cache, which max_steps already covers) for that pass.  An entry point and not a field of
  * hqt_config, so that the struct, and with it ABI version 9, stay what they are (as with hqt_set_row_samplers).  Call it between hqt_create
  * and hqt_finalize_weights (HQT_ERR_STATE afterwards: lanes, captured graphs and the persistent chain's phase tables hold workspace pointers);
  * lanes made by hqt_clone inherit the value.  HQT_ERR_INVALID: max_prefix outside [0, max_steps - 1], a handle without stage 2, text
- * conditioning. */
+ * conditioning with three code levels, text conditioning with max_batch * (ctx_len_txt + max_prefix) beyond the 16384 rows of one pass. */
 int hqt_set_max_prefix(hqt_handle* h, int max_prefix);
 
 /* hqt_sample_prefix / hqt_sample_prefix_l3 -- completion (no reference counterpart as a call: the reference can only
@@ -269,6 +270,8 @@ int hqt_set_max_prefix(hqt_handle* h, int max_prefix);
  * tables.  The prefix is not fed through the model one position at a time: its prefix_len + 1 body input rows per sample (the sos / class row,
  * then the input embedding of every prefix position) are written by one kernel and all body blocks run causally over them in ONE pass that
  * fills the KV cache; the depth head runs on the last row only and draws position prefix_len.  The remaining positions are ordinary decode steps.
+ * Text conditioning (two code levels): the ctx_len_txt prompt rows and the prefix_len input rows of positions 1 .. prefix_len are that ONE
+ * pass (ctx_len_txt + prefix_len rows per sample; FAST: the tiled matrix-core prefill attention from 65 rows on).
  *   prefix_len   1 .. min(n_steps - 1, max_prefix of the handle: hqt_set_max_prefix)
  *   prefix_top   int64 [B, prefix_len]; prefix_bot int64 [B, prefix_len, 4]   (l3: prefix0 [B, P], prefix1 [B, P, 4], prefix2 [B, P, 16]);
  *                values outside the vocabulary are clamped into it on the device, as every id that arrives from the caller (cond,
@@ -279,7 +282,7 @@ int hqt_set_max_prefix(hqt_handle* h, int max_prefix);
  *   force_*      [B, n_steps] ... as in hqt_sample; entries of positions < prefix_len are not read
  *   logits_out   as in hqt_sample; the rows of positions < prefix_len are not written
  * Every other argument as in hqt_sample / hqt_sample_l3.  HQT_ERR_INVALID: prefix_len < 1, prefix_len >= n_steps, prefix_len >
- * the handle's max_prefix (the message names hqt_set_max_prefix), a NULL prefix pointer, a text-conditional model. */
+ * the handle's max_prefix (the message names hqt_set_max_prefix), a NULL prefix pointer, a text-conditional model with three code levels. */
 int hqt_sample_prefix(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts* opts, const float* noise,
                       int prefix_len, const int64_t* prefix_top, const int64_t* prefix_bot,
                       const int64_t* force_top, const int64_t* force_bot, float* logits_out,

@@ -5,6 +5,9 @@
     forced    the only way without the feature: ``Engine.sample`` of n_steps = P with force_top / force_bot, i.e. P teacher-forced decode steps,
               each with its depth head, two heads and five draws (graphed).  Uses nothing newer, so the file also runs in an older checkout:
               the figure of record for this mode is taken on the parent commit
+With a text-conditional ``--config`` (configs/cc15m-12l-txt.yaml) the same two modes around the prompt: ``prefix`` is the ONE pass of
+ctx_len_txt + P rows per sample that draws position P, ``forced`` the prompt prefill followed by P teacher-forced decode steps (n_steps = P + 1:
+the prefill draws position 0, the last step position P); the record is profiles/text_prefix_prefill.json.
 Each mode: HIP events around the call, median of --reps after --warmup, one JSON line.  ``--merge FORCED.json PREFIX.json --out FILE`` joins two such
 lines into the record (profiles/prefix_prefill.json) with their ratio.
     python tools/bench_prefix.py --mode prefix [--P 32] [--reps 5] [--warmup 2]"""
@@ -49,9 +52,10 @@ def main():
     from hqtransformer_amd.models import ImageGPT2
     B, P = a.batch, a.P
     m = ImageGPT2(load_config(a.config), seed=0).to('cuda').eval()
-    V = m.stage2.spec.vocab_top
+    spec = m.stage2.spec
+    V, text = spec.vocab_top, spec.cond == 2
     g = torch.Generator().manual_seed(0)
-    cond = torch.randint(0, 1000, (B,), generator=g).cuda()
+    cond = (torch.randint(0, spec.vocab_txt, (B, spec.ctx_len_txt), generator=g) if text else torch.randint(0, 1000, (B,), generator=g)).cuda()
     top, bot = torch.randint(0, V, (B, P), generator=g).cuda(), torch.randint(0, V, (B, P, 4), generator=g).cuda()
     if a.mode == 'prefix':
         eng = m.stage2.engine(B, P + 1, max_prefix=P)
@@ -59,10 +63,13 @@ def main():
         def run():
             eng.sample(B, cond, P + 1, precision=PRECISION_FAST, seed=1, prefix=[top, bot])
     else:
-        eng = m.stage2.engine(B, P)
+        n = P + 1 if text else P
+        eng = m.stage2.engine(B, n)
+        if text:                                     # position P is drawn, as in the prefix mode: its forced entry is never embedded
+            top, bot = torch.cat([top, top[:, :1]], 1), torch.cat([bot, bot[:, :1]], 1)
 
         def run():
-            eng.sample(B, cond, P, precision=PRECISION_FAST, seed=1, force_top=top, force_bot=bot)
+            eng.sample(B, cond, n, precision=PRECISION_FAST, seed=1, force_top=top, force_bot=bot)
     for _ in range(a.warmup):
         run()
     torch.cuda.synchronize()
@@ -75,7 +82,7 @@ def main():
         torch.cuda.synchronize()
         ms.append(round(e0.elapsed_time(e1), 3))
     eng.range_check()
-    print(json.dumps({'mode': a.mode, 'B': B, 'P': P, 'ms': ms, 'ms_median': statistics.median(ms), 'workspace_bytes': eng.workspace_bytes()}), flush=True)
+    print(json.dumps({'mode': a.mode, 'B': B, 'P': P, 'rows_per_sample': (spec.ctx_len_txt if text else 0) + (P if text or a.mode == 'forced' else P + 1), 'ms': ms, 'ms_median': statistics.median(ms), 'workspace_bytes': eng.workspace_bytes()}), flush=True)
 
 
 if __name__ == '__main__':
