@@ -147,6 +147,7 @@ struct hqt_handle {
     int rows_next = 0;
     RowSampler* row_set = nullptr;            // [max_batch] per-row sampler settings of the current call (hqt_set_row_samplers)
     std::vector<hqt_row_sampler> row_set_staged;   // host table waiting for the next hqt_sample / hqt_sample_l3 of this handle, which takes it
+    float* logprob_staged = nullptr;          // hqt_set_logprob_out: device fp32 [B, n_steps, draws] the next sampling call of this handle takes (and clears)
     int64_t *cond_buf = nullptr, *codes_top = nullptr, *codes_bot = nullptr;   // call-independent homes of cond / the drawn codes
     int64_t* codes_l2 = nullptr;              // third level: [B, max_steps, 16]
     Lin head_l2;                              // head_levels.2 (three-level models; head_top / head_bot hold levels 0 / 1)
@@ -585,6 +586,7 @@ extern "C" int hqt_clone(hqt_handle* src, hqt_handle** out) {
     for (int i = 0; i < hqt_handle::ROWS_RING; ++i) { h->rows_pinned[i] = nullptr; h->rows_ev[i] = nullptr; h->rows_busy[i] = false; }
     h->rows_next = 0;
     h->row_set_staged.clear();                   // a lane has its own table
+    h->logprob_staged = nullptr;                 // ... and its own log-probability buffer
     h->nparts = h->npartsd = 0;
     h->pbody.d_phases = nullptr; h->pfull.d_phases = nullptr;      // phase tables hold workspace pointers: bound per handle (persist_bind)
     h->persist_used = false; h->persist_tripped = false; h->capture_persist = false; h->graph_has_persist = false;
@@ -1095,6 +1097,7 @@ struct SampleCtx {
     const int64_t* prefix[3] = {nullptr, nullptr, nullptr};   // ... as [B, prefix_len], [B, prefix_len, 4][, [B, prefix_len, 16]]
     bool with_prefix = false;                    // the call came through a prefix entry point (prefix_len is then validated)
     float* logits_out;
+    float* logprob_out = nullptr;                // hqt_set_logprob_out: [B, n_steps, draws], NULL: no code_logprob launches at all
     hipStream_t st;
     Mode md;
 };
@@ -1547,6 +1550,13 @@ static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body
                 sa.emb_xpk = dln_next ? h->xdpk : nullptr; sa.emb_pk_mb = dln_next ? packed_mb(4 * B) : 0; sa.emb_parts = h->partsd;
             }
             HIPCHK(launch_sampler(sa, c.st));
+            if (c.logprob_out) {      // one launch per draw of this sub-step, each under the timing slot of its own: the sampler's scope ends with the sampler
+                t.next("code_logprob");
+                for (int slot = 0; slot < s.Tq; ++slot) {
+                    if (slot) t.next("code_logprob");
+                    HIPCHK(launch_code_logprob(sa, c.feed[s.lv], c.logprob_out, slot, c.st));
+                }
+            }
         }
     }
     return HQT_OK;
@@ -1593,6 +1603,8 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     std::vector<hqt_row_sampler> staged;
     staged.swap(h->row_set_staged);
     const size_t staged_rows = staged.size();
+    c.logprob_out = h->logprob_staged;           // ... and so does the staged log-probability buffer
+    h->logprob_staged = nullptr;
     c.row_set = staged_rows ? staged.data() : nullptr;
     if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
     const hqt_config& cf = h->cfg;
@@ -1661,6 +1673,12 @@ template <class Opts> static SampleCtx sample_ctx(int levels, int B, const Opts*
 
 static_assert(sizeof(hqt_row_sampler) == 36 && sizeof(RowSampler) == sizeof(hqt_row_sampler), "hqt_row_sampler is copied to the device as RowSampler");
 
+extern "C" int hqt_set_logprob_out(hqt_handle* h, float* logprobs) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    h->logprob_staged = logprobs;                // NULL clears; the shape [B, n_steps, draws] is the taking call's (the caller sizes the buffer for it)
+    return HQT_OK;
+}
+
 extern "C" int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler* rows) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
     h->row_set_staged.clear();
@@ -1674,7 +1692,7 @@ extern "C" int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler*
 static int sample2(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts* opts, const float* noise, int prefix_len,
                    const int64_t* prefix_top, const int64_t* prefix_bot, const int64_t* force_top, const int64_t* force_bot,
                    float* logits_out, int64_t* out_top, int64_t* out_bot, void* stream) {
-    if (h && (!opts || !out_top || !out_bot)) h->row_set_staged.clear();
+    if (h && (!opts || !out_top || !out_bot)) { h->row_set_staged.clear(); h->logprob_staged = nullptr; }
     if (!h || !opts || !out_top || !out_bot) return fail(HQT_ERR_INVALID, "null argument");
     SampleCtx c = sample_ctx(2, B, opts, noise, logits_out);
     c.lv[0] = {opts->temperature_top, opts->top_k_top, opts->top_p_top};
@@ -1688,7 +1706,7 @@ static int sample2(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_o
 static int sample3(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts_l3* opts, const float* noise, int prefix_len,
                    const int64_t* const* prefix, const int64_t* force0, const int64_t* force1, const int64_t* force2, float* logits_out,
                    int64_t* out0, int64_t* out1, int64_t* out2, void* stream) {
-    if (h && (!opts || !out0 || !out1 || !out2)) h->row_set_staged.clear();
+    if (h && (!opts || !out0 || !out1 || !out2)) { h->row_set_staged.clear(); h->logprob_staged = nullptr; }
     if (!h || !opts || !out0 || !out1 || !out2) return fail(HQT_ERR_INVALID, "null argument");
     SampleCtx c = sample_ctx(3, B, opts, noise, logits_out);
     for (int i = 0; i < 3; ++i) c.lv[i] = {opts->temperature[i], opts->top_k[i], opts->top_p[i]};
@@ -1824,7 +1842,7 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         static const int gmax = getenv("HQT_GRAPH_POSITIONS") ? std::max(1, atoi(getenv("HQT_GRAPH_POSITIONS"))) : 16;
         int G = 1;
         for (int d = std::min(gmax, remaining); d >= 1; --d) if (remaining % d == 0) { G = d; break; }
-        std::vector<uint64_t> key = {(uint64_t)G, (uint64_t)B, (uint64_t)(c.cond != nullptr), (uint64_t)c.noise, (uint64_t)c.logits_out,
+        std::vector<uint64_t> key = {(uint64_t)G, (uint64_t)B, (uint64_t)(c.cond != nullptr), (uint64_t)c.noise, (uint64_t)c.logits_out, (uint64_t)c.logprob_out,
                                      (uint64_t)c.precision, (uint64_t)c.n_steps, (uint64_t)c.levels, (uint64_t)h->policy,
                                      (uint64_t)((h->persist_enabled && !h->persist_tripped ? 1 : 0) + (h->single_key ? 0 : 4) + (h->split_kslices ? 0 : 8))};
         for (const int64_t* f : c.feed) key.push_back((uint64_t)f);

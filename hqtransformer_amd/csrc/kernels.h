@@ -138,6 +138,10 @@ struct SamplerArgs {
 // Uniform call: one launch.  With a row table in a FAST pass whose vocabulary the register-resident kernel takes: that kernel, then the general one, each over
 // every row -- which rows are in which class is read on the device, so the launch sequence does not depend on the table's values.
 hipError_t launch_sampler(const SamplerArgs& a, hipStream_t st);
+// code_logprob_kernel, behind launch_sampler on the same stream with the same arguments: logprob[(b * n_steps + step) * draws + draw0 + slot] = log-softmax of the RAW row
+// b * slots + slot of a.logits (before temperature, no cut-off; IEEE expf / logf in every precision) at feed[index of that draw in `out`] -- `feed` is the forced
+// codes of the level, or a.out itself (the code just drawn).  One launch per slot, B workgroups; a row's value depends on its own bits and V only.
+hipError_t launch_code_logprob(const SamplerArgs& a, const int64_t* feed, float* logprob, int slot, hipStream_t st);
 // depth sub-step 2 of the three-level model (hqtransformer.py:537-551): token i (raster (H1 H2 W1 W2)) =
 // tok1[codes1[b, step, parent(i)]] + pos[i] (+ tok0[codes0[b, step]]: 'add', tok0 non-NULL), 16 rows per sample; tok1_ld = 4 D:
 // the 'reduce' table, child (H2 W2) takes its D-slice of the parent's row

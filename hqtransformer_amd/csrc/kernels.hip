@@ -1685,6 +1685,65 @@ hipError_t launch_sampler(const SamplerArgs& args, hipStream_t st) {
     return hipGetLastError();
 }
 
+// Log-probability of the code a draw feeds forward, under the model's own distribution (T = 1, no cut-off): l[code] - max(l) - log sum exp(l - max(l)) over the RAW
+// logits row the sampler has just read (launched behind it; the row is in L2).  One launch per draw (slot): workgroup b takes row b * slots + slot, 256 threads per
+// row as in sampler_plain_fast_kernel -- thread t owns the float4 groups t, t + 256, ... (16-byte loads, the row stays in registers between the two passes; groups past
+// V are skipped, so any V % 4 == 0 up to 1024 G4 entries works).  Two passes, IEEE expf / logf in every precision: a reported number, not a draw.  Deterministic and row-local:
+// per thread a pairwise tree over its groups (padded with zeros to G4), then the xor butterfly of the wave, then the four wave sums as (w0 + w1) + (w2 + w3) -- the
+// value depends on the row's bits and on V alone, never on B, the batch row or the other rows.  `feed` is indexed like `out`: the forced code where a level is forced
+// (clamped into the vocabulary, as the embedding kernels clamp it), else the code the sampler wrote.
+template <int G4>
+__global__ __launch_bounds__(256) void code_logprob_kernel(SamplerArgs a, const int64_t* feed, float* logprob, int slot) {
+    __shared__ float redf[4], reds[4], sel;
+    const int V = a.V, tid = threadIdx.x;
+    const int b = blockIdx.x, r = b * a.slots + slot;
+    const int step = a.state->step;
+    const int draw = a.draw0 + slot;
+    const int draws = a.draws > 0 ? a.draws : 5;
+    const float* lg = a.logits + (long long)r * V;
+    const long long pos = (long long)b * a.n_steps + step;
+    const int code = (int)clamp_idx(feed[a.out_stride > 0 ? pos * a.out_stride + a.out_slot : pos * a.slots + slot], V);
+    float4 v[G4];
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < G4; ++k) {
+        const int i4 = tid + 256 * k;
+        if (i4 * 4 < V) {                                 // V % 4 == 0
+            v[k] = *reinterpret_cast<const float4*>(lg + i4 * 4);
+            m = fmaxf(fmaxf(m, fmaxf(v[k].x, v[k].y)), fmaxf(v[k].z, v[k].w));
+            if (i4 == (code >> 2)) { const int e = code & 3; sel = e == 0 ? v[k].x : (e == 1 ? v[k].y : (e == 2 ? v[k].z : v[k].w)); }      // one thread of the workgroup
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    if ((tid & 63) == 0) redf[tid >> 6] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(redf[0], redf[1]), fmaxf(redf[2], redf[3]));
+    float s[G4];
+#pragma unroll
+    for (int k = 0; k < G4; ++k) {
+        s[k] = 0.0f;
+        if ((tid + 256 * k) * 4 < V) s[k] = (expf(v[k].x - m) + expf(v[k].y - m)) + (expf(v[k].z - m) + expf(v[k].w - m));
+    }
+#pragma unroll
+    for (int w = 1; w < G4; w <<= 1)
+#pragma unroll
+        for (int k = 0; k < G4; k += 2 * w) s[k] += s[k + w];
+    float sum = s[0];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    if ((tid & 63) == 0) reds[tid >> 6] = sum;
+    __syncthreads();
+    if (tid == 0) logprob[pos * draws + draw] = (sel - m) - logf((reds[0] + reds[1]) + (reds[2] + reds[3]));
+}
+hipError_t launch_code_logprob(const SamplerArgs& a, const int64_t* feed, float* logprob, int slot, hipStream_t st) {
+    if (a.V % 4 || a.V > HQT_MAX_V || slot < 0 || slot >= a.slots) return hipErrorInvalidValue;
+    if (a.V <= 4096) code_logprob_kernel<4><<<a.B, 256, 0, st>>>(a, feed, logprob, slot);
+    else if (a.V <= 8192) code_logprob_kernel<8><<<a.B, 256, 0, st>>>(a, feed, logprob, slot);
+    else code_logprob_kernel<16><<<a.B, 256, 0, st>>>(a, feed, logprob, slot);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------
 // A9/A10/A13: codebook gather + PixelShuffle(2) + concat, NHWC output
 // (quantizer.py:179-186, generator.py:316-318,361-364; sampling_hqmodel.py:119-120)

@@ -326,8 +326,9 @@ class Engine:
     # Code levels are lists, coarse to fine; their number (2: hqt_sample, 3: hqt_sample_l3) is all that differs below.
     def _sample_levels(self, levels: int, batch: int, cond, n_steps: int, *, precision, top_k, top_p, temperature, noise, seed, sample_offset,
                        force: Sequence[Optional[torch.Tensor]], out: Optional[Sequence[torch.Tensor]], return_logits, use_graph,
-                       row_seeds, row_offsets, row_samplers=None, prefix=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor]]:
-        """Returns (codes [B, n], [B, n, 4][, [B, n, 16]], logits [n, draws, B, V] or None)."""
+                       row_seeds, row_offsets, row_samplers=None, prefix=None,
+                       return_logprobs=False) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """Returns (codes [B, n], [B, n, 4][, [B, n, 16]], logits [n, draws, B, V] or None, logprobs [B, n, draws] or None)."""
         dev = self.device
         B, V, L = int(batch), self.s2.vocab_top, int(levels)
         # (a text engine was asked for the shared prompt + prefix prefill when it was built with max_prefix; without it P > max_prefix = 0 refuses)
@@ -358,6 +359,11 @@ class Engine:
             outs = [self._check_out(t, shp, torch.int64, dev, f'out[{i}]') for i, (t, shp) in enumerate(zip(out, shapes))]
         # (with a prefix the rows of positions < P are not written: zeros)
         logits = (torch.zeros if P else torch.empty)((n_steps, draws, B, V), dtype=torch.float32, device=dev) if return_logits else None
+        # (the positions a prefix call does not compute stay NaN: a zero would read as "certain", and a sum over a half-scored sequence must not look like a score)
+        logprobs = None
+        if return_logprobs:
+            logprobs = (torch.full((B, n_steps, draws), float('nan'), dtype=torch.float32, device=dev) if P
+                        else torch.empty((B, n_steps, draws), dtype=torch.float32, device=dev))
         if P:
             entry = self.lib.hqt_sample_prefix if L == 2 else self.lib.hqt_sample_prefix_l3
 
@@ -369,12 +375,14 @@ class Engine:
         with torch.cuda.device(dev):
             if table is not None:                   # staged on the handle; the call below takes it (and clears it even when it fails)
                 _lib.check(self.lib.hqt_set_row_samplers(self.h, len(table), table.ctypes.data_as(C.POINTER(hqt_row_sampler))))
+            if logprobs is not None:                # staged like the table: taken and cleared by the call below
+                _lib.check(self.lib.hqt_set_logprob_out(self.h, _ptr(logprobs)))
             _lib.check(fn(self.h, B, _ptr(cond), C.byref(o), _ptr(noise), *map(_ptr, force), _ptr(logits), *map(_ptr, outs), C.c_void_p(stream)))
             self._note_split(precision, stream, ar_rows=B)        # every head runs persistently (run_position)
         # inputs must outlive the asynchronous launches
         self._keep = (cond, noise, force, rows, prefix)     # (the row-sampler table was copied by hqt_set_row_samplers)
         self._trust(*outs, bound=max(self.s2.vocab_top, self.s2.vocab_bot))     # the sampler only writes ids inside the vocabulary
-        return outs, logits
+        return outs, logits, logprobs
 
     def sample(self, batch: int, cond: Optional[torch.Tensor], n_steps: int, *, precision: int = PRECISION_FAST,
                top_k: Sequence[Optional[int]] = (None, None), top_p: Sequence[Optional[float]] = (None, None),
@@ -383,8 +391,11 @@ class Engine:
                return_logits: bool = False, use_graph: bool = True,
                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
-               row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None):
-        """Two-level sampling: returns (codes_top [B, n], codes_bot [B, n, 4][, logits [n, 5, B, V]]).
+               row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
+               return_logprobs: bool = False):
+        """Two-level sampling: returns (codes_top [B, n], codes_bot [B, n, 4][, logits [n, 5, B, V]][, logprobs [B, n, 5]]).
+        ``return_logprobs``: fp32 log-probability of every code the call feeds forward -- the drawn one, or the forced one where ``force_*`` is
+        given -- under the raw logits of its draw (T = 1, no cut-off: ``hqt_set_logprob_out``), appended last; with a prefix the positions < P are NaN.
         ``prefix`` = [top [B, P], bot [B, P, 4]], 1 <= P <= min(n - 1, max_prefix of this engine): completion (``hqt_sample_prefix``) -- the
         returned codes hold the prefix at positions < P, and positions >= P are drawn as a free run would draw them had its first P positions
         produced these codes (same Philox keys, same slice of ``noise``, same sampler settings); the prefix runs through the body in ONE pass
@@ -396,25 +407,27 @@ class Engine:
         those settings for every row (``hqt_set_row_samplers``)."""
         if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
             raise ValueError('out: expected a pair (codes_top [B, n_steps], codes_bot [B, n_steps, 4])')
-        outs, logits = self._sample_levels(2, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
+        outs, logits, logprobs = self._sample_levels(2, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(force_top, force_bot), out=out,
                                            return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
-                                           row_samplers=row_samplers, prefix=prefix)
-        return (outs[0], outs[1], logits) if return_logits else (outs[0], outs[1])
+                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs)
+        return (outs[0], outs[1]) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
 
     def sample3(self, batch: int, cond: Optional[torch.Tensor], n_steps: int, *, precision: int = PRECISION_FAST,
                 top_k: Sequence[Optional[int]] = (None, None, None), top_p: Sequence[Optional[float]] = (None, None, None),
                 temperature: Sequence[float] = (1.0, 1.0, 1.0), noise: Optional[torch.Tensor] = None, seed: int = 0,
                 sample_offset: int = 0, force: Optional[Sequence[torch.Tensor]] = None, return_logits: bool = False,
                 use_graph: bool = True, row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
-                row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None):
-        """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]]); ``row_samplers`` as in ``sample``;
+                row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
+                return_logprobs: bool = False):
+        """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]][, logprobs [B, n, 21]]); ``row_samplers``
+        and ``return_logprobs`` as in ``sample``;
         ``prefix`` = [[B, P], [B, P, 4], [B, P, 16]]: completion, as in ``sample`` (``hqt_sample_prefix_l3``)."""
-        outs, logits = self._sample_levels(3, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
+        outs, logits, logprobs = self._sample_levels(3, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(None,) * 3 if force is None else force,
                                            out=None, return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
-                                           row_samplers=row_samplers, prefix=prefix)
-        return (*outs, logits) if return_logits else tuple(outs)
+                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs)
+        return tuple(outs) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
 
     # ------------------------------------------------------------------ stage 1, encode side
     @property

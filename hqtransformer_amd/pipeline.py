@@ -20,13 +20,14 @@ from typing import Any, Callable, List, NamedTuple, Optional, Tuple
 import torch
 
 from ._lib import POLICY_LATENCY, POLICY_THROUGHPUT
-from .sampling import rearrange_levels, sampling_hqtransformer, sampling_ihqgpt
+from .sampling import _batch_and_cond, _precision, rearrange_levels, sampling_hqtransformer, sampling_ihqgpt
 
 
 # Code levels travel as one list, coarse to fine.  These are the only places that tell two levels from three: the sampler call, and the
 # (codes_top, codes_bot) shape of a result, whose second entry is a tensor (two levels) or the list of the finer levels (three).
 def sample_codes(stage2, num_candidates: int, cond, **kw) -> list:
-    """One ``sampling_ihqgpt`` / ``sampling_hqtransformer`` call (keywords of that sampler) -> its codes as a list."""
+    """One ``sampling_ihqgpt`` / ``sampling_hqtransformer`` call (keywords of that sampler) -> its codes as a list; ``return_logprobs=True``
+    travels with the keywords, and the log-probabilities fp32 [B, n, draws] are then the list's last entry, behind the codes."""
     sampler = sampling_hqtransformer if stage2.spec.levels == 3 else sampling_ihqgpt
     return list(sampler(stage2, num_candidates=num_candidates, cond=cond, is_tqdm=False, **kw))
 
@@ -70,6 +71,83 @@ def decode_codes(stage1, codes: list, precision: Optional[str] = None, decode_ba
         pixels = torch.cat([stage1.decode_code([g[j:j + decode_batch] for g in grids], precision=precision) for j in range(0, B, decode_batch)], dim=0)
         return (0.5 * pixels + 0.5).clamp(0, 1)
     return stage1.decode_sequences(codes, precision=precision, clamp01=True)
+
+
+def sequence_logprob(logprobs: torch.Tensor) -> torch.Tensor:
+    """Log-probabilities of a sampler call fp32 [B, n, draws] -> the log-probability of every sample's whole code sequence, fp64 [B], summed over positions and
+    draws in fp64 where the tensor lives.  NaN propagates: a sample with positions that were not scored (below a prefix) has no score -- slice them
+    away first (``logprobs[:, P:]``) for the score of the completion alone."""
+    if logprobs.dim() != 3:
+        raise ValueError(f'logprobs: expected [B, n, draws], got {tuple(logprobs.shape)}')
+    return logprobs.to(torch.float64).sum(dim=(1, 2))
+
+
+def rank_candidates(scores: torch.Tensor, keep: int) -> torch.Tensor:
+    """``scores`` [groups, candidates] -> int64 [groups, keep]: per group the indices of the ``keep`` highest scores, descending; equal scores keep their
+    order (the lower candidate index first: a stable sort)."""
+    if scores.dim() != 2 or not 1 <= int(keep) <= int(scores.shape[1]):
+        raise ValueError(f'rank_candidates: keep={keep} of scores {tuple(scores.shape)}: expected [groups, candidates] and 1 <= keep <= candidates')
+    return torch.sort(scores, dim=1, descending=True, stable=True).indices[:, :int(keep)]
+
+
+def score_codes(stage2, codes, cond, precision: Optional[str] = None, **kw) -> torch.Tensor:
+    """Log-probabilities of GIVEN codes under the model: ``codes`` = the code levels as one list, coarse to fine (int64 [B, n], [B, n, 4][, [B, n, 16]]),
+    ``cond`` as in ``sampling_ihqgpt`` -> fp32 [B, n, draws], entry (b, t, d) the log-probability (T = 1, no cut-off) of the code of draw d at position t
+    given the sample's codes before it: ``-sequence_logprob(...)`` is the stage-2 negative log-likelihood in nats.  ONE sampler call with every level forced
+    to ``codes`` (seed 0; its draws are discarded): teacher forcing through the sequential decode steps, so the cost is that of sampling n positions -- n
+    decode steps --, not of one parallel pass.  ``precision`` 'exact' | 'fast' | 'split' (default: ``use_fp16`` of ``kw``, i.e. FAST); further keywords:
+    ``use_fp16``, ``lane``, ``use_graph``.  ValueError for the 'bidirectional' depth head, where the sampling surface refuses forced codes too
+    (``given_top_code``: the reference ignores them there)."""
+    spec = stage2.spec
+    if spec.depth_decoding == 'bidirectional':
+        raise ValueError("score_codes forces every code level, which the 'bidirectional' depth head does not support (as with given_top_code: the reference ignores it there)")
+    codes = [torch.as_tensor(c) for c in codes]
+    if len(codes) != spec.levels or codes[0].dim() != 2:
+        raise ValueError(f'codes: expected the {spec.levels} code levels as one list, coarse to fine, the first of shape [B, n]')
+    use_fp16, lane = kw.pop('use_fp16', True), kw.pop('lane', 0)
+    unknown = set(kw) - {'use_graph'}
+    if unknown:
+        raise TypeError(f'score_codes: unexpected keywords {sorted(unknown)}')
+    n = int(codes[0].shape[1])
+    B, cond = _batch_and_cond(stage2, int(codes[0].shape[0]), cond)
+    if B != int(codes[0].shape[0]):
+        raise ValueError(f'codes hold {int(codes[0].shape[0])} samples, cond {B}')
+    eng = stage2.engine(B, n, lane)
+    common = dict(precision=_precision(precision, use_fp16), seed=0, return_logprobs=True, **kw)
+    if spec.levels == 3:
+        return eng.sample3(B, cond, n, force=codes, **common)[-1]
+    return eng.sample(B, cond, n, force_top=codes[0], force_bot=codes[1], **common)[-1]
+
+
+def sample_best_of(stage2, cond, num_candidates: int, keep: int, **sampler) -> Tuple[list, torch.Tensor]:
+    """Sample ``num_candidates`` per condition and keep the ``keep`` most likely: ``cond`` = class ids (an int, or a tensor / list of G ids), text prompts
+    [G, ctx_len_txt], or anything for an unconditional model (one group).  ONE sampler call over all G * num_candidates rows (group-major: row
+    g * num_candidates + c), keywords of ``sampling_ihqgpt`` / ``sampling_hqtransformer`` in ``sampler``; every candidate is scored by
+    ``sequence_logprob`` of its own draws (the model's log-probability at T = 1, whatever temperature and cut-offs drew it; with ``prefix_codes`` over
+    the completed positions only) and ranked within its group, descending, ties to the lower candidate index; codes and scores are gathered on the
+    device.  Returns ``(codes, scores)``: the code levels as one list, [G * keep, n], [G * keep, n, 4][, ...], group-major, best first, and fp64 [G, keep]."""
+    C, K = int(num_candidates), int(keep)
+    if not 1 <= K <= C:
+        raise ValueError(f'keep={K} outside [1, num_candidates={C}]')
+    if stage2.use_txt_cond:
+        cond = torch.as_tensor(cond)
+        if cond.dim() != 2:
+            raise ValueError('text conditioning expects cond of shape [G, ctx_len_txt]')
+        G = int(cond.shape[0])
+        rows = cond.repeat_interleave(C, dim=0)
+    elif stage2.use_cls_cond:
+        ids = torch.as_tensor(cond).reshape(-1).to(torch.int64)
+        G = int(ids.numel())
+        rows = ids.repeat_interleave(C)
+    else:
+        G, rows = 1, cond
+    *codes, logprobs = sample_codes(stage2, G * C, rows, return_logprobs=True, **sampler)
+    prefix = sampler.get('prefix_codes')
+    P = 0 if prefix is None else int(torch.as_tensor(prefix[0]).shape[-1])
+    scores = sequence_logprob(logprobs[:, P:]).reshape(G, C)
+    idx = rank_candidates(scores, K)                                           # [G, K], on the device
+    flat = (idx + torch.arange(G, device=idx.device).unsqueeze(1) * C).reshape(-1)
+    return [c.index_select(0, flat) for c in codes], scores.gather(1, idx)
 
 
 def grids_to_sequences(grids: list) -> list:
@@ -144,6 +222,9 @@ class _Step(NamedTuple):
     order_after_current: bool
     sample_kw: dict
 
+    def wants_logprobs(self) -> bool:
+        return bool(self.sample_kw.get('return_logprobs'))
+
     def prefix_len(self) -> int:
         """P of the step's ``prefix_codes`` (0: none)."""
         prefix = self.sample_kw.get('prefix_codes')
@@ -152,7 +233,7 @@ class _Step(NamedTuple):
     def settings(self, mixed_samplers: bool = False) -> tuple:
         """What the steps of one merged pass must share (``mixed_samplers``: all but the sampler settings, which then travel per row).
         Prefix codes belong to a step's rows like its class ids; their LENGTH is shared (a pass has one prefill)."""
-        free = ('sample_offset', 'prefix_codes') + (SAMPLER_KEYS if mixed_samplers else ())
+        free = ('sample_offset', 'prefix_codes', 'return_logprobs') + (SAMPLER_KEYS if mixed_samplers else ())
         return (self.max_seq_len, self.use_fp16, self.precision, self.clamp01, self.use_graph, self.prefix_len(),
                 {k: v for k, v in self.sample_kw.items() if k not in free})
 
@@ -214,7 +295,10 @@ class InflightSampler:
                after=None, phase_events=None, order_after_current: bool = True, **sample_kw) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], torch.cuda.Event]:
         """Queue one batch on the next lane; returns (codes_top, codes_bot, pixels or None, done_event) immediately.
         The tensors are valid once ``done_event`` has completed (or after ``drain()``).  ``phase_events``: three timing
-        events recorded on the lane's stream at AR start / AR end / decode end (lane time: phases of different lanes overlap)."""
+        events recorded on the lane's stream at AR start / AR end / decode end (lane time: phases of different lanes overlap).
+        ``return_logprobs=True`` (with the sampler keywords): the step's log-probabilities fp32 [num_candidates, max_seq_len, draws] as one more element,
+        behind ``done_event``.  Steps of a merged pass need not agree on it: the pass computes the buffer if any of its steps asks, and only
+        those steps get their rows."""
         if self.merge > 1:
             if decode is False or phase_events is not None or sample_kw.get('noise') is not None:
                 raise ValueError('merged steps support the plain sample + decode step only (no explicit noise, no phase events)')
@@ -239,7 +323,10 @@ class InflightSampler:
         ref = q[0]
         sizes = [e.num_candidates for e in q]
         los = [sum(sizes[:i]) for i in range(len(q))]
-        kw = {k: v for k, v in ref.sample_kw.items() if k not in ('sample_offset', 'prefix_codes')}
+        kw = {k: v for k, v in ref.sample_kw.items() if k not in ('sample_offset', 'prefix_codes', 'return_logprobs')}
+        want_lp = any(e.wants_logprobs() for e in q)
+        if want_lp:
+            kw['return_logprobs'] = True
         if ref.prefix_len():                         # every step's own prefix rows, in step order (one P: check_mergeable)
             where = torch.as_tensor(ref.sample_kw['prefix_codes'][0]).device       # device prefixes stay there: no copy back to the host
             kw['prefix_codes'] = [torch.cat([torch.as_tensor(e.sample_kw['prefix_codes'][l]).to(where, torch.int64) for e in q])
@@ -269,12 +356,12 @@ class InflightSampler:
         if self.record_phases:
             phases = tuple(torch.cuda.Event(enable_timing=True) for _ in range(3))
             self.phase_log.append((phases, sum(sizes)))
-        ct, cb, px, ev = self._launch(sum(sizes), cond, seed=seeds[0], max_seq_len=ref.max_seq_len, use_fp16=ref.use_fp16, decode=True,
+        ct, cb, px, ev, *lp = self._launch(sum(sizes), cond, seed=seeds[0], max_seq_len=ref.max_seq_len, use_fp16=ref.use_fp16, decode=True,
                                       precision=ref.precision, clamp01=ref.clamp01, use_graph=ref.use_graph,
                                       after=split_after if any(e.after is not None for e in q) else None, phase_events=phases,
                                       order_after_current=any(e.order_after_current for e in q), row_seeds=row_seeds, row_offsets=row_offsets, **kw)
         for e, lo in zip(q, los):
-            e.pending.value = (*_rows(ct, cb, px, lo, e.num_candidates), ev)
+            e.pending.value = (*_rows(ct, cb, px, lo, e.num_candidates), ev) + ((lp[0][lo:lo + e.num_candidates],) if e.wants_logprobs() else ())
 
     def _launch(self, num_candidates: int, cond, *, seed: Optional[int] = None, max_seq_len: int = 64, use_fp16: bool = True,
                 decode: bool = True, precision: Optional[str] = None, clamp01: bool = True, use_graph: bool = True,
@@ -284,6 +371,7 @@ class InflightSampler:
         # `ar_precision` ('exact' | 'fast' | 'split', optional, travels with the sampler settings): arithmetic of the AR loop, overriding
         # use_fp16 (sampling_ihqgpt's `precision`; the `precision` of this method is the DECODE arithmetic)
         ar_precision = sample_kw.pop('ar_precision', None)
+        want_lp = bool(sample_kw.pop('return_logprobs', False))
         st = self.streams[lane]
         caller = torch.cuda.current_stream(self.device)
         # order the lane after whatever the caller's stream has queued (inputs; earlier direct use of lane 0's engine):
@@ -303,13 +391,15 @@ class InflightSampler:
             if phase_events is not None:
                 phase_events[0].record(ast)
             codes = sample_codes(self.model.stage2, num_candidates, cond, seed=seed, max_seq_len=max_seq_len, use_fp16=use_fp16,
-                                 use_graph=use_graph, lane=lane, precision=ar_precision, **sample_kw)
+                                 use_graph=use_graph, lane=lane, precision=ar_precision, return_logprobs=want_lp, **sample_kw)
+            logprobs = codes.pop() if want_lp else None
             if phase_events is not None:
                 phase_events[1].record(ast)
         if ast is not st:
             st.wait_stream(ast)
-            for t in codes:
-                t.record_stream(st)
+            for t in (*codes, logprobs):
+                if t is not None:
+                    t.record_stream(st)
         ct, cb = _public(codes)                      # the 4-tuple shape of the result, whatever the level count
         with torch.cuda.stream(st):
             px = None
@@ -323,10 +413,10 @@ class InflightSampler:
             ev.record(st)
         # the results were allocated on the lane's stream and will be read (and eventually freed) on the caller's: tell the
         # caching allocator, or it may hand the memory to the lane again while the caller's stream still reads it
-        for t in (*codes, px):
+        for t in (*codes, px, logprobs):
             if t is not None:
                 t.record_stream(caller)
-        return ct, cb, px, ev
+        return (ct, cb, px, ev) + ((logprobs,) if want_lp else ())
 
     def release(self, batch: int, max_seq_len: int) -> None:
         """Back to the latency-oriented kernels on lane 0 (the engine direct ``sampling_ihqgpt`` calls use)."""

@@ -75,8 +75,13 @@ def sampling_ihqgpt(model,
                     precision: Optional[str] = None,
                     row_samplers=None,
                     prefix_codes=None,
-                    text_prefix: bool = False):
-    """Returns ``(codes_top int64 [B, max_seq_len], codes_bot int64 [B, max_seq_len, 4])`` on the model's GPU.
+                    text_prefix: bool = False,
+                    *,
+                    return_logprobs: bool = False):
+    """Returns ``(codes_top int64 [B, max_seq_len], codes_bot int64 [B, max_seq_len, 4])`` on the model's GPU; ``return_logprobs=True`` appends
+    ``logprobs`` fp32 [B, max_seq_len, 5]: the log-probability of every code the call feeds forward (the drawn one; the given one where
+    ``given_top_code`` forces the top level) under the raw logits of its draw -- temperature 1, no cut-off, so always finite; draw order top,
+    bot0..bot3; positions below a prefix are NaN (``hqt_set_logprob_out``; ``pipeline.sequence_logprob`` sums them per sample).
 
     ``model`` is ``ImageGPT2.stage2``.  ``cond``: python int (class id, repeated for every candidate), an
     int64 tensor [B] of class ids, an int64 tensor [B, ctx_len_txt] (text; B replaces num_candidates,
@@ -124,7 +129,7 @@ def sampling_ihqgpt(model,
     return eng.sample(B, cond, max_seq_len, precision=_precision(precision, use_fp16),
                       top_k=(top_k_top, top_k_bot), top_p=(top_p_top, top_p_bot), temperature=softmax_temperature,
                       noise=noise, seed=seed or 0, sample_offset=sample_offset, force_top=force_top, use_graph=use_graph,
-                      row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix)
+                      row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs)
 
 
 def _prefix_room(spec, prefix) -> int:
@@ -155,13 +160,15 @@ def sampling_hqtransformer(model,
                            row_offsets=None,
                            precision: Optional[str] = None,
                            row_samplers=None,
-                           prefix_codes=None):
+                           prefix_codes=None,
+                           *,
+                           return_logprobs: bool = False):
     """Counterpart of ``hqvae.utils.sampling.sampling_hqtransformer`` (sampling.py:240-307) for the three-level
     HQTransformer: returns ``[codes0 int64 [B, L], codes1 [B, L, 4], codes2 [B, L, 16]]`` on the model's GPU.
     ``top_k`` / ``top_p`` / ``softmax_temperature`` are per-level lists (None = no cut-off); ``cond`` as in
     ``sampling_ihqgpt``.  Extensions: ``noise`` fp32 [L, 21, B, V], ``seed`` / ``sample_offset``, ``lane``,
     ``row_samplers`` (per-row settings, as in ``sampling_ihqgpt``), ``prefix_codes`` = ``[t [B, P], m [B, P, 4], b [B, P, 16]]`` (completion,
-    as in ``sampling_ihqgpt``)."""
+    as in ``sampling_ihqgpt``), ``return_logprobs`` (appends fp32 [B, L, 21] to the list, as in ``sampling_ihqgpt``)."""
     spec = model.spec
     if spec.levels != 3:
         raise ValueError('sampling_hqtransformer needs the three-level HQTransformer (stage2.type multilevel-hq)')
@@ -174,7 +181,7 @@ def sampling_hqtransformer(model,
         seed = _seed_from_torch()
     return list(eng.sample3(B, cond, max_seq_len, precision=_precision(precision, use_fp16), top_k=top_k, top_p=top_p,
                             temperature=softmax_temperature, noise=noise, seed=seed or 0, sample_offset=sample_offset, use_graph=use_graph,
-                            row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix))
+                            row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs))
 
 
 def rearrange_levels(codes: List[torch.Tensor], top_resolution: int) -> tuple:

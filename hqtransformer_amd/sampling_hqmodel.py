@@ -20,7 +20,7 @@ import torch
 
 from .config import load_config
 from .models import ImageGPT2
-from .pipeline import complete_images, decode_codes, sample_codes, sampler_cutoffs
+from .pipeline import complete_images, decode_codes, sample_best_of, sample_codes, sampler_cutoffs
 from .utils import set_seed
 
 
@@ -117,8 +117,13 @@ def sample_pixels(model: ImageGPT2, args, num_candidates: int, cond) -> np.ndarr
         model.stage1.range_check()
         model.stage2.range_check()
         return pixels.cpu().numpy()
-    codes = sample_codes(model.stage2, num_candidates, cond, softmax_temperature=temps, use_fp16=True, max_seq_len=args.top_resolution * args.top_resolution,
-                         model_stage1=model.stage1, **sampler_cutoffs(args.code_level, args.top_k, args.top_p))
+    sampler = dict(softmax_temperature=temps, use_fp16=True, max_seq_len=args.top_resolution * args.top_resolution, model_stage1=model.stage1,
+                   **sampler_cutoffs(args.code_level, args.top_k, args.top_p))
+    best_of = getattr(args, 'best_of', 1)
+    if best_of > 1:                      # --best-of N: N x num_candidates per condition in one pass, the num_candidates most likely kept
+        codes, _ = sample_best_of(model.stage2, cond, best_of * num_candidates, num_candidates, **sampler)
+    else:
+        codes = sample_codes(model.stage2, num_candidates, cond, **sampler)
     pixels = decode_codes(model.stage1, codes, args.decode_precision)
     model.stage1.range_check()          # SPLIT decode: raises if an activation left the fp16 range
     model.stage2.range_check()          # FAST AR sampling of up to 64 rows: raises if a persistent launch gave up (hqt_range_check)

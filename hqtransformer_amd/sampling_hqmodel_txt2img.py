@@ -12,6 +12,8 @@ one ``samples_({batch+1}_{batch_size}).pkl`` per batch = pickle of a float32 num
 instead (no tokenizer files needed: smoke runs).  The last, shorter batch is kept (the reference's DataLoader does the same).
 ``--complete-from FILE.npy --keep-rows R`` (no reference counterpart): meaning and file formats of ``sampling_hqmodel --complete-from`` -- prompt i
 completes image i mod N to its caption, the first R rows of its top code grid kept.
+``--best-of N`` (no reference counterpart: the reference leaves the choice among its candidates to an external model): N candidates are sampled per
+caption in one pass and the most likely one under the stage-2 model is kept (``pipeline.sample_best_of``); the output format is unchanged.
 """
 from __future__ import annotations
 
@@ -25,6 +27,13 @@ from .sampling_hqmodel import common_arguments, load_completion, load_model, sam
 from .utils import set_seed
 
 
+def _at_least_one(text: str) -> int:
+    n = int(text)
+    if n < 1:
+        raise argparse.ArgumentTypeError(f'expected an integer >= 1, got {n}')
+    return n
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = common_arguments(argparse.ArgumentParser())
     p.add_argument('--batch_size', type=int, default=32)
@@ -36,6 +45,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--reference-root', type=str, default=os.environ.get('HQT_REFERENCE_ROOT'),
                    help='checkout of kakaobrain/hqtransformer to take the bundled bpe-16k vocabulary from')
     p.add_argument('--synthetic-prompts', type=int, default=0, help='N random-id prompts instead of captions (smoke runs)')
+    p.add_argument('--best-of', type=_at_least_one, default=1, metavar='N',
+                   help='sample N x num_candidates images per caption and keep the num_candidates the stage-2 model finds most likely (1: keep all)')
     return p
 
 
@@ -61,6 +72,8 @@ def main(argv=None):
     if args.code_level != 2:
         raise NotImplementedError('--code-level 3 (HQTransformer 3-level path) is not built yet (SURVEY.md §8f rank 1)')
     load_completion(args)
+    if args.best_of > 1 and args.complete_from is not None:
+        raise SystemExit('--best-of and --complete-from do not combine')
     set_seed(args.seed)
     os.makedirs(args.result_path, exist_ok=True)
     model = load_model(args.model_path).eval()

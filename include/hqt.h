@@ -213,6 +213,19 @@ int hqt_set_switch(hqt_handle* h, int which, int on);
 typedef struct { float temperature[3]; int32_t top_k[3]; float top_p[3]; } hqt_row_sampler;   /* 36 bytes */
 int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler* rows);
 
+/* hqt_set_logprob_out -- no reference counterpart: the reference draws from its logits and keeps no probability (hierarchical_ar.py:762-785).  `logprobs` is a
+ * DEVICE pointer, fp32 [B, n_steps, draws] (draws = 5, or 21 with three code levels; draw order as in `noise`), STAGED on the handle (a lane from hqt_clone has its
+ * own): the next hqt_sample / hqt_sample_l3 / hqt_sample_prefix / hqt_sample_prefix_l3 on that handle takes it and clears it, whether that call succeeds or
+ * not; NULL clears; a NULL handle is HQT_ERR_INVALID.  The taking call writes, behind every draw,
+ *   logprobs[(b * n_steps + step) * draws + draw] = l[code] - max(l) - log sum_i exp(l_i - max(l))
+ * over the RAW logits row l of that draw: before temperature, without top-k / top-p -- the model's own log-probability at T = 1, finite whatever cut-off the
+ * draw used; two passes in fp32 with IEEE expf / logf in every precision, a fixed reduction order per row (the same bits for the same logits at any B, eager
+ * or replayed).  `code` is the code the call FEEDS FORWARD: where a level is forced (force_*, given_top_code) the forced code -- not the drawn one, which is
+ * still written to out_* --, otherwise the code just drawn.  With a prefix the entries of positions < prefix_len are not written (as with logits_out).  The
+ * pointer is part of the graph key; a call without it launches exactly what it launched before, a call with it one more kernel per draw (timing slot
+ * "code_logprob").  Forcing every level to given codes makes the call a scorer of those codes, at the cost of its n_steps decode steps. */
+int hqt_set_logprob_out(hqt_handle* h, float* logprobs);
+
 /* hqt_sample -- replaces sampling_ihqgpt + iHQGPT.sampling_step (hqvae/utils/sampling.py:164-237,
  * hierarchical_ar.py:428-480, 482-563, 667-789) for a batch of B independent images.
  *   cond        int64 [B] class ids (HQT_COND_CLASS), int64 [B, ctx_len_txt] token ids
