@@ -83,6 +83,10 @@ class hqt_row_sampler(C.Structure):
     _fields_ = [('temperature', C.c_float * 3), ('top_k', C.c_int32 * 3), ('top_p', C.c_float * 3)]
 
 
+class hqt_guide_pair(C.Structure):
+    _fields_ = [('pos_row', C.c_int32), ('neg_row', C.c_int32), ('scale', C.c_float * 3)]
+
+
 class hqt_encode_out(C.Structure):
     _fields_ = [
         ('codes', C.c_void_p * 3), ('quant', C.c_void_p * 3), ('resid', C.c_void_p * 3),
@@ -103,6 +107,7 @@ SYMBOLS = {
     'hqt_set_switch': (C.c_int, [_VP, C.c_int, C.c_int]),
     'hqt_set_row_samplers': (C.c_int, [_VP, C.c_int, C.POINTER(hqt_row_sampler)]),
     'hqt_set_logprob_out': (C.c_int, [_VP, _F32P]),
+    'hqt_set_guidance': (C.c_int, [_VP, C.c_int, C.POINTER(hqt_guide_pair)]),
     'hqt_sample': (C.c_int, [_VP, C.c_int, _I64P, C.POINTER(hqt_sample_opts), _F32P, _I64P, _I64P, _F32P, _I64P, _I64P, _VP]),
     'hqt_set_max_prefix': (C.c_int, [_VP, C.c_int]),
     'hqt_sample_prefix': (C.c_int, [_VP, C.c_int, _I64P, C.POINTER(hqt_sample_opts), _F32P, C.c_int, _I64P, _I64P, _I64P, _I64P, _F32P, _I64P, _I64P, _VP]),

@@ -205,6 +205,10 @@ struct RowSampler {          // per batch row, device memory owned by the handle
     int top_k[3];            // <= 0: none
     float top_p[3];          // <= 0: none
 };
+struct GuidePair {           // device memory owned by the handle: two rows of one pass whose logits are mixed (= hqt_guide_pair of hqt.h)
+    int pos_row, neg_row;    // batch rows, both inside [0, B), different, each in at most one pair (checked on the host)
+    float scale[3];          // per code level: g = l_pos + (scale - 1) (l_pos - l_neg)
+};
 
 #define HQT_MAX_V 16384
 

@@ -141,13 +141,16 @@ struct hqt_handle {
     // per-row keys of merged steps travel through a ring of PINNED staging buffers (an asynchronous copy from pinned memory reads its
     // source when the stream gets there: a buffer is rewritten only after the copy that last read it has completed, hipEventSynchronize)
     static constexpr int ROWS_RING = 4;
-    RowKey* rows_pinned[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};       // each: RowKey[max_batch], then RowSampler[max_batch]
+    RowKey* rows_pinned[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};       // each: RowKey[max_batch], then RowSampler[max_batch], then GuidePair[guide_room]
     hipEvent_t rows_ev[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};
     bool rows_busy[ROWS_RING] = {false, false, false, false};
     int rows_next = 0;
     RowSampler* row_set = nullptr;            // [max_batch] per-row sampler settings of the current call (hqt_set_row_samplers)
     std::vector<hqt_row_sampler> row_set_staged;   // host table waiting for the next hqt_sample / hqt_sample_l3 of this handle, which takes it
     float* logprob_staged = nullptr;          // hqt_set_logprob_out: device fp32 [B, n_steps, draws] the next sampling call of this handle takes (and clears)
+    GuidePair* guide = nullptr;               // [guide_room()] pair table of the current call (hqt_set_guidance)
+    std::vector<hqt_guide_pair> guide_staged; // host table waiting for the next sampling call of this handle, which takes it
+    size_t guide_room() const { return (size_t)std::max(1, cfg.max_batch / 2); }      // a row is in at most one pair
     int64_t *cond_buf = nullptr, *codes_top = nullptr, *codes_bot = nullptr;   // call-independent homes of cond / the drawn codes
     int64_t* codes_l2 = nullptr;              // third level: [B, max_steps, 16]
     Lin head_l2;                              // head_levels.2 (three-level models; head_top / head_bot hold levels 0 / 1)
@@ -506,6 +509,7 @@ static int alloc_workspace(hqt_handle* hp) {
         CHK(dev_alloc(h.get(), (void**)&h->state, sizeof(StepState), true));
         CHK(dev_alloc(h.get(), (void**)&h->rows, B * sizeof(RowKey), true));
         CHK(dev_alloc(h.get(), (void**)&h->row_set, B * sizeof(RowSampler), true));
+        CHK(dev_alloc(h.get(), (void**)&h->guide, h->guide_room() * sizeof(GuidePair), true));
         CHK(dev_alloc(h.get(), (void**)&h->cond_buf, B * (size_t)std::max(1, c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : 1) * 8, true));
         CHK(dev_alloc(h.get(), (void**)&h->codes_top, B * (size_t)c.max_steps * 8, true));
         CHK(dev_alloc(h.get(), (void**)&h->codes_bot, B * (size_t)c.max_steps * 4 * 8, true));
@@ -587,6 +591,7 @@ extern "C" int hqt_clone(hqt_handle* src, hqt_handle** out) {
     h->rows_next = 0;
     h->row_set_staged.clear();                   // a lane has its own table
     h->logprob_staged = nullptr;                 // ... and its own log-probability buffer
+    h->guide_staged.clear();                     // ... and its own pair table
     h->nparts = h->npartsd = 0;
     h->pbody.d_phases = nullptr; h->pfull.d_phases = nullptr;      // phase tables hold workspace pointers: bound per handle (persist_bind)
     h->persist_used = false; h->persist_tripped = false; h->capture_persist = false; h->graph_has_persist = false;
@@ -1098,6 +1103,8 @@ struct SampleCtx {
     bool with_prefix = false;                    // the call came through a prefix entry point (prefix_len is then validated)
     float* logits_out;
     float* logprob_out = nullptr;                // hqt_set_logprob_out: [B, n_steps, draws], NULL: no code_logprob launches at all
+    const hqt_guide_pair* guide = nullptr;       // host table of n_guide pairs staged by hqt_set_guidance, NULL: no guide_logits launches at all
+    int n_guide = 0;
     hipStream_t st;
     Mode md;
 };
@@ -1531,6 +1538,10 @@ static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body
             CHK(run_depth(h, c, dln, s.Tq, s.tbase));
         }
         if (!in_pfull) CHK(run_head(h, c, *heads[s.lv], s.lv, M, dln, normed[s.lv]));
+        if (c.guide) {            // both rows of every pair become the guided row before anything reads the logits (the sampler, its logits_out copy, code_logprob)
+            Timed t(h, "guide_logits", c.st);
+            HIPCHK(launch_guide_logits(h->logits, h->guide, c.n_guide, V, s.Tq, s.lv, c.st));
+        }
         {
             Timed t(h, bidir ? (s.lv ? "bidir_sampler_bot" : "bidir_sampler_top") : "sampler", c.st);
             const SamplerSet& set = bidir ? bidir_set : c.lv[s.lv];
@@ -1606,6 +1617,10 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     c.logprob_out = h->logprob_staged;           // ... and so does the staged log-probability buffer
     h->logprob_staged = nullptr;
     c.row_set = staged_rows ? staged.data() : nullptr;
+    std::vector<hqt_guide_pair> guide;           // ... and the staged pair table
+    guide.swap(h->guide_staged);
+    c.guide = guide.empty() ? nullptr : guide.data();
+    c.n_guide = (int)guide.size();
     if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
     const hqt_config& cf = h->cfg;
     if (c.levels == 2 && !cf.has_stage2) return fail(HQT_ERR_STATE, "handle was created without stage 2");
@@ -1637,6 +1652,27 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
         }
     if (top_p && cf.vocab_top > 8192) return fail(HQT_ERR_INVALID, "top-p needs vocab <= 8192");
     c.row_top_p = c.row_set && top_p;
+    if (c.guide) {
+        if (cf.cond_type == HQT_COND_NONE) return fail(HQT_ERR_INVALID, "guidance needs a conditional model: this handle has cond_type HQT_COND_NONE, its rows have no condition to differ in");
+        if ((c.row_seeds || c.row_offsets) && (!c.row_seeds || !c.row_offsets)) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
+        std::vector<char> paired(B, 0);
+        for (int i = 0; i < c.n_guide; ++i) {
+            const hqt_guide_pair& p = c.guide[i];
+            if (p.pos_row < 0 || p.pos_row >= B || p.neg_row < 0 || p.neg_row >= B)
+                return fail(HQT_ERR_INVALID, "guidance pair %d: rows (%d, %d) outside [0, B=%d)", i, p.pos_row, p.neg_row, B);
+            if (p.pos_row == p.neg_row) return fail(HQT_ERR_INVALID, "guidance pair %d: pos_row == neg_row == %d", i, p.pos_row);
+            if (paired[p.pos_row] || paired[p.neg_row])
+                return fail(HQT_ERR_INVALID, "guidance pair %d: row %d appears in more than one pair", i, paired[p.pos_row] ? p.pos_row : p.neg_row);
+            paired[p.pos_row] = paired[p.neg_row] = 1;
+            for (int l = 0; l < c.levels; ++l)
+                if (!std::isfinite(p.scale[l])) return fail(HQT_ERR_INVALID, "guidance pair %d: scale[%d] is not finite", i, l);
+            // both rows must draw the same code from the same (guided) logits: same settings, same Philox key
+            if (c.row_set && memcmp(&c.row_set[p.pos_row], &c.row_set[p.neg_row], sizeof(hqt_row_sampler)))
+                return fail(HQT_ERR_INVALID, "guidance pair %d: rows %d and %d have different sampler settings in the staged row-sampler table", i, p.pos_row, p.neg_row);
+            if (c.row_seeds && (c.row_seeds[p.pos_row] != c.row_seeds[p.neg_row] || c.row_offsets[p.pos_row] != c.row_offsets[p.neg_row]))
+                return fail(HQT_ERR_INVALID, "guidance pair %d: row_seeds / row_offsets give rows %d and %d different keys (both rows of a pair must draw with one key)", i, p.pos_row, p.neg_row);
+        }
+    }
     ON_DEVICE(h);
     // The launch sequence reads cond and writes the drawn codes in buffers owned by the handle, and takes the Philox seed
     // and the global row offset from device memory: nothing that changes from call to call is baked into the captured
@@ -1679,6 +1715,18 @@ extern "C" int hqt_set_logprob_out(hqt_handle* h, float* logprobs) {
     return HQT_OK;
 }
 
+static_assert(sizeof(hqt_guide_pair) == 20 && sizeof(GuidePair) == sizeof(hqt_guide_pair), "hqt_guide_pair is copied to the device as GuidePair");
+
+extern "C" int hqt_set_guidance(hqt_handle* h, int n_pairs, const hqt_guide_pair* pairs) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    h->guide_staged.clear();
+    if (n_pairs == 0 || !pairs) return HQT_OK;
+    if (n_pairs < 0 || 2 * (long long)n_pairs > h->cfg.max_batch)
+        return fail(HQT_ERR_INVALID, "n_pairs=%d outside [0, max_batch / 2 = %d]: a pair takes two rows of the pass", n_pairs, h->cfg.max_batch / 2);
+    h->guide_staged.assign(pairs, pairs + n_pairs);      // rows, scales and keys are checked by the call that takes it
+    return HQT_OK;
+}
+
 extern "C" int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler* rows) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
     h->row_set_staged.clear();
@@ -1692,7 +1740,7 @@ extern "C" int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler*
 static int sample2(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts* opts, const float* noise, int prefix_len,
                    const int64_t* prefix_top, const int64_t* prefix_bot, const int64_t* force_top, const int64_t* force_bot,
                    float* logits_out, int64_t* out_top, int64_t* out_bot, void* stream) {
-    if (h && (!opts || !out_top || !out_bot)) { h->row_set_staged.clear(); h->logprob_staged = nullptr; }
+    if (h && (!opts || !out_top || !out_bot)) { h->row_set_staged.clear(); h->logprob_staged = nullptr; h->guide_staged.clear(); }
     if (!h || !opts || !out_top || !out_bot) return fail(HQT_ERR_INVALID, "null argument");
     SampleCtx c = sample_ctx(2, B, opts, noise, logits_out);
     c.lv[0] = {opts->temperature_top, opts->top_k_top, opts->top_p_top};
@@ -1706,7 +1754,7 @@ static int sample2(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_o
 static int sample3(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts_l3* opts, const float* noise, int prefix_len,
                    const int64_t* const* prefix, const int64_t* force0, const int64_t* force1, const int64_t* force2, float* logits_out,
                    int64_t* out0, int64_t* out1, int64_t* out2, void* stream) {
-    if (h && (!opts || !out0 || !out1 || !out2)) { h->row_set_staged.clear(); h->logprob_staged = nullptr; }
+    if (h && (!opts || !out0 || !out1 || !out2)) { h->row_set_staged.clear(); h->logprob_staged = nullptr; h->guide_staged.clear(); }
     if (!h || !opts || !out0 || !out1 || !out2) return fail(HQT_ERR_INVALID, "null argument");
     SampleCtx c = sample_ctx(3, B, opts, noise, logits_out);
     for (int i = 0; i < 3; ++i) c.lv[i] = {opts->temperature[i], opts->top_k[i], opts->top_p[i]};
@@ -1779,17 +1827,23 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
     CHK(persist_bind(h));
     HIPCHK(launch_set_step(h->state, 0, 0, c.st));
     if ((c.row_seeds || c.row_offsets) && (!c.row_seeds || !c.row_offsets)) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
-    if (c.row_seeds || c.row_set) {          // merged steps: per-row Philox keys and / or sampler settings (host arrays of B <= max_batch entries, through the pinned ring)
+    // merged steps: per-row Philox keys and / or sampler settings (host arrays of B <= max_batch entries, through the pinned ring); a guided call: its pair
+    // table, and ALWAYS the keys -- the implicit ones (seed, sample_offset + b) are built here, the negative row of every pair taking its positive row's
+    if (c.row_seeds || c.row_set || c.guide) {
         const int slot = h->rows_next;
         h->rows_next = (slot + 1) % hqt_handle::ROWS_RING;
         if (!h->rows_pinned[slot]) {
-            HIPCHK(hipHostMalloc((void**)&h->rows_pinned[slot], (size_t)h->cfg.max_batch * (sizeof(RowKey) + sizeof(RowSampler)), hipHostMallocDefault));
+            HIPCHK(hipHostMalloc((void**)&h->rows_pinned[slot], (size_t)h->cfg.max_batch * (sizeof(RowKey) + sizeof(RowSampler)) + h->guide_room() * sizeof(GuidePair), hipHostMallocDefault));
             HIPCHK(hipEventCreateWithFlags(&h->rows_ev[slot], hipEventDisableTiming));
         }
         if (h->rows_busy[slot]) HIPCHK(hipEventSynchronize(h->rows_ev[slot]));       // the copy that last read this buffer (4 calls ago) is done
         RowKey* rk = h->rows_pinned[slot];
-        if (c.row_seeds) {
-            for (int b = 0; b < B; ++b) { rk[b].seed = c.row_seeds[b]; rk[b].global_row = c.row_offsets[b]; }
+        if (c.row_seeds || c.guide) {
+            for (int b = 0; b < B; ++b) {
+                rk[b].seed = c.row_seeds ? c.row_seeds[b] : c.seed;
+                rk[b].global_row = c.row_offsets ? c.row_offsets[b] : c.sample_offset + b;
+            }
+            for (int i = 0; i < c.n_guide; ++i) rk[c.guide[i].neg_row] = rk[c.guide[i].pos_row];      // (explicit keys were checked to agree: sample_call)
             HIPCHK(hipMemcpyAsync(h->rows, rk, (size_t)B * sizeof(RowKey), hipMemcpyHostToDevice, c.st));
         }
         if (c.row_set) {
@@ -1797,10 +1851,15 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
             memcpy(rs, c.row_set, (size_t)B * sizeof(RowSampler));
             HIPCHK(hipMemcpyAsync(h->row_set, rs, (size_t)B * sizeof(RowSampler), hipMemcpyHostToDevice, c.st));
         }
+        if (c.guide) {
+            GuidePair* gp = reinterpret_cast<GuidePair*>(reinterpret_cast<RowSampler*>(rk + h->cfg.max_batch) + h->cfg.max_batch);
+            memcpy(gp, c.guide, (size_t)c.n_guide * sizeof(GuidePair));
+            HIPCHK(hipMemcpyAsync(h->guide, gp, (size_t)c.n_guide * sizeof(GuidePair), hipMemcpyHostToDevice, c.st));
+        }
         HIPCHK(hipEventRecord(h->rows_ev[slot], c.st));
         h->rows_busy[slot] = true;
     }
-    if (!c.row_seeds) HIPCHK(launch_set_rows(h->rows, B, c.seed, c.sample_offset, c.st));
+    if (!c.row_seeds && !c.guide) HIPCHK(launch_set_rows(h->rows, B, c.seed, c.sample_offset, c.st));
     int first = 0;
     const int64_t* const own[3] = {h->codes_top, h->codes_bot, h->codes_l2};
     if (cf.cond_type == HQT_COND_TEXT) {     // 64-token causal prefill (sampling.py:187-190, layers.py:107-111)
@@ -1854,6 +1913,8 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         // a row table: that there is one (two sampler launches per draw where the pass dispatches) and whether a row uses top-p (the LDS of the general
         // kernel) -- never its values, which the kernels read from device memory: a changed table replays the same graph
         key.push_back((uint64_t)((c.row_set ? 1 : 0) + (c.row_top_p ? 2 : 0)));
+        // a pair table: that there is one (one more launch per sub-step) and its pair count (that launch's grid), never its rows or scales
+        key.push_back((uint64_t)c.n_guide);
         if (!h->graph_exec || key != h->graph_key) {
             if (h->graph_exec) {                         // rare (options or test-only buffers changed): drain before destroying
                 HIPCHK(hipStreamSynchronize(c.st));

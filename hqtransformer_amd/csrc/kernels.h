@@ -142,6 +142,10 @@ hipError_t launch_sampler(const SamplerArgs& a, hipStream_t st);
 // b * slots + slot of a.logits (before temperature, no cut-off; IEEE expf / logf in every precision) at feed[index of that draw in `out`] -- `feed` is the forced
 // codes of the level, or a.out itself (the code just drawn).  One launch per slot, B workgroups; a row's value depends on its own bits and V only.
 hipError_t launch_code_logprob(const SamplerArgs& a, const int64_t* feed, float* logprob, int slot, hipStream_t st);
+// guide_logits_kernel, IN FRONT of launch_sampler on the same stream: for every pair of `pairs` [n_pairs] (device) and every slot < slots, the rows
+// pos_row * slots + slot and neg_row * slots + slot of logits [B * slots, V] are both overwritten with g = l_pos + (scale[level] - 1) (l_pos - l_neg), each
+// operation rounded to fp32 on its own (no FMA) in every precision.  One launch per sub-step, n_pairs x slots workgroups; rows outside every pair are not touched.
+hipError_t launch_guide_logits(float* logits, const GuidePair* pairs, int n_pairs, int V, int slots, int level, hipStream_t st);
 // depth sub-step 2 of the three-level model (hqtransformer.py:537-551): token i (raster (H1 H2 W1 W2)) =
 // tok1[codes1[b, step, parent(i)]] + pos[i] (+ tok0[codes0[b, step]]: 'add', tok0 non-NULL), 16 rows per sample; tok1_ld = 4 D:
 // the 'reduce' table, child (H2 W2) takes its D-slice of the parent's row

@@ -1744,6 +1744,47 @@ hipError_t launch_code_logprob(const SamplerArgs& a, const int64_t* feed, float*
     return hipGetLastError();
 }
 
+// Guidance: the logits rows of a pair (the same image under two conditions, two rows of one pass) become ONE row, g = l_pos + (s - 1) (l_pos - l_neg), written
+// over both, in place, between the head GEMM and the sampler.  Both rows carry the same Philox key and sampler settings (engine.hip), so both draw the same code from
+// the same bits and feed it forward: the two KV caches stay in step without any kernel knowing of pairs.  Workgroup (pair, slot) of a sub-step's logits
+// [B * slots, V]; the pair is read from the device table at a workgroup-uniform address (every lane loads the same 20 bytes: vector loads, one cache line), so a changed table replays the same graph.  256 threads per
+// row pair as in code_logprob_kernel: thread t owns the float4 groups t, t + 256, ... and skips groups past V.  V % 4 == 0 always -- hqt_create refuses any other
+// vocabulary, so rows are 16-byte aligned and there is no scalar path.  Every group is read from both rows before either is written, and no other workgroup touches
+// these two rows (a row is in at most one pair: checked on the host), so the update in place is safe.  s - 1, the difference, the product and the sum are four
+// separately rounded fp32 operations in every precision: numpy in float32 gives the same bits, and s = 1 gives m = +-0 and hence l_pos itself (finite logits; a
+// logit of -0 may come back as +0).  No LDS, no atomics, no dependence between rows of different pairs.
+// guide_mix: the product must not be contracted with the sum into a v_fma.  __fsub_rn / __fmul_rn / __fadd_rn do not see to that: in this toolchain's headers they
+// are the plain operators (no OCML_BASIC_ROUNDED_OPERATIONS) and, once inlined, contract like them.  What holds is the pragma on the operators themselves, as in
+// split_ring.h (hipcc's default, fast-honor-pragmas, honours it); the ISA of this kernel holds v_pk_add_f32 / v_pk_mul_f32 and no v_fma / v_fmac.
+__device__ __forceinline__ float guide_mix(float a, float b, float sm1) {
+#pragma clang fp contract(off)
+    const float d = a - b;
+    const float m = sm1 * d;
+    return a + m;
+}
+__global__ __launch_bounds__(256) void guide_logits_kernel(float* logits, const GuidePair* pairs, int V, int slots, int level) {
+    const GuidePair p = pairs[blockIdx.x];
+    const int slot = blockIdx.y;
+    const float sm1 = p.scale[level] - 1.0f;
+    float4* lp = reinterpret_cast<float4*>(logits + ((long long)p.pos_row * slots + slot) * V);
+    float4* ln = reinterpret_cast<float4*>(logits + ((long long)p.neg_row * slots + slot) * V);
+    for (int i4 = threadIdx.x; i4 * 4 < V; i4 += 256) {
+        const float4 a = lp[i4], b = ln[i4];
+        float4 g;
+        g.x = guide_mix(a.x, b.x, sm1);
+        g.y = guide_mix(a.y, b.y, sm1);
+        g.z = guide_mix(a.z, b.z, sm1);
+        g.w = guide_mix(a.w, b.w, sm1);
+        lp[i4] = g;
+        ln[i4] = g;
+    }
+}
+hipError_t launch_guide_logits(float* logits, const GuidePair* pairs, int n_pairs, int V, int slots, int level, hipStream_t st) {
+    if (V % 4 || V > HQT_MAX_V || n_pairs < 1 || slots < 1 || level < 0 || level > 2) return hipErrorInvalidValue;
+    guide_logits_kernel<<<dim3(n_pairs, slots), 256, 0, st>>>(logits, pairs, V, slots, level);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------
 // A9/A10/A13: codebook gather + PixelShuffle(2) + concat, NHWC output
 // (quantizer.py:179-186, generator.py:316-318,361-364; sampling_hqmodel.py:119-120)

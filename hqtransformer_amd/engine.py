@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import PRECISION_EXACT, PRECISION_FAST, hqt_config, hqt_encode_out, hqt_row_sampler, hqt_sample_opts, hqt_sample_opts_l3
+from ._lib import PRECISION_EXACT, PRECISION_FAST, hqt_config, hqt_encode_out, hqt_guide_pair, hqt_row_sampler, hqt_sample_opts, hqt_sample_opts_l3
 from .spec import DEPTH_DECODINGS, STAGE1_RESAMPLES, Stage1Spec, Stage2Spec
 
 
@@ -80,6 +80,32 @@ def row_sampler_table(levels: int, row_samplers) -> np.ndarray:
             row = done[(t, k, p)] = np.concatenate([tf.view(np.uint32), ki.view(np.uint32), pf.view(np.uint32)])
         rows[b] = row
     return rows
+
+
+def guide_pair_table(levels: int, guidance):
+    """Guidance pairs -> the ``hqt_guide_pair`` array ``hqt_set_guidance`` takes (20 bytes per pair).  Each entry is ``(pos_row, neg_row, scale)``:
+    two different rows of the pass, and one scale for every code level or one per level, coarse to fine (levels the model lacks stay at 1.0 =
+    no guidance).  Which rows exist, and that no row is named twice, is checked by the library against the call that takes the table."""
+    L = int(levels)
+    table = (hqt_guide_pair * len(guidance))()
+    for i, entry in enumerate(guidance):
+        if len(entry) != 3:
+            raise ValueError(f'guidance[{i}]: expected (pos_row, neg_row, scale)')
+        pos, neg, scale = entry
+        scale = [float(scale)] * L if isinstance(scale, (int, float)) else [float(v) for v in scale]
+        if len(scale) != L:
+            raise ValueError(f'guidance[{i}]: expected one scale or {L} (one per code level), got {len(scale)}')
+        table[i].pos_row, table[i].neg_row = int(pos), int(neg)
+        for l in range(3):
+            table[i].scale[l] = scale[l] if l < L else 1.0
+    return table
+
+
+def check_guided_rows(batch: int, n_pairs: int, max_batch: int) -> None:
+    """ValueError, naming the doubling, when the rows of a guided call do not fit the engine: every image is two rows of the pass."""
+    if int(batch) > int(max_batch):
+        raise ValueError(f'guided sampling runs every image as two rows of one pass (positive and negative condition): batch={int(batch)} rows for '
+                         f'{int(n_pairs)} pairs exceed max_batch={int(max_batch)} of this engine -- build it for twice the images')
 
 
 # what the two- and the three-level surface call their levels in messages
@@ -327,7 +353,7 @@ class Engine:
     def _sample_levels(self, levels: int, batch: int, cond, n_steps: int, *, precision, top_k, top_p, temperature, noise, seed, sample_offset,
                        force: Sequence[Optional[torch.Tensor]], out: Optional[Sequence[torch.Tensor]], return_logits, use_graph,
                        row_seeds, row_offsets, row_samplers=None, prefix=None,
-                       return_logprobs=False) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+                       return_logprobs=False, guidance=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
         """Returns (codes [B, n], [B, n, 4][, [B, n, 16]], logits [n, draws, B, V] or None, logprobs [B, n, draws] or None)."""
         dev = self.device
         B, V, L = int(batch), self.s2.vocab_top, int(levels)
@@ -348,6 +374,9 @@ class Engine:
         o.seed, o.sample_offset, o.use_graph = int(seed) & (2 ** 64 - 1), int(sample_offset), int(bool(use_graph))
         rows = self._row_keys(o, B, row_seeds, row_offsets)
         table = None if row_samplers is None else row_sampler_table(L, row_samplers)     # its length is checked against B by the library
+        pairs = guide_pair_table(L, guidance) if guidance is not None and len(guidance) else None      # its rows are checked against B by the library
+        if pairs is not None:
+            check_guided_rows(B, len(pairs), self.max_batch)
         cond = self._prep_cond(cond, B)
         noise = self._prep(noise, (n_steps, draws, B, V), torch.float32, 'noise')
         force = [self._prep(f, shp, torch.int64, what, V) for f, shp, what in zip(force, shapes, _FORCE_NAMES[L])]
@@ -377,6 +406,8 @@ class Engine:
                 _lib.check(self.lib.hqt_set_row_samplers(self.h, len(table), table.ctypes.data_as(C.POINTER(hqt_row_sampler))))
             if logprobs is not None:                # staged like the table: taken and cleared by the call below
                 _lib.check(self.lib.hqt_set_logprob_out(self.h, _ptr(logprobs)))
+            if pairs is not None:                   # ... and so is the pair table (copied by the library)
+                _lib.check(self.lib.hqt_set_guidance(self.h, len(pairs), pairs))
             _lib.check(fn(self.h, B, _ptr(cond), C.byref(o), _ptr(noise), *map(_ptr, force), _ptr(logits), *map(_ptr, outs), C.c_void_p(stream)))
             self._note_split(precision, stream, ar_rows=B)        # every head runs persistently (run_position)
         # inputs must outlive the asynchronous launches
@@ -392,7 +423,7 @@ class Engine:
                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
                row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
-               return_logprobs: bool = False):
+               return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None):
         """Two-level sampling: returns (codes_top [B, n], codes_bot [B, n, 4][, logits [n, 5, B, V]][, logprobs [B, n, 5]]).
         ``return_logprobs``: fp32 log-probability of every code the call feeds forward -- the drawn one, or the forced one where ``force_*`` is
         given -- under the raw logits of its draw (T = 1, no cut-off: ``hqt_set_logprob_out``), appended last; with a prefix the positions < P are NaN.
@@ -404,13 +435,18 @@ class Engine:
         global index ``row_offsets[b]`` of a call seeded ``row_seeds[b]`` draws (``hqt_sample_opts.row_seeds``).
         ``row_samplers`` (``batch`` entries ``(temperature per level, top_k per level, top_p per level)``, see ``row_sampler_table``): row b
         draws with its own settings in place of ``top_k`` / ``top_p`` / ``temperature`` -- bit for bit what it draws in a call that has
-        those settings for every row (``hqt_set_row_samplers``)."""
+        those settings for every row (``hqt_set_row_samplers``).
+        ``guidance`` (entries ``(pos_row, neg_row, scale)``, scale a float or one per level: ``guide_pair_table``): guided sampling
+        (``hqt_set_guidance``) -- the two rows of a pair are one image under two conditions (``cond[pos_row]`` / ``cond[neg_row]``); every code of both
+        is drawn from ``l_pos + (scale - 1) (l_pos - l_neg)`` with the positive row's Philox key, so both rows return the same codes.  ``batch``
+        counts all rows; ``noise``, ``force_*`` and ``prefix`` must agree in the two rows of a pair; returned logits hold the guided row in both,
+        returned log-probabilities score the code under it.  Rows outside every pair draw what they draw without ``guidance``."""
         if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
             raise ValueError('out: expected a pair (codes_top [B, n_steps], codes_bot [B, n_steps, 4])')
         outs, logits, logprobs = self._sample_levels(2, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(force_top, force_bot), out=out,
                                            return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
-                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs)
+                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance)
         return (outs[0], outs[1]) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
 
     def sample3(self, batch: int, cond: Optional[torch.Tensor], n_steps: int, *, precision: int = PRECISION_FAST,
@@ -419,14 +455,14 @@ class Engine:
                 sample_offset: int = 0, force: Optional[Sequence[torch.Tensor]] = None, return_logits: bool = False,
                 use_graph: bool = True, row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
                 row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
-                return_logprobs: bool = False):
-        """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]][, logprobs [B, n, 21]]); ``row_samplers``
-        and ``return_logprobs`` as in ``sample``;
+                return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None):
+        """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]][, logprobs [B, n, 21]]); ``row_samplers``,
+        ``return_logprobs`` and ``guidance`` (three scales per pair) as in ``sample``;
         ``prefix`` = [[B, P], [B, P, 4], [B, P, 16]]: completion, as in ``sample`` (``hqt_sample_prefix_l3``)."""
         outs, logits, logprobs = self._sample_levels(3, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(None,) * 3 if force is None else force,
                                            out=None, return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
-                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs)
+                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance)
         return tuple(outs) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
 
     # ------------------------------------------------------------------ stage 1, encode side

@@ -20,14 +20,16 @@ from typing import Any, Callable, List, NamedTuple, Optional, Tuple
 import torch
 
 from ._lib import POLICY_LATENCY, POLICY_THROUGHPUT
-from .sampling import _batch_and_cond, _precision, rearrange_levels, sampling_hqtransformer, sampling_ihqgpt
+from .sampling import (_batch_and_cond, _precision, guidance_scales, negative_cond, rearrange_levels, sampling_hqtransformer,
+                       sampling_ihqgpt)
 
 
 # Code levels travel as one list, coarse to fine.  These are the only places that tell two levels from three: the sampler call, and the
 # (codes_top, codes_bot) shape of a result, whose second entry is a tensor (two levels) or the list of the finer levels (three).
 def sample_codes(stage2, num_candidates: int, cond, **kw) -> list:
     """One ``sampling_ihqgpt`` / ``sampling_hqtransformer`` call (keywords of that sampler) -> its codes as a list; ``return_logprobs=True``
-    travels with the keywords, and the log-probabilities fp32 [B, n, draws] are then the list's last entry, behind the codes."""
+    travels with the keywords, and the log-probabilities fp32 [B, n, draws] are then the list's last entry, behind the codes; so do
+    ``guidance_scale`` / ``neg_cond`` (guided sampling: 2 B rows in the pass, the B positive ones returned)."""
     sampler = sampling_hqtransformer if stage2.spec.levels == 3 else sampling_ihqgpt
     return list(sampler(stage2, num_candidates=num_candidates, cond=cond, is_tqdm=False, **kw))
 
@@ -60,6 +62,40 @@ def step_row_samplers(levels: int, sizes, sample_kws) -> list:
             raise ValueError(f'sampler settings of a {L}-level step need {L} entries each, got {kw}')
         rows.extend([(temperature, top_k, top_p)] * int(n))
     return rows
+
+
+# what a step of a merged pass may set for itself besides its rows: guided steps merge with each other and with unguided ones (the pair table is per row)
+GUIDANCE_KEYS = ('guidance_scale', 'neg_cond')
+
+
+def step_guidance(levels: int, sizes, sample_kws) -> Tuple[list, list]:
+    """Steps of a merged pass -> its guidance: the pass lays the steps' own rows out first, step after step (``sizes[i]`` rows each, N in all: what an
+    unguided pass holds), then one negative row for every row of every guided step, in the same order.  Returns ``(pairs, mirrors)``: ``pairs`` is
+    ``guidance=`` of the samplers, step i's ``guidance_scale`` (``sample_kws[i]``; a float or one per level) on every pair of its rows
+    ``(lo_i + j, N + k)``; ``mirrors[k]`` is the row that negative row ``N + k`` repeats in everything but its condition (key, sampler settings,
+    prefix).  No guided step: ``([], [])``."""
+    N = sum(int(n) for n in sizes)
+    pairs, mirrors, lo = [], [], 0
+    for n, kw in zip(sizes, sample_kws):
+        scales = guidance_scales(levels, kw.get('guidance_scale'))
+        if scales is None and kw.get('neg_cond') is not None:
+            raise ValueError('neg_cond comes with guidance_scale')
+        for j in range(int(n) if scales is not None else 0):
+            pairs.append((lo + j, N + len(mirrors), scales))
+            mirrors.append(lo + j)
+        lo += int(n)
+    return pairs, mirrors
+
+
+def check_guided_step(stage2, num_candidates: int, sample_kw: dict) -> None:
+    """What ``flush`` would refuse in a guided step, raised when the step is submitted: a scale count that does not match the levels, ``neg_cond``
+    without a scale, a class model without ``neg_cond``, a ``neg_cond`` of the wrong length or outside the classes, an unconditional model."""
+    scales = guidance_scales(stage2.spec.levels, sample_kw.get('guidance_scale'))
+    if scales is None:
+        if sample_kw.get('neg_cond') is not None:
+            raise ValueError('neg_cond comes with guidance_scale')
+        return
+    negative_cond(stage2, int(num_candidates), sample_kw.get('neg_cond'))
 
 
 def decode_codes(stage1, codes: list, precision: Optional[str] = None, decode_batch: int = 0, top_resolution: int = 0) -> torch.Tensor:
@@ -124,7 +160,7 @@ def sample_best_of(stage2, cond, num_candidates: int, keep: int, **sampler) -> T
     [G, ctx_len_txt], or anything for an unconditional model (one group).  ONE sampler call over all G * num_candidates rows (group-major: row
     g * num_candidates + c), keywords of ``sampling_ihqgpt`` / ``sampling_hqtransformer`` in ``sampler``; every candidate is scored by
     ``sequence_logprob`` of its own draws (the model's log-probability at T = 1, whatever temperature and cut-offs drew it; with ``prefix_codes`` over
-    the completed positions only) and ranked within its group, descending, ties to the lower candidate index; codes and scores are gathered on the
+    the completed positions only; with ``guidance_scale`` -- ``neg_cond`` then per group, like ``cond`` -- under the guided logits) and ranked within its group, descending, ties to the lower candidate index; codes and scores are gathered on the
     device.  Returns ``(codes, scores)``: the code levels as one list, [G * keep, n], [G * keep, n, 4][, ...], group-major, best first, and fp64 [G, keep]."""
     C, K = int(num_candidates), int(keep)
     if not 1 <= K <= C:
@@ -141,6 +177,10 @@ def sample_best_of(stage2, cond, num_candidates: int, keep: int, **sampler) -> T
         rows = ids.repeat_interleave(C)
     else:
         G, rows = 1, cond
+    if sampler.get('neg_cond') is not None and not isinstance(sampler['neg_cond'], int):      # per group, like cond: one row per candidate
+        neg = torch.as_tensor(sampler['neg_cond'])
+        neg = neg.reshape(-1, int(neg.shape[-1])) if stage2.use_txt_cond else neg.reshape(-1)
+        sampler['neg_cond'] = neg.repeat_interleave(C, dim=0) if int(neg.shape[0]) == G and G > 1 else neg
     *codes, logprobs = sample_codes(stage2, G * C, rows, return_logprobs=True, **sampler)
     prefix = sampler.get('prefix_codes')
     P = 0 if prefix is None else int(torch.as_tensor(prefix[0]).shape[-1])
@@ -233,7 +273,7 @@ class _Step(NamedTuple):
     def settings(self, mixed_samplers: bool = False) -> tuple:
         """What the steps of one merged pass must share (``mixed_samplers``: all but the sampler settings, which then travel per row).
         Prefix codes belong to a step's rows like its class ids; their LENGTH is shared (a pass has one prefill)."""
-        free = ('sample_offset', 'prefix_codes', 'return_logprobs') + (SAMPLER_KEYS if mixed_samplers else ())
+        free = ('sample_offset', 'prefix_codes', 'return_logprobs') + GUIDANCE_KEYS + (SAMPLER_KEYS if mixed_samplers else ())
         return (self.max_seq_len, self.use_fp16, self.precision, self.clamp01, self.use_graph, self.prefix_len(),
                 {k: v for k, v in self.sample_kw.items() if k not in free})
 
@@ -298,13 +338,16 @@ class InflightSampler:
         events recorded on the lane's stream at AR start / AR end / decode end (lane time: phases of different lanes overlap).
         ``return_logprobs=True`` (with the sampler keywords): the step's log-probabilities fp32 [num_candidates, max_seq_len, draws] as one more element,
         behind ``done_event``.  Steps of a merged pass need not agree on it: the pass computes the buffer if any of its steps asks, and only
-        those steps get their rows."""
+        those steps get their rows.  ``guidance_scale`` / ``neg_cond`` (with the sampler keywords, as in ``sampling_ihqgpt``): a guided step; it
+        merges with guided and unguided steps alike -- the pass carries one negative row per row of a guided step behind the rows of all steps
+        (``step_guidance``), which are neither decoded nor returned."""
         if self.merge > 1:
             if decode is False or phase_events is not None or sample_kw.get('noise') is not None:
                 raise ValueError('merged steps support the plain sample + decode step only (no explicit noise, no phase events)')
             p = Pending()
             step = _Step(p, num_candidates, cond, seed, max_seq_len, use_fp16, precision, clamp01, use_graph, after, order_after_current, sample_kw)
             # checked HERE, before the step is queued: a mismatch raises without touching the queue (every Pending already handed out stays valid)
+            check_guided_step(self.model.stage2, num_candidates, sample_kw)
             if self._queue:
                 check_mergeable(step, self._queue[0], self.mixed_samplers)
             self._queue.append(step)
@@ -323,7 +366,8 @@ class InflightSampler:
         ref = q[0]
         sizes = [e.num_candidates for e in q]
         los = [sum(sizes[:i]) for i in range(len(q))]
-        kw = {k: v for k, v in ref.sample_kw.items() if k not in ('sample_offset', 'prefix_codes', 'return_logprobs')}
+        kw = {k: v for k, v in ref.sample_kw.items() if k not in ('sample_offset', 'prefix_codes', 'return_logprobs') + GUIDANCE_KEYS}
+        pairs, mirrors = step_guidance(self.model.stage2.spec.levels, sizes, [e.sample_kw for e in q])
         want_lp = any(e.wants_logprobs() for e in q)
         if want_lp:
             kw['return_logprobs'] = True
@@ -331,9 +375,12 @@ class InflightSampler:
             where = torch.as_tensor(ref.sample_kw['prefix_codes'][0]).device       # device prefixes stay there: no copy back to the host
             kw['prefix_codes'] = [torch.cat([torch.as_tensor(e.sample_kw['prefix_codes'][l]).to(where, torch.int64) for e in q])
                                   for l in range(len(ref.sample_kw['prefix_codes']))]
+            if mirrors:
+                kw['prefix_codes'] = [torch.cat([p, p[mirrors]]) for p in kw['prefix_codes']]
         if self.mixed_samplers:                      # every row keeps the sampler settings of its own step
             kw = {k: v for k, v in kw.items() if k not in SAMPLER_KEYS}
             kw['row_samplers'] = step_row_samplers(self.model.stage2.spec.levels, sizes, [e.sample_kw for e in q])
+            kw['row_samplers'] += [kw['row_samplers'][r] for r in mirrors]
         offs = [int(e.sample_kw.get('sample_offset', 0)) for e in q]
         cond = None
         if self.model.stage2.use_txt_cond:           # [n, ctx_len_txt] token ids per step
@@ -344,9 +391,16 @@ class InflightSampler:
                 c = torch.as_tensor(e.cond).reshape(-1).to('cpu', torch.int64)
                 parts.append(c.expand(e.num_candidates) if c.numel() == 1 else c)
             cond = torch.cat(parts)
+        if pairs:                                    # the negative rows, behind the rows of all steps: every guided step's negative condition for its rows
+            kw['guidance'] = pairs
+            negs = [negative_cond(self.model.stage2, n, e.sample_kw.get('neg_cond'))
+                    for e, n in zip(q, sizes) if e.sample_kw.get('guidance_scale') is not None]
+            cond = torch.cat([cond] + [n.to('cpu', torch.int64) for n in negs])
         seeds = [int(e.seed) if e.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()) for e in q]
         row_seeds = [s for s, n in zip(seeds, sizes) for _ in range(n)]
         row_offsets = [o + i for o, n in zip(offs, sizes) for i in range(n)]
+        row_seeds += [row_seeds[r] for r in mirrors]     # a negative row draws with its positive row's key
+        row_offsets += [row_offsets[r] for r in mirrors]
 
         def split_after(ct, cb, px):
             for e, lo in zip(q, los):
@@ -356,7 +410,7 @@ class InflightSampler:
         if self.record_phases:
             phases = tuple(torch.cuda.Event(enable_timing=True) for _ in range(3))
             self.phase_log.append((phases, sum(sizes)))
-        ct, cb, px, ev, *lp = self._launch(sum(sizes), cond, seed=seeds[0], max_seq_len=ref.max_seq_len, use_fp16=ref.use_fp16, decode=True,
+        ct, cb, px, ev, *lp = self._launch(sum(sizes) + len(mirrors), cond, keep_rows=sum(sizes), seed=seeds[0], max_seq_len=ref.max_seq_len, use_fp16=ref.use_fp16, decode=True,
                                       precision=ref.precision, clamp01=ref.clamp01, use_graph=ref.use_graph,
                                       after=split_after if any(e.after is not None for e in q) else None, phase_events=phases,
                                       order_after_current=any(e.order_after_current for e in q), row_seeds=row_seeds, row_offsets=row_offsets, **kw)
@@ -365,7 +419,7 @@ class InflightSampler:
 
     def _launch(self, num_candidates: int, cond, *, seed: Optional[int] = None, max_seq_len: int = 64, use_fp16: bool = True,
                 decode: bool = True, precision: Optional[str] = None, clamp01: bool = True, use_graph: bool = True,
-                after=None, phase_events=None, order_after_current: bool = True, **sample_kw):
+                after=None, phase_events=None, order_after_current: bool = True, keep_rows: Optional[int] = None, **sample_kw):
         lane = self.k % self.n
         self.k += 1
         # `ar_precision` ('exact' | 'fast' | 'split', optional, travels with the sampler settings): arithmetic of the AR loop, overriding
@@ -381,7 +435,8 @@ class InflightSampler:
         if self.n > 1:
             # several batches in flight: kernels that cost the fewest CU-microseconds (hqt_set_policy).  The policy lives on the
             # engine object, so a lane rebuilt for a larger batch (or after the model dropped its engines) gets it again.
-            eng = self.model.stage2.engine(num_candidates, max_seq_len, lane)
+            rows = num_candidates * (2 if sample_kw.get('guidance_scale') is not None else 1)      # a guided call doubles its rows itself
+            eng = self.model.stage2.engine(rows, max_seq_len, lane)
             if eng.policy != POLICY_THROUGHPUT:
                 eng.set_policy(POLICY_THROUGHPUT)
         ast = self.ar_streams[lane] if self.ar_streams else st
@@ -392,6 +447,8 @@ class InflightSampler:
                 phase_events[0].record(ast)
             codes = sample_codes(self.model.stage2, num_candidates, cond, seed=seed, max_seq_len=max_seq_len, use_fp16=use_fp16,
                                  use_graph=use_graph, lane=lane, precision=ar_precision, return_logprobs=want_lp, **sample_kw)
+            if keep_rows is not None and keep_rows < num_candidates:      # a merged pass's negative rows end here: not decoded, not returned
+                codes = [c[:keep_rows] for c in codes]
             logprobs = codes.pop() if want_lp else None
             if phase_events is not None:
                 phase_events[1].record(ast)

@@ -11,6 +11,7 @@ import torch
 
 from ._lib import PRECISION_EXACT, PRECISION_FAST, PRECISIONS
 from .engine import check_prefix
+from .text import pad_caption
 
 
 def _seed_from_torch() -> int:
@@ -51,6 +52,80 @@ def _batch_and_cond(model, num_candidates: int, cond):
     return B, cond
 
 
+# ---------------------------------------------------------------------------------------------- guided sampling
+# Every image runs as TWO rows of one pass, the same image under a positive and a negative condition; every code of both rows is drawn from
+# l_pos + (scale - 1) (l_pos - l_neg) with one Philox key (hqt_set_guidance), so both rows return the same codes.  The reference trains without
+# condition dropout and its class models have no "null" class: this is the mechanism and its arithmetic, not a claim about image quality.
+def guidance_scales(levels: int, guidance_scale) -> Optional[tuple]:
+    """``guidance_scale`` of the samplers -> one float per code level, coarse to fine (None stays None: no guidance): a float holds for every
+    level, a list gives one per level."""
+    if guidance_scale is None:
+        return None
+    L = int(levels)
+    scales = (float(guidance_scale),) * L if isinstance(guidance_scale, (int, float)) else tuple(float(v) for v in guidance_scale)
+    if len(scales) != L:
+        raise ValueError(f'guidance_scale: expected a float or {L} floats (one per code level), got {len(scales)}')
+    return scales
+
+
+def guided_pairs(n: int, scales, lo: int = 0) -> list:
+    """The pair table of ``n`` guided images whose 2 n rows start at row ``lo`` of a pass, positives first, then negatives: row ``lo + i`` is paired
+    with row ``lo + n + i`` (entries ``(pos_row, neg_row, scales)``: ``guidance=`` of ``Engine.sample``)."""
+    return [(int(lo) + i, int(lo) + int(n) + i, tuple(scales)) for i in range(int(n))]
+
+
+def _twice(t, dim: int = 0):
+    """A per-row input of n rows -> the 2 n rows of a guided call (the negative half repeats the positive one); None stays None."""
+    return None if t is None else torch.cat([torch.as_tensor(t)] * 2, dim=dim)
+
+
+def _twice_rows(rows):
+    """``row_seeds`` / ``row_offsets`` / ``row_samplers`` of n rows -> 2 n rows; None stays None."""
+    return None if rows is None else list(rows) * 2
+
+
+def negative_cond(model, B: int, neg_cond) -> torch.Tensor:
+    """The conditions of the B negative rows of a guided call -- text models: prompts [B, ctx_len_txt] or one prompt for all, default the
+    all-``[PAD]`` caption (``text.pad_caption``); class models: one class id or B of them, required (the released class models have no "null" class
+    to default to).  ValueError for an unconditional model."""
+    if model.use_txt_cond:
+        T = int(model.spec.ctx_len_txt)
+        neg = pad_caption(B, T) if neg_cond is None else torch.as_tensor(neg_cond).reshape(-1, T).to(torch.int64)
+    elif model.use_cls_cond:
+        if neg_cond is None:
+            raise ValueError('guidance_scale on a class-conditional model needs neg_cond: the class to push away from (there is no "null" class)')
+        neg = torch.as_tensor(neg_cond).reshape(-1).to(torch.int64)
+        if int(neg.min()) < 0 or int(neg.max()) >= model.spec.n_classes:
+            raise IndexError('index out of range in self')
+    else:
+        raise ValueError('guidance_scale needs a conditional model: an unconditional model has no second condition to run its rows under')
+    if int(neg.shape[0]) == 1:
+        neg = neg.expand(B, *neg.shape[1:])
+    if int(neg.shape[0]) != B:
+        raise ValueError(f'neg_cond: expected one condition or {B} (one per image), got {int(neg.shape[0])}')
+    return neg
+
+
+def guided_cond(model, B: int, cond, neg_cond) -> torch.Tensor:
+    """The conditions of a guided call's 2 B rows: ``cond`` (as ``_batch_and_cond`` returns it) for the positives, then ``negative_cond``."""
+    neg = negative_cond(model, B, neg_cond)
+    pos = torch.as_tensor(cond)
+    return torch.cat([pos.to(torch.int64), neg.to(pos.device)])
+
+
+def _guided(model, B: int, cond, guidance_scale, neg_cond, guidance):
+    """What ``guidance_scale`` makes of a call: (rows of the pass, cond, pair table, rows to return).  Without a scale the call is what it was
+    (``guidance``: a ready pair table over the rows as given, for callers that lay the rows out themselves)."""
+    scales = guidance_scales(model.spec.levels, guidance_scale)
+    if scales is None:
+        if neg_cond is not None:
+            raise ValueError('neg_cond comes with guidance_scale')
+        return B, cond, guidance, B
+    if guidance is not None:
+        raise ValueError('guidance_scale builds the pair table itself: pass either guidance_scale (+ neg_cond) or guidance, not both')
+    return 2 * B, guided_cond(model, B, cond, neg_cond), guided_pairs(B, scales), B
+
+
 @torch.no_grad()
 def sampling_ihqgpt(model,
                     num_candidates: int,
@@ -77,7 +152,10 @@ def sampling_ihqgpt(model,
                     prefix_codes=None,
                     text_prefix: bool = False,
                     *,
-                    return_logprobs: bool = False):
+                    return_logprobs: bool = False,
+                    guidance_scale=None,
+                    neg_cond=None,
+                    guidance=None):
     """Returns ``(codes_top int64 [B, max_seq_len], codes_bot int64 [B, max_seq_len, 4])`` on the model's GPU; ``return_logprobs=True`` appends
     ``logprobs`` fp32 [B, max_seq_len, 5]: the log-probability of every code the call feeds forward (the drawn one; the given one where
     ``given_top_code`` forces the top level) under the raw logits of its draw -- temperature 1, no cut-off, so always finite; draw order top,
@@ -104,6 +182,14 @@ def sampling_ihqgpt(model,
     With text conditioning only on request, ``text_prefix=True``: the prompt and the prefix then share ONE prefill of ctx_len_txt + P rows per
     sample, and the engine's row workspace is sized for it (about twice the row buffers at the CC-15M shape: DESIGN §5.4); without the flag a
     text model refuses ``prefix_codes`` with ValueError before any engine is built.
+    ``guidance_scale`` (a float, or one per code level) with ``neg_cond``: guided sampling -- every image runs as two rows of one pass, under ``cond``
+    and under ``neg_cond`` (text: negative prompts [B, ctx_len_txt] or one for all, default the all-``[PAD]`` caption; class: the class id(s) to push
+    away from, required), and every code is drawn from ``l_pos + (s - 1) (l_pos - l_neg)`` (``hqt_set_guidance``); s = 1 draws what the unguided
+    call draws.  The pass has 2 B rows, positives first (the engine grows to that batch); ``noise``, ``given_top_code``, ``prefix_codes``,
+    ``row_samplers`` and ``row_seeds`` / ``row_offsets`` are given for B rows and repeated for the negative half; the B positive rows are
+    returned, so every result keeps its documented shape.  ValueError for an unconditional model.  The reference trains without condition dropout:
+    what is claimed is the arithmetic, not an effect on image quality.  ``guidance`` instead of the two: a ready pair table
+    ``[(pos_row, neg_row, scales), ...]`` over the B rows as given (``Engine.sample``; ``InflightSampler`` lays merged steps out this way).
 
     The call is asynchronous and does not read the device's flags: 'split' passes above 256 rows SATURATE activations outside the fp16 range and
     only flag them, and a persistent FAST launch (up to 64 samples) that could not finish on a shared GPU only marks the handle -- call
@@ -111,6 +197,14 @@ def sampling_ihqgpt(model,
     """
     spec = model.spec
     B, cond = _batch_and_cond(model, num_candidates, cond)
+    rows, cond, guidance, keep = _guided(model, B, cond, guidance_scale, neg_cond, guidance)
+    if rows != B:                                    # the negative half repeats every per-row input of the positive one
+        noise, prefix_codes = _twice(noise, 2), None if prefix_codes is None else [_twice(p) for p in prefix_codes]
+        row_seeds, row_offsets, row_samplers = _twice_rows(row_seeds), _twice_rows(row_offsets), _twice_rows(row_samplers)
+        if given_top_code is not None:
+            g = torch.as_tensor(given_top_code)
+            given_top_code = g if g.dim() == 1 or g.shape[0] == 1 else _twice(g)
+        B = rows
     prefix = check_prefix(spec, B, max_seq_len, prefix_codes, text_prefix=text_prefix)       # refused here, before an engine is built
     force_top = None
     if given_top_code is not None and spec.depth_decoding == 'bidirectional':
@@ -126,10 +220,12 @@ def sampling_ihqgpt(model,
     eng = model.engine(B, max_seq_len, lane, max_prefix=_prefix_room(spec, prefix))
     if seed is None and noise is None:
         seed = _seed_from_torch()
-    return eng.sample(B, cond, max_seq_len, precision=_precision(precision, use_fp16),
-                      top_k=(top_k_top, top_k_bot), top_p=(top_p_top, top_p_bot), temperature=softmax_temperature,
-                      noise=noise, seed=seed or 0, sample_offset=sample_offset, force_top=force_top, use_graph=use_graph,
-                      row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs)
+    out = eng.sample(B, cond, max_seq_len, precision=_precision(precision, use_fp16),
+                     top_k=(top_k_top, top_k_bot), top_p=(top_p_top, top_p_bot), temperature=softmax_temperature,
+                     noise=noise, seed=seed or 0, sample_offset=sample_offset, force_top=force_top, use_graph=use_graph,
+                     row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs,
+                     guidance=guidance)
+    return out if keep == B else tuple(t[:keep] for t in out)          # (codes and log-probabilities are [B, ...]: the positive half)
 
 
 def _prefix_room(spec, prefix) -> int:
@@ -162,26 +258,37 @@ def sampling_hqtransformer(model,
                            row_samplers=None,
                            prefix_codes=None,
                            *,
-                           return_logprobs: bool = False):
+                           return_logprobs: bool = False,
+                           guidance_scale=None,
+                           neg_cond=None,
+                           guidance=None):
     """Counterpart of ``hqvae.utils.sampling.sampling_hqtransformer`` (sampling.py:240-307) for the three-level
     HQTransformer: returns ``[codes0 int64 [B, L], codes1 [B, L, 4], codes2 [B, L, 16]]`` on the model's GPU.
     ``top_k`` / ``top_p`` / ``softmax_temperature`` are per-level lists (None = no cut-off); ``cond`` as in
     ``sampling_ihqgpt``.  Extensions: ``noise`` fp32 [L, 21, B, V], ``seed`` / ``sample_offset``, ``lane``,
     ``row_samplers`` (per-row settings, as in ``sampling_ihqgpt``), ``prefix_codes`` = ``[t [B, P], m [B, P, 4], b [B, P, 16]]`` (completion,
-    as in ``sampling_ihqgpt``), ``return_logprobs`` (appends fp32 [B, L, 21] to the list, as in ``sampling_ihqgpt``)."""
+    as in ``sampling_ihqgpt``), ``return_logprobs`` (appends fp32 [B, L, 21] to the list, as in ``sampling_ihqgpt``), ``guidance_scale`` (a float or
+    three, one per level) / ``neg_cond`` / ``guidance`` (guided sampling over 2 B rows, the B positive ones returned, as in ``sampling_ihqgpt``)."""
     spec = model.spec
     if spec.levels != 3:
         raise ValueError('sampling_hqtransformer needs the three-level HQTransformer (stage2.type multilevel-hq)')
     B, cond = _batch_and_cond(model, num_candidates, cond)
+    rows, cond, guidance, keep = _guided(model, B, cond, guidance_scale, neg_cond, guidance)
+    if rows != B:
+        noise, prefix_codes = _twice(noise, 2), None if prefix_codes is None else [_twice(p) for p in prefix_codes]
+        row_seeds, row_offsets, row_samplers = _twice_rows(row_seeds), _twice_rows(row_offsets), _twice_rows(row_samplers)
+        B = rows
     prefix = check_prefix(spec, B, max_seq_len, prefix_codes)
     top_k = list(top_k) if top_k is not None else [None, None, None]
     top_p = list(top_p) if top_p is not None else [None, None, None]
     eng = model.engine(B, max_seq_len, lane, max_prefix=_prefix_room(spec, prefix))
     if seed is None and noise is None:
         seed = _seed_from_torch()
-    return list(eng.sample3(B, cond, max_seq_len, precision=_precision(precision, use_fp16), top_k=top_k, top_p=top_p,
-                            temperature=softmax_temperature, noise=noise, seed=seed or 0, sample_offset=sample_offset, use_graph=use_graph,
-                            row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs))
+    out = eng.sample3(B, cond, max_seq_len, precision=_precision(precision, use_fp16), top_k=top_k, top_p=top_p,
+                      temperature=softmax_temperature, noise=noise, seed=seed or 0, sample_offset=sample_offset, use_graph=use_graph,
+                      row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs,
+                      guidance=guidance)
+    return list(out if keep == B else (t[:keep] for t in out))
 
 
 def rearrange_levels(codes: List[torch.Tensor], top_resolution: int) -> tuple:

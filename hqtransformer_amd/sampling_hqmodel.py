@@ -41,6 +41,9 @@ def common_arguments(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument('--complete-from', type=str, default=None, metavar='FILE.npy',
                    help='complete images instead of sampling from scratch: float32 [N, 3, H, W] in [0, 1] (the layout of the samples this driver writes); '
                         'row i of a batch completes image (batch index * batch size + i) mod N.  Needs --keep-rows')
+    p.add_argument('--guidance-scale', type=float, default=None, metavar='S',
+                   help='guided sampling: every image runs under its condition and a negative one, codes are drawn from l_pos + (S - 1) (l_pos - l_neg); '
+                        '1 draws what the unguided run draws (the reference trains without condition dropout: no effect on quality is claimed)')
     p.add_argument('--keep-rows', type=int, default=None, help='with --complete-from: rows of the top code grid kept from the image (1 .. top_resolution - 1)')
     return p
 
@@ -50,6 +53,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--batch-size', type=int, default=50)
     p.add_argument('--num-classes', type=int, default=1000)
     p.add_argument('--samples-per-class', type=int, default=None, help='default 50000 // num_classes')
+    p.add_argument('--negative-class', type=int, default=None, metavar='C', help='with --guidance-scale: the class id to push away from (required: there is no "null" class)')
     return p
 
 
@@ -106,6 +110,9 @@ def sample_pixels(model: ImageGPT2, args, num_candidates: int, cond) -> np.ndarr
     """One batch of either driver (sampling_hqmodel.py:101-153,201-214): ``top_k`` / ``top_p`` shared by the levels, temperatures
     ``T * decay^level``, decode + ``clamp(0.5 x + 0.5, 0, 1)``; float32 [B, 3, H, W] in [0, 1] on the host."""
     temps = [args.temperature * (args.temperature_decay ** i) for i in range(args.code_level)]
+    guided = {}
+    if getattr(args, 'guidance_scale', None) is not None:      # --guidance-scale: twice the rows per pass, the negative condition from the driver
+        guided = dict(guidance_scale=args.guidance_scale, neg_cond=getattr(args, 'neg_cond', None))
     images = getattr(args, 'complete_images', None)
     if images is not None:               # --complete-from: the same sampler settings, the first rows of every image kept
         first = getattr(args, 'complete_next', 0)
@@ -113,12 +120,12 @@ def sample_pixels(model: ImageGPT2, args, num_candidates: int, cond) -> np.ndarr
         args.complete_next = first + count
         rows = torch.from_numpy(images[np.arange(first, first + count) % len(images)])
         pixels, _ = complete_images(model, 2.0 * rows - 1.0, args.keep_rows, cond=cond, decode_precision=args.decode_precision, softmax_temperature=temps,
-                                    use_fp16=True, **sampler_cutoffs(args.code_level, args.top_k, args.top_p))
+                                    use_fp16=True, **guided, **sampler_cutoffs(args.code_level, args.top_k, args.top_p))
         model.stage1.range_check()
         model.stage2.range_check()
         return pixels.cpu().numpy()
     sampler = dict(softmax_temperature=temps, use_fp16=True, max_seq_len=args.top_resolution * args.top_resolution, model_stage1=model.stage1,
-                   **sampler_cutoffs(args.code_level, args.top_k, args.top_p))
+                   **guided, **sampler_cutoffs(args.code_level, args.top_k, args.top_p))
     best_of = getattr(args, 'best_of', 1)
     if best_of > 1:                      # --best-of N: N x num_candidates per condition in one pass, the num_candidates most likely kept
         codes, _ = sample_best_of(model.stage2, cond, best_of * num_candidates, num_candidates, **sampler)
@@ -147,6 +154,9 @@ def main(argv=None):
     if args.code_level not in (2, 3):
         raise NotImplementedError('--code-level must be 2 or 3')
     load_completion(args)
+    if (args.guidance_scale is None) != (args.negative_class is None):
+        raise SystemExit('--guidance-scale and --negative-class come together')
+    args.neg_cond = args.negative_class
     set_seed(args.seed)
     os.makedirs(args.result_path, exist_ok=True)
     model = load_model(args.model_path).eval()

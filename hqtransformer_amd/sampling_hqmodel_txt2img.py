@@ -47,6 +47,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--synthetic-prompts', type=int, default=0, help='N random-id prompts instead of captions (smoke runs)')
     p.add_argument('--best-of', type=_at_least_one, default=1, metavar='N',
                    help='sample N x num_candidates images per caption and keep the num_candidates the stage-2 model finds most likely (1: keep all)')
+    p.add_argument('--negative-prompt', type=str, default=None, metavar='TEXT',
+                   help='with --guidance-scale: the caption to push away from (needs the tokenizer; default: the empty, all-[PAD] caption)')
     return p
 
 
@@ -56,15 +58,31 @@ def prompt_ids(args, ctx_len: int, vocab_txt: int) -> torch.Tensor:
         return torch.randint(0, vocab_txt, (args.synthetic_prompts, ctx_len), generator=g, dtype=torch.int64)
     if not args.captions:
         raise SystemExit('give --captions FILE (with a tokenizer) or --synthetic-prompts N')
+    return encode_checked(tokenizer(args, ctx_len), T.read_captions(args.captions), vocab_txt)
+
+
+def tokenizer(args, ctx_len: int):
     pair = (args.tokenizer_vocab, args.tokenizer_merges) if args.tokenizer_vocab and args.tokenizer_merges else \
         T.find_reference_vocab(args.reference_root)
     if pair is None:
         raise SystemExit('no tokenizer: pass --tokenizer-vocab/--tokenizer-merges or --reference-root')
-    tok = T.build_tokenizer(pair[0], pair[1], context_length=ctx_len)
-    ids = T.encode(tok, T.read_captions(args.captions))
+    return T.build_tokenizer(pair[0], pair[1], context_length=ctx_len)
+
+
+def encode_checked(tok, texts, vocab_txt: int) -> torch.Tensor:
+    ids = T.encode(tok, texts)
     if int(ids.max()) >= vocab_txt:
         raise SystemExit(f'token id {int(ids.max())} outside the model vocabulary ({vocab_txt})')
     return ids
+
+
+def negative_ids(args, ctx_len: int, vocab_txt: int):
+    """``neg_cond`` of the samplers for --guidance-scale: the tokenized --negative-prompt [1, ctx_len], or None (the samplers' all-[PAD] caption)."""
+    if args.negative_prompt is None:
+        return None
+    if args.guidance_scale is None:
+        raise SystemExit('--negative-prompt comes with --guidance-scale')
+    return encode_checked(tokenizer(args, ctx_len), [args.negative_prompt], vocab_txt)
 
 
 def main(argv=None):
@@ -81,6 +99,7 @@ def main(argv=None):
         raise SystemExit('the model is not text-conditional (stage2.use_txt_cond)')
     spec = model.stage2.spec
     ids = prompt_ids(args, spec.ctx_len_txt, spec.vocab_txt)
+    args.neg_cond = negative_ids(args, spec.ctx_len_txt, spec.vocab_txt)
     n = args.batch_size
     for batch_idx, txts in enumerate(ids.split(n)):     # one image per prompt (num_candidates=1: B = number of prompts, sampling.py:187-190)
         save_pickle(os.path.join(args.result_path, f'samples_({batch_idx + 1}_{n}).pkl'), sample_pixels(model, args, 1, txts.cuda()))

@@ -17,6 +17,16 @@ import torch
 REFERENCE_BPE16K = ('hqvae/tokenizers/pretrained/bpe-16k-vocab.json', 'hqvae/tokenizers/pretrained/bpe-16k-merges.txt')
 
 
+# the reference's bpe-16k vocabulary lists '[PAD]' first (``add_special_tokens`` then finds it and adds nothing); a tokenizer built from another
+# vocabulary says its own: ``tok.token_to_id('[PAD]')``
+PAD_ID = 0
+
+
+def pad_caption(n: int, context_length: int, pad_id: int = PAD_ID) -> torch.Tensor:
+    """int64 [n, context_length] of ``[PAD]`` ids: what ``encode`` returns for the empty caption -- the default negative prompt of guided sampling."""
+    return torch.full((int(n), int(context_length)), int(pad_id), dtype=torch.int64)
+
+
 def build_tokenizer(vocab: str, merges: str, context_length: int = 64):
     """``create_tokenizer('bpe16k_huggingface', lowercase=True, dropout=None)`` + the dataset's padding / truncation setup."""
     from tokenizers import CharBPETokenizer

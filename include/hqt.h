@@ -226,6 +226,27 @@ int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler* rows);
  * "code_logprob").  Forcing every level to given codes makes the call a scorer of those codes, at the cost of its n_steps decode steps. */
 int hqt_set_logprob_out(hqt_handle* h, float* logprobs);
 
+/* hqt_set_guidance -- no reference counterpart: the reference trains without condition dropout and draws every image under one condition.  Guided sampling
+ * runs an image under TWO conditions, as two rows of one pass (both count against max_batch), and draws every code of both rows from
+ *   g = l_pos + (scale - 1) * (l_pos - l_neg)
+ * -- scale 1: the positive row's own logits; scale > 1: away from the negative condition (for text models typically the all-[PAD] caption, for class models a
+ * class the caller names).  `pairs` is a HOST array of n_pairs entries, copied; 0 / NULL clears; a NULL handle or n_pairs outside [0, max_batch / 2] is
+ * HQT_ERR_INVALID.  The table is STAGED on the handle (a lane from hqt_clone has its own): the next hqt_sample / hqt_sample_l3 / hqt_sample_prefix /
+ * hqt_sample_prefix_l3 on that handle takes it and clears it, whether that call succeeds or not.  That call, between the head GEMM and the sampler of every
+ * sub-step, overwrites the logits rows of pos_row AND neg_row with g, scale[level] being the scale of the code level drawn (one kernel per sub-step, timing
+ * slot "guide_logits"): three fp32 operations, each rounded on its own in every precision -- d = l_pos - l_neg, m = (scale - 1) * d, g = l_pos + m (scale - 1
+ * itself rounded to fp32) --, so fp32 arithmetic on the host reproduces the row bit for bit.  The negative row's Philox key is made the positive row's
+ * (whether keys come from seed / sample_offset or from row_seeds / row_offsets), so both rows draw the same code and feed the same code forward; rows outside
+ * every pair are untouched and draw what they draw without a table.  What the order implies: `logits_out` holds the GUIDED row, in both rows of a pair; a staged
+ * hqt_set_logprob_out buffer scores the fed-forward code under the guided row, equally in both rows.  Per-row inputs that the engine cannot compare -- `noise`,
+ * `force_*`, prefix codes: device pointers -- must hold the same values for both rows of a pair; the caller sees to that.  Only that a table is staged and its pair
+ * count enter the graph key: a changed table of the same size replays the same graph.  The taking call fails with HQT_ERR_INVALID (and a message naming the
+ * pair) when a row is outside [0, B), pos_row == neg_row, a row appears in more than one pair, a scale of a level the model has is not finite, the handle's
+ * cond_type is HQT_COND_NONE, a staged hqt_set_row_samplers table gives the two rows different settings, or row_seeds / row_offsets give them different keys
+ * (implicit keys are overridden; explicit ones are never silently changed).  Without a staged table a call launches exactly what it launched before. */
+typedef struct { int32_t pos_row, neg_row; float scale[3]; } hqt_guide_pair;   /* 20 bytes */
+int hqt_set_guidance(hqt_handle* h, int n_pairs, const hqt_guide_pair* pairs);
+
 /* hqt_sample -- replaces sampling_ihqgpt + iHQGPT.sampling_step (hqvae/utils/sampling.py:164-237,
  * hierarchical_ar.py:428-480, 482-563, 667-789) for a batch of B independent images.
  *   cond        int64 [B] class ids (HQT_COND_CLASS), int64 [B, ctx_len_txt] token ids
