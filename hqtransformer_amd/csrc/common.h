@@ -11,6 +11,12 @@ __device__ __host__ inline float bf16_to_f32(bf16_t v) {
     c.u = ((uint32_t)v) << 16;
     return c.f;
 }
+// the eight bf16 of one 16-byte vector, in memory order
+__device__ __forceinline__ void bf16x8_to_f32(const uint4& raw, float (&f)[8]) {
+    const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { f[2 * i] = bf16_to_f32((bf16_t)(w[i] & 0xffffu)); f[2 * i + 1] = bf16_to_f32((bf16_t)(w[i] >> 16)); }
+}
 // round-to-nearest-even; NaN stays NaN.  On the device this is gfx950's v_cvt_pk_bf16_f32 (same rounding; the
 // branchy software form cost more than the LDS traffic in the conv epilogues).
 __device__ __host__ inline bf16_t f32_to_bf16(float f) {

@@ -1,7 +1,7 @@
 // Micro-benchmark: the decode-step attention kernel at merged-pass batch sizes, cold K/V (12 layers' caches in rotation, as the body
 // runs them), by number of cached keys -- achieved bytes/s against the K/V bytes the launch must read.  Also a head-major cache layout
 // ([b][head][t][hs]: one (sample, head)'s keys contiguous) through the same arithmetic, to price the layout.
-#include "../../hqtransformer_amd/csrc/kernels.hip"
+#include "../../hqtransformer_amd/csrc/attention.hip"
 #include <cstdio>
 #include <vector>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void attn_strided_kernel(AttnArgs a, long long
     const bf16_t* kc = reinterpret_cast<const bf16_t*>(a.kcache) + b * sb + h * sh + c * 8;
     const bf16_t* vc = reinterpret_cast<const bf16_t*>(a.vcache) + b * sb + h * sh + c * 8;
     float qv[8];
-    ld8<bf16_t>(q, qv);
+    unpack_row<bf16_t>(reinterpret_cast<const uint4*>(q), qv);
     const int nkeys = a.t_base + 1;
     const float scale = 1.0f / sqrtf((float)hs);
     float run_max = -INFINITY, run_sum = 0.0f, acc[8];
