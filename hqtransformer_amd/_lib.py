@@ -111,6 +111,8 @@ SYMBOLS = {
     'hqt_sample': (C.c_int, [_VP, C.c_int, _I64P, C.POINTER(hqt_sample_opts), _F32P, _I64P, _I64P, _F32P, _I64P, _I64P, _VP]),
     'hqt_set_max_prefix': (C.c_int, [_VP, C.c_int]),
     'hqt_sample_prefix': (C.c_int, [_VP, C.c_int, _I64P, C.POINTER(hqt_sample_opts), _F32P, C.c_int, _I64P, _I64P, _I64P, _I64P, _F32P, _I64P, _I64P, _VP]),
+    'hqt_set_score_chunk': (C.c_int, [_VP, C.c_int]),
+    'hqt_score': (C.c_int, [_VP, C.c_int, _I64P, C.POINTER(C.c_void_p), C.c_int, C.c_int, _F32P, C.POINTER(C.c_void_p), _VP]),
     'hqt_decode': (C.c_int, [_VP, C.c_int, _I64P, _I64P, _F32P, C.c_int, C.c_int, _VP]),
     'hqt_decode_seq': (C.c_int, [_VP, C.c_int, _I64P, _I64P, _F32P, C.c_int, C.c_int, _VP]),
     'hqt_sample_l3': (C.c_int, [_VP, C.c_int, _I64P, C.POINTER(hqt_sample_opts_l3), _F32P, _I64P, _I64P, _I64P, _F32P, _I64P, _I64P, _I64P, _VP]),

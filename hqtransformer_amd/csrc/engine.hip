@@ -125,6 +125,10 @@ struct hqt_handle {
     static constexpr int BODY_BUFS = 10;
     size_t body_bytes[BODY_BUFS] = {};        // what alloc_body_rows allocated, in its order
     int depth_rows = 0;                       // keys of the depth cache: 5 (two code levels) or 21 (three)
+    int score_chunk = 0;                      // hqt_set_score_chunk: (sample, position) pairs per depth chunk of hqt_score (0: max_batch); lanes inherit it
+    int depth_cap() const { return std::max(cfg.max_batch, score_chunk); }      // "samples" the depth workspace (xd, logits, dk, dv) holds
+    static constexpr int DEPTH_BUFS = 4;
+    size_t depth_bytes[DEPTH_BUFS] = {};      // what alloc_depth_ws allocated, in its order
     float *x = nullptr, *xd = nullptr, *logits = nullptr;
     void *hbuf = nullptr, *qbuf = nullptr, *abuf = nullptr, *mbuf = nullptr;    // fp32-sized, reused as bf16 in FAST
     void *kcache = nullptr, *vcache = nullptr, *dk = nullptr, *dv = nullptr;
@@ -440,7 +444,8 @@ static int alloc_body_rows(hqt_handle* h, bool release_old) {
     const size_t B = (size_t)c.max_batch, D = c.embed_dim;
     const int Tp = c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt + h->max_prefix : (h->max_prefix > 0 ? h->max_prefix + 1 : 1);    // rows per sample of the widest body pass
     const int Tdepth = c.code_levels == 3 ? 16 : (c.depth_decoding == HQT_DEPTH_BIDIRECTIONAL ? 5 : 4);
-    const size_t rows = (B * (size_t)std::max(Tp, Tdepth) + 31) / 32 * 32;
+    // (hqt_set_score_chunk: a depth chunk of hqt_score runs depth_cap() pairs x Tdepth rows through the same buffers; never called, depth_cap() is B)
+    const size_t rows = (std::max(B * (size_t)std::max(Tp, Tdepth), (size_t)h->depth_cap() * Tdepth) + 31) / 32 * 32;
     // packed_off() buffers are addressed with a row stride of 32 * packed_mb(M) (32 / 64 / ... / 4096 rows), which can
     // exceed round32(M): size them for the widest padded block any M <= PACKED_MAX_ROWS pass can use
     size_t rows_pk = 256;
@@ -462,6 +467,45 @@ static int alloc_body_rows(hqt_handle* h, bool release_old) {
         h->body_bytes[i] = bytes[i];
     }
     return HQT_OK;
+}
+
+// The depth workspace: input rows, logits and the depth K/V cache of depth_cap() "samples" (max_batch; hqt_set_score_chunk: the pairs of a chunk)
+static int alloc_depth_ws(hqt_handle* h, bool release_old) {
+    const hqt_config& c = h->cfg;
+    const size_t cap = (size_t)h->depth_cap(), D = c.embed_dim;
+    const int Tdepth = c.code_levels == 3 ? 16 : (c.depth_decoding == HQT_DEPTH_BIDIRECTIONAL ? 5 : 4);      // rows per sample of the widest depth sub-step
+    const size_t dkv = (size_t)c.n_layers_depth * cap * h->depth_rows * D * 4;
+    void** const bufs[hqt_handle::DEPTH_BUFS] = {(void**)&h->xd, (void**)&h->logits, &h->dk, &h->dv};
+    const size_t bytes[hqt_handle::DEPTH_BUFS] = {cap * Tdepth * D * 4, cap * Tdepth * (size_t)c.vocab_top * 4, dkv, dkv};
+    for (int i = 0; i < hqt_handle::DEPTH_BUFS; ++i) {
+        if (release_old && *bufs[i]) {
+            HIPCHK(hipFree(*bufs[i]));
+            h->owned.erase(std::remove(h->owned.begin(), h->owned.end(), *bufs[i]), h->owned.end());
+            h->workspace_bytes -= h->depth_bytes[i];
+            *bufs[i] = nullptr;
+        }
+        CHK(dev_alloc(h, bufs[i], bytes[i], true));
+        h->depth_bytes[i] = bytes[i];
+    }
+    return HQT_OK;
+}
+
+extern "C" int hqt_set_score_chunk(hqt_handle* h, int pairs) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    const hqt_config& c = h->cfg;
+    if (!c.has_stage2) return fail(HQT_ERR_INVALID, "hqt_set_score_chunk: the handle was created without stage 2");
+    if (h->finalized || h->parent) return fail(HQT_ERR_STATE, "hqt_set_score_chunk comes between hqt_create and hqt_finalize_weights (lanes inherit the value)");
+    const int Tdepth = c.code_levels == 3 ? 16 : (c.depth_decoding == HQT_DEPTH_BIDIRECTIONAL ? 5 : 4);
+    if (pairs < 0) return fail(HQT_ERR_INVALID, "hqt_set_score_chunk: pairs=%d is negative (0 restores the default, max_batch pairs)", pairs);
+    if ((long long)pairs * Tdepth > PACKED_MAX_ROWS)
+        return fail(HQT_ERR_INVALID, "hqt_set_score_chunk: pairs * Tdepth = %d * %d exceeds the %d rows of one pass (at most %d pairs for this depth head)", pairs, Tdepth, PACKED_MAX_ROWS, PACKED_MAX_ROWS / Tdepth);
+    if (pairs == h->score_chunk) return HQT_OK;
+    ON_DEVICE(h);
+    const int cap_before = h->depth_cap();
+    h->score_chunk = pairs;
+    if (h->depth_cap() == cap_before) return HQT_OK;         // a chunk of at most max_batch pairs fits what hqt_create allocated
+    CHK(alloc_depth_ws(h, true));
+    return alloc_body_rows(h, true);
 }
 
 extern "C" int hqt_set_max_prefix(hqt_handle* h, int max_prefix) {
@@ -495,17 +539,13 @@ static int alloc_workspace(hqt_handle* hp) {
     if (c.has_stage2) {
         const size_t D = c.embed_dim;
         h->Tmax = (c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : 0) + c.max_steps;
-        const int Tdepth = c.code_levels == 3 ? 16 : (c.depth_decoding == HQT_DEPTH_BIDIRECTIONAL ? 5 : 4);      // rows per sample of the widest depth sub-step
         h->depth_rows = c.code_levels == 3 ? 21 : 5;
         CHK(alloc_body_rows(h.get(), false));
-        CHK(dev_alloc(h.get(), (void**)&h->xd, B * Tdepth * D * 4, true));
-        CHK(dev_alloc(h.get(), (void**)&h->logits, B * Tdepth * (size_t)c.vocab_top * 4, true));
+        h->xd = h->logits = nullptr; h->dk = h->dv = nullptr;     // (a clone starts from its root's pointers)
+        CHK(alloc_depth_ws(h.get(), false));
         const size_t kv = (size_t)c.n_layers * B * h->Tmax * D * 4;
         CHK(dev_alloc(h.get(), &h->kcache, kv, true));
         CHK(dev_alloc(h.get(), &h->vcache, kv, true));
-        const size_t dkv = (size_t)c.n_layers_depth * B * h->depth_rows * D * 4;
-        CHK(dev_alloc(h.get(), &h->dk, dkv, true));
-        CHK(dev_alloc(h.get(), &h->dv, dkv, true));
         CHK(dev_alloc(h.get(), (void**)&h->state, sizeof(StepState), true));
         CHK(dev_alloc(h.get(), (void**)&h->rows, B * sizeof(RowKey), true));
         CHK(dev_alloc(h.get(), (void**)&h->row_set, B * sizeof(RowSampler), true));
@@ -1254,7 +1294,7 @@ static int persist_bind(hqt_handle* h) {
         size_t p = bind_body(h->pfull);
         PersistPhase& lf = h->pfull.phases[p++];
         lf.A = h->xpk; lf.bias = h->lnf_shift; lf.colsum = W(h, "ln_f.weight"); lf.out = h->xdpk;
-        const size_t dkv_layer = (size_t)c.max_batch * h->depth_rows * D;
+        const size_t dkv_layer = (size_t)h->depth_cap() * h->depth_rows * D;      // run_depth's stride: the chain's sub-step 1 reads what this launch appends
         for (int l = 0; l < c.n_layers_depth; ++l) {
             const BlockW& bw = h->depth[l];
             PersistPhase* ph = &h->pfull.phases[p];
@@ -1403,7 +1443,7 @@ static int run_body(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_b
 // The depth blocks over the Tq tokens per sample in xd, at offset tbase of the depth cache
 static int run_depth(hqt_handle* h, const SampleCtx& c, bool dln, int Tq, int tbase) {
     const hqt_config& cf = h->cfg;
-    const size_t dkv_layer = (size_t)cf.max_batch * h->depth_rows * cf.embed_dim * c.md.act_sz();
+    const size_t dkv_layer = (size_t)h->depth_cap() * h->depth_rows * cf.embed_dim * c.md.act_sz();      // (max_batch, unless hqt_set_score_chunk made room for more)
     const Resid r{h->xd, dln ? h->xdpk : nullptr, h->partsd, &h->npartsd};
     for (int l = 0; l < cf.n_layers_depth; ++l)
         CHK(run_block(h, c, h->depth[l], r, Tq, (char*)h->dk + l * dkv_layer, (char*)h->dv + l * dkv_layer, h->depth_rows, tbase, nullptr, 0));
@@ -1416,7 +1456,8 @@ static int head_pk(const SampleCtx& c, const Lin& head, int M) {      // FAST: t
 
 // Logits of the M depth rows of code level lv into h->logits: ln_levels[lv] folded into the head GEMM (dln: the deferred-LayerNorm operand), or
 // the LayerNorm of xd into hbuf and then the GEMM.  `normed` non-null: the operand is already normalised there (the bidirectional head).
-static int run_head(hqt_handle* h, const SampleCtx& c, const Lin& head, int lv, int M, bool dln, void* normed) {
+// `out` non-null (hqt_score): the rows go there instead (contiguous, ldc = V).
+static int run_head(hqt_handle* h, const SampleCtx& c, const Lin& head, int lv, int M, bool dln, void* normed, float* out = nullptr) {
     static const char* const ln_names[3][2] = {{"ln_top.weight", "ln_top.bias"}, {"ln_bot.weight", "ln_bot.bias"}, {"ln_levels.2.weight", "ln_levels.2.bias"}};
     const int adt = c.md.act_dt(), pk = head_pk(c, head, M);
     GemmArgs g{};
@@ -1429,7 +1470,7 @@ static int run_head(hqt_handle* h, const SampleCtx& c, const Lin& head, int lv, 
         }
         g.A = normed;
     }
-    g.a_packed_mb = pk; g.M = M; g.batch = 1; g.C = h->logits; g.ldc = h->cfg.vocab_top; g.store = STORE_ROWS;
+    g.a_packed_mb = pk; g.M = M; g.batch = 1; g.C = out ? out : h->logits; g.ldc = h->cfg.vocab_top; g.store = STORE_ROWS;
     return ar_linear(h, c.md, g, head, adt, DT_F32, c.st, "gemm_head");
 }
 
@@ -1789,6 +1830,143 @@ extern "C" int hqt_sample_prefix_l3(hqt_handle* h, int B, const int64_t* cond, c
                                     int64_t* out0, int64_t* out1, int64_t* out2, void* stream) {
     const int64_t* const prefix[3] = {prefix0, prefix1, prefix2};
     return sample3(h, B, cond, opts, noise, std::max(prefix_len, 0), prefix, force0, force1, force2, logits_out, out0, out1, out2, stream);
+}
+
+// hqt_score: the log-probability of GIVEN codes in one teacher-forced pass (the reference's eval-mode forward, hierarchical_ar.py:246-426,
+// hqtransformer.py:226-407).  Body: the prefix prefill with P = n - 1 -- copy_prefix, embed_prefix (text: embed_text + the prefix rows), run_body with
+// t_base = 0 over n (text: T + n - 1) rows per sample, the classic LayerNorm path (a single row per sample, n = 1 without text, is the decode step's
+// embedding and may take the deferred one; never the persistent chain: the step state is not where t_base comes from).  Depth: a (sample, position) pair
+// p = b n + t is a depth "sample"; chunks of at most score_chunk pairs (default max_batch) run the sub-step schedule of run_position -- input rows,
+// run_depth with the chunk's pair count as batch, run_head, the log-probabilities -- with no sampler, no guidance and no draws.  Eager, no graph.
+extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_t* const* codes, int n, int precision, float* logprobs,
+                         float* const* logits_out, void* stream) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    // a staged table or buffer belongs to a sampling call: it must not wait for a later one behind this call
+    const bool staged = !h->row_set_staged.empty() || h->logprob_staged || !h->guide_staged.empty();
+    h->row_set_staged.clear(); h->logprob_staged = nullptr; h->guide_staged.clear();
+    if (staged) return fail(HQT_ERR_STATE, "hqt_score: a row-sampler table, guidance pair table or log-probability buffer was staged on this handle (hqt_set_row_samplers / "
+                            "hqt_set_guidance / hqt_set_logprob_out): they belong to a sampling call and were cleared");
+    if (!logprobs) return fail(HQT_ERR_INVALID, "hqt_score: logprobs is NULL");
+    if (!codes) return fail(HQT_ERR_INVALID, "hqt_score: codes is NULL");
+    if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
+    const hqt_config& cf = h->cfg;
+    if (!cf.has_stage2) return fail(HQT_ERR_STATE, "handle was created without stage 2");
+    const int levels = cf.code_levels == 3 ? 3 : 2;
+    for (int i = 0; i < levels; ++i) if (!codes[i]) return fail(HQT_ERR_INVALID, "hqt_score: codes of level %d are NULL", i);
+    if (cf.depth_decoding == HQT_DEPTH_TOP2MID2BOT)
+        return fail(HQT_ERR_INVALID, "hqt_score: the 'top2mid2bot' depth head (21 causal sub-steps per position) is not built for the one-pass score: force the codes through hqt_sample_l3");
+    const bool text = cf.cond_type == HQT_COND_TEXT;
+    if (text && levels == 3) return fail(HQT_ERR_INVALID, "hqt_score: text conditioning with three code levels is not built (two code levels are)");
+    if (B < 1 || B > cf.max_batch) return fail(HQT_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cf.max_batch);
+    if (n < 1 || n > cf.max_steps) return fail(HQT_ERR_INVALID, "n=%d outside [1, %d]", n, cf.max_steps);
+    if (cf.cond_type != HQT_COND_NONE && !cond) return fail(HQT_ERR_INVALID, "cond is required for class/text conditioning");
+    if (n - 1 > h->max_prefix)
+        return fail(HQT_ERR_STATE, "hqt_score: n=%d positions need max_prefix >= %d, this handle has %d (hqt_set_max_prefix sizes the body workspace for the pass's rows)", n, n - 1, h->max_prefix);
+    SampleCtx c{};
+    c.levels = levels; c.B = B; c.n_steps = n; c.precision = precision; c.st = (hipStream_t)stream;
+    CHK(mode_of(precision, false, &c.md));
+    CHK(layout_check(h, c.md));
+    ON_DEVICE(h);
+    int64_t* const own[3] = {h->codes_top, h->codes_bot, h->codes_l2};
+    static const int width[3] = {1, 4, 16};
+    if (cond) HIPCHK(hipMemcpyAsync(h->cond_buf, cond, (size_t)B * (text ? cf.ctx_len_txt : 1) * 8, hipMemcpyDefault, c.st));
+    c.cond = cond ? h->cond_buf : nullptr;
+    for (int i = 0; i < levels; ++i) {             // [B, n, width]: the handle's code buffers hold the pairs contiguously, pair p at index p
+        HIPCHK(launch_copy_prefix(codes[i], own[i], B, n, n, width[i], cf.vocab_top, c.st));
+        c.feed[i] = own[i]; c.out[i] = own[i];
+    }
+    HIPCHK(launch_set_step(h->state, 0, 0, c.st));
+    // ---- body: n rows per sample (text: the T prompt rows, then the input rows of positions 1 .. n - 1)
+    const int D = cf.embed_dim, V = cf.vocab_top, T = text ? cf.ctx_len_txt : 0;
+    const int Tq = text ? T + n - 1 : n, row_off = text ? T - 1 : 0;          // body row of pair (b, t): b Tq + row_off + t
+    if (text) {
+        HIPCHK(launch_embed_text(c.cond, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, B, T, D, c.st, cf.vocab_txt, Tq));
+        if (n > 1) {
+            Timed t(h, "embed_prefix", c.st);
+            HIPCHK(launch_embed_prefix(embed_args(h, c, own), n - 1, Tq, T, 1, c.st));
+        }
+    } else if (n > 1) {
+        Timed t(h, "embed_prefix", c.st);
+        HIPCHK(launch_embed_prefix(embed_args(h, c, own), n, n, 0, 0, c.st));
+    } else {                                       // one row per sample: the decode step's embedding at step 0 (with the packed copy where run_body wants it)
+        Timed t(h, "embed", c.st);
+        EmbedArgs e = embed_args(h, c, own);
+        if (dln_ok(h, c, h->body[0], B)) { e.xpk = h->xpk; e.pk_mb = packed_mb(B); h->nparts = 1; }
+        HIPCHK(launch_embed_step(e, c.st));
+    }
+    bool pfull = false;
+    CHK(run_body(h, c, Tq, 0, false, false, &pfull));
+    if (h->pend.slabs) {                           // split-K slabs the last GEMM left for "the next LayerNorm": folded into ALL rows here, before the depth GEMMs reuse the slab workspace
+        CHK(run_ln(h, c.st, h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), nullptr, h->hbuf, B * Tq, D, 1, 0, DT_F32, 0));
+    }
+    // ---- depth: chunks of pairs
+    const Lin* heads[3] = {&h->head_top, &h->head_bot, &h->head_l2};
+    const int64_t* const feed[3] = {h->codes_top, h->codes_bot, h->codes_l2};
+    const bool bidir = cf.depth_decoding == HQT_DEPTH_BIDIRECTIONAL;
+    const int dmul = cf.depth_decoding == HQT_DEPTH_PARALLEL_REDUCE ? 4 : 1;
+    const int chunk = h->score_chunk > 0 ? h->score_chunk : cf.max_batch, total = B * n, draws = h->depth_rows;
+    SampleCtx cc = c;
+    for (int p0 = 0; p0 < total; p0 += chunk) {
+        const int np = std::min(chunk, total - p0);
+        cc.B = np;
+        auto dln_of = [&](const SubStep& s) { return !bidir && dln_ok(h, cc, h->depth[0], np * s.Tq) && heads[s.lv]->wpk_ln; };
+        void* normed[3] = {nullptr, nullptr, nullptr};
+        if (bidir) {              // one pass of the depth blocks over five rows per pair (run_position)
+            const int M = np * h->depth_rows;
+            const bool dln = dln_ok(h, cc, h->depth[0], M);
+            {
+                Timed t(h, "score_depth_input", c.st);
+                LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, np, D, 1, 0, 1e-5f, DT_F32, 0,
+                          nullptr, 0, 0, nullptr, dln ? h->xdpk : nullptr, dln ? packed_mb(M) : 0, h->partsd};
+                ln.fill = W(h, "pos_emb_depth.weight");
+                HIPCHK(launch_score_depth_input(ln, p0, n, Tq, row_off, c.st));
+                h->npartsd = 1;
+            }
+            CHK(run_depth(h, cc, dln, h->depth_rows, 0));
+            {
+                Timed t(h, "bidir_head_ln", c.st);
+                LNArgs ln{h->xd, W(h, "ln_top.weight"), W(h, "ln_top.bias"), nullptr, h->hbuf, M, D, 1, 0, 1e-5f, c.md.act_dt(), head_pk(cc, h->head_top, np)};
+                ln.gamma2 = W(h, "ln_bot.weight"); ln.beta2 = W(h, "ln_bot.bias"); ln.y2 = h->abuf; ln.out2_packed_mb = head_pk(cc, h->head_bot, 4 * np);
+                take_pend(h, ln);
+                HIPCHK(launch_bidir_head_ln(ln, c.st));
+            }
+            normed[0] = h->hbuf; normed[1] = h->abuf;
+        }
+        for (int sub = 0; sub < levels; ++sub) {
+            const SubStep s = sub_step(cf, sub);
+            const int M = np * s.Tq;
+            const bool dln = dln_of(s);
+            if (!bidir) {
+                bf16_t* xpk = dln ? h->xdpk : nullptr;
+                const int pk = dln ? packed_mb(M) : 0;
+                if (sub == 0) {
+                    Timed t(h, "score_depth_input", c.st);
+                    LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, np, D, 1, 0, 1e-5f, DT_F32, 0,
+                              nullptr, 0, 0, nullptr, xpk, pk, h->partsd};
+                    HIPCHK(launch_score_depth_input(ln, p0, n, Tq, row_off, c.st));
+                } else if (sub == 1) {
+                    Timed t(h, "embed", c.st);
+                    HIPCHK(launch_score_depth_embed(feed[0], p0, np, W(h, "tok_emb_top_depth.weight"), W(h, "pos_emb_depth.weight"), h->xd, D, xpk, pk, h->partsd,
+                                                    c.st, V, dmul * D));
+                } else {
+                    Timed t(h, "embed", c.st);
+                    HIPCHK(launch_score_depth_embed_l2(feed[0], feed[1], p0, np, cf.depth_decoding == HQT_DEPTH_PARALLEL_ADD ? W(h, "tok_emb_top_depth.weight") : nullptr,
+                                                       W(h, "tok_emb_depth_levels.1.weight"), W(h, "pos_emb_depths.1.weight"), h->xd, D, xpk, pk, h->partsd,
+                                                       c.st, V, dmul * D));
+                }
+                h->npartsd = 1;
+                CHK(run_depth(h, cc, dln, s.Tq, s.tbase));
+            }
+            // the head GEMM writes the caller's buffer directly where one is given: rows of a level are contiguous over pairs
+            float* lg = (logits_out && logits_out[s.lv]) ? logits_out[s.lv] + (size_t)p0 * s.Tq * V : h->logits;
+            CHK(run_head(h, cc, *heads[s.lv], s.lv, M, dln, normed[s.lv], lg));
+            {
+                Timed t(h, "score_logprob", c.st);
+                HIPCHK(launch_score_logprob(lg, feed[s.lv] + (size_t)p0 * s.Tq, logprobs + (size_t)p0 * draws, np, V, s.Tq, s.tbase, draws, c.st));
+            }
+        }
+    }
+    return HQT_OK;
 }
 
 // Persistent launches need every compute unit of the device: two of them in flight at once (two root handles sampling on two streams)

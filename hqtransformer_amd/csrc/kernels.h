@@ -50,6 +50,10 @@ hipError_t launch_embed_text(const int64_t* cond, const float* tok, const float*
 hipError_t launch_depth_embed(const int64_t* codes_top, int n_steps, const StepState* state, const float* tok,
                               const float* pos, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V = 0, int tok_ld = 0);
 
+// hqt_score: launch_depth_embed over a chunk of pairs addressed by pair index -- rows [4 i, 4 i + 4) from codes_top[pair0 + i], i < pairs (codes_top [B n])
+hipError_t launch_score_depth_embed(const int64_t* codes_top, int pair0, int pairs, const float* tok, const float* pos, float* x, int D, bf16_t* xpk,
+                                    int pk_mb, float* parts, hipStream_t st, int V = 0, int tok_ld = 0);
+
 struct LNArgs {
     float* x;                    // [rows_in, D]; rewritten in place when split-K slabs are folded in
     const float* gamma;
@@ -79,6 +83,10 @@ struct LNArgs {
     int out2_packed_mb;
 };
 hipError_t launch_layernorm(const LNArgs& a, hipStream_t st);
+// hqt_score, depth input of level 0 for a chunk of a.M (sample, position) pairs: row m (bidirectional, a.fill non-NULL: row 5 m, then the four fill rows, as
+// launch_bidir_depth_input) = ln_f + add of body row b * stride + off + t of pair p = pair0 + m = b n + t; a.in_rows_per_group / in_row_offset are not read.
+// fp32 y, optional packed copy + row statistics (ypk); the row arithmetic is launch_layernorm's own (ln_row)
+hipError_t launch_score_depth_input(const LNArgs& a, int pair0, int n, int stride, int off, hipStream_t st);
 // bidirectional depth head (hierarchical_ar.py:803-826): x[b] = last body row of sample b (in_rows_per_group / in_row_offset) ->
 // y rows [5 b] = ln_f(x[b]) + add, [5 b + 1 .. 5 b + 4] = fill[0..3]; fp32 y, optional packed copy + row statistics (ypk)
 hipError_t launch_bidir_depth_input(const LNArgs& a, hipStream_t st);
@@ -142,6 +150,9 @@ hipError_t launch_sampler(const SamplerArgs& a, hipStream_t st);
 // b * slots + slot of a.logits (before temperature, no cut-off; IEEE expf / logf in every precision) at feed[index of that draw in `out`] -- `feed` is the forced
 // codes of the level, or a.out itself (the code just drawn).  One launch per slot, B workgroups; a row's value depends on its own bits and V only.
 hipError_t launch_code_logprob(const SamplerArgs& a, const int64_t* feed, float* logprob, int slot, hipStream_t st);
+// score_logprob_kernel (hqt_score): the value code_logprob_kernel defines, for ALL rows of a sub-step in one launch, one workgroup per (pair, slot): row
+// r = i * slots + slot of logits [pairs * slots, V] at codes[r] -> logprob[i * draws + draw0 + slot]; every pointer is at the chunk's first pair
+hipError_t launch_score_logprob(const float* logits, const int64_t* codes, float* logprob, int pairs, int V, int slots, int draw0, int draws, hipStream_t st);
 // guide_logits_kernel, IN FRONT of launch_sampler on the same stream: for every pair of `pairs` [n_pairs] (device) and every slot < slots, the rows
 // pos_row * slots + slot and neg_row * slots + slot of logits [B * slots, V] are both overwritten with g = l_pos + (scale[level] - 1) (l_pos - l_neg), each
 // operation rounded to fp32 on its own (no FMA) in every precision.  One launch per sub-step, n_pairs x slots workgroups; rows outside every pair are not touched.
@@ -152,6 +163,9 @@ hipError_t launch_guide_logits(float* logits, const GuidePair* pairs, int n_pair
 hipError_t launch_depth_embed_l2(const int64_t* codes0, const int64_t* codes1, int n_steps, const StepState* state, const float* tok0,
                                  const float* tok1, const float* pos, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts,
                                  hipStream_t st, int V = 0, int tok1_ld = 0);
+// hqt_score: launch_depth_embed_l2 over a chunk of pairs -- rows [16 i, 16 i + 16) from codes0[pair0 + i] and codes1[(pair0 + i) * 4 ..]
+hipError_t launch_score_depth_embed_l2(const int64_t* codes0, const int64_t* codes1, int pair0, int pairs, const float* tok0, const float* tok1, const float* pos,
+                                       float* x, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V = 0, int tok1_ld = 0);
 // 'top2mid2bot' head (hqtransformer.py:700-735): input of causal sub-step cnt >= 1 = tok[codes[(b * n_steps + step) * stride + slot]] + pos_row
 hipError_t launch_depth_embed_causal(const int64_t* codes, int stride, int slot, int n_steps, const StepState* state, const float* tok,
                                      const float* pos_row, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V);

@@ -171,15 +171,35 @@ hipError_t launch_embed_text(const int64_t* cond, const float* tok, const float*
 
 // `tok_ld` = row length of the table: D, or 4 D for the 'reduce' head, where slot s of a code takes the D-slice s of its row
 // (hqtransformer.py:108-116,532-533)
+// depth_embed_row: output row `row` (slot row & 3 of its group), from the top code at index `at` of codes_top.  Shared by the decode step's kernel
+// (at = b * n_steps + step) and hqt_score's (at = the pair's index)
+__device__ __forceinline__ void depth_embed_row(const int64_t* codes_top, long long at, int row, const float* tok, const float* pos, float* x, int D,
+                                                bf16_t* xpk, int pk_mb, float* parts, int V, int tok_ld, float* red) {
+    const int s = row & 3;
+    const long long code = clamp_idx(codes_top[at], V);
+    const float* e = tok + code * tok_ld + (tok_ld > D ? s * D : 0);
+    for (int d = threadIdx.x; d < D; d += blockDim.x) x[(long long)row * D + d] = e[d] + pos[(long long)s * D + d];
+    if (xpk) { __syncthreads(); emit_packed_row(x + (long long)row * D, row, D, xpk, pk_mb, parts, red); }
+}
 __global__ __launch_bounds__(256) void depth_embed_kernel(const int64_t* codes_top, int n_steps, const StepState* state,
                                                           const float* tok, const float* pos, float* x, int D, bf16_t* xpk,
                                                           int pk_mb, float* parts, int V, int tok_ld) {
     __shared__ float red[4];
-    const int row = blockIdx.x, b = row >> 2, s = row & 3;
-    const long long code = clamp_idx(codes_top[(long long)b * n_steps + state->step], V);
-    const float* e = tok + code * tok_ld + (tok_ld > D ? s * D : 0);
-    for (int d = threadIdx.x; d < D; d += blockDim.x) x[(long long)row * D + d] = e[d] + pos[(long long)s * D + d];
-    if (xpk) { __syncthreads(); emit_packed_row(x + (long long)row * D, row, D, xpk, pk_mb, parts, red); }
+    const int row = blockIdx.x, b = row >> 2;
+    depth_embed_row(codes_top, (long long)b * n_steps + state->step, row, tok, pos, x, D, xpk, pk_mb, parts, V, tok_ld, red);
+}
+// hqt_score: the rows of a chunk of pairs, pair pair0 + (row >> 2) -- codes_top is [B n] there, indexed by the pair
+__global__ __launch_bounds__(256) void score_depth_embed_kernel(const int64_t* codes_top, int pair0, const float* tok, const float* pos, float* x, int D,
+                                                                bf16_t* xpk, int pk_mb, float* parts, int V, int tok_ld) {
+    __shared__ float red[4];
+    const int row = blockIdx.x;
+    depth_embed_row(codes_top, (long long)pair0 + (row >> 2), row, tok, pos, x, D, xpk, pk_mb, parts, V, tok_ld, red);
+}
+hipError_t launch_score_depth_embed(const int64_t* codes_top, int pair0, int pairs, const float* tok, const float* pos, float* x, int D, bf16_t* xpk,
+                                    int pk_mb, float* parts, hipStream_t st, int V, int tok_ld) {
+    if (pair0 < 0 || pairs < 1) return hipErrorInvalidValue;
+    score_depth_embed_kernel<<<pairs * 4, 256, 0, st>>>(codes_top, pair0, tok, pos, x, D, xpk, pk_mb, parts, V, tok_ld > 0 ? tok_ld : D);
+    return hipGetLastError();
 }
 hipError_t launch_depth_embed(const int64_t* codes_top, int n_steps, const StepState* state, const float* tok,
                               const float* pos, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V, int tok_ld) {
@@ -189,15 +209,14 @@ hipError_t launch_depth_embed(const int64_t* codes_top, int n_steps, const StepS
 
 // Level-2 tokens of the three-level head, (H1 H2 W1 W2) raster: token i carries its parent's level-1 embedding (the D-slice of child
 // (H2 W2) when the table is [V, 4 D]: 'reduce'), position i and -- `tok0` non-NULL: 'add' -- the top code's embedding (hqtransformer.py:537-551)
-__global__ __launch_bounds__(256) void depth_embed_l2_kernel(const int64_t* codes0, const int64_t* codes1, int n_steps, const StepState* state,
-                                                             const float* tok0, const float* tok1, const float* pos, float* x, int D,
-                                                             bf16_t* xpk, int pk_mb, float* parts, int V, int tok1_ld) {
-    __shared__ float red[4];
-    const int row = blockIdx.x, b = row >> 4, i = row & 15;
+// depth_embed_l2_row: output row `row` (token row & 15 of its group), from the codes at index `at` of codes0 / group `at` of codes1 (see depth_embed_row)
+__device__ __forceinline__ void depth_embed_l2_row(const int64_t* codes0, const int64_t* codes1, long long at, int row, const float* tok0, const float* tok1,
+                                                   const float* pos, float* x, int D, bf16_t* xpk, int pk_mb, float* parts, int V, int tok1_ld, float* red) {
+    const int i = row & 15;
     const int parent = (i >> 3) * 2 + ((i & 3) >> 1);                  // (H1 H2 W1 W2) raster -> (H1 W1)
     const int child = ((i >> 2) & 1) * 2 + (i & 1);                    //                      -> (H2 W2)
-    const long long c0 = clamp_idx(codes0[(long long)b * n_steps + state->step], V);
-    const long long c1 = clamp_idx(codes1[((long long)b * n_steps + state->step) * 4 + parent], V);
+    const long long c0 = clamp_idx(codes0[at], V);
+    const long long c1 = clamp_idx(codes1[at * 4 + parent], V);
     const float* e1 = tok1 + c1 * tok1_ld + (tok1_ld > D ? child * D : 0);
     for (int d = threadIdx.x; d < D; d += blockDim.x) {
         float v = e1[d] + pos[(long long)i * D + d];
@@ -205,6 +224,25 @@ __global__ __launch_bounds__(256) void depth_embed_l2_kernel(const int64_t* code
         x[(long long)row * D + d] = v;
     }
     if (xpk) { __syncthreads(); emit_packed_row(x + (long long)row * D, row, D, xpk, pk_mb, parts, red); }
+}
+__global__ __launch_bounds__(256) void depth_embed_l2_kernel(const int64_t* codes0, const int64_t* codes1, int n_steps, const StepState* state,
+                                                             const float* tok0, const float* tok1, const float* pos, float* x, int D,
+                                                             bf16_t* xpk, int pk_mb, float* parts, int V, int tok1_ld) {
+    __shared__ float red[4];
+    const int row = blockIdx.x, b = row >> 4;
+    depth_embed_l2_row(codes0, codes1, (long long)b * n_steps + state->step, row, tok0, tok1, pos, x, D, xpk, pk_mb, parts, V, tok1_ld, red);
+}
+__global__ __launch_bounds__(256) void score_depth_embed_l2_kernel(const int64_t* codes0, const int64_t* codes1, int pair0, const float* tok0, const float* tok1,
+                                                                   const float* pos, float* x, int D, bf16_t* xpk, int pk_mb, float* parts, int V, int tok1_ld) {
+    __shared__ float red[4];
+    const int row = blockIdx.x;
+    depth_embed_l2_row(codes0, codes1, (long long)pair0 + (row >> 4), row, tok0, tok1, pos, x, D, xpk, pk_mb, parts, V, tok1_ld, red);
+}
+hipError_t launch_score_depth_embed_l2(const int64_t* codes0, const int64_t* codes1, int pair0, int pairs, const float* tok0, const float* tok1, const float* pos,
+                                       float* x, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V, int tok1_ld) {
+    if (pair0 < 0 || pairs < 1) return hipErrorInvalidValue;
+    score_depth_embed_l2_kernel<<<pairs * 16, 256, 0, st>>>(codes0, codes1, pair0, tok0, tok1, pos, x, D, xpk, pk_mb, parts, V, tok1_ld > 0 ? tok1_ld : D);
+    return hipGetLastError();
 }
 hipError_t launch_depth_embed_l2(const int64_t* codes0, const int64_t* codes1, int n_steps, const StepState* state, const float* tok0,
                                  const float* tok1, const float* pos, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts,
@@ -239,11 +277,10 @@ hipError_t launch_depth_embed_causal(const int64_t* codes, int stride, int slot,
 //   LN_BIDIR_HEADS: input row m = 5 b + s; s == 0 -> ln_top (gamma / beta) into row b of y, s > 0 -> ln_bot (gamma2 / beta2) into
 //                   row 4 b + s - 1 of y2 (each with its own packed layout).
 enum { LN_PLAIN = 0, LN_BIDIR_INPUT = 1, LN_BIDIR_HEADS = 2 };
-template <typename TO, int MODE = LN_PLAIN>
-__global__ __launch_bounds__(256) void layernorm_kernel(LNArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (m >= a.M) return;
+// ln_row: one row by one wave -- row m of the launch, read from input row in_row.  The ONE place that does this arithmetic: layernorm_kernel and
+// score_depth_input_kernel (whose rows come through a row map) both call it, so a row is bit-identical whichever kernel wrote it.
+template <typename TO, int MODE>
+__device__ __forceinline__ void ln_row(const LNArgs& a, int m, long long in_row, int lane) {
     const int D = a.D;
     int om = m, opk = a.out_packed_mb;
     const float* gamma = a.gamma;
@@ -255,7 +292,6 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LNArgs a) {
         om = s ? 4 * b + s - 1 : b;
         if (s) { gamma = a.gamma2; beta = a.beta2; y = a.y2; opk = a.out2_packed_mb; }
     }
-    const long long in_row = (long long)m * a.in_rows_per_group + a.in_row_offset;      // ln_f of the prefill reads the last token of each sample
     float* x = a.x + in_row * D;
     constexpr int MAXV = 8;                       // D <= 2048 in registers; wider rows fall back to re-reading
     float4 v[MAXV], gmv[MAXV], btv[MAXV];      // affine parameters are fetched with the row, ahead of the reductions
@@ -359,6 +395,27 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LNArgs a) {
             }
         }
     }
+}
+template <typename TO, int MODE = LN_PLAIN>
+__global__ __launch_bounds__(256) void layernorm_kernel(LNArgs a) {
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= a.M) return;
+    ln_row<TO, MODE>(a, m, (long long)m * a.in_rows_per_group + a.in_row_offset, threadIdx.x & 63);      // ln_f of the prefill reads the last token of each sample
+}
+// hqt_score: depth input of level 0 for a chunk of (sample, position) pairs -- ln_f + sos_depth of body row b * stride + off + t of pair
+// p = pair0 + m = b n + t (stride = n, off = 0; text: stride = T + n - 1, off = T - 1), into row m of xd (BIDIR: row 5 m, then the four pos_emb_depth rows)
+template <int MODE>
+__global__ __launch_bounds__(256) void score_depth_input_kernel(LNArgs a, int pair0, int n, int stride, int off) {
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= a.M) return;
+    const int p = pair0 + m, b = p / n, t = p - b * n;
+    ln_row<float, MODE>(a, m, (long long)b * stride + off + t, threadIdx.x & 63);
+}
+hipError_t launch_score_depth_input(const LNArgs& a, int pair0, int n, int stride, int off, hipStream_t st) {
+    if (a.D % 4 != 0 || a.out_dtype != DT_F32 || a.out_packed_mb || a.n_slabs || pair0 < 0 || n < 1 || off < 0 || off + n > stride) return hipErrorInvalidValue;
+    if (a.fill) score_depth_input_kernel<LN_BIDIR_INPUT><<<(a.M + 3) / 4, 256, 0, st>>>(a, pair0, n, stride, off);
+    else score_depth_input_kernel<LN_PLAIN><<<(a.M + 3) / 4, 256, 0, st>>>(a, pair0, n, stride, off);
+    return hipGetLastError();
 }
 hipError_t launch_layernorm(const LNArgs& a, hipStream_t st) {
     if (a.D % 4 != 0) return hipErrorInvalidValue;
@@ -901,17 +958,12 @@ hipError_t launch_sampler(const SamplerArgs& args, hipStream_t st) {
 // per thread a pairwise tree over its groups (padded with zeros to G4), then the xor butterfly of the wave, then the four wave sums as (w0 + w1) + (w2 + w3) -- the
 // value depends on the row's bits and on V alone, never on B, the batch row or the other rows.  `feed` is indexed like `out`: the forced code where a level is forced
 // (clamped into the vocabulary, as the embedding kernels clamp it), else the code the sampler wrote.
+// logprob_row: the value of one row, by the 256 threads of a workgroup; thread 0 stores it in *dst.  The ONE place that does this arithmetic
+// (code_logprob_kernel and score_logprob_kernel call it).
 template <int G4>
-__global__ __launch_bounds__(256) void code_logprob_kernel(SamplerArgs a, const int64_t* feed, float* logprob, int slot) {
+__device__ __forceinline__ void logprob_row(const float* lg, int code, int V, float* dst) {
     __shared__ float redf[4], reds[4], sel;
-    const int V = a.V, tid = threadIdx.x;
-    const int b = blockIdx.x, r = b * a.slots + slot;
-    const int step = a.state->step;
-    const int draw = a.draw0 + slot;
-    const int draws = a.draws > 0 ? a.draws : 5;
-    const float* lg = a.logits + (long long)r * V;
-    const long long pos = (long long)b * a.n_steps + step;
-    const int code = (int)clamp_idx(feed[a.out_stride > 0 ? pos * a.out_stride + a.out_slot : pos * a.slots + slot], V);
+    const int tid = threadIdx.x;
     float4 v[G4];
     float m = -INFINITY;
 #pragma unroll
@@ -943,7 +995,33 @@ __global__ __launch_bounds__(256) void code_logprob_kernel(SamplerArgs a, const 
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
     if ((tid & 63) == 0) reds[tid >> 6] = sum;
     __syncthreads();
-    if (tid == 0) logprob[pos * draws + draw] = (sel - m) - logf((reds[0] + reds[1]) + (reds[2] + reds[3]));
+    if (tid == 0) *dst = (sel - m) - logf((reds[0] + reds[1]) + (reds[2] + reds[3]));
+}
+template <int G4>
+__global__ __launch_bounds__(256) void code_logprob_kernel(SamplerArgs a, const int64_t* feed, float* logprob, int slot) {
+    const int V = a.V;
+    const int b = blockIdx.x, r = b * a.slots + slot;
+    const int step = a.state->step;
+    const int draw = a.draw0 + slot;
+    const int draws = a.draws > 0 ? a.draws : 5;
+    const long long pos = (long long)b * a.n_steps + step;
+    const int code = (int)clamp_idx(feed[a.out_stride > 0 ? pos * a.out_stride + a.out_slot : pos * a.slots + slot], V);
+    logprob_row<G4>(a.logits + (long long)r * V, code, V, logprob + pos * draws + draw);
+}
+// hqt_score: ALL rows of a sub-step in one launch, one workgroup per (pair, slot): row r = pair * slots + slot of logits [pairs * slots, V], the code
+// codes[r] (the level's codes of these pairs, [pairs, slots]) -> logprob[pair * draws + draw0 + slot]; both pointers are already at the chunk's first pair
+template <int G4>
+__global__ __launch_bounds__(256) void score_logprob_kernel(const float* logits, const int64_t* codes, float* logprob, int V, int slots, int draw0, int draws) {
+    const int r = blockIdx.x, pair = r / slots, slot = r - pair * slots;
+    logprob_row<G4>(logits + (long long)r * V, (int)clamp_idx(codes[r], V), V, logprob + (long long)pair * draws + draw0 + slot);
+}
+hipError_t launch_score_logprob(const float* logits, const int64_t* codes, float* logprob, int pairs, int V, int slots, int draw0, int draws, hipStream_t st) {
+    if (V % 4 || V > HQT_MAX_V || pairs < 1 || slots < 1 || draw0 < 0 || draw0 + slots > draws) return hipErrorInvalidValue;
+    const unsigned rows = (unsigned)pairs * slots;
+    if (V <= 4096) score_logprob_kernel<4><<<rows, 256, 0, st>>>(logits, codes, logprob, V, slots, draw0, draws);
+    else if (V <= 8192) score_logprob_kernel<8><<<rows, 256, 0, st>>>(logits, codes, logprob, V, slots, draw0, draws);
+    else score_logprob_kernel<16><<<rows, 256, 0, st>>>(logits, codes, logprob, V, slots, draw0, draws);
+    return hipGetLastError();
 }
 hipError_t launch_code_logprob(const SamplerArgs& a, const int64_t* feed, float* logprob, int slot, hipStream_t st) {
     if (a.V % 4 || a.V > HQT_MAX_V || slot < 0 || slot >= a.slots) return hipErrorInvalidValue;

@@ -155,16 +155,48 @@ def check_prefix(s2: Stage2Spec, batch: int, n_steps: int, prefix, max_prefix: O
     return levels
 
 
+def check_score_codes(s2: Stage2Spec, codes, what: str = 'one-pass scoring') -> int:
+    """Codes for ``Engine.score`` checked on the host, before any engine is built or touched: the model's code levels as one list, coarse to fine, int64 [B, n],
+    [B, n, 4][, [B, n, 16]]; host tensors inside the vocabulary (IndexError otherwise; device tensors are checked once by the engine).  ValueError for the heads
+    the one pass is not built for.  Returns n."""
+    if s2.depth_decoding == 'top2mid2bot':
+        raise ValueError(f"{what}: the 'top2mid2bot' depth head runs 21 causal sub-steps per position and is scored stepwise only: use one_pass=False")
+    if s2.cond == 2 and s2.levels == 3:
+        raise ValueError(f'{what}: text conditioning with three code levels is not built (two code levels are): use one_pass=False')
+    L = s2.levels
+    if not isinstance(codes, (list, tuple)) or len(codes) != L:
+        raise ValueError(f'codes: expected the {L} code levels as one list, coarse to fine')
+    levels = [torch.as_tensor(c) for c in codes]
+    if levels[0].dim() != 2 or int(levels[0].shape[1]) < 1:
+        raise ValueError(f'codes[0]: expected shape (B, n), got {tuple(levels[0].shape)}')
+    B, n = (int(v) for v in levels[0].shape)
+    if n > s2.ctx_len_img:
+        raise ValueError(f'codes of n={n} positions: the model has ctx_len_img={s2.ctx_len_img}')
+    for l, t in enumerate(levels):
+        want = (B, n) + ((4 ** l,) if l else ())
+        if tuple(t.shape) != want:
+            raise ValueError(f'codes[{l}]: expected shape {want}, got {tuple(t.shape)}')
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError(f'codes[{l}]: expected integer codes, got {t.dtype}')
+        if not t.is_cuda:
+            lo, hi = int(t.min()), int(t.max())
+            if lo < 0 or hi >= s2.vocab_top:
+                raise IndexError(f'codes[{l}]: index out of range (values span [{lo}, {hi}], table has {s2.vocab_top} rows)')
+    return n
+
+
 class Engine:
     """One libhqt handle on one GPU.  Not thread-safe; asynchronous on torch's current stream."""
 
     def __init__(self, s2: Optional[Stage2Spec], s1: Optional[Stage1Spec], device: torch.device, max_batch: int,
-                 max_steps: Optional[int] = None, ar_layouts: int = 0, max_prefix: int = 0):
+                 max_steps: Optional[int] = None, ar_layouts: int = 0, max_prefix: int = 0, score_chunk: int = 0):
         """``ar_layouts``: bit mask of ``_lib.LAYOUT_*`` -- which derived layouts of the AR loop's weights ``finalize`` builds
         (``hqt_config.ar_layouts``; 0 = all).  A FAST-only replica passes ``_lib.LAYOUT_FAST`` and holds 5.2 instead of 9.1 GB for the
         ImageNet-12L model; a call in a precision the engine was built without raises HqtError (HQT_ERR_STATE).
         ``max_prefix``: longest code prefix ``sample(..., prefix=...)`` may pass (``hqt_set_max_prefix``, called right after ``hqt_create``; 0 = none, and the workspace
-        is exactly what it is without the feature)."""
+        is exactly what it is without the feature).
+        ``score_chunk``: (sample, position) pairs per depth chunk of ``score`` (``hqt_set_score_chunk``, called right after ``hqt_create``; 0 = ``max_batch`` pairs,
+        and nothing is allocated for it)."""
         self.lib = _lib.load()                      # raises HqtLibraryError when the HIP library is absent
         self.s2, self.s1 = s2, s1
         self.device = torch.device(device)
@@ -181,6 +213,10 @@ class Engine:
         if self.max_prefix:
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.hqt_set_max_prefix(self.h, self.max_prefix))
+        self.score_chunk = int(score_chunk)
+        if self.score_chunk:
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.hqt_set_score_chunk(self.h, self.score_chunk))
         self.policy = _lib.POLICY_LATENCY
 
     def clone(self) -> 'Engine':
@@ -191,6 +227,7 @@ class Engine:
         e = Engine.__new__(Engine)
         e.lib, e.s2, e.s1, e.device = self.lib, self.s2, self.s1, self.device
         e.max_batch, e.max_steps, e.max_prefix, e.cfg = self.max_batch, self.max_steps, self.max_prefix, self.cfg
+        e.score_chunk = self.score_chunk
         h = C.c_void_p()
         _lib.check(self.lib.hqt_clone(self.h, C.byref(h)))
         e.h, e.finalized = h, True
@@ -464,6 +501,34 @@ class Engine:
                                            out=None, return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
                                            row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance)
         return tuple(outs) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
+
+    def score(self, batch: int, cond: Optional[torch.Tensor], codes: Sequence[torch.Tensor], *, precision: int = PRECISION_FAST,
+              return_logits: bool = False):
+        """``hqt_score``: log-probabilities fp32 [B, n, draws] of GIVEN codes (the code levels as one list, coarse to fine, int64 [B, n], [B, n, 4][, [B, n, 16]])
+        in ONE teacher-forced pass over all positions -- entry (b, t, d) is what ``sample(..., force_*=codes, return_logprobs=True)`` reports, at the cost of one
+        body pass over n rows per sample and the depth head over the B n pairs in chunks of ``score_chunk``.  The engine needs ``max_prefix >= n - 1``.
+        ``return_logits``: also the raw logits per level, fp32 [B, n, V], [B, n, 4, V][, [B, n, 16, V]] (the head GEMMs then write them directly).
+        Asynchronous on torch's current stream, like ``sample``."""
+        dev = self.device
+        B, V, L = int(batch), self.s2.vocab_top, self.s2.levels
+        check_score_codes(self.s2, codes)
+        n = int(torch.as_tensor(codes[0]).shape[1])
+        if int(torch.as_tensor(codes[0]).shape[0]) != B:
+            raise ValueError(f'codes hold {int(torch.as_tensor(codes[0]).shape[0])} samples, batch={B}')
+        shapes = [(B, n) + ((4 ** l,) if l else ()) for l in range(L)]
+        draws = (4 ** L - 1) // 3
+        cond = self._prep_cond(cond, B)
+        cs = [self._prep(c, shp, torch.int64, f'codes[{l}]', V) for l, (c, shp) in enumerate(zip(codes, shapes))]
+        logprobs = torch.empty((B, n, draws), dtype=torch.float32, device=dev)
+        logits = [torch.empty(shp + (V,), dtype=torch.float32, device=dev) for shp in shapes] if return_logits else None
+        cp = (C.c_void_p * 3)(*[_ptr(c) for c in cs])
+        lp = (C.c_void_p * 3)(*[_ptr(t) for t in logits]) if logits is not None else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            _lib.check(self.lib.hqt_score(self.h, B, _ptr(cond), cp, n, int(precision), _ptr(logprobs), lp, C.c_void_p(stream)))
+            self._note_split(precision, stream)
+        self._keep = (cond, cs, cp, lp)
+        return (logprobs, logits) if return_logits else logprobs
 
     # ------------------------------------------------------------------ stage 1, encode side
     @property

@@ -156,15 +156,18 @@ class HQTransformerStage2(_Stage):
     def pos_emb_txt(self):
         return _Table(self._w['pos_emb_txt.weight'])
 
-    def engine(self, batch: int, n_steps: int, lane: int = 0, max_prefix: int = 0) -> Engine:
+    def engine(self, batch: int, n_steps: int, lane: int = 0, max_prefix: int = 0, score_chunk: Optional[int] = None) -> Engine:
         """``max_prefix`` > 0: the engine must take code prefixes of that many positions (``hqt_set_max_prefix``); like ``batch`` it only
-        ever grows, and a model that never completes a prefix keeps the workspace it always had."""
+        ever grows, and a model that never completes a prefix keeps the workspace it always had.
+        ``score_chunk``: pairs per depth chunk of ``Engine.score`` (``hqt_set_score_chunk``); None keeps what the engine has (0, i.e. ``max_batch`` pairs, for a
+        new one), another value than the engine's rebuilds it."""
         self._need_gpu()
         e = self._engine
-        if e is None or batch > e.max_batch or n_steps > e.max_steps or max_prefix > e.max_prefix:
+        chunk = (e.score_chunk if e else 0) if score_chunk is None else int(score_chunk)
+        if e is None or batch > e.max_batch or n_steps > e.max_steps or max_prefix > e.max_prefix or chunk != e.score_chunk:
             self._drop_engine()
             e = Engine(self.spec, None, self._device, max(batch, e.max_batch if e else 0), self.spec.ctx_len_img,
-                       max_prefix=max(int(max_prefix), e.max_prefix if e else 0))
+                       max_prefix=max(int(max_prefix), e.max_prefix if e else 0), score_chunk=chunk)
             unused = stage2_unused(self.spec)
             e.load(stage2={k: v for k, v in self._w.items() if k not in unused})
             e.finalize()
@@ -292,6 +295,33 @@ class ImageGPT2:
 
     def eval(self):
         return self
+
+    def forward(self, codes, labels=None, precision: Optional[str] = None):
+        """``iHQGPT.forward`` in eval mode (hierarchical_ar.py:246-426) for two-level class-conditional / unconditional models: ``codes = (top [B, n],
+        bot [B, 4 n])`` with ``bot`` in the reference's global raster layout ('B (H H2 W W2)', n = H W a square) -> ``(logits_top [B, n, V], logits_bot
+        [B, 4 n, V])`` as :398-403 returns them, fp32 raw logits, computed by ``hqt_score`` in one teacher-forced pass ('exact' unless ``precision`` says otherwise).
+        Text models return a third tensor there, ``logits_txt`` of ``head_txt`` -- the training-only text head, which is not built: NotImplementedError."""
+        from .sampling import check_forward_codes, global_to_sequence_index
+        s2 = self.stage2
+        top, bot = check_forward_codes(s2.spec, codes)
+        B, n = (int(v) for v in top.shape)
+        idx = global_to_sequence_index(n)                                   # [n, 4]: global raster index of slot s of position t
+        eng = s2.engine(B, n, 0, max_prefix=n - 1)
+        dev = eng.device
+        seq_bot = bot.to(dev)[:, idx.to(dev).reshape(-1)].reshape(B, n, 4).contiguous()
+        cond = None
+        if s2.use_cls_cond:
+            if labels is None:
+                raise ValueError('forward: a class-conditional model needs labels [B]')
+            cond = torch.as_tensor(labels).reshape(-1)
+        prec = PRECISIONS[precision] if precision is not None else PRECISION_EXACT
+        _, (lt, lb) = eng.score(B, cond, [top, seq_bot], precision=prec, return_logits=True)
+        eng.range_check()
+        out_bot = torch.empty((B, 4 * n, lb.shape[-1]), dtype=lb.dtype, device=dev)
+        out_bot[:, idx.to(dev).reshape(-1)] = lb.reshape(B, 4 * n, -1)
+        return lt, out_bot
+
+    __call__ = forward
 
     def to(self, device=None, **kw):
         self.stage1.to(device)

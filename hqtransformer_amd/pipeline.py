@@ -126,17 +126,25 @@ def rank_candidates(scores: torch.Tensor, keep: int) -> torch.Tensor:
     return torch.sort(scores, dim=1, descending=True, stable=True).indices[:, :int(keep)]
 
 
-def score_codes(stage2, codes, cond, precision: Optional[str] = None, **kw) -> torch.Tensor:
+def score_codes(stage2, codes, cond, precision: Optional[str] = None, one_pass: bool = False, score_chunk: Optional[int] = None, **kw) -> torch.Tensor:
     """Log-probabilities of GIVEN codes under the model: ``codes`` = the code levels as one list, coarse to fine (int64 [B, n], [B, n, 4][, [B, n, 16]]),
     ``cond`` as in ``sampling_ihqgpt`` -> fp32 [B, n, draws], entry (b, t, d) the log-probability (T = 1, no cut-off) of the code of draw d at position t
-    given the sample's codes before it: ``-sequence_logprob(...)`` is the stage-2 negative log-likelihood in nats.  ONE sampler call with every level forced
+    given the sample's codes before it: ``-sequence_logprob(...)`` is the stage-2 negative log-likelihood in nats.
+    ``one_pass=False`` (the default): ONE sampler call with every level forced
     to ``codes`` (seed 0; its draws are discarded): teacher forcing through the sequential decode steps, so the cost is that of sampling n positions -- n
-    decode steps --, not of one parallel pass.  ``precision`` 'exact' | 'fast' | 'split' (default: ``use_fp16`` of ``kw``, i.e. FAST); further keywords:
-    ``use_fp16``, ``lane``, ``use_graph``.  ValueError for the 'bidirectional' depth head, where the sampling surface refuses forced codes too
-    (``given_top_code``: the reference ignores them there)."""
+    decode steps --, not of one parallel pass.  ValueError for the 'bidirectional' depth head, where the sampling surface refuses forced codes too
+    (``given_top_code``: the reference ignores them there).
+    ``one_pass=True``: ``hqt_score`` -- the body once over all n rows per sample, the depth head over the B n (sample, position) pairs in chunks of
+    ``score_chunk`` pairs (None: what the engine has, ``max_batch`` for a new one); the engine is asked for ``max_prefix = n - 1``.  Takes the 'bidirectional'
+    head (nothing is forced in its depth pass); ValueError for 'top2mid2bot', which is scored stepwise only (``one_pass=False``).
+    ``precision`` 'exact' | 'fast' | 'split' (default: ``use_fp16`` of ``kw``, i.e. FAST); further keywords: ``use_fp16``, ``lane``, ``use_graph`` (stepwise only)."""
     spec = stage2.spec
-    if spec.depth_decoding == 'bidirectional':
-        raise ValueError("score_codes forces every code level, which the 'bidirectional' depth head does not support (as with given_top_code: the reference ignores it there)")
+    if one_pass:
+        from .engine import check_score_codes
+        check_score_codes(spec, codes, 'score_codes(one_pass=True)')
+    elif spec.depth_decoding == 'bidirectional':
+        raise ValueError("score_codes forces every code level, which the 'bidirectional' depth head does not support (as with given_top_code: the reference ignores it there); "
+                         'one_pass=True scores it')
     codes = [torch.as_tensor(c) for c in codes]
     if len(codes) != spec.levels or codes[0].dim() != 2:
         raise ValueError(f'codes: expected the {spec.levels} code levels as one list, coarse to fine, the first of shape [B, n]')
@@ -148,11 +156,21 @@ def score_codes(stage2, codes, cond, precision: Optional[str] = None, **kw) -> t
     B, cond = _batch_and_cond(stage2, int(codes[0].shape[0]), cond)
     if B != int(codes[0].shape[0]):
         raise ValueError(f'codes hold {int(codes[0].shape[0])} samples, cond {B}')
+    if one_pass:
+        eng = stage2.engine(B, n, lane, max_prefix=n - 1, score_chunk=score_chunk)
+        return eng.score(B, cond, codes, precision=_precision(precision, use_fp16))
     eng = stage2.engine(B, n, lane)
     common = dict(precision=_precision(precision, use_fp16), seed=0, return_logprobs=True, **kw)
     if spec.levels == 3:
         return eng.sample3(B, cond, n, force=codes, **common)[-1]
     return eng.sample(B, cond, n, force_top=codes[0], force_bot=codes[1], **common)[-1]
+
+
+def score_images(model, images: torch.Tensor, cond=None, encode_precision: Optional[str] = None, **score_kw) -> Tuple[torch.Tensor, list]:
+    """Stage-2 log-likelihood of real images: ``images`` fp32 [B, 3, R, R] in [-1, 1] -> ``stage1.code_grids`` -> ``grids_to_sequences`` ->
+    ``score_codes(one_pass=True)`` (``score_kw``: its further keywords).  Returns ``(sequence_logprob fp64 [B], codes)``, the codes in the sampler's layout."""
+    codes = grids_to_sequences(list(model.stage1.code_grids(images, precision=encode_precision)))
+    return sequence_logprob(score_codes(model.stage2, codes, cond, one_pass=True, **score_kw)), codes
 
 
 def sample_best_of(stage2, cond, num_candidates: int, keep: int, **sampler) -> Tuple[list, torch.Tensor]:

@@ -305,3 +305,37 @@ def rearrange_codes3(codes: List[torch.Tensor], top_resolution: int):
 def rearrange_codes(codes_top: torch.Tensor, codes_bot: torch.Tensor, top_resolution: int):
     """The two rearranges of ``sampling_hqmodel.py:119-120``, ``measure_throughput/__main__.py:106-107``."""
     return rearrange_levels([codes_top, codes_bot], top_resolution)
+
+
+# ---------------------------------------------------------------------------------------------- the reference's forward() layout
+def global_to_sequence_index(n: int, level: int = 1) -> torch.Tensor:
+    """int64 [n, 4 ** level]: entry (t, s) is the index, in the reference's global raster layout of code level ``level`` ('B (H H2 W W2)': the
+    flattened (K << level) x (K << level) grid, n = K K), of slot s (row-major in the position's 2 ** level x 2 ** level block) of top position t --
+    the sampler's layout [B, n, 4 ** level] is ``global[:, index]``."""
+    K = int(round(n ** 0.5))
+    if K * K != int(n):
+        raise ValueError(f'n={n} top positions are not a square grid')
+    k = 2 ** int(level)
+    grid = torch.arange(n * k * k, dtype=torch.int64).reshape(1, K * k, K * k)
+    return grid.reshape(1, K, k, K, k).permute(0, 1, 3, 2, 4).reshape(n, k * k)
+
+
+def check_forward_codes(spec, codes):
+    """Arguments of ``ImageGPT2.forward`` checked on the host, before any engine is built: two code levels, no text conditioning (its third output,
+    ``logits_txt`` of the training-only ``head_txt``, is not built), ``codes = (top [B, n], bot [B, 4 n])`` with n a square."""
+    if spec.cond == 2:
+        raise NotImplementedError('forward of a text-conditional model also returns logits_txt = head_txt(ln_txt(h_txt)) (hierarchical_ar.py:386-390): head_txt '
+                                  'is the training-only text head and is not built; score the image codes with pipeline.score_codes(one_pass=True)')
+    if spec.levels != 2:
+        raise ValueError('forward is built for two-level models (iHQGPT.forward); three-level codes are scored by pipeline.score_codes(one_pass=True)')
+    if not isinstance(codes, (list, tuple)) or len(codes) != 2:
+        raise ValueError('codes: expected (top [B, n], bot [B, 4 n])')
+    top, bot = (torch.as_tensor(c) for c in codes)
+    if top.dim() != 2:
+        raise ValueError(f'codes[0]: expected shape (B, n), got {tuple(top.shape)}')
+    B, n = (int(v) for v in top.shape)
+    if int(round(n ** 0.5)) ** 2 != n:
+        raise ValueError(f'codes[0]: n={n} top positions are not a square grid (the global raster layout of the bottom codes needs one)')
+    if tuple(bot.shape) != (B, 4 * n):
+        raise ValueError(f'codes[1]: expected shape {(B, 4 * n)} (global raster layout), got {tuple(bot.shape)}')
+    return top, bot

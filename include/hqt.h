@@ -325,6 +325,28 @@ int hqt_sample_prefix_l3(hqt_handle* h, int B, const int64_t* cond, const hqt_sa
                          int prefix_len, const int64_t* prefix0, const int64_t* prefix1, const int64_t* prefix2,
                          const int64_t* force0, const int64_t* force1, const int64_t* force2, float* logits_out,
                          int64_t* out0, int64_t* out1, int64_t* out2, void* stream);
+/* hqt_score -- the eval-mode `forward` of the reference (iHQGPT.forward, hierarchical_ar.py:246-426; HQTransformer.forward,
+ * hqtransformer.py:226-407) as a scoring call: the log-probability of GIVEN codes in one teacher-forced pass over all positions.  Every body
+ * input row follows from the codes, so the body runs once, causally, over n rows per sample (the prefix prefill with prefix_len = n - 1; text:
+ * ctx_len_txt + n - 1 rows); the depth head then runs over all B n (sample, position) pairs, numbered p = b n + t, in chunks of at most
+ * `chunk` pairs (hqt_set_score_chunk; never called: max_batch pairs and no allocation beyond hqt_create's).  A chunk may straddle samples.
+ *   codes        one device pointer per level, coarse to fine, in the sampler's layout: int64 [B, n], [B, n, 4][, [B, n, 16]]; values outside
+ *                the vocabulary are clamped into it, as in hqt_sample_prefix
+ *   logprobs     fp32 [B, n, draws], draws = 5 or 21: entry (b, t, d) = l[code] - max(l) - logf(sum expf(l - max(l))) over the raw logits row
+ *                of draw d at position t given the sample's codes before t (T = 1, no cut-off: what hqt_set_logprob_out reports for a forced run)
+ *   logits_out   NULL, or one pointer per level, each NULL or fp32 raw logits [B, n, V], [B, n, 4, V][, [B, n, 16, V]]
+ * Runs eagerly on `stream`; touches neither the graph cache nor its key, leaves the step state at (0, 0) and the K/V cache and the code
+ * buffers overwritten: a sampling call afterwards draws what it drew before.  The handle needs hqt_set_max_prefix(h, >= n - 1) (n = 1: none).
+ * HQT_ERR_STATE: not finalized, max_prefix too small, a precision whose layout the handle was built without, a staged row-sampler table,
+ * pair table or log-probability buffer (they belong to a sampling call; hqt_score clears them).  HQT_ERR_INVALID: NULL logprobs / codes,
+ * B or n out of range, the 'top2mid2bot' head (21 causal sub-steps: score it stepwise, hqt_sample_l3 with forced codes), three code levels
+ * with text conditioning.
+ * hqt_set_score_chunk -- pairs per depth chunk, between hqt_create and hqt_finalize_weights (lanes inherit it): sizes the depth workspace
+ * (depth rows, logits, depth K/V) for `pairs` pairs and the row buffers for pairs x Tdepth rows (Tdepth = 4, 5 'bidirectional', 16 three
+ * levels) where they are smaller.  HQT_ERR_INVALID: pairs < 0 or pairs x Tdepth beyond the 16384 rows of one pass; 0 restores the default. */
+int hqt_set_score_chunk(hqt_handle* h, int pairs);
+int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_t* const* codes, int n, int precision, float* logprobs,
+              float* const* logits_out, void* stream);
 int hqt_decode_l3(hqt_handle* h, int B, const int64_t* code_t, const int64_t* code_m, const int64_t* code_b, float* out_pixels,
                   int clamp01, int precision, void* stream);
 int hqt_decode_seq_l3(hqt_handle* h, int B, const int64_t* codes0, const int64_t* codes1, const int64_t* codes2, float* out_pixels,
