@@ -1089,8 +1089,14 @@ static int ar_linear(hqt_handle* h, const Mode& md, GemmArgs g, const Lin& l, in
             return HQT_OK;
         }
         g.Bw = l.w16;
-        if (mfma_gemm_ok(g, a_dt, DT_BF16, c_dt)) HIPCHK(launch_mfma_gemm(g, a_dt, DT_BF16, c_dt, st));
-        else HIPCHK(launch_gemm_generic(g, a_dt, DT_BF16, c_dt, st));
+        // no packed layout for this shape (stream_gemm_supported: N, K multiples of 32): the plain MFMA kernel, or the generic one where K % 32 != 0
+        if (mfma_gemm_ok(g, a_dt, DT_BF16, c_dt)) {
+            HIPCHK(launch_mfma_gemm(g, a_dt, DT_BF16, c_dt, st));
+            count_variant(h, "variant:mfma_gemm:%s", tag);
+        } else {
+            HIPCHK(launch_gemm_generic(g, a_dt, DT_BF16, c_dt, st));
+            count_variant(h, "variant:gemm_generic_bf16:%s", tag);
+        }
         return HQT_OK;
     }
     // (up to 256 rows the fp32 matrix instructions of exact_gemm.hip are faster than three fp16 MFMAs on 128 x 128 tiles that are mostly padding:
@@ -1117,7 +1123,7 @@ static int ar_linear(hqt_handle* h, const Mode& md, GemmArgs g, const Lin& l, in
         return HQT_OK;
     }
     HIPCHK(launch_gemm_generic(g, DT_F32, DT_F32, DT_F32, st));
-    if (md.split_ar) count_variant(h, "variant:gemm_generic_f32:%s", tag);
+    count_variant(h, "variant:gemm_generic_f32:%s", tag);
     return HQT_OK;
 }
 

@@ -578,9 +578,9 @@ __global__ __launch_bounds__(576, 1) void persist_kernel(PersistArgs a) {
                 for (int i2 = wave; i2 < nit; i2 += 8) {
                     const int u = cu + i2 * ncu;
                     const int h = u / nb8, bb = u - h * nb8;
-                    if (lane < chunks * 8) {
-                        const int cc = lane >> 3, w = lane & 7, m = bb * 8 + w;
-                        if (m < M) st16_sc1(rsO, packed_off(m, h * hs + cc * 8, MB) * 2, *reinterpret_cast<const u32x4*>(stage + (size_t)i2 * (hs * 16) + lane * 16));
+                    for (int e = lane; e < chunks * 8; e += 64) {            // hs / 8 granules x 8 samples: more than one round of the wave from head size 128 on
+                        const int cc = e >> 3, w = e & 7, m = bb * 8 + w;
+                        if (m < M) st16_sc1(rsO, packed_off(m, h * hs + cc * 8, MB) * 2, *reinterpret_cast<const u32x4*>(stage + (size_t)i2 * (hs * 16) + e * 16));
                     }
                 }
             }
