@@ -145,7 +145,7 @@ struct hqt_handle {
     // per-row keys of merged steps travel through a ring of PINNED staging buffers (an asynchronous copy from pinned memory reads its
     // source when the stream gets there: a buffer is rewritten only after the copy that last read it has completed, hipEventSynchronize)
     static constexpr int ROWS_RING = 4;
-    RowKey* rows_pinned[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};       // each: RowKey[max_batch], then RowSampler[max_batch], then GuidePair[guide_room]
+    RowKey* rows_pinned[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};       // each: RowKey[max_batch], then RowSampler[max_batch], then GuidePair[guide_room], then the keep mask [max_batch * max_steps]
     hipEvent_t rows_ev[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};
     bool rows_busy[ROWS_RING] = {false, false, false, false};
     int rows_next = 0;
@@ -155,6 +155,12 @@ struct hqt_handle {
     GuidePair* guide = nullptr;               // [guide_room()] pair table of the current call (hqt_set_guidance)
     std::vector<hqt_guide_pair> guide_staged; // host table waiting for the next sampling call of this handle, which takes it
     size_t guide_room() const { return (size_t)std::max(1, cfg.max_batch / 2); }      // a row is in at most one pair
+    // hqt_set_keep_mask: host mask [keep_B, keep_n] and one device pointer per level, waiting for the next hqt_sample / hqt_sample_l3 of this handle, which takes them
+    std::vector<uint8_t> keep_staged;
+    int keep_B = 0, keep_n = 0;
+    const int64_t* keep_codes[3] = {nullptr, nullptr, nullptr};
+    unsigned char* keep_mask = nullptr;       // [max_batch * max_steps] mask of the current call
+    void clear_staged() { row_set_staged.clear(); logprob_staged = nullptr; guide_staged.clear(); keep_staged.clear(); }
     int64_t *cond_buf = nullptr, *codes_top = nullptr, *codes_bot = nullptr;   // call-independent homes of cond / the drawn codes
     int64_t* codes_l2 = nullptr;              // third level: [B, max_steps, 16]
     Lin head_l2;                              // head_levels.2 (three-level models; head_top / head_bot hold levels 0 / 1)
@@ -550,6 +556,7 @@ static int alloc_workspace(hqt_handle* hp) {
         CHK(dev_alloc(h.get(), (void**)&h->rows, B * sizeof(RowKey), true));
         CHK(dev_alloc(h.get(), (void**)&h->row_set, B * sizeof(RowSampler), true));
         CHK(dev_alloc(h.get(), (void**)&h->guide, h->guide_room() * sizeof(GuidePair), true));
+        CHK(dev_alloc(h.get(), (void**)&h->keep_mask, B * (size_t)c.max_steps, true));
         CHK(dev_alloc(h.get(), (void**)&h->cond_buf, B * (size_t)std::max(1, c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : 1) * 8, true));
         CHK(dev_alloc(h.get(), (void**)&h->codes_top, B * (size_t)c.max_steps * 8, true));
         CHK(dev_alloc(h.get(), (void**)&h->codes_bot, B * (size_t)c.max_steps * 4 * 8, true));
@@ -632,6 +639,7 @@ extern "C" int hqt_clone(hqt_handle* src, hqt_handle** out) {
     h->row_set_staged.clear();                   // a lane has its own table
     h->logprob_staged = nullptr;                 // ... and its own log-probability buffer
     h->guide_staged.clear();                     // ... and its own pair table
+    h->keep_staged.clear();                      // ... and its own keep table
     h->nparts = h->npartsd = 0;
     h->pbody.d_phases = nullptr; h->pfull.d_phases = nullptr;      // phase tables hold workspace pointers: bound per handle (persist_bind)
     h->persist_used = false; h->persist_tripped = false; h->capture_persist = false; h->graph_has_persist = false;
@@ -1151,6 +1159,8 @@ struct SampleCtx {
     float* logprob_out = nullptr;                // hqt_set_logprob_out: [B, n_steps, draws], NULL: no code_logprob launches at all
     const hqt_guide_pair* guide = nullptr;       // host table of n_guide pairs staged by hqt_set_guidance, NULL: no guide_logits launches at all
     int n_guide = 0;
+    const uint8_t* keep = nullptr;               // host mask [B, n_steps] staged by hqt_set_keep_mask, NULL: every position is drawn (and nothing below is read)
+    const int64_t* keep_codes[3] = {nullptr, nullptr, nullptr};   // its codes per level, device, [B, n_steps(, 4 | 16)]
     hipStream_t st;
     Mode md;
 };
@@ -1600,6 +1610,7 @@ static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body
                 sa.row_set = h->row_set; sa.row_top_p = c.row_top_p ? 1 : 0;
                 sa.row_lv_t = bidir ? 0 : s.lv; sa.row_lv_k = bidir ? 1 : s.lv;
             }
+            if (c.keep) sa.keep = h->keep_mask;
             if (fuse && sub == 0) {
                 const bool dln_next = dln_of(sub_step(cf, 1));
                 sa.emb_tok = W(h, "tok_emb_top_depth.weight"); sa.emb_pos = W(h, "pos_emb_depth.weight");
@@ -1668,6 +1679,10 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     guide.swap(h->guide_staged);
     c.guide = guide.empty() ? nullptr : guide.data();
     c.n_guide = (int)guide.size();
+    std::vector<uint8_t> keep;                   // ... and the staged keep table
+    keep.swap(h->keep_staged);
+    c.keep = keep.empty() ? nullptr : keep.data();
+    for (int i = 0; i < 3; ++i) c.keep_codes[i] = h->keep_codes[i];
     if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
     const hqt_config& cf = h->cfg;
     if (c.levels == 2 && !cf.has_stage2) return fail(HQT_ERR_STATE, "handle was created without stage 2");
@@ -1685,6 +1700,24 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
         if (c.prefix_len > h->max_prefix)
             return fail(HQT_ERR_INVALID, "prefix_len=%d exceeds max_prefix=%d of this handle (hqt_set_max_prefix sizes the body workspace for the prefill's rows)", c.prefix_len, h->max_prefix);
         for (int i = 0; i < c.levels; ++i) if (!c.prefix[i]) return fail(HQT_ERR_INVALID, "prefix codes of level %d are NULL", i);
+    }
+    if (c.keep) {
+        if (c.with_prefix) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: the staged keep table was taken by a prefix entry point; a leading run of the mask is the prefix (hqt_sample / hqt_sample_l3 take the table)");
+        if (h->keep_B != B || h->keep_n != c.n_steps)
+            return fail(HQT_ERR_INVALID, "hqt_set_keep_mask staged a table of B=%d, n_steps=%d, this call has B=%d, n_steps=%d", h->keep_B, h->keep_n, B, c.n_steps);
+        static const char* const fname[2][3] = {{"force_top", "force_bot", ""}, {"force0", "force1", "force2"}};
+        for (int i = 0; i < c.levels; ++i)
+            if (c.feed[i]) return fail(HQT_ERR_INVALID, "%s together with a keep table is not built: put the forced codes into the kept codes (hqt_set_keep_mask)", fname[c.levels == 3][i]);
+        for (int i = 0; i < c.levels; ++i) if (!c.keep_codes[i]) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: kept codes of level %d are NULL", i);
+        // the leading run every row shares goes through the one-pass prefix prefill, where it is built (hqt_set_max_prefix; not text with three code levels)
+        int L = std::min(h->max_prefix, c.n_steps - 1);
+        if (cf.cond_type == HQT_COND_TEXT && c.levels == 3) L = 0;
+        for (int b = 0; b < B && L > 0; ++b) {
+            int run = 0;
+            while (run < L && c.keep[(size_t)b * c.n_steps + run]) ++run;
+            L = run;
+        }
+        c.prefix_len = L;
     }
     if (c.row_set) {                             // per-row settings replace the scalars of `opts`: those are neither checked nor part of the graph key
         if ((int)staged_rows != B) return fail(HQT_ERR_INVALID, "hqt_set_row_samplers staged %d rows, this call has B=%d", (int)staged_rows, B);
@@ -1716,6 +1749,8 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
             // both rows must draw the same code from the same (guided) logits: same settings, same Philox key
             if (c.row_set && memcmp(&c.row_set[p.pos_row], &c.row_set[p.neg_row], sizeof(hqt_row_sampler)))
                 return fail(HQT_ERR_INVALID, "guidance pair %d: rows %d and %d have different sampler settings in the staged row-sampler table", i, p.pos_row, p.neg_row);
+            if (c.keep && memcmp(c.keep + (size_t)p.pos_row * c.n_steps, c.keep + (size_t)p.neg_row * c.n_steps, (size_t)c.n_steps))
+                return fail(HQT_ERR_INVALID, "guidance pair %d: rows %d and %d have different rows in the staged keep table (both rows of a pair keep the same positions)", i, p.pos_row, p.neg_row);
             if (c.row_seeds && (c.row_seeds[p.pos_row] != c.row_seeds[p.neg_row] || c.row_offsets[p.pos_row] != c.row_offsets[p.neg_row]))
                 return fail(HQT_ERR_INVALID, "guidance pair %d: row_seeds / row_offsets give rows %d and %d different keys (both rows of a pair must draw with one key)", i, p.pos_row, p.neg_row);
         }
@@ -1737,7 +1772,7 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     static const size_t width[3] = {1, 4, 16};
     // the prefix goes into the handle's code buffers (outside any captured graph): the prefill's embedding, the embedding of position
     // prefix_len + 1 and the copies below read it there
-    for (int i = 0; i < (c.prefix_len ? c.levels : 0); ++i)
+    for (int i = 0; i < (c.prefix_len && !c.keep ? c.levels : 0); ++i)
         HIPCHK(launch_copy_prefix(c.prefix[i], codes[i], B, c.prefix_len, c.n_steps, (int)width[i], cf.vocab_top, c.st));
     CHK(sample_run(h, c));
     for (int i = 0; i < c.levels; ++i)
@@ -1774,6 +1809,21 @@ extern "C" int hqt_set_guidance(hqt_handle* h, int n_pairs, const hqt_guide_pair
     return HQT_OK;
 }
 
+extern "C" int hqt_set_keep_mask(hqt_handle* h, int B, int n_steps, const uint8_t* keep, const int64_t* const* codes) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    h->keep_staged.clear();
+    if (B == 0 || !keep) return HQT_OK;
+    if (B < 0 || B > h->cfg.max_batch) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: B=%d outside [0, max_batch=%d]", B, h->cfg.max_batch);
+    if (n_steps < 1 || n_steps > h->cfg.max_steps) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: n_steps=%d outside [1, max_steps=%d]", n_steps, h->cfg.max_steps);
+    if (!codes) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: codes is NULL");
+    const int levels = h->cfg.code_levels == 3 ? 3 : 2;
+    for (int i = 0; i < 3; ++i) h->keep_codes[i] = i < levels ? codes[i] : nullptr;      // a NULL level is refused by the call that takes the table
+    h->keep_B = B; h->keep_n = n_steps;
+    h->keep_staged.resize((size_t)B * n_steps);
+    for (size_t i = 0; i < h->keep_staged.size(); ++i) h->keep_staged[i] = keep[i] ? 1 : 0;
+    return HQT_OK;
+}
+
 extern "C" int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler* rows) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
     h->row_set_staged.clear();
@@ -1787,7 +1837,7 @@ extern "C" int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler*
 static int sample2(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts* opts, const float* noise, int prefix_len,
                    const int64_t* prefix_top, const int64_t* prefix_bot, const int64_t* force_top, const int64_t* force_bot,
                    float* logits_out, int64_t* out_top, int64_t* out_bot, void* stream) {
-    if (h && (!opts || !out_top || !out_bot)) { h->row_set_staged.clear(); h->logprob_staged = nullptr; h->guide_staged.clear(); }
+    if (h && (!opts || !out_top || !out_bot)) h->clear_staged();
     if (!h || !opts || !out_top || !out_bot) return fail(HQT_ERR_INVALID, "null argument");
     SampleCtx c = sample_ctx(2, B, opts, noise, logits_out);
     c.lv[0] = {opts->temperature_top, opts->top_k_top, opts->top_p_top};
@@ -1801,7 +1851,7 @@ static int sample2(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_o
 static int sample3(hqt_handle* h, int B, const int64_t* cond, const hqt_sample_opts_l3* opts, const float* noise, int prefix_len,
                    const int64_t* const* prefix, const int64_t* force0, const int64_t* force1, const int64_t* force2, float* logits_out,
                    int64_t* out0, int64_t* out1, int64_t* out2, void* stream) {
-    if (h && (!opts || !out0 || !out1 || !out2)) { h->row_set_staged.clear(); h->logprob_staged = nullptr; h->guide_staged.clear(); }
+    if (h && (!opts || !out0 || !out1 || !out2)) h->clear_staged();
     if (!h || !opts || !out0 || !out1 || !out2) return fail(HQT_ERR_INVALID, "null argument");
     SampleCtx c = sample_ctx(3, B, opts, noise, logits_out);
     for (int i = 0; i < 3; ++i) c.lv[i] = {opts->temperature[i], opts->top_k[i], opts->top_p[i]};
@@ -1848,10 +1898,10 @@ extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_
                          float* const* logits_out, void* stream) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
     // a staged table or buffer belongs to a sampling call: it must not wait for a later one behind this call
-    const bool staged = !h->row_set_staged.empty() || h->logprob_staged || !h->guide_staged.empty();
-    h->row_set_staged.clear(); h->logprob_staged = nullptr; h->guide_staged.clear();
+    const bool staged = !h->row_set_staged.empty() || h->logprob_staged || !h->guide_staged.empty() || !h->keep_staged.empty();
+    h->clear_staged();
     if (staged) return fail(HQT_ERR_STATE, "hqt_score: a row-sampler table, guidance pair table or log-probability buffer was staged on this handle (hqt_set_row_samplers / "
-                            "hqt_set_guidance / hqt_set_logprob_out): they belong to a sampling call and were cleared");
+                            "hqt_set_guidance / hqt_set_logprob_out / hqt_set_keep_mask): they belong to a sampling call and were cleared");
     if (!logprobs) return fail(HQT_ERR_INVALID, "hqt_score: logprobs is NULL");
     if (!codes) return fail(HQT_ERR_INVALID, "hqt_score: codes is NULL");
     if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
@@ -2013,11 +2063,11 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
     if ((c.row_seeds || c.row_offsets) && (!c.row_seeds || !c.row_offsets)) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
     // merged steps: per-row Philox keys and / or sampler settings (host arrays of B <= max_batch entries, through the pinned ring); a guided call: its pair
     // table, and ALWAYS the keys -- the implicit ones (seed, sample_offset + b) are built here, the negative row of every pair taking its positive row's
-    if (c.row_seeds || c.row_set || c.guide) {
+    if (c.row_seeds || c.row_set || c.guide || c.keep) {
         const int slot = h->rows_next;
         h->rows_next = (slot + 1) % hqt_handle::ROWS_RING;
         if (!h->rows_pinned[slot]) {
-            HIPCHK(hipHostMalloc((void**)&h->rows_pinned[slot], (size_t)h->cfg.max_batch * (sizeof(RowKey) + sizeof(RowSampler)) + h->guide_room() * sizeof(GuidePair), hipHostMallocDefault));
+            HIPCHK(hipHostMalloc((void**)&h->rows_pinned[slot], (size_t)h->cfg.max_batch * (sizeof(RowKey) + sizeof(RowSampler)) + h->guide_room() * sizeof(GuidePair) + (size_t)h->cfg.max_batch * h->cfg.max_steps, hipHostMallocDefault));
             HIPCHK(hipEventCreateWithFlags(&h->rows_ev[slot], hipEventDisableTiming));
         }
         if (h->rows_busy[slot]) HIPCHK(hipEventSynchronize(h->rows_ev[slot]));       // the copy that last read this buffer (4 calls ago) is done
@@ -2040,8 +2090,19 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
             memcpy(gp, c.guide, (size_t)c.n_guide * sizeof(GuidePair));
             HIPCHK(hipMemcpyAsync(h->guide, gp, (size_t)c.n_guide * sizeof(GuidePair), hipMemcpyHostToDevice, c.st));
         }
+        if (c.keep) {             // the mask, then the kept codes into the handle's code buffers (outside any captured graph): every level's embeddings, the
+                                  // samplers' guard and code_logprob read them there
+            unsigned char* km = reinterpret_cast<unsigned char*>(reinterpret_cast<GuidePair*>(reinterpret_cast<RowSampler*>(rk + h->cfg.max_batch) + h->cfg.max_batch) + h->guide_room());
+            memcpy(km, c.keep, (size_t)B * c.n_steps);
+            HIPCHK(hipMemcpyAsync(h->keep_mask, km, (size_t)B * c.n_steps, hipMemcpyHostToDevice, c.st));
+        }
         HIPCHK(hipEventRecord(h->rows_ev[slot], c.st));
         h->rows_busy[slot] = true;
+    }
+    if (c.keep) {
+        static const int width[3] = {1, 4, 16};
+        for (int i = 0; i < c.levels; ++i)
+            HIPCHK(launch_copy_kept(c.keep_codes[i], c.out[i], h->keep_mask, B, c.n_steps, width[i], cf.vocab_top, c.st));
     }
     if (!c.row_seeds && !c.guide) HIPCHK(launch_set_rows(h->rows, B, c.seed, c.sample_offset, c.st));
     int first = 0;
@@ -2099,6 +2160,8 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         key.push_back((uint64_t)((c.row_set ? 1 : 0) + (c.row_top_p ? 2 : 0)));
         // a pair table: that there is one (one more launch per sub-step) and its pair count (that launch's grid), never its rows or scales
         key.push_back((uint64_t)c.n_guide);
+        // a keep table: that there is one (the samplers' guard) and the length of its prefill (the positions the graph covers), never its values
+        key.push_back(c.keep ? (uint64_t)c.prefix_len + 1 : 0);
         if (!h->graph_exec || key != h->graph_key) {
             if (h->graph_exec) {                         // rare (options or test-only buffers changed): drain before destroying
                 HIPCHK(hipStreamSynchronize(c.st));

@@ -41,6 +41,8 @@ hipError_t launch_embed_step(const EmbedArgs& a, hipStream_t st);
 hipError_t launch_embed_prefix(const EmbedArgs& a, int rows, int stride, int row_off, int step_off, hipStream_t st);
 // dst[b, p < P, :] = src[b, p, :] for one code level (dst [B, n_steps, width], src [B, P, width]), clamped into [0, V)
 hipError_t launch_copy_prefix(const int64_t* src, int64_t* dst, int B, int P, int n_steps, int width, int V, hipStream_t st);
+// The masked sibling (hqt_set_keep_mask): dst[b, t, :] = clamp(src[b, t, :]) where keep[b * n_steps + t] != 0, both [B, n_steps, width]; other entries of dst are left alone
+hipError_t launch_copy_kept(const int64_t* src, int64_t* dst, const unsigned char* keep, int B, int n_steps, int width, int V, hipStream_t st);
 
 // text prompt: x[b * rows_per_sample + t, :] = tok_emb_txt[cond[b, t]] + pos_emb_txt[t]
 hipError_t launch_embed_text(const int64_t* cond, const float* tok, const float* pos, float* x, int B, int T, int D,
@@ -142,6 +144,9 @@ struct SamplerArgs {
     int row_lv_t, row_lv_k;
     int row_top_p;               // some row of the table uses top-p: the general kernel's LDS is sized for it (a launch-time choice, so a host-side one)
     int row_dispatch;            // set by launch_sampler: both kernels run over the pass and a workgroup leaves at once when its row belongs to the other one
+    // ---- kept positions (hqt_set_keep_mask): where keep[b * n_steps + step] != 0 the draw is spent and discarded -- `out` already holds the kept code, which is
+    //      left in place and is what the fused embedding looks up.  NULL: every position is drawn.
+    const unsigned char* keep;   // [B, n_steps], device
 };
 // Uniform call: one launch.  With a row table in a FAST pass whose vocabulary the register-resident kernel takes: that kernel, then the general one, each over
 // every row -- which rows are in which class is read on the device, so the launch sequence does not depend on the table's values.

@@ -154,6 +154,19 @@ hipError_t launch_copy_prefix(const int64_t* src, int64_t* dst, int B, int P, in
     return hipGetLastError();
 }
 
+// The kept codes of one level (hqt_set_keep_mask): both buffers are [B, n_steps, width]; entry i belongs to (sample, position) i / width
+__global__ __launch_bounds__(256) void copy_kept_kernel(const int64_t* src, int64_t* dst, const unsigned char* keep, long long n, int width, int V) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (keep[i / width]) dst[i] = clamp_idx(src[i], V);
+}
+hipError_t launch_copy_kept(const int64_t* src, int64_t* dst, const unsigned char* keep, int B, int n_steps, int width, int V, hipStream_t st) {
+    if (B < 1 || n_steps < 1 || width < 1 || !keep) return hipErrorInvalidValue;
+    const long long n = (long long)B * n_steps * width;
+    copy_kept_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(src, dst, keep, n, width, V);
+    return hipGetLastError();
+}
+
 // The T prompt rows of every sample, x[b * rows_per_sample + t] (rows_per_sample > T: a code prefix's rows follow, embed_prefix_kernel)
 __global__ __launch_bounds__(256) void embed_text_kernel(const int64_t* cond, const float* tok, const float* pos,
                                                          float* x, int T, int D, int vocab, int rows_per_sample) {
@@ -737,7 +750,9 @@ __global__ __launch_bounds__(NT, 8) void sampler_kernel(SamplerArgs a, int n2) {
     if (tid == 0) {
         for (int w = 1; w < NT / 64; ++w)
             if (redf[w] > best || (redf[w] == best && redi[w] < besti)) { best = redf[w]; besti = redi[w]; }
-        a.out[a.out_stride > 0 ? ((long long)b * a.n_steps + step) * a.out_stride + a.out_slot : ((long long)b * a.n_steps + step) * a.slots + slot] = (int64_t)besti;
+        int64_t* const dst = a.out + (a.out_stride > 0 ? ((long long)b * a.n_steps + step) * a.out_stride + a.out_slot : ((long long)b * a.n_steps + step) * a.slots + slot);
+        if (a.keep && a.keep[(long long)b * a.n_steps + step]) besti = (int)*dst;      // a kept position: the draw is discarded, the code (clamped when it was stored) stays
+        else *dst = (int64_t)besti;
         if (a.emb_tok) sel[0] = a.emb_feed ? (int)clamp_idx(a.emb_feed[((long long)b * a.n_steps + step) * a.slots + slot], a.V) : besti;
     }
     if (!a.emb_tok) return;                              // workgroup-uniform
@@ -855,7 +870,9 @@ __global__ __launch_bounds__(256) void sampler_plain_fast_kernel(SamplerArgs a) 
     if (tid == 0) {
         for (int w = 1; w < 4; ++w)
             if (redf[w] > best || (redf[w] == best && redi[w] < besti)) { best = redf[w]; besti = redi[w]; }
-        a.out[a.out_stride > 0 ? ((long long)b * a.n_steps + step) * a.out_stride + a.out_slot : ((long long)b * a.n_steps + step) * a.slots + slot] = (int64_t)besti;
+        int64_t* const dst = a.out + (a.out_stride > 0 ? ((long long)b * a.n_steps + step) * a.out_stride + a.out_slot : ((long long)b * a.n_steps + step) * a.slots + slot);
+        if (a.keep && a.keep[(long long)b * a.n_steps + step]) besti = (int)*dst;      // a kept position: the draw is discarded, the code (clamped when it was stored) stays
+        else *dst = (int64_t)besti;
         if (a.emb_tok) redi[0] = a.emb_feed ? (int)clamp_idx(a.emb_feed[((long long)b * a.n_steps + step) * a.slots + slot], a.V) : besti;
     }
     if (!a.emb_tok) return;                              // workgroup-uniform

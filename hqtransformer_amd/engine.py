@@ -155,6 +155,53 @@ def check_prefix(s2: Stage2Spec, batch: int, n_steps: int, prefix, max_prefix: O
     return levels
 
 
+def keep_leading_run(mask, max_prefix: int, text_l3: bool = False) -> int:
+    """``L`` of a keep table (``hqt_set_keep_mask``): the smallest count of leading kept positions over the rows of ``mask`` [B, n], clipped to
+    min(``max_prefix`` of the engine, n - 1), and 0 where the prefix prefill is not built (``text_l3``: text conditioning with three code levels).
+    Positions < L go through the one-pass prefix prefill; the library applies the same rule to the table it is given."""
+    m = np.asarray(torch.as_tensor(mask).cpu() if isinstance(mask, torch.Tensor) else mask).astype(bool)
+    if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] < 1:
+        raise ValueError(f'keep mask: expected shape (B, n), got {m.shape}')
+    if text_l3:
+        return 0
+    run = np.where(m.all(axis=1), m.shape[1], np.argmin(m, axis=1))      # per row: index of its first 0
+    return int(max(0, min(int(run.min()), int(max_prefix), m.shape[1] - 1)))
+
+
+def check_keep(s2: Stage2Spec, batch: int, n_steps: int, keep) -> Optional[tuple]:
+    """A keep table checked on the host, before any engine is built or touched: ``keep = (mask, codes)``, mask bool [B, n] (1 = keep every level of that
+    position), codes the code levels as one list, coarse to fine, int64 [B, n], [B, n, 4][, [B, n, 16]], read where the mask is set; host codes inside the
+    vocabulary there (IndexError otherwise, as nn.Embedding raises in the reference; device tensors are checked once by the engine).  Returns
+    (mask as a contiguous uint8 numpy array, the levels as tensors); None stays None."""
+    if keep is None:
+        return None
+    if not isinstance(keep, (list, tuple)) or len(keep) != 2:
+        raise ValueError('keep: expected (mask [B, n], codes: the code levels as one list)')
+    mask, codes = keep
+    m = torch.as_tensor(mask).cpu()
+    if tuple(m.shape) != (int(batch), int(n_steps)):
+        raise ValueError(f'keep mask: expected shape {(int(batch), int(n_steps))}, got {tuple(m.shape)}')
+    if m.dtype.is_floating_point:
+        raise ValueError(f'keep mask: expected bool (or 0 / 1 integers), got {m.dtype}')
+    m = np.ascontiguousarray((m != 0).numpy().astype(np.uint8))
+    L = s2.levels
+    if not isinstance(codes, (list, tuple)) or len(codes) != L:
+        raise ValueError(f'kept codes: expected the {L} code levels as one list, coarse to fine')
+    levels = [torch.as_tensor(c) for c in codes]
+    for l, t in enumerate(levels):
+        want = (int(batch), int(n_steps)) + ((4 ** l,) if l else ())
+        if tuple(t.shape) != want:
+            raise ValueError(f'kept codes[{l}]: expected shape {want}, got {tuple(t.shape)}')
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError(f'kept codes[{l}]: expected integer codes, got {t.dtype}')
+        if not t.is_cuda and m.any():
+            sel = t[torch.from_numpy(m.astype(bool))]
+            lo, hi = int(sel.min()), int(sel.max())
+            if lo < 0 or hi >= s2.vocab_top:
+                raise IndexError(f'kept codes[{l}]: index out of range (values span [{lo}, {hi}], table has {s2.vocab_top} rows)')
+    return m, levels
+
+
 def check_score_codes(s2: Stage2Spec, codes, what: str = 'one-pass scoring') -> int:
     """Codes for ``Engine.score`` checked on the host, before any engine is built or touched: the model's code levels as one list, coarse to fine, int64 [B, n],
     [B, n, 4][, [B, n, 16]]; host tensors inside the vocabulary (IndexError otherwise; device tensors are checked once by the engine).  ValueError for the heads
@@ -390,13 +437,22 @@ class Engine:
     def _sample_levels(self, levels: int, batch: int, cond, n_steps: int, *, precision, top_k, top_p, temperature, noise, seed, sample_offset,
                        force: Sequence[Optional[torch.Tensor]], out: Optional[Sequence[torch.Tensor]], return_logits, use_graph,
                        row_seeds, row_offsets, row_samplers=None, prefix=None,
-                       return_logprobs=False, guidance=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+                       return_logprobs=False, guidance=None, keep=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
         """Returns (codes [B, n], [B, n, 4][, [B, n, 16]], logits [n, draws, B, V] or None, logprobs [B, n, draws] or None)."""
         dev = self.device
         B, V, L = int(batch), self.s2.vocab_top, int(levels)
         # (a text engine was asked for the shared prompt + prefix prefill when it was built with max_prefix; without it P > max_prefix = 0 refuses)
         prefix = check_prefix(self.s2, B, n_steps, prefix, self.max_prefix, text_prefix=True)
         P = 0 if prefix is None else int(prefix[0].shape[1])
+        keep = check_keep(self.s2, B, n_steps, keep)
+        if keep is not None:
+            if prefix is not None:
+                raise ValueError('keep and prefix: a prefix is a leading run of the keep mask -- put it there')
+            for f, what in zip(force, _FORCE_NAMES[L]):
+                if f is not None:
+                    raise ValueError(f'{what} together with keep is not built: put the forced codes into the kept codes')
+            # the leading run every row shares runs as the prefix prefill; its rows of the logits / log-probabilities are not written, as with a prefix
+            P = keep_leading_run(keep[0], self.max_prefix, text_l3=self.s2.cond == 2 and L == 3)
         draws = (4 ** L - 1) // 3                   # one draw per code of a position: 1 + 4 (+ 16)
         shapes = [(B, n_steps) + ((4 ** l,) if l else ()) for l in range(L)]
         o = hqt_sample_opts() if L == 2 else hqt_sample_opts_l3()
@@ -417,6 +473,17 @@ class Engine:
         cond = self._prep_cond(cond, B)
         noise = self._prep(noise, (n_steps, draws, B, V), torch.float32, 'noise')
         force = [self._prep(f, shp, torch.int64, what, V) for f, shp, what in zip(force, shapes, _FORCE_NAMES[L])]
+        if keep is not None:
+            sel = torch.from_numpy(keep[0].astype(bool))
+
+            def kept(t, shp, what):              # ids are checked where they are read: under the mask
+                if t.is_cuda and sel.any():
+                    try:                         # the whole tensor first: a tensor that passes is remembered, and a steady stream of calls never synchronises
+                        self._check_index(t, V, what)
+                    except IndexError:
+                        self._check_index(t[sel.to(t.device)], V, what)
+                return self._prep(t, shp, torch.int64, what)
+            keep = (keep[0], [kept(t, shp, f'kept codes[{l}]') for l, (t, shp) in enumerate(zip(keep[1], shapes))])
         if prefix is not None:
             prefix = [self._prep(p, (B, P) + shp[2:], torch.int64, f'prefix[{l}]', V) for l, (p, shp) in enumerate(zip(prefix, shapes))]
         if out is None:
@@ -430,7 +497,7 @@ class Engine:
         if return_logprobs:
             logprobs = (torch.full((B, n_steps, draws), float('nan'), dtype=torch.float32, device=dev) if P
                         else torch.empty((B, n_steps, draws), dtype=torch.float32, device=dev))
-        if P:
+        if prefix is not None:
             entry = self.lib.hqt_sample_prefix if L == 2 else self.lib.hqt_sample_prefix_l3
 
             def fn(h, b, cnd, opts, nz, *rest):
@@ -445,10 +512,13 @@ class Engine:
                 _lib.check(self.lib.hqt_set_logprob_out(self.h, _ptr(logprobs)))
             if pairs is not None:                   # ... and so is the pair table (copied by the library)
                 _lib.check(self.lib.hqt_set_guidance(self.h, len(pairs), pairs))
+            if keep is not None:                    # ... and the keep table (the mask is copied; the codes are read by the call below)
+                kp = (C.c_void_p * 3)(*[_ptr(t) for t in keep[1]])
+                _lib.check(self.lib.hqt_set_keep_mask(self.h, B, int(n_steps), keep[0].ctypes.data_as(C.c_void_p), kp))
             _lib.check(fn(self.h, B, _ptr(cond), C.byref(o), _ptr(noise), *map(_ptr, force), _ptr(logits), *map(_ptr, outs), C.c_void_p(stream)))
             self._note_split(precision, stream, ar_rows=B)        # every head runs persistently (run_position)
         # inputs must outlive the asynchronous launches
-        self._keep = (cond, noise, force, rows, prefix)     # (the row-sampler table was copied by hqt_set_row_samplers)
+        self._keep = (cond, noise, force, rows, prefix, keep)     # (the row-sampler table was copied by hqt_set_row_samplers)
         self._trust(*outs, bound=max(self.s2.vocab_top, self.s2.vocab_bot))     # the sampler only writes ids inside the vocabulary
         return outs, logits, logprobs
 
@@ -460,7 +530,7 @@ class Engine:
                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
                row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
-               return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None):
+               return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None, keep: Optional[tuple] = None):
         """Two-level sampling: returns (codes_top [B, n], codes_bot [B, n, 4][, logits [n, 5, B, V]][, logprobs [B, n, 5]]).
         ``return_logprobs``: fp32 log-probability of every code the call feeds forward -- the drawn one, or the forced one where ``force_*`` is
         given -- under the raw logits of its draw (T = 1, no cut-off: ``hqt_set_logprob_out``), appended last; with a prefix the positions < P are NaN.
@@ -477,13 +547,18 @@ class Engine:
         (``hqt_set_guidance``) -- the two rows of a pair are one image under two conditions (``cond[pos_row]`` / ``cond[neg_row]``); every code of both
         is drawn from ``l_pos + (scale - 1) (l_pos - l_neg)`` with the positive row's Philox key, so both rows return the same codes.  ``batch``
         counts all rows; ``noise``, ``force_*`` and ``prefix`` must agree in the two rows of a pair; returned logits hold the guided row in both,
-        returned log-probabilities score the code under it.  Rows outside every pair draw what they draw without ``guidance``."""
+        returned log-probabilities score the code under it.  Rows outside every pair draw what they draw without ``guidance``.
+        ``keep`` = (mask bool [B, n], codes [top [B, n], bot [B, n, 4]]): any positions of the grid held fixed (``hqt_set_keep_mask``) -- where the mask is set
+        every level of the position is the given code, returned and fed forward; every other position is drawn as a plain call draws it whose earlier
+        positions had produced the same codes.  The leading run all rows share, up to ``max_prefix`` of this engine, runs as the prefix prefill (its logits
+        rows are zeros, its log-probabilities NaN, as with ``prefix``); every other kept position costs a decode step.  Not together with ``force_*`` or
+        ``prefix``; the two rows of a guided pair keep the same positions."""
         if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
             raise ValueError('out: expected a pair (codes_top [B, n_steps], codes_bot [B, n_steps, 4])')
         outs, logits, logprobs = self._sample_levels(2, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(force_top, force_bot), out=out,
                                            return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
-                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance)
+                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance, keep=keep)
         return (outs[0], outs[1]) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
 
     def sample3(self, batch: int, cond: Optional[torch.Tensor], n_steps: int, *, precision: int = PRECISION_FAST,
@@ -492,14 +567,15 @@ class Engine:
                 sample_offset: int = 0, force: Optional[Sequence[torch.Tensor]] = None, return_logits: bool = False,
                 use_graph: bool = True, row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
                 row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
-                return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None):
+                return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None, keep: Optional[tuple] = None):
         """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]][, logprobs [B, n, 21]]); ``row_samplers``,
         ``return_logprobs`` and ``guidance`` (three scales per pair) as in ``sample``;
-        ``prefix`` = [[B, P], [B, P, 4], [B, P, 16]]: completion, as in ``sample`` (``hqt_sample_prefix_l3``)."""
+        ``prefix`` = [[B, P], [B, P, 4], [B, P, 16]]: completion, as in ``sample`` (``hqt_sample_prefix_l3``);
+        ``keep`` = (mask [B, n], [[B, n], [B, n, 4], [B, n, 16]]): kept positions, as in ``sample``."""
         outs, logits, logprobs = self._sample_levels(3, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(None,) * 3 if force is None else force,
                                            out=None, return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
-                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance)
+                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance, keep=keep)
         return tuple(outs) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
 
     def score(self, batch: int, cond: Optional[torch.Tensor], codes: Sequence[torch.Tensor], *, precision: int = PRECISION_FAST,

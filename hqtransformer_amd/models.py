@@ -71,6 +71,8 @@ class _Stage:
             self._engine.close()                     # closes its lanes first
         self._engine = None
         self._lanes = {}
+        for other in self.__dict__.get('_scaled', {}).values():      # HQVAEStage1.at_resolution: engines over the same weights
+            other._drop_engine()
 
     def _lane(self, base: Engine, lane: int) -> Engine:
         """Lane 0 is the engine that owns the weights; lane k > 0 is a clone sharing them (own workspace), created on
@@ -192,6 +194,27 @@ class HQVAEStage1(_Stage):
 
     def _ignored(self, key: str) -> bool:
         return stage1_is_ignored(key)
+
+    def at_resolution(self, resolution: int) -> 'HQVAEStage1':
+        """This stage 1 over images of another size: the SAME weights (the decoder and the encoder are convolutions and attention, none of whose
+        tensors depends on the image size) under a spec whose ``resolution`` and ``attn_resolutions`` are scaled by ``resolution / spec.resolution``,
+        so that attention sits at the layers it sits at.  A second engine, built on first use and kept; ``pipeline.sample_canvas`` decodes its
+        canvas with it.  ValueError unless the scaled sizes are integers."""
+        R, base = int(resolution), self.spec.resolution
+        if R == base:
+            return self
+        if R < 1 or any((a * R) % base for a in self.spec.attn_resolutions) or (self.spec.z_res * R) % base:
+            raise ValueError(f'at_resolution({R}): the code grid and attn_resolutions {self.spec.attn_resolutions} of a resolution-{base} spec do not scale to integers')
+        scaled = self.__dict__.setdefault('_scaled', {})
+        if R not in scaled:
+            import dataclasses
+            other = HQVAEStage1.__new__(HQVAEStage1)
+            other.__dict__.update(_shapes=self._shapes, _w=self._w, _device=self._device, _engine=None, _dirty=True, _lanes={},
+                                  spec=dataclasses.replace(self.spec, resolution=R, attn_resolutions=[a * R // base for a in self.spec.attn_resolutions]),
+                                  precision=self.precision, bottom_window=self.bottom_window)
+            scaled[R] = other
+        scaled[R]._device, scaled[R].precision = self._device, self.precision
+        return scaled[R]
 
     def from_ckpt(self, path: str, strict: bool = True) -> None:       # generator.py:389-395: keys lose their first 10 characters
         super().from_ckpt(path, strict=strict, strip_prefix=10)

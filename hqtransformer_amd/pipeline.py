@@ -241,6 +241,112 @@ def complete_images(model, images: torch.Tensor, keep_rows: int, cond=None, enco
     return decode_codes(model.stage1, codes, decode_precision), codes
 
 
+def box_keep_mask(K: int, box) -> torch.Tensor:
+    """bool [K K]: the top positions OUTSIDE ``box = (r0, r1, c0, c1)`` (half-open, in cells of the K x K top grid), raster order -- the keep mask of one
+    image whose box is drawn again.  ValueError unless 0 <= r0 < r1 <= K and 0 <= c0 < c1 <= K."""
+    r0, r1, c0, c1 = (int(v) for v in box)
+    if not (0 <= r0 < r1 <= K and 0 <= c0 < c1 <= K):
+        raise ValueError(f'box={(r0, r1, c0, c1)}: expected (r0, r1, c0, c1) with 0 <= r0 < r1 <= {K} and 0 <= c0 < c1 <= {K} (half-open, top-grid cells)')
+    keep = torch.ones((K, K), dtype=torch.bool)
+    keep[r0:r1, c0:c1] = False
+    return keep.reshape(-1)
+
+
+def regenerate_region(model, images: torch.Tensor, box, cond=None, encode_precision: Optional[str] = None,
+                      decode_precision: Optional[str] = None, **sampler) -> Tuple[torch.Tensor, list]:
+    """Draw a box of every image again and keep everything around it: ``images`` fp32 [B, 3, R, R] in [-1, 1] -> ``stage1`` codes -> one sampler call
+    over all ``top_resolution ** 2`` positions that keeps every cell outside ``box = (r0, r1, c0, c1)`` (half-open, in top-grid cells) on every code
+    level (``keep_mask`` / ``kept_codes`` of the samplers) and draws the inside, each position given everything before it in raster order -- the kept
+    cells to the right of and below the box are not seen by the draws, as in any raster-order model -> ``decode_codes``.  ``cond`` and ``sampler`` as in
+    ``complete_images``.  Returns ``(pixels fp32 [B, 3, R, R] in [0, 1], codes)``, the codes in the sampler's layout.  What is claimed is the mechanism,
+    not the quality of the seam."""
+    grids = list(model.stage1.code_grids(images, precision=encode_precision))
+    B, K = int(images.shape[0]), int(grids[0].shape[-1])
+    mask = box_keep_mask(K, box).unsqueeze(0).expand(B, K * K)
+    if model.stage2.use_txt_cond and model.stage2.spec.levels == 2:
+        sampler['text_prefix'] = True
+    codes = sample_codes(model.stage2, B, cond, max_seq_len=K * K, keep_mask=mask, kept_codes=grids_to_sequences(grids), **sampler)
+    return decode_codes(model.stage1, codes, decode_precision), codes
+
+
+def canvas_windows(G: int, w: int, s: int) -> list:
+    """Offsets ``(oy, ox)`` of the w x w windows that tile a G x G canvas with stride s, over {0, s, ..., G - w} squared, in raster order.
+    ValueError unless 1 <= s < w <= G and (G - w) % s == 0."""
+    G, w, s = int(G), int(w), int(s)
+    if not (1 <= s < w <= G) or (G - w) % s:
+        raise ValueError(f'canvas_windows(G={G}, w={w}, s={s}): expected 1 <= s < w <= G and (G - w) % s == 0')
+    steps = range(0, G - w + 1, s)
+    return [(oy, ox) for oy in steps for ox in steps]
+
+
+def canvas_keep_masks(G: int, w: int, s: int) -> list:
+    """Per window of ``canvas_windows``, in its order: ``(oy, ox, keep bool [w, w])`` with ``keep`` the cells of the window that earlier windows filled."""
+    filled = torch.zeros((G, G), dtype=torch.bool)
+    out = []
+    for oy, ox in canvas_windows(G, w, s):
+        out.append((oy, ox, filled[oy:oy + w, ox:ox + w].clone()))
+        filled[oy:oy + w, ox:ox + w] = True
+    return out
+
+
+def sample_canvas(model, cond, grid: int, stride: int, seed: int = 0, decode: bool = True, num_candidates: Optional[int] = None,
+                  decode_precision: Optional[str] = None, **sampler) -> Tuple[list, Optional[torch.Tensor]]:
+    """Sample a code canvas larger than the trained grid with a sliding window: the model's w x w top grid (w w = ctx_len_img) moves over a
+    ``grid`` x ``grid`` canvas with ``stride`` (``canvas_windows``); window number k is ONE sampler call seeded ``seed + k`` whose keep mask is the
+    cells of the window that earlier windows filled (``keep_mask`` / ``kept_codes`` of the samplers), and the cells it draws are written back to the canvas.
+    ``cond``: as in ``sampling_ihqgpt``, the same for every window; ``num_candidates``: images B (default: one per entry of ``cond``); ``sampler``: further
+    keywords of the sampler.  Returns ``(grids, pixels)``: the canvas code grids int64 [B, G, G], [B, 2 G, 2 G][, [B, 4 G, 4 G]] and, with ``decode``,
+    pixels fp32 [B, 3, R G / w, R G / w] in [0, 1] from ``stage1.at_resolution`` (the same weights under a spec scaled by G / w: a second engine, built
+    on first use), else None.  Square canvases only.  The model was trained on w x w grids with absolute positions: what is claimed is the mechanism --
+    every window is an ordinary masked call that a plain forced call replays --, not the quality of the picture."""
+    s2 = model.stage2.spec
+    w = int(round(s2.ctx_len_img ** 0.5))
+    if w * w != s2.ctx_len_img:
+        raise ValueError(f'ctx_len_img={s2.ctx_len_img} is not a square grid')
+    G, L = int(grid), s2.levels
+    plan = canvas_keep_masks(G, w, int(stride))
+    if num_candidates is None:
+        num_candidates = 1 if isinstance(cond, int) or cond is None else int(torch.as_tensor(cond).shape[0])
+    B = int(num_candidates)
+    dev = model.stage2._device
+    canvas = [torch.zeros((B, G << l, G << l), dtype=torch.int64, device=dev) for l in range(L)]
+    for k, (oy, ox, keep) in enumerate(plan):
+        window = [c[:, oy << l:(oy + w) << l, ox << l:(ox + w) << l] for l, c in enumerate(canvas)]
+        codes = sample_codes(model.stage2, B, cond, seed=int(seed) + k, max_seq_len=w * w, keep_mask=keep.reshape(1, -1).expand(B, w * w),
+                             kept_codes=grids_to_sequences(window), **sampler)
+        for dst, g in zip(window, rearrange_levels(codes, w)):
+            dst.copy_(g)                                 # the kept cells come back verbatim: only the cells this window owns change
+    pixels = None
+    if decode:
+        R = model.stage1.spec.resolution
+        if (R * G) % w:
+            raise ValueError(f'a {G} x {G} canvas of a model with resolution {R} over a {w} x {w} grid has no integer resolution')
+        pixels = (0.5 * model.stage1.at_resolution(R * G // w).decode_code(canvas, precision=decode_precision) + 0.5).clamp(0, 1)
+    return canvas, pixels
+
+
+def step_keep_table(levels: int, sizes, n: int, sample_kws) -> Tuple[torch.Tensor, list]:
+    """Steps of a pass with mixed prefixes -> its keep table: step i's ``prefix_codes`` (``sample_kws[i]``; none: nothing kept) become its ``sizes[i]`` rows
+    of ``(mask bool [N, n], codes [N, n], [N, n, 4][, [N, n, 16]])`` -- row r of a step with a prefix of P positions keeps its first P positions.  The result is
+    ``keep_mask=`` / ``kept_codes=`` of the samplers; the leading run all rows share, i.e. the shortest prefix, is the pass's one prefill."""
+    N = sum(int(b) for b in sizes)
+    mask = torch.zeros((N, int(n)), dtype=torch.bool)
+    where = next((torch.as_tensor(kw['prefix_codes'][0]).device for kw in sample_kws if kw.get('prefix_codes') is not None), torch.device('cpu'))
+    codes = [torch.zeros((N, int(n)) + ((4 ** l,) if l else ()), dtype=torch.int64, device=where) for l in range(int(levels))]
+    lo = 0
+    for b, kw in zip(sizes, sample_kws):
+        prefix = kw.get('prefix_codes')
+        if prefix is not None:
+            P = int(torch.as_tensor(prefix[0]).shape[-1])
+            if len(prefix) != int(levels) or not 1 <= P < int(n):
+                raise ValueError(f'prefix_codes: expected the {int(levels)} code levels with 1 <= P <= {int(n) - 1} positions')
+            mask[lo:lo + int(b), :P] = True
+            for c, p in zip(codes, prefix):
+                c[lo:lo + int(b), :P] = torch.as_tensor(p).to(where, torch.int64)
+        lo += int(b)
+    return mask, codes
+
+
 def _public(codes: list) -> tuple:
     return codes[0], (codes[1] if len(codes) == 2 else codes[1:])
 
@@ -288,20 +394,21 @@ class _Step(NamedTuple):
         prefix = self.sample_kw.get('prefix_codes')
         return 0 if prefix is None else int(torch.as_tensor(prefix[0]).shape[-1])
 
-    def settings(self, mixed_samplers: bool = False) -> tuple:
+    def settings(self, mixed_samplers: bool = False, mixed_prefixes: bool = False) -> tuple:
         """What the steps of one merged pass must share (``mixed_samplers``: all but the sampler settings, which then travel per row).
-        Prefix codes belong to a step's rows like its class ids; their LENGTH is shared (a pass has one prefill)."""
+        Prefix codes belong to a step's rows like its class ids; their LENGTH is shared (a pass has one prefill) unless ``mixed_prefixes``:
+        every step's prefix is then its rows of the pass's keep table."""
         free = ('sample_offset', 'prefix_codes', 'return_logprobs') + GUIDANCE_KEYS + (SAMPLER_KEYS if mixed_samplers else ())
-        return (self.max_seq_len, self.use_fp16, self.precision, self.clamp01, self.use_graph, self.prefix_len(),
+        return (self.max_seq_len, self.use_fp16, self.precision, self.clamp01, self.use_graph, 0 if mixed_prefixes else self.prefix_len(),
                 {k: v for k, v in self.sample_kw.items() if k not in free})
 
 
-def check_mergeable(step: _Step, first: _Step, mixed_samplers: bool = False) -> None:
+def check_mergeable(step: _Step, first: _Step, mixed_samplers: bool = False, mixed_prefixes: bool = False) -> None:
     """ValueError unless ``step`` can join the pass that ``first`` opened."""
-    if step.prefix_len() != first.prefix_len():
+    if not mixed_prefixes and step.prefix_len() != first.prefix_len():
         raise ValueError(f'steps merged into one pass must share the prefix length: this step has P={step.prefix_len()}, the pass P={first.prefix_len()} '
                          '(a merged pass has one prefill; flush() first to start a new pass)')
-    if not _same(step.settings(mixed_samplers), first.settings(mixed_samplers)):
+    if not _same(step.settings(mixed_samplers, mixed_prefixes), first.settings(mixed_samplers, mixed_prefixes)):
         if mixed_samplers:
             raise ValueError('steps of a mixed pass may differ in temperature, top-k and top-p only: max_seq_len, precision and every other '
                              'setting must match (flush() first to start a new pass)')
@@ -323,7 +430,7 @@ class Pending:
 
 class InflightSampler:
     def __init__(self, model, lanes: int = 3, device: Optional[torch.device] = None, merge: int = 1, record_phases: bool = False,
-                 ar_high_priority: bool = False, mixed_samplers: bool = False):
+                 ar_high_priority: bool = False, mixed_samplers: bool = False, mixed_prefixes: bool = False):
         if lanes < 1 or merge < 1:
             raise ValueError('lanes and merge must be >= 1')
         self.model = model
@@ -331,6 +438,9 @@ class InflightSampler:
         # merged steps may differ in top_k* / top_p* / softmax_temperature: every pass stages a row table on its lane (always, also when its steps
         # happen to agree: the launch sequence, hence the captured graph, then never depends on what was queued)
         self.mixed_samplers = bool(mixed_samplers)
+        # merged steps may differ in the length of their prefix (none included): every pass stages a keep table on its lane (hqt_set_keep_mask; always,
+        # as with the row table) whose rows keep their own step's prefix; the shortest prefix is the pass's one prefill, the rest are decode steps
+        self.mixed_prefixes = bool(mixed_prefixes)
         self.record_phases = bool(record_phases)     # merged passes: (AR start, AR end, decode end) events per pass, appended to phase_log
         self.phase_log: list = []
         self._queue: list = []
@@ -367,7 +477,7 @@ class InflightSampler:
             # checked HERE, before the step is queued: a mismatch raises without touching the queue (every Pending already handed out stays valid)
             check_guided_step(self.model.stage2, num_candidates, sample_kw)
             if self._queue:
-                check_mergeable(step, self._queue[0], self.mixed_samplers)
+                check_mergeable(step, self._queue[0], self.mixed_samplers, self.mixed_prefixes)
             self._queue.append(step)
             if len(self._queue) >= self.merge:
                 self.flush()
@@ -389,7 +499,11 @@ class InflightSampler:
         want_lp = any(e.wants_logprobs() for e in q)
         if want_lp:
             kw['return_logprobs'] = True
-        if ref.prefix_len():                         # every step's own prefix rows, in step order (one P: check_mergeable)
+        if self.mixed_prefixes:                      # every step's own prefix as its rows of the keep table (the negative rows repeat their positive ones)
+            mask, kept = step_keep_table(self.model.stage2.spec.levels, sizes, ref.max_seq_len, [e.sample_kw for e in q])
+            kw['keep_mask'] = torch.cat([mask, mask[mirrors]]) if mirrors else mask
+            kw['kept_codes'] = [torch.cat([c, c[mirrors]]) for c in kept] if mirrors else kept
+        elif ref.prefix_len():                       # every step's own prefix rows, in step order (one P: check_mergeable)
             where = torch.as_tensor(ref.sample_kw['prefix_codes'][0]).device       # device prefixes stay there: no copy back to the host
             kw['prefix_codes'] = [torch.cat([torch.as_tensor(e.sample_kw['prefix_codes'][l]).to(where, torch.int64) for e in q])
                                   for l in range(len(ref.sample_kw['prefix_codes']))]

@@ -10,7 +10,7 @@ from typing import List, Optional
 import torch
 
 from ._lib import PRECISION_EXACT, PRECISION_FAST, PRECISIONS
-from .engine import check_prefix
+from .engine import check_keep, check_prefix, keep_leading_run
 from .text import pad_caption
 
 
@@ -155,7 +155,9 @@ def sampling_ihqgpt(model,
                     return_logprobs: bool = False,
                     guidance_scale=None,
                     neg_cond=None,
-                    guidance=None):
+                    guidance=None,
+                    keep_mask=None,
+                    kept_codes=None):
     """Returns ``(codes_top int64 [B, max_seq_len], codes_bot int64 [B, max_seq_len, 4])`` on the model's GPU; ``return_logprobs=True`` appends
     ``logprobs`` fp32 [B, max_seq_len, 5]: the log-probability of every code the call feeds forward (the drawn one; the given one where
     ``given_top_code`` forces the top level) under the raw logits of its draw -- temperature 1, no cut-off, so always finite; draw order top,
@@ -190,6 +192,13 @@ def sampling_ihqgpt(model,
     returned, so every result keeps its documented shape.  ValueError for an unconditional model.  The reference trains without condition dropout:
     what is claimed is the arithmetic, not an effect on image quality.  ``guidance`` instead of the two: a ready pair table
     ``[(pos_row, neg_row, scales), ...]`` over the B rows as given (``Engine.sample``; ``InflightSampler`` lays merged steps out this way).
+    ``keep_mask`` bool [B, max_seq_len] with ``kept_codes`` = ``[top [B, max_seq_len], bot [B, max_seq_len, 4]]``: any positions of the grid held fixed
+    (``hqt_set_keep_mask``) -- where the mask is set every level of the position is the given code, returned and fed forward; every other position is
+    drawn as a free run would draw it had its earlier positions produced the same codes.  Rows may keep different positions: prefixes of different
+    lengths, columns, everything outside a box.  The leading run all rows share goes through the one-pass prefill like ``prefix_codes`` (text
+    conditioning: with ``text_prefix=True``; otherwise, and for every later kept position, a decode step each); log-probabilities of that run are
+    NaN.  IndexError for a kept code outside the vocabulary.  Not together with ``given_top_code`` or ``prefix_codes``; with ``guidance_scale`` the
+    two are given for B rows and repeated for the negative half.  Only the mechanism is claimed, not what it does to image quality.
 
     The call is asynchronous and does not read the device's flags: 'split' passes above 256 rows SATURATE activations outside the fp16 range and
     only flag them, and a persistent FAST launch (up to 64 samples) that could not finish on a shared GPU only marks the handle -- call
@@ -201,11 +210,13 @@ def sampling_ihqgpt(model,
     if rows != B:                                    # the negative half repeats every per-row input of the positive one
         noise, prefix_codes = _twice(noise, 2), None if prefix_codes is None else [_twice(p) for p in prefix_codes]
         row_seeds, row_offsets, row_samplers = _twice_rows(row_seeds), _twice_rows(row_offsets), _twice_rows(row_samplers)
+        keep_mask, kept_codes = _twice(keep_mask), None if kept_codes is None else [_twice(c) for c in kept_codes]
         if given_top_code is not None:
             g = torch.as_tensor(given_top_code)
             given_top_code = g if g.dim() == 1 or g.shape[0] == 1 else _twice(g)
         B = rows
     prefix = check_prefix(spec, B, max_seq_len, prefix_codes, text_prefix=text_prefix)       # refused here, before an engine is built
+    kept = _check_kept(spec, B, max_seq_len, keep_mask, kept_codes, prefix, given_top_code)
     force_top = None
     if given_top_code is not None and spec.depth_decoding == 'bidirectional':
         # the reference passes given_top_code to the 'parallel' head only and silently ignores it here (hierarchical_ar.py:451-479)
@@ -217,14 +228,14 @@ def sampling_ihqgpt(model,
         if force_top.shape[0] != B:
             force_top = force_top.repeat(B, 1)
         force_top = force_top[:, :max_seq_len]
-    eng = model.engine(B, max_seq_len, lane, max_prefix=_prefix_room(spec, prefix))
+    eng = model.engine(B, max_seq_len, lane, max_prefix=_prefix_room(spec, prefix) or _keep_room(spec, kept, text_prefix))
     if seed is None and noise is None:
         seed = _seed_from_torch()
     out = eng.sample(B, cond, max_seq_len, precision=_precision(precision, use_fp16),
                      top_k=(top_k_top, top_k_bot), top_p=(top_p_top, top_p_bot), temperature=softmax_temperature,
                      noise=noise, seed=seed or 0, sample_offset=sample_offset, force_top=force_top, use_graph=use_graph,
                      row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs,
-                     guidance=guidance)
+                     guidance=guidance, keep=kept)
     return out if keep == B else tuple(t[:keep] for t in out)          # (codes and log-probabilities are [B, ...]: the positive half)
 
 
@@ -235,6 +246,28 @@ def _prefix_room(spec, prefix) -> int:
     the room only grows: a longer prefix later rebuilds the engine (weights are loaded and finalized again), and a caller who knows its
     longest prefix asks for it once with ``model.engine(batch, n_steps, max_prefix=...)``."""
     return 0 if prefix is None else int(prefix[0].shape[1])
+
+
+def _check_kept(spec, B: int, n: int, keep_mask, kept_codes, prefix=None, given=None) -> Optional[tuple]:
+    """``keep_mask`` / ``kept_codes`` of the samplers, checked on the host before an engine is built -> ``keep=`` of ``Engine.sample`` (None: neither given)."""
+    if keep_mask is None and kept_codes is None:
+        return None
+    if keep_mask is None or kept_codes is None:
+        raise ValueError('keep_mask and kept_codes come together')
+    if prefix is not None:
+        raise ValueError('keep_mask and prefix_codes: a prefix is a leading run of the keep mask -- put it there')
+    if given is not None:
+        raise ValueError('given_top_code together with keep_mask is not built: put the given codes into kept_codes')
+    m, levels = check_keep(spec, B, n, (keep_mask, list(kept_codes)))
+    return m, levels
+
+
+def _keep_room(spec, kept, text_prefix: bool = True) -> int:
+    """``max_prefix`` of the engine a call with this keep table asks for: the leading run all its rows share (``_prefix_room`` of that prefix); a text
+    model shares the prompt's prefill with it on request only (``text_prefix``), as with ``prefix_codes`` -- without it every kept position is a decode step."""
+    if kept is None or (spec.cond == 2 and (not text_prefix or spec.levels == 3 or spec.depth_decoding == 'bidirectional')):
+        return 0
+    return keep_leading_run(kept[0], kept[0].shape[1] - 1)
 
 
 def sampling_hqtransformer(model,
@@ -261,14 +294,17 @@ def sampling_hqtransformer(model,
                            return_logprobs: bool = False,
                            guidance_scale=None,
                            neg_cond=None,
-                           guidance=None):
+                           guidance=None,
+                           keep_mask=None,
+                           kept_codes=None):
     """Counterpart of ``hqvae.utils.sampling.sampling_hqtransformer`` (sampling.py:240-307) for the three-level
     HQTransformer: returns ``[codes0 int64 [B, L], codes1 [B, L, 4], codes2 [B, L, 16]]`` on the model's GPU.
     ``top_k`` / ``top_p`` / ``softmax_temperature`` are per-level lists (None = no cut-off); ``cond`` as in
     ``sampling_ihqgpt``.  Extensions: ``noise`` fp32 [L, 21, B, V], ``seed`` / ``sample_offset``, ``lane``,
     ``row_samplers`` (per-row settings, as in ``sampling_ihqgpt``), ``prefix_codes`` = ``[t [B, P], m [B, P, 4], b [B, P, 16]]`` (completion,
     as in ``sampling_ihqgpt``), ``return_logprobs`` (appends fp32 [B, L, 21] to the list, as in ``sampling_ihqgpt``), ``guidance_scale`` (a float or
-    three, one per level) / ``neg_cond`` / ``guidance`` (guided sampling over 2 B rows, the B positive ones returned, as in ``sampling_ihqgpt``)."""
+    three, one per level) / ``neg_cond`` / ``guidance`` (guided sampling over 2 B rows, the B positive ones returned, as in ``sampling_ihqgpt``),
+    ``keep_mask`` [B, L] / ``kept_codes`` = ``[[B, L], [B, L, 4], [B, L, 16]]`` (kept positions, as in ``sampling_ihqgpt``)."""
     spec = model.spec
     if spec.levels != 3:
         raise ValueError('sampling_hqtransformer needs the three-level HQTransformer (stage2.type multilevel-hq)')
@@ -277,17 +313,19 @@ def sampling_hqtransformer(model,
     if rows != B:
         noise, prefix_codes = _twice(noise, 2), None if prefix_codes is None else [_twice(p) for p in prefix_codes]
         row_seeds, row_offsets, row_samplers = _twice_rows(row_seeds), _twice_rows(row_offsets), _twice_rows(row_samplers)
+        keep_mask, kept_codes = _twice(keep_mask), None if kept_codes is None else [_twice(c) for c in kept_codes]
         B = rows
     prefix = check_prefix(spec, B, max_seq_len, prefix_codes)
+    kept = _check_kept(spec, B, max_seq_len, keep_mask, kept_codes, prefix)
     top_k = list(top_k) if top_k is not None else [None, None, None]
     top_p = list(top_p) if top_p is not None else [None, None, None]
-    eng = model.engine(B, max_seq_len, lane, max_prefix=_prefix_room(spec, prefix))
+    eng = model.engine(B, max_seq_len, lane, max_prefix=_prefix_room(spec, prefix) or _keep_room(spec, kept))
     if seed is None and noise is None:
         seed = _seed_from_torch()
     out = eng.sample3(B, cond, max_seq_len, precision=_precision(precision, use_fp16), top_k=top_k, top_p=top_p,
                       temperature=softmax_temperature, noise=noise, seed=seed or 0, sample_offset=sample_offset, use_graph=use_graph,
                       row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs,
-                      guidance=guidance)
+                      guidance=guidance, keep=kept)
     return list(out if keep == B else (t[:keep] for t in out))
 
 

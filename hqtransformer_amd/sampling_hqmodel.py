@@ -20,7 +20,7 @@ import torch
 
 from .config import load_config
 from .models import ImageGPT2
-from .pipeline import complete_images, decode_codes, sample_best_of, sample_codes, sampler_cutoffs
+from .pipeline import canvas_windows, complete_images, decode_codes, sample_best_of, sample_canvas, sample_codes, sampler_cutoffs
 from .utils import set_seed
 
 
@@ -53,6 +53,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--batch-size', type=int, default=50)
     p.add_argument('--num-classes', type=int, default=1000)
     p.add_argument('--samples-per-class', type=int, default=None, help='default 50000 // num_classes')
+    p.add_argument('--canvas-grid', type=int, default=None, metavar='G',
+                   help='sample a G x G top-code canvas (larger than the trained --top-resolution grid) with a sliding window; images come out at '
+                        'resolution * G / top_resolution.  Needs --canvas-stride.  The mechanism is claimed, not the quality of the picture')
+    p.add_argument('--canvas-stride', type=int, default=None, metavar='S', help='with --canvas-grid: cells the window moves by (1 <= S < top_resolution, (G - top_resolution) % S == 0)')
     p.add_argument('--negative-class', type=int, default=None, metavar='C', help='with --guidance-scale: the class id to push away from (required: there is no "null" class)')
     return p
 
@@ -124,6 +128,15 @@ def sample_pixels(model: ImageGPT2, args, num_candidates: int, cond) -> np.ndarr
         model.stage1.range_check()
         model.stage2.range_check()
         return pixels.cpu().numpy()
+    if getattr(args, 'canvas_grid', None) is not None:         # --canvas-grid: one sliding-window canvas per row, window k seeded seed + k of this batch
+        first = getattr(args, 'canvas_next', 0)
+        args.canvas_next = first + len(canvas_windows(args.canvas_grid, args.top_resolution, args.canvas_stride))
+        _, pixels = sample_canvas(model, cond, grid=args.canvas_grid, stride=args.canvas_stride, seed=args.seed + first, num_candidates=num_candidates,
+                                  decode_precision=args.decode_precision, softmax_temperature=temps, use_fp16=True, **guided,
+                                  **sampler_cutoffs(args.code_level, args.top_k, args.top_p))
+        model.stage1.at_resolution(int(pixels.shape[-1])).range_check()
+        model.stage2.range_check()
+        return pixels.cpu().numpy()
     sampler = dict(softmax_temperature=temps, use_fp16=True, max_seq_len=args.top_resolution * args.top_resolution, model_stage1=model.stage1,
                    **guided, **sampler_cutoffs(args.code_level, args.top_k, args.top_p))
     best_of = getattr(args, 'best_of', 1)
@@ -157,6 +170,15 @@ def main(argv=None):
     if (args.guidance_scale is None) != (args.negative_class is None):
         raise SystemExit('--guidance-scale and --negative-class come together')
     args.neg_cond = args.negative_class
+    if (args.canvas_grid is None) != (args.canvas_stride is None):
+        raise SystemExit('--canvas-grid and --canvas-stride come together')
+    if args.canvas_grid is not None:
+        if args.complete_from is not None:
+            raise SystemExit('--canvas-grid samples from scratch: not together with --complete-from')
+        try:
+            canvas_windows(args.canvas_grid, args.top_resolution, args.canvas_stride)
+        except ValueError as e:
+            raise SystemExit(f'--canvas-grid / --canvas-stride: {e}')
     set_seed(args.seed)
     os.makedirs(args.result_path, exist_ok=True)
     model = load_model(args.model_path).eval()

@@ -247,6 +247,29 @@ int hqt_set_logprob_out(hqt_handle* h, float* logprobs);
 typedef struct { int32_t pos_row, neg_row; float scale[3]; } hqt_guide_pair;   /* 20 bytes */
 int hqt_set_guidance(hqt_handle* h, int n_pairs, const hqt_guide_pair* pairs);
 
+/* hqt_set_keep_mask -- no reference counterpart: the reference can hold codes fixed only by teacher-forcing a level at every position (given_top_code).  A keep
+ * table fixes any set of (row, position) cells of the code grid and lets the call draw the rest around them: rows of one pass with prefixes of different lengths
+ * (or none), the left columns of an image, everything outside a box, the cells of a sliding window that earlier windows filled.  `keep` is a HOST array
+ * [B, n_steps] of 0 / 1, copied before return; `codes` holds one DEVICE pointer per code level, coarse to fine, in the sampler's layout (int64 [B, n_steps],
+ * [B, n_steps, 4][, [B, n_steps, 16]]), read by the taking call and only where keep is 1; values outside the vocabulary are clamped into it on the device, as every
+ * id that arrives from the caller.  The table is STAGED on the handle (a lane from hqt_clone has its own): the next hqt_sample / hqt_sample_l3 on that handle takes it
+ * and clears it, whether that call succeeds or not; B == 0 or a NULL keep clears; a NULL handle is HQT_ERR_INVALID.
+ * The taking call first scatters the kept codes into the handle's code buffers (one launch per level, outside any captured graph), where every level's embeddings read
+ * them; the sampler kernels then leave those entries alone.  At a kept (b, t) EVERY level of the position is the kept code: it is what out_* holds and what is fed
+ * forward.  Every other position draws exactly what it draws in a plain call whose earlier positions had produced the same codes: Philox keys by (seed, global row,
+ * ABSOLUTE position, draw, chunk), the same slice of `noise`, the same sampler settings and row tables.  A kept position still spends its draw; the result is
+ * discarded.  `logits_out` and a staged hqt_set_logprob_out buffer are written at kept positions as at any other, the log-probability being that of the code fed
+ * forward, i.e. the kept one: a fully kept row scores itself.
+ * Leading run: with L = the smallest count of leading ones over the rows, clipped to min(max_prefix of the handle, n_steps - 1) -- and 0 where the prefix prefill is
+ * not built (text conditioning with three code levels) --, positions < L go through the one-pass prefix prefill exactly as hqt_sample_prefix with prefix_len = L runs
+ * them, and like there their rows of logits_out / the log-probabilities are not written.  All later kept positions are ordinary decode steps.  Only "a table is
+ * staged" and L enter the graph key; the mask lives in device memory: a changed table with the same L replays the same graph.  Every depth head and every precision.
+ * The taking call fails with HQT_ERR_INVALID (and a message naming the cause) when B or n_steps differ from the table's, a level pointer is NULL, force_* is given
+ * (refused by name: the caller puts forced codes into the kept codes), the call is a prefix entry point (the leading run IS the prefix), or the two rows of a
+ * hqt_set_guidance pair keep different positions.  Keeping some levels of a position and not others is not built.  Without a staged table a call launches exactly
+ * what it launched before. */
+int hqt_set_keep_mask(hqt_handle* h, int B, int n_steps, const uint8_t* keep, const int64_t* const* codes);
+
 /* hqt_sample -- replaces sampling_ihqgpt + iHQGPT.sampling_step (hqvae/utils/sampling.py:164-237,
  * hierarchical_ar.py:428-480, 482-563, 667-789) for a batch of B independent images.
  *   cond        int64 [B] class ids (HQT_COND_CLASS), int64 [B, ctx_len_txt] token ids
