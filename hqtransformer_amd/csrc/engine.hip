@@ -2255,10 +2255,13 @@ static int s1_split_pack(S1Ctx& c, GemmArgs* g, const float* stats, const float*
 // SPLIT: GroupNorm statistics of the fp32 tensor `src`, from the per-tile sums its producing conv left or by a pass over it
 static int s1_split_stats(S1Ctx& c, const void* src, int C, int hw, float* stats) {
     Timed t(c.h, "gn_stats", c.st);
-    if (c.gn_ready.tensor == src && c.gn_ready.dbl)
+    if (c.gn_ready.tensor == src && c.gn_ready.dbl) {
+        count_variant(c.h, "variant:gn_stats_tiles:gn");
         HIPCHK(launch_gn_finalize_tiles_d(reinterpret_cast<const double*>(c.h->gn_tiles), stats, c.n, c.gn_ready.tiles, hw, C, 32, 1e-6f, c.st));
-    else
+    } else {
+        count_variant(c.h, "variant:gn_stats_pass:gn");
         HIPCHK(launch_gn_stats_fast(src, stats, c.h->gn_partial, c.n, hw, C, 32, 1e-6f, c.st, DT_F32));
+    }
     return HQT_OK;
 }
 
@@ -2275,10 +2278,13 @@ static int s1_norm(S1Ctx& c, const void* src, int C, int hw, float* stats, const
     if (c.md.fast) {
         {
             Timed t(h, "gn_stats", st);
-            if (c.gn_ready.tensor == src && !c.gn_ready.dbl)       // the producing conv already reduced its tiles: only the fixed-order finalize is left
+            if (c.gn_ready.tensor == src && !c.gn_ready.dbl) {     // the producing conv already reduced its tiles: only the fixed-order finalize is left
+                count_variant(h, "variant:gn_stats_tiles:gn");
                 HIPCHK(launch_gn_finalize_tiles(h->gn_tiles, stats, c.n, c.gn_ready.tiles, hw, C, 32, 1e-6f, st));
-            else
+            } else {
+                count_variant(h, "variant:gn_stats_pass:gn");
                 HIPCHK(launch_gn_stats_fast(src, stats, h->gn_partial, c.n, hw, C, 32, 1e-6f, st));
+            }
         }
         { Timed t(h, "gn_apply", st); HIPCHK(launch_gn_apply(src, c.tn, stats, gamma, beta, c.n, hw, C, 32, swish, st)); }
         g->A = c.tn;
@@ -2288,6 +2294,7 @@ static int s1_norm(S1Ctx& c, const void* src, int C, int hw, float* stats, const
         *a = S1_PLANES;
     } else {
         { Timed t(h, "gn_stats", st); HIPCHK(launch_gn_stats(src, c.adt, stats, c.n, hw, C, 32, 1e-6f, st)); }
+        count_variant(h, "variant:gn_stats_two_pass:gn");
         with_gn(*g, stats, gamma, beta, swish);
     }
     return HQT_OK;
@@ -2319,7 +2326,8 @@ static int s1_conv(S1Ctx& c, GemmArgs g, S1Operand a, const Lin& l, int c_dt, co
     Timed t(h, SlotName(tag, g.M).s, c.st);
     if (c.gn_ready.tensor == g.C) c.gn_ready.tensor = nullptr;          // the tensor is being overwritten
     if (a != S1_TENSOR) {
-        if (g.conv_taps != 9) { HIPCHK(launch_split_gemm(g, c.st)); return HQT_OK; }
+        if (g.conv_taps != 9) { count_variant(h, "variant:split_gemm:%s", tag); HIPCHK(launch_split_gemm(g, c.st)); return HQT_OK; }
+        count_variant(h, "variant:split_conv3:%s", tag);
         if (g.store == STORE_ROWS && h->gn_tiles && conv_halo_stats_ok(g.N, 32)) {   // every such output is normalised next
             g.gn_part_out_d = reinterpret_cast<double*>(h->gn_tiles); g.gn_out_groups = 32;
             c.gn_ready = {g.C, split_conv3_tiles_per_image(g), true};
@@ -2329,7 +2337,12 @@ static int s1_conv(S1Ctx& c, GemmArgs g, S1Operand a, const Lin& l, int c_dt, co
     }
     if (c.md.fast) {
         g.Bw = l.w16;
-        if (!mfma_gemm_ok(g, c.adt, DT_BF16, c_dt)) { HIPCHK(launch_gemm_generic(g, c.adt, DT_BF16, c_dt, c.st)); return HQT_OK; }
+        if (!mfma_gemm_ok(g, c.adt, DT_BF16, c_dt)) {
+            count_variant(h, "variant:gemm_generic_bf16:%s", tag);
+            HIPCHK(launch_gemm_generic(g, c.adt, DT_BF16, c_dt, c.st));
+            return HQT_OK;
+        }
+        if (h->timing) count_variant(h, conv_halo_ok(g, c_dt) ? "variant:halo_conv:%s" : "variant:mfma_gemm:%s", tag);
         // a 3x3 halo conv also leaves per-tile GroupNorm statistics of its output
         if (g.conv_taps == 9 && g.store == STORE_ROWS && h->gn_tiles && conv_halo_ok(g, c_dt) && conv_halo_stats_ok(g.N, 32) &&
             !getenv("HQT_NO_FUSED_GN")) {
@@ -2340,6 +2353,7 @@ static int s1_conv(S1Ctx& c, GemmArgs g, S1Operand a, const Lin& l, int c_dt, co
         return HQT_OK;
     }
     g.Bw = l.w32;                                // (k_quarters stays 0: the summation order of the AR loop's nn.Linear is not a convolution's)
+    count_variant(h, "variant:gemm_generic_f32:%s", tag);
     HIPCHK(launch_gemm_generic(g, DT_F32, DT_F32, DT_F32, c.st));
     return HQT_OK;
 }
@@ -2427,9 +2441,16 @@ static int s1_layer(S1Ctx& c, const DecLayer& l, const DecLayer* next = nullptr)
             sg.C = out; sg.ldc = N; sg.c_batch_stride = (long long)M * N;
             sg.M = M; sg.N = N; sg.K = K; sg.batch = n; sg.alpha = alpha; sg.store = STORE_ROWS;
             sg.zero_page = h->zero_page;          // lets the LDS-DMA kernel take the batched product
-            if (c.md.fast && mfma_gemm_ok(sg, adt, adt, adt)) HIPCHK(launch_mfma_gemm(sg, adt, adt, adt, st));
-            else if (s1_split_product(h, c.md, sg)) HIPCHK(launch_split_gemm(sg, st));
-            else HIPCHK(launch_gemm_generic(sg, adt, adt, adt, st));
+            if (c.md.fast && mfma_gemm_ok(sg, adt, adt, adt)) {
+                count_variant(h, "variant:mfma_gemm:attn_gemm");
+                HIPCHK(launch_mfma_gemm(sg, adt, adt, adt, st));
+            } else if (s1_split_product(h, c.md, sg)) {
+                count_variant(h, "variant:split_gemm:attn_gemm");
+                HIPCHK(launch_split_gemm(sg, st));
+            } else {
+                count_variant(h, c.md.fast ? "variant:gemm_generic_bf16:attn_gemm" : "variant:gemm_generic_f32:attn_gemm");
+                HIPCHK(launch_gemm_generic(sg, adt, adt, adt, st));
+            }
             return HQT_OK;
         };
         CHK(product(h->aq, h->ak, h->as, hw, hw, C, 1.0f / sqrtf((float)C)));      // S[i, j] = q_i . k_j * C^-0.5

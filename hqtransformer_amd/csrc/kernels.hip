@@ -1329,31 +1329,50 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* x, double* par
         partial[((long long)blockIdx.x * groups + g) * 2 + 1] = c2;
     }
 }
-// channel counts the fixed mapping does not cover (C / 8 does not divide 256): one thread per 16-B vector, LDS float atomics
+// channel counts the fixed mapping does not cover (C / 8 does not divide 256, e.g. C = 96, 160, 192): the same thread <-> channel mapping with
+// rpi = floor(256 / vpp) pixel lanes -- the threads beyond rpi * vpp sit the pixel loop out -- and the same fixed-order LDS pass: no atomics, so
+// the statistics (and every SPLIT / FAST pixel behind them) do not depend on the order in which waves arrive.  More than 256 vectors per pixel:
+// one pixel lane, a thread walks vectors t, t + 256, ...
+static inline int gn_generic_rpi(int C) { const int vpp = C / 8; return vpp <= 256 ? 256 / vpp : 1; }
 template <typename T>
 __global__ __launch_bounds__(256) void gn_partial_generic_kernel(const T* x, double* partial, int HW, int C, int groups, int nchunk, int chunk_pix) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* ssum = reinterpret_cast<float*>(smem_raw);      // [C] sum, [C] sumsq
-    float* ssq = ssum + C;
+    float* part = reinterpret_cast<float*>(smem_raw);      // [rpi][C] sums, then [rpi][C] sums of squares; later [C] + [C] totals
     const int b = blockIdx.x / nchunk, ch = blockIdx.x % nchunk;
     const int p0 = ch * chunk_pix, p1 = min(HW, p0 + chunk_pix);
-    for (int c = threadIdx.x; c < 2 * C; c += 256) ssum[c] = 0.0f;
-    __syncthreads();
-    const int vec_per_pix = C / 8;
-    const int total = (p1 - p0) * vec_per_pix;
-    const T* base = x + ((long long)b * HW + p0) * C;
-    for (int v = threadIdx.x; v < total; v += 256) {
-        float f[8];
-        ld8<T>(base + (long long)v * 8, f);
-        const int c8 = (v % vec_per_pix) * 8;
+    const int vpp = C / 8, rpi = vpp <= 256 ? 256 / vpp : 1;
+    const int pl = threadIdx.x / vpp;
+    const T* img = x + ((long long)b * HW) * C;
+    if (pl < rpi) {
+        for (int cv = threadIdx.x - pl * vpp; cv < vpp; cv += 256) {
+            float s[8], q[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { atomicAdd(&ssum[c8 + i], f[i]); atomicAdd(&ssq[c8 + i], f[i] * f[i]); }
+            for (int i = 0; i < 8; ++i) { s[i] = 0.0f; q[i] = 0.0f; }
+            for (int p = p0 + pl; p < p1; p += rpi) {
+                float f[8];
+                ld8<T>(img + (long long)p * C + cv * 8, f);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) { s[i] += f[i]; q[i] += f[i] * f[i]; }
+            }
+            float* ps = part + (size_t)pl * C + cv * 8;
+            float* pq = part + (size_t)(rpi + pl) * C + cv * 8;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { ps[i] = s[i]; pq[i] = q[i]; }
+        }
     }
     __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {           // fixed order over the pixel lanes
+        float ts = 0.0f, tq = 0.0f;
+        for (int r = 0; r < rpi; ++r) { ts += part[(size_t)r * C + c]; tq += part[(size_t)(rpi + r) * C + c]; }
+        part[(size_t)2 * rpi * C + c] = ts;
+        part[(size_t)2 * rpi * C + C + c] = tq;
+    }
+    __syncthreads();
+    const float* tot = part + (size_t)2 * rpi * C;
     const int cpg = C / groups;
     for (int g = threadIdx.x; g < groups; g += 256) {
         double a = 0.0, c2 = 0.0;
-        for (int i = 0; i < cpg; ++i) { a += (double)ssum[g * cpg + i]; c2 += (double)ssq[g * cpg + i]; }
+        for (int i = 0; i < cpg; ++i) { a += (double)tot[g * cpg + i]; c2 += (double)tot[C + g * cpg + i]; }
         partial[((long long)blockIdx.x * groups + g) * 2] = a;
         partial[((long long)blockIdx.x * groups + g) * 2 + 1] = c2;
     }
@@ -1416,8 +1435,10 @@ hipError_t launch_gn_stats_fast(const void* x, float* stats, double* partial, in
         if (dtype == DT_F32) gn_partial_kernel<float><<<B * nchunk, 256, smem, st>>>((const float*)x, partial, HW, C, groups, nchunk, cp);
         else gn_partial_kernel<bf16_t><<<B * nchunk, 256, smem, st>>>((const bf16_t*)x, partial, HW, C, groups, nchunk, cp);
     } else {
-        if (dtype == DT_F32) gn_partial_generic_kernel<float><<<B * nchunk, 256, 2 * C * sizeof(float), st>>>((const float*)x, partial, HW, C, groups, nchunk, cp);
-        else gn_partial_generic_kernel<bf16_t><<<B * nchunk, 256, 2 * C * sizeof(float), st>>>((const bf16_t*)x, partial, HW, C, groups, nchunk, cp);
+        const size_t smem = (size_t)(2 * gn_generic_rpi(C) + 2) * C * sizeof(float);
+        if (C % 8 != 0 || smem > 64 * 1024) return hipErrorInvalidValue;
+        if (dtype == DT_F32) gn_partial_generic_kernel<float><<<B * nchunk, 256, smem, st>>>((const float*)x, partial, HW, C, groups, nchunk, cp);
+        else gn_partial_generic_kernel<bf16_t><<<B * nchunk, 256, smem, st>>>((const bf16_t*)x, partial, HW, C, groups, nchunk, cp);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

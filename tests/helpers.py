@@ -50,6 +50,32 @@ def gate(name: str, value: float, limit: float, op: str = '<=') -> None:
     assert ok, f'{name}: measured {value} violates {op} {limit}'
 
 
+def _synth_images(seed, B, R):
+    r = np.random.default_rng([seed, 78])
+    yy, xx = np.meshgrid(np.linspace(0, 1, R, dtype=np.float32), np.linspace(0, 1, R, dtype=np.float32), indexing='ij')
+    img = np.zeros((B, 3, R, R), np.float32)
+    for b in range(B):
+        for c in range(3):
+            for _ in range(4):
+                fx_, fy_, ph = r.uniform(0.5, 6.0), r.uniform(0.5, 6.0), r.uniform(0, 2 * np.pi)
+                img[b, c] += r.uniform(0.1, 0.4) * np.sin(2 * np.pi * (fx_ * xx + fy_ * yy) + ph).astype(np.float32)
+    return np.clip(img + 0.05 * r.standard_normal(img.shape).astype(np.float32), -1.0, 1.0).astype(np.float32)
+
+
+def _excess_distance(resid, emb, codes):
+    """float64 d(z, e[code]) - min_n d(z, e[n]) per row: 0 where the code is the nearest one."""
+    z = np.ascontiguousarray(resid.transpose(0, 2, 3, 1)).reshape(-1, resid.shape[1]).astype(np.float64)
+    e = emb.astype(np.float64)
+    d = (z ** 2).sum(1, keepdims=True) + (e ** 2).sum(1)[None] - 2 * z @ e.T
+    return d[np.arange(len(z)), codes.reshape(-1)] - d.min(1)
+
+
+def _codebooks(spec, weights):
+    if spec.code_levels == 3:
+        return [weights[f'quantizers.{l}.embedding'] for l in range(3)]
+    return [weights['quantize_t.embedding'], weights['quantize_b.embedding']]
+
+
 def philox_exp_noise(row_seeds, global_rows, n_steps: int, V: int, draws: int = 5) -> np.ndarray:
     """The Exp(1) noise libhqt's sampler generates in-kernel (csrc/kernels.hip, sampler_kernel): Philox4x32-10 with key = the
     row's 64-bit seed, counter = (vocabulary index // 4, step * draws + draw, global row lo, global row hi), lane v % 4 of the

@@ -19,7 +19,8 @@ from hqtransformer_amd._lib import PRECISION_EXACT, PRECISION_FAST
 from hqtransformer_amd.engine import Engine
 from hqtransformer_amd.spec import Stage1Spec, Stage2Spec
 from oracle import hqt_oracle as O
-from tests.helpers import gate, load, oracle_stage1, oracle_stage2, stage1_from_fixture, stage2_from_fixture
+from tests.helpers import (_codebooks, _excess_distance, _synth_images, gate, load, oracle_stage1, oracle_stage2, stage1_from_fixture,
+                           stage2_from_fixture)
 
 pytestmark = pytest.mark.gpu
 LOGIT_TOL = 2e-4
@@ -561,32 +562,6 @@ def test_l3_decode_vs_reference_fixture():
 
 
 # --------------------------------------------------------------------------------------------- HQ-VAE encode side (hqt_encode)
-def _synth_images(seed, B, R):
-    r = np.random.default_rng([seed, 78])
-    yy, xx = np.meshgrid(np.linspace(0, 1, R, dtype=np.float32), np.linspace(0, 1, R, dtype=np.float32), indexing='ij')
-    img = np.zeros((B, 3, R, R), np.float32)
-    for b in range(B):
-        for c in range(3):
-            for _ in range(4):
-                fx_, fy_, ph = r.uniform(0.5, 6.0), r.uniform(0.5, 6.0), r.uniform(0, 2 * np.pi)
-                img[b, c] += r.uniform(0.1, 0.4) * np.sin(2 * np.pi * (fx_ * xx + fy_ * yy) + ph).astype(np.float32)
-    return np.clip(img + 0.05 * r.standard_normal(img.shape).astype(np.float32), -1.0, 1.0).astype(np.float32)
-
-
-def _excess_distance(resid, emb, codes):
-    """float64 d(z, e[code]) - min_n d(z, e[n]) per row: 0 where the code is the nearest one."""
-    z = np.ascontiguousarray(resid.transpose(0, 2, 3, 1)).reshape(-1, resid.shape[1]).astype(np.float64)
-    e = emb.astype(np.float64)
-    d = (z ** 2).sum(1, keepdims=True) + (e ** 2).sum(1)[None] - 2 * z @ e.T
-    return d[np.arange(len(z)), codes.reshape(-1)] - d.min(1)
-
-
-def _codebooks(spec, weights):
-    if spec.code_levels == 3:
-        return [weights[f'quantizers.{l}.embedding'] for l in range(3)]
-    return [weights['quantize_t.embedding'], weights['quantize_b.embedding']]
-
-
 @pytest.mark.parametrize('name', ['g9_encode_64.npz', 'g9_encode_64_noinit.npz', 'g9_encode_64_l3.npz'])
 def test_encode_exact_vs_reference_fixture(name):
     """hqt_encode in EXACT precision against the reference's own encode (tools/gen_golden_enc.py): bit-identical codes at every
