@@ -649,50 +649,70 @@ static hipError_t launch_fewq8(const AttnArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_attention(const AttnArgs& a, hipStream_t st) {
+// The one choice of kernel for a call (kernels.h): launch_attention switches on it, run_block reports it.
+AttnKernel attention_choice(const AttnArgs& a) {
     const int chunks = a.head_dim / 8;
-    if (a.head_dim % 8 != 0 || chunks > 64 || (chunks & (chunks - 1)) != 0) return hipErrorInvalidValue;
+    if (a.head_dim % 8 != 0 || chunks > 64 || (chunks & (chunks - 1)) != 0) return ATTN_INVALID;
     // few queries over a cache known on the host to fit one pass (depth sub-steps): one wave per (sample, head), see attention_fewq_kernel
     if (a.Tq > 1 && a.Tq <= 16 && !a.t_base_dev && !a.dbg && a.t_base + a.Tq <= 2 * (64 / chunks)) {
         static const bool off = getenv("HQT_NO_FEWQ_ATTN") != nullptr;          // A/B switch
         if (!off) {
             // head size 64, <= 4 queries over <= 8 keys, 64+ samples: eight heads per wave (attention_fewq8_kernel; HQT_NO_FEWQ8=1: A/B switch)
             static const bool off8 = getenv("HQT_NO_FEWQ8") != nullptr;
-            if (!off8 && a.head_dim == 64 && a.Tq <= 4 && a.t_base + a.Tq <= 8 && a.B >= 64)
-                return a.dtype == DT_BF16 ? launch_fewq8<bf16_t>(a, st) : launch_fewq8<float>(a, st);
-            const int g2 = (a.B * a.n_heads + 3) / 4, one = a.t_base + a.Tq <= 64 / chunks;
-            if (a.dtype == DT_BF16) { if (one) attention_fewq_kernel<bf16_t, 1><<<g2, 256, 0, st>>>(a); else attention_fewq_kernel<bf16_t, 2><<<g2, 256, 0, st>>>(a); }
-            else { if (one) attention_fewq_kernel<float, 1><<<g2, 256, 0, st>>>(a); else attention_fewq_kernel<float, 2><<<g2, 256, 0, st>>>(a); }
-            return hipGetLastError();
+            if (!off8 && a.head_dim == 64 && a.Tq <= 4 && a.t_base + a.Tq <= 8 && a.B >= 64) return ATTN_FEWQ8;
+            return a.t_base + a.Tq <= 64 / chunks ? ATTN_FEWQ1 : ATTN_FEWQ2;
         }
     }
     // causal prefill of a whole prompt (bf16, head size 64, nothing cached before it) on the matrix cores: up to 64 rows per sample one wave
     // per (sample, head) with the whole problem in registers, above that one wave per 32-query tile (attention_prefill_tiled_kernel).
     // HQT_PREFILL_TILED=1 (test hook, read per launch so that one process can compare the two): the tiled kernel from 5 rows on
     const bool prefill = a.causal && a.dtype == DT_BF16 && a.head_dim == 64 && a.Tq > 4 && a.t_base == 0 && !a.t_base_dev && !a.dbg && (a.n_heads * 64) % 8 == 0;
-    if (prefill && (a.Tq > 64 || getenv("HQT_PREFILL_TILED") != nullptr)) {
-        if (a.Tq > a.Tmax) return hipErrorInvalidValue;
-        const long long waves = (long long)a.B * a.n_heads * ((a.Tq + 31) / 32);
-        attention_prefill_tiled_kernel<<<(unsigned)((waves + 3) / 4), 256, 0, st>>>(a);
-        return hipGetLastError();
-    }
-    if (prefill) {                                                    // (4 < Tq <= 64 here)
-        const int g2 = (a.B * a.n_heads + 3) / 4;
-        if (a.Tq <= 32) attention_prefill_mfma_kernel<1><<<g2, 256, 0, st>>>(a);
-        else attention_prefill_mfma_kernel<2><<<g2, 256, 0, st>>>(a);
-        return hipGetLastError();
-    }
+    if (prefill) return a.Tq > 64 || getenv("HQT_PREFILL_TILED") != nullptr ? ATTN_PREFILL_TILED : ATTN_PREFILL_MFMA;      // (MFMA: 4 < Tq <= 64)
     // one query per sample, head size 64 (the decode steps of a merged FAST pass): eight heads per wave (HQT_NO_HEADS8=1: A/B switch)
     static const bool no_h8 = getenv("HQT_NO_HEADS8") != nullptr;
     // FAST only, from 256 samples: below that the launch is a handful of waves and the chunk-by-chunk walk loses to attention_kernel's
     // single round trip from 32 keys on (64 samples x 64 keys: 19.1 vs 9.3 us); EXACT keeps ONE kernel for every row count, so that a
     // row's draws do not depend on the pass it sits in (hqt.h: merged steps).
-    if (!no_h8 && a.Tq == 1 && a.head_dim == 64 && !a.dbg && a.dtype == DT_BF16 && a.B >= 256) {
-        attention_heads8_kernel<<<(a.B * a.n_heads + 31) / 32, 256, 0, st>>>(a);
-        return hipGetLastError();
+    if (!no_h8 && a.Tq == 1 && a.head_dim == 64 && !a.dbg && a.dtype == DT_BF16 && a.B >= 256) return ATTN_HEADS8;
+    return ATTN_GENERIC;
+}
+const char* attention_kernel_name(AttnKernel k) {
+    static const char* const names[] = {"invalid", "fewq1", "fewq2", "fewq8", "prefill_mfma", "prefill_tiled", "heads8", "generic"};
+    return names[k];
+}
+
+hipError_t launch_attention(const AttnArgs& a, hipStream_t st) {
+    const int g2 = (a.B * a.n_heads + 3) / 4;                         // one wave per (sample, head)
+    switch (attention_choice(a)) {
+    case ATTN_INVALID: return hipErrorInvalidValue;
+    case ATTN_FEWQ8: return a.dtype == DT_BF16 ? launch_fewq8<bf16_t>(a, st) : launch_fewq8<float>(a, st);
+    case ATTN_FEWQ1:
+        if (a.dtype == DT_BF16) attention_fewq_kernel<bf16_t, 1><<<g2, 256, 0, st>>>(a);
+        else attention_fewq_kernel<float, 1><<<g2, 256, 0, st>>>(a);
+        break;
+    case ATTN_FEWQ2:
+        if (a.dtype == DT_BF16) attention_fewq_kernel<bf16_t, 2><<<g2, 256, 0, st>>>(a);
+        else attention_fewq_kernel<float, 2><<<g2, 256, 0, st>>>(a);
+        break;
+    case ATTN_PREFILL_TILED: {
+        if (a.Tq > a.Tmax) return hipErrorInvalidValue;
+        const long long waves = (long long)a.B * a.n_heads * ((a.Tq + 31) / 32);
+        attention_prefill_tiled_kernel<<<(unsigned)((waves + 3) / 4), 256, 0, st>>>(a);
+        break;
     }
-    const int grid = (a.B * a.n_heads * a.Tq + 3) / 4;
-    if (a.dtype == DT_BF16) attention_kernel<bf16_t><<<grid, 256, 0, st>>>(a);
-    else attention_kernel<float><<<grid, 256, 0, st>>>(a);
+    case ATTN_PREFILL_MFMA:
+        if (a.Tq <= 32) attention_prefill_mfma_kernel<1><<<g2, 256, 0, st>>>(a);
+        else attention_prefill_mfma_kernel<2><<<g2, 256, 0, st>>>(a);
+        break;
+    case ATTN_HEADS8:
+        attention_heads8_kernel<<<(a.B * a.n_heads + 31) / 32, 256, 0, st>>>(a);
+        break;
+    case ATTN_GENERIC: {
+        const int grid = (a.B * a.n_heads * a.Tq + 3) / 4;
+        if (a.dtype == DT_BF16) attention_kernel<bf16_t><<<grid, 256, 0, st>>>(a);
+        else attention_kernel<float><<<grid, 256, 0, st>>>(a);
+        break;
+    }
+    }
     return hipGetLastError();
 }

@@ -1422,6 +1422,7 @@ static int run_block(hqt_handle* h, const SampleCtx& c, const BlockW& bw, const 
         CHK(ar_linear(h, c.md, g, bw.qkv, adt, adt, c.st, "gemm_qkv"));
         Timed t(h, "attention", c.st);
         AttnArgs a{h->qbuf, kc, vc, h->abuf, c.B, Tq, h->cfg.n_heads, D / h->cfg.n_heads, Tcache, t_base, t_base_dev, causal, adt, pk, nullptr};
+        if (h->timing) count_variant(h, "variant:attn_%s:%s", attention_kernel_name(attention_choice(a)), r.x == h->xd ? "depth" : "body");
         HIPCHK(launch_attention(a, c.st));
     }
     CHK(residual(h->abuf, bw.proj, "gemm_proj"));

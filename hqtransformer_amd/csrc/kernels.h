@@ -108,6 +108,11 @@ struct AttnArgs {
     int out_packed_mb;           // > 0: write out in the packed_off() layout
     long long* dbg;              // tools/micro only: per-wave clock stamps (NULL in the product)
 };
+// Which kernel of attention.hip serves a call: the one choice, read by launch_attention (which switches on it) and by the timing report
+// ("variant:attn_<name>:<body|depth>", counted in run_block).  ATTN_INVALID: a head size no kernel takes.
+enum AttnKernel { ATTN_INVALID = 0, ATTN_FEWQ1, ATTN_FEWQ2, ATTN_FEWQ8, ATTN_PREFILL_MFMA, ATTN_PREFILL_TILED, ATTN_HEADS8, ATTN_GENERIC };
+AttnKernel attention_choice(const AttnArgs& a);
+const char* attention_kernel_name(AttnKernel k);      // "fewq1", "fewq2", "fewq8", "prefill_mfma", "prefill_tiled", "heads8", "generic"
 hipError_t launch_attention(const AttnArgs& a, hipStream_t st);
 
 struct SamplerArgs {

@@ -33,9 +33,10 @@ def g15_noise(fx, spec):
 
 class OracleBidirectional(OracleStage2):
     """iHQGPT 'bidirectional4' sampling (hierarchical_ar.py:791-878) on the oracle's blocks: per position ONE pass of the depth blocks over five rows,
-    [ln_f(h) + sos_depth, pos_emb_depth[0..3]], full attention and no cache; top logits from row 0, bottom from rows 1..4.  T = 1, no cut-offs."""
+    [ln_f(h) + sos_depth, pos_emb_depth[0..3]], full attention and no cache; top logits from row 0, bottom from rows 1..4.  All five draws use
+    temperature[0], top_k[1] and top_p[1] (:866-873, as run_position does); by default T = 1 without cut-offs.  The logits returned are the raw ones."""
 
-    def sample(self, cond, batch, n_steps, noise, return_logits=True):
+    def sample(self, cond, batch, n_steps, noise, top_k=(None, None), top_p=(None, None), temperature=(1.0, 1.0), return_logits=True):
         w, s = self.w, self.s
         B = batch
         sos = w['sos.weight'][np.asarray(cond, np.int64).reshape(-1)][:, None, :] if s.cond == 1 else np.repeat(w['sos'], B, axis=0)
@@ -53,9 +54,9 @@ class OracleBidirectional(OracleStage2):
                 xd = self._block(f'depths.{j}', xd, dcache, causal_new=False)
             logits[cnt, 0] = linear(layer_norm(xd[:, :1], w['ln_top.weight'], w['ln_top.bias']), w['head_top.weight'])[:, 0]
             logits[cnt, 1:] = linear(layer_norm(xd[:, 1:], w['ln_bot.weight'], w['ln_bot.bias']), w['head_bot.weight']).transpose(1, 0, 2)
-            ct[:, cnt], _ = sample_filtered(logits[cnt, 0], noise[cnt, 0], 1.0, None, None)
+            ct[:, cnt], _ = sample_filtered(logits[cnt, 0], noise[cnt, 0], temperature[0], top_k[1], top_p[1])
             for k in range(4):
-                cb[:, cnt, k], _ = sample_filtered(logits[cnt, 1 + k], noise[cnt, 1 + k], 1.0, None, None)
+                cb[:, cnt, k], _ = sample_filtered(logits[cnt, 1 + k], noise[cnt, 1 + k], temperature[0], top_k[1], top_p[1])
         return ct, cb, logits
 
 
