@@ -145,7 +145,7 @@ struct hqt_handle {
     // per-row keys of merged steps travel through a ring of PINNED staging buffers (an asynchronous copy from pinned memory reads its
     // source when the stream gets there: a buffer is rewritten only after the copy that last read it has completed, hipEventSynchronize)
     static constexpr int ROWS_RING = 4;
-    RowKey* rows_pinned[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};       // each: RowKey[max_batch], then RowSampler[max_batch], then GuidePair[guide_room], then the keep mask [max_batch * max_steps]
+    RowKey* rows_pinned[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};       // each: RowKey[max_batch], then RowSampler[max_batch], then GuidePair[guide_room], then the group table int32[max_batch], then the keep mask [max_batch * max_steps]
     hipEvent_t rows_ev[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};
     bool rows_busy[ROWS_RING] = {false, false, false, false};
     int rows_next = 0;
@@ -160,7 +160,17 @@ struct hqt_handle {
     int keep_B = 0, keep_n = 0;
     const int64_t* keep_codes[3] = {nullptr, nullptr, nullptr};
     unsigned char* keep_mask = nullptr;       // [max_batch * max_steps] mask of the current call
-    void clear_staged() { row_set_staged.clear(); logprob_staged = nullptr; guide_staged.clear(); keep_staged.clear(); }
+    // hqt_set_prompt_groups: host table [B] of prompt indices in [0, groups_G), waiting for the next hqt_sample / hqt_sample_l3 of this handle, which takes it
+    std::vector<int32_t> groups_staged;
+    int groups_G = 0;
+    int* group_of_row = nullptr;              // [max_batch] group table of the current call
+    // staging of a shared prefill, sized (grown) by hqt_set_prompt_groups and by nothing else: K and V of [n_layers][pg_cap][ctx_len_txt][D] at 4 bytes
+    // per element (any mode's activation type fits), and the [max_batch, D] fp32 rows the fan-out gathers for the depth head of position 0
+    void *pg_k = nullptr, *pg_v = nullptr;
+    float* pg_x = nullptr;
+    int pg_cap = 0;                           // prompts the staging holds
+    size_t pg_bytes = 0;                      // bytes of pg_k (= pg_v)
+    void clear_staged() { row_set_staged.clear(); logprob_staged = nullptr; guide_staged.clear(); keep_staged.clear(); groups_staged.clear(); }
     int64_t *cond_buf = nullptr, *codes_top = nullptr, *codes_bot = nullptr;   // call-independent homes of cond / the drawn codes
     int64_t* codes_l2 = nullptr;              // third level: [B, max_steps, 16]
     Lin head_l2;                              // head_levels.2 (three-level models; head_top / head_bot hold levels 0 / 1)
@@ -557,6 +567,7 @@ static int alloc_workspace(hqt_handle* hp) {
         CHK(dev_alloc(h.get(), (void**)&h->row_set, B * sizeof(RowSampler), true));
         CHK(dev_alloc(h.get(), (void**)&h->guide, h->guide_room() * sizeof(GuidePair), true));
         CHK(dev_alloc(h.get(), (void**)&h->keep_mask, B * (size_t)c.max_steps, true));
+        CHK(dev_alloc(h.get(), (void**)&h->group_of_row, B * sizeof(int), true));
         CHK(dev_alloc(h.get(), (void**)&h->cond_buf, B * (size_t)std::max(1, c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : 1) * 8, true));
         CHK(dev_alloc(h.get(), (void**)&h->codes_top, B * (size_t)c.max_steps * 8, true));
         CHK(dev_alloc(h.get(), (void**)&h->codes_bot, B * (size_t)c.max_steps * 4 * 8, true));
@@ -640,6 +651,8 @@ extern "C" int hqt_clone(hqt_handle* src, hqt_handle** out) {
     h->logprob_staged = nullptr;                 // ... and its own log-probability buffer
     h->guide_staged.clear();                     // ... and its own pair table
     h->keep_staged.clear();                      // ... and its own keep table
+    h->groups_staged.clear();                    // ... and its own group table and staging (hqt_set_prompt_groups on the lane sizes it)
+    h->pg_k = h->pg_v = nullptr; h->pg_x = nullptr; h->pg_cap = 0; h->pg_bytes = 0;
     h->nparts = h->npartsd = 0;
     h->pbody.d_phases = nullptr; h->pfull.d_phases = nullptr;      // phase tables hold workspace pointers: bound per handle (persist_bind)
     h->persist_used = false; h->persist_tripped = false; h->capture_persist = false; h->graph_has_persist = false;
@@ -1161,6 +1174,8 @@ struct SampleCtx {
     int n_guide = 0;
     const uint8_t* keep = nullptr;               // host mask [B, n_steps] staged by hqt_set_keep_mask, NULL: every position is drawn (and nothing below is read)
     const int64_t* keep_codes[3] = {nullptr, nullptr, nullptr};   // its codes per level, device, [B, n_steps(, 4 | 16)]
+    const int32_t* groups = nullptr;             // host table [B] staged by hqt_set_prompt_groups, NULL: every row prefills its own prompt (and cond is [B, T])
+    int n_groups = 0;                            // with a table: cond is [n_groups, T]
     hipStream_t st;
     Mode md;
 };
@@ -1438,9 +1453,15 @@ static int run_block(hqt_handle* h, const SampleCtx& c, const BlockW& bw, const 
 // The body blocks of one position over Tq_body rows: as ONE persistent launch up to the top logits (pfull: two code levels, 'parallel' -- persist_build
 // makes that program for no other head; dln0: sub-step 0 of the depth head takes the deferred-LayerNorm path), as one persistent launch of the body
 // alone (pbody), or as the launch chain.  *pfull: the whole-position launch ran.
-static int run_body(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_base, bool body_tbase_from_state, bool dln0, bool* pfull) {
+// `stage` (a shared prefill, hqt_set_prompt_groups): K/V go to the staging buffer of [n_layers][c.B][Tq_body][D] instead of the cache.
+struct KvStage { void *k, *v; };
+static int run_body(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_base, bool body_tbase_from_state, bool dln0, bool* pfull,
+                    const KvStage* stage = nullptr) {
     const hqt_config& cf = h->cfg;
-    const size_t kv_layer = (size_t)cf.max_batch * h->Tmax * cf.embed_dim * c.md.act_sz();
+    const int Tcache = stage ? Tq_body : h->Tmax;
+    const size_t kv_layer = (size_t)(stage ? c.B : cf.max_batch) * Tcache * cf.embed_dim * c.md.act_sz();
+    char* const kc = (char*)(stage ? stage->k : h->kcache);
+    char* const vc = (char*)(stage ? stage->v : h->vcache);
     const int* tb_dev = body_tbase_from_state ? &h->state->t_base : nullptr;
     // deferred LayerNorm needs the packed copy + row statistics of x from the caller's embedding kernel: embed_step emits
     // them (decode steps, Tq = 1); the text prefill's embed_text does not, so the prefill pass takes the classic path
@@ -1453,7 +1474,7 @@ static int run_body(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_b
     if (pbody) CHK(run_persist(h, c, h->pbody, h->x, 1, tb_dev, "persist_body"));
     const Resid r{h->x, dln_body ? h->xpk : nullptr, h->parts, &h->nparts};
     for (int l = 0; l < (pbody || *pfull ? 0 : cf.n_layers); ++l)
-        CHK(run_block(h, c, h->body[l], r, Tq_body, (char*)h->kcache + l * kv_layer, (char*)h->vcache + l * kv_layer, h->Tmax, body_t_base, tb_dev, 1));
+        CHK(run_block(h, c, h->body[l], r, Tq_body, kc + l * kv_layer, vc + l * kv_layer, Tcache, body_t_base, tb_dev, 1));
     return HQT_OK;
 }
 
@@ -1536,6 +1557,12 @@ static int run_depth_input(hqt_handle* h, const SampleCtx& c, int sub, bool dln,
     return HQT_OK;
 }
 
+// Sub-step `s` of the depth head takes the deferred-LayerNorm path (never the bidirectional head's single pass, which decides for itself)
+static bool depth_dln(hqt_handle* h, const SampleCtx& c, const SubStep& s) {
+    const Lin* heads[3] = {&h->head_top, &h->head_bot, &h->head_l2};
+    return h->cfg.depth_decoding != HQT_DEPTH_BIDIRECTIONAL && dln_ok(h, c, h->depth[0], c.B * s.Tq) && heads[s.lv]->wpk_ln;
+}
+
 // Everything of one top position after the body input x is ready (hierarchical_ar.py:482-563,667-789; three code levels:
 // hqtransformer.py:409-635): the body blocks, ln_f, then the depth sub-steps, each an input step, the depth blocks, a head and its draws.
 //  - 'parallel' (two levels; three: 'parallel-add', 'parallel-reduce'): one sub-step per level over 1, 4 (and 16) tokens.  Every sub-step's
@@ -1548,15 +1575,15 @@ static int run_depth_input(hqt_handle* h, const SampleCtx& c, int sub, bool dln,
 //    depth blocks over five rows per sample, [ln_f(h) + sos_depth, pos_emb_depth[0..3]], with full 5 x 5 attention and no cache carried to
 //    the next position; then the two 'parallel' sub-steps' heads and draws, top logits from row 0 (ln_top, head_top), bottom from rows 1..4
 //    (ln_bot, head_bot).  All five draws use temperature_top, top_k_bot and top_p_bot, as the reference does (:866-873).
-static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_base, bool body_tbase_from_state) {
+// The depth-head half of a position: ln_f on the last of the Tq_body rows per sample in h->x, the sub-steps and their draws.  pfull: the
+// whole-position persistent launch already computed sub-step 0 up to its logits (run_body).
+static int run_depth_head(hqt_handle* h, const SampleCtx& c, int Tq_body, bool pfull) {
     const hqt_config& cf = h->cfg;
     const int D = cf.embed_dim, B = c.B, V = cf.vocab_top;
     const Lin* heads[3] = {&h->head_top, &h->head_bot, &h->head_l2};
     const bool bidir = cf.depth_decoding == HQT_DEPTH_BIDIRECTIONAL, causal_head = cf.depth_decoding == HQT_DEPTH_TOP2MID2BOT;
     const int nsub = causal_head ? h->depth_rows : c.levels;       // 'top2mid2bot': one sub-step per depth token
-    auto dln_of = [&](const SubStep& s) { return !bidir && dln_ok(h, c, h->depth[0], B * s.Tq) && heads[s.lv]->wpk_ln; };
-    bool pfull = false;
-    CHK(run_body(h, c, Tq_body, body_t_base, body_tbase_from_state, dln_of(sub_step(cf, 0)), &pfull));
+    auto dln_of = [&](const SubStep& s) { return depth_dln(h, c, s); };
     // the draw and the embedding lookup of the drawn code in one kernel: the two-level top sampler's workgroup of sample b also writes the
     // four input rows of depth sub-step 1 (HQT_NO_FUSED_EMBED=1: separate depth_embed_kernel, for A/B runs)
     static const bool fuse_env = !getenv("HQT_NO_FUSED_EMBED");
@@ -1632,6 +1659,13 @@ static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body
     return HQT_OK;
 }
 
+// One position: the body blocks, then the depth head
+static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_base, bool body_tbase_from_state) {
+    bool pfull = false;
+    CHK(run_body(h, c, Tq_body, body_t_base, body_tbase_from_state, depth_dln(h, c, sub_step(h->cfg, 0)), &pfull));
+    return run_depth_head(h, c, Tq_body, pfull);
+}
+
 // hqt_config.ar_layouts: a precision whose weight layout the handle was created without fails here, loudly (never a silent slower path)
 static int layout_check(const hqt_handle* h, const Mode& md) {
     if (md.fast && !(h->layouts & HQT_LAYOUT_FAST)) return fail(HQT_ERR_STATE, "HQT_PRECISION_FAST on a handle created without HQT_LAYOUT_FAST (hqt_config.ar_layouts = %d)", h->cfg.ar_layouts);
@@ -1684,6 +1718,10 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     keep.swap(h->keep_staged);
     c.keep = keep.empty() ? nullptr : keep.data();
     for (int i = 0; i < 3; ++i) c.keep_codes[i] = h->keep_codes[i];
+    std::vector<int32_t> groups;                 // ... and the staged group table
+    groups.swap(h->groups_staged);
+    c.groups = groups.empty() ? nullptr : groups.data();
+    c.n_groups = c.groups ? h->groups_G : 0;
     if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
     const hqt_config& cf = h->cfg;
     if (c.levels == 2 && !cf.has_stage2) return fail(HQT_ERR_STATE, "handle was created without stage 2");
@@ -1693,6 +1731,8 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     if (B < 1 || B > cf.max_batch) return fail(HQT_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cf.max_batch);
     if (c.n_steps < 1 || c.n_steps > cf.max_steps) return fail(HQT_ERR_INVALID, "n_steps=%d outside [1, %d]", c.n_steps, cf.max_steps);
     if (cf.cond_type != HQT_COND_NONE && !cond) return fail(HQT_ERR_INVALID, "cond is required for class/text conditioning");
+    if (c.groups && c.with_prefix)
+        return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups together with a code prefix (a prefix entry point) is not built: the prompt and the prefix are one prefill whose prefix rows differ per row");
     if (c.with_prefix) {
         if (cf.cond_type == HQT_COND_TEXT && c.levels == 3)
             return fail(HQT_ERR_INVALID, "a code prefix with text conditioning and three code levels is not built (two code levels are)");
@@ -1719,6 +1759,14 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
             L = run;
         }
         c.prefix_len = L;
+    }
+    if (c.groups) {
+        if ((int)groups.size() != B) return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups staged a table of B=%d, this call has B=%d", (int)groups.size(), B);
+        if (c.prefix_len > 0)
+            return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups together with a code prefix or a keep table whose rows share a leading run (prefix_len=%d) is not built: "
+                                         "the prompt and the prefix are one prefill whose prefix rows differ per row", c.prefix_len);
+        // (the staging holds n_groups prompts: the table and the buffer were sized together by hqt_set_prompt_groups)
+        if (c.n_groups > h->pg_cap || !h->pg_k || !h->pg_v || !h->pg_x) return fail(HQT_ERR_STATE, "hqt_set_prompt_groups: the staging buffer holds %d prompts, the table has %d", h->pg_cap, c.n_groups);
     }
     if (c.row_set) {                             // per-row settings replace the scalars of `opts`: those are neither checked nor part of the graph key
         if ((int)staged_rows != B) return fail(HQT_ERR_INVALID, "hqt_set_row_samplers staged %d rows, this call has B=%d", (int)staged_rows, B);
@@ -1769,7 +1817,8 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     c.st = (hipStream_t)stream;
     CHK(mode_of(c.precision, false, &c.md));
     CHK(layout_check(h, c.md));
-    if (cond) HIPCHK(hipMemcpyAsync(h->cond_buf, cond, (size_t)B * (cf.cond_type == HQT_COND_TEXT ? cf.ctx_len_txt : 1) * 8, hipMemcpyDefault, c.st));
+    // (a group table: cond is [n_groups, ctx_len_txt], n_groups <= B)
+    if (cond) HIPCHK(hipMemcpyAsync(h->cond_buf, cond, (size_t)(c.groups ? c.n_groups : B) * (cf.cond_type == HQT_COND_TEXT ? cf.ctx_len_txt : 1) * 8, hipMemcpyDefault, c.st));
     static const size_t width[3] = {1, 4, 16};
     // the prefix goes into the handle's code buffers (outside any captured graph): the prefill's embedding, the embedding of position
     // prefix_len + 1 and the copies below read it there
@@ -1831,6 +1880,46 @@ extern "C" int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler*
     if (n == 0 || !rows) return HQT_OK;
     if (n < 0 || n > h->cfg.max_batch) return fail(HQT_ERR_INVALID, "n=%d outside [0, max_batch=%d]", n, h->cfg.max_batch);
     h->row_set_staged.assign(rows, rows + n);    // checked against B, the levels and the vocabulary by the call that takes it
+    return HQT_OK;
+}
+
+// The one place that allocates for shared prompts: the staging K/V of n_groups prompts (grown, never shrunk: a larger table frees the old pair once
+// the device has drained, a smaller one reuses it) and, with the first table, the gathered x rows.  A sampling call allocates nothing.
+extern "C" int hqt_set_prompt_groups(hqt_handle* h, int B, int n_groups, const int32_t* group_of_row) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    h->groups_staged.clear();
+    const hqt_config& c = h->cfg;
+    if (!c.has_stage2 || c.cond_type != HQT_COND_TEXT)
+        return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups: the handle is not text-conditional (cond_type %d): one embedding row per sample leaves no prefill to share", c.cond_type);
+    if (!group_of_row) return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups: group_of_row is NULL");
+    if (B < 1 || B > c.max_batch) return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups: B=%d outside [1, max_batch=%d]", B, c.max_batch);
+    if (n_groups < 1 || n_groups > c.max_batch) return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups: n_groups=%d outside [1, max_batch=%d]", n_groups, c.max_batch);
+    if (n_groups > B) return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups: n_groups=%d exceeds B=%d (a prompt no row carries would be prefilled for nothing)", n_groups, B);
+    for (int b = 0; b < B; ++b)
+        if (group_of_row[b] < 0 || group_of_row[b] >= n_groups)
+            return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups: group_of_row[%d]=%d outside [0, n_groups=%d)", b, group_of_row[b], n_groups);
+    if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
+    ON_DEVICE(h);
+    if (!h->pg_x) CHK(dev_alloc(h, (void**)&h->pg_x, (size_t)c.max_batch * c.embed_dim * 4, true));
+    if (n_groups > h->pg_cap) {
+        if (h->pg_k) {
+            HIPCHK(hipDeviceSynchronize());      // an earlier call may still be reading the old pair
+            for (void** p : {&h->pg_k, &h->pg_v}) {
+                HIPCHK(hipFree(*p));
+                h->owned.erase(std::remove(h->owned.begin(), h->owned.end(), *p), h->owned.end());
+                h->workspace_bytes -= h->pg_bytes;
+                *p = nullptr;
+            }
+            h->pg_cap = 0;
+        }
+        const size_t bytes = (size_t)c.n_layers * n_groups * c.ctx_len_txt * c.embed_dim * 4;
+        CHK(dev_alloc(h, &h->pg_k, bytes, true));
+        CHK(dev_alloc(h, &h->pg_v, bytes, true));
+        h->pg_bytes = bytes;
+        h->pg_cap = n_groups;
+    }
+    h->groups_G = n_groups;
+    h->groups_staged.assign(group_of_row, group_of_row + B);
     return HQT_OK;
 }
 
@@ -1899,10 +1988,10 @@ extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_
                          float* const* logits_out, void* stream) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
     // a staged table or buffer belongs to a sampling call: it must not wait for a later one behind this call
-    const bool staged = !h->row_set_staged.empty() || h->logprob_staged || !h->guide_staged.empty() || !h->keep_staged.empty();
+    const bool staged = !h->row_set_staged.empty() || h->logprob_staged || !h->guide_staged.empty() || !h->keep_staged.empty() || !h->groups_staged.empty();
     h->clear_staged();
-    if (staged) return fail(HQT_ERR_STATE, "hqt_score: a row-sampler table, guidance pair table or log-probability buffer was staged on this handle (hqt_set_row_samplers / "
-                            "hqt_set_guidance / hqt_set_logprob_out / hqt_set_keep_mask): they belong to a sampling call and were cleared");
+    if (staged) return fail(HQT_ERR_STATE, "hqt_score: a row-sampler table, guidance pair table, keep table, prompt-group table or log-probability buffer was staged on this handle "
+                            "(hqt_set_row_samplers / hqt_set_guidance / hqt_set_logprob_out / hqt_set_keep_mask / hqt_set_prompt_groups): they belong to a sampling call and were cleared");
     if (!logprobs) return fail(HQT_ERR_INVALID, "hqt_score: logprobs is NULL");
     if (!codes) return fail(HQT_ERR_INVALID, "hqt_score: codes is NULL");
     if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
@@ -2064,11 +2153,11 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
     if ((c.row_seeds || c.row_offsets) && (!c.row_seeds || !c.row_offsets)) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
     // merged steps: per-row Philox keys and / or sampler settings (host arrays of B <= max_batch entries, through the pinned ring); a guided call: its pair
     // table, and ALWAYS the keys -- the implicit ones (seed, sample_offset + b) are built here, the negative row of every pair taking its positive row's
-    if (c.row_seeds || c.row_set || c.guide || c.keep) {
+    if (c.row_seeds || c.row_set || c.guide || c.keep || c.groups) {
         const int slot = h->rows_next;
         h->rows_next = (slot + 1) % hqt_handle::ROWS_RING;
         if (!h->rows_pinned[slot]) {
-            HIPCHK(hipHostMalloc((void**)&h->rows_pinned[slot], (size_t)h->cfg.max_batch * (sizeof(RowKey) + sizeof(RowSampler)) + h->guide_room() * sizeof(GuidePair) + (size_t)h->cfg.max_batch * h->cfg.max_steps, hipHostMallocDefault));
+            HIPCHK(hipHostMalloc((void**)&h->rows_pinned[slot], (size_t)h->cfg.max_batch * (sizeof(RowKey) + sizeof(RowSampler)) + h->guide_room() * sizeof(GuidePair) + (size_t)h->cfg.max_batch * sizeof(int32_t) + (size_t)h->cfg.max_batch * h->cfg.max_steps, hipHostMallocDefault));
             HIPCHK(hipEventCreateWithFlags(&h->rows_ev[slot], hipEventDisableTiming));
         }
         if (h->rows_busy[slot]) HIPCHK(hipEventSynchronize(h->rows_ev[slot]));       // the copy that last read this buffer (4 calls ago) is done
@@ -2093,9 +2182,14 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         }
         if (c.keep) {             // the mask, then the kept codes into the handle's code buffers (outside any captured graph): every level's embeddings, the
                                   // samplers' guard and code_logprob read them there
-            unsigned char* km = reinterpret_cast<unsigned char*>(reinterpret_cast<GuidePair*>(reinterpret_cast<RowSampler*>(rk + h->cfg.max_batch) + h->cfg.max_batch) + h->guide_room());
+            unsigned char* km = reinterpret_cast<unsigned char*>(reinterpret_cast<int32_t*>(reinterpret_cast<GuidePair*>(reinterpret_cast<RowSampler*>(rk + h->cfg.max_batch) + h->cfg.max_batch) + h->guide_room()) + h->cfg.max_batch);
             memcpy(km, c.keep, (size_t)B * c.n_steps);
             HIPCHK(hipMemcpyAsync(h->keep_mask, km, (size_t)B * c.n_steps, hipMemcpyHostToDevice, c.st));
+        }
+        if (c.groups) {
+            int32_t* gr = reinterpret_cast<int32_t*>(reinterpret_cast<GuidePair*>(reinterpret_cast<RowSampler*>(rk + h->cfg.max_batch) + h->cfg.max_batch) + h->guide_room());
+            memcpy(gr, c.groups, (size_t)B * sizeof(int32_t));
+            HIPCHK(hipMemcpyAsync(h->group_of_row, gr, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, c.st));
         }
         HIPCHK(hipEventRecord(h->rows_ev[slot], c.st));
         h->rows_busy[slot] = true;
@@ -2108,7 +2202,38 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
     if (!c.row_seeds && !c.guide) HIPCHK(launch_set_rows(h->rows, B, c.seed, c.sample_offset, c.st));
     int first = 0;
     const int64_t* const own[3] = {h->codes_top, h->codes_bot, h->codes_l2};
-    if (cf.cond_type == HQT_COND_TEXT) {     // 64-token causal prefill (sampling.py:187-190, layers.py:107-111)
+    if (cf.cond_type == HQT_COND_TEXT && c.groups) {
+        const int T = cf.ctx_len_txt;
+        // Shared prompts (hqt_set_prompt_groups; P = 0, checked by sample_call): the prompt rows of a sample depend on nothing but its prompt, so the
+        // embedding and the body blocks run over the G distinct prompts, K/V into the staging buffer [n_layers][G][T][D] -- never cache slot g, which
+        // is the destination of row g of the pass, a row that may carry another prompt --; ONE launch then copies the staged K/V of every row's
+        // prompt into its cache slot and gathers the last prompt row of x per row; the depth head runs over the B gathered rows and draws position 0.
+        // Afterwards the cache and the step state are what the unshared prefill leaves: the decode steps below are the same launches.
+        const int G = c.n_groups, D = cf.embed_dim;
+        SampleCtx cg = c;
+        cg.B = G;
+        HIPCHK(launch_embed_text(c.cond, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, G, T, D, c.st, cf.vocab_txt, T));
+        const KvStage stage{h->pg_k, h->pg_v};
+        bool pfull = false;
+        CHK(run_body(h, cg, T, 0, false, false, &pfull, &stage));
+        // split-K slabs the last body GEMM left for "the next LayerNorm" belong to the G T rows: folded into all of them here (the normalised rows in
+        // hbuf are not read), before x is gathered and before the depth GEMMs reuse the slab workspace
+        if (h->pend.slabs) CHK(run_ln(h, c.st, h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), nullptr, h->hbuf, G * T, D, 1, 0, DT_F32, 0));
+        {
+            Timed t(h, "prompt_fanout", c.st);
+            const FanoutArgs fa{h->pg_k, h->pg_v, h->kcache, h->vcache, h->x, h->pg_x, h->group_of_row, cf.n_layers, B, G, T, D,
+                                D * (int)c.md.act_sz(), cf.max_batch, h->Tmax};
+            HIPCHK(launch_prompt_fanout(fa, c.st));
+        }
+        // the depth head reads its B input rows from h->x: the gathered rows stand in for it while its launches are issued (one row per sample)
+        float* const x_body = h->x;
+        h->x = h->pg_x;
+        const int rc = run_depth_head(h, c, 1, false);
+        h->x = x_body;
+        CHK(rc);
+        HIPCHK(launch_advance_step(h->state, T, c.st));
+        first = 1;
+    } else if (cf.cond_type == HQT_COND_TEXT) {     // 64-token causal prefill (sampling.py:187-190, layers.py:107-111)
         // With a code prefix of P positions the prompt and the prefix are ONE pass of T + P rows per sample: rows 0 .. T - 1 the prompt rows,
         // row T + j the input the decode step at position j + 1 computes from the codes of position j (embed_row, read from the handle's
         // code buffers).  K/V of all rows go to the cache; ln_f and the depth head run on the last row and draw position P: the step state

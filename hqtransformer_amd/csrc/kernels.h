@@ -48,6 +48,23 @@ hipError_t launch_copy_kept(const int64_t* src, int64_t* dst, const unsigned cha
 hipError_t launch_embed_text(const int64_t* cond, const float* tok, const float* pos, float* x, int B, int T, int D,
                              hipStream_t st, int vocab = 0, int rows_per_sample = 0);      // rows_per_sample 0: T
 
+// Shared prompts (hqt_set_prompt_groups): the prefill ran over G distinct prompts into a staging K/V of [n_layers][G][T][row_bytes]; one launch hands
+// every row b of the pass the prompt of its group g = group_of_row[b] (device, B entries):
+//   cache slot b, tokens 0 .. T - 1 of every layer <- staging rows of g (K and V; the cache is [n_layers][cache_slots][Tcache][row_bytes]),
+//   x_out[b, :] <- x_src[g * T + T - 1, :] (fp32 [., D]: the last prompt row of the residual stream; x_out must not overlap x_src)
+// A pure byte copy (row_bytes = D * sizeof(activation)); rows whose group is outside [0, G) are left alone.
+struct FanoutArgs {
+    const void *k_src, *v_src;   // staging
+    void *k_dst, *v_dst;         // the handle's cache
+    const float* x_src;          // [G * T, D]
+    float* x_out;                // [B, D]
+    const int* group_of_row;     // device, [B]
+    int n_layers, B, G, T, D;
+    int row_bytes;               // D * sizeof(activation)
+    int cache_slots, Tcache;     // max_batch and Tmax of the cache
+};
+hipError_t launch_prompt_fanout(const FanoutArgs& a, hipStream_t st);
+
 // depth sub-step 1 input: x[b*4+s, :] = tok_top_depth[top[b, step]] + pos_depth[s]
 hipError_t launch_depth_embed(const int64_t* codes_top, int n_steps, const StepState* state, const float* tok,
                               const float* pos, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V = 0, int tok_ld = 0);

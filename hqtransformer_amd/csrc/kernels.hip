@@ -182,6 +182,71 @@ hipError_t launch_embed_text(const int64_t* cond, const float* tok, const float*
     return hipGetLastError();
 }
 
+// Shared prompts: the hand-out of a prefill that ran over the G distinct prompts of a pass (FanoutArgs, kernels.h).  The T rows of a (layer, prompt)
+// are contiguous in the staging buffer and the T prompt tokens of a (layer, cache slot) are contiguous in the cache, so the work is
+// 2 n_layers B "chunks" of T * row_bytes bytes (blockIdx.x = ((layer * B + b) * 2 + (0: K, 1: V))) and B chunks of one fp32 x row behind them;
+// blockIdx.y cuts a chunk into pieces of FANOUT_PIECE bytes, eight 16-byte vectors per thread with all loads issued before the stores.  A chunk
+// whose pointers or length are not multiples of 16 (D * sizeof(activation) % 16 != 0) goes in 2-byte units instead: every length here is even.
+// Nothing is computed and no type is interpreted.  Every index is checked: a group outside [0, G) copies nothing.
+constexpr int FANOUT_VECS = 8, FANOUT_PIECE = 256 * FANOUT_VECS * 16;
+__global__ __launch_bounds__(256) void prompt_fanout_kernel(FanoutArgs a) {
+    const long long kv_chunks = 2LL * a.n_layers * a.B, chunk = blockIdx.x;
+    const char* src;
+    char* dst;
+    long long bytes;
+    if (chunk < kv_chunks) {
+        const int kv = (int)(chunk & 1);
+        const long long lb = chunk >> 1;
+        const int b = (int)(lb % a.B), l = (int)(lb / a.B);
+        const int g = a.group_of_row[b];
+        if (g < 0 || g >= a.G) return;
+        bytes = (long long)a.T * a.row_bytes;
+        src = reinterpret_cast<const char*>(kv ? a.v_src : a.k_src) + ((long long)l * a.G + g) * bytes;
+        dst = reinterpret_cast<char*>(kv ? a.v_dst : a.k_dst) + ((long long)l * a.cache_slots + b) * a.Tcache * a.row_bytes;
+    } else {
+        const long long b = chunk - kv_chunks;
+        if (b >= a.B) return;
+        const int g = a.group_of_row[b];
+        if (g < 0 || g >= a.G) return;
+        bytes = (long long)a.D * 4;
+        src = reinterpret_cast<const char*>(a.x_src + ((long long)g * a.T + a.T - 1) * a.D);
+        dst = reinterpret_cast<char*>(a.x_out + b * a.D);
+    }
+    const long long p0 = (long long)blockIdx.y * FANOUT_PIECE, p1 = min(p0 + FANOUT_PIECE, bytes);
+    if (p0 >= bytes) return;
+    if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | (uintptr_t)bytes) & 15) == 0) {
+        const uint4* s = reinterpret_cast<const uint4*>(src + p0);
+        uint4* d = reinterpret_cast<uint4*>(dst + p0);
+        const int nvec = (int)((p1 - p0) >> 4);
+        uint4 v[FANOUT_VECS];
+#pragma unroll
+        for (int i = 0; i < FANOUT_VECS; ++i) {
+            const int idx = i * 256 + threadIdx.x;
+            if (idx < nvec) v[i] = s[idx];
+        }
+#pragma unroll
+        for (int i = 0; i < FANOUT_VECS; ++i) {
+            const int idx = i * 256 + threadIdx.x;
+            if (idx < nvec) d[idx] = v[i];
+        }
+    } else {
+        const unsigned short* s = reinterpret_cast<const unsigned short*>(src + p0);
+        unsigned short* d = reinterpret_cast<unsigned short*>(dst + p0);
+        const int n = (int)((p1 - p0) >> 1);
+        for (int i = threadIdx.x; i < n; i += 256) d[i] = s[i];
+    }
+}
+hipError_t launch_prompt_fanout(const FanoutArgs& a, hipStream_t st) {
+    if (a.n_layers < 1 || a.B < 1 || a.G < 1 || a.G > a.B || a.T < 1 || a.D < 1 || a.B > a.cache_slots || a.T > a.Tcache) return hipErrorInvalidValue;
+    if ((a.row_bytes != 2 * a.D && a.row_bytes != 4 * a.D) || !a.group_of_row || !a.k_src || !a.v_src || !a.k_dst || !a.v_dst || !a.x_src || !a.x_out) return hipErrorInvalidValue;
+    const long long chunks = 2LL * a.n_layers * a.B + a.B;
+    const long long longest = std::max((long long)a.T * a.row_bytes, (long long)a.D * 4);
+    const long long pieces = (longest + FANOUT_PIECE - 1) / FANOUT_PIECE;
+    if (chunks > 0x7fffffffLL || pieces > 65535) return hipErrorInvalidValue;
+    prompt_fanout_kernel<<<dim3((unsigned)chunks, (unsigned)pieces), 256, 0, st>>>(a);
+    return hipGetLastError();
+}
+
 // `tok_ld` = row length of the table: D, or 4 D for the 'reduce' head, where slot s of a code takes the D-slice s of its row
 // (hqtransformer.py:108-116,532-533)
 // depth_embed_row: output row `row` (slot row & 3 of its group), from the top code at index `at` of codes_top.  Shared by the decode step's kernel

@@ -108,6 +108,36 @@ def check_guided_rows(batch: int, n_pairs: int, max_batch: int) -> None:
                          f'{int(n_pairs)} pairs exceed max_batch={int(max_batch)} of this engine -- build it for twice the images')
 
 
+def check_prompt_groups(s2: Stage2Spec, batch: int, cond, prompt_groups, max_batch: int, prefix=None, keep=None):
+    """A prompt-group table (``hqt_set_prompt_groups``) checked on the host, before any engine is built or touched: ``prompt_groups`` holds one integer per row
+    of the pass, row b carrying prompt ``cond[prompt_groups[b]]`` of ``cond`` [G, ctx_len_txt], 1 <= G <= batch.  Returns (table as a contiguous int32 numpy
+    array, G); None stays None."""
+    if prompt_groups is None:
+        return None
+    if s2.cond != 2:
+        raise ValueError('prompt_groups: the model is not text-conditional (one embedding row per sample leaves no prefill to share)')
+    if prefix is not None or keep is not None:
+        raise ValueError('prompt_groups together with prefix or keep is not built: the prompt and a code prefix are one prefill whose prefix rows differ per row')
+    B = int(batch)
+    if B < 1 or B > int(max_batch):
+        raise ValueError(f'prompt_groups: B={B} outside [1, max_batch={int(max_batch)}]')
+    g = torch.as_tensor(prompt_groups).cpu()
+    if g.dtype.is_floating_point or g.dtype == torch.bool:
+        raise ValueError(f'prompt_groups: expected integers, got {g.dtype}')
+    if tuple(g.shape) != (B,):
+        raise ValueError(f'prompt_groups: expected shape ({B},) -- one entry per row of the pass --, got {tuple(g.shape)}')
+    cshape = tuple(torch.as_tensor(cond).shape) if cond is not None else None
+    if cshape is None or len(cshape) != 2 or cshape[1] != s2.ctx_len_txt or cshape[0] < 1:
+        raise ValueError(f'cond (text token ids) with prompt_groups: expected shape (G, {s2.ctx_len_txt}), one row per distinct prompt, got {cshape}')
+    G = int(cshape[0])
+    if G > B:
+        raise ValueError(f'prompt_groups: n_groups={G} exceeds B={B}')
+    lo, hi = int(g.min()), int(g.max())
+    if lo < 0 or hi >= G:
+        raise ValueError(f'prompt_groups: index outside [0, n_groups={G}) (values span [{lo}, {hi}])')
+    return np.ascontiguousarray(g.numpy().astype(np.int32)), G
+
+
 # what the two- and the three-level surface call their levels in messages
 _FORCE_NAMES = {2: ('force_top', 'force_bot'), 3: ('force[0]', 'force[1]', 'force[2]')}
 _CODE_NAMES = {2: ('code_t', 'code_b'), 3: ('code grid',) * 3}
@@ -437,10 +467,12 @@ class Engine:
     def _sample_levels(self, levels: int, batch: int, cond, n_steps: int, *, precision, top_k, top_p, temperature, noise, seed, sample_offset,
                        force: Sequence[Optional[torch.Tensor]], out: Optional[Sequence[torch.Tensor]], return_logits, use_graph,
                        row_seeds, row_offsets, row_samplers=None, prefix=None,
-                       return_logprobs=False, guidance=None, keep=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+                       return_logprobs=False, guidance=None, keep=None,
+                       prompt_groups=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
         """Returns (codes [B, n], [B, n, 4][, [B, n, 16]], logits [n, draws, B, V] or None, logprobs [B, n, draws] or None)."""
         dev = self.device
         B, V, L = int(batch), self.s2.vocab_top, int(levels)
+        groups = None if prompt_groups is None else check_prompt_groups(self.s2, B, cond, prompt_groups, self.max_batch, prefix, keep)
         # (a text engine was asked for the shared prompt + prefix prefill when it was built with max_prefix; without it P > max_prefix = 0 refuses)
         prefix = check_prefix(self.s2, B, n_steps, prefix, self.max_prefix, text_prefix=True)
         P = 0 if prefix is None else int(prefix[0].shape[1])
@@ -470,7 +502,7 @@ class Engine:
         pairs = guide_pair_table(L, guidance) if guidance is not None and len(guidance) else None      # its rows are checked against B by the library
         if pairs is not None:
             check_guided_rows(B, len(pairs), self.max_batch)
-        cond = self._prep_cond(cond, B)
+        cond = self._prep_cond(cond, B if groups is None else groups[1])     # (a group table: one row per distinct prompt)
         noise = self._prep(noise, (n_steps, draws, B, V), torch.float32, 'noise')
         force = [self._prep(f, shp, torch.int64, what, V) for f, shp, what in zip(force, shapes, _FORCE_NAMES[L])]
         if keep is not None:
@@ -515,6 +547,8 @@ class Engine:
             if keep is not None:                    # ... and the keep table (the mask is copied; the codes are read by the call below)
                 kp = (C.c_void_p * 3)(*[_ptr(t) for t in keep[1]])
                 _lib.check(self.lib.hqt_set_keep_mask(self.h, B, int(n_steps), keep[0].ctypes.data_as(C.c_void_p), kp))
+            if groups is not None:                  # ... and the group table (copied; this is also where the staging buffer of the shared prefill is sized)
+                _lib.check(self.lib.hqt_set_prompt_groups(self.h, B, groups[1], groups[0].ctypes.data_as(C.c_void_p)))
             _lib.check(fn(self.h, B, _ptr(cond), C.byref(o), _ptr(noise), *map(_ptr, force), _ptr(logits), *map(_ptr, outs), C.c_void_p(stream)))
             self._note_split(precision, stream, ar_rows=B)        # every head runs persistently (run_position)
         # inputs must outlive the asynchronous launches
@@ -530,7 +564,8 @@ class Engine:
                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
                row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
-               return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None, keep: Optional[tuple] = None):
+               return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None, keep: Optional[tuple] = None,
+               prompt_groups=None):
         """Two-level sampling: returns (codes_top [B, n], codes_bot [B, n, 4][, logits [n, 5, B, V]][, logprobs [B, n, 5]]).
         ``return_logprobs``: fp32 log-probability of every code the call feeds forward -- the drawn one, or the forced one where ``force_*`` is
         given -- under the raw logits of its draw (T = 1, no cut-off: ``hqt_set_logprob_out``), appended last; with a prefix the positions < P are NaN.
@@ -552,13 +587,17 @@ class Engine:
         every level of the position is the given code, returned and fed forward; every other position is drawn as a plain call draws it whose earlier
         positions had produced the same codes.  The leading run all rows share, up to ``max_prefix`` of this engine, runs as the prefix prefill (its logits
         rows are zeros, its log-probabilities NaN, as with ``prefix``); every other kept position costs a decode step.  Not together with ``force_*`` or
-        ``prefix``; the two rows of a guided pair keep the same positions."""
+        ``prefix``; the two rows of a guided pair keep the same positions.
+        ``prompt_groups`` (int tensor [B], text models): shared prompts (``hqt_set_prompt_groups``) -- ``cond`` is then [G, ctx_len_txt], one row per DISTINCT prompt,
+        and row b of the pass carries ``cond[prompt_groups[b]]``; the prompt prefill runs over the G prompts once and its K/V are copied to the rows.  EXACT returns
+        bit for bit what the call returns with ``cond`` expanded to [B, ctx_len_txt].  Not together with ``prefix`` or ``keep``."""
         if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
             raise ValueError('out: expected a pair (codes_top [B, n_steps], codes_bot [B, n_steps, 4])')
         outs, logits, logprobs = self._sample_levels(2, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(force_top, force_bot), out=out,
                                            return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
-                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance, keep=keep)
+                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance, keep=keep,
+                                           prompt_groups=prompt_groups)
         return (outs[0], outs[1]) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
 
     def sample3(self, batch: int, cond: Optional[torch.Tensor], n_steps: int, *, precision: int = PRECISION_FAST,
@@ -567,15 +606,17 @@ class Engine:
                 sample_offset: int = 0, force: Optional[Sequence[torch.Tensor]] = None, return_logits: bool = False,
                 use_graph: bool = True, row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
                 row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
-                return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None, keep: Optional[tuple] = None):
+                return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None, keep: Optional[tuple] = None,
+                prompt_groups=None):
         """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]][, logprobs [B, n, 21]]); ``row_samplers``,
         ``return_logprobs`` and ``guidance`` (three scales per pair) as in ``sample``;
         ``prefix`` = [[B, P], [B, P, 4], [B, P, 16]]: completion, as in ``sample`` (``hqt_sample_prefix_l3``);
-        ``keep`` = (mask [B, n], [[B, n], [B, n, 4], [B, n, 16]]): kept positions, as in ``sample``."""
+        ``keep`` = (mask [B, n], [[B, n], [B, n, 4], [B, n, 16]]): kept positions, as in ``sample``; ``prompt_groups``: shared prompts, as in ``sample``."""
         outs, logits, logprobs = self._sample_levels(3, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(None,) * 3 if force is None else force,
                                            out=None, return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
-                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance, keep=keep)
+                                           row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance, keep=keep,
+                                           prompt_groups=prompt_groups)
         return tuple(outs) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
 
     def score(self, batch: int, cond: Optional[torch.Tensor], codes: Sequence[torch.Tensor], *, precision: int = PRECISION_FAST,

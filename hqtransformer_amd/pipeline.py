@@ -173,13 +173,15 @@ def score_images(model, images: torch.Tensor, cond=None, encode_precision: Optio
     return sequence_logprob(score_codes(model.stage2, codes, cond, one_pass=True, **score_kw)), codes
 
 
-def sample_best_of(stage2, cond, num_candidates: int, keep: int, **sampler) -> Tuple[list, torch.Tensor]:
+def sample_best_of(stage2, cond, num_candidates: int, keep: int, share_prompts: bool = False, **sampler) -> Tuple[list, torch.Tensor]:
     """Sample ``num_candidates`` per condition and keep the ``keep`` most likely: ``cond`` = class ids (an int, or a tensor / list of G ids), text prompts
     [G, ctx_len_txt], or anything for an unconditional model (one group).  ONE sampler call over all G * num_candidates rows (group-major: row
     g * num_candidates + c), keywords of ``sampling_ihqgpt`` / ``sampling_hqtransformer`` in ``sampler``; every candidate is scored by
     ``sequence_logprob`` of its own draws (the model's log-probability at T = 1, whatever temperature and cut-offs drew it; with ``prefix_codes`` over
     the completed positions only; with ``guidance_scale`` -- ``neg_cond`` then per group, like ``cond`` -- under the guided logits) and ranked within its group, descending, ties to the lower candidate index; codes and scores are gathered on the
-    device.  Returns ``(codes, scores)``: the code levels as one list, [G * keep, n], [G * keep, n, 4][, ...], group-major, best first, and fp64 [G, keep]."""
+    device.  Returns ``(codes, scores)``: the code levels as one list, [G * keep, n], [G * keep, n, 4][, ...], group-major, best first, and fp64 [G, keep].
+    ``share_prompts=True`` (text models): the ``num_candidates`` rows of a caption are one prompt -- it is prefilled once and handed to them
+    (``sampling_ihqgpt``; with ``guidance_scale`` the negative rows are deduplicated too)."""
     C, K = int(num_candidates), int(keep)
     if not 1 <= K <= C:
         raise ValueError(f'keep={K} outside [1, num_candidates={C}]')
@@ -199,6 +201,8 @@ def sample_best_of(stage2, cond, num_candidates: int, keep: int, **sampler) -> T
         neg = torch.as_tensor(sampler['neg_cond'])
         neg = neg.reshape(-1, int(neg.shape[-1])) if stage2.use_txt_cond else neg.reshape(-1)
         sampler['neg_cond'] = neg.repeat_interleave(C, dim=0) if int(neg.shape[0]) == G and G > 1 else neg
+    if share_prompts:
+        sampler['share_prompts'] = True
     *codes, logprobs = sample_codes(stage2, G * C, rows, return_logprobs=True, **sampler)
     prefix = sampler.get('prefix_codes')
     P = 0 if prefix is None else int(torch.as_tensor(prefix[0]).shape[-1])
@@ -430,9 +434,15 @@ class Pending:
 
 class InflightSampler:
     def __init__(self, model, lanes: int = 3, device: Optional[torch.device] = None, merge: int = 1, record_phases: bool = False,
-                 ar_high_priority: bool = False, mixed_samplers: bool = False, mixed_prefixes: bool = False):
+                 ar_high_priority: bool = False, mixed_samplers: bool = False, mixed_prefixes: bool = False, share_prompts: bool = False):
         if lanes < 1 or merge < 1:
             raise ValueError('lanes and merge must be >= 1')
+        if share_prompts and mixed_prefixes:
+            raise ValueError('share_prompts together with mixed_prefixes is not built: every pass of a mixed_prefixes sampler stages a keep table, and the prompt '
+                             'and a code prefix are one prefill whose prefix rows differ per row')
+        # text models: every pass prefills each DISTINCT prompt of its rows once -- over all its steps, negative rows included -- and hands it to the rows
+        # that carry it (sampling_ihqgpt's share_prompts).  A pass-wide setting: it travels with every step's sampler keywords, which steps must share
+        self.share_prompts = bool(share_prompts)
         self.model = model
         self.merge = int(merge)
         # merged steps may differ in top_k* / top_p* / softmax_temperature: every pass stages a row table on its lane (always, also when its steps
@@ -469,6 +479,8 @@ class InflightSampler:
         those steps get their rows.  ``guidance_scale`` / ``neg_cond`` (with the sampler keywords, as in ``sampling_ihqgpt``): a guided step; it
         merges with guided and unguided steps alike -- the pass carries one negative row per row of a guided step behind the rows of all steps
         (``step_guidance``), which are neither decoded nor returned."""
+        if self.share_prompts:
+            sample_kw.setdefault('share_prompts', True)
         if self.merge > 1:
             if decode is False or phase_events is not None or sample_kw.get('noise') is not None:
                 raise ValueError('merged steps support the plain sample + decode step only (no explicit noise, no phase events)')

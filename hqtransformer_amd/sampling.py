@@ -126,6 +126,36 @@ def _guided(model, B: int, cond, guidance_scale, neg_cond, guidance):
     return 2 * B, guided_cond(model, B, cond, neg_cond), guided_pairs(B, scales), B
 
 
+# ---------------------------------------------------------------------------------------------- shared prompts
+# The prompt rows of a sample depend on nothing but its prompt: a pass whose rows repeat prompts (candidates of one caption, the negative rows of a guided
+# batch) prefills every DISTINCT prompt once and copies the result to the rows that carry it (hqt_set_prompt_groups).
+def prompt_groups_of(cond):
+    """Text prompts [B, ctx_len_txt] -> (unique [G, ctx_len_txt], group_of_row int32 [B]): identical rows share a group, groups are numbered in the order in
+    which their prompt first appears, and ``unique[group_of_row]`` reproduces ``cond``."""
+    c = torch.as_tensor(cond)
+    if c.dim() != 2 or int(c.shape[0]) < 1:
+        raise ValueError(f'prompt_groups_of: expected prompts of shape [B, ctx_len_txt], got {tuple(c.shape)}')
+    seen, first, group = {}, [], []
+    for b, row in enumerate(c.cpu().tolist()):
+        g = seen.setdefault(tuple(row), len(first))
+        if g == len(first):
+            first.append(b)
+        group.append(g)
+    return c[torch.as_tensor(first, device=c.device)], torch.tensor(group, dtype=torch.int32)
+
+
+def _shared(model, share_prompts: bool, cond, prefix_codes=None, keep_mask=None, kept_codes=None):
+    """What ``share_prompts`` makes of the rows of a pass as they will run (a guided call: positives, then negatives): (cond, prompt_groups) of ``Engine.sample``."""
+    if not share_prompts:
+        return cond, None
+    if prefix_codes is not None or keep_mask is not None or kept_codes is not None:
+        raise ValueError('share_prompts together with prefix_codes or keep_mask is not built: the prompt and a code prefix are one prefill whose prefix rows '
+                         'differ per row')
+    if not model.use_txt_cond:
+        raise ValueError('share_prompts needs a text-conditional model: one embedding row per sample leaves no prefill to share')
+    return prompt_groups_of(cond)
+
+
 @torch.no_grad()
 def sampling_ihqgpt(model,
                     num_candidates: int,
@@ -157,7 +187,8 @@ def sampling_ihqgpt(model,
                     neg_cond=None,
                     guidance=None,
                     keep_mask=None,
-                    kept_codes=None):
+                    kept_codes=None,
+                    share_prompts: bool = False):
     """Returns ``(codes_top int64 [B, max_seq_len], codes_bot int64 [B, max_seq_len, 4])`` on the model's GPU; ``return_logprobs=True`` appends
     ``logprobs`` fp32 [B, max_seq_len, 5]: the log-probability of every code the call feeds forward (the drawn one; the given one where
     ``given_top_code`` forces the top level) under the raw logits of its draw -- temperature 1, no cut-off, so always finite; draw order top,
@@ -199,6 +230,9 @@ def sampling_ihqgpt(model,
     conditioning: with ``text_prefix=True``; otherwise, and for every later kept position, a decode step each); log-probabilities of that run are
     NaN.  IndexError for a kept code outside the vocabulary.  Not together with ``given_top_code`` or ``prefix_codes``; with ``guidance_scale`` the
     two are given for B rows and repeated for the negative half.  Only the mechanism is claimed, not what it does to image quality.
+    ``share_prompts=True`` (text models): identical prompts among the rows of the pass -- with ``guidance_scale`` the negative rows count, so one negative
+    prompt for all is one group -- are prefilled once and handed to their rows (``prompt_groups_of``, ``hqt_set_prompt_groups``).  'exact' returns bit for bit
+    what the call returns without it.  ValueError together with ``prefix_codes`` or ``keep_mask``.
 
     The call is asynchronous and does not read the device's flags: 'split' passes above 256 rows SATURATE activations outside the fp16 range and
     only flag them, and a persistent FAST launch (up to 64 samples) that could not finish on a shared GPU only marks the handle -- call
@@ -215,6 +249,7 @@ def sampling_ihqgpt(model,
             g = torch.as_tensor(given_top_code)
             given_top_code = g if g.dim() == 1 or g.shape[0] == 1 else _twice(g)
         B = rows
+    cond, groups = _shared(model, share_prompts, cond, prefix_codes, keep_mask, kept_codes)
     prefix = check_prefix(spec, B, max_seq_len, prefix_codes, text_prefix=text_prefix)       # refused here, before an engine is built
     kept = _check_kept(spec, B, max_seq_len, keep_mask, kept_codes, prefix, given_top_code)
     force_top = None
@@ -235,7 +270,7 @@ def sampling_ihqgpt(model,
                      top_k=(top_k_top, top_k_bot), top_p=(top_p_top, top_p_bot), temperature=softmax_temperature,
                      noise=noise, seed=seed or 0, sample_offset=sample_offset, force_top=force_top, use_graph=use_graph,
                      row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs,
-                     guidance=guidance, keep=kept)
+                     guidance=guidance, keep=kept, **({} if groups is None else {'prompt_groups': groups}))
     return out if keep == B else tuple(t[:keep] for t in out)          # (codes and log-probabilities are [B, ...]: the positive half)
 
 
@@ -296,7 +331,8 @@ def sampling_hqtransformer(model,
                            neg_cond=None,
                            guidance=None,
                            keep_mask=None,
-                           kept_codes=None):
+                           kept_codes=None,
+                           share_prompts: bool = False):
     """Counterpart of ``hqvae.utils.sampling.sampling_hqtransformer`` (sampling.py:240-307) for the three-level
     HQTransformer: returns ``[codes0 int64 [B, L], codes1 [B, L, 4], codes2 [B, L, 16]]`` on the model's GPU.
     ``top_k`` / ``top_p`` / ``softmax_temperature`` are per-level lists (None = no cut-off); ``cond`` as in
@@ -304,7 +340,8 @@ def sampling_hqtransformer(model,
     ``row_samplers`` (per-row settings, as in ``sampling_ihqgpt``), ``prefix_codes`` = ``[t [B, P], m [B, P, 4], b [B, P, 16]]`` (completion,
     as in ``sampling_ihqgpt``), ``return_logprobs`` (appends fp32 [B, L, 21] to the list, as in ``sampling_ihqgpt``), ``guidance_scale`` (a float or
     three, one per level) / ``neg_cond`` / ``guidance`` (guided sampling over 2 B rows, the B positive ones returned, as in ``sampling_ihqgpt``),
-    ``keep_mask`` [B, L] / ``kept_codes`` = ``[[B, L], [B, L, 4], [B, L, 16]]`` (kept positions, as in ``sampling_ihqgpt``)."""
+    ``keep_mask`` [B, L] / ``kept_codes`` = ``[[B, L], [B, L, 4], [B, L, 16]]`` (kept positions, as in ``sampling_ihqgpt``),
+    ``share_prompts`` (identical prompts of the pass prefilled once, as in ``sampling_ihqgpt``)."""
     spec = model.spec
     if spec.levels != 3:
         raise ValueError('sampling_hqtransformer needs the three-level HQTransformer (stage2.type multilevel-hq)')
@@ -315,6 +352,7 @@ def sampling_hqtransformer(model,
         row_seeds, row_offsets, row_samplers = _twice_rows(row_seeds), _twice_rows(row_offsets), _twice_rows(row_samplers)
         keep_mask, kept_codes = _twice(keep_mask), None if kept_codes is None else [_twice(c) for c in kept_codes]
         B = rows
+    cond, groups = _shared(model, share_prompts, cond, prefix_codes, keep_mask, kept_codes)
     prefix = check_prefix(spec, B, max_seq_len, prefix_codes)
     kept = _check_kept(spec, B, max_seq_len, keep_mask, kept_codes, prefix)
     top_k = list(top_k) if top_k is not None else [None, None, None]
@@ -325,7 +363,7 @@ def sampling_hqtransformer(model,
     out = eng.sample3(B, cond, max_seq_len, precision=_precision(precision, use_fp16), top_k=top_k, top_p=top_p,
                       temperature=softmax_temperature, noise=noise, seed=seed or 0, sample_offset=sample_offset, use_graph=use_graph,
                       row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs,
-                      guidance=guidance, keep=kept)
+                      guidance=guidance, keep=kept, **({} if groups is None else {'prompt_groups': groups}))
     return list(out if keep == B else (t[:keep] for t in out))
 
 

@@ -139,6 +139,8 @@ def sample_pixels(model: ImageGPT2, args, num_candidates: int, cond) -> np.ndarr
         return pixels.cpu().numpy()
     sampler = dict(softmax_temperature=temps, use_fp16=True, max_seq_len=args.top_resolution * args.top_resolution, model_stage1=model.stage1,
                    **guided, **sampler_cutoffs(args.code_level, args.top_k, args.top_p))
+    if getattr(args, 'share_prompts', False):      # --share-prompts (text driver): identical prompts of the pass are prefilled once
+        sampler['share_prompts'] = True
     best_of = getattr(args, 'best_of', 1)
     if best_of > 1:                      # --best-of N: N x num_candidates per condition in one pass, the num_candidates most likely kept
         codes, _ = sample_best_of(model.stage2, cond, best_of * num_candidates, num_candidates, **sampler)

@@ -14,6 +14,8 @@ instead (no tokenizer files needed: smoke runs).  The last, shorter batch is kep
 completes image i mod N to its caption, the first R rows of its top code grid kept.
 ``--best-of N`` (no reference counterpart: the reference leaves the choice among its candidates to an external model): N candidates are sampled per
 caption in one pass and the most likely one under the stage-2 model is kept (``pipeline.sample_best_of``); the output format is unchanged.
+``--share-prompts`` (no reference counterpart): identical prompts among the rows of a pass -- the N candidates of a caption with ``--best-of``, the negative
+rows with ``--guidance-scale`` -- are prefilled once and handed to their rows (``hqt_set_prompt_groups``); harmless where no prompt repeats.
 """
 from __future__ import annotations
 
@@ -49,6 +51,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help='sample N x num_candidates images per caption and keep the num_candidates the stage-2 model finds most likely (1: keep all)')
     p.add_argument('--negative-prompt', type=str, default=None, metavar='TEXT',
                    help='with --guidance-scale: the caption to push away from (needs the tokenizer; default: the empty, all-[PAD] caption)')
+    p.add_argument('--share-prompts', action='store_true',
+                   help='prefill every distinct prompt of a pass once and hand it to the rows that carry it (pays with --best-of and --guidance-scale)')
     return p
 
 
@@ -92,6 +96,8 @@ def main(argv=None):
     load_completion(args)
     if args.best_of > 1 and args.complete_from is not None:
         raise SystemExit('--best-of and --complete-from do not combine')
+    if args.share_prompts and args.complete_from is not None:
+        raise SystemExit('--share-prompts and --complete-from do not combine: the prompt and the kept code prefix are one prefill')
     set_seed(args.seed)
     os.makedirs(args.result_path, exist_ok=True)
     model = load_model(args.model_path).eval()

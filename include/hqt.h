@@ -270,6 +270,24 @@ int hqt_set_guidance(hqt_handle* h, int n_pairs, const hqt_guide_pair* pairs);
  * what it launched before. */
 int hqt_set_keep_mask(hqt_handle* h, int B, int n_steps, const uint8_t* keep, const int64_t* const* codes);
 
+/* hqt_set_prompt_groups -- no reference counterpart: the reference prefills the text prompt of every row (sampling.py:187-190), also where the rows are candidates of
+ * one caption or the negative rows of a guided batch.  The prompt rows of a sample depend on nothing but the prompt, so the taking call prefills every DISTINCT prompt
+ * once and hands the result to the rows that carry it.  `group_of_row` is a HOST array of B entries in [0, n_groups), copied before return; the mapping is arbitrary
+ * (unsorted, groups of any size).  The table is STAGED on the handle (a lane from hqt_clone has its own, and its own staging buffer): the next hqt_sample /
+ * hqt_sample_l3 on that handle takes it and clears it, whether that call succeeds or not.  In that call `cond` is [n_groups, ctx_len_txt] (prompt g in row g) and
+ * row b of the pass carries prompt group_of_row[b]: the prompt embedding and the body blocks run causally over n_groups * ctx_len_txt rows, their K/V going to a
+ * staging buffer of [n_layers][n_groups][ctx_len_txt][D]; one launch (timing slot "prompt_fanout") copies the K/V of every row's prompt into its cache slot and
+ * gathers the last prompt row of the residual stream per row; the depth head then runs on the B rows and draws position 0.  The decode steps, the captured graph and
+ * its key are those of a call without a table: they see the cache an unshared prefill leaves.  In HQT_PRECISION_EXACT the call returns bit for bit what the same call
+ * returns with the prompts expanded to [B, ctx_len_txt]; in the other precisions the prefill of fewer rows may be served by other GEMM kernels.
+ * Memory: the staging buffer (2 * n_layers * n_groups * ctx_len_txt * D * 4 bytes, counted by hqt_workspace_bytes) and the gathered rows (max_batch * D * 4 bytes)
+ * are allocated HERE -- grown when n_groups exceeds what an earlier table needed, never shrunk -- and nowhere else: a sampling call allocates nothing.
+ * HQT_ERR_INVALID, with a message naming the cause: a NULL handle or table, a handle that is not text-conditional, B or n_groups outside [1, max_batch],
+ * n_groups > B, an entry outside [0, n_groups); in the taking call: a B that differs from the table's, a prefix entry point, or a staged hqt_set_keep_mask table
+ * whose rows share a leading run (prefix_len > 0: the prompt and the prefix are then one prefill whose prefix rows differ per row).  hqt_score clears a staged table
+ * and fails with HQT_ERR_STATE.  Without a staged table a call launches exactly what it launched before. */
+int hqt_set_prompt_groups(hqt_handle* h, int B, int n_groups, const int32_t* group_of_row);
+
 /* hqt_sample -- replaces sampling_ihqgpt + iHQGPT.sampling_step (hqvae/utils/sampling.py:164-237,
  * hierarchical_ar.py:428-480, 482-563, 667-789) for a batch of B independent images.
  *   cond        int64 [B] class ids (HQT_COND_CLASS), int64 [B, ctx_len_txt] token ids
