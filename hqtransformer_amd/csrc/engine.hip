@@ -170,7 +170,12 @@ struct hqt_handle {
     float* pg_x = nullptr;
     int pg_cap = 0;                           // prompts the staging holds
     size_t pg_bytes = 0;                      // bytes of pg_k (= pg_v)
-    void clear_staged() { row_set_staged.clear(); logprob_staged = nullptr; guide_staged.clear(); keep_staged.clear(); groups_staged.clear(); }
+    // hqt_set_segment: positions [seg_start, seg_stop) waiting for the next hqt_sample / hqt_sample_l3 of this handle, which takes them
+    bool seg_staged = false;
+    int seg_start = 0, seg_stop = 0;
+    // the pass a segment stopped in: what a continuation must match, and `pos`, the position it goes on from (the step state says pos over t_live keys)
+    struct Paused { bool live = false; int B = 0, n_steps = 0, levels = 0, precision = 0, pos = 0; } paused;
+    void clear_staged() { row_set_staged.clear(); logprob_staged = nullptr; guide_staged.clear(); keep_staged.clear(); groups_staged.clear(); seg_staged = false; }
     int64_t *cond_buf = nullptr, *codes_top = nullptr, *codes_bot = nullptr;   // call-independent homes of cond / the drawn codes
     int64_t* codes_l2 = nullptr;              // third level: [B, max_steps, 16]
     Lin head_l2;                              // head_levels.2 (three-level models; head_top / head_bot hold levels 0 / 1)
@@ -653,6 +658,8 @@ extern "C" int hqt_clone(hqt_handle* src, hqt_handle** out) {
     h->keep_staged.clear();                      // ... and its own keep table
     h->groups_staged.clear();                    // ... and its own group table and staging (hqt_set_prompt_groups on the lane sizes it)
     h->pg_k = h->pg_v = nullptr; h->pg_x = nullptr; h->pg_cap = 0; h->pg_bytes = 0;
+    h->seg_staged = false;                       // ... and its own segment and paused pass
+    h->paused = hqt_handle::Paused();
     h->nparts = h->npartsd = 0;
     h->pbody.d_phases = nullptr; h->pfull.d_phases = nullptr;      // phase tables hold workspace pointers: bound per handle (persist_bind)
     h->persist_used = false; h->persist_tripped = false; h->capture_persist = false; h->graph_has_persist = false;
@@ -1176,6 +1183,8 @@ struct SampleCtx {
     const int64_t* keep_codes[3] = {nullptr, nullptr, nullptr};   // its codes per level, device, [B, n_steps(, 4 | 16)]
     const int32_t* groups = nullptr;             // host table [B] staged by hqt_set_prompt_groups, NULL: every row prefills its own prompt (and cond is [B, T])
     int n_groups = 0;                            // with a table: cond is [n_groups, T]
+    bool seg = false;                            // hqt_set_segment staged a segment: the call runs positions [start, stop) of its n_steps ...
+    int start = 0, stop = 0;                     // ... (without one: 0 and n_steps); start > 0 continues the handle's paused pass
     hipStream_t st;
     Mode md;
 };
@@ -1699,6 +1708,7 @@ static int run_decode_step(hqt_handle* h, const SampleCtx& c) {      // one KV-c
 }
 
 static int sample_run(hqt_handle* h, const SampleCtx& c);
+static int rows_ring_take(hqt_handle* h, int* out);
 
 // hqt_sample / hqt_sample_l3 after their null checks: `c` holds the call's options, sampler settings and forced codes (feed); validates them,
 // runs the call and copies the drawn codes of every level out
@@ -1722,6 +1732,10 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     groups.swap(h->groups_staged);
     c.groups = groups.empty() ? nullptr : groups.data();
     c.n_groups = c.groups ? h->groups_G : 0;
+    c.seg = h->seg_staged;                       // ... and the staged segment
+    h->seg_staged = false;
+    c.start = c.seg ? h->seg_start : 0;
+    c.stop = c.seg ? h->seg_stop : c.n_steps;
     if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
     const hqt_config& cf = h->cfg;
     if (c.levels == 2 && !cf.has_stage2) return fail(HQT_ERR_STATE, "handle was created without stage 2");
@@ -1731,6 +1745,24 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     if (B < 1 || B > cf.max_batch) return fail(HQT_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cf.max_batch);
     if (c.n_steps < 1 || c.n_steps > cf.max_steps) return fail(HQT_ERR_INVALID, "n_steps=%d outside [1, %d]", c.n_steps, cf.max_steps);
     if (cf.cond_type != HQT_COND_NONE && !cond) return fail(HQT_ERR_INVALID, "cond is required for class/text conditioning");
+    if (c.seg) {
+        if (c.start < 0 || c.stop <= c.start || c.stop > c.n_steps)
+            return fail(HQT_ERR_INVALID, "hqt_set_segment staged [%d, %d): a segment needs 0 <= start < stop <= n_steps = %d", c.start, c.stop, c.n_steps);
+        if (c.with_prefix) return fail(HQT_ERR_INVALID, "hqt_set_segment: the staged segment was taken by a prefix entry point; segments of a pass with a code prefix are not built (hqt_sample / hqt_sample_l3 take the segment)");
+        if (c.keep) return fail(HQT_ERR_INVALID, "hqt_set_segment together with a staged keep table (hqt_set_keep_mask) is not built");
+        if (c.groups && c.start > 0)
+            return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups together with a segment that starts at position %d: the prompt prefill belongs to the segment that starts at 0", c.start);
+        if (c.start > 0) {                       // a continuation: the cache and the step state must be those of THIS pass, stopped in front of `start`
+            const hqt_handle::Paused& p = h->paused;
+            if (!p.live) return fail(HQT_ERR_STATE, "hqt_set_segment: a segment that starts at position %d continues a paused pass, and this handle holds none "
+                                                    "(none was begun, the pass was finished, or another call has overwritten its cache since)", c.start);
+            if (p.B != B) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass has B=%d, this call has B=%d (hqt_select_rows changes the rows of a paused pass)", p.B, B);
+            if (p.n_steps != c.n_steps) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass has n_steps=%d, this call has n_steps=%d", p.n_steps, c.n_steps);
+            if (p.levels != c.levels) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass has %d code levels, this call has %d", p.levels, c.levels);
+            if (p.precision != c.precision) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass runs in precision %d, this call asks for precision %d (the cache holds that precision's type)", p.precision, c.precision);
+            if (p.pos != c.start) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass stands at position %d, this segment has start=%d", p.pos, c.start);
+        }
+    }
     if (c.groups && c.with_prefix)
         return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups together with a code prefix (a prefix entry point) is not built: the prompt and the prefix are one prefill whose prefix rows differ per row");
     if (c.with_prefix) {
@@ -1824,9 +1856,20 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     // prefix_len + 1 and the copies below read it there
     for (int i = 0; i < (c.prefix_len && !c.keep ? c.levels : 0); ++i)
         HIPCHK(launch_copy_prefix(c.prefix[i], codes[i], B, c.prefix_len, c.n_steps, (int)width[i], cf.vocab_top, c.st));
+    // whatever this call is, it writes the body cache and the step state: a paused pass is over, or goes on below and is recorded anew behind its segment
+    h->paused.live = false;
+    // a continuation reads the codes of position start - 1 where the caller holds them: a level that is not forced takes them from out_* (the caller may have
+    // edited them, or gathered its rows along with hqt_select_rows)
+    for (int i = 0; i < (c.start > 0 ? c.levels : 0); ++i)
+        if (c.feed[i] == codes[i]) HIPCHK(launch_copy_positions(out[i], codes[i], B, c.n_steps, (int)width[i], c.start - 1, c.start, c.st));
     CHK(sample_run(h, c));
-    for (int i = 0; i < c.levels; ++i)
-        HIPCHK(hipMemcpyAsync(out[i], codes[i], (size_t)B * c.n_steps * width[i] * 8, hipMemcpyDeviceToDevice, c.st));
+    if (!c.seg) {
+        for (int i = 0; i < c.levels; ++i)
+            HIPCHK(hipMemcpyAsync(out[i], codes[i], (size_t)B * c.n_steps * width[i] * 8, hipMemcpyDeviceToDevice, c.st));
+        return HQT_OK;
+    }
+    for (int i = 0; i < c.levels; ++i) HIPCHK(launch_copy_positions(codes[i], out[i], B, c.n_steps, (int)width[i], c.start, c.stop, c.st));
+    if (c.stop < c.n_steps) h->paused = hqt_handle::Paused{true, B, c.n_steps, c.levels, c.precision, c.stop};
     return HQT_OK;
 }
 
@@ -1920,6 +1963,53 @@ extern "C" int hqt_set_prompt_groups(hqt_handle* h, int B, int n_groups, const i
     }
     h->groups_G = n_groups;
     h->groups_staged.assign(group_of_row, group_of_row + B);
+    return HQT_OK;
+}
+
+extern "C" int hqt_set_segment(hqt_handle* h, int start, int stop) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    h->seg_staged = true;                        // checked against n_steps and the paused pass by the call that takes it
+    h->seg_start = start; h->seg_stop = stop;
+    return HQT_OK;
+}
+
+// The rows of a paused pass re-mapped: one gather of the live cache rows along the batch axis (K and V of every body layer, in the paused precision's
+// type).  Between two positions nothing else of a row lives in the handle: the depth cache is rebuilt every position, the step state is shared by all
+// rows, the codes are the caller's.  Allocates nothing: the table travels through the pinned ring into the group table's device buffer (a prefill's, free here).
+extern "C" int hqt_select_rows(hqt_handle* h, int B_new, const int32_t* rows_from, void* stream) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    const hqt_config& cf = h->cfg;
+    const hqt_handle::Paused& p = h->paused;
+    if (!p.live) return fail(HQT_ERR_STATE, "hqt_select_rows: this handle holds no paused pass (hqt_set_segment with stop < n_steps leaves one)");
+    if (!rows_from) return fail(HQT_ERR_INVALID, "hqt_select_rows: rows_from is NULL");
+    if (B_new < 1 || B_new > cf.max_batch) return fail(HQT_ERR_INVALID, "hqt_select_rows: B_new=%d outside [1, max_batch=%d]", B_new, cf.max_batch);
+    for (int j = 0; j < B_new; ++j)
+        if (rows_from[j] < 0 || rows_from[j] >= p.B)
+            return fail(HQT_ERR_INVALID, "hqt_select_rows: rows_from[%d]=%d outside [0, B=%d) of the paused pass", j, rows_from[j], p.B);
+    if ((size_t)B_new * 16 > kv_gather_lds_limit())
+        return fail(HQT_ERR_INVALID, "hqt_select_rows: B_new=%d rows of 16 bytes do not fit the %d KiB of LDS of a compute unit (at most %d rows)", B_new,
+                    (int)(kv_gather_lds_limit() / 1024), (int)(kv_gather_lds_limit() / 16));
+    Mode md;
+    CHK(mode_of(p.precision, false, &md));
+    ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    // live keys: the step state says (pos, t_base) with t_base = pos for class / no conditioning, ctx_len_txt + pos - 1 for text (the prefill drew position 0)
+    const int t_live = cf.cond_type == HQT_COND_TEXT ? cf.ctx_len_txt + p.pos - 1 : p.pos;
+    if (t_live < 1 || t_live > h->Tmax) return fail(HQT_ERR_STATE, "hqt_select_rows: %d live cache rows outside [1, %d]", t_live, h->Tmax);
+    int slot = 0;
+    CHK(rows_ring_take(h, &slot));
+    int32_t* gr = reinterpret_cast<int32_t*>(reinterpret_cast<GuidePair*>(reinterpret_cast<RowSampler*>(h->rows_pinned[slot] + cf.max_batch) + cf.max_batch) + h->guide_room());
+    memcpy(gr, rows_from, (size_t)B_new * sizeof(int32_t));
+    HIPCHK(hipMemcpyAsync(h->group_of_row, gr, (size_t)B_new * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(h->rows_ev[slot], st));
+    h->rows_busy[slot] = true;
+    {
+        Timed t(h, "kv_gather_rows", st);
+        const long long row_bytes = (long long)cf.embed_dim * (long long)md.act_sz();
+        const KvGatherArgs ga{h->kcache, h->vcache, h->group_of_row, cf.n_layers, B_new, cf.max_batch, (long long)h->Tmax * row_bytes, (long long)t_live * row_bytes};
+        HIPCHK(launch_kv_gather_rows(ga, st));
+    }
+    h->paused.B = B_new;
     return HQT_OK;
 }
 
@@ -2021,6 +2111,7 @@ extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_
         HIPCHK(launch_copy_prefix(codes[i], own[i], B, n, n, width[i], cf.vocab_top, c.st));
         c.feed[i] = own[i]; c.out[i] = own[i];
     }
+    h->paused.live = false;                        // the pass overwrites the body cache and the step state: a paused pass (hqt_set_segment) is over
     HIPCHK(launch_set_step(h->state, 0, 0, c.st));
     // ---- body: n rows per sample (text: the T prompt rows, then the input rows of positions 1 .. n - 1)
     const int D = cf.embed_dim, V = cf.vocab_top, T = text ? cf.ctx_len_txt : 0;
@@ -2142,6 +2233,19 @@ struct PersistOrder {
     }
 };
 
+// The next buffer of the pinned ring, free to be rewritten: the copy that last read it (4 takes ago) is done.  The caller records rows_ev[slot] behind its copies.
+static int rows_ring_take(hqt_handle* h, int* out) {
+    const int slot = h->rows_next;
+    h->rows_next = (slot + 1) % hqt_handle::ROWS_RING;
+    if (!h->rows_pinned[slot]) {
+        HIPCHK(hipHostMalloc((void**)&h->rows_pinned[slot], (size_t)h->cfg.max_batch * (sizeof(RowKey) + sizeof(RowSampler)) + h->guide_room() * sizeof(GuidePair) + (size_t)h->cfg.max_batch * sizeof(int32_t) + (size_t)h->cfg.max_batch * h->cfg.max_steps, hipHostMallocDefault));
+        HIPCHK(hipEventCreateWithFlags(&h->rows_ev[slot], hipEventDisableTiming));
+    }
+    if (h->rows_busy[slot]) HIPCHK(hipEventSynchronize(h->rows_ev[slot]));
+    *out = slot;
+    return HQT_OK;
+}
+
 static int sample_run(hqt_handle* h, const SampleCtx& c) {
     const hqt_config& cf = h->cfg;
     const int B = c.B;
@@ -2149,18 +2253,13 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
     for (int i = 0; i < c.levels; ++i) top_p = top_p || c.lv[i].top_p > 0.f;
     HIPCHK(sampler_configure(cf.vocab_top, top_p || c.row_top_p));
     CHK(persist_bind(h));
-    HIPCHK(launch_set_step(h->state, 0, 0, c.st));
+    if (c.start == 0) HIPCHK(launch_set_step(h->state, 0, 0, c.st));      // (a continuation goes on from the step state its pass stopped at)
     if ((c.row_seeds || c.row_offsets) && (!c.row_seeds || !c.row_offsets)) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
     // merged steps: per-row Philox keys and / or sampler settings (host arrays of B <= max_batch entries, through the pinned ring); a guided call: its pair
     // table, and ALWAYS the keys -- the implicit ones (seed, sample_offset + b) are built here, the negative row of every pair taking its positive row's
     if (c.row_seeds || c.row_set || c.guide || c.keep || c.groups) {
-        const int slot = h->rows_next;
-        h->rows_next = (slot + 1) % hqt_handle::ROWS_RING;
-        if (!h->rows_pinned[slot]) {
-            HIPCHK(hipHostMalloc((void**)&h->rows_pinned[slot], (size_t)h->cfg.max_batch * (sizeof(RowKey) + sizeof(RowSampler)) + h->guide_room() * sizeof(GuidePair) + (size_t)h->cfg.max_batch * sizeof(int32_t) + (size_t)h->cfg.max_batch * h->cfg.max_steps, hipHostMallocDefault));
-            HIPCHK(hipEventCreateWithFlags(&h->rows_ev[slot], hipEventDisableTiming));
-        }
-        if (h->rows_busy[slot]) HIPCHK(hipEventSynchronize(h->rows_ev[slot]));       // the copy that last read this buffer (4 calls ago) is done
+        int slot = 0;
+        CHK(rows_ring_take(h, &slot));
         RowKey* rk = h->rows_pinned[slot];
         if (c.row_seeds || c.guide) {
             for (int b = 0; b < B; ++b) {
@@ -2200,9 +2299,11 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
             HIPCHK(launch_copy_kept(c.keep_codes[i], c.out[i], h->keep_mask, B, c.n_steps, width[i], cf.vocab_top, c.st));
     }
     if (!c.row_seeds && !c.guide) HIPCHK(launch_set_rows(h->rows, B, c.seed, c.sample_offset, c.st));
-    int first = 0;
+    int first = c.start;
     const int64_t* const own[3] = {h->codes_top, h->codes_bot, h->codes_l2};
-    if (cf.cond_type == HQT_COND_TEXT && c.groups) {
+    if (c.start > 0) {
+        // a continuation (hqt_set_segment): no prefill -- the cache holds the prompt rows and every position below start
+    } else if (cf.cond_type == HQT_COND_TEXT && c.groups) {
         const int T = cf.ctx_len_txt;
         // Shared prompts (hqt_set_prompt_groups; P = 0, checked by sample_call): the prompt rows of a sample depend on nothing but its prompt, so the
         // embedding and the body blocks run over the G distinct prompts, K/V into the staging buffer [n_layers][G][T][D] -- never cache slot g, which
@@ -2264,7 +2365,7 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         HIPCHK(launch_advance_step(h->state, P + 1, c.st));
         first = P + 1;
     }
-    const int remaining = c.n_steps - first;
+    const int remaining = c.stop - first;       // (without a segment: stop = n_steps)
     if (remaining <= 0) return HQT_OK;
     if (c.use_graph && !h->timing) {
         // positions per captured graph: the largest divisor of the remaining positions up to HQT_GRAPH_POSITIONS (default 16):

@@ -65,6 +65,21 @@ struct FanoutArgs {
 };
 hipError_t launch_prompt_fanout(const FanoutArgs& a, hipStream_t st);
 
+// Paused passes (hqt_select_rows): cache slot j of every layer <- what slot rows_from[j] held, j < B_new, for the first live_bytes bytes of a slot (the live
+// tokens 0 .. t_base - 1, contiguous), K and V, in place: any mapping (identity, permutation, subset, duplicates, B_new above the paused row count).  A pure byte
+// copy through LDS; entries of rows_from outside [0, cache_slots) move nothing.  B_new * 16 bytes must fit kv_gather_lds_limit() (the CU's LDS).
+struct KvGatherArgs {
+    void *k, *v;                 // the handle's cache, [n_layers][cache_slots][slot_bytes]
+    const int* rows_from;        // device, [B_new]
+    int n_layers, B_new, cache_slots;
+    long long slot_bytes;        // Tmax * D * sizeof(activation)
+    long long live_bytes;        // t_base * D * sizeof(activation)
+};
+size_t kv_gather_lds_limit();
+hipError_t launch_kv_gather_rows(const KvGatherArgs& a, hipStream_t st);
+// dst[b, p, :] = src[b, p, :] for p in [p0, p1), both [B, n_steps, width] (one code level of a segment, hqt_set_segment)
+hipError_t launch_copy_positions(const int64_t* src, int64_t* dst, int B, int n_steps, int width, int p0, int p1, hipStream_t st);
+
 // depth sub-step 1 input: x[b*4+s, :] = tok_top_depth[top[b, step]] + pos_depth[s]
 hipError_t launch_depth_embed(const int64_t* codes_top, int n_steps, const StepState* state, const float* tok,
                               const float* pos, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V = 0, int tok_ld = 0);

@@ -247,6 +247,78 @@ hipError_t launch_prompt_fanout(const FanoutArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+// hqt_select_rows: the gather of cache rows along the batch axis, in place (KvGatherArgs, kernels.h).  The live tokens of a (K | V, layer, cache slot) are
+// one contiguous run of `live_bytes` bytes, and slot j of every run becomes what slot rows_from[j] held: a piece (one byte range of the run, the same in
+// every slot) depends on no other piece.  A workgroup owns one piece of one (K | V, layer) (blockIdx.y = layer * 2 + (0: K, 1: V), blockIdx.x = piece):
+// it reads the B_new source pieces into LDS, passes the barrier, then writes slots 0 .. B_new - 1.  Workgroups touch disjoint pieces, so duplicates, cycles
+// and sources at or above B_new need no ordering between them.  Unit = uint4 (16 bytes per lane) where run length and pointers allow, else 2 bytes: every
+// length here is even.  Nothing is computed and no type is interpreted.  Every index is checked: an entry outside [0, cache_slots) moves nothing.
+template <class Unit>
+__global__ __launch_bounds__(256) void kv_gather_rows_kernel(KvGatherArgs a, int piece_units) {
+    extern __shared__ uint4 gather_lds[];
+    Unit* lds = reinterpret_cast<Unit*>(gather_lds);
+    const int kv = (int)(blockIdx.y & 1), l = (int)(blockIdx.y >> 1);
+    const long long run_units = a.live_bytes / (long long)sizeof(Unit);
+    const long long u0 = (long long)blockIdx.x * piece_units;
+    if (l >= a.n_layers || u0 >= run_units) return;
+    const int nu = (int)min((long long)piece_units, run_units - u0);
+    char* const base = reinterpret_cast<char*>(kv ? a.v : a.k) + (long long)l * a.cache_slots * a.slot_bytes;
+    const int total = a.B_new * nu;
+    for (int e = threadIdx.x; e < total; e += 256) {
+        const int j = e / nu, u = e - j * nu;
+        const int src = a.rows_from[j];
+        if (src < 0 || src >= a.cache_slots) continue;
+        lds[e] = reinterpret_cast<const Unit*>(base + (long long)src * a.slot_bytes)[u0 + u];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < total; e += 256) {
+        const int j = e / nu, u = e - j * nu;
+        const int src = a.rows_from[j];
+        if (src < 0 || src >= a.cache_slots) continue;
+        reinterpret_cast<Unit*>(base + (long long)j * a.slot_bytes)[u0 + u] = lds[e];
+    }
+}
+size_t kv_gather_lds_limit() { return 160u * 1024u; }
+hipError_t launch_kv_gather_rows(const KvGatherArgs& a, hipStream_t st) {
+    if (a.n_layers < 1 || a.B_new < 1 || a.B_new > a.cache_slots || a.live_bytes < 2 || a.live_bytes > a.slot_bytes || !a.k || !a.v || !a.rows_from) return hipErrorInvalidValue;
+    if ((a.live_bytes | a.slot_bytes) & 1) return hipErrorInvalidValue;
+    const bool vec = (((uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.live_bytes | (uintptr_t)a.slot_bytes) & 15) == 0;
+    const long long unit = vec ? 16 : 2, run_units = a.live_bytes / unit;
+    // piece width: as many units as B_new pieces fit into KV_GATHER_LDS (two workgroups per CU); more rows than that: up to the CU's whole LDS
+    constexpr long long KV_GATHER_LDS = 64 * 1024;
+    long long lds = KV_GATHER_LDS;
+    if ((long long)a.B_new * unit > lds) lds = (long long)kv_gather_lds_limit();
+    long long piece = lds / ((long long)a.B_new * unit);
+    if (piece < 1) return hipErrorInvalidValue;                  // (hqt_select_rows refuses such a B_new by name first)
+    piece = std::min(piece, run_units);
+    const long long pieces = (run_units + piece - 1) / piece;
+    if (pieces > 0x7fffffffLL || 2LL * a.n_layers > 65535 || (long long)a.B_new * piece > 0x7fffffffLL) return hipErrorInvalidValue;
+    const size_t shmem = (size_t)((long long)a.B_new * piece * unit);
+    const dim3 grid((unsigned)pieces, (unsigned)(2 * a.n_layers));
+    if (vec) {
+        if (shmem > 64 * 1024) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kv_gather_rows_kernel<uint4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); if (e != hipSuccess) return e; }
+        kv_gather_rows_kernel<uint4><<<grid, 256, shmem, st>>>(a, (int)piece);
+    } else {
+        if (shmem > 64 * 1024) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kv_gather_rows_kernel<unsigned short>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); if (e != hipSuccess) return e; }
+        kv_gather_rows_kernel<unsigned short><<<grid, 256, shmem, st>>>(a, (int)piece);
+    }
+    return hipGetLastError();
+}
+
+// Positions [p0, p1) of one code level between two [B, n_steps, width] buffers (a segment of a pass: hqt_set_segment); other entries are neither read nor written
+__global__ __launch_bounds__(256) void copy_positions_kernel(const int64_t* src, int64_t* dst, long long n, int per_sample, int stride, int off) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long b = i / per_sample, r = i - b * per_sample;
+    dst[b * stride + off + r] = src[b * stride + off + r];
+}
+hipError_t launch_copy_positions(const int64_t* src, int64_t* dst, int B, int n_steps, int width, int p0, int p1, hipStream_t st) {
+    if (B < 1 || width < 1 || p0 < 0 || p1 <= p0 || p1 > n_steps || !src || !dst) return hipErrorInvalidValue;
+    const long long n = (long long)B * (p1 - p0) * width;
+    copy_positions_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(src, dst, n, (p1 - p0) * width, n_steps * width, p0 * width);
+    return hipGetLastError();
+}
+
 // `tok_ld` = row length of the table: D, or 4 D for the 'reduce' head, where slot s of a code takes the D-slice s of its row
 // (hqtransformer.py:108-116,532-533)
 // depth_embed_row: output row `row` (slot row & 3 of its group), from the top code at index `at` of codes_top.  Shared by the decode step's kernel

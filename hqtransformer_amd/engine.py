@@ -232,6 +232,46 @@ def check_keep(s2: Stage2Spec, batch: int, n_steps: int, keep) -> Optional[tuple
     return m, levels
 
 
+def check_segment(n_steps: int, segment, prefix=None, keep=None, prompt_groups=None) -> Optional[Tuple[int, int]]:
+    """A segment (``hqt_set_segment``) checked on the host, before any engine is built or touched: ``segment = (start, stop)`` with
+    0 <= start < stop <= n_steps, integers; not together with ``prefix`` or ``keep``, and with ``prompt_groups`` only where start == 0 (the prompt prefill
+    belongs to the first segment).  Returns (start, stop) as ints; None stays None."""
+    if segment is None:
+        return None
+    if not isinstance(segment, (list, tuple)) or len(segment) != 2:
+        raise ValueError('segment: expected (start, stop)')
+    for v in segment:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f'segment: expected two integers, got {segment!r}')
+    start, stop = int(segment[0]), int(segment[1])
+    if start < 0 or stop <= start or stop > int(n_steps):
+        raise ValueError(f'segment=({start}, {stop}): a segment needs 0 <= start < stop <= n_steps = {int(n_steps)}')
+    if prefix is not None:
+        raise ValueError('segment together with prefix is not built (segments of a pass with a code prefix)')
+    if keep is not None:
+        raise ValueError('segment together with keep is not built')
+    if prompt_groups is not None and start > 0:
+        raise ValueError(f'segment=({start}, {stop}) together with prompt_groups: the prompt prefill belongs to the segment that starts at 0')
+    return start, stop
+
+
+def check_select_rows(rows_from, paused_batch: Optional[int], max_batch: int) -> np.ndarray:
+    """A row mapping for ``Engine.select_rows`` (``hqt_select_rows``) checked on the host: integers, one dimension, 1 <= B_new <= ``max_batch`` entries, each in
+    [0, ``paused_batch``) -- the rows of the paused pass; None: unknown to the caller, the library checks the entries.  Any mapping: the identity, a permutation, a
+    subset, duplicates.  Returns it as a contiguous int32 numpy array."""
+    r = torch.as_tensor(rows_from).cpu()
+    if r.dim() != 1 or r.numel() < 1:
+        raise ValueError(f'rows_from: expected a one-dimensional mapping of at least one row, got shape {tuple(r.shape)}')
+    if r.dtype.is_floating_point or r.dtype == torch.bool:
+        raise ValueError(f'rows_from: expected integers, got {r.dtype}')
+    if r.numel() > int(max_batch):
+        raise ValueError(f'rows_from: B_new={r.numel()} exceeds max_batch={int(max_batch)} of this engine')
+    lo, hi = int(r.min()), int(r.max())
+    if lo < 0 or (paused_batch is not None and hi >= int(paused_batch)):
+        raise ValueError(f'rows_from: index outside [0, B={paused_batch}) of the paused pass (values span [{lo}, {hi}])')
+    return np.ascontiguousarray(r.numpy().astype(np.int32))
+
+
 def check_score_codes(s2: Stage2Spec, codes, what: str = 'one-pass scoring') -> int:
     """Codes for ``Engine.score`` checked on the host, before any engine is built or touched: the model's code levels as one list, coarse to fine, int64 [B, n],
     [B, n, 4][, [B, n, 16]]; host tensors inside the vocabulary (IndexError otherwise; device tensors are checked once by the engine).  ValueError for the heads
@@ -468,10 +508,14 @@ class Engine:
                        force: Sequence[Optional[torch.Tensor]], out: Optional[Sequence[torch.Tensor]], return_logits, use_graph,
                        row_seeds, row_offsets, row_samplers=None, prefix=None,
                        return_logprobs=False, guidance=None, keep=None,
-                       prompt_groups=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+                       prompt_groups=None, segment=None, logits_out=None,
+                       logprobs_out=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
         """Returns (codes [B, n], [B, n, 4][, [B, n, 16]], logits [n, draws, B, V] or None, logprobs [B, n, draws] or None)."""
         dev = self.device
         B, V, L = int(batch), self.s2.vocab_top, int(levels)
+        segment = check_segment(n_steps, segment, prefix, keep, prompt_groups)
+        if segment is not None and segment[0] > 0 and out is None:
+            raise ValueError(f'segment={segment}: a continuation reads the codes of position {segment[0] - 1} from out -- pass the tensors the earlier segments wrote')
         groups = None if prompt_groups is None else check_prompt_groups(self.s2, B, cond, prompt_groups, self.max_batch, prefix, keep)
         # (a text engine was asked for the shared prompt + prefix prefill when it was built with max_prefix; without it P > max_prefix = 0 refuses)
         prefix = check_prefix(self.s2, B, n_steps, prefix, self.max_prefix, text_prefix=True)
@@ -524,9 +568,16 @@ class Engine:
             outs = [self._check_out(t, shp, torch.int64, dev, f'out[{i}]') for i, (t, shp) in enumerate(zip(out, shapes))]
         # (with a prefix the rows of positions < P are not written: zeros)
         logits = (torch.zeros if P else torch.empty)((n_steps, draws, B, V), dtype=torch.float32, device=dev) if return_logits else None
+        # (buffers a segmented pass fills piece by piece: every segment writes its own positions and no others)
+        if logits_out is not None:
+            logits, return_logits = self._check_out(logits_out, (n_steps, draws, B, V), torch.float32, dev, 'logits_out'), True
+        if logprobs_out is not None:
+            return_logprobs = True
         # (the positions a prefix call does not compute stay NaN: a zero would read as "certain", and a sum over a half-scored sequence must not look like a score)
         logprobs = None
-        if return_logprobs:
+        if logprobs_out is not None:
+            logprobs = self._check_out(logprobs_out, (B, n_steps, draws), torch.float32, dev, 'logprobs_out')
+        elif return_logprobs:
             logprobs = (torch.full((B, n_steps, draws), float('nan'), dtype=torch.float32, device=dev) if P
                         else torch.empty((B, n_steps, draws), dtype=torch.float32, device=dev))
         if prefix is not None:
@@ -549,6 +600,8 @@ class Engine:
                 _lib.check(self.lib.hqt_set_keep_mask(self.h, B, int(n_steps), keep[0].ctypes.data_as(C.c_void_p), kp))
             if groups is not None:                  # ... and the group table (copied; this is also where the staging buffer of the shared prefill is sized)
                 _lib.check(self.lib.hqt_set_prompt_groups(self.h, B, groups[1], groups[0].ctypes.data_as(C.c_void_p)))
+            if segment is not None:                 # ... and the segment
+                _lib.check(self.lib.hqt_set_segment(self.h, segment[0], segment[1]))
             _lib.check(fn(self.h, B, _ptr(cond), C.byref(o), _ptr(noise), *map(_ptr, force), _ptr(logits), *map(_ptr, outs), C.c_void_p(stream)))
             self._note_split(precision, stream, ar_rows=B)        # every head runs persistently (run_position)
         # inputs must outlive the asynchronous launches
@@ -565,7 +618,8 @@ class Engine:
                row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
                row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
                return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None, keep: Optional[tuple] = None,
-               prompt_groups=None):
+               prompt_groups=None, segment: Optional[Tuple[int, int]] = None, logits_out: Optional[torch.Tensor] = None,
+               logprobs_out: Optional[torch.Tensor] = None):
         """Two-level sampling: returns (codes_top [B, n], codes_bot [B, n, 4][, logits [n, 5, B, V]][, logprobs [B, n, 5]]).
         ``return_logprobs``: fp32 log-probability of every code the call feeds forward -- the drawn one, or the forced one where ``force_*`` is
         given -- under the raw logits of its draw (T = 1, no cut-off: ``hqt_set_logprob_out``), appended last; with a prefix the positions < P are NaN.
@@ -590,15 +644,23 @@ class Engine:
         ``prefix``; the two rows of a guided pair keep the same positions.
         ``prompt_groups`` (int tensor [B], text models): shared prompts (``hqt_set_prompt_groups``) -- ``cond`` is then [G, ctx_len_txt], one row per DISTINCT prompt,
         and row b of the pass carries ``cond[prompt_groups[b]]``; the prompt prefill runs over the G prompts once and its K/V are copied to the rows.  EXACT returns
-        bit for bit what the call returns with ``cond`` expanded to [B, ctx_len_txt].  Not together with ``prefix`` or ``keep``."""
+        bit for bit what the call returns with ``cond`` expanded to [B, ctx_len_txt].  Not together with ``prefix`` or ``keep``.
+        ``segment`` = (start, stop): the call runs positions [start, stop) of a pass of ``n_steps`` positions (``hqt_set_segment``) and leaves the pass paused behind
+        stop - 1 (stop == n_steps finishes it).  Every tensor keeps its full-length shape; entries outside the segment are neither read nor written, except the
+        codes of position start - 1.  start == 0 begins a pass; start > 0 continues the paused pass of this engine (same batch, n_steps and precision, paused at
+        ``start``: HqtError otherwise) and needs ``out`` -- the tensors the earlier segments wrote, edited or gathered as the caller sees fit.  Samplers, row tables,
+        guidance and keys may differ from segment to segment; all segments together return bit for bit what one call returns.  ``logits_out`` [n, 5, B, V] /
+        ``logprobs_out`` [B, n, 5]: caller-owned buffers the call writes (and returns) in place of fresh ones, so that a segmented pass fills one tensor.  Not
+        together with ``prefix`` or ``keep``; ``prompt_groups`` with start == 0 only."""
         if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
             raise ValueError('out: expected a pair (codes_top [B, n_steps], codes_bot [B, n_steps, 4])')
         outs, logits, logprobs = self._sample_levels(2, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(force_top, force_bot), out=out,
                                            return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
                                            row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance, keep=keep,
-                                           prompt_groups=prompt_groups)
-        return (outs[0], outs[1]) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
+                                           prompt_groups=prompt_groups, segment=segment, logits_out=logits_out, logprobs_out=logprobs_out)
+        return ((outs[0], outs[1]) + ((logits,) if return_logits or logits_out is not None else ())
+                + ((logprobs,) if return_logprobs or logprobs_out is not None else ()))
 
     def sample3(self, batch: int, cond: Optional[torch.Tensor], n_steps: int, *, precision: int = PRECISION_FAST,
                 top_k: Sequence[Optional[int]] = (None, None, None), top_p: Sequence[Optional[float]] = (None, None, None),
@@ -607,17 +669,33 @@ class Engine:
                 use_graph: bool = True, row_seeds: Optional[Sequence[int]] = None, row_offsets: Optional[Sequence[int]] = None,
                 row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
                 return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None, keep: Optional[tuple] = None,
-                prompt_groups=None):
+                prompt_groups=None, segment: Optional[Tuple[int, int]] = None, out: Optional[Sequence[torch.Tensor]] = None,
+                logits_out: Optional[torch.Tensor] = None, logprobs_out: Optional[torch.Tensor] = None):
         """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]][, logprobs [B, n, 21]]); ``row_samplers``,
         ``return_logprobs`` and ``guidance`` (three scales per pair) as in ``sample``;
         ``prefix`` = [[B, P], [B, P, 4], [B, P, 16]]: completion, as in ``sample`` (``hqt_sample_prefix_l3``);
-        ``keep`` = (mask [B, n], [[B, n], [B, n, 4], [B, n, 16]]): kept positions, as in ``sample``; ``prompt_groups``: shared prompts, as in ``sample``."""
+        ``keep`` = (mask [B, n], [[B, n], [B, n, 4], [B, n, 16]]): kept positions, as in ``sample``; ``prompt_groups``: shared prompts, as in ``sample``;
+        ``segment`` / ``logits_out`` / ``logprobs_out``: a segment of a pass, as in ``sample``; ``out`` = the three code tensors to write into, as ``sample`` takes two."""
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 3):
+            raise ValueError('out: expected the three code tensors ([B, n_steps], [B, n_steps, 4], [B, n_steps, 16])')
         outs, logits, logprobs = self._sample_levels(3, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(None,) * 3 if force is None else force,
-                                           out=None, return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
+                                           out=out, return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
                                            row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance, keep=keep,
-                                           prompt_groups=prompt_groups)
-        return tuple(outs) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
+                                           prompt_groups=prompt_groups, segment=segment, logits_out=logits_out, logprobs_out=logprobs_out)
+        return (tuple(outs) + ((logits,) if return_logits or logits_out is not None else ())
+                + ((logprobs,) if return_logprobs or logprobs_out is not None else ()))
+
+    def select_rows(self, rows_from, paused_batch: Optional[int] = None) -> int:
+        """``hqt_select_rows``: re-maps the rows of the pass a ``segment`` call left paused -- afterwards row j of the K/V cache holds what row ``rows_from[j]``
+        held (any mapping: a permutation, a subset, duplicates), and the pass goes on with ``len(rows_from)`` rows.  The codes, keys and conditions are the
+        caller's: gather them with the same mapping.  ``paused_batch``: the rows of the paused pass where the caller knows them (the mapping is then checked on the
+        host, before any engine call; the library checks it in any case).  Asynchronous on torch's current stream.  Returns the new row count."""
+        table = check_select_rows(rows_from, paused_batch, self.max_batch)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.hqt_select_rows(self.h, len(table), table.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+        return len(table)
 
     def score(self, batch: int, cond: Optional[torch.Tensor], codes: Sequence[torch.Tensor], *, precision: int = PRECISION_FAST,
               return_logits: bool = False):

@@ -71,6 +71,7 @@ class _Stage:
             self._engine.close()                     # closes its lanes first
         self._engine = None
         self._lanes = {}
+        self.__dict__.pop('_step_sessions', None)    # (sampling_step: their paused passes lived in the engine that just went)
         for other in self.__dict__.get('_scaled', {}).values():      # HQVAEStage1.at_resolution: engines over the same weights
             other._drop_engine()
 
@@ -175,6 +176,65 @@ class HQTransformerStage2(_Stage):
             e.finalize()
             self._engine = e
         return self._lane(e, lane)
+
+    def sampling_step(self, sos, codes_t=None, codes_b=None, pos_codes=None, use_fp16: bool = True, top_k_top=None, top_p_top=None,
+                      top_k_bot=None, top_p_bot=None, softmax_temperature=(1.0, 1.0), past=None, model_stage1=None, given_top_code=None, *,
+                      seed: Optional[int] = None, max_seq_len: Optional[int] = None, precision: Optional[str] = None):
+        """``iHQGPT.sampling_step`` (hierarchical_ar.py:429-480) with the reference's keyword names, for callers that drive the per-position loop of
+        ``sampling_ihqgpt`` (hqvae/utils/sampling.py:194-235) themselves: one position per call, returns ``(code_top [B, 1], code_bot [B, 1, 4], presents)``.
+        A thin shim over ``pipeline.SamplingSession.advance(1)`` -- the K/V cache lives in the engine, so what differs from the reference is:
+        ``sos`` is the CONDITION, not its embedding (the engine embeds it): class ids int64 [B], prompts int64 [B, ctx_len_txt], or for an unconditional
+        model any tensor with B rows; ``past`` / ``presents`` are opaque one-element tensor lists that only identify the session (``past=None`` begins one,
+        ``torch.stack(presents)`` appended to ``past`` as the reference's loop does carries it on); ``codes_t`` [B, 1] / ``codes_b`` [B, 4] are written into
+        the session's buffers at the previous position before the step, so a loop that alters them is obeyed as the reference obeys it; ``pos_codes`` and
+        ``model_stage1`` are accepted and ignored.  Draws are Philox draws keyed by ``seed=`` (default: from torch's generator, once per session), row and
+        absolute position -- not ``torch.multinomial`` --: a loop of n steps returns the codes of ``sampling_ihqgpt(..., max_seq_len=n, seed=seed)``.
+        ``given_top_code`` [B]: the top code of this position is the given one, as in the reference (hierarchical_ar.py:768-774) -- it is fed forward and
+        returned as ``code_top`` (the session's ``codes`` hold it, not the discarded draw).
+        ``max_seq_len`` (read when the session begins; default ctx_len_img): the positions of the pass.  Two code levels only.  One session at a time: the
+        shim runs on lane 0, whose engine holds one paused pass, so beginning a session (``past=None``) ends and forgets an unfinished earlier one."""
+        from .pipeline import SamplingSession
+        if self.spec.levels != 2:
+            raise ValueError('sampling_step is the two-level iHQGPT step; drive a three-level pass with pipeline.SamplingSession')
+        sessions = self.__dict__.setdefault('_step_sessions', {})
+        if past is None:
+            cond = torch.as_tensor(sos)
+            if (self.use_cls_cond or self.use_txt_cond) and (cond.dtype.is_floating_point or cond.dim() != (2 if self.use_txt_cond else 1)):
+                raise ValueError('sampling_step: sos is the condition itself here -- class ids int64 [B] or prompts int64 [B, ctx_len_txt] --, not its embedding '
+                                 '(the engine embeds it)')
+            n = int(max_seq_len) if max_seq_len is not None else self.spec.ctx_len_img
+            session = SamplingSession(self, int(cond.shape[0]), cond, n, seed=seed, use_fp16=use_fp16, precision=precision)
+            key = self.__dict__['_step_next'] = self.__dict__.get('_step_next', 0) + 1
+            sessions.clear()                         # (the new pass overwrites the cache an abandoned loop's paused pass lived in)
+            sessions[key] = session
+        else:
+            key = int(torch.as_tensor(past[-1]).reshape(-1)[0])
+            session = sessions.get(key)
+            if session is None:
+                raise ValueError('sampling_step: past does not belong to a running session of this model (it is finished, or came from another model)')
+        pos = session.position
+        if pos > 0 and codes_t is not None:
+            session.codes[0][:, pos - 1] = torch.as_tensor(codes_t).reshape(session.B).to(session.codes[0].device)
+        if pos > 0 and codes_b is not None:
+            session.codes[1][:, pos - 1] = torch.as_tensor(codes_b).reshape(session.B, 4).to(session.codes[1].device)
+        force = None
+        if given_top_code is not None:
+            if self.spec.depth_decoding == 'bidirectional':
+                raise ValueError("given_top_code is not supported by the 'bidirectional' depth head (the reference ignores it)")
+            # ONE forced tensor per session (a stable pointer: the captured graph is replayed, not captured anew at every position).  A forced level is read
+            # from it at position pos - 1 as well -- the engine takes the previous codes of a level from force_* where one is given --, so it carries that code
+            top = session.__dict__.setdefault('_given_top', torch.zeros_like(session.codes[0]))
+            if pos > 0:
+                top[:, pos - 1] = session.codes[0][:, pos - 1]
+            top[:, pos] = torch.as_tensor(given_top_code).reshape(session.B).to(top.device)
+            force = [top, None]
+        session.advance(1, force=force, top_k_top=top_k_top, top_p_top=top_p_top, top_k_bot=top_k_bot, top_p_bot=top_p_bot,
+                        softmax_temperature=softmax_temperature)
+        if force is not None:
+            session.codes[0][:, pos] = force[0][:, pos]
+        if session.done:
+            del sessions[key]
+        return session.codes[0][:, pos:pos + 1], session.codes[1][:, pos:pos + 1], [torch.tensor([key], dtype=torch.int64)]
 
 
 class HQVAEStage1(_Stage):

@@ -20,8 +20,9 @@ from typing import Any, Callable, List, NamedTuple, Optional, Tuple
 import torch
 
 from ._lib import POLICY_LATENCY, POLICY_THROUGHPUT
-from .sampling import (_batch_and_cond, _precision, guidance_scales, negative_cond, rearrange_levels, sampling_hqtransformer,
-                       sampling_ihqgpt)
+from .engine import check_select_rows
+from .sampling import (_batch_and_cond, _precision, _seed_from_torch, guidance_scales, negative_cond, prompt_groups_of, rearrange_levels,
+                       sampling_hqtransformer, sampling_ihqgpt)
 
 
 # Code levels travel as one list, coarse to fine.  These are the only places that tell two levels from three: the sampler call, and the
@@ -173,7 +174,189 @@ def score_images(model, images: torch.Tensor, cond=None, encode_precision: Optio
     return sequence_logprob(score_codes(model.stage2, codes, cond, one_pass=True, **score_kw)), codes
 
 
-def sample_best_of(stage2, cond, num_candidates: int, keep: int, share_prompts: bool = False, **sampler) -> Tuple[list, torch.Tensor]:
+def session_cutoffs(levels: int, kw: dict) -> Tuple[tuple, tuple, tuple]:
+    """Sampler keywords of ``sampling_ihqgpt`` (two levels) / ``sampling_hqtransformer`` (three; missing = the sampler's default) ->
+    ``(top_k, top_p, temperature)`` per level, what ``Engine.sample`` / ``sample3`` take."""
+    L = int(levels)
+    if L == 3:
+        top_k, top_p = (tuple(kw[k]) if kw.get(k) is not None else (None,) * 3 for k in ('top_k', 'top_p'))
+    else:
+        top_k, top_p = (kw.get('top_k_top'), kw.get('top_k_bot')), (kw.get('top_p_top'), kw.get('top_p_bot'))
+    t = kw.get('softmax_temperature')
+    temperature = tuple(float(v) for v in t) if t is not None else (1.0,) * L
+    if not (len(temperature) == len(top_k) == len(top_p) == L):
+        raise ValueError(f'sampler settings of a {L}-level model need {L} entries each, got {kw}')
+    return top_k, top_p, temperature
+
+
+class SamplingSession:
+    """A sampling pass that can stop between two positions (``hqt_set_segment`` / ``hqt_select_rows``): ``advance`` draws the next positions, ``select``
+    re-maps the rows -- reorder, drop, fork -- and ``finish`` draws what remains.  All segments together draw bit for bit what ONE sampler call with the same
+    keys draws: ``SamplingSession(stage2, B, cond, n, seed=s).finish()`` equals ``sampling_ihqgpt(stage2, B, cond, max_seq_len=n, seed=s)``.
+    The session owns the code tensors (``codes``: the levels as one list, full length; positions >= ``position`` are not drawn yet), the optional
+    log-probabilities (``return_logprobs=True``: fp32 [B, n, draws], NaN where not drawn) and one explicit Philox key per row -- ``row_seeds`` / ``row_offsets``,
+    default ``(seed, sample_offset + b)``, the implicit keys of a plain call -- so that a row keeps its identity, and goes on drawing what it would have drawn,
+    wherever ``select`` puts it.  ``cond`` as in ``sampling_ihqgpt``; ``sampler``: its sampler keywords (``top_k_top`` ... / ``top_k``, ``top_p``,
+    ``softmax_temperature``), ``row_samplers`` and ``guidance`` (a ready pair table over the rows), the defaults of every ``advance``.
+    ``share_prompts`` (text models): the first segment prefills every distinct prompt once.  One session at a time per engine lane: any other sampling or scoring
+    call on the lane ends the paused pass, and the next ``advance`` raises ``HqtError``.  Not with ``prefix_codes``, ``keep_mask`` or ``guidance_scale``."""
+    _DEFAULTS = SAMPLER_KEYS + ('row_samplers', 'guidance')
+
+    def __init__(self, stage2, num_candidates: int, cond, n: int = 64, *, seed: Optional[int] = None, sample_offset: int = 0, row_seeds=None,
+                 row_offsets=None, precision: Optional[str] = None, use_fp16: bool = True, use_graph: bool = True, lane: int = 0,
+                 return_logprobs: bool = False, share_prompts: bool = False, **sampler):
+        unknown = set(sampler) - set(self._DEFAULTS)
+        if unknown:
+            raise TypeError(f'SamplingSession: unexpected keywords {sorted(unknown)} (sampler settings, row_samplers and guidance travel here)')
+        self.stage2, self.L, self.n = stage2, int(stage2.spec.levels), int(n)
+        if not 1 <= self.n <= stage2.spec.ctx_len_img:
+            raise ValueError(f'n={self.n} outside [1, ctx_len_img={stage2.spec.ctx_len_img}]')
+        self.B, self.cond = _batch_and_cond(stage2, int(num_candidates), cond)
+        if share_prompts and not stage2.use_txt_cond:
+            raise ValueError('share_prompts needs a text-conditional model: one embedding row per sample leaves no prefill to share')
+        session_cutoffs(self.L, sampler)
+        self.sampler, self.share_prompts = dict(sampler), bool(share_prompts)
+        if (row_seeds is None) != (row_offsets is None):
+            raise ValueError('row_seeds and row_offsets come together')
+        if row_seeds is None:
+            seed = _seed_from_torch() if seed is None else int(seed)
+            row_seeds, row_offsets = [seed] * self.B, [int(sample_offset) + b for b in range(self.B)]
+        if len(row_seeds) != self.B or len(row_offsets) != self.B:
+            raise ValueError(f'row_seeds and row_offsets: {self.B} entries each')
+        self.row_seeds, self.row_offsets = [int(v) for v in row_seeds], [int(v) for v in row_offsets]
+        self.precision, self.use_graph = _precision(precision, use_fp16), bool(use_graph)
+        self.engine = stage2.engine(self.B, self.n, lane)
+        dev = self.engine.device
+        self.position = 0
+        self.codes = [torch.zeros((self.B, self.n) + ((4 ** l,) if l else ()), dtype=torch.int64, device=dev) for l in range(self.L)]
+        self.logprobs = torch.full((self.B, self.n, (4 ** self.L - 1) // 3), float('nan'), dtype=torch.float32, device=dev) if return_logprobs else None
+
+    @property
+    def done(self) -> bool:
+        return self.position >= self.n
+
+    def advance(self, k: Optional[int] = None, force=None, **overrides) -> list:
+        """Draws the next ``k`` positions (None: all that remain) and returns the codes so far, ``[c[:, :position] for c in codes]``.  ``overrides``: sampler
+        keywords, ``row_samplers`` or ``guidance`` for THIS call in place of the session's; ``force``: one entry per level, None or a full-length code tensor
+        fed forward in place of the draws (``force_top`` / ``force_bot`` of ``Engine.sample``).  Codes of position ``position - 1`` that the caller has edited in
+        ``codes`` are what the pass goes on from -- for a level that is NOT forced: the engine reads the previous codes of a forced level from its ``force``
+        tensor, which must therefore hold the code of position ``position - 1`` as well as those of the positions this call draws."""
+        unknown = set(overrides) - set(self._DEFAULTS)
+        if unknown:
+            raise TypeError(f'advance: unexpected keywords {sorted(unknown)}')
+        if self.done:
+            raise ValueError(f'the session is finished: all {self.n} positions are drawn')
+        k = self.n - self.position if k is None else int(k)
+        if k < 1 or self.position + k > self.n:
+            raise ValueError(f'advance(k={k}) at position {self.position}: expected 1 <= k <= {self.n - self.position} remaining positions')
+        kw = {**self.sampler, **overrides}
+        top_k, top_p, temperature = session_cutoffs(self.L, kw)
+        start, stop = self.position, self.position + k
+        cond, extra = self.cond, {}
+        if self.share_prompts and start == 0:
+            cond, extra['prompt_groups'] = prompt_groups_of(self.cond)
+        force = [None] * self.L if force is None else list(force)
+        if len(force) != self.L:
+            raise ValueError(f'force: expected one entry per code level ({self.L}), None where a level is drawn')
+        common = dict(precision=self.precision, top_k=top_k, top_p=top_p, temperature=temperature, seed=0, use_graph=self.use_graph,
+                      row_seeds=self.row_seeds, row_offsets=self.row_offsets, row_samplers=kw.get('row_samplers'), guidance=kw.get('guidance'),
+                      out=self.codes, segment=(start, stop), logprobs_out=self.logprobs, **extra)
+        if self.L == 3:
+            self.engine.sample3(self.B, cond, self.n, force=force, **common)
+        else:
+            self.engine.sample(self.B, cond, self.n, force_top=force[0], force_bot=force[1], **common)
+        self.position = stop
+        return [c[:, :stop] for c in self.codes]
+
+    def select(self, rows_from, row_seeds=None, row_offsets=None, guidance=None) -> None:
+        """Row j of the session becomes what row ``rows_from[j]`` was: the K/V cache (one gather on the device, ``hqt_select_rows``), the codes, the
+        log-probabilities, the conditions, the Philox keys and the session's ``row_samplers`` table.  Any mapping: a permutation, a subset (prune), duplicates
+        (fork).  Rows that share a key go on drawing the same codes; ``row_seeds`` / ``row_offsets`` (both, one entry per NEW row) give forked rows keys of
+        their own.  A session built with a ``guidance`` pair table names rows by index, which no mapping carries over: ``guidance=`` gives the table over the
+        NEW rows (``[]``: none from here on), and ValueError without it."""
+        if self.done:
+            raise ValueError('select on a finished session: nothing is left to draw')
+        table = check_select_rows(rows_from, self.B, self.engine.max_batch)
+        if self.sampler.get('guidance') and guidance is None:
+            raise ValueError('select: the session\'s guidance pairs name rows by index -- pass guidance= with the pair table over the new rows ([]: none)')
+        if (row_seeds is None) != (row_offsets is None):
+            raise ValueError('row_seeds and row_offsets come together')
+        if row_seeds is not None and (len(row_seeds) != len(table) or len(row_offsets) != len(table)):
+            raise ValueError(f'row_seeds and row_offsets: {len(table)} entries each, one per new row')
+        if self.position > 0:                        # (before the first position the cache holds nothing of this pass)
+            self.engine.select_rows(table, self.B)
+        rows = [int(r) for r in table]
+        idx = torch.as_tensor(rows, dtype=torch.int64, device=self.codes[0].device)
+        self.codes = [c.index_select(0, idx) for c in self.codes]
+        if self.logprobs is not None:
+            self.logprobs = self.logprobs.index_select(0, idx)
+        if self.cond is not None:
+            self.cond = torch.as_tensor(self.cond)
+            self.cond = self.cond.index_select(0, idx.to(self.cond.device))
+        self.row_seeds = [self.row_seeds[r] for r in rows] if row_seeds is None else [int(v) for v in row_seeds]
+        self.row_offsets = [self.row_offsets[r] for r in rows] if row_offsets is None else [int(v) for v in row_offsets]
+        if self.sampler.get('row_samplers') is not None:
+            self.sampler['row_samplers'] = [self.sampler['row_samplers'][r] for r in rows]
+        if guidance is not None:
+            self.sampler['guidance'] = list(guidance) or None
+        self.B = len(rows)
+
+    def finish(self) -> list:
+        """Draws what remains (nothing, when the session is done) and returns the full-length codes."""
+        if not self.done:
+            self.advance()
+        return self.codes
+
+
+def check_prune(prune, num_candidates: int, keep: int, n: int) -> list:
+    """``prune`` of ``sample_best_of`` checked on the host, before any engine is built: a list ``[(position, survivors_per_group), ...]`` with positions
+    ascending inside [1, n - 1] and survivors descending, below ``num_candidates`` and never below ``keep``.  Returns it as a list of int pairs."""
+    if not isinstance(prune, (list, tuple)) or not prune:
+        raise ValueError('prune: expected a list [(position, survivors_per_group), ...]')
+    plan, last_pos, last_s = [], 0, int(num_candidates)
+    for entry in prune:
+        if not isinstance(entry, (list, tuple)) or len(entry) != 2:
+            raise ValueError(f'prune: expected (position, survivors_per_group) entries, got {entry!r}')
+        pos, s = int(entry[0]), int(entry[1])
+        if pos <= last_pos or pos >= int(n):
+            raise ValueError(f'prune: positions must ascend inside [1, n - 1 = {int(n) - 1}], got {pos} after {last_pos}')
+        if s >= last_s or s < int(keep):
+            raise ValueError(f'prune: survivors must descend and stay at or above keep={int(keep)}, got {s} after {last_s}')
+        plan.append((pos, s))
+        last_pos, last_s = pos, s
+    return plan
+
+
+def prune_survivors(scores: torch.Tensor, survivors: int) -> torch.Tensor:
+    """``scores`` [groups, candidates] -> int64 [groups, survivors]: per group the ``rank_candidates`` winners (ties to the lower index), listed in ASCENDING
+    candidate index -- the order they keep among the rows of the pass, so that the final ranking breaks ties as the unpruned call does."""
+    return torch.sort(rank_candidates(scores, survivors), dim=1).values
+
+
+def _best_of_pruned(stage2, G: int, C: int, K: int, rows, plan, sampler: dict) -> Tuple[list, torch.Tensor]:
+    for k in ('prefix_codes', 'keep_mask', 'kept_codes'):
+        if sampler.get(k) is not None:
+            raise ValueError(f'prune together with {k} is not built (segments of a pass with a code prefix or a keep table)')
+    if sampler.get('guidance_scale') is not None or sampler.get('neg_cond') is not None:
+        raise ValueError('prune together with guidance_scale is not built: lay the rows out yourself (SamplingSession, guidance=)')
+    sampler = {k: v for k, v in sampler.items() if k not in ('is_tqdm', 'model_stage1')}
+    n = int(sampler.pop('max_seq_len', 256))
+    session = SamplingSession(stage2, G * C, rows, n, return_logprobs=True, **sampler)
+    cur = C
+    for pos, s in plan:
+        session.advance(pos - session.position)
+        scores = sequence_logprob(session.logprobs[:, :pos]).reshape(G, cur)
+        idx = prune_survivors(scores, s)                                       # [G, s], candidate indices among the cur rows of the group
+        session.select((idx + torch.arange(G, device=idx.device).unsqueeze(1) * cur).reshape(-1).cpu())
+        cur = s
+    codes = session.finish()
+    scores = sequence_logprob(session.logprobs).reshape(G, cur)
+    idx = rank_candidates(scores, K)
+    flat = (idx + torch.arange(G, device=idx.device).unsqueeze(1) * cur).reshape(-1)
+    return [c.index_select(0, flat) for c in codes], scores.gather(1, idx)
+
+
+def sample_best_of(stage2, cond, num_candidates: int, keep: int, share_prompts: bool = False, prune=None, **sampler) -> Tuple[list, torch.Tensor]:
     """Sample ``num_candidates`` per condition and keep the ``keep`` most likely: ``cond`` = class ids (an int, or a tensor / list of G ids), text prompts
     [G, ctx_len_txt], or anything for an unconditional model (one group).  ONE sampler call over all G * num_candidates rows (group-major: row
     g * num_candidates + c), keywords of ``sampling_ihqgpt`` / ``sampling_hqtransformer`` in ``sampler``; every candidate is scored by
@@ -181,10 +364,16 @@ def sample_best_of(stage2, cond, num_candidates: int, keep: int, share_prompts: 
     the completed positions only; with ``guidance_scale`` -- ``neg_cond`` then per group, like ``cond`` -- under the guided logits) and ranked within its group, descending, ties to the lower candidate index; codes and scores are gathered on the
     device.  Returns ``(codes, scores)``: the code levels as one list, [G * keep, n], [G * keep, n, 4][, ...], group-major, best first, and fp64 [G, keep].
     ``share_prompts=True`` (text models): the ``num_candidates`` rows of a caption are one prompt -- it is prefilled once and handed to them
-    (``sampling_ihqgpt``; with ``guidance_scale`` the negative rows are deduplicated too)."""
+    (``sampling_ihqgpt``; with ``guidance_scale`` the negative rows are deduplicated too).
+    ``prune`` = ``[(position, survivors_per_group), ...]`` (positions ascending, survivors descending, never below ``keep``): the pass stops behind each
+    position, ranks every group by ``sequence_logprob`` of the positions drawn so far (ties to the lower candidate index) and goes on with the survivors only
+    (``SamplingSession.select``), so a discarded candidate costs the positions up to its cut, not all of them.  Survivors draw what they draw unpruned (their
+    Philox keys travel with them; bit for bit in 'exact').  None: the one call above, untouched.  Not together with ``prefix_codes``, ``keep_mask`` or
+    ``guidance_scale``."""
     C, K = int(num_candidates), int(keep)
     if not 1 <= K <= C:
         raise ValueError(f'keep={K} outside [1, num_candidates={C}]')
+    plan = None if prune is None else check_prune(prune, C, K, int(sampler.get('max_seq_len', 256)))
     if stage2.use_txt_cond:
         cond = torch.as_tensor(cond)
         if cond.dim() != 2:
@@ -203,6 +392,8 @@ def sample_best_of(stage2, cond, num_candidates: int, keep: int, share_prompts: 
         sampler['neg_cond'] = neg.repeat_interleave(C, dim=0) if int(neg.shape[0]) == G and G > 1 else neg
     if share_prompts:
         sampler['share_prompts'] = True
+    if plan is not None:
+        return _best_of_pruned(stage2, G, C, K, rows, plan, sampler)
     *codes, logprobs = sample_codes(stage2, G * C, rows, return_logprobs=True, **sampler)
     prefix = sampler.get('prefix_codes')
     P = 0 if prefix is None else int(torch.as_tensor(prefix[0]).shape[-1])

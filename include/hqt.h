@@ -288,6 +288,40 @@ int hqt_set_keep_mask(hqt_handle* h, int B, int n_steps, const uint8_t* keep, co
  * and fails with HQT_ERR_STATE.  Without a staged table a call launches exactly what it launched before. */
 int hqt_set_prompt_groups(hqt_handle* h, int B, int n_groups, const int32_t* group_of_row);
 
+/* hqt_set_segment -- the engine side of the reference's per-position loop (sampling_ihqgpt calls stage2.sampling_step once per position, hqvae/utils/sampling.py:
+ * 194-235, and its caller may look at, or change, the codes between two of them): a pass that stops behind any position and goes on later, bit for bit.  The
+ * segment is STAGED on the handle (a lane from hqt_clone has its own): the next hqt_sample / hqt_sample_l3 on that handle takes it and clears it, whether that
+ * call succeeds or not; a NULL handle is HQT_ERR_INVALID.  The taking call runs positions [start, stop) of a pass that is opts->n_steps positions long.  Every
+ * buffer keeps its full-length layout and absolute indexing -- out_*, force_*, noise, logits_out, a staged hqt_set_logprob_out buffer --; entries outside
+ * [start, stop) are neither read nor written, except that the codes of position start - 1 are read.
+ *   start == 0  the call launches what a plain call launches for those positions (text models: the prompt prefill too, and a staged hqt_set_prompt_groups table
+ *               is allowed), stops behind position stop - 1 and leaves the step state there.  The handle records the PAUSED pass: B, n_steps, code levels,
+ *               precision and position = stop.
+ *   start > 0   needs a paused pass on this handle with the same B, n_steps, code levels and precision and with position == start; anything else is
+ *               HQT_ERR_STATE, with a message naming what differs (the paused pass is kept).  The call sets the Philox keys and any staged table as every call
+ *               does, does NOT reset the step state, runs no prefill, and runs stop - start decode steps, eager or from the graph (the graph key is what it was;
+ *               the positions per graph launch are chosen from stop - start).  The codes of position start - 1 are read from this call's own out_* buffers (a
+ *               forced level: from force_*): the caller passes buffers that hold them, and if it has edited them since they were drawn the pass goes on as if the
+ *               edited codes had been drawn.
+ *   stop == n_steps: the pass is finished and the record is cleared.
+ * Row-sampler tables, guidance tables, the log-probability buffer, row_seeds / row_offsets and logits_out work in every segment as in a whole call, so settings
+ * may change from one segment to the next: Philox keys are (seed, global row, ABSOLUTE position, draw, chunk), and between two positions a row's whole state is its
+ * body K/V rows, the step state and the codes in the caller's buffers (the depth cache is rebuilt every position).
+ * HQT_ERR_INVALID in the taking call, with a message naming the cause: stop <= start, start < 0 or stop > n_steps; a prefix entry point; a staged keep table;
+ * a staged prompt-group table with start > 0.  The record of a paused pass is cleared by every other call that writes the body cache or the step state: a plain or
+ * prefix sampling call, a segment with start == 0, hqt_score.  Without a staged segment a call launches exactly what it launched before.
+ * Not built: segments together with keep tables or code prefixes; rows of one pass at different positions (a per-row t_base in every attention kernel).
+ *
+ * hqt_select_rows -- re-maps the rows of the paused pass: afterwards cache row j of every body layer holds what row rows_from[j] held, for the live rows
+ * 0 .. t_base - 1 (text models: the prompt rows and the drawn positions), K and V, in the cache's type for the paused precision; the paused B becomes B_new.
+ * `rows_from` is a HOST array of B_new entries in [0, paused B), 1 <= B_new <= max_batch, copied before return; any mapping: the identity, a permutation, a subset
+ * (drop rows), duplicates (fork rows), B_new above the paused B.  The codes are the caller's tensors: the caller gathers them itself, and gives forked rows new
+ * Philox keys (row_seeds / row_offsets) where they are to differ.  The step state does not change.  One launch (timing slot "kv_gather_rows"), in place through
+ * LDS, on `stream`; allocates no device memory (the table travels through the pinned staging ring of the row tables).  HQT_ERR_STATE: no paused pass.  HQT_ERR_INVALID: a NULL argument, B_new outside [1, max_batch], an entry out of range,
+ * B_new * 16 bytes beyond the 160 KiB of LDS of a compute unit (10240 rows). */
+int hqt_set_segment(hqt_handle* h, int start, int stop);
+int hqt_select_rows(hqt_handle* h, int B_new, const int32_t* rows_from, void* stream);
+
 /* hqt_sample -- replaces sampling_ihqgpt + iHQGPT.sampling_step (hqvae/utils/sampling.py:164-237,
  * hierarchical_ar.py:428-480, 482-563, 667-789) for a batch of B independent images.
  *   cond        int64 [B] class ids (HQT_COND_CLASS), int64 [B, ctx_len_txt] token ids
