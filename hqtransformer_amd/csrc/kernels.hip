@@ -590,8 +590,12 @@ hipError_t launch_bidir_head_ln(const LNArgs& a, hipStream_t st) {
 // One 256-thread workgroup per logits row.  Restates hqvae/utils/sampling.py:12-37 and
 // hierarchical_ar.py:762-785; torch.multinomial(p, 1) == argmax(p / q), q ~ Exp(1).
 // ---------------------------------------------------------------------------------------------
+// The radix key of the top-k select: unsigned order == float order.  Both zeros get the key of +0.0: the reference masks `logits < kth`
+// (sampling.py:18), where -0.0 is not below +0.0, and a tiny negative logit divided by the temperature underflows to -0.0 -- with the sign
+// bit in the key such a token was masked whenever the k-th largest value was +0.0 (tests/test_gpu_sampler_rows.py).
 __device__ __forceinline__ uint32_t f2ord(float f) {
-    const uint32_t u = __float_as_uint(f);
+    uint32_t u = __float_as_uint(f);
+    if ((u << 1) == 0u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ uint32_t mulhi32(uint32_t a, uint32_t b) { return __umulhi(a, b); }
