@@ -145,37 +145,40 @@ struct hqt_handle {
     // per-row keys of merged steps travel through a ring of PINNED staging buffers (an asynchronous copy from pinned memory reads its
     // source when the stream gets there: a buffer is rewritten only after the copy that last read it has completed, hipEventSynchronize)
     static constexpr int ROWS_RING = 4;
-    RowKey* rows_pinned[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};       // each: RowKey[max_batch], then RowSampler[max_batch], then GuidePair[guide_room], then the group table int32[max_batch], then the keep mask [max_batch * max_steps]
+    RowKey* rows_pinned[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};       // each: the five tables of a RingSlot (ring_slot)
     hipEvent_t rows_ev[ROWS_RING] = {nullptr, nullptr, nullptr, nullptr};
     bool rows_busy[ROWS_RING] = {false, false, false, false};
     int rows_next = 0;
     RowSampler* row_set = nullptr;            // [max_batch] per-row sampler settings of the current call (hqt_set_row_samplers)
-    std::vector<hqt_row_sampler> row_set_staged;   // host table waiting for the next hqt_sample / hqt_sample_l3 of this handle, which takes it
-    float* logprob_staged = nullptr;          // hqt_set_logprob_out: device fp32 [B, n_steps, draws] the next sampling call of this handle takes (and clears)
     GuidePair* guide = nullptr;               // [guide_room()] pair table of the current call (hqt_set_guidance)
-    std::vector<hqt_guide_pair> guide_staged; // host table waiting for the next sampling call of this handle, which takes it
     size_t guide_room() const { return (size_t)std::max(1, cfg.max_batch / 2); }      // a row is in at most one pair
-    // hqt_set_keep_mask: host mask [keep_B, keep_n] and one device pointer per level, waiting for the next hqt_sample / hqt_sample_l3 of this handle, which takes them
-    std::vector<uint8_t> keep_staged;
-    int keep_B = 0, keep_n = 0;
-    const int64_t* keep_codes[3] = {nullptr, nullptr, nullptr};
     unsigned char* keep_mask = nullptr;       // [max_batch * max_steps] mask of the current call
-    // hqt_set_prompt_groups: host table [B] of prompt indices in [0, groups_G), waiting for the next hqt_sample / hqt_sample_l3 of this handle, which takes it
-    std::vector<int32_t> groups_staged;
-    int groups_G = 0;
     int* group_of_row = nullptr;              // [max_batch] group table of the current call
+    // What the hqt_set_* calls leave for the next hqt_sample / hqt_sample_l3 (or prefix entry point) of this handle, which takes all of it
+    struct Staged {
+        std::vector<hqt_row_sampler> row_set;     // hqt_set_row_samplers: host table
+        float* logprob = nullptr;                 // hqt_set_logprob_out: device fp32 [B, n_steps, draws]
+        std::vector<hqt_guide_pair> guide;        // hqt_set_guidance: host table
+        std::vector<uint8_t> keep;                // hqt_set_keep_mask: host mask [keep_B, keep_n] and one device pointer per level
+        int keep_B = 0, keep_n = 0;
+        const int64_t* keep_codes[3] = {nullptr, nullptr, nullptr};
+        std::vector<int32_t> groups;              // hqt_set_prompt_groups: host table [B] of prompt indices in [0, groups_G)
+        int groups_G = 0;
+        bool seg = false;                         // hqt_set_segment: positions [seg_start, seg_stop)
+        int seg_start = 0, seg_stop = 0;
+        // what hqt_score refuses; deliberately not the segment: one staged alone is cleared there without a refusal
+        bool holds_table() const { return !row_set.empty() || logprob || !guide.empty() || !keep.empty() || !groups.empty(); }
+    } staged;
+    Staged take_staged() { Staged s = std::move(staged); staged = Staged(); return s; }
+    void clear_staged() { staged = Staged(); }
     // staging of a shared prefill, sized (grown) by hqt_set_prompt_groups and by nothing else: K and V of [n_layers][pg_cap][ctx_len_txt][D] at 4 bytes
     // per element (any mode's activation type fits), and the [max_batch, D] fp32 rows the fan-out gathers for the depth head of position 0
     void *pg_k = nullptr, *pg_v = nullptr;
     float* pg_x = nullptr;
     int pg_cap = 0;                           // prompts the staging holds
     size_t pg_bytes = 0;                      // bytes of pg_k (= pg_v)
-    // hqt_set_segment: positions [seg_start, seg_stop) waiting for the next hqt_sample / hqt_sample_l3 of this handle, which takes them
-    bool seg_staged = false;
-    int seg_start = 0, seg_stop = 0;
     // the pass a segment stopped in: what a continuation must match, and `pos`, the position it goes on from (the step state says pos over t_live keys)
     struct Paused { bool live = false; int B = 0, n_steps = 0, levels = 0, precision = 0, pos = 0; } paused;
-    void clear_staged() { row_set_staged.clear(); logprob_staged = nullptr; guide_staged.clear(); keep_staged.clear(); groups_staged.clear(); seg_staged = false; }
     int64_t *cond_buf = nullptr, *codes_top = nullptr, *codes_bot = nullptr;   // call-independent homes of cond / the drawn codes
     int64_t* codes_l2 = nullptr;              // third level: [B, max_steps, 16]
     Lin head_l2;                              // head_levels.2 (three-level models; head_top / head_bot hold levels 0 / 1)
@@ -652,14 +655,9 @@ extern "C" int hqt_clone(hqt_handle* src, hqt_handle** out) {
     h->pend = {nullptr, 0, 0, nullptr};
     for (int i = 0; i < hqt_handle::ROWS_RING; ++i) { h->rows_pinned[i] = nullptr; h->rows_ev[i] = nullptr; h->rows_busy[i] = false; }
     h->rows_next = 0;
-    h->row_set_staged.clear();                   // a lane has its own table
-    h->logprob_staged = nullptr;                 // ... and its own log-probability buffer
-    h->guide_staged.clear();                     // ... and its own pair table
-    h->keep_staged.clear();                      // ... and its own keep table
-    h->groups_staged.clear();                    // ... and its own group table and staging (hqt_set_prompt_groups on the lane sizes it)
-    h->pg_k = h->pg_v = nullptr; h->pg_x = nullptr; h->pg_cap = 0; h->pg_bytes = 0;
-    h->seg_staged = false;                       // ... and its own segment and paused pass
-    h->paused = hqt_handle::Paused();
+    h->clear_staged();                           // a lane has its own staged tables, buffer and segment
+    h->pg_k = h->pg_v = nullptr; h->pg_x = nullptr; h->pg_cap = 0; h->pg_bytes = 0;      // ... its own prefill staging (hqt_set_prompt_groups on the lane sizes it)
+    h->paused = hqt_handle::Paused();            // ... and its own paused pass
     h->nparts = h->npartsd = 0;
     h->pbody.d_phases = nullptr; h->pfull.d_phases = nullptr;      // phase tables hold workspace pointers: bound per handle (persist_bind)
     h->persist_used = false; h->persist_tripped = false; h->capture_persist = false; h->graph_has_persist = false;
@@ -1156,6 +1154,7 @@ static int ar_linear(hqt_handle* h, const Mode& md, GemmArgs g, const Lin& l, in
 }
 
 // ------------------------------------------------------------------------------------------ stage 2
+static const int LEVEL_WIDTH[3] = {1, 4, 16};    // codes per position of each code level
 struct SamplerSet { float temperature = 1.f; int top_k = 0; float top_p = 0.f; };   // one code level's sampler settings
 struct SampleCtx {
     int B;
@@ -1168,7 +1167,7 @@ struct SampleCtx {
     const int64_t* row_offsets;
     SamplerSet lv[3];
     const hqt_row_sampler* row_set = nullptr;    // host table of B rows staged by hqt_set_row_samplers: in place of lv[] (which then holds defaults)
-    bool row_top_p = false;                      // some row of it uses top-p
+    bool top_p = false, row_top_p = false;       // some level (or row of the table) uses top-p; row_top_p: and it is a row of the table
     const float* noise;
     const int64_t* feed[3] = {nullptr, nullptr, nullptr};   // codes each level's embeddings read: the drawn ones (out) or the forced ones
     int64_t* out[3] = {nullptr, nullptr, nullptr};
@@ -1525,10 +1524,10 @@ static int run_head(hqt_handle* h, const SampleCtx& c, const Lin& head, int lv, 
 // sampler); out_stride > 0: each token writes slot out_slot of an out_stride-wide code group (the 21-step causal head)
 struct SubStep { int lv, Tq, tbase, out_stride, out_slot; };
 static SubStep sub_step(const hqt_config& cf, int sub) {
-    static const int first[3] = {0, 1, 5}, width[3] = {1, 4, 16};
-    if (cf.depth_decoding != HQT_DEPTH_TOP2MID2BOT) return {sub, width[sub], first[sub], 0, 0};
+    static const int first[3] = {0, 1, 5};
+    if (cf.depth_decoding != HQT_DEPTH_TOP2MID2BOT) return {sub, LEVEL_WIDTH[sub], first[sub], 0, 0};
     const int lv = sub == 0 ? 0 : (sub < 5 ? 1 : 2);
-    return {lv, 1, sub, lv ? width[lv] : 0, sub - first[lv]};
+    return {lv, 1, sub, lv ? LEVEL_WIDTH[lv] : 0, sub - first[lv]};
 }
 
 // The input rows of depth sub-step `sub` in xd (dln: with their packed copy and row statistics)
@@ -1572,6 +1571,27 @@ static bool depth_dln(hqt_handle* h, const SampleCtx& c, const SubStep& s) {
     return h->cfg.depth_decoding != HQT_DEPTH_BIDIRECTIONAL && dln_ok(h, c, h->depth[0], c.B * s.Tq) && heads[s.lv]->wpk_ln;
 }
 
+// The bidirectional head behind its input launch: one pass of the depth blocks over the depth_rows rows per sample in xd, then ln_top / ln_bot of the
+// interleaved rows into two compact head operands, normed[0] = [B, D] (hbuf) and normed[1] = [4 B, D] (abuf)
+static int run_bidir_tail(hqt_handle* h, const SampleCtx& c, bool dln, void** normed) {
+    const int B = c.B, M = B * h->depth_rows;
+    CHK(run_depth(h, c, dln, h->depth_rows, 0));      // Tq = 5 > 1: never the single-key shortcut of run_block
+    Timed t(h, "bidir_head_ln", c.st);
+    LNArgs ln{h->xd, W(h, "ln_top.weight"), W(h, "ln_top.bias"), nullptr, h->hbuf, M, h->cfg.embed_dim, 1, 0, 1e-5f, c.md.act_dt(), head_pk(c, h->head_top, B)};
+    ln.gamma2 = W(h, "ln_bot.weight"); ln.beta2 = W(h, "ln_bot.bias"); ln.y2 = h->abuf; ln.out2_packed_mb = head_pk(c, h->head_bot, 4 * B);
+    take_pend(h, ln);
+    HIPCHK(launch_bidir_head_ln(ln, c.st));
+    normed[0] = h->hbuf; normed[1] = h->abuf;
+    return HQT_OK;
+}
+
+// Split-K slabs the last body GEMM left for "the next LayerNorm" belong to all M rows of x: folded into them here through ln_f (the normalised rows in hbuf
+// are not read), before anything gathers x and before the depth GEMMs reuse the slab workspace
+static int fold_pending(hqt_handle* h, const SampleCtx& c, int M) {
+    if (!h->pend.slabs) return HQT_OK;
+    return run_ln(h, c.st, h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), nullptr, h->hbuf, M, h->cfg.embed_dim, 1, 0, DT_F32, 0);
+}
+
 // Everything of one top position after the body input x is ready (hierarchical_ar.py:482-563,667-789; three code levels:
 // hqtransformer.py:409-635): the body blocks, ln_f, then the depth sub-steps, each an input step, the depth blocks, a head and its draws.
 //  - 'parallel' (two levels; three: 'parallel-add', 'parallel-reduce'): one sub-step per level over 1, 4 (and 16) tokens.  Every sub-step's
@@ -1611,15 +1631,7 @@ static int run_depth_head(hqt_handle* h, const SampleCtx& c, int Tq_body, bool p
             HIPCHK(launch_bidir_depth_input(ln, c.st));
             h->npartsd = 1;
         }
-        CHK(run_depth(h, c, dln, h->depth_rows, 0));      // Tq = 5 > 1: never the single-key shortcut of run_block
-        {   // ln_top / ln_bot of the interleaved rows into two compact operands: [B, D] (hbuf) and [4 B, D] (abuf)
-            Timed t(h, "bidir_head_ln", c.st);
-            LNArgs ln{h->xd, W(h, "ln_top.weight"), W(h, "ln_top.bias"), nullptr, h->hbuf, M, D, 1, 0, 1e-5f, c.md.act_dt(), head_pk(c, h->head_top, B)};
-            ln.gamma2 = W(h, "ln_bot.weight"); ln.beta2 = W(h, "ln_bot.bias"); ln.y2 = h->abuf; ln.out2_packed_mb = head_pk(c, h->head_bot, 4 * B);
-            take_pend(h, ln);
-            HIPCHK(launch_bidir_head_ln(ln, c.st));
-        }
-        normed[0] = h->hbuf; normed[1] = h->abuf;
+        CHK(run_bidir_tail(h, c, dln, normed));
         bidir_set = {c.lv[0].temperature, c.lv[1].top_k, c.lv[1].top_p};
     }
     for (int sub = 0; sub < nsub; ++sub) {
@@ -1695,6 +1707,21 @@ static EmbedArgs embed_args(hqt_handle* h, const SampleCtx& c, const int64_t* co
     return e;
 }
 
+// The body input rows of a prefill over P given positions, whose codes the embedding reads from `codes`; *rows: the body rows per sample.
+//  - text: the T prompt rows, then row T + j = the input the decode step at position j + 1 computes from the codes of position j
+//  - otherwise: the sos row, then the same P rows
+static int embed_prefill(hqt_handle* h, const SampleCtx& c, const int64_t* const* codes, int P, int* rows) {
+    const hqt_config& cf = h->cfg;
+    const bool text = cf.cond_type == HQT_COND_TEXT;
+    const int T = text ? cf.ctx_len_txt : 0;
+    *rows = text ? T + P : P + 1;
+    if (text) HIPCHK(launch_embed_text(c.cond, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, c.B, T, cf.embed_dim, c.st, cf.vocab_txt, T + P));
+    if (text && P == 0) return HQT_OK;
+    Timed t(h, "embed_prefix", c.st);
+    HIPCHK(launch_embed_prefix(embed_args(h, c, codes), *rows - T, *rows, T, text ? 1 : 0, c.st));      // text: P rows behind the prompt, at step offset 1; otherwise P + 1 from the sos row
+    return HQT_OK;
+}
+
 static int run_decode_step(hqt_handle* h, const SampleCtx& c) {      // one KV-cached position, Tq = 1
     {
         Timed t(h, "embed", c.st);
@@ -1708,34 +1735,70 @@ static int run_decode_step(hqt_handle* h, const SampleCtx& c) {      // one KV-c
 }
 
 static int sample_run(hqt_handle* h, const SampleCtx& c);
-static int rows_ring_take(hqt_handle* h, int* out);
+
+// One buffer of the pinned ring (hqt_handle::rows_pinned) as the five host tables it holds.  ring_slot is the only place that knows their order and
+// sizes: the keys come first, and every later section starts at a multiple of 4 bytes, which aligns each for its type.
+struct RingSlot { RowKey* keys; RowSampler* samplers; GuidePair* pairs; int32_t* groups; unsigned char* keep; size_t bytes; };
+static_assert(alignof(RowKey) == 8 && alignof(RowSampler) == 4 && alignof(GuidePair) == 4 && alignof(int32_t) == 4 &&
+              sizeof(RowKey) % 4 == 0 && sizeof(RowSampler) % 4 == 0 && sizeof(GuidePair) % 4 == 0, "the order of a ring slot's sections no longer aligns each for its type");
+static RingSlot ring_slot(const hqt_handle* h, RowKey* base) {      // (base null: only `bytes`, what a slot needs)
+    const size_t B = h->cfg.max_batch;
+    const size_t samplers = B * sizeof(RowKey), pairs = samplers + B * sizeof(RowSampler), groups = pairs + h->guide_room() * sizeof(GuidePair),
+                 keep = groups + B * sizeof(int32_t);
+    RingSlot r{};
+    r.bytes = keep + B * h->cfg.max_steps;
+    if (!base) return r;
+    unsigned char* const p = reinterpret_cast<unsigned char*>(base);
+    r.keys = base;
+    r.samplers = reinterpret_cast<RowSampler*>(p + samplers);
+    r.pairs = reinterpret_cast<GuidePair*>(p + pairs);
+    r.groups = reinterpret_cast<int32_t*>(p + groups);
+    r.keep = p + keep;
+    return r;
+}
+
+// The next buffer of the pinned ring, free to be rewritten: the copy that last read it (4 takes ago) is done.  The caller ends with ring_sent behind its copies.
+static int rows_ring_take(hqt_handle* h, int* slot_out, RingSlot* view) {
+    const int slot = h->rows_next;
+    h->rows_next = (slot + 1) % hqt_handle::ROWS_RING;
+    if (!h->rows_pinned[slot]) {
+        HIPCHK(hipHostMalloc((void**)&h->rows_pinned[slot], ring_slot(h, nullptr).bytes, hipHostMallocDefault));
+        HIPCHK(hipEventCreateWithFlags(&h->rows_ev[slot], hipEventDisableTiming));
+    }
+    if (h->rows_busy[slot]) HIPCHK(hipEventSynchronize(h->rows_ev[slot]));
+    *slot_out = slot;
+    *view = ring_slot(h, h->rows_pinned[slot]);
+    return HQT_OK;
+}
+// n elements of a host table into a section of the slot (table null: they were built there) and, behind the stream's work, on to the device buffer
+template <class T, class S> static int ring_send(T* section, const S* table, size_t n, T* dev, hipStream_t st) {
+    static_assert(sizeof(T) == sizeof(S), "a staged table travels to the device as it is");
+    if (table) memcpy(section, table, n * sizeof(T));
+    HIPCHK(hipMemcpyAsync(dev, section, n * sizeof(T), hipMemcpyHostToDevice, st));
+    return HQT_OK;
+}
+static int ring_sent(hqt_handle* h, int slot, hipStream_t st) {
+    HIPCHK(hipEventRecord(h->rows_ev[slot], st));
+    h->rows_busy[slot] = true;
+    return HQT_OK;
+}
 
 // hqt_sample / hqt_sample_l3 after their null checks: `c` holds the call's options, sampler settings and forced codes (feed); validates them,
 // runs the call and copies the drawn codes of every level out
 static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t* const* out, void* stream) {
-    // the staged row table belongs to THIS call and to no later one, whatever becomes of the call
-    std::vector<hqt_row_sampler> staged;
-    staged.swap(h->row_set_staged);
-    const size_t staged_rows = staged.size();
-    c.logprob_out = h->logprob_staged;           // ... and so does the staged log-probability buffer
-    h->logprob_staged = nullptr;
-    c.row_set = staged_rows ? staged.data() : nullptr;
-    std::vector<hqt_guide_pair> guide;           // ... and the staged pair table
-    guide.swap(h->guide_staged);
-    c.guide = guide.empty() ? nullptr : guide.data();
-    c.n_guide = (int)guide.size();
-    std::vector<uint8_t> keep;                   // ... and the staged keep table
-    keep.swap(h->keep_staged);
-    c.keep = keep.empty() ? nullptr : keep.data();
-    for (int i = 0; i < 3; ++i) c.keep_codes[i] = h->keep_codes[i];
-    std::vector<int32_t> groups;                 // ... and the staged group table
-    groups.swap(h->groups_staged);
-    c.groups = groups.empty() ? nullptr : groups.data();
-    c.n_groups = c.groups ? h->groups_G : 0;
-    c.seg = h->seg_staged;                       // ... and the staged segment
-    h->seg_staged = false;
-    c.start = c.seg ? h->seg_start : 0;
-    c.stop = c.seg ? h->seg_stop : c.n_steps;
+    // what was staged belongs to THIS call and to no later one, whatever becomes of the call; `s` owns the host tables until it returns
+    const hqt_handle::Staged s = h->take_staged();
+    c.row_set = s.row_set.empty() ? nullptr : s.row_set.data();
+    c.logprob_out = s.logprob;
+    c.guide = s.guide.empty() ? nullptr : s.guide.data();
+    c.n_guide = (int)s.guide.size();
+    c.keep = s.keep.empty() ? nullptr : s.keep.data();
+    for (int i = 0; i < 3; ++i) c.keep_codes[i] = s.keep_codes[i];
+    c.groups = s.groups.empty() ? nullptr : s.groups.data();
+    c.n_groups = c.groups ? s.groups_G : 0;
+    c.seg = s.seg;
+    c.start = c.seg ? s.seg_start : 0;
+    c.stop = c.seg ? s.seg_stop : c.n_steps;
     if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
     const hqt_config& cf = h->cfg;
     if (c.levels == 2 && !cf.has_stage2) return fail(HQT_ERR_STATE, "handle was created without stage 2");
@@ -1776,8 +1839,8 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     }
     if (c.keep) {
         if (c.with_prefix) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: the staged keep table was taken by a prefix entry point; a leading run of the mask is the prefix (hqt_sample / hqt_sample_l3 take the table)");
-        if (h->keep_B != B || h->keep_n != c.n_steps)
-            return fail(HQT_ERR_INVALID, "hqt_set_keep_mask staged a table of B=%d, n_steps=%d, this call has B=%d, n_steps=%d", h->keep_B, h->keep_n, B, c.n_steps);
+        if (s.keep_B != B || s.keep_n != c.n_steps)
+            return fail(HQT_ERR_INVALID, "hqt_set_keep_mask staged a table of B=%d, n_steps=%d, this call has B=%d, n_steps=%d", s.keep_B, s.keep_n, B, c.n_steps);
         static const char* const fname[2][3] = {{"force_top", "force_bot", ""}, {"force0", "force1", "force2"}};
         for (int i = 0; i < c.levels; ++i)
             if (c.feed[i]) return fail(HQT_ERR_INVALID, "%s together with a keep table is not built: put the forced codes into the kept codes (hqt_set_keep_mask)", fname[c.levels == 3][i]);
@@ -1793,7 +1856,7 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
         c.prefix_len = L;
     }
     if (c.groups) {
-        if ((int)groups.size() != B) return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups staged a table of B=%d, this call has B=%d", (int)groups.size(), B);
+        if ((int)s.groups.size() != B) return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups staged a table of B=%d, this call has B=%d", (int)s.groups.size(), B);
         if (c.prefix_len > 0)
             return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups together with a code prefix or a keep table whose rows share a leading run (prefix_len=%d) is not built: "
                                          "the prompt and the prefix are one prefill whose prefix rows differ per row", c.prefix_len);
@@ -1801,18 +1864,17 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
         if (c.n_groups > h->pg_cap || !h->pg_k || !h->pg_v || !h->pg_x) return fail(HQT_ERR_STATE, "hqt_set_prompt_groups: the staging buffer holds %d prompts, the table has %d", h->pg_cap, c.n_groups);
     }
     if (c.row_set) {                             // per-row settings replace the scalars of `opts`: those are neither checked nor part of the graph key
-        if ((int)staged_rows != B) return fail(HQT_ERR_INVALID, "hqt_set_row_samplers staged %d rows, this call has B=%d", (int)staged_rows, B);
+        if ((int)s.row_set.size() != B) return fail(HQT_ERR_INVALID, "hqt_set_row_samplers staged %d rows, this call has B=%d", (int)s.row_set.size(), B);
         for (int i = 0; i < 3; ++i) c.lv[i] = SamplerSet();
     }
-    bool top_p = false;
     for (int b = 0; b < (c.row_set ? B : 1); ++b)
         for (int i = 0; i < c.levels; ++i) {
             const SamplerSet l = c.row_set ? SamplerSet{c.row_set[b].temperature[i], c.row_set[b].top_k[i], c.row_set[b].top_p[i]} : c.lv[i];
             if (!(l.temperature > 0.f)) return fail(HQT_ERR_INVALID, "temperatures must be > 0");
-            top_p = top_p || l.top_p > 0.f;
+            c.top_p = c.top_p || l.top_p > 0.f;
         }
-    if (top_p && cf.vocab_top > 8192) return fail(HQT_ERR_INVALID, "top-p needs vocab <= 8192");
-    c.row_top_p = c.row_set && top_p;
+    if (c.top_p && cf.vocab_top > 8192) return fail(HQT_ERR_INVALID, "top-p needs vocab <= 8192");
+    c.row_top_p = c.row_set && c.top_p;
     if (c.guide) {
         if (cf.cond_type == HQT_COND_NONE) return fail(HQT_ERR_INVALID, "guidance needs a conditional model: this handle has cond_type HQT_COND_NONE, its rows have no condition to differ in");
         if ((c.row_seeds || c.row_offsets) && (!c.row_seeds || !c.row_offsets)) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
@@ -1851,24 +1913,23 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     CHK(layout_check(h, c.md));
     // (a group table: cond is [n_groups, ctx_len_txt], n_groups <= B)
     if (cond) HIPCHK(hipMemcpyAsync(h->cond_buf, cond, (size_t)(c.groups ? c.n_groups : B) * (cf.cond_type == HQT_COND_TEXT ? cf.ctx_len_txt : 1) * 8, hipMemcpyDefault, c.st));
-    static const size_t width[3] = {1, 4, 16};
     // the prefix goes into the handle's code buffers (outside any captured graph): the prefill's embedding, the embedding of position
     // prefix_len + 1 and the copies below read it there
     for (int i = 0; i < (c.prefix_len && !c.keep ? c.levels : 0); ++i)
-        HIPCHK(launch_copy_prefix(c.prefix[i], codes[i], B, c.prefix_len, c.n_steps, (int)width[i], cf.vocab_top, c.st));
+        HIPCHK(launch_copy_prefix(c.prefix[i], codes[i], B, c.prefix_len, c.n_steps, LEVEL_WIDTH[i], cf.vocab_top, c.st));
     // whatever this call is, it writes the body cache and the step state: a paused pass is over, or goes on below and is recorded anew behind its segment
     h->paused.live = false;
     // a continuation reads the codes of position start - 1 where the caller holds them: a level that is not forced takes them from out_* (the caller may have
     // edited them, or gathered its rows along with hqt_select_rows)
     for (int i = 0; i < (c.start > 0 ? c.levels : 0); ++i)
-        if (c.feed[i] == codes[i]) HIPCHK(launch_copy_positions(out[i], codes[i], B, c.n_steps, (int)width[i], c.start - 1, c.start, c.st));
+        if (c.feed[i] == codes[i]) HIPCHK(launch_copy_positions(out[i], codes[i], B, c.n_steps, LEVEL_WIDTH[i], c.start - 1, c.start, c.st));
     CHK(sample_run(h, c));
     if (!c.seg) {
         for (int i = 0; i < c.levels; ++i)
-            HIPCHK(hipMemcpyAsync(out[i], codes[i], (size_t)B * c.n_steps * width[i] * 8, hipMemcpyDeviceToDevice, c.st));
+            HIPCHK(hipMemcpyAsync(out[i], codes[i], (size_t)B * c.n_steps * LEVEL_WIDTH[i] * 8, hipMemcpyDeviceToDevice, c.st));
         return HQT_OK;
     }
-    for (int i = 0; i < c.levels; ++i) HIPCHK(launch_copy_positions(codes[i], out[i], B, c.n_steps, (int)width[i], c.start, c.stop, c.st));
+    for (int i = 0; i < c.levels; ++i) HIPCHK(launch_copy_positions(codes[i], out[i], B, c.n_steps, LEVEL_WIDTH[i], c.start, c.stop, c.st));
     if (c.stop < c.n_steps) h->paused = hqt_handle::Paused{true, B, c.n_steps, c.levels, c.precision, c.stop};
     return HQT_OK;
 }
@@ -1886,7 +1947,7 @@ static_assert(sizeof(hqt_row_sampler) == 36 && sizeof(RowSampler) == sizeof(hqt_
 
 extern "C" int hqt_set_logprob_out(hqt_handle* h, float* logprobs) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
-    h->logprob_staged = logprobs;                // NULL clears; the shape [B, n_steps, draws] is the taking call's (the caller sizes the buffer for it)
+    h->staged.logprob = logprobs;                // NULL clears; the shape [B, n_steps, draws] is the taking call's (the caller sizes the buffer for it)
     return HQT_OK;
 }
 
@@ -1894,35 +1955,36 @@ static_assert(sizeof(hqt_guide_pair) == 20 && sizeof(GuidePair) == sizeof(hqt_gu
 
 extern "C" int hqt_set_guidance(hqt_handle* h, int n_pairs, const hqt_guide_pair* pairs) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
-    h->guide_staged.clear();
+    h->staged.guide.clear();
     if (n_pairs == 0 || !pairs) return HQT_OK;
     if (n_pairs < 0 || 2 * (long long)n_pairs > h->cfg.max_batch)
         return fail(HQT_ERR_INVALID, "n_pairs=%d outside [0, max_batch / 2 = %d]: a pair takes two rows of the pass", n_pairs, h->cfg.max_batch / 2);
-    h->guide_staged.assign(pairs, pairs + n_pairs);      // rows, scales and keys are checked by the call that takes it
+    h->staged.guide.assign(pairs, pairs + n_pairs);      // rows, scales and keys are checked by the call that takes it
     return HQT_OK;
 }
 
 extern "C" int hqt_set_keep_mask(hqt_handle* h, int B, int n_steps, const uint8_t* keep, const int64_t* const* codes) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
-    h->keep_staged.clear();
+    h->staged.keep.clear();
     if (B == 0 || !keep) return HQT_OK;
     if (B < 0 || B > h->cfg.max_batch) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: B=%d outside [0, max_batch=%d]", B, h->cfg.max_batch);
     if (n_steps < 1 || n_steps > h->cfg.max_steps) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: n_steps=%d outside [1, max_steps=%d]", n_steps, h->cfg.max_steps);
     if (!codes) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: codes is NULL");
     const int levels = h->cfg.code_levels == 3 ? 3 : 2;
-    for (int i = 0; i < 3; ++i) h->keep_codes[i] = i < levels ? codes[i] : nullptr;      // a NULL level is refused by the call that takes the table
-    h->keep_B = B; h->keep_n = n_steps;
-    h->keep_staged.resize((size_t)B * n_steps);
-    for (size_t i = 0; i < h->keep_staged.size(); ++i) h->keep_staged[i] = keep[i] ? 1 : 0;
+    hqt_handle::Staged& s = h->staged;
+    for (int i = 0; i < 3; ++i) s.keep_codes[i] = i < levels ? codes[i] : nullptr;      // a NULL level is refused by the call that takes the table
+    s.keep_B = B; s.keep_n = n_steps;
+    s.keep.resize((size_t)B * n_steps);
+    for (size_t i = 0; i < s.keep.size(); ++i) s.keep[i] = keep[i] ? 1 : 0;
     return HQT_OK;
 }
 
 extern "C" int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler* rows) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
-    h->row_set_staged.clear();
+    h->staged.row_set.clear();
     if (n == 0 || !rows) return HQT_OK;
     if (n < 0 || n > h->cfg.max_batch) return fail(HQT_ERR_INVALID, "n=%d outside [0, max_batch=%d]", n, h->cfg.max_batch);
-    h->row_set_staged.assign(rows, rows + n);    // checked against B, the levels and the vocabulary by the call that takes it
+    h->staged.row_set.assign(rows, rows + n);    // checked against B, the levels and the vocabulary by the call that takes it
     return HQT_OK;
 }
 
@@ -1930,7 +1992,7 @@ extern "C" int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler*
 // the device has drained, a smaller one reuses it) and, with the first table, the gathered x rows.  A sampling call allocates nothing.
 extern "C" int hqt_set_prompt_groups(hqt_handle* h, int B, int n_groups, const int32_t* group_of_row) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
-    h->groups_staged.clear();
+    h->staged.groups.clear();
     const hqt_config& c = h->cfg;
     if (!c.has_stage2 || c.cond_type != HQT_COND_TEXT)
         return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups: the handle is not text-conditional (cond_type %d): one embedding row per sample leaves no prefill to share", c.cond_type);
@@ -1961,15 +2023,15 @@ extern "C" int hqt_set_prompt_groups(hqt_handle* h, int B, int n_groups, const i
         h->pg_bytes = bytes;
         h->pg_cap = n_groups;
     }
-    h->groups_G = n_groups;
-    h->groups_staged.assign(group_of_row, group_of_row + B);
+    h->staged.groups_G = n_groups;
+    h->staged.groups.assign(group_of_row, group_of_row + B);
     return HQT_OK;
 }
 
 extern "C" int hqt_set_segment(hqt_handle* h, int start, int stop) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
-    h->seg_staged = true;                        // checked against n_steps and the paused pass by the call that takes it
-    h->seg_start = start; h->seg_stop = stop;
+    h->staged.seg = true;                        // checked against n_steps and the paused pass by the call that takes it
+    h->staged.seg_start = start; h->staged.seg_stop = stop;
     return HQT_OK;
 }
 
@@ -1997,12 +2059,10 @@ extern "C" int hqt_select_rows(hqt_handle* h, int B_new, const int32_t* rows_fro
     const int t_live = cf.cond_type == HQT_COND_TEXT ? cf.ctx_len_txt + p.pos - 1 : p.pos;
     if (t_live < 1 || t_live > h->Tmax) return fail(HQT_ERR_STATE, "hqt_select_rows: %d live cache rows outside [1, %d]", t_live, h->Tmax);
     int slot = 0;
-    CHK(rows_ring_take(h, &slot));
-    int32_t* gr = reinterpret_cast<int32_t*>(reinterpret_cast<GuidePair*>(reinterpret_cast<RowSampler*>(h->rows_pinned[slot] + cf.max_batch) + cf.max_batch) + h->guide_room());
-    memcpy(gr, rows_from, (size_t)B_new * sizeof(int32_t));
-    HIPCHK(hipMemcpyAsync(h->group_of_row, gr, (size_t)B_new * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(h->rows_ev[slot], st));
-    h->rows_busy[slot] = true;
+    RingSlot ring;
+    CHK(rows_ring_take(h, &slot, &ring));
+    CHK(ring_send(ring.groups, rows_from, (size_t)B_new, h->group_of_row, st));
+    CHK(ring_sent(h, slot, st));
     {
         Timed t(h, "kv_gather_rows", st);
         const long long row_bytes = (long long)cf.embed_dim * (long long)md.act_sz();
@@ -2078,7 +2138,7 @@ extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_
                          float* const* logits_out, void* stream) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
     // a staged table or buffer belongs to a sampling call: it must not wait for a later one behind this call
-    const bool staged = !h->row_set_staged.empty() || h->logprob_staged || !h->guide_staged.empty() || !h->keep_staged.empty() || !h->groups_staged.empty();
+    const bool staged = h->staged.holds_table();
     h->clear_staged();
     if (staged) return fail(HQT_ERR_STATE, "hqt_score: a row-sampler table, guidance pair table, keep table, prompt-group table or log-probability buffer was staged on this handle "
                             "(hqt_set_row_samplers / hqt_set_guidance / hqt_set_logprob_out / hqt_set_keep_mask / hqt_set_prompt_groups): they belong to a sampling call and were cleared");
@@ -2104,27 +2164,20 @@ extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_
     CHK(layout_check(h, c.md));
     ON_DEVICE(h);
     int64_t* const own[3] = {h->codes_top, h->codes_bot, h->codes_l2};
-    static const int width[3] = {1, 4, 16};
     if (cond) HIPCHK(hipMemcpyAsync(h->cond_buf, cond, (size_t)B * (text ? cf.ctx_len_txt : 1) * 8, hipMemcpyDefault, c.st));
     c.cond = cond ? h->cond_buf : nullptr;
     for (int i = 0; i < levels; ++i) {             // [B, n, width]: the handle's code buffers hold the pairs contiguously, pair p at index p
-        HIPCHK(launch_copy_prefix(codes[i], own[i], B, n, n, width[i], cf.vocab_top, c.st));
+        HIPCHK(launch_copy_prefix(codes[i], own[i], B, n, n, LEVEL_WIDTH[i], cf.vocab_top, c.st));
         c.feed[i] = own[i]; c.out[i] = own[i];
     }
     h->paused.live = false;                        // the pass overwrites the body cache and the step state: a paused pass (hqt_set_segment) is over
     HIPCHK(launch_set_step(h->state, 0, 0, c.st));
     // ---- body: n rows per sample (text: the T prompt rows, then the input rows of positions 1 .. n - 1)
     const int D = cf.embed_dim, V = cf.vocab_top, T = text ? cf.ctx_len_txt : 0;
-    const int Tq = text ? T + n - 1 : n, row_off = text ? T - 1 : 0;          // body row of pair (b, t): b Tq + row_off + t
-    if (text) {
-        HIPCHK(launch_embed_text(c.cond, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, B, T, D, c.st, cf.vocab_txt, Tq));
-        if (n > 1) {
-            Timed t(h, "embed_prefix", c.st);
-            HIPCHK(launch_embed_prefix(embed_args(h, c, own), n - 1, Tq, T, 1, c.st));
-        }
-    } else if (n > 1) {
-        Timed t(h, "embed_prefix", c.st);
-        HIPCHK(launch_embed_prefix(embed_args(h, c, own), n, n, 0, 0, c.st));
+    const int row_off = text ? T - 1 : 0;          // body row of pair (b, t): b Tq + row_off + t
+    int Tq = 1;
+    if (text || n > 1) {
+        CHK(embed_prefill(h, c, own, n - 1, &Tq));
     } else {                                       // one row per sample: the decode step's embedding at step 0 (with the packed copy where run_body wants it)
         Timed t(h, "embed", c.st);
         EmbedArgs e = embed_args(h, c, own);
@@ -2133,9 +2186,7 @@ extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_
     }
     bool pfull = false;
     CHK(run_body(h, c, Tq, 0, false, false, &pfull));
-    if (h->pend.slabs) {                           // split-K slabs the last GEMM left for "the next LayerNorm": folded into ALL rows here, before the depth GEMMs reuse the slab workspace
-        CHK(run_ln(h, c.st, h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), nullptr, h->hbuf, B * Tq, D, 1, 0, DT_F32, 0));
-    }
+    CHK(fold_pending(h, c, B * Tq));
     // ---- depth: chunks of pairs
     const Lin* heads[3] = {&h->head_top, &h->head_bot, &h->head_l2};
     const int64_t* const feed[3] = {h->codes_top, h->codes_bot, h->codes_l2};
@@ -2159,15 +2210,7 @@ extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_
                 HIPCHK(launch_score_depth_input(ln, p0, n, Tq, row_off, c.st));
                 h->npartsd = 1;
             }
-            CHK(run_depth(h, cc, dln, h->depth_rows, 0));
-            {
-                Timed t(h, "bidir_head_ln", c.st);
-                LNArgs ln{h->xd, W(h, "ln_top.weight"), W(h, "ln_top.bias"), nullptr, h->hbuf, M, D, 1, 0, 1e-5f, c.md.act_dt(), head_pk(cc, h->head_top, np)};
-                ln.gamma2 = W(h, "ln_bot.weight"); ln.beta2 = W(h, "ln_bot.bias"); ln.y2 = h->abuf; ln.out2_packed_mb = head_pk(cc, h->head_bot, 4 * np);
-                take_pend(h, ln);
-                HIPCHK(launch_bidir_head_ln(ln, c.st));
-            }
-            normed[0] = h->hbuf; normed[1] = h->abuf;
+            CHK(run_bidir_tail(h, cc, dln, normed));
         }
         for (int sub = 0; sub < levels; ++sub) {
             const SubStep s = sub_step(cf, sub);
@@ -2233,25 +2276,10 @@ struct PersistOrder {
     }
 };
 
-// The next buffer of the pinned ring, free to be rewritten: the copy that last read it (4 takes ago) is done.  The caller records rows_ev[slot] behind its copies.
-static int rows_ring_take(hqt_handle* h, int* out) {
-    const int slot = h->rows_next;
-    h->rows_next = (slot + 1) % hqt_handle::ROWS_RING;
-    if (!h->rows_pinned[slot]) {
-        HIPCHK(hipHostMalloc((void**)&h->rows_pinned[slot], (size_t)h->cfg.max_batch * (sizeof(RowKey) + sizeof(RowSampler)) + h->guide_room() * sizeof(GuidePair) + (size_t)h->cfg.max_batch * sizeof(int32_t) + (size_t)h->cfg.max_batch * h->cfg.max_steps, hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&h->rows_ev[slot], hipEventDisableTiming));
-    }
-    if (h->rows_busy[slot]) HIPCHK(hipEventSynchronize(h->rows_ev[slot]));
-    *out = slot;
-    return HQT_OK;
-}
-
 static int sample_run(hqt_handle* h, const SampleCtx& c) {
     const hqt_config& cf = h->cfg;
     const int B = c.B;
-    bool top_p = false;
-    for (int i = 0; i < c.levels; ++i) top_p = top_p || c.lv[i].top_p > 0.f;
-    HIPCHK(sampler_configure(cf.vocab_top, top_p || c.row_top_p));
+    HIPCHK(sampler_configure(cf.vocab_top, c.top_p));
     CHK(persist_bind(h));
     if (c.start == 0) HIPCHK(launch_set_step(h->state, 0, 0, c.st));      // (a continuation goes on from the step state its pass stopped at)
     if ((c.row_seeds || c.row_offsets) && (!c.row_seeds || !c.row_offsets)) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
@@ -2259,45 +2287,27 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
     // table, and ALWAYS the keys -- the implicit ones (seed, sample_offset + b) are built here, the negative row of every pair taking its positive row's
     if (c.row_seeds || c.row_set || c.guide || c.keep || c.groups) {
         int slot = 0;
-        CHK(rows_ring_take(h, &slot));
-        RowKey* rk = h->rows_pinned[slot];
+        RingSlot ring;
+        CHK(rows_ring_take(h, &slot, &ring));
+        RowKey* rk = ring.keys;
         if (c.row_seeds || c.guide) {
             for (int b = 0; b < B; ++b) {
                 rk[b].seed = c.row_seeds ? c.row_seeds[b] : c.seed;
                 rk[b].global_row = c.row_offsets ? c.row_offsets[b] : c.sample_offset + b;
             }
             for (int i = 0; i < c.n_guide; ++i) rk[c.guide[i].neg_row] = rk[c.guide[i].pos_row];      // (explicit keys were checked to agree: sample_call)
-            HIPCHK(hipMemcpyAsync(h->rows, rk, (size_t)B * sizeof(RowKey), hipMemcpyHostToDevice, c.st));
+            CHK(ring_send(rk, (const RowKey*)nullptr, (size_t)B, h->rows, c.st));
         }
-        if (c.row_set) {
-            RowSampler* rs = reinterpret_cast<RowSampler*>(rk + h->cfg.max_batch);
-            memcpy(rs, c.row_set, (size_t)B * sizeof(RowSampler));
-            HIPCHK(hipMemcpyAsync(h->row_set, rs, (size_t)B * sizeof(RowSampler), hipMemcpyHostToDevice, c.st));
-        }
-        if (c.guide) {
-            GuidePair* gp = reinterpret_cast<GuidePair*>(reinterpret_cast<RowSampler*>(rk + h->cfg.max_batch) + h->cfg.max_batch);
-            memcpy(gp, c.guide, (size_t)c.n_guide * sizeof(GuidePair));
-            HIPCHK(hipMemcpyAsync(h->guide, gp, (size_t)c.n_guide * sizeof(GuidePair), hipMemcpyHostToDevice, c.st));
-        }
-        if (c.keep) {             // the mask, then the kept codes into the handle's code buffers (outside any captured graph): every level's embeddings, the
-                                  // samplers' guard and code_logprob read them there
-            unsigned char* km = reinterpret_cast<unsigned char*>(reinterpret_cast<int32_t*>(reinterpret_cast<GuidePair*>(reinterpret_cast<RowSampler*>(rk + h->cfg.max_batch) + h->cfg.max_batch) + h->guide_room()) + h->cfg.max_batch);
-            memcpy(km, c.keep, (size_t)B * c.n_steps);
-            HIPCHK(hipMemcpyAsync(h->keep_mask, km, (size_t)B * c.n_steps, hipMemcpyHostToDevice, c.st));
-        }
-        if (c.groups) {
-            int32_t* gr = reinterpret_cast<int32_t*>(reinterpret_cast<GuidePair*>(reinterpret_cast<RowSampler*>(rk + h->cfg.max_batch) + h->cfg.max_batch) + h->guide_room());
-            memcpy(gr, c.groups, (size_t)B * sizeof(int32_t));
-            HIPCHK(hipMemcpyAsync(h->group_of_row, gr, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, c.st));
-        }
-        HIPCHK(hipEventRecord(h->rows_ev[slot], c.st));
-        h->rows_busy[slot] = true;
+        if (c.row_set) CHK(ring_send(ring.samplers, c.row_set, (size_t)B, h->row_set, c.st));
+        if (c.guide) CHK(ring_send(ring.pairs, c.guide, (size_t)c.n_guide, h->guide, c.st));
+        if (c.keep) CHK(ring_send(ring.keep, c.keep, (size_t)B * c.n_steps, h->keep_mask, c.st));
+        if (c.groups) CHK(ring_send(ring.groups, c.groups, (size_t)B, h->group_of_row, c.st));
+        CHK(ring_sent(h, slot, c.st));
     }
-    if (c.keep) {
-        static const int width[3] = {1, 4, 16};
-        for (int i = 0; i < c.levels; ++i)
-            HIPCHK(launch_copy_kept(c.keep_codes[i], c.out[i], h->keep_mask, B, c.n_steps, width[i], cf.vocab_top, c.st));
-    }
+    // the kept codes go into the handle's code buffers (outside any captured graph) behind the mask: every level's embeddings, the samplers' guard and
+    // code_logprob read them there
+    for (int i = 0; i < (c.keep ? c.levels : 0); ++i)
+        HIPCHK(launch_copy_kept(c.keep_codes[i], c.out[i], h->keep_mask, B, c.n_steps, LEVEL_WIDTH[i], cf.vocab_top, c.st));
     if (!c.row_seeds && !c.guide) HIPCHK(launch_set_rows(h->rows, B, c.seed, c.sample_offset, c.st));
     int first = c.start;
     const int64_t* const own[3] = {h->codes_top, h->codes_bot, h->codes_l2};
@@ -2317,9 +2327,7 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         const KvStage stage{h->pg_k, h->pg_v};
         bool pfull = false;
         CHK(run_body(h, cg, T, 0, false, false, &pfull, &stage));
-        // split-K slabs the last body GEMM left for "the next LayerNorm" belong to the G T rows: folded into all of them here (the normalised rows in
-        // hbuf are not read), before x is gathered and before the depth GEMMs reuse the slab workspace
-        if (h->pend.slabs) CHK(run_ln(h, c.st, h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), nullptr, h->hbuf, G * T, D, 1, 0, DT_F32, 0));
+        CHK(fold_pending(h, c, G * T));                  // (the G T staged rows, before the fan-out gathers x)
         {
             Timed t(h, "prompt_fanout", c.st);
             const FanoutArgs fa{h->pg_k, h->pg_v, h->kcache, h->vcache, h->x, h->pg_x, h->group_of_row, cf.n_layers, B, G, T, D,
@@ -2334,35 +2342,18 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         CHK(rc);
         HIPCHK(launch_advance_step(h->state, T, c.st));
         first = 1;
-    } else if (cf.cond_type == HQT_COND_TEXT) {     // 64-token causal prefill (sampling.py:187-190, layers.py:107-111)
-        // With a code prefix of P positions the prompt and the prefix are ONE pass of T + P rows per sample: rows 0 .. T - 1 the prompt rows,
-        // row T + j the input the decode step at position j + 1 computes from the codes of position j (embed_row, read from the handle's
-        // code buffers).  K/V of all rows go to the cache; ln_f and the depth head run on the last row and draw position P: the step state
-        // says (P, 0) while the pass runs and (P + 1, T + P) afterwards.  P = 0: the launches of before, unchanged.
-        const int T = cf.ctx_len_txt, P = c.prefix_len;
-        if (P) HIPCHK(launch_set_step(h->state, P, 0, c.st));
-        HIPCHK(launch_embed_text(c.cond, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, B, T, cf.embed_dim, c.st, cf.vocab_txt, T + P));
-        if (P) {
-            Timed t(h, "embed_prefix", c.st);
-            HIPCHK(launch_embed_prefix(embed_args(h, c, own), P, T + P, T, 1, c.st));
-        }
-        CHK(run_position(h, c, T + P, 0, false));
-        HIPCHK(launch_advance_step(h->state, T + P, c.st));
-        first = P + 1;
-    } else if (c.prefix_len) {
-        // Prefix prefill: the P + 1 body input rows of every sample (sos, then the embeddings of positions 0 .. P - 1, read from the
-        // handle's code buffers) in one launch, all body blocks causally over them -- K/V of all rows go to the cache --, the depth
-        // head on the last row, which draws position P: the step state says P while that pass runs (sampler keys, noise slice, where
-        // the codes go), and P + 1 over P + 1 keys afterwards.  Like the text prefill the pass takes the classic path (Tq_body > 1:
-        // run_body); the persistent chain first reads the step state in the decode steps below, behind the advance.
+    } else if (cf.cond_type == HQT_COND_TEXT || c.prefix_len) {
+        // The prefill: the text prompt (64-token causal prefill: sampling.py:187-190, layers.py:107-111) and / or a code prefix of P positions as ONE pass
+        // over the rows embed_prefill lays out, read from the handle's code buffers.  All body blocks run causally over them -- K/V of all rows go to the
+        // cache --, ln_f and the depth head on the last row, which draws position P: the step state says (P, 0) while that pass runs (sampler keys, noise
+        // slice, where the codes go) and P + 1 over all the rows afterwards.  The pass takes the classic path (Tq_body > 1: run_body); the persistent chain
+        // first reads the step state in the decode steps below, behind the advance.  Text with P = 0: the plain prompt prefill.
         const int P = c.prefix_len;
-        HIPCHK(launch_set_step(h->state, P, 0, c.st));
-        {
-            Timed t(h, "embed_prefix", c.st);
-            HIPCHK(launch_embed_prefix(embed_args(h, c, own), P + 1, P + 1, 0, 0, c.st));
-        }
-        CHK(run_position(h, c, P + 1, 0, false));
-        HIPCHK(launch_advance_step(h->state, P + 1, c.st));
+        int rows = 0;
+        if (P) HIPCHK(launch_set_step(h->state, P, 0, c.st));
+        CHK(embed_prefill(h, c, own, P, &rows));
+        CHK(run_position(h, c, rows, 0, false));
+        HIPCHK(launch_advance_step(h->state, rows, c.st));
         first = P + 1;
     }
     const int remaining = c.stop - first;       // (without a segment: stop = n_steps)

@@ -14,6 +14,10 @@ sample / sample3 in EXACT, SPLIT and FAST, persist on and off, eager and graph; 
 policy (tiled GEMM, split-K combine, K-sliced SPLIT GEMM); decode and encode in the three precisions on a stage 1 with attention, an
 upsampling conv and a nin_shortcut (planes-out, conv_out-direct, the halo conv's fused statistics), one decode with HQT_NO_FUSED_GN=1.
 
+The ``staged/*`` cases (``staged_cases``) cover the calls that stage something on the handle first -- code prefixes, kept positions, row samplers (six calls
+back to back through the four-slot pinned ring), guidance, shared prompts, segments with ``select_rows`` -- and ``score``, on the tiny spec; ``staged/refusals/*``
+record the code and text of refused raw-ABI calls and the hash of a plain call behind each.
+
 The ``surface/*`` cases record hashes only, with fixed seeds, of what the Python surface above the engine returns on the tiny configs:
 ``sampling_ihqgpt`` (class / text / bidirectional; every form of ``cond``, ``given_top_code``, ``row_seeds``, 'split', a seed drawn from
 torch's generator), ``sampling_hqtransformer``, ``decode_code`` / ``decode_sequences`` (two and three levels, a level missing) and
@@ -184,6 +188,179 @@ def surface_cases(rec):
                 pipe.release(B, n_pos)
 
 
+def flat_all(out):
+    """Every tensor of a nest of lists / tuples, in order."""
+    return [t for o in out for t in flat_all(o)] if isinstance(out, (list, tuple)) else [out]
+
+
+def staged_cases(rec, tiny):
+    """``staged/*``: the calls that stage something on the handle first (row samplers, log-probabilities, guidance, prefixes, kept positions, shared prompts,
+    segments with select_rows) and ``score``, on the tiny spec with B = 4, n = 6, max_prefix = 5 and score_chunk = 5 (24 pairs: chunks of 5, 5, 5, 5, 4).
+    Draws are keyed (no ``noise``): the per-row keys travel with the tables.  ``staged/refusals/*``: refused raw-ABI calls, their code and text, and
+    the hash of a plain call behind each -- nothing was left staged."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    from hqtransformer_amd import _lib, synth
+    from hqtransformer_amd.engine import Engine, guide_pair_table, row_sampler_table
+    from hqtransformer_amd.spec import Stage2Spec
+    dev = torch.device('cuda:0')
+    B, n, P, V = 4, 6, 2, tiny['vocab_top']
+    specs = {'class': Stage2Spec(**tiny), 'text': Stage2Spec(**dict(tiny, cond=2, n_classes=0)),
+             'l3_parallel_add': Stage2Spec(**tiny, levels=3, depth_decoding='parallel-add'), 'bidirectional': Stage2Spec(**tiny, depth_decoding='bidirectional')}
+    engines = {}
+
+    def engine(model):
+        if model not in engines:
+            spec = specs[model]
+            eng = engines[model] = Engine(spec, None, dev, B, spec.ctx_len_img, max_prefix=5, score_chunk=5)
+            eng.load(stage2=synth.stage2_weights(spec, 60 + len(engines), 'fixture'))
+            eng.finalize()
+        return engines[model]
+
+    def cond_of(model, rows=B):
+        spec = specs[model]
+        if spec.cond == 2:
+            return torch.from_numpy(synth.text_ids(71, rows, spec.ctx_len_txt, spec.vocab_txt))
+        return torch.from_numpy((np.arange(rows) * 7) % spec.n_classes)
+
+    def codes_of(model, seed):
+        r = np.random.default_rng([seed, 2])
+        return [torch.from_numpy(r.integers(0, V, (B, n) + ((4 ** l,) if l else ()))) for l in range(specs[model].levels)]
+
+    def put(case, model, call, precs=('exact', 'fast'), graph=True, persist=None):
+        """``call(precision, use_graph)`` -> tensors: launch counts and hashes of the eager pass, hashes of the graphed one."""
+        eng = engine(model)
+        for prec in precs:
+            for on in (True,) if persist is None else persist:
+                eng.set_persist(on)
+                counts, out = timed(eng, lambda: call(_lib.PRECISIONS[prec], False))
+                entry = {'launches': counts, 'eager': [digest(t) for t in flat_all(out)]}
+                if graph:
+                    out = call(_lib.PRECISIONS[prec], True)
+                    torch.cuda.synchronize()
+                    eng.range_check()
+                    entry['graph'] = [digest(t) for t in flat_all(out)]
+                rec[f'staged/{case}/{model}/{prec}' + ('' if persist is None else f'/persist={int(on)}')] = entry
+        eng.set_persist(True)
+
+    def fn_of(model):
+        return engine(model).sample3 if specs[model].levels == 3 else engine(model).sample
+
+    for model in ('class', 'text', 'l3_parallel_add'):
+        prefix = [c[:, :P].contiguous() for c in codes_of(model, 81)]
+        put('prefix', model, lambda p, g, m=model, px=prefix: fn_of(m)(B, cond_of(m), n, precision=p, use_graph=g, seed=82, prefix=px,
+                                                                       return_logits=True, return_logprobs=True))
+    # every row keeps position 0 (the shared leading run: the prefix prefill); beyond it the rows differ
+    mask = np.zeros((B, n), dtype=bool)
+    mask[:, 0] = True
+    mask[0, 3] = mask[1, 4] = mask[2, 2] = mask[2, 5] = True
+    for model in ('class', 'l3_parallel_add'):
+        put('keep', model, lambda p, g, m=model: fn_of(m)(B, cond_of(m), n, precision=p, use_graph=g, seed=83, keep=(mask, codes_of(m, 84)), return_logits=True))
+    pairs = [(0, 2, 1.5), (1, 3, 2.0)]
+    paired = [0, 1, 0, 1]                            # both rows of a pair keep the same positions and codes
+    put('keep_guided', 'class', lambda p, g: fn_of('class')(B, cond_of('class'), n, precision=p, use_graph=g, seed=85, guidance=pairs,
+                                                             keep=(mask[paired], [c[paired].contiguous() for c in codes_of('class', 84)])))
+    table = [((1.0, 0.9), (100, 50), None), ((0.8, 1.0), (None, 20), None), ((1.0, 1.0), None, (0.9, None)), ((1.1, 0.7), (10, None), None)]
+    put('row_samplers', 'class', lambda p, g: fn_of('class')(B, cond_of('class'), n, precision=p, use_graph=g, seed=86, row_samplers=table), precs=('exact',))
+    put('row_samplers', 'class', lambda p, g: fn_of('class')(B, cond_of('class'), n, precision=p, use_graph=g, seed=86, row_samplers=table), precs=('fast',),
+        persist=(True, False))
+    put('row_samplers', 'bidirectional', lambda p, g: fn_of('bidirectional')(B, cond_of('bidirectional'), n, precision=p, use_graph=g, seed=87, row_samplers=table))
+    # six calls, four ring slots, no synchronisation in between: the fifth and sixth rewrite a slot behind a copy that may still be pending
+    put('ring', 'class', lambda p, g: [fn_of('class')(B, cond_of('class'), n, precision=p, use_graph=g, seed=90 + k, row_samplers=table[k % B:] + table[:k % B],
+                                                      row_seeds=[90 + k] * B, row_offsets=[(b + k) % B for b in range(B)]) for k in range(6)])
+    put('guidance', 'class', lambda p, g: fn_of('class')(B, cond_of('class'), n, precision=p, use_graph=g, seed=88, guidance=pairs, return_logprobs=True))
+    groups = torch.tensor([0, 1, 1, 0])
+    put('prompt_groups', 'text', lambda p, g: fn_of('text')(B, cond_of('text', 2), n, precision=p, use_graph=g, seed=89, prompt_groups=groups))
+
+    def segments(model, p, g):
+        spec, eng, draws = specs[model], engine(model), 5
+        shared = dict(prompt_groups=groups) if spec.cond == 2 else {}
+        cond = cond_of(model, 2) if shared else cond_of(model)
+        outs = [torch.zeros((B, n) + ((4 ** l,) if l else ()), dtype=torch.int64, device=dev) for l in range(spec.levels)]
+        lg, lp = torch.zeros((n, draws, B, V), device=dev), torch.zeros((B, n, draws), device=dev)
+        kw = dict(precision=p, use_graph=g, seed=91)
+        eng.sample(B, cond, n, segment=(0, 2), out=outs, logits_out=lg, logprobs_out=lp, **shared, **kw)
+        eng.sample(B, cond[groups] if shared else cond, n, segment=(2, 4), out=outs, logits_out=lg, logprobs_out=lp, **kw)
+        rows = [2, 0, 0]
+        eng.select_rows(rows, paused_batch=B)
+        outs3, lg3, lp3 = [o[rows].contiguous() for o in outs], lg[:, :, rows].contiguous(), lp[rows].contiguous()
+        eng.sample(len(rows), (cond[groups] if shared else cond)[rows], n, segment=(4, 6), out=outs3, logits_out=lg3, logprobs_out=lp3,
+                   row_seeds=[91] * len(rows), row_offsets=rows, **kw)
+        return [outs, lg, lp, outs3, lg3, lp3]
+    for model in ('class', 'text'):
+        put('segments', model, lambda p, g, m=model: segments(m, p, g))
+    for model in ('class', 'text', 'bidirectional', 'l3_parallel_add'):
+        put('score', model, lambda p, g, m=model: [engine(m).score(B, cond_of(m), [c[:, :k].contiguous() for c in codes_of(m, 92)], precision=p, return_logits=True)
+                                                   for k in (n, 1)], graph=False)
+
+    # ---- refusals, through the C ABI: what the Python surface checks first never reaches the library
+    def ptr(t):
+        return C.c_void_p(t.data_ptr())
+
+    def raw_sample(eng, model, rows=B, prefix_len=None, opts=True):
+        o = _lib.hqt_sample_opts()
+        o.precision, o.n_steps, o.temperature_top, o.temperature_bot, o.seed = _lib.PRECISION_EXACT, n, 1.0, 1.0, 5
+        cond = cond_of(model, rows).to(dev)
+        outs = [torch.zeros((rows, n), dtype=torch.int64, device=dev), torch.zeros((rows, n, 4), dtype=torch.int64, device=dev)]
+        head = [eng.h, rows, ptr(cond), C.byref(o) if opts else None, None]
+        tail = [None, None, None, ptr(outs[0]), ptr(outs[1]), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)]
+        if prefix_len is None:
+            return eng.lib.hqt_sample(*head, *tail)
+        px = [torch.zeros((rows, prefix_len), dtype=torch.int64, device=dev), torch.zeros((rows, prefix_len, 4), dtype=torch.int64, device=dev)]
+        return eng.lib.hqt_sample_prefix(*head, prefix_len, ptr(px[0]), ptr(px[1]), *tail)
+
+    def raw_score(eng, model):
+        codes = [c.to(dev) for c in codes_of(model, 92)]
+        cond, lp = cond_of(model).to(dev), torch.zeros((B, n, 5), device=dev)
+        return eng.lib.hqt_score(eng.h, B, ptr(cond), (C.c_void_p * 3)(*[c.data_ptr() for c in codes]), n, _lib.PRECISION_EXACT, ptr(lp), None,
+                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+
+    def set_rows(eng, rows):
+        t = row_sampler_table(2, table[:rows])
+        return eng.lib.hqt_set_row_samplers(eng.h, rows, t.ctypes.data_as(C.POINTER(_lib.hqt_row_sampler)))
+
+    def set_keep(eng, rows):
+        m = np.ones((rows, n), dtype=np.uint8)
+        kept = [torch.zeros((rows, n), dtype=torch.int64, device=dev), torch.zeros((rows, n, 4), dtype=torch.int64, device=dev)]
+        return eng.lib.hqt_set_keep_mask(eng.h, rows, n, m.ctypes.data_as(C.c_void_p), (C.c_void_p * 3)(*[t.data_ptr() for t in kept]))
+
+    def set_groups(eng, table_):
+        g = np.asarray(table_, dtype=np.int32)
+        return eng.lib.hqt_set_prompt_groups(eng.h, len(g), 2, g.ctypes.data_as(C.c_void_p))
+
+    def set_logprob(eng):
+        eng._refusal_buf = torch.zeros((B, n, 5), device=dev)
+        return eng.lib.hqt_set_logprob_out(eng.h, ptr(eng._refusal_buf))
+
+    refusals = [
+        ('row_table_wrong_B', 'class', lambda e: set_rows(e, 3), lambda e: raw_sample(e, 'class')),
+        ('keep_table_wrong_B', 'class', lambda e: set_keep(e, 3), lambda e: raw_sample(e, 'class')),
+        ('group_table_wrong_B', 'text', lambda e: set_groups(e, [0, 1, 1]), lambda e: raw_sample(e, 'text')),
+        ('segment_on_prefix_entry', 'class', lambda e: e.lib.hqt_set_segment(e.h, 0, 2), lambda e: raw_sample(e, 'class', prefix_len=P)),
+        ('continuation_without_pass', 'class', lambda e: e.lib.hqt_set_segment(e.h, 2, 4), lambda e: raw_sample(e, 'class')),
+        ('groups_with_prefix', 'text', lambda e: set_groups(e, [0, 1, 1, 0]), lambda e: raw_sample(e, 'text', prefix_len=P)),
+        ('keep_on_prefix_entry', 'class', lambda e: set_keep(e, B), lambda e: raw_sample(e, 'class', prefix_len=P)),
+        ('guidance_row_outside_B', 'class', lambda e: e.lib.hqt_set_guidance(e.h, 1, guide_pair_table(2, [(0, 5, 1.5)])), lambda e: raw_sample(e, 'class')),
+        ('null_opts_behind_table', 'class', lambda e: set_rows(e, B), lambda e: raw_sample(e, 'class', opts=False)),
+        ('score_behind_row_table', 'class', lambda e: set_rows(e, B), lambda e: raw_score(e, 'class')),
+        ('score_behind_logprob_and_segment', 'class', lambda e: set_logprob(e) or e.lib.hqt_set_segment(e.h, 0, 2), lambda e: raw_score(e, 'class')),
+        # not a refusal: a segment alone is cleared by hqt_score without one, and the plain call behind it runs all n positions
+        ('score_behind_segment_alone', 'class', lambda e: e.lib.hqt_set_segment(e.h, 0, 2), lambda e: raw_score(e, 'class')),
+    ]
+    for name, model, stage, call in refusals:
+        eng = engine(model)
+        with torch.cuda.device(dev):
+            staged_rc = stage(eng)
+            rc = call(eng)
+            text = eng.lib.hqt_last_error().decode() if rc != 0 else ''
+        after = fn_of(model)(B, cond_of(model), n, precision=_lib.PRECISION_EXACT, use_graph=False, seed=93)
+        torch.cuda.synchronize()
+        rec[f'staged/refusals/{name}'] = {'staged_rc': int(staged_rc), 'rc': int(rc), 'error': text, 'after': [digest(t) for t in flat_all(after)]}
+    for eng in engines.values():
+        eng.close()
+
+
 def record() -> dict:
     from hqtransformer_amd import _lib
     from hqtransformer_amd.spec import Stage2Spec
@@ -198,6 +375,7 @@ def record() -> dict:
     wide = Stage2Spec(embed_dim=1536, n_layers=1, n_heads=24, n_layers_depth=1, vocab_top=8192, vocab_bot=8192, vocab_txt=64,
                       ctx_len_img=64, ctx_len_txt=16, n_classes=1000, cond=1, embedding=0)
     sample_cases(rec, 'merged640', wide, 31, 640, 2, policy=_lib.POLICY_THROUGHPUT, persist=(True,))
+    staged_cases(rec, tiny)
     stage1_cases(rec)
     surface_cases(rec)
     return rec
@@ -209,6 +387,21 @@ COVERAGE = {
     'merged640/split/persist=1': ('variant:split_gemm_kslices',),
     'stage1/decode/split': ('variant:conv3x3_planes_out', 'variant:conv_out_direct'),
     'stage1/decode/fast': ('gn_apply',),
+    'staged/prefix/class/exact': ('embed_prefix', 'code_logprob'),
+    'staged/prefix/text/fast': ('embed_prefix', 'code_logprob'),
+    'staged/prefix/l3_parallel_add/exact': ('embed_prefix', 'code_logprob'),
+    'staged/keep/class/exact': ('embed_prefix',),
+    'staged/keep_guided/class/fast': ('embed_prefix', 'guide_logits'),
+    'staged/row_samplers/class/fast/persist=1': ('persist_position',),
+    'staged/row_samplers/bidirectional/exact': ('bidir_sampler_top', 'bidir_head_ln'),
+    'staged/guidance/class/exact': ('guide_logits', 'code_logprob'),
+    'staged/prompt_groups/text/exact': ('prompt_fanout',),
+    'staged/segments/class/fast': ('kv_gather_rows', 'code_logprob'),
+    'staged/segments/text/exact': ('kv_gather_rows', 'prompt_fanout'),
+    'staged/score/class/exact': ('score_logprob', 'embed_prefix', 'score_depth_input'),
+    'staged/score/text/fast': ('score_logprob', 'embed_prefix'),
+    'staged/score/bidirectional/fast': ('score_logprob', 'bidir_head_ln'),
+    'staged/score/l3_parallel_add/exact': ('score_logprob',),
 }
 
 
