@@ -89,7 +89,8 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
     const T* vc = reinterpret_cast<const T*>(a.vcache) + (long long)b * a.Tmax * D + h * hs + c * 8;
     float qv[8];
     unpack_row<T>(reinterpret_cast<const raw_t<T>*>(q), qv);                              // independent of the step state: in flight while t_base arrives
-    const int tb = a.t_base + (a.t_base_dev ? *a.t_base_dev : 0);
+    // (a rolling pass: every sample at its own position -- the wave's key count is its own, and its arithmetic depends on nothing else)
+    const int tb = a.t_base + (a.row_pos ? row_live(a.row_pos, b) : (a.t_base_dev ? *a.t_base_dev : 0));
     const int nkeys = a.causal ? tb + qi + 1 : tb + a.Tq;
     const float scale = 1.0f / sqrtf((float)hs);
     constexpr int PB = 8;                        // passes whose loads are issued together
@@ -578,7 +579,9 @@ __global__ __launch_bounds__(256) void attention_heads8_kernel(AttnArgs a) {
 #pragma unroll
         for (int e = 0; e < NRAW<T>; ++e) qraw[e] = qs[e];                 // independent of the step state: in flight while t_base arrives
     }
-    const int nkeys = a.t_base + (a.t_base_dev ? *a.t_base_dev : 0) + 1;       // Tq == 1: causal or not, the query sees every cached key and itself
+    // Tq == 1: causal or not, the query sees every cached key and itself.  A rolling pass: the key count is per sample, i.e. per 8-lane group -- the groups
+    // of a wave leave the chunk loop at different trips, and every shuffle below stays inside one group
+    const int nkeys = a.t_base + (a.row_pos ? row_live(a.row_pos, b) : (a.t_base_dev ? *a.t_base_dev : 0)) + 1;
     raw_t<T> kb[2][CH][NRAW<T>], vb[2][CH][NRAW<T>];
     auto fetch = [&](int j0, int slot) {
 #pragma unroll

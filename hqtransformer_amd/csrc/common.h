@@ -196,12 +196,24 @@ struct GemmArgs {
     float* k_slabs;          //   fp32 [slice][M][N] in k_slabs; split_rows_combine_kernel adds the slices in index order, the bias and the residual (launch_split_gemm)
     int tile_panel;          // workgroup-order experiments.  SPLIT 3x3 convs: pixel tiles per panel (0: the n-tile runs fastest; measured: no effect,
                              // profiles/r04_conv_tile_order.txt)
+    const int* row_pos;      // STORE_QKV of a rolling pass (hqt_set_row_positions): the K / V row of group b = m / rows_per_group goes to cache row
+                             //   row_offset + row_live(row_pos, b) in place of row_offset + *row_offset_dev.  NULL: the scalar, as ever
 };
+
+// Rolling pass: row_pos[b] is the position row b of the pass draws in this step; negative = an idle row (an empty slot, or a row past its last position).
+// An idle row still occupies a row of every GEMM: it computes as a row at position 0 would (row 0 of its OWN cache slot, one key) and the samplers leave
+// everything the caller can see of it alone (row_idle).
+__device__ __forceinline__ int row_live(const int* row_pos, int b) { const int p = row_pos[b]; return p < 0 ? 0 : p; }
+__device__ __forceinline__ bool row_idle(const int* row_pos, int b) { return row_pos && row_pos[b] < 0; }
+// the K / V cache row offset of group b: per row in a rolling pass, else the launch-uniform value the kernel fetched at its start
+__device__ __forceinline__ int qkv_row_of(const GemmArgs& g, int b, int uniform) { return g.row_pos ? row_live(g.row_pos, b) : uniform; }
 
 struct StepState {           // lives in device memory; lets one captured graph serve every position AND every call
     int step;                // current top position (0-based)
     int t_base;              // KV rows already in the body cache
 };
+// the position row b draws: its own in a rolling pass, else the step state's
+__device__ __forceinline__ int step_of(const StepState* state, const int* row_pos, int b) { return row_pos ? row_live(row_pos, b) : state->step; }
 struct RowKey {              // per batch row, device memory owned by the handle: the Philox key of the row's call and its global index
     unsigned long long seed;
     long long global_row;

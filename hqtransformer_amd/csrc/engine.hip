@@ -154,6 +154,8 @@ struct hqt_handle {
     size_t guide_room() const { return (size_t)std::max(1, cfg.max_batch / 2); }      // a row is in at most one pair
     unsigned char* keep_mask = nullptr;       // [max_batch * max_steps] mask of the current call
     int* group_of_row = nullptr;              // [max_batch] group table of the current call
+    int* row_pos = nullptr;                   // [2 * max_batch] rolling pass (hqt_set_row_positions): [0, max_batch) the position every row stands at, moved on by
+                                              // advance_rows between the steps of a call; [max_batch, 2 max_batch) the table as the call received it (what it copies out)
     // What the hqt_set_* calls leave for the next hqt_sample / hqt_sample_l3 (or prefix entry point) of this handle, which takes all of it
     struct Staged {
         std::vector<hqt_row_sampler> row_set;     // hqt_set_row_samplers: host table
@@ -166,6 +168,8 @@ struct hqt_handle {
         int groups_G = 0;
         bool seg = false;                         // hqt_set_segment: positions [seg_start, seg_stop)
         int seg_start = 0, seg_stop = 0;
+        std::vector<int32_t> roll;                // hqt_set_row_positions: host table [B] of next positions (-1: empty slot) and the steps of the call
+        int roll_k = 0;
         // what hqt_score refuses; deliberately not the segment: one staged alone is cleared there without a refusal
         bool holds_table() const { return !row_set.empty() || logprob || !guide.empty() || !keep.empty() || !groups.empty(); }
     } staged;
@@ -179,6 +183,8 @@ struct hqt_handle {
     size_t pg_bytes = 0;                      // bytes of pg_k (= pg_v)
     // the pass a segment stopped in: what a continuation must match, and `pos`, the position it goes on from (the step state says pos over t_live keys)
     struct Paused { bool live = false; int B = 0, n_steps = 0, levels = 0, precision = 0, pos = 0; } paused;
+    // the rolling pass the last hqt_set_row_positions call left: what the next one must match, and per slot the position it draws next (-1: empty)
+    struct Rolling { bool live = false; int B = 0, n_steps = 0, levels = 0, precision = 0; std::vector<int32_t> next; } rolling;
     int64_t *cond_buf = nullptr, *codes_top = nullptr, *codes_bot = nullptr;   // call-independent homes of cond / the drawn codes
     int64_t* codes_l2 = nullptr;              // third level: [B, max_steps, 16]
     Lin head_l2;                              // head_levels.2 (three-level models; head_top / head_bot hold levels 0 / 1)
@@ -576,6 +582,7 @@ static int alloc_workspace(hqt_handle* hp) {
         CHK(dev_alloc(h.get(), (void**)&h->guide, h->guide_room() * sizeof(GuidePair), true));
         CHK(dev_alloc(h.get(), (void**)&h->keep_mask, B * (size_t)c.max_steps, true));
         CHK(dev_alloc(h.get(), (void**)&h->group_of_row, B * sizeof(int), true));
+        CHK(dev_alloc(h.get(), (void**)&h->row_pos, 2 * B * sizeof(int), true));
         CHK(dev_alloc(h.get(), (void**)&h->cond_buf, B * (size_t)std::max(1, c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : 1) * 8, true));
         CHK(dev_alloc(h.get(), (void**)&h->codes_top, B * (size_t)c.max_steps * 8, true));
         CHK(dev_alloc(h.get(), (void**)&h->codes_bot, B * (size_t)c.max_steps * 4 * 8, true));
@@ -658,6 +665,7 @@ extern "C" int hqt_clone(hqt_handle* src, hqt_handle** out) {
     h->clear_staged();                           // a lane has its own staged tables, buffer and segment
     h->pg_k = h->pg_v = nullptr; h->pg_x = nullptr; h->pg_cap = 0; h->pg_bytes = 0;      // ... its own prefill staging (hqt_set_prompt_groups on the lane sizes it)
     h->paused = hqt_handle::Paused();            // ... and its own paused pass
+    h->rolling = hqt_handle::Rolling();          // ... and its own rolling pass
     h->nparts = h->npartsd = 0;
     h->pbody.d_phases = nullptr; h->pfull.d_phases = nullptr;      // phase tables hold workspace pointers: bound per handle (persist_bind)
     h->persist_used = false; h->persist_tripped = false; h->capture_persist = false; h->graph_has_persist = false;
@@ -1184,6 +1192,10 @@ struct SampleCtx {
     int n_groups = 0;                            // with a table: cond is [n_groups, T]
     bool seg = false;                            // hqt_set_segment staged a segment: the call runs positions [start, stop) of its n_steps ...
     int start = 0, stop = 0;                     // ... (without one: 0 and n_steps); start > 0 continues the handle's paused pass
+    const int32_t* roll = nullptr;               // host table [B] staged by hqt_set_row_positions, NULL: every row stands at the step state's position
+    int roll_k = 0;                              // ... and the steps the call runs (it then is positions [0, roll_k) of the launch loop: start = 0, stop = roll_k)
+    const int* row_pos = nullptr;                // ... and its device copy (h->row_pos) that the launches of a rolling call read, NULL otherwise
+    const int64_t* roll_prev[3] = {nullptr, nullptr, nullptr};   // ... and the caller's out_*: where the codes of position pos[b] - 1 of every continued row are read
     hipStream_t st;
     Mode md;
 };
@@ -1353,7 +1365,8 @@ static int persist_bind(hqt_handle* h) {
 }
 
 static bool persist_on(hqt_handle* h, const SampleCtx& c, const PersistProg& pr) {
-    return h->persist_enabled && !h->persist_tripped && pr.ok && pr.d_phases && c.md.fast && c.B <= 64 && h->policy == HQT_POLICY_LATENCY && !h->parent;
+    return h->persist_enabled && !h->persist_tripped && pr.ok && pr.d_phases && c.md.fast && c.B <= 64 && h->policy == HQT_POLICY_LATENCY && !h->parent &&
+           !c.row_pos;       // a rolling pass takes the launch chain: the persistent launch keeps ONE t_base for all its rows (persist.h)
 }
 
 static int run_persist(hqt_handle* h, const SampleCtx& c, const PersistProg& pr, float* x32, int write_back, const int* t_dev, const char* slot) {
@@ -1428,6 +1441,9 @@ static int run_block(hqt_handle* h, const SampleCtx& c, const BlockW& bw, const 
     CHK(normed(g, bw.ln1_g, bw.ln1_b, bw.qkv));
     g.C = h->qbuf; g.C2 = kc; g.C3 = vc; g.ldc = D; g.qkv_D = D; g.store = STORE_QKV;
     g.rows_per_group = Tq; g.group_stride = Tcache; g.row_offset = t_base; g.row_offset_dev = t_base_dev;
+    // a rolling pass: where a decode step of the body reads the step state's t_base, every sample reads its own position (the depth blocks never do)
+    const int* const row_pos = t_base_dev ? c.row_pos : nullptr;
+    g.row_pos = row_pos;
     // One query over one key (depth sub-step 0: hierarchical_ar.py:690-702 with an empty cache): softmax of a single
     // score is exactly 1, so the attention output is the value row itself.  The GEMM then skips the query third of
     // the fused weight (rows [D, 3D) only), appends K/V to the cache for sub-step 1 and writes V straight into the
@@ -1444,7 +1460,7 @@ static int run_block(hqt_handle* h, const SampleCtx& c, const BlockW& bw, const 
     } else {
         CHK(ar_linear(h, c.md, g, bw.qkv, adt, adt, c.st, "gemm_qkv"));
         Timed t(h, "attention", c.st);
-        AttnArgs a{h->qbuf, kc, vc, h->abuf, c.B, Tq, h->cfg.n_heads, D / h->cfg.n_heads, Tcache, t_base, t_base_dev, causal, adt, pk, nullptr};
+        AttnArgs a{h->qbuf, kc, vc, h->abuf, c.B, Tq, h->cfg.n_heads, D / h->cfg.n_heads, Tcache, t_base, t_base_dev, causal, adt, pk, nullptr, row_pos};
         if (h->timing) count_variant(h, "variant:attn_%s:%s", attention_kernel_name(attention_choice(a)), r.x == h->xd ? "depth" : "body");
         HIPCHK(launch_attention(a, c.st));
     }
@@ -1549,18 +1565,18 @@ static int run_depth_input(hqt_handle* h, const SampleCtx& c, int sub, bool dln,
         const int tbl = sub == 1 ? 0 : (sub < 5 ? 1 : 2);
         const float* tok = tbl == 0 ? W(h, "tok_emb_top.weight") : (tbl == 1 ? W(h, "tok_emb_bot.weight") : W(h, "tok_emb_levels.2.weight"));
         HIPCHK(launch_depth_embed_causal(c.feed[p.lv], p.lv ? p.out_stride : 1, p.out_slot, c.n_steps, h->state, tok,
-                                         W(h, "pos_emb_depth.weight") + (size_t)p.tbase * D, h->xd, B, D, xpk, pk, h->partsd, c.st, V));
+                                         W(h, "pos_emb_depth.weight") + (size_t)p.tbase * D, h->xd, B, D, xpk, pk, h->partsd, c.st, V, c.row_pos));
     } else if (s.lv == 1) {   // emb(top code) + positions 0..3 (fuse: the top sampler wrote them)
         if (fuse) return HQT_OK;
         Timed t(h, "embed", c.st);
         HIPCHK(launch_depth_embed(c.feed[0], c.n_steps, h->state, W(h, "tok_emb_top_depth.weight"), W(h, "pos_emb_depth.weight"),
-                                  h->xd, B, D, xpk, pk, h->partsd, c.st, V, dmul * D));
+                                  h->xd, B, D, xpk, pk, h->partsd, c.st, V, dmul * D, c.row_pos));
     } else {                  // parent's level-1 embedding + position i (+ emb(top code): 'add'), 16 tokens
         Timed t(h, "embed", c.st);
         HIPCHK(launch_depth_embed_l2(c.feed[0], c.feed[1], c.n_steps, h->state,
                                      cf.depth_decoding == HQT_DEPTH_PARALLEL_ADD ? W(h, "tok_emb_top_depth.weight") : nullptr,
                                      W(h, "tok_emb_depth_levels.1.weight"), W(h, "pos_emb_depths.1.weight"),
-                                     h->xd, B, D, xpk, pk, h->partsd, c.st, V, dmul * D));
+                                     h->xd, B, D, xpk, pk, h->partsd, c.st, V, dmul * D, c.row_pos));
     }
     return HQT_OK;
 }
@@ -1660,6 +1676,7 @@ static int run_depth_head(hqt_handle* h, const SampleCtx& c, int Tq_body, bool p
                 sa.row_lv_t = bidir ? 0 : s.lv; sa.row_lv_k = bidir ? 1 : s.lv;
             }
             if (c.keep) sa.keep = h->keep_mask;
+            sa.row_pos = c.row_pos;
             if (fuse && sub == 0) {
                 const bool dln_next = dln_of(sub_step(cf, 1));
                 sa.emb_tok = W(h, "tok_emb_top_depth.weight"); sa.emb_pos = W(h, "pos_emb_depth.weight");
@@ -1704,6 +1721,7 @@ static EmbedArgs embed_args(hqt_handle* h, const SampleCtx& c, const int64_t* co
                 codes[0], codes[1], h->x, nullptr, 0, h->parts};
     if (c.levels == 3) { e.levels = 3; e.tok_l2 = W(h, "tok_emb_levels.2.weight"); e.codes_l2 = codes[2]; }
     e.V = cf.vocab_top; e.n_classes = cf.n_classes;
+    e.row_pos = c.row_pos;                       // (read by the decode step's kernel only: a rolling call runs no prefill)
     return e;
 }
 
@@ -1730,21 +1748,22 @@ static int run_decode_step(hqt_handle* h, const SampleCtx& c) {      // one KV-c
         HIPCHK(launch_embed_step(e, c.st));
     }
     CHK(run_position(h, c, 1, 0, true));
-    HIPCHK(launch_advance_step(h->state, 1, c.st));
+    if (c.row_pos) HIPCHK(launch_advance_rows(h->row_pos, c.B, c.n_steps, c.st));      // a rolling pass: every live row moves on; the step state is not read
+    else HIPCHK(launch_advance_step(h->state, 1, c.st));
     return HQT_OK;
 }
 
 static int sample_run(hqt_handle* h, const SampleCtx& c);
 
-// One buffer of the pinned ring (hqt_handle::rows_pinned) as the five host tables it holds.  ring_slot is the only place that knows their order and
+// One buffer of the pinned ring (hqt_handle::rows_pinned) as the six host tables it holds.  ring_slot is the only place that knows their order and
 // sizes: the keys come first, and every later section starts at a multiple of 4 bytes, which aligns each for its type.
-struct RingSlot { RowKey* keys; RowSampler* samplers; GuidePair* pairs; int32_t* groups; unsigned char* keep; size_t bytes; };
+struct RingSlot { RowKey* keys; RowSampler* samplers; GuidePair* pairs; int32_t* groups; int32_t* pos; unsigned char* keep; size_t bytes; };
 static_assert(alignof(RowKey) == 8 && alignof(RowSampler) == 4 && alignof(GuidePair) == 4 && alignof(int32_t) == 4 &&
               sizeof(RowKey) % 4 == 0 && sizeof(RowSampler) % 4 == 0 && sizeof(GuidePair) % 4 == 0, "the order of a ring slot's sections no longer aligns each for its type");
 static RingSlot ring_slot(const hqt_handle* h, RowKey* base) {      // (base null: only `bytes`, what a slot needs)
     const size_t B = h->cfg.max_batch;
     const size_t samplers = B * sizeof(RowKey), pairs = samplers + B * sizeof(RowSampler), groups = pairs + h->guide_room() * sizeof(GuidePair),
-                 keep = groups + B * sizeof(int32_t);
+                 pos = groups + B * sizeof(int32_t), keep = pos + B * sizeof(int32_t);
     RingSlot r{};
     r.bytes = keep + B * h->cfg.max_steps;
     if (!base) return r;
@@ -1753,6 +1772,7 @@ static RingSlot ring_slot(const hqt_handle* h, RowKey* base) {      // (base nul
     r.samplers = reinterpret_cast<RowSampler*>(p + samplers);
     r.pairs = reinterpret_cast<GuidePair*>(p + pairs);
     r.groups = reinterpret_cast<int32_t*>(p + groups);
+    r.pos = reinterpret_cast<int32_t*>(p + pos);
     r.keep = p + keep;
     return r;
 }
@@ -1799,6 +1819,8 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     c.seg = s.seg;
     c.start = c.seg ? s.seg_start : 0;
     c.stop = c.seg ? s.seg_stop : c.n_steps;
+    c.roll = s.roll.empty() ? nullptr : s.roll.data();
+    c.roll_k = s.roll_k;
     if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
     const hqt_config& cf = h->cfg;
     if (c.levels == 2 && !cf.has_stage2) return fail(HQT_ERR_STATE, "handle was created without stage 2");
@@ -1825,6 +1847,45 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
             if (p.precision != c.precision) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass runs in precision %d, this call asks for precision %d (the cache holds that precision's type)", p.precision, c.precision);
             if (p.pos != c.start) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass stands at position %d, this segment has start=%d", p.pos, c.start);
         }
+    }
+    if (c.roll) {
+        const int n = c.n_steps;
+        if (cf.cond_type == HQT_COND_TEXT)
+            return fail(HQT_ERR_INVALID, "hqt_set_row_positions: a rolling pass on a text-conditional handle is not built (a row that joins at position 0 needs a prompt prefill of its own)");
+        if (c.with_prefix) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: the staged positions were taken by a prefix entry point; a rolling pass with a code prefix is not built (hqt_sample / hqt_sample_l3 take the table)");
+        if (c.seg) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged segment (hqt_set_segment) is not built: the k of the table is the call's span");
+        if (c.keep) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged keep table (hqt_set_keep_mask) is not built");
+        if (c.groups) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged prompt-group table (hqt_set_prompt_groups) is not built");
+        if ((int)s.roll.size() != B) return fail(HQT_ERR_INVALID, "hqt_set_row_positions staged a table of B=%d, this call has B=%d", (int)s.roll.size(), B);
+        if (c.roll_k < 1 || c.roll_k > n) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: k=%d outside [1, n_steps = %d]", c.roll_k, n);
+        for (int b = 0; b < B; ++b)
+            if (c.roll[b] < -1 || c.roll[b] > n - 1)
+                return fail(HQT_ERR_INVALID, "hqt_set_row_positions: pos[%d]=%d outside [-1, n_steps - 1 = %d] (-1: an empty slot)", b, c.roll[b], n - 1);
+        for (int i = 0; i < c.n_guide; ++i) {      // (rows outside [0, B) are refused below, by the pair checks of every call)
+            const hqt_guide_pair& p = c.guide[i];
+            if (p.pos_row < 0 || p.pos_row >= B || p.neg_row < 0 || p.neg_row >= B || c.roll[p.pos_row] == c.roll[p.neg_row]) continue;
+            if (c.roll[p.pos_row] < 0 || c.roll[p.neg_row] < 0)
+                return fail(HQT_ERR_INVALID, "guidance pair %d: exactly one of rows %d and %d is an empty slot of the rolling pass (positions %d and %d)", i, p.pos_row, p.neg_row, c.roll[p.pos_row], c.roll[p.neg_row]);
+            return fail(HQT_ERR_INVALID, "guidance pair %d: rows %d and %d stand at different positions of the rolling pass (%d and %d): both rows of a pair draw one position", i, p.pos_row, p.neg_row,
+                        c.roll[p.pos_row], c.roll[p.neg_row]);
+        }
+        // every slot against the rolling pass this handle holds: empty, a join at 0, or exactly where the slot stands
+        const hqt_handle::Rolling& r = h->rolling;
+        if (r.live) {
+            if (r.B != B) return fail(HQT_ERR_STATE, "hqt_set_row_positions: the rolling pass has B=%d, this call has B=%d", r.B, B);
+            if (r.n_steps != n) return fail(HQT_ERR_STATE, "hqt_set_row_positions: the rolling pass has n_steps=%d, this call has n_steps=%d", r.n_steps, n);
+            if (r.levels != c.levels) return fail(HQT_ERR_STATE, "hqt_set_row_positions: the rolling pass has %d code levels, this call has %d", r.levels, c.levels);
+            if (r.precision != c.precision) return fail(HQT_ERR_STATE, "hqt_set_row_positions: the rolling pass runs in precision %d, this call asks for precision %d (the cache holds that precision's type)", r.precision, c.precision);
+        }
+        for (int b = 0; b < B; ++b) {
+            const int want = r.live ? r.next[b] : -1;
+            if (c.roll[b] <= 0 || c.roll[b] == want) continue;
+            if (!r.live) return fail(HQT_ERR_STATE, "hqt_set_row_positions: row %d continues at position %d, and this handle holds no rolling pass (none was begun, or another call has "
+                                                    "overwritten its cache since): every entry must be 0 (join) or -1 (empty)", b, c.roll[b]);
+            if (want < 0) return fail(HQT_ERR_STATE, "hqt_set_row_positions: row %d continues at position %d, but the slot is empty in the rolling pass (0 joins, -1 stays empty)", b, c.roll[b]);
+            return fail(HQT_ERR_STATE, "hqt_set_row_positions: row %d continues at position %d, but the slot stands at position %d of the rolling pass", b, c.roll[b], want);
+        }
+        c.start = 0; c.stop = c.roll_k;
     }
     if (c.groups && c.with_prefix)
         return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups together with a code prefix (a prefix entry point) is not built: the prompt and the prefix are one prefill whose prefix rows differ per row");
@@ -1919,6 +1980,24 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
         HIPCHK(launch_copy_prefix(c.prefix[i], codes[i], B, c.prefix_len, c.n_steps, LEVEL_WIDTH[i], cf.vocab_top, c.st));
     // whatever this call is, it writes the body cache and the step state: a paused pass is over, or goes on below and is recorded anew behind its segment
     h->paused.live = false;
+    h->rolling.live = false;                     // ... and so is a rolling pass, unless this call is its next one (recorded anew below)
+    if (c.roll) {
+        c.row_pos = h->row_pos;
+        for (int i = 0; i < c.levels; ++i) c.roll_prev[i] = out[i];
+        bool any = false;
+        for (int b = 0; b < B; ++b) any = any || c.roll[b] >= 0;
+        if (any) {                               // (only empty slots: legal, draws nothing, launches nothing)
+            CHK(sample_run(h, c));
+            for (int i = 0; i < c.levels; ++i)
+                HIPCHK(launch_copy_row_positions(codes[i], out[i], h->row_pos + cf.max_batch, B, c.n_steps, LEVEL_WIDTH[i], 0, c.roll_k, c.st));
+        }
+        hqt_handle::Rolling& r = h->rolling;
+        r.live = true; r.B = B; r.n_steps = c.n_steps; r.levels = c.levels; r.precision = c.precision;
+        r.next.assign(B, -1);
+        for (int b = 0; b < B; ++b) if (c.roll[b] >= 0 && c.roll[b] + c.roll_k < c.n_steps) r.next[b] = c.roll[b] + c.roll_k;
+        r.live = std::any_of(r.next.begin(), r.next.end(), [](int32_t p) { return p >= 0; });      // every slot empty: the pass is over, nothing is left to match
+        return HQT_OK;
+    }
     // a continuation reads the codes of position start - 1 where the caller holds them: a level that is not forced takes them from out_* (the caller may have
     // edited them, or gathered its rows along with hqt_select_rows)
     for (int i = 0; i < (c.start > 0 ? c.levels : 0); ++i)
@@ -2028,6 +2107,25 @@ extern "C" int hqt_set_prompt_groups(hqt_handle* h, int B, int n_groups, const i
     return HQT_OK;
 }
 
+extern "C" int hqt_set_row_positions(hqt_handle* h, int B, const int32_t* pos, int k) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    h->staged.roll.clear();
+    h->staged.roll_k = 0;
+    if (B == 0 || !pos) return HQT_OK;
+    const hqt_config& c = h->cfg;
+    if (!c.has_stage2) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: the handle was created without stage 2");
+    if (c.cond_type == HQT_COND_TEXT)
+        return fail(HQT_ERR_INVALID, "hqt_set_row_positions: a rolling pass on a text-conditional handle is not built (a row that joins at position 0 needs a prompt prefill of its own)");
+    if (B < 1 || B > c.max_batch) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: B=%d outside [1, max_batch=%d]", B, c.max_batch);
+    if (k < 1 || k > c.max_steps) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: k=%d outside [1, n_steps] (n_steps <= max_steps = %d)", k, c.max_steps);
+    for (int b = 0; b < B; ++b)
+        if (pos[b] < -1 || pos[b] > c.max_steps - 1)
+            return fail(HQT_ERR_INVALID, "hqt_set_row_positions: pos[%d]=%d outside [-1, n_steps - 1] (n_steps <= max_steps = %d; -1: an empty slot)", b, pos[b], c.max_steps);
+    h->staged.roll.assign(pos, pos + B);         // checked against B, n_steps and the rolling pass by the call that takes it
+    h->staged.roll_k = k;
+    return HQT_OK;
+}
+
 extern "C" int hqt_set_segment(hqt_handle* h, int start, int stop) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
     h->staged.seg = true;                        // checked against n_steps and the paused pass by the call that takes it
@@ -2042,6 +2140,7 @@ extern "C" int hqt_select_rows(hqt_handle* h, int B_new, const int32_t* rows_fro
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
     const hqt_config& cf = h->cfg;
     const hqt_handle::Paused& p = h->paused;
+    if (h->rolling.live) return fail(HQT_ERR_STATE, "hqt_select_rows: this handle holds a rolling pass (hqt_set_row_positions), whose slots are reused in place; re-mapping its rows is not built");
     if (!p.live) return fail(HQT_ERR_STATE, "hqt_select_rows: this handle holds no paused pass (hqt_set_segment with stop < n_steps leaves one)");
     if (!rows_from) return fail(HQT_ERR_INVALID, "hqt_select_rows: rows_from is NULL");
     if (B_new < 1 || B_new > cf.max_batch) return fail(HQT_ERR_INVALID, "hqt_select_rows: B_new=%d outside [1, max_batch=%d]", B_new, cf.max_batch);
@@ -2171,6 +2270,7 @@ extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_
         c.feed[i] = own[i]; c.out[i] = own[i];
     }
     h->paused.live = false;                        // the pass overwrites the body cache and the step state: a paused pass (hqt_set_segment) is over
+    h->rolling.live = false;                       // ... and so is a rolling pass (hqt_set_row_positions)
     HIPCHK(launch_set_step(h->state, 0, 0, c.st));
     // ---- body: n rows per sample (text: the T prompt rows, then the input rows of positions 1 .. n - 1)
     const int D = cf.embed_dim, V = cf.vocab_top, T = text ? cf.ctx_len_txt : 0;
@@ -2285,7 +2385,7 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
     if ((c.row_seeds || c.row_offsets) && (!c.row_seeds || !c.row_offsets)) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
     // merged steps: per-row Philox keys and / or sampler settings (host arrays of B <= max_batch entries, through the pinned ring); a guided call: its pair
     // table, and ALWAYS the keys -- the implicit ones (seed, sample_offset + b) are built here, the negative row of every pair taking its positive row's
-    if (c.row_seeds || c.row_set || c.guide || c.keep || c.groups) {
+    if (c.row_seeds || c.row_set || c.guide || c.keep || c.groups || c.roll) {
         int slot = 0;
         RingSlot ring;
         CHK(rows_ring_take(h, &slot, &ring));
@@ -2302,6 +2402,10 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         if (c.guide) CHK(ring_send(ring.pairs, c.guide, (size_t)c.n_guide, h->guide, c.st));
         if (c.keep) CHK(ring_send(ring.keep, c.keep, (size_t)B * c.n_steps, h->keep_mask, c.st));
         if (c.groups) CHK(ring_send(ring.groups, c.groups, (size_t)B, h->group_of_row, c.st));
+        if (c.roll) {             // the positions the rows stand at (moved on between the steps) and, behind them, the table as received (what sample_call copies out)
+            CHK(ring_send(ring.pos, c.roll, (size_t)B, h->row_pos, c.st));
+            CHK(ring_send(ring.pos, (const int32_t*)nullptr, (size_t)B, h->row_pos + cf.max_batch, c.st));
+        }
         CHK(ring_sent(h, slot, c.st));
     }
     // the kept codes go into the handle's code buffers (outside any captured graph) behind the mask: every level's embeddings, the samplers' guard and
@@ -2311,6 +2415,9 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
     if (!c.row_seeds && !c.guide) HIPCHK(launch_set_rows(h->rows, B, c.seed, c.sample_offset, c.st));
     int first = c.start;
     const int64_t* const own[3] = {h->codes_top, h->codes_bot, h->codes_l2};
+    // a rolling pass: every continued row reads the codes of its position pos[b] - 1 where the caller holds them, as a segment does (a forced level: force_*)
+    for (int i = 0; i < (c.roll ? c.levels : 0); ++i)
+        if (c.feed[i] == own[i]) HIPCHK(launch_copy_row_positions(c.roll_prev[i], c.out[i], h->row_pos + cf.max_batch, B, c.n_steps, LEVEL_WIDTH[i], -1, 0, c.st));
     if (c.start > 0) {
         // a continuation (hqt_set_segment): no prefill -- the cache holds the prompt rows and every position below start
     } else if (cf.cond_type == HQT_COND_TEXT && c.groups) {
@@ -2365,7 +2472,7 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         int G = 1;
         for (int d = std::min(gmax, remaining); d >= 1; --d) if (remaining % d == 0) { G = d; break; }
         std::vector<uint64_t> key = {(uint64_t)G, (uint64_t)B, (uint64_t)(c.cond != nullptr), (uint64_t)c.noise, (uint64_t)c.logits_out, (uint64_t)c.logprob_out,
-                                     (uint64_t)c.precision, (uint64_t)c.n_steps, (uint64_t)c.levels, (uint64_t)h->policy,
+                                     (uint64_t)c.precision, (uint64_t)c.n_steps, (uint64_t)c.levels, (uint64_t)h->policy + (c.roll ? 16 : 0),      // (+ 16: a rolling pass, never its positions)
                                      (uint64_t)((h->persist_enabled && !h->persist_tripped ? 1 : 0) + (h->single_key ? 0 : 4) + (h->split_kslices ? 0 : 8))};
         for (const int64_t* f : c.feed) key.push_back((uint64_t)f);
         for (const SamplerSet& l : c.lv) {

@@ -423,7 +423,7 @@ __global__ __launch_bounds__(NW * 64, stream_min_waves(MBW, NT, NW, U)) void str
             if (g.store == STORE_QKV) {
                 const int nn = ncol - qkv_part_local * g.qkv_D;
                 long long row = m;
-                if (qkv_part > 0) row = (m / g.rows_per_group) * g.group_stride + m % g.rows_per_group + g.row_offset + qkv_row_dev;
+                if (qkv_part > 0) row = (m / g.rows_per_group) * g.group_stride + m % g.rows_per_group + g.row_offset + qkv_row_of(g, m / g.rows_per_group, qkv_row_dev);
                 st4<TC>(qkv_base + row * g.ldc + nn, v);
                 if (qkv_vcopy) st4<bf16_t>(qkv_vcopy + packed_off(m, nn, g.c_packed_mb), v);
                 continue;
@@ -474,7 +474,7 @@ __global__ __launch_bounds__(NW * 64, stream_min_waves(MBW, NT, NW, U)) void str
             const int nn = ncol - qkv_part_local * g.qkv_D;
             long long row = m;
             if (qkv_part > 0) {
-                row = (m / g.rows_per_group) * g.group_stride + m % g.rows_per_group + g.row_offset + qkv_row_dev;
+                row = (m / g.rows_per_group) * g.group_stride + m % g.rows_per_group + g.row_offset + qkv_row_of(g, m / g.rows_per_group, qkv_row_dev);
             }
             st1<TC>(qkv_base + row * g.ldc + nn, v);
             if (qkv_vcopy) qkv_vcopy[packed_off(m, nn, g.c_packed_mb)] = f32_to_bf16(v);

@@ -129,7 +129,8 @@ __device__ __forceinline__ void gemm_store(const GemmArgs& g, int bz, int m, int
     int orow = m;
     if (g.rows_per_group > 0) {
         orow = (m / g.rows_per_group) * g.group_stride + m % g.rows_per_group + g.row_offset;
-        if (g.row_offset_dev) orow += *g.row_offset_dev;
+        if (g.row_pos) orow += row_live(g.row_pos, m / g.rows_per_group);      // rolling pass: each group at its own cache row
+        else if (g.row_offset_dev) orow += *g.row_offset_dev;
     }
     if (g.store == STORE_QKV) {
         const int part = n / g.qkv_D, nn = n - part * g.qkv_D, which = part + g.qkv_first;

@@ -34,6 +34,7 @@ struct EmbedArgs {
     const float* tok_l2;         // [V, D] tok_emb_levels.2
     const int64_t* codes_l2;     // [B, n_steps, 16]
     int V, n_classes;            // table sizes for the index clamp (0: unchecked)
+    const int* row_pos;          // rolling pass (embed_step only): sample b stands at row_live(row_pos, b) in place of state->step; NULL: the step state
 };
 hipError_t launch_embed_step(const EmbedArgs& a, hipStream_t st);
 // prefix prefill: x[b * stride + row_off + j] = body input row step_off + j of sample b, j < rows (row 0: sos; row s: position s - 1's codes),
@@ -80,9 +81,13 @@ hipError_t launch_kv_gather_rows(const KvGatherArgs& a, hipStream_t st);
 // dst[b, p, :] = src[b, p, :] for p in [p0, p1), both [B, n_steps, width] (one code level of a segment, hqt_set_segment)
 hipError_t launch_copy_positions(const int64_t* src, int64_t* dst, int B, int n_steps, int width, int p0, int p1, hipStream_t st);
 
+// dst[b, p, :] = src[b, p, :] for p in [pos[b] + lo, pos[b] + hi) clipped to [0, n_steps), rows with pos[b] < 0 skipped (pos: device, [B]; a rolling pass)
+hipError_t launch_copy_row_positions(const int64_t* src, int64_t* dst, const int* pos, int B, int n_steps, int width, int lo, int hi, hipStream_t st);
+
 // depth sub-step 1 input: x[b*4+s, :] = tok_top_depth[top[b, step]] + pos_depth[s]
 hipError_t launch_depth_embed(const int64_t* codes_top, int n_steps, const StepState* state, const float* tok,
-                              const float* pos, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V = 0, int tok_ld = 0);
+                              const float* pos, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V = 0, int tok_ld = 0,
+                              const int* row_pos = nullptr);      // row_pos (here and in the two launchers below): a rolling pass, step = row_live(row_pos, b)
 
 // hqt_score: launch_depth_embed over a chunk of pairs addressed by pair index -- rows [4 i, 4 i + 4) from codes_top[pair0 + i], i < pairs (codes_top [B n])
 hipError_t launch_score_depth_embed(const int64_t* codes_top, int pair0, int pairs, const float* tok, const float* pos, float* x, int D, bf16_t* xpk,
@@ -139,6 +144,7 @@ struct AttnArgs {
     int dtype;                   // DT_* of q / cache / out
     int out_packed_mb;           // > 0: write out in the packed_off() layout
     long long* dbg;              // tools/micro only: per-wave clock stamps (NULL in the product)
+    const int* row_pos;          // rolling pass, Tq == 1 (attention_kernel / attention_heads8_kernel): sample b has row_live(row_pos, b) keys cached in place of *t_base_dev
 };
 // Which kernel of attention.hip serves a call: the one choice, read by launch_attention (which switches on it) and by the timing report
 // ("variant:attn_<name>:<body|depth>", counted in run_block).  ATTN_INVALID: a head size no kernel takes.
@@ -184,6 +190,9 @@ struct SamplerArgs {
     // ---- kept positions (hqt_set_keep_mask): where keep[b * n_steps + step] != 0 the draw is spent and discarded -- `out` already holds the kept code, which is
     //      left in place and is what the fused embedding looks up.  NULL: every position is drawn.
     const unsigned char* keep;   // [B, n_steps], device
+    // ---- rolling pass (hqt_set_row_positions): row b draws position row_live(row_pos, b) in place of state->step -- the Philox position, the slice of `noise`, the
+    //      indices into out / logits_out / the log-probabilities --, and an idle row (row_pos[b] < 0) spends its draw without writing any of them.  NULL: the step state.
+    const int* row_pos;          // [B], device
 };
 // Uniform call: one launch.  With a row table in a FAST pass whose vocabulary the register-resident kernel takes: that kernel, then the general one, each over
 // every row -- which rows are in which class is read on the device, so the launch sequence does not depend on the table's values.
@@ -204,17 +213,19 @@ hipError_t launch_guide_logits(float* logits, const GuidePair* pairs, int n_pair
 // the 'reduce' table, child (H2 W2) takes its D-slice of the parent's row
 hipError_t launch_depth_embed_l2(const int64_t* codes0, const int64_t* codes1, int n_steps, const StepState* state, const float* tok0,
                                  const float* tok1, const float* pos, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts,
-                                 hipStream_t st, int V = 0, int tok1_ld = 0);
+                                 hipStream_t st, int V = 0, int tok1_ld = 0, const int* row_pos = nullptr);
 // hqt_score: launch_depth_embed_l2 over a chunk of pairs -- rows [16 i, 16 i + 16) from codes0[pair0 + i] and codes1[(pair0 + i) * 4 ..]
 hipError_t launch_score_depth_embed_l2(const int64_t* codes0, const int64_t* codes1, int pair0, int pairs, const float* tok0, const float* tok1, const float* pos,
                                        float* x, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V = 0, int tok1_ld = 0);
 // 'top2mid2bot' head (hqtransformer.py:700-735): input of causal sub-step cnt >= 1 = tok[codes[(b * n_steps + step) * stride + slot]] + pos_row
 hipError_t launch_depth_embed_causal(const int64_t* codes, int stride, int slot, int n_steps, const StepState* state, const float* tok,
-                                     const float* pos_row, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V);
+                                     const float* pos_row, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V, const int* row_pos = nullptr);
 // raises the dynamic-LDS limit of the sampler for (V, top-p) outside any stream capture
 hipError_t sampler_configure(int V, bool use_top_p);
 
 hipError_t launch_advance_step(StepState* state, int d_tbase, hipStream_t st);
+// rolling pass: row_pos[b] += 1 for every live row (>= 0) of the B; a row that reaches n_steps turns idle (-1)
+hipError_t launch_advance_rows(int* row_pos, int B, int n_steps, hipStream_t st);
 hipError_t launch_set_step(StepState* state, int step, int t_base, hipStream_t st);
 // rows[b] = (seed, sample_offset + b) for b < B
 hipError_t launch_set_rows(RowKey* rows, int B, uint64_t seed, int64_t sample_offset, hipStream_t st);

@@ -61,6 +61,17 @@ hipError_t launch_advance_step(StepState* s, int d_tbase, hipStream_t st) {
     advance_step_kernel<<<1, 1, 0, st>>>(s, d_tbase);
     return hipGetLastError();
 }
+// Rolling pass, between two steps of a call: every live row moves on by one position; a row that has just drawn its last one (n_steps - 1) turns idle
+__global__ void advance_rows_kernel(int* row_pos, int B, int n_steps) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int p = row_pos[b];
+    if (p >= 0) row_pos[b] = p + 1 < n_steps ? p + 1 : -1;
+}
+hipError_t launch_advance_rows(int* row_pos, int B, int n_steps, hipStream_t st) {
+    advance_rows_kernel<<<(B + 255) / 256, 256, 0, st>>>(row_pos, B, n_steps);
+    return hipGetLastError();
+}
 hipError_t launch_set_step(StepState* s, int step, int t_base, hipStream_t st) {
     set_step_kernel<<<1, 1, 0, st>>>(s, step, t_base);
     return hipGetLastError();
@@ -115,7 +126,7 @@ __global__ __launch_bounds__(256) void embed_step_kernel(EmbedArgs a) {
     __shared__ float red[4];
     const int b = blockIdx.x;
     float* x = a.x + (long long)b * a.D;
-    embed_row(a, b, a.state->step, x);
+    embed_row(a, b, step_of(a.state, a.row_pos, b), x);
     if (a.xpk) { __syncthreads(); emit_packed_row(x, b, a.D, a.xpk, a.pk_mb, a.parts, red); }
 }
 hipError_t launch_embed_step(const EmbedArgs& a, hipStream_t st) {
@@ -319,6 +330,25 @@ hipError_t launch_copy_positions(const int64_t* src, int64_t* dst, int B, int n_
     return hipGetLastError();
 }
 
+// The per-row sibling (a rolling pass: hqt_set_row_positions): row b copies positions [pos[b] + lo, pos[b] + hi) clipped to [0, n_steps); a row with pos[b] < 0
+// (an empty slot) copies nothing.  `pos` is the table as the call received it (device, [B]).
+__global__ __launch_bounds__(256) void copy_row_positions_kernel(const int64_t* src, int64_t* dst, const int* pos, long long n, int span, int width, int n_steps, int lo) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long b = i / (span * width), r = i - b * (span * width);
+    const int p0 = pos[b];
+    const int p = p0 + lo + (int)(r / width);
+    if (p0 < 0 || p < 0 || p >= n_steps) return;
+    const long long at = (b * n_steps + p) * width + r % width;
+    dst[at] = src[at];
+}
+hipError_t launch_copy_row_positions(const int64_t* src, int64_t* dst, const int* pos, int B, int n_steps, int width, int lo, int hi, hipStream_t st) {
+    if (B < 1 || width < 1 || hi <= lo || !src || !dst || !pos) return hipErrorInvalidValue;
+    const long long n = (long long)B * (hi - lo) * width;
+    copy_row_positions_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(src, dst, pos, n, hi - lo, width, n_steps, lo);
+    return hipGetLastError();
+}
+
 // `tok_ld` = row length of the table: D, or 4 D for the 'reduce' head, where slot s of a code takes the D-slice s of its row
 // (hqtransformer.py:108-116,532-533)
 // depth_embed_row: output row `row` (slot row & 3 of its group), from the top code at index `at` of codes_top.  Shared by the decode step's kernel
@@ -333,10 +363,10 @@ __device__ __forceinline__ void depth_embed_row(const int64_t* codes_top, long l
 }
 __global__ __launch_bounds__(256) void depth_embed_kernel(const int64_t* codes_top, int n_steps, const StepState* state,
                                                           const float* tok, const float* pos, float* x, int D, bf16_t* xpk,
-                                                          int pk_mb, float* parts, int V, int tok_ld) {
+                                                          int pk_mb, float* parts, int V, int tok_ld, const int* row_pos) {
     __shared__ float red[4];
     const int row = blockIdx.x, b = row >> 2;
-    depth_embed_row(codes_top, (long long)b * n_steps + state->step, row, tok, pos, x, D, xpk, pk_mb, parts, V, tok_ld, red);
+    depth_embed_row(codes_top, (long long)b * n_steps + step_of(state, row_pos, b), row, tok, pos, x, D, xpk, pk_mb, parts, V, tok_ld, red);
 }
 // hqt_score: the rows of a chunk of pairs, pair pair0 + (row >> 2) -- codes_top is [B n] there, indexed by the pair
 __global__ __launch_bounds__(256) void score_depth_embed_kernel(const int64_t* codes_top, int pair0, const float* tok, const float* pos, float* x, int D,
@@ -352,8 +382,8 @@ hipError_t launch_score_depth_embed(const int64_t* codes_top, int pair0, int pai
     return hipGetLastError();
 }
 hipError_t launch_depth_embed(const int64_t* codes_top, int n_steps, const StepState* state, const float* tok,
-                              const float* pos, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V, int tok_ld) {
-    depth_embed_kernel<<<B * 4, 256, 0, st>>>(codes_top, n_steps, state, tok, pos, x, D, xpk, pk_mb, parts, V, tok_ld > 0 ? tok_ld : D);
+                              const float* pos, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V, int tok_ld, const int* row_pos) {
+    depth_embed_kernel<<<B * 4, 256, 0, st>>>(codes_top, n_steps, state, tok, pos, x, D, xpk, pk_mb, parts, V, tok_ld > 0 ? tok_ld : D, row_pos);
     return hipGetLastError();
 }
 
@@ -377,10 +407,10 @@ __device__ __forceinline__ void depth_embed_l2_row(const int64_t* codes0, const 
 }
 __global__ __launch_bounds__(256) void depth_embed_l2_kernel(const int64_t* codes0, const int64_t* codes1, int n_steps, const StepState* state,
                                                              const float* tok0, const float* tok1, const float* pos, float* x, int D,
-                                                             bf16_t* xpk, int pk_mb, float* parts, int V, int tok1_ld) {
+                                                             bf16_t* xpk, int pk_mb, float* parts, int V, int tok1_ld, const int* row_pos) {
     __shared__ float red[4];
     const int row = blockIdx.x, b = row >> 4;
-    depth_embed_l2_row(codes0, codes1, (long long)b * n_steps + state->step, row, tok0, tok1, pos, x, D, xpk, pk_mb, parts, V, tok1_ld, red);
+    depth_embed_l2_row(codes0, codes1, (long long)b * n_steps + step_of(state, row_pos, b), row, tok0, tok1, pos, x, D, xpk, pk_mb, parts, V, tok1_ld, red);
 }
 __global__ __launch_bounds__(256) void score_depth_embed_l2_kernel(const int64_t* codes0, const int64_t* codes1, int pair0, const float* tok0, const float* tok1,
                                                                    const float* pos, float* x, int D, bf16_t* xpk, int pk_mb, float* parts, int V, int tok1_ld) {
@@ -396,23 +426,23 @@ hipError_t launch_score_depth_embed_l2(const int64_t* codes0, const int64_t* cod
 }
 hipError_t launch_depth_embed_l2(const int64_t* codes0, const int64_t* codes1, int n_steps, const StepState* state, const float* tok0,
                                  const float* tok1, const float* pos, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts,
-                                 hipStream_t st, int V, int tok1_ld) {
-    depth_embed_l2_kernel<<<B * 16, 256, 0, st>>>(codes0, codes1, n_steps, state, tok0, tok1, pos, x, D, xpk, pk_mb, parts, V, tok1_ld > 0 ? tok1_ld : D);
+                                 hipStream_t st, int V, int tok1_ld, const int* row_pos) {
+    depth_embed_l2_kernel<<<B * 16, 256, 0, st>>>(codes0, codes1, n_steps, state, tok0, tok1, pos, x, D, xpk, pk_mb, parts, V, tok1_ld > 0 ? tok1_ld : D, row_pos);
     return hipGetLastError();
 }
 
 __global__ __launch_bounds__(256) void depth_embed_causal_kernel(const int64_t* codes, int stride, int slot, int n_steps, const StepState* state,
                                                                  const float* tok, const float* pos_row, float* x, int D, bf16_t* xpk,
-                                                                 int pk_mb, float* parts, int V) {
+                                                                 int pk_mb, float* parts, int V, const int* row_pos) {
     __shared__ float red[4];
     const int b = blockIdx.x;
-    const long long code = clamp_idx(codes[((long long)b * n_steps + state->step) * stride + slot], V);
+    const long long code = clamp_idx(codes[((long long)b * n_steps + step_of(state, row_pos, b)) * stride + slot], V);
     for (int d = threadIdx.x; d < D; d += blockDim.x) x[(long long)b * D + d] = tok[code * D + d] + pos_row[d];
     if (xpk) { __syncthreads(); emit_packed_row(x + (long long)b * D, b, D, xpk, pk_mb, parts, red); }
 }
 hipError_t launch_depth_embed_causal(const int64_t* codes, int stride, int slot, int n_steps, const StepState* state, const float* tok,
-                                     const float* pos_row, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V) {
-    depth_embed_causal_kernel<<<B, 256, 0, st>>>(codes, stride, slot, n_steps, state, tok, pos_row, x, D, xpk, pk_mb, parts, V);
+                                     const float* pos_row, float* x, int B, int D, bf16_t* xpk, int pk_mb, float* parts, hipStream_t st, int V, const int* row_pos) {
+    depth_embed_causal_kernel<<<B, 256, 0, st>>>(codes, stride, slot, n_steps, state, tok, pos_row, x, D, xpk, pk_mb, parts, V, row_pos);
     return hipGetLastError();
 }
 
@@ -647,7 +677,8 @@ __global__ __launch_bounds__(NT, 8) void sampler_kernel(SamplerArgs a, int n2) {
         temperature = rs.temperature[a.row_lv_t]; top_k = rs.top_k[a.row_lv_k]; top_p = rs.top_p[a.row_lv_k];
         if (a.row_dispatch && sampler_row_plain(top_k, top_p, V)) return;
     }
-    const int step = a.state->step;
+    const int step = step_of(a.state, a.row_pos, b);
+    const bool idle = row_idle(a.row_pos, b);        // rolling pass: the row computes (as at position 0) and writes nothing the caller can see
     const int draw = a.draw0 + slot;
     const float* lg = a.logits + (long long)r * V;
     const int draws = a.draws > 0 ? a.draws : 5;
@@ -657,7 +688,7 @@ __global__ __launch_bounds__(NT, 8) void sampler_kernel(SamplerArgs a, int n2) {
     const float inv_t = FM ? __builtin_amdgcn_rcpf(temperature) : 0.0f;
     for (int i = tid; i < V; i += NT) {
         const float v = lg[i];
-        if (a.logits_out) a.logits_out[nidx + i] = v;
+        if (a.logits_out && !idle) a.logits_out[nidx + i] = v;
         lp[i] = FM ? v * inv_t : v / temperature;
     }
     __syncthreads();
@@ -892,7 +923,8 @@ __global__ __launch_bounds__(NT, 8) void sampler_kernel(SamplerArgs a, int n2) {
         for (int w = 1; w < NT / 64; ++w)
             if (redf[w] > best || (redf[w] == best && redi[w] < besti)) { best = redf[w]; besti = redi[w]; }
         int64_t* const dst = a.out + (a.out_stride > 0 ? ((long long)b * a.n_steps + step) * a.out_stride + a.out_slot : ((long long)b * a.n_steps + step) * a.slots + slot);
-        if (a.keep && a.keep[(long long)b * a.n_steps + step]) besti = (int)*dst;      // a kept position: the draw is discarded, the code (clamped when it was stored) stays
+        if (idle) {}                                     // an idle row: the draw is discarded and `out` is left alone (the fused embedding below takes the discarded code: any code in range)
+        else if (a.keep && a.keep[(long long)b * a.n_steps + step]) besti = (int)*dst;      // a kept position: the draw is discarded, the code (clamped when it was stored) stays
         else *dst = (int64_t)besti;
         if (a.emb_tok) sel[0] = a.emb_feed ? (int)clamp_idx(a.emb_feed[((long long)b * a.n_steps + step) * a.slots + slot], a.V) : besti;
     }
@@ -949,7 +981,8 @@ __global__ __launch_bounds__(256) void sampler_plain_fast_kernel(SamplerArgs a) 
         temperature = rs.temperature[a.row_lv_t];
         if (!sampler_row_plain(rs.top_k[a.row_lv_k], rs.top_p[a.row_lv_k], V)) return;      // workgroup-uniform
     }
-    const int step = a.state->step;
+    const int step = step_of(a.state, a.row_pos, b);
+    const bool idle = row_idle(a.row_pos, b);        // rolling pass: the row computes (as at position 0) and writes nothing the caller can see
     const int draw = a.draw0 + slot;
     const float* lg = a.logits + (long long)r * V;
     const int draws = a.draws > 0 ? a.draws : 5;
@@ -962,7 +995,7 @@ __global__ __launch_bounds__(256) void sampler_plain_fast_kernel(SamplerArgs a) 
         const int i4 = tid + 256 * k;
         if (i4 * 4 < V) {                                 // V % 4 == 0
             v[k] = *reinterpret_cast<const float4*>(lg + i4 * 4);
-            if (a.logits_out) *reinterpret_cast<float4*>(a.logits_out + nidx + i4 * 4) = v[k];
+            if (a.logits_out && !idle) *reinterpret_cast<float4*>(a.logits_out + nidx + i4 * 4) = v[k];
             v[k].x *= inv_t; v[k].y *= inv_t; v[k].z *= inv_t; v[k].w *= inv_t;
             m = fmaxf(fmaxf(m, fmaxf(v[k].x, v[k].y)), fmaxf(v[k].z, v[k].w));
         }
@@ -1012,7 +1045,8 @@ __global__ __launch_bounds__(256) void sampler_plain_fast_kernel(SamplerArgs a) 
         for (int w = 1; w < 4; ++w)
             if (redf[w] > best || (redf[w] == best && redi[w] < besti)) { best = redf[w]; besti = redi[w]; }
         int64_t* const dst = a.out + (a.out_stride > 0 ? ((long long)b * a.n_steps + step) * a.out_stride + a.out_slot : ((long long)b * a.n_steps + step) * a.slots + slot);
-        if (a.keep && a.keep[(long long)b * a.n_steps + step]) besti = (int)*dst;      // a kept position: the draw is discarded, the code (clamped when it was stored) stays
+        if (idle) {}                                     // an idle row: the draw is discarded and `out` is left alone (the fused embedding below takes the discarded code: any code in range)
+        else if (a.keep && a.keep[(long long)b * a.n_steps + step]) besti = (int)*dst;      // a kept position: the draw is discarded, the code (clamped when it was stored) stays
         else *dst = (int64_t)besti;
         if (a.emb_tok) redi[0] = a.emb_feed ? (int)clamp_idx(a.emb_feed[((long long)b * a.n_steps + step) * a.slots + slot], a.V) : besti;
     }
@@ -1159,7 +1193,8 @@ template <int G4>
 __global__ __launch_bounds__(256) void code_logprob_kernel(SamplerArgs a, const int64_t* feed, float* logprob, int slot) {
     const int V = a.V;
     const int b = blockIdx.x, r = b * a.slots + slot;
-    const int step = a.state->step;
+    if (row_idle(a.row_pos, b)) return;                  // workgroup-uniform: an idle row of a rolling pass has no entry
+    const int step = step_of(a.state, a.row_pos, b);
     const int draw = a.draw0 + slot;
     const int draws = a.draws > 0 ? a.draws : 5;
     const long long pos = (long long)b * a.n_steps + step;

@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256, NSTAGE == 2 ? 2 : 1) void conv_glds_kernel(Gem
                     // fused [query; key; value] with the KV-cache row remap: the 4 columns lie in one part
                     const int part = n4 / g.qkv_D, nn = n4 - part * g.qkv_D, which = part + g.qkv_first;
                     long long row = m;
-                    if (which > 0) row = (m / g.rows_per_group) * g.group_stride + m % g.rows_per_group + g.row_offset + qkv_dev;
+                    if (which > 0) row = (m / g.rows_per_group) * g.group_stride + m % g.rows_per_group + g.row_offset + qkv_row_of(g, m / g.rows_per_group, qkv_dev);
                     TC* base = reinterpret_cast<TC*>(which == 0 ? g.C : (which == 1 ? g.C2 : g.C3));
                     st4<TC>(base + row * g.ldc + nn, v);
                 } else if (MODE == 2) {

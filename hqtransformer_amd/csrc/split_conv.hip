@@ -691,7 +691,7 @@ __global__ __launch_bounds__(256, 2) void split_gemm_kernel(GemmArgs g, int a_lo
                 f32x4 v = *reinterpret_cast<const f32x4*>(stg + r * PITCH + cg);
                 if (Rb) v += x0[p];
                 long long orow = m;
-                if (remap) orow = (long long)(m / g.rows_per_group) * g.group_stride + m % g.rows_per_group + g.row_offset + qkv_row_dev;
+                if (remap) orow = (long long)(m / g.rows_per_group) * g.group_stride + m % g.rows_per_group + g.row_offset + qkv_row_of(g, min(m, g.M - 1) / g.rows_per_group, qkv_row_dev);      // (a padded row is not stored)
                 if (m < g.M && col_ok) *reinterpret_cast<f32x4*>(Cw + orow * ldc + ccol0 + cg) = v;
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");

@@ -518,7 +518,7 @@ __global__ __launch_bounds__(G::NW * 64, (G::NW / 4) * G::WG_PER_CU) void tile_g
                 if (m >= g.M) continue;
                 if (MODE == TS_QKV) {
                     long long row = m;
-                    if (qkv_part > 0) row = (long long)(m / g.rows_per_group) * g.group_stride + m % g.rows_per_group + g.row_offset + qkv_row_dev;
+                    if (qkv_part > 0) row = (long long)(m / g.rows_per_group) * g.group_stride + m % g.rows_per_group + g.row_offset + qkv_row_of(g, m / g.rows_per_group, qkv_row_dev);
                     const long long eoff = row * g.ldc + (wcol0 + cg - qkv_part_local * g.qkv_D);      // elements from the (wave-uniform) base of this part
                     // WRITE-THROUGH (sc1): a launch whose output stays dirty in L2 ends with the write-back of all of it at once; the attention kernel that reads
                     // these rows runs on other CUs anyway (round 6 A/B, same box, AR pass at 640 rows: qkv 22.6 -> 22.1 ms per pass; fp32 rows, slabs and residual

@@ -255,6 +255,32 @@ def check_segment(n_steps: int, segment, prefix=None, keep=None, prompt_groups=N
     return start, stop
 
 
+def check_row_positions(cond_type: int, batch: int, n_steps: int, row_positions, prefix=None, keep=None, prompt_groups=None, segment=None):
+    """A rolling call (``hqt_set_row_positions``) checked on the host, before any engine is touched: ``row_positions = (pos, k)`` with ``pos`` one integer per row of
+    the batch in [-1, n_steps - 1] (-1: an empty slot) and 1 <= k <= n_steps; not on a text-conditional model (a joining row needs a prompt prefill: not built) and
+    not together with ``prefix``, ``keep``, ``prompt_groups`` or ``segment``.  Returns (pos as a contiguous int32 numpy array, k); None stays None."""
+    if row_positions is None:
+        return None
+    if not isinstance(row_positions, (list, tuple)) or len(row_positions) != 2:
+        raise ValueError('row_positions: expected (pos, k)')
+    if int(cond_type) == 2:
+        raise ValueError('row_positions: a rolling pass on a text-conditional model is not built (a row that joins at position 0 needs a prompt prefill of its own)')
+    for other, what in ((prefix, 'prefix'), (keep, 'keep'), (prompt_groups, 'prompt_groups'), (segment, 'segment')):
+        if other is not None:
+            raise ValueError(f'row_positions together with {what} is not built')
+    pos, k = row_positions
+    p = torch.as_tensor(pos).cpu()
+    if p.dtype.is_floating_point or p.dtype == torch.bool or p.dim() != 1 or p.numel() != int(batch):
+        raise ValueError(f'row_positions: pos holds one integer per row of the batch ({int(batch)}), got {p.dtype} of shape {tuple(p.shape)}')
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= int(n_steps):
+        raise ValueError(f'row_positions: k={k!r} outside [1, n_steps = {int(n_steps)}]')
+    p = np.ascontiguousarray(p.numpy().astype(np.int32))
+    bad = np.nonzero((p < -1) | (p > int(n_steps) - 1))[0]
+    if bad.size:
+        raise ValueError(f'row_positions: pos[{int(bad[0])}]={int(p[bad[0]])} outside [-1, n_steps - 1 = {int(n_steps) - 1}] (-1: an empty slot)')
+    return p, int(k)
+
+
 def check_select_rows(rows_from, paused_batch: Optional[int], max_batch: int) -> np.ndarray:
     """A row mapping for ``Engine.select_rows`` (``hqt_select_rows``) checked on the host: integers, one dimension, 1 <= B_new <= ``max_batch`` entries, each in
     [0, ``paused_batch``) -- the rows of the paused pass; None: unknown to the caller, the library checks the entries.  Any mapping: the identity, a permutation, a
@@ -509,11 +535,14 @@ class Engine:
                        row_seeds, row_offsets, row_samplers=None, prefix=None,
                        return_logprobs=False, guidance=None, keep=None,
                        prompt_groups=None, segment=None, logits_out=None,
-                       logprobs_out=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+                       logprobs_out=None, row_positions=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
         """Returns (codes [B, n], [B, n, 4][, [B, n, 16]], logits [n, draws, B, V] or None, logprobs [B, n, draws] or None)."""
         dev = self.device
         B, V, L = int(batch), self.s2.vocab_top, int(levels)
         segment = check_segment(n_steps, segment, prefix, keep, prompt_groups)
+        roll = check_row_positions(self.s2.cond, B, n_steps, row_positions, prefix, keep, prompt_groups, segment)
+        if roll is not None and out is None:
+            raise ValueError('row_positions: a rolling call writes the positions its rows draw into out (and reads the codes in front of them there) -- pass the tensors the pass lives in')
         if segment is not None and segment[0] > 0 and out is None:
             raise ValueError(f'segment={segment}: a continuation reads the codes of position {segment[0] - 1} from out -- pass the tensors the earlier segments wrote')
         groups = None if prompt_groups is None else check_prompt_groups(self.s2, B, cond, prompt_groups, self.max_batch, prefix, keep)
@@ -602,6 +631,8 @@ class Engine:
                 _lib.check(self.lib.hqt_set_prompt_groups(self.h, B, groups[1], groups[0].ctypes.data_as(C.c_void_p)))
             if segment is not None:                 # ... and the segment
                 _lib.check(self.lib.hqt_set_segment(self.h, segment[0], segment[1]))
+            if roll is not None:                    # ... and the positions of a rolling pass (copied)
+                _lib.check(self.lib.hqt_set_row_positions(self.h, B, roll[0].ctypes.data_as(C.c_void_p), roll[1]))
             _lib.check(fn(self.h, B, _ptr(cond), C.byref(o), _ptr(noise), *map(_ptr, force), _ptr(logits), *map(_ptr, outs), C.c_void_p(stream)))
             self._note_split(precision, stream, ar_rows=B)        # every head runs persistently (run_position)
         # inputs must outlive the asynchronous launches
@@ -619,7 +650,7 @@ class Engine:
                row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
                return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None, keep: Optional[tuple] = None,
                prompt_groups=None, segment: Optional[Tuple[int, int]] = None, logits_out: Optional[torch.Tensor] = None,
-               logprobs_out: Optional[torch.Tensor] = None):
+               logprobs_out: Optional[torch.Tensor] = None, row_positions: Optional[tuple] = None):
         """Two-level sampling: returns (codes_top [B, n], codes_bot [B, n, 4][, logits [n, 5, B, V]][, logprobs [B, n, 5]]).
         ``return_logprobs``: fp32 log-probability of every code the call feeds forward -- the drawn one, or the forced one where ``force_*`` is
         given -- under the raw logits of its draw (T = 1, no cut-off: ``hqt_set_logprob_out``), appended last; with a prefix the positions < P are NaN.
@@ -651,14 +682,21 @@ class Engine:
         ``start``: HqtError otherwise) and needs ``out`` -- the tensors the earlier segments wrote, edited or gathered as the caller sees fit.  Samplers, row tables,
         guidance and keys may differ from segment to segment; all segments together return bit for bit what one call returns.  ``logits_out`` [n, 5, B, V] /
         ``logprobs_out`` [B, n, 5]: caller-owned buffers the call writes (and returns) in place of fresh ones, so that a segmented pass fills one tensor.  Not
-        together with ``prefix`` or ``keep``; ``prompt_groups`` with start == 0 only."""
+        together with ``prefix`` or ``keep``; ``prompt_groups`` with start == 0 only.
+        ``row_positions`` = (pos, k): a ROLLING call (``hqt_set_row_positions``) -- the ``batch`` rows are slots, ``pos[b]`` the position slot b draws next (-1: empty); the
+        call runs k steps, in step j every row with pos[b] + j < n_steps draws position pos[b] + j as a plain call draws it given that row's earlier codes.  Needs ``out``
+        (the tensors the pass lives in: the positions drawn are written there, the codes of pos[b] - 1 read from there); ``logits_out`` / ``logprobs_out`` are filled
+        the same way, and nothing of an idle row is written.  A slot continues exactly where the engine's rolling pass left it, joins at 0 or is empty (HqtError
+        otherwise); ``cond[b]`` is read where a row stands at 0, ``row_seeds`` / ``row_offsets`` / ``row_samplers`` give each slot its request's key and settings.
+        Not on text models, not together with ``prefix``, ``keep``, ``prompt_groups`` or ``segment``."""
         if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
             raise ValueError('out: expected a pair (codes_top [B, n_steps], codes_bot [B, n_steps, 4])')
         outs, logits, logprobs = self._sample_levels(2, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(force_top, force_bot), out=out,
                                            return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
                                            row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance, keep=keep,
-                                           prompt_groups=prompt_groups, segment=segment, logits_out=logits_out, logprobs_out=logprobs_out)
+                                           prompt_groups=prompt_groups, segment=segment, logits_out=logits_out, logprobs_out=logprobs_out,
+                                           row_positions=row_positions)
         return ((outs[0], outs[1]) + ((logits,) if return_logits or logits_out is not None else ())
                 + ((logprobs,) if return_logprobs or logprobs_out is not None else ()))
 
@@ -670,19 +708,21 @@ class Engine:
                 row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
                 return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None, keep: Optional[tuple] = None,
                 prompt_groups=None, segment: Optional[Tuple[int, int]] = None, out: Optional[Sequence[torch.Tensor]] = None,
-                logits_out: Optional[torch.Tensor] = None, logprobs_out: Optional[torch.Tensor] = None):
+                logits_out: Optional[torch.Tensor] = None, logprobs_out: Optional[torch.Tensor] = None, row_positions: Optional[tuple] = None):
         """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]][, logprobs [B, n, 21]]); ``row_samplers``,
         ``return_logprobs`` and ``guidance`` (three scales per pair) as in ``sample``;
         ``prefix`` = [[B, P], [B, P, 4], [B, P, 16]]: completion, as in ``sample`` (``hqt_sample_prefix_l3``);
         ``keep`` = (mask [B, n], [[B, n], [B, n, 4], [B, n, 16]]): kept positions, as in ``sample``; ``prompt_groups``: shared prompts, as in ``sample``;
-        ``segment`` / ``logits_out`` / ``logprobs_out``: a segment of a pass, as in ``sample``; ``out`` = the three code tensors to write into, as ``sample`` takes two."""
+        ``segment`` / ``logits_out`` / ``logprobs_out``: a segment of a pass, as in ``sample``; ``out`` = the three code tensors to write into, as ``sample`` takes two;
+        ``row_positions`` = (pos, k): a rolling call, as in ``sample``."""
         if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 3):
             raise ValueError('out: expected the three code tensors ([B, n_steps], [B, n_steps, 4], [B, n_steps, 16])')
         outs, logits, logprobs = self._sample_levels(3, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
                                            noise=noise, seed=seed, sample_offset=sample_offset, force=(None,) * 3 if force is None else force,
                                            out=out, return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
                                            row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance, keep=keep,
-                                           prompt_groups=prompt_groups, segment=segment, logits_out=logits_out, logprobs_out=logprobs_out)
+                                           prompt_groups=prompt_groups, segment=segment, logits_out=logits_out, logprobs_out=logprobs_out,
+                                           row_positions=row_positions)
         return (tuple(outs) + ((logits,) if return_logits or logits_out is not None else ())
                 + ((logprobs,) if return_logprobs or logprobs_out is not None else ()))
 

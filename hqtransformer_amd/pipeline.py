@@ -308,6 +308,103 @@ class SamplingSession:
         return self.codes
 
 
+class RollingSampler:
+    """A rolling pass (``hqt_set_row_positions``): ``slots`` rows in which every request stands at its own position.  ``submit`` queues one request (one image:
+    its class id -- None for an unconditional model --, its Philox seed and global row offset, its own sampler keywords), ``step`` admits queued requests into
+    free slots at position 0 while their neighbours are mid-image, runs ONE engine call of ``k`` steps over all slots, and returns the requests that drew their
+    last position in it; ``drain`` steps until nothing is queued or live.  A request draws bit for bit what the plain call of the same batch draws for it in its
+    slot -- in EXACT arithmetic, where a row's draws do not depend on the pass it sits in, what ``sampling_ihqgpt(stage2, 1, cond, max_seq_len=n, seed=seed)`` draws.
+    The sampler holds the slot bookkeeping on the host (free list, positions, keys, conditions, the row-sampler table) and the code tensors of the pass on the
+    device; one rolling pass at a time per engine lane (any other sampling or scoring call on the lane ends it, and the next ``step`` raises ``HqtError``).
+    Text models are refused: a row that joins at position 0 would need a prompt prefill of its own, which is not built."""
+
+    def __init__(self, stage2, slots: int, n: int, *, precision: Optional[str] = None, use_fp16: bool = True, use_graph: bool = True, lane: int = 0,
+                 return_logprobs: bool = False):
+        if stage2.use_txt_cond:
+            raise ValueError('RollingSampler: a rolling pass on a text-conditional model is not built (a row that joins at position 0 needs a prompt prefill of its own)')
+        self.stage2, self.L, self.slots, self.n = stage2, int(stage2.spec.levels), int(slots), int(n)
+        if self.slots < 1:
+            raise ValueError(f'slots={self.slots}: a rolling pass needs at least one slot')
+        if not 1 <= self.n <= stage2.spec.ctx_len_img:
+            raise ValueError(f'n={self.n} outside [1, ctx_len_img={stage2.spec.ctx_len_img}]')
+        self.precision, self.use_graph = _precision(precision, use_fp16), bool(use_graph)
+        self.engine = stage2.engine(self.slots, self.n, lane)
+        dev = self.engine.device
+        self.codes = [torch.full((self.slots, self.n) + ((4 ** l,) if l else ()), -1, dtype=torch.int64, device=dev) for l in range(self.L)]
+        self.logprobs = torch.full((self.slots, self.n, (4 ** self.L - 1) // 3), float('nan'), dtype=torch.float32, device=dev) if return_logprobs else None
+        self.class_cond = bool(stage2.spec.cond == 1)
+        default = step_row_samplers(self.L, [1], [{}])[0]
+        # per slot: the position it draws next (-1: empty), its request's ticket, condition, key and sampler settings
+        self.pos, self.ticket = [-1] * self.slots, [None] * self.slots
+        self.cond, self.row_seeds, self.row_offsets = [0] * self.slots, [0] * self.slots, [0] * self.slots
+        self.row_samplers = [default] * self.slots
+        self.free = list(range(self.slots))          # ascending: a request joins in the lowest free slot
+        self.queue: list = []
+        self.tickets = 0
+
+    @property
+    def live(self) -> int:
+        return sum(p >= 0 for p in self.pos)
+
+    def submit(self, cond, seed: int, sample_offset: int = 0, **sampler) -> int:
+        """Queues one request and returns its ticket.  ``sampler``: the sampler keywords of ``sampling_ihqgpt`` / ``sampling_hqtransformer``; they travel as the
+        ``row_samplers`` entry of the slot the request is admitted to."""
+        unknown = set(sampler) - set(SAMPLER_KEYS)
+        if unknown:
+            raise TypeError(f'submit: unexpected keywords {sorted(unknown)} (sampler settings travel here)')
+        if self.class_cond:
+            if cond is None or isinstance(cond, bool) or not 0 <= int(cond) < self.stage2.spec.n_classes:
+                raise ValueError(f'cond={cond!r}: a class id in [0, {self.stage2.spec.n_classes}) is required')
+            cond = int(cond)
+        elif cond is not None:
+            raise ValueError('cond: an unconditional model takes None')
+        entry = step_row_samplers(self.L, [1], [sampler])[0]
+        ticket, self.tickets = self.tickets, self.tickets + 1
+        self.queue.append((ticket, cond or 0, int(seed), int(sample_offset), entry))
+        return ticket
+
+    def step(self, k: int = 1) -> list:
+        """Admits queued requests into free slots (in submission order, lowest free slot first), runs one rolling call of ``k`` steps and returns the requests
+        that finished in it as ``(ticket, codes[, logprobs])``: ``codes`` the levels as one list, [n], [n, 4][, [n, 16]], gathered on the device.  A slot freed
+        in this call takes a new request in the next one.  Nothing queued or live: no engine call, []."""
+        k = int(k)
+        if not 1 <= k <= self.n:
+            raise ValueError(f'step(k={k}): expected 1 <= k <= n = {self.n}')
+        while self.queue and self.free:
+            slot = self.free.pop(0)
+            self.ticket[slot], self.cond[slot], self.row_seeds[slot], self.row_offsets[slot], self.row_samplers[slot] = self.queue.pop(0)
+            self.pos[slot] = 0
+        if not self.live:
+            return []
+        cond = torch.tensor(self.cond, dtype=torch.int64) if self.class_cond else None
+        common = dict(precision=self.precision, seed=0, use_graph=self.use_graph, row_seeds=list(self.row_seeds), row_offsets=list(self.row_offsets),
+                      row_samplers=list(self.row_samplers), out=self.codes, logprobs_out=self.logprobs, row_positions=(list(self.pos), k))
+        if self.L == 3:
+            self.engine.sample3(self.slots, cond, self.n, **common)
+        else:
+            self.engine.sample(self.slots, cond, self.n, **common)
+        done = [s for s in range(self.slots) if self.pos[s] >= 0 and self.pos[s] + k >= self.n]
+        self.pos = [-1 if p < 0 or p + k >= self.n else p + k for p in self.pos]
+        if not done:
+            return []
+        idx = torch.as_tensor(done, dtype=torch.int64, device=self.codes[0].device)
+        codes = [c.index_select(0, idx) for c in self.codes]
+        logprobs = self.logprobs.index_select(0, idx) if self.logprobs is not None else None
+        out = []
+        for i, s in enumerate(done):
+            out.append((self.ticket[s], [c[i] for c in codes]) + ((logprobs[i],) if logprobs is not None else ()))
+            self.ticket[s] = None
+        self.free = sorted(self.free + done)
+        return out
+
+    def drain(self, k: int = 1) -> list:
+        """Steps until nothing is queued or live; returns every request that finished on the way, in the order they finished."""
+        out = []
+        while self.queue or self.live:
+            out.extend(self.step(k))
+        return out
+
+
 def check_prune(prune, num_candidates: int, keep: int, n: int) -> list:
     """``prune`` of ``sample_best_of`` checked on the host, before any engine is built: a list ``[(position, survivors_per_group), ...]`` with positions
     ascending inside [1, n - 1] and survivors descending, below ``num_candidates`` and never below ``keep``.  Returns it as a list of int pairs."""

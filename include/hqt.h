@@ -310,7 +310,7 @@ int hqt_set_prompt_groups(hqt_handle* h, int B, int n_groups, const int32_t* gro
  * HQT_ERR_INVALID in the taking call, with a message naming the cause: stop <= start, start < 0 or stop > n_steps; a prefix entry point; a staged keep table;
  * a staged prompt-group table with start > 0.  The record of a paused pass is cleared by every other call that writes the body cache or the step state: a plain or
  * prefix sampling call, a segment with start == 0, hqt_score.  Without a staged segment a call launches exactly what it launched before.
- * Not built: segments together with keep tables or code prefixes; rows of one pass at different positions (a per-row t_base in every attention kernel).
+ * Not built: segments together with keep tables or code prefixes.  Rows of one pass at different positions: hqt_set_row_positions, below.
  *
  * hqt_select_rows -- re-maps the rows of the paused pass: afterwards cache row j of every body layer holds what row rows_from[j] held, for the live rows
  * 0 .. t_base - 1 (text models: the prompt rows and the drawn positions), K and V, in the cache's type for the paused precision; the paused B becomes B_new.
@@ -321,6 +321,34 @@ int hqt_set_prompt_groups(hqt_handle* h, int B, int n_groups, const int32_t* gro
  * B_new * 16 bytes beyond the 160 KiB of LDS of a compute unit (10240 rows). */
 int hqt_set_segment(hqt_handle* h, int start, int stop);
 int hqt_select_rows(hqt_handle* h, int B_new, const int32_t* rows_from, void* stream);
+
+/* hqt_set_row_positions -- no reference counterpart: the reference starts all rows of a batch together.  A ROLLING pass is a fixed number of slots (the B rows of
+ * a call) in which every row stands at its own position: a row that finishes frees its slot, a new request joins in a free slot at position 0 while its neighbours
+ * are mid-image, so the weights streamed for a position serve a full pass.  `pos` is a HOST array of B entries, copied before return (it travels through the pinned
+ * staging ring of the row tables): pos[b] is the position row b draws next, -1 an empty slot.  The table is STAGED on the handle (a lane from hqt_clone has its own):
+ * the next hqt_sample / hqt_sample_l3 on that handle takes it and clears it, whether that call succeeds or not; B == 0 or a NULL pos clears.
+ * The taking call, with n = opts->n_steps, runs k steps (1 <= k <= n).  In step j every row with pos[b] >= 0 and pos[b] + j < n draws position pos[b] + j exactly as
+ * a plain call draws it given that row's earlier codes: Philox keys by (seed, global row, ABSOLUTE position, draw, chunk), the same slice of `noise`, the same sampler
+ * settings and row tables; force_*, logits_out and a staged hqt_set_logprob_out buffer behave as in a plain call, all indexed by absolute position.  cond[b] is read
+ * where a row stands at position 0; row_seeds / row_offsets give each slot its request's key.  The codes of position pos[b] - 1 are read from the caller's out_* (a
+ * forced level: force_*), as a segment reads them.  Every depth head and every precision; a row's bits do not depend on where its neighbours stand.
+ * Idle rows -- empty slots, and rows that have drawn position n - 1 in an earlier step of the call -- still occupy rows of the GEMMs: they compute as a row at
+ * position 0 would, inside their own cache slot, and nothing the caller can see of them is written (out_*, logits_out, the log-probabilities).
+ * The handle records the ROLLING PASS: B, n, code levels, precision and per slot the next position; a slot whose row reached n becomes empty.  The taking call
+ * checks every slot against the record and fails with HQT_ERR_STATE naming the row (the record is kept) unless pos[b] is -1 (vacate, or stay empty), 0 (join: always
+ * allowed, the slot's old contents are dead) or exactly the recorded next position (continue); without a record every entry must be 0 or -1.  A B, n, level count or
+ * precision that differs from the record's is HQT_ERR_STATE.  The record is cleared by every other call that writes the body cache (a plain, prefix or segment
+ * sampling call, hqt_score), as the paused pass is; a rolling call clears a paused pass.  A pass whose slots are all empty is over (its record is dropped: the
+ * next rolling call begins a pass, with any B, n and precision).  A first call of empty slots only is legal and draws nothing.
+ * Rolling calls always take the launch chain (the persistent launch keeps one t_base for all its rows).  The positions live in device memory: only "rolling" and
+ * the steps per graph launch enter the graph key, calls that differ only in positions replay one graph.  Without a staged table a call launches exactly what it
+ * launched before.
+ * HQT_ERR_INVALID, with a message naming the cause: a NULL handle; B outside [1, max_batch] or different from the taking call's; k outside [1, n]; an entry outside
+ * [-1, n - 1]; a text-conditional handle (a joining row needs a prompt prefill: not built); a prefix entry point; a staged segment, keep table or prompt-group table;
+ * a hqt_set_guidance pair whose two rows stand at different positions or of which exactly one is empty.
+ * Not built: text-conditional rolling passes; rolling together with segments, keep tables or prefixes; hqt_select_rows on a rolling pass (HQT_ERR_STATE: slots are
+ * reused in place); a rolling form of the persistent launch. */
+int hqt_set_row_positions(hqt_handle* h, int B, const int32_t* pos, int k);
 
 /* hqt_sample -- replaces sampling_ihqgpt + iHQGPT.sampling_step (hqvae/utils/sampling.py:164-237,
  * hierarchical_ar.py:428-480, 482-563, 667-789) for a batch of B independent images.
