@@ -87,6 +87,13 @@ class hqt_guide_pair(C.Structure):
     _fields_ = [('pos_row', C.c_int32), ('neg_row', C.c_int32), ('scale', C.c_float * 3)]
 
 
+REPORT_MAX_TOP = 16
+
+
+class hqt_draw_report(C.Structure):
+    _fields_ = [('entropy', C.c_void_p), ('rank', C.c_void_p), ('top_n', C.c_int32), ('top_codes', C.c_void_p), ('top_logprobs', C.c_void_p)]
+
+
 class hqt_encode_out(C.Structure):
     _fields_ = [
         ('codes', C.c_void_p * 3), ('quant', C.c_void_p * 3), ('resid', C.c_void_p * 3),
@@ -107,6 +114,7 @@ SYMBOLS = {
     'hqt_set_switch': (C.c_int, [_VP, C.c_int, C.c_int]),
     'hqt_set_row_samplers': (C.c_int, [_VP, C.c_int, C.POINTER(hqt_row_sampler)]),
     'hqt_set_logprob_out': (C.c_int, [_VP, _F32P]),
+    'hqt_set_draw_report': (C.c_int, [_VP, C.POINTER(hqt_draw_report)]),
     'hqt_set_guidance': (C.c_int, [_VP, C.c_int, C.POINTER(hqt_guide_pair)]),
     'hqt_set_keep_mask': (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.POINTER(C.c_void_p)]),
     'hqt_set_prompt_groups': (C.c_int, [_VP, C.c_int, C.c_int, _VP]),

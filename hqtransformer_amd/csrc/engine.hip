@@ -160,6 +160,7 @@ struct hqt_handle {
     struct Staged {
         std::vector<hqt_row_sampler> row_set;     // hqt_set_row_samplers: host table
         float* logprob = nullptr;                 // hqt_set_logprob_out: device fp32 [B, n_steps, draws]
+        ReportOut report = {nullptr, nullptr, 0, nullptr, nullptr};   // hqt_set_draw_report: device buffers [B, n_steps, draws(, top_n)]; hqt_score takes it too
         std::vector<hqt_guide_pair> guide;        // hqt_set_guidance: host table
         std::vector<uint8_t> keep;                // hqt_set_keep_mask: host mask [keep_B, keep_n] and one device pointer per level
         int keep_B = 0, keep_n = 0;
@@ -1184,6 +1185,7 @@ struct SampleCtx {
     bool with_prefix = false;                    // the call came through a prefix entry point (prefix_len is then validated)
     float* logits_out;
     float* logprob_out = nullptr;                // hqt_set_logprob_out: [B, n_steps, draws], NULL: no code_logprob launches at all
+    ReportOut report = {nullptr, nullptr, 0, nullptr, nullptr};   // hqt_set_draw_report: nothing to write: no draw_report launches at all; with something, they take code_logprob's place
     const hqt_guide_pair* guide = nullptr;       // host table of n_guide pairs staged by hqt_set_guidance, NULL: no guide_logits launches at all
     int n_guide = 0;
     const uint8_t* keep = nullptr;               // host mask [B, n_steps] staged by hqt_set_keep_mask, NULL: every position is drawn (and nothing below is read)
@@ -1685,7 +1687,13 @@ static int run_depth_head(hqt_handle* h, const SampleCtx& c, int Tq_body, bool p
                 sa.emb_xpk = dln_next ? h->xdpk : nullptr; sa.emb_pk_mb = dln_next ? packed_mb(4 * B) : 0; sa.emb_parts = h->partsd;
             }
             HIPCHK(launch_sampler(sa, c.st));
-            if (c.logprob_out) {      // one launch per draw of this sub-step, each under the timing slot of its own: the sampler's scope ends with the sampler
+            if (c.report.any()) {     // one launch per draw writes the report and, where a buffer is staged too, the log-probability: no code_logprob launch then
+                t.next("draw_report");
+                for (int slot = 0; slot < s.Tq; ++slot) {
+                    if (slot) t.next("draw_report");
+                    HIPCHK(launch_draw_report(sa, c.feed[s.lv], c.logprob_out, c.report, slot, c.st));
+                }
+            } else if (c.logprob_out) {      // one launch per draw of this sub-step, each under the timing slot of its own: the sampler's scope ends with the sampler
                 t.next("code_logprob");
                 for (int slot = 0; slot < s.Tq; ++slot) {
                     if (slot) t.next("code_logprob");
@@ -1810,6 +1818,7 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     const hqt_handle::Staged s = h->take_staged();
     c.row_set = s.row_set.empty() ? nullptr : s.row_set.data();
     c.logprob_out = s.logprob;
+    c.report = s.report;
     c.guide = s.guide.empty() ? nullptr : s.guide.data();
     c.n_guide = (int)s.guide.size();
     c.keep = s.keep.empty() ? nullptr : s.keep.data();
@@ -1830,6 +1839,8 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     if (B < 1 || B > cf.max_batch) return fail(HQT_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cf.max_batch);
     if (c.n_steps < 1 || c.n_steps > cf.max_steps) return fail(HQT_ERR_INVALID, "n_steps=%d outside [1, %d]", c.n_steps, cf.max_steps);
     if (cf.cond_type != HQT_COND_NONE && !cond) return fail(HQT_ERR_INVALID, "cond is required for class/text conditioning");
+    if (c.report.top_n > cf.vocab_top)
+        return fail(HQT_ERR_INVALID, "hqt_set_draw_report staged top_n=%d, this model's vocabulary has %d codes", c.report.top_n, cf.vocab_top);
     if (c.seg) {
         if (c.start < 0 || c.stop <= c.start || c.stop > c.n_steps)
             return fail(HQT_ERR_INVALID, "hqt_set_segment staged [%d, %d): a segment needs 0 <= start < stop <= n_steps = %d", c.start, c.stop, c.n_steps);
@@ -2027,6 +2038,23 @@ static_assert(sizeof(hqt_row_sampler) == 36 && sizeof(RowSampler) == sizeof(hqt_
 extern "C" int hqt_set_logprob_out(hqt_handle* h, float* logprobs) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
     h->staged.logprob = logprobs;                // NULL clears; the shape [B, n_steps, draws] is the taking call's (the caller sizes the buffer for it)
+    return HQT_OK;
+}
+
+static_assert(sizeof(hqt_draw_report) == 40 && HQT_REPORT_MAX_TOP == 16, "hqt_draw_report: four pointers and top_n; the per-thread taken-mask of the kernel holds 64 bits");
+
+extern "C" int hqt_set_draw_report(hqt_handle* h, const hqt_draw_report* r) {
+    if (h) h->staged.report = {nullptr, nullptr, 0, nullptr, nullptr};     // r == NULL, nothing to write, or a struct that is refused: nothing stays staged
+    if (!r) return h ? HQT_OK : fail(HQT_ERR_INVALID, "null handle");
+    // (the struct first: what is wrong with it does not depend on the handle)
+    if (r->top_n < 0 || r->top_n > HQT_REPORT_MAX_TOP)
+        return fail(HQT_ERR_INVALID, "hqt_set_draw_report: top_n=%d outside [0, HQT_REPORT_MAX_TOP = %d]", r->top_n, HQT_REPORT_MAX_TOP);
+    if (r->top_n > 0 && !r->top_codes) return fail(HQT_ERR_INVALID, "hqt_set_draw_report: top_n=%d and top_codes is NULL", r->top_n);
+    if (r->top_n > 0 && !r->top_logprobs) return fail(HQT_ERR_INVALID, "hqt_set_draw_report: top_n=%d and top_logprobs is NULL", r->top_n);
+    if (r->top_n == 0 && r->top_codes) return fail(HQT_ERR_INVALID, "hqt_set_draw_report: top_codes is set and top_n is 0");
+    if (r->top_n == 0 && r->top_logprobs) return fail(HQT_ERR_INVALID, "hqt_set_draw_report: top_logprobs is set and top_n is 0");
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    h->staged.report = {r->entropy, r->rank, r->top_n, r->top_codes, r->top_logprobs};     // the shapes are the taking call's (the caller sizes the buffers for it)
     return HQT_OK;
 }
 
@@ -2238,6 +2266,7 @@ extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
     // a staged table or buffer belongs to a sampling call: it must not wait for a later one behind this call
     const bool staged = h->staged.holds_table();
+    const ReportOut report = h->staged.report;     // a staged draw report is this call's (hqt_set_draw_report); taken and cleared whatever becomes of the call
     h->clear_staged();
     if (staged) return fail(HQT_ERR_STATE, "hqt_score: a row-sampler table, guidance pair table, keep table, prompt-group table or log-probability buffer was staged on this handle "
                             "(hqt_set_row_samplers / hqt_set_guidance / hqt_set_logprob_out / hqt_set_keep_mask / hqt_set_prompt_groups): they belong to a sampling call and were cleared");
@@ -2255,6 +2284,8 @@ extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_
     if (B < 1 || B > cf.max_batch) return fail(HQT_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cf.max_batch);
     if (n < 1 || n > cf.max_steps) return fail(HQT_ERR_INVALID, "n=%d outside [1, %d]", n, cf.max_steps);
     if (cf.cond_type != HQT_COND_NONE && !cond) return fail(HQT_ERR_INVALID, "cond is required for class/text conditioning");
+    if (report.top_n > cf.vocab_top)
+        return fail(HQT_ERR_INVALID, "hqt_set_draw_report staged top_n=%d, this model's vocabulary has %d codes", report.top_n, cf.vocab_top);
     if (n - 1 > h->max_prefix)
         return fail(HQT_ERR_STATE, "hqt_score: n=%d positions need max_prefix >= %d, this handle has %d (hqt_set_max_prefix sizes the body workspace for the pass's rows)", n, n - 1, h->max_prefix);
     SampleCtx c{};
@@ -2343,6 +2374,10 @@ extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_
             {
                 Timed t(h, "score_logprob", c.st);
                 HIPCHK(launch_score_logprob(lg, feed[s.lv] + (size_t)p0 * s.Tq, logprobs + (size_t)p0 * draws, np, V, s.Tq, s.tbase, draws, c.st));
+            }
+            if (report.any()) {       // the chunk's (pair, slot) rows of this level in one launch, over the logits the log-probabilities were read from
+                Timed t(h, "draw_report", c.st);
+                HIPCHK(launch_score_report(lg, feed[s.lv] + (size_t)p0 * s.Tq, report, p0, np, V, s.Tq, s.tbase, draws, c.st));
             }
         }
     }
@@ -2487,6 +2522,9 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         key.push_back((uint64_t)c.n_guide);
         // a keep table: that there is one (the samplers' guard) and the length of its prefill (the positions the graph covers), never its values
         key.push_back(c.keep ? (uint64_t)c.prefix_len + 1 : 0);
+        // a draw report: its pointers and top_n (kernel arguments of the launches that take code_logprob's place)
+        for (const void* p : {(const void*)c.report.entropy, (const void*)c.report.rank, (const void*)c.report.top_codes, (const void*)c.report.top_logprobs}) key.push_back((uint64_t)p);
+        key.push_back((uint64_t)c.report.top_n);
         if (!h->graph_exec || key != h->graph_key) {
             if (h->graph_exec) {                         // rare (options or test-only buffers changed): drain before destroying
                 HIPCHK(hipStreamSynchronize(c.st));

@@ -204,6 +204,26 @@ hipError_t launch_code_logprob(const SamplerArgs& a, const int64_t* feed, float*
 // score_logprob_kernel (hqt_score): the value code_logprob_kernel defines, for ALL rows of a sub-step in one launch, one workgroup per (pair, slot): row
 // r = i * slots + slot of logits [pairs * slots, V] at codes[r] -> logprob[i * draws + draw0 + slot]; every pointer is at the chunk's first pair
 hipError_t launch_score_logprob(const float* logits, const int64_t* codes, float* logprob, int pairs, int V, int slots, int draw0, int draws, hipStream_t st);
+// Draw report (hqt_set_draw_report): what the distribution behind a draw looked like, one entry per (b, step, draw) laid out as the log-probabilities are --
+// e = (b * n_steps + step) * draws + draw0 + slot.  Over the same RAW row l, with the same m = max l and S = sum expf(l - m) as the log-probability (shared code):
+//   entropy[e]              = logf(S) - T / S, T = sum expf(l_i - m) (l_i - m), reduced in the order of S            (nats; NULL: not written)
+//   rank[e]                 = #{i : l_i > l_c} + #{i < c : l_i == l_c}, c the fed-forward code                        (0-based; NULL: not written)
+//   top_codes[e * top_n + j]    = the j-th index by (l descending, index ascending), float compares: -0.0 ties with +0.0 and the lower index wins
+//   top_logprobs[e * top_n + j] = (l[top_codes[j]] - m) - logf(S): the bits the log-probability has when that code is fed forward
+struct ReportOut {
+    float* entropy;
+    int* rank;
+    int top_n;                   // 0 .. 16 <= V
+    int* top_codes;
+    float* top_logprobs;
+    bool any() const { return entropy || rank || top_n > 0; }
+};
+// draw_report_kernel, in code_logprob_kernel's place (same stream, same arguments, one launch per slot, B workgroups): writes the report entry of the draw and,
+// logprob non-NULL, the log-probability too -- bit for bit what launch_code_logprob writes, so a call with both staged launches this one alone.
+hipError_t launch_draw_report(const SamplerArgs& a, const int64_t* feed, float* logprob, const ReportOut& rep, int slot, hipStream_t st);
+// score_report_kernel (hqt_score): the report of ALL rows of a sub-step's chunk in one launch, one workgroup per (pair, slot) as in launch_score_logprob; `rep`
+// holds the call's base pointers and pair0 is the chunk's first pair: entry e = (pair0 + i) * draws + draw0 + slot.  logits / codes are at the chunk's first pair.
+hipError_t launch_score_report(const float* logits, const int64_t* codes, const ReportOut& rep, int pair0, int pairs, int V, int slots, int draw0, int draws, hipStream_t st);
 // guide_logits_kernel, IN FRONT of launch_sampler on the same stream: for every pair of `pairs` [n_pairs] (device) and every slot < slots, the rows
 // pos_row * slots + slot and neg_row * slots + slot of logits [B * slots, V] are both overwritten with g = l_pos + (scale[level] - 1) (l_pos - l_neg), each
 // operation rounded to fp32 on its own (no FMA) in every precision.  One launch per sub-step, n_pairs x slots workgroups; rows outside every pair are not touched.

@@ -1150,13 +1150,14 @@ hipError_t launch_sampler(const SamplerArgs& args, hipStream_t st) {
 // per thread a pairwise tree over its groups (padded with zeros to G4), then the xor butterfly of the wave, then the four wave sums as (w0 + w1) + (w2 + w3) -- the
 // value depends on the row's bits and on V alone, never on B, the batch row or the other rows.  `feed` is indexed like `out`: the forced code where a level is forced
 // (clamped into the vocabulary, as the embedding kernels clamp it), else the code the sampler wrote.
-// logprob_row: the value of one row, by the 256 threads of a workgroup; thread 0 stores it in *dst.  The ONE place that does this arithmetic
-// (code_logprob_kernel and score_logprob_kernel call it).
+// row_max_sel / row_sums / logprob_row: the arithmetic of one row, by the 256 threads of a workgroup.  The ONE place that does it: code_logprob_kernel and
+// score_logprob_kernel call logprob_row, the draw-report kernels call the same two halves and go on with the row they left in registers.
+// row_max_sel: loads the row into v (groups past V are left unset and never read), returns m = max l to every thread and leaves l[code] in *sel (LDS; valid
+// for every thread once the function returns).
 template <int G4>
-__device__ __forceinline__ void logprob_row(const float* lg, int code, int V, float* dst) {
-    __shared__ float redf[4], reds[4], sel;
+__device__ __forceinline__ float row_max_sel(const float* lg, int code, int V, float4 (&v)[G4], float* sel) {
+    __shared__ float redf[4];
     const int tid = threadIdx.x;
-    float4 v[G4];
     float m = -INFINITY;
 #pragma unroll
     for (int k = 0; k < G4; ++k) {
@@ -1164,30 +1165,60 @@ __device__ __forceinline__ void logprob_row(const float* lg, int code, int V, fl
         if (i4 * 4 < V) {                                 // V % 4 == 0
             v[k] = *reinterpret_cast<const float4*>(lg + i4 * 4);
             m = fmaxf(fmaxf(m, fmaxf(v[k].x, v[k].y)), fmaxf(v[k].z, v[k].w));
-            if (i4 == (code >> 2)) { const int e = code & 3; sel = e == 0 ? v[k].x : (e == 1 ? v[k].y : (e == 2 ? v[k].z : v[k].w)); }      // one thread of the workgroup
+            if (i4 == (code >> 2)) { const int e = code & 3; *sel = e == 0 ? v[k].x : (e == 1 ? v[k].y : (e == 2 ? v[k].z : v[k].w)); }      // one thread of the workgroup
         }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
     if ((tid & 63) == 0) redf[tid >> 6] = m;
     __syncthreads();
-    m = fmaxf(fmaxf(redf[0], redf[1]), fmaxf(redf[2], redf[3]));
-    float s[G4];
+    return fmaxf(fmaxf(redf[0], redf[1]), fmaxf(redf[2], redf[3]));
+}
+// one product of the entropy's T = sum expf(l - m) (l - m), rounded on its own (never contracted with the sum around it: numpy in float32 follows it step by step)
+__device__ __forceinline__ float exp_times(float e, float d) {
+#pragma clang fp contract(off)
+    const float p = e * d;
+    return p;
+}
+// row_sums: S = sum expf(l_i - m) and, WITH_T, T = sum expf(l_i - m) (l_i - m), to every thread; both in the one fixed order (see above): per float4 group
+// (x + y) + (z + w), per thread a pairwise tree over its groups, the xor butterfly of the wave, the four wave sums as (w0 + w1) + (w2 + w3).
+template <int G4, bool WITH_T>
+__device__ __forceinline__ void row_sums(const float4 (&v)[G4], float m, int V, float& S, float& T) {
+    __shared__ float reds[4], redt[4];
+    const int tid = threadIdx.x;
+    float s[G4], t[WITH_T ? G4 : 1];
 #pragma unroll
     for (int k = 0; k < G4; ++k) {
         s[k] = 0.0f;
-        if ((tid + 256 * k) * 4 < V) s[k] = (expf(v[k].x - m) + expf(v[k].y - m)) + (expf(v[k].z - m) + expf(v[k].w - m));
+        if (WITH_T) t[k] = 0.0f;
+        if ((tid + 256 * k) * 4 < V) {
+            const float dx = v[k].x - m, dy = v[k].y - m, dz = v[k].z - m, dw = v[k].w - m;
+            const float ex = expf(dx), ey = expf(dy), ez = expf(dz), ew = expf(dw);
+            s[k] = (ex + ey) + (ez + ew);
+            if (WITH_T) t[k] = (exp_times(ex, dx) + exp_times(ey, dy)) + (exp_times(ez, dz) + exp_times(ew, dw));
+        }
     }
 #pragma unroll
     for (int w = 1; w < G4; w <<= 1)
 #pragma unroll
-        for (int k = 0; k < G4; k += 2 * w) s[k] += s[k + w];
-    float sum = s[0];
+        for (int k = 0; k < G4; k += 2 * w) { s[k] += s[k + w]; if (WITH_T) t[k] += t[k + w]; }
+    float sum = s[0], tsum = WITH_T ? t[0] : 0.0f;
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-    if ((tid & 63) == 0) reds[tid >> 6] = sum;
+    for (int off = 32; off > 0; off >>= 1) { sum += __shfl_xor(sum, off, 64); if (WITH_T) tsum += __shfl_xor(tsum, off, 64); }
+    if ((tid & 63) == 0) { reds[tid >> 6] = sum; if (WITH_T) redt[tid >> 6] = tsum; }
     __syncthreads();
-    if (tid == 0) *dst = (sel - m) - logf((reds[0] + reds[1]) + (reds[2] + reds[3]));
+    S = (reds[0] + reds[1]) + (reds[2] + reds[3]);
+    T = WITH_T ? (redt[0] + redt[1]) + (redt[2] + redt[3]) : 0.0f;
+}
+// logprob_row: thread 0 stores the value of the row at `code` in *dst
+template <int G4>
+__device__ __forceinline__ void logprob_row(const float* lg, int code, int V, float* dst) {
+    __shared__ float sel;
+    float4 v[G4];
+    const float m = row_max_sel<G4>(lg, code, V, v, &sel);
+    float S, T;
+    row_sums<G4, false>(v, m, V, S, T);
+    if (threadIdx.x == 0) *dst = (sel - m) - logf(S);
 }
 template <int G4>
 __global__ __launch_bounds__(256) void code_logprob_kernel(SamplerArgs a, const int64_t* feed, float* logprob, int slot) {
@@ -1221,6 +1252,129 @@ hipError_t launch_code_logprob(const SamplerArgs& a, const int64_t* feed, float*
     if (a.V <= 4096) code_logprob_kernel<4><<<a.B, 256, 0, st>>>(a, feed, logprob, slot);
     else if (a.V <= 8192) code_logprob_kernel<8><<<a.B, 256, 0, st>>>(a, feed, logprob, slot);
     else code_logprob_kernel<16><<<a.B, 256, 0, st>>>(a, feed, logprob, slot);
+    return hipGetLastError();
+}
+
+// Draw report (kernels.h: ReportOut): entropy, rank and the top-N of the row behind a draw, by the 256 threads that hold the row in registers as logprob_row
+// holds it -- m and S come from the same two functions, so a log-probability written here has the bits code_logprob_kernel gives it.  Every index into v[] is a
+// compile-time one (fully unrolled loops; what is taken is a 4 G4-bit mask per thread, tested at constant shifts): no scratch.  No atomics: every tie is decided
+// by index.  The order is (value descending, index ascending) under float compares, so -0.0 and +0.0 tie and the lower index comes first; NaN logits are not
+// ordered at all (finite logits are assumed, as everywhere behind the head GEMM).
+__device__ __forceinline__ bool report_before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
+// the thread's best element not yet taken; none left: (-inf, INT_MAX), which loses against every element of the row
+template <int G4>
+__device__ __forceinline__ void report_local_best(const float4 (&v)[G4], unsigned long long taken, float& bv, int& bi) {
+    bv = -INFINITY;
+    bi = INT_MAX;
+#pragma unroll
+    for (int k = 0; k < G4; ++k) {
+        const int base = ((int)threadIdx.x + 256 * k) * 4;
+        if (!((taken >> (4 * k + 0)) & 1) && report_before(v[k].x, base + 0, bv, bi)) { bv = v[k].x; bi = base + 0; }
+        if (!((taken >> (4 * k + 1)) & 1) && report_before(v[k].y, base + 1, bv, bi)) { bv = v[k].y; bi = base + 1; }
+        if (!((taken >> (4 * k + 2)) & 1) && report_before(v[k].z, base + 2, bv, bi)) { bv = v[k].z; bi = base + 2; }
+        if (!((taken >> (4 * k + 3)) & 1) && report_before(v[k].w, base + 3, bv, bi)) { bv = v[k].w; bi = base + 3; }
+    }
+}
+// one row: entry e of the report and, logprob_dst non-NULL, the log-probability.  r is workgroup-uniform, so every barrier below is reached by all or by none.
+template <int G4>
+__device__ __forceinline__ void report_row(const float* lg, int code, int V, float* logprob_dst, const ReportOut& r, long long e) {
+    __shared__ float sel, wv[2][4];
+    __shared__ int wi[2][4], wcnt[4];
+    const int tid = threadIdx.x;
+    float4 v[G4];
+    const float m = row_max_sel<G4>(lg, code, V, v, &sel);
+    float S, T;
+    row_sums<G4, true>(v, m, V, S, T);
+    const float lc = sel, logS = logf(S);
+    if (tid == 0) {
+        if (logprob_dst) *logprob_dst = (lc - m) - logS;
+        if (r.entropy) r.entropy[e] = logS - T / S;
+    }
+    if (r.rank) {                                         // an integer count: elements in front of (l_c, c) in the order
+        int cnt = 0;
+#pragma unroll
+        for (int k = 0; k < G4; ++k) {
+            const int base = (tid + 256 * k) * 4;
+            if (base < V)
+                cnt += (int)report_before(v[k].x, base + 0, lc, code) + (int)report_before(v[k].y, base + 1, lc, code) +
+                       (int)report_before(v[k].z, base + 2, lc, code) + (int)report_before(v[k].w, base + 3, lc, code);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+        if ((tid & 63) == 0) wcnt[tid >> 6] = cnt;
+        __syncthreads();
+        if (tid == 0) r.rank[e] = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+    }
+    if (r.top_n > 0) {
+        // top_n rounds of a workgroup argmax: every thread offers its best element not yet taken, the wave's butterfly and then the four wave winners (through
+        // LDS, two buffers in turn: one barrier per round) name the round's element, and only the thread that owns it looks for its next best
+        unsigned long long taken = 0;
+#pragma unroll
+        for (int k = 0; k < G4; ++k) if ((tid + 256 * k) * 4 >= V) taken |= 0xFull << (4 * k);        // groups past V: never loaded, never offered
+        float bv;
+        int bi;
+        report_local_best<G4>(v, taken, bv, bi);
+        for (int j = 0; j < r.top_n; ++j) {
+            float cv = bv;
+            int ci = bi;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const float ov = __shfl_xor(cv, off, 64);
+                const int oi = __shfl_xor(ci, off, 64);
+                if (report_before(ov, oi, cv, ci)) { cv = ov; ci = oi; }
+            }
+            const int buf = j & 1;
+            if ((tid & 63) == 0) { wv[buf][tid >> 6] = cv; wi[buf][tid >> 6] = ci; }
+            __syncthreads();
+            cv = wv[buf][0];
+            ci = wi[buf][0];
+#pragma unroll
+            for (int w = 1; w < 4; ++w) if (report_before(wv[buf][w], wi[buf][w], cv, ci)) { cv = wv[buf][w]; ci = wi[buf][w]; }
+            if (tid == 0) {
+                r.top_codes[e * r.top_n + j] = ci;
+                r.top_logprobs[e * r.top_n + j] = (cv - m) - logS;
+            }
+            if (ci < V && ((ci >> 2) & 255) == tid) {     // element ci = 4 (tid + 256 k) + lane: bit 4 k + lane of the owner's mask
+                taken |= 1ull << (4 * (ci >> 10) + (ci & 3));
+                report_local_best<G4>(v, taken, bv, bi);
+            }
+        }
+    }
+}
+template <int G4>
+__global__ __launch_bounds__(256) void draw_report_kernel(SamplerArgs a, const int64_t* feed, float* logprob, ReportOut rep, int slot) {
+    const int V = a.V;
+    const int b = blockIdx.x, r = b * a.slots + slot;
+    if (row_idle(a.row_pos, b)) return;                  // workgroup-uniform: an idle row of a rolling pass has no entry
+    const int step = step_of(a.state, a.row_pos, b);
+    const int draw = a.draw0 + slot;
+    const int draws = a.draws > 0 ? a.draws : 5;
+    const long long pos = (long long)b * a.n_steps + step;
+    const int code = (int)clamp_idx(feed[a.out_stride > 0 ? pos * a.out_stride + a.out_slot : pos * a.slots + slot], V);
+    const long long e = pos * draws + draw;
+    report_row<G4>(a.logits + (long long)r * V, code, V, logprob ? logprob + e : nullptr, rep, e);
+}
+template <int G4>
+__global__ __launch_bounds__(256) void score_report_kernel(const float* logits, const int64_t* codes, ReportOut rep, int pair0, int V, int slots, int draw0, int draws) {
+    const int r = blockIdx.x, pair = r / slots, slot = r - pair * slots;
+    report_row<G4>(logits + (long long)r * V, (int)clamp_idx(codes[r], V), V, nullptr, rep, (long long)(pair0 + pair) * draws + draw0 + slot);
+}
+static bool report_ok(const ReportOut& rep, int V) {
+    return rep.any() && rep.top_n >= 0 && rep.top_n <= 16 && rep.top_n <= V && (rep.top_n == 0 || (rep.top_codes && rep.top_logprobs));
+}
+hipError_t launch_draw_report(const SamplerArgs& a, const int64_t* feed, float* logprob, const ReportOut& rep, int slot, hipStream_t st) {
+    if (a.V % 4 || a.V > HQT_MAX_V || slot < 0 || slot >= a.slots || !report_ok(rep, a.V)) return hipErrorInvalidValue;
+    if (a.V <= 4096) draw_report_kernel<4><<<a.B, 256, 0, st>>>(a, feed, logprob, rep, slot);
+    else if (a.V <= 8192) draw_report_kernel<8><<<a.B, 256, 0, st>>>(a, feed, logprob, rep, slot);
+    else draw_report_kernel<16><<<a.B, 256, 0, st>>>(a, feed, logprob, rep, slot);
+    return hipGetLastError();
+}
+hipError_t launch_score_report(const float* logits, const int64_t* codes, const ReportOut& rep, int pair0, int pairs, int V, int slots, int draw0, int draws, hipStream_t st) {
+    if (V % 4 || V > HQT_MAX_V || pair0 < 0 || pairs < 1 || slots < 1 || draw0 < 0 || draw0 + slots > draws || !report_ok(rep, V)) return hipErrorInvalidValue;
+    const unsigned rows = (unsigned)pairs * slots;
+    if (V <= 4096) score_report_kernel<4><<<rows, 256, 0, st>>>(logits, codes, rep, pair0, V, slots, draw0, draws);
+    else if (V <= 8192) score_report_kernel<8><<<rows, 256, 0, st>>>(logits, codes, rep, pair0, V, slots, draw0, draws);
+    else score_report_kernel<16><<<rows, 256, 0, st>>>(logits, codes, rep, pair0, V, slots, draw0, draws);
     return hipGetLastError();
 }
 

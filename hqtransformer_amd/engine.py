@@ -6,13 +6,13 @@ from __future__ import annotations
 
 import ctypes as C
 import weakref
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import PRECISION_EXACT, PRECISION_FAST, hqt_config, hqt_encode_out, hqt_guide_pair, hqt_row_sampler, hqt_sample_opts, hqt_sample_opts_l3
+from ._lib import PRECISION_EXACT, PRECISION_FAST, hqt_config, hqt_draw_report, hqt_encode_out, hqt_guide_pair, hqt_row_sampler, hqt_sample_opts, hqt_sample_opts_l3
 from .spec import DEPTH_DECODINGS, STAGE1_RESAMPLES, Stage1Spec, Stage2Spec
 
 
@@ -281,6 +281,74 @@ def check_row_positions(cond_type: int, batch: int, n_steps: int, row_positions,
     return p, int(k)
 
 
+class DrawReport(NamedTuple):
+    """The report of a call's draws (``hqt_set_draw_report``), every tensor [B, n, draws] as the log-probabilities are, the two top arrays with a last axis of N:
+    ``entropy`` fp32 (nats) and ``rank`` int32 (0-based) of the fed-forward code in the raw row of its draw, ``top_codes`` int32 / ``top_logprobs`` fp32 the N most
+    likely codes by (logit descending, index ascending).  A field that was not asked for is None."""
+    entropy: Optional[torch.Tensor]
+    rank: Optional[torch.Tensor]
+    top_codes: Optional[torch.Tensor]
+    top_logprobs: Optional[torch.Tensor]
+
+
+def check_report_n(return_report, what: str = 'return_report') -> Optional[int]:
+    """``return_report=N`` checked on the host: None (no report) stays None; otherwise an integer in [0, 16] -- 0: entropy and rank only, 1..16: the top-N arrays too.
+    A bool is refused: False would read as N = 0, which IS a report."""
+    if return_report is None:
+        return None
+    if isinstance(return_report, bool) or not isinstance(return_report, (int, np.integer)):
+        raise ValueError(f'{what}: expected None or an integer N in [0, {_lib.REPORT_MAX_TOP}] (0: entropy and rank only), got {return_report!r}')
+    if not 0 <= int(return_report) <= _lib.REPORT_MAX_TOP:
+        raise ValueError(f'{what}: N={int(return_report)} outside [0, {_lib.REPORT_MAX_TOP}]')
+    return int(return_report)
+
+
+def new_draw_report(batch: int, n_steps: int, draws: int, top_n: int, device) -> DrawReport:
+    """Fresh buffers for a report with ``top_n`` alternatives, filled with what reads as "not written" (NaN; -1): the positions a prefix call does not compute, the
+    entries of an idle slot of a rolling call."""
+    shp = (int(batch), int(n_steps), int(draws))
+    return DrawReport(torch.full(shp, float('nan'), dtype=torch.float32, device=device), torch.full(shp, -1, dtype=torch.int32, device=device),
+                      torch.full(shp + (top_n,), -1, dtype=torch.int32, device=device) if top_n else None,
+                      torch.full(shp + (top_n,), float('nan'), dtype=torch.float32, device=device) if top_n else None)
+
+
+def check_report_out(report_out, batch: int, n_steps: int, draws: int, device=None, vocab: Optional[int] = None):
+    """``report_out`` checked on the host, before any engine is touched: an object with the four fields of ``DrawReport``, each None or a contiguous tensor on
+    ``device`` -- ``entropy`` fp32 and ``rank`` int32 of shape [batch, n_steps, draws], ``top_codes`` int32 and ``top_logprobs`` fp32 of shape [batch, n_steps, draws, N],
+    both or neither, 1 <= N <= 16 (and N <= ``vocab`` where given).  Returns (the ``hqt_draw_report`` to stage, N), or None when there is nothing to write."""
+    if report_out is None:
+        return None
+    fields = ('entropy', 'rank', 'top_codes', 'top_logprobs')
+    if not all(hasattr(report_out, f) for f in fields):
+        raise ValueError(f'report_out: expected an object with the fields {fields} (engine.DrawReport), got {type(report_out).__name__}')
+    ent, rank, tc, tl = (getattr(report_out, f) for f in fields)
+    if (tc is None) != (tl is None):
+        raise ValueError('report_out: top_codes and top_logprobs come together')
+    shp = (int(batch), int(n_steps), int(draws))
+    top_n = 0
+    if tc is not None:
+        if not isinstance(tc, torch.Tensor) or tc.dim() != 4:
+            raise ValueError(f'report_out.top_codes: expected a tensor of shape {shp + ("N",)}, got {tuple(getattr(tc, "shape", ()))}')
+        top_n = int(tc.shape[3])
+        if not 1 <= top_n <= _lib.REPORT_MAX_TOP:
+            raise ValueError(f'report_out.top_codes: N={top_n} alternatives outside [1, {_lib.REPORT_MAX_TOP}]')
+        if vocab is not None and top_n > int(vocab):
+            raise ValueError(f'report_out.top_codes: N={top_n} alternatives, the vocabulary has {int(vocab)} codes')
+    for t, what, want, dtype in ((ent, 'entropy', shp, torch.float32), (rank, 'rank', shp, torch.int32),
+                                 (tc, 'top_codes', shp + (top_n,), torch.int32), (tl, 'top_logprobs', shp + (top_n,), torch.float32)):
+        if t is None:
+            continue
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != want or t.dtype != dtype or not t.is_contiguous()
+                or (device is not None and t.device != torch.device(device))):
+            raise ValueError(f'report_out.{what}: expected a contiguous {dtype} tensor of shape {want}' + (f' on {device}' if device is not None else '') +
+                             f', got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))} on {getattr(t, "device", "?")}')
+    if ent is None and rank is None and not top_n:
+        return None
+    r = hqt_draw_report()
+    r.entropy, r.rank, r.top_n, r.top_codes, r.top_logprobs = _ptr(ent), _ptr(rank), top_n, _ptr(tc), _ptr(tl)
+    return r, top_n
+
+
 def check_select_rows(rows_from, paused_batch: Optional[int], max_batch: int) -> np.ndarray:
     """A row mapping for ``Engine.select_rows`` (``hqt_select_rows``) checked on the host: integers, one dimension, 1 <= B_new <= ``max_batch`` entries, each in
     [0, ``paused_batch``) -- the rows of the paused pass; None: unknown to the caller, the library checks the entries.  Any mapping: the identity, a permutation, a
@@ -535,7 +603,7 @@ class Engine:
                        row_seeds, row_offsets, row_samplers=None, prefix=None,
                        return_logprobs=False, guidance=None, keep=None,
                        prompt_groups=None, segment=None, logits_out=None,
-                       logprobs_out=None, row_positions=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+                       logprobs_out=None, row_positions=None, report_out=None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
         """Returns (codes [B, n], [B, n, 4][, [B, n, 16]], logits [n, draws, B, V] or None, logprobs [B, n, draws] or None)."""
         dev = self.device
         B, V, L = int(batch), self.s2.vocab_top, int(levels)
@@ -559,6 +627,7 @@ class Engine:
             # the leading run every row shares runs as the prefix prefill; its rows of the logits / log-probabilities are not written, as with a prefix
             P = keep_leading_run(keep[0], self.max_prefix, text_l3=self.s2.cond == 2 and L == 3)
         draws = (4 ** L - 1) // 3                   # one draw per code of a position: 1 + 4 (+ 16)
+        report = check_report_out(report_out, B, n_steps, draws, dev, V)
         shapes = [(B, n_steps) + ((4 ** l,) if l else ()) for l in range(L)]
         o = hqt_sample_opts() if L == 2 else hqt_sample_opts_l3()
         o.precision, o.n_steps = int(precision), int(n_steps)
@@ -622,6 +691,8 @@ class Engine:
                 _lib.check(self.lib.hqt_set_row_samplers(self.h, len(table), table.ctypes.data_as(C.POINTER(hqt_row_sampler))))
             if logprobs is not None:                # staged like the table: taken and cleared by the call below
                 _lib.check(self.lib.hqt_set_logprob_out(self.h, _ptr(logprobs)))
+            if report is not None:                  # ... and so is the draw report (the caller's buffers, written where the log-probabilities are)
+                _lib.check(self.lib.hqt_set_draw_report(self.h, C.byref(report[0])))
             if pairs is not None:                   # ... and so is the pair table (copied by the library)
                 _lib.check(self.lib.hqt_set_guidance(self.h, len(pairs), pairs))
             if keep is not None:                    # ... and the keep table (the mask is copied; the codes are read by the call below)
@@ -636,7 +707,7 @@ class Engine:
             _lib.check(fn(self.h, B, _ptr(cond), C.byref(o), _ptr(noise), *map(_ptr, force), _ptr(logits), *map(_ptr, outs), C.c_void_p(stream)))
             self._note_split(precision, stream, ar_rows=B)        # every head runs persistently (run_position)
         # inputs must outlive the asynchronous launches
-        self._keep = (cond, noise, force, rows, prefix, keep)     # (the row-sampler table was copied by hqt_set_row_samplers)
+        self._keep = (cond, noise, force, rows, prefix, keep, report_out)     # (the row-sampler table was copied by hqt_set_row_samplers)
         self._trust(*outs, bound=max(self.s2.vocab_top, self.s2.vocab_bot))     # the sampler only writes ids inside the vocabulary
         return outs, logits, logprobs
 
@@ -650,7 +721,7 @@ class Engine:
                row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
                return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None, keep: Optional[tuple] = None,
                prompt_groups=None, segment: Optional[Tuple[int, int]] = None, logits_out: Optional[torch.Tensor] = None,
-               logprobs_out: Optional[torch.Tensor] = None, row_positions: Optional[tuple] = None):
+               logprobs_out: Optional[torch.Tensor] = None, row_positions: Optional[tuple] = None, report_out=None):
         """Two-level sampling: returns (codes_top [B, n], codes_bot [B, n, 4][, logits [n, 5, B, V]][, logprobs [B, n, 5]]).
         ``return_logprobs``: fp32 log-probability of every code the call feeds forward -- the drawn one, or the forced one where ``force_*`` is
         given -- under the raw logits of its draw (T = 1, no cut-off: ``hqt_set_logprob_out``), appended last; with a prefix the positions < P are NaN.
@@ -688,7 +759,9 @@ class Engine:
         (the tensors the pass lives in: the positions drawn are written there, the codes of pos[b] - 1 read from there); ``logits_out`` / ``logprobs_out`` are filled
         the same way, and nothing of an idle row is written.  A slot continues exactly where the engine's rolling pass left it, joins at 0 or is empty (HqtError
         otherwise); ``cond[b]`` is read where a row stands at 0, ``row_seeds`` / ``row_offsets`` / ``row_samplers`` give each slot its request's key and settings.
-        Not on text models, not together with ``prefix``, ``keep``, ``prompt_groups`` or ``segment``."""
+        Not on text models, not together with ``prefix``, ``keep``, ``prompt_groups`` or ``segment``.
+        ``report_out`` (a ``DrawReport`` of caller-owned tensors, see ``check_report_out`` / ``new_draw_report``): the call writes entropy, rank and the top-N codes of the
+        row behind every draw into them (``hqt_set_draw_report``), exactly where ``logprobs_out`` entries are written; nothing is appended to the returned values."""
         if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
             raise ValueError('out: expected a pair (codes_top [B, n_steps], codes_bot [B, n_steps, 4])')
         outs, logits, logprobs = self._sample_levels(2, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
@@ -696,7 +769,7 @@ class Engine:
                                            return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
                                            row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance, keep=keep,
                                            prompt_groups=prompt_groups, segment=segment, logits_out=logits_out, logprobs_out=logprobs_out,
-                                           row_positions=row_positions)
+                                           row_positions=row_positions, report_out=report_out)
         return ((outs[0], outs[1]) + ((logits,) if return_logits or logits_out is not None else ())
                 + ((logprobs,) if return_logprobs or logprobs_out is not None else ()))
 
@@ -708,13 +781,14 @@ class Engine:
                 row_samplers: Optional[Sequence[tuple]] = None, prefix: Optional[Sequence[torch.Tensor]] = None,
                 return_logprobs: bool = False, guidance: Optional[Sequence[tuple]] = None, keep: Optional[tuple] = None,
                 prompt_groups=None, segment: Optional[Tuple[int, int]] = None, out: Optional[Sequence[torch.Tensor]] = None,
-                logits_out: Optional[torch.Tensor] = None, logprobs_out: Optional[torch.Tensor] = None, row_positions: Optional[tuple] = None):
+                logits_out: Optional[torch.Tensor] = None, logprobs_out: Optional[torch.Tensor] = None, row_positions: Optional[tuple] = None,
+                report_out=None):
         """Three-level sampling: returns (codes0 [B, n], codes1 [B, n, 4], codes2 [B, n, 16][, logits [n, 21, B, V]][, logprobs [B, n, 21]]); ``row_samplers``,
         ``return_logprobs`` and ``guidance`` (three scales per pair) as in ``sample``;
         ``prefix`` = [[B, P], [B, P, 4], [B, P, 16]]: completion, as in ``sample`` (``hqt_sample_prefix_l3``);
         ``keep`` = (mask [B, n], [[B, n], [B, n, 4], [B, n, 16]]): kept positions, as in ``sample``; ``prompt_groups``: shared prompts, as in ``sample``;
         ``segment`` / ``logits_out`` / ``logprobs_out``: a segment of a pass, as in ``sample``; ``out`` = the three code tensors to write into, as ``sample`` takes two;
-        ``row_positions`` = (pos, k): a rolling call, as in ``sample``."""
+        ``row_positions`` = (pos, k): a rolling call, as in ``sample``; ``report_out``: a ``DrawReport`` of [B, n, 21(, N)] tensors to write, as in ``sample``."""
         if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 3):
             raise ValueError('out: expected the three code tensors ([B, n_steps], [B, n_steps, 4], [B, n_steps, 16])')
         outs, logits, logprobs = self._sample_levels(3, batch, cond, n_steps, precision=precision, top_k=top_k, top_p=top_p, temperature=temperature,
@@ -722,7 +796,7 @@ class Engine:
                                            out=out, return_logits=return_logits, use_graph=use_graph, row_seeds=row_seeds, row_offsets=row_offsets,
                                            row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs, guidance=guidance, keep=keep,
                                            prompt_groups=prompt_groups, segment=segment, logits_out=logits_out, logprobs_out=logprobs_out,
-                                           row_positions=row_positions)
+                                           row_positions=row_positions, report_out=report_out)
         return (tuple(outs) + ((logits,) if return_logits or logits_out is not None else ())
                 + ((logprobs,) if return_logprobs or logprobs_out is not None else ()))
 
@@ -738,11 +812,12 @@ class Engine:
         return len(table)
 
     def score(self, batch: int, cond: Optional[torch.Tensor], codes: Sequence[torch.Tensor], *, precision: int = PRECISION_FAST,
-              return_logits: bool = False):
+              return_logits: bool = False, report_out=None):
         """``hqt_score``: log-probabilities fp32 [B, n, draws] of GIVEN codes (the code levels as one list, coarse to fine, int64 [B, n], [B, n, 4][, [B, n, 16]])
         in ONE teacher-forced pass over all positions -- entry (b, t, d) is what ``sample(..., force_*=codes, return_logprobs=True)`` reports, at the cost of one
         body pass over n rows per sample and the depth head over the B n pairs in chunks of ``score_chunk``.  The engine needs ``max_prefix >= n - 1``.
         ``return_logits``: also the raw logits per level, fp32 [B, n, V], [B, n, 4, V][, [B, n, 16, V]] (the head GEMMs then write them directly).
+        ``report_out``: a ``DrawReport`` of [B, n, draws(, N)] tensors the pass writes for the GIVEN codes (``hqt_set_draw_report``), as in ``sample``.
         Asynchronous on torch's current stream, like ``sample``."""
         dev = self.device
         B, V, L = int(batch), self.s2.vocab_top, self.s2.levels
@@ -752,6 +827,7 @@ class Engine:
             raise ValueError(f'codes hold {int(torch.as_tensor(codes[0]).shape[0])} samples, batch={B}')
         shapes = [(B, n) + ((4 ** l,) if l else ()) for l in range(L)]
         draws = (4 ** L - 1) // 3
+        report = check_report_out(report_out, B, n, draws, dev, V)
         cond = self._prep_cond(cond, B)
         cs = [self._prep(c, shp, torch.int64, f'codes[{l}]', V) for l, (c, shp) in enumerate(zip(codes, shapes))]
         logprobs = torch.empty((B, n, draws), dtype=torch.float32, device=dev)
@@ -760,9 +836,11 @@ class Engine:
         lp = (C.c_void_p * 3)(*[_ptr(t) for t in logits]) if logits is not None else None
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
+            if report is not None:                  # staged on the handle; hqt_score takes it (and clears it even when it fails)
+                _lib.check(self.lib.hqt_set_draw_report(self.h, C.byref(report[0])))
             _lib.check(self.lib.hqt_score(self.h, B, _ptr(cond), cp, n, int(precision), _ptr(logprobs), lp, C.c_void_p(stream)))
             self._note_split(precision, stream)
-        self._keep = (cond, cs, cp, lp)
+        self._keep = (cond, cs, cp, lp, report_out)
         return (logprobs, logits) if return_logits else logprobs
 
     # ------------------------------------------------------------------ stage 1, encode side

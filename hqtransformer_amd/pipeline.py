@@ -20,8 +20,8 @@ from typing import Any, Callable, List, NamedTuple, Optional, Tuple
 import torch
 
 from ._lib import POLICY_LATENCY, POLICY_THROUGHPUT
-from .engine import check_select_rows
-from .sampling import (_batch_and_cond, _precision, _seed_from_torch, guidance_scales, negative_cond, prompt_groups_of, rearrange_levels,
+from .engine import DrawReport, check_select_rows, new_draw_report
+from .sampling import (_batch_and_cond, _first_rows, _precision, _report_n, _seed_from_torch, guidance_scales, negative_cond, prompt_groups_of, rearrange_levels,
                        sampling_hqtransformer, sampling_ihqgpt)
 
 
@@ -127,7 +127,32 @@ def rank_candidates(scores: torch.Tensor, keep: int) -> torch.Tensor:
     return torch.sort(scores, dim=1, descending=True, stable=True).indices[:, :int(keep)]
 
 
-def score_codes(stage2, codes, cond, precision: Optional[str] = None, one_pass: bool = False, score_chunk: Optional[int] = None, **kw) -> torch.Tensor:
+def uncertainty_map(entropy: torch.Tensor, levels: int) -> list:
+    """The entropies of a ``DrawReport`` fp32 [B, n, draws] (n = K K top positions; draws = 5, or 21 with three levels, in the draw order top, bot0..bot3[,
+    l2 0..15]) -> one grid per code level, so that a map lies over the decoded image: [B, K, K], [B, 2 K, 2 K][, [B, 4 K, 4 K]] -- cell (position t, slot s) of
+    a level lands where ``decode_sequences`` / ``seq_layout`` place that code (``rearrange_levels``: 'B (H W) (kh kw) -> B (H kh) (W kw)').  Works on any per-draw
+    quantity laid out like the log-probabilities (the rank, ``-logprobs``)."""
+    L = int(levels)
+    if L not in (2, 3) or entropy.dim() != 3 or int(entropy.shape[2]) != (4 ** L - 1) // 3:
+        raise ValueError(f'uncertainty_map: expected [B, n, {(4 ** L - 1) // 3 if L in (2, 3) else "draws"}] for {levels} code levels, got {tuple(entropy.shape)}')
+    n = int(entropy.shape[1])
+    K = int(round(n ** 0.5))
+    if K * K != n:
+        raise ValueError(f'uncertainty_map: n={n} top positions are not a square grid')
+    first = [(4 ** l - 1) // 3 for l in range(L + 1)]             # level l holds the draws [first[l], first[l + 1])
+    per_level = [entropy[:, :, first[l]:first[l + 1]] for l in range(L)]
+    per_level[0] = per_level[0][:, :, 0]
+    return list(rearrange_levels(per_level, K))
+
+
+def _score_report(eng, B: int, n: int, draws: int, report):
+    """``report=N`` of the scoring calls -> the fresh ``DrawReport`` buffers the engine writes (None: none)."""
+    from .engine import new_draw_report
+    return None if report is None else new_draw_report(B, n, draws, report, eng.device)
+
+
+def score_codes(stage2, codes, cond, precision: Optional[str] = None, one_pass: bool = False, score_chunk: Optional[int] = None, report: Optional[int] = None,
+                **kw):
     """Log-probabilities of GIVEN codes under the model: ``codes`` = the code levels as one list, coarse to fine (int64 [B, n], [B, n, 4][, [B, n, 16]]),
     ``cond`` as in ``sampling_ihqgpt`` -> fp32 [B, n, draws], entry (b, t, d) the log-probability (T = 1, no cut-off) of the code of draw d at position t
     given the sample's codes before it: ``-sequence_logprob(...)`` is the stage-2 negative log-likelihood in nats.
@@ -138,8 +163,11 @@ def score_codes(stage2, codes, cond, precision: Optional[str] = None, one_pass: 
     ``one_pass=True``: ``hqt_score`` -- the body once over all n rows per sample, the depth head over the B n (sample, position) pairs in chunks of
     ``score_chunk`` pairs (None: what the engine has, ``max_batch`` for a new one); the engine is asked for ``max_prefix = n - 1``.  Takes the 'bidirectional'
     head (nothing is forced in its depth pass); ValueError for 'top2mid2bot', which is scored stepwise only (``one_pass=False``).
-    ``precision`` 'exact' | 'fast' | 'split' (default: ``use_fp16`` of ``kw``, i.e. FAST); further keywords: ``use_fp16``, ``lane``, ``use_graph`` (stepwise only)."""
+    ``precision`` 'exact' | 'fast' | 'split' (default: ``use_fp16`` of ``kw``, i.e. FAST); further keywords: ``use_fp16``, ``lane``, ``use_graph`` (stepwise only).
+    ``report=N`` (0..16; None: none), on either path: returns ``(logprobs, DrawReport)`` -- entropy and rank of every GIVEN code in the row it is scored under and,
+    N >= 1, the N most likely codes there (``hqt_set_draw_report``; ``uncertainty_map`` folds the entropies into one grid per level)."""
     spec = stage2.spec
+    report = _report_n(spec, report)                 # refused here, before an engine is built
     if one_pass:
         from .engine import check_score_codes
         check_score_codes(spec, codes, 'score_codes(one_pass=True)')
@@ -159,19 +187,29 @@ def score_codes(stage2, codes, cond, precision: Optional[str] = None, one_pass: 
         raise ValueError(f'codes hold {int(codes[0].shape[0])} samples, cond {B}')
     if one_pass:
         eng = stage2.engine(B, n, lane, max_prefix=n - 1, score_chunk=score_chunk)
-        return eng.score(B, cond, codes, precision=_precision(precision, use_fp16))
+        rep = _score_report(eng, B, n, (4 ** spec.levels - 1) // 3, report)
+        logprobs = eng.score(B, cond, codes, precision=_precision(precision, use_fp16), report_out=rep)
+        return logprobs if rep is None else (logprobs, rep)
     eng = stage2.engine(B, n, lane)
-    common = dict(precision=_precision(precision, use_fp16), seed=0, return_logprobs=True, **kw)
+    rep = _score_report(eng, B, n, (4 ** spec.levels - 1) // 3, report)
+    common = dict(precision=_precision(precision, use_fp16), seed=0, return_logprobs=True, report_out=rep, **kw)
     if spec.levels == 3:
-        return eng.sample3(B, cond, n, force=codes, **common)[-1]
-    return eng.sample(B, cond, n, force_top=codes[0], force_bot=codes[1], **common)[-1]
+        logprobs = eng.sample3(B, cond, n, force=codes, **common)[-1]
+    else:
+        logprobs = eng.sample(B, cond, n, force_top=codes[0], force_bot=codes[1], **common)[-1]
+    return logprobs if rep is None else (logprobs, rep)
 
 
-def score_images(model, images: torch.Tensor, cond=None, encode_precision: Optional[str] = None, **score_kw) -> Tuple[torch.Tensor, list]:
+def score_images(model, images: torch.Tensor, cond=None, encode_precision: Optional[str] = None, report: Optional[int] = None, **score_kw):
     """Stage-2 log-likelihood of real images: ``images`` fp32 [B, 3, R, R] in [-1, 1] -> ``stage1.code_grids`` -> ``grids_to_sequences`` ->
-    ``score_codes(one_pass=True)`` (``score_kw``: its further keywords).  Returns ``(sequence_logprob fp64 [B], codes)``, the codes in the sampler's layout."""
+    ``score_codes(one_pass=True)`` (``score_kw``: its further keywords, ``one_pass=False`` among them).  Returns ``(sequence_logprob fp64 [B], codes)``, the codes in
+    the sampler's layout; ``report=N`` appends the ``DrawReport`` of the image's own codes -- ``uncertainty_map(report.entropy, levels)`` is an anomaly map over it."""
     codes = grids_to_sequences(list(model.stage1.code_grids(images, precision=encode_precision)))
-    return sequence_logprob(score_codes(model.stage2, codes, cond, one_pass=True, **score_kw)), codes
+    score_kw.setdefault('one_pass', True)
+    if report is None:
+        return sequence_logprob(score_codes(model.stage2, codes, cond, **score_kw)), codes
+    logprobs, rep = score_codes(model.stage2, codes, cond, report=report, **score_kw)
+    return sequence_logprob(logprobs), codes, rep
 
 
 def session_cutoffs(levels: int, kw: dict) -> Tuple[tuple, tuple, tuple]:
@@ -194,7 +232,8 @@ class SamplingSession:
     re-maps the rows -- reorder, drop, fork -- and ``finish`` draws what remains.  All segments together draw bit for bit what ONE sampler call with the same
     keys draws: ``SamplingSession(stage2, B, cond, n, seed=s).finish()`` equals ``sampling_ihqgpt(stage2, B, cond, max_seq_len=n, seed=s)``.
     The session owns the code tensors (``codes``: the levels as one list, full length; positions >= ``position`` are not drawn yet), the optional
-    log-probabilities (``return_logprobs=True``: fp32 [B, n, draws], NaN where not drawn) and one explicit Philox key per row -- ``row_seeds`` / ``row_offsets``,
+    log-probabilities (``return_logprobs=True``: fp32 [B, n, draws], NaN where not drawn), the optional draw report (``return_report=N``: ``report``, a
+    ``DrawReport`` of [B, n, draws(, N)] tensors, NaN / -1 where not drawn; ``select`` re-maps its rows with the log-probabilities) and one explicit Philox key per row -- ``row_seeds`` / ``row_offsets``,
     default ``(seed, sample_offset + b)``, the implicit keys of a plain call -- so that a row keeps its identity, and goes on drawing what it would have drawn,
     wherever ``select`` puts it.  ``cond`` as in ``sampling_ihqgpt``; ``sampler``: its sampler keywords (``top_k_top`` ... / ``top_k``, ``top_p``,
     ``softmax_temperature``), ``row_samplers`` and ``guidance`` (a ready pair table over the rows), the defaults of every ``advance``.
@@ -204,7 +243,8 @@ class SamplingSession:
 
     def __init__(self, stage2, num_candidates: int, cond, n: int = 64, *, seed: Optional[int] = None, sample_offset: int = 0, row_seeds=None,
                  row_offsets=None, precision: Optional[str] = None, use_fp16: bool = True, use_graph: bool = True, lane: int = 0,
-                 return_logprobs: bool = False, share_prompts: bool = False, **sampler):
+                 return_logprobs: bool = False, share_prompts: bool = False, return_report: Optional[int] = None, **sampler):
+        top_n = _report_n(stage2.spec, return_report)
         unknown = set(sampler) - set(self._DEFAULTS)
         if unknown:
             raise TypeError(f'SamplingSession: unexpected keywords {sorted(unknown)} (sampler settings, row_samplers and guidance travel here)')
@@ -230,6 +270,7 @@ class SamplingSession:
         self.position = 0
         self.codes = [torch.zeros((self.B, self.n) + ((4 ** l,) if l else ()), dtype=torch.int64, device=dev) for l in range(self.L)]
         self.logprobs = torch.full((self.B, self.n, (4 ** self.L - 1) // 3), float('nan'), dtype=torch.float32, device=dev) if return_logprobs else None
+        self.report = None if top_n is None else new_draw_report(self.B, self.n, (4 ** self.L - 1) // 3, top_n, dev)
 
     @property
     def done(self) -> bool:
@@ -260,7 +301,7 @@ class SamplingSession:
             raise ValueError(f'force: expected one entry per code level ({self.L}), None where a level is drawn')
         common = dict(precision=self.precision, top_k=top_k, top_p=top_p, temperature=temperature, seed=0, use_graph=self.use_graph,
                       row_seeds=self.row_seeds, row_offsets=self.row_offsets, row_samplers=kw.get('row_samplers'), guidance=kw.get('guidance'),
-                      out=self.codes, segment=(start, stop), logprobs_out=self.logprobs, **extra)
+                      out=self.codes, segment=(start, stop), logprobs_out=self.logprobs, report_out=self.report, **extra)
         if self.L == 3:
             self.engine.sample3(self.B, cond, self.n, force=force, **common)
         else:
@@ -290,6 +331,8 @@ class SamplingSession:
         self.codes = [c.index_select(0, idx) for c in self.codes]
         if self.logprobs is not None:
             self.logprobs = self.logprobs.index_select(0, idx)
+        if self.report is not None:
+            self.report = DrawReport(*(None if f is None else f.index_select(0, idx) for f in self.report))
         if self.cond is not None:
             self.cond = torch.as_tensor(self.cond)
             self.cond = self.cond.index_select(0, idx.to(self.cond.device))
@@ -319,7 +362,8 @@ class RollingSampler:
     Text models are refused: a row that joins at position 0 would need a prompt prefill of its own, which is not built."""
 
     def __init__(self, stage2, slots: int, n: int, *, precision: Optional[str] = None, use_fp16: bool = True, use_graph: bool = True, lane: int = 0,
-                 return_logprobs: bool = False):
+                 return_logprobs: bool = False, return_report: Optional[int] = None):
+        top_n = _report_n(stage2.spec, return_report)
         if stage2.use_txt_cond:
             raise ValueError('RollingSampler: a rolling pass on a text-conditional model is not built (a row that joins at position 0 needs a prompt prefill of its own)')
         self.stage2, self.L, self.slots, self.n = stage2, int(stage2.spec.levels), int(slots), int(n)
@@ -332,6 +376,7 @@ class RollingSampler:
         dev = self.engine.device
         self.codes = [torch.full((self.slots, self.n) + ((4 ** l,) if l else ()), -1, dtype=torch.int64, device=dev) for l in range(self.L)]
         self.logprobs = torch.full((self.slots, self.n, (4 ** self.L - 1) // 3), float('nan'), dtype=torch.float32, device=dev) if return_logprobs else None
+        self.report = None if top_n is None else new_draw_report(self.slots, self.n, (4 ** self.L - 1) // 3, top_n, dev)
         self.class_cond = bool(stage2.spec.cond == 1)
         default = step_row_samplers(self.L, [1], [{}])[0]
         # per slot: the position it draws next (-1: empty), its request's ticket, condition, key and sampler settings
@@ -365,7 +410,8 @@ class RollingSampler:
 
     def step(self, k: int = 1) -> list:
         """Admits queued requests into free slots (in submission order, lowest free slot first), runs one rolling call of ``k`` steps and returns the requests
-        that finished in it as ``(ticket, codes[, logprobs])``: ``codes`` the levels as one list, [n], [n, 4][, [n, 16]], gathered on the device.  A slot freed
+        that finished in it as ``(ticket, codes[, logprobs][, report])``: ``codes`` the levels as one list, [n], [n, 4][, [n, 16]], gathered on the device;
+        ``report`` (``return_report=N``): the request's ``DrawReport`` slice, [n, draws(, N)] per field.  A slot freed
         in this call takes a new request in the next one.  Nothing queued or live: no engine call, []."""
         k = int(k)
         if not 1 <= k <= self.n:
@@ -378,7 +424,8 @@ class RollingSampler:
             return []
         cond = torch.tensor(self.cond, dtype=torch.int64) if self.class_cond else None
         common = dict(precision=self.precision, seed=0, use_graph=self.use_graph, row_seeds=list(self.row_seeds), row_offsets=list(self.row_offsets),
-                      row_samplers=list(self.row_samplers), out=self.codes, logprobs_out=self.logprobs, row_positions=(list(self.pos), k))
+                      row_samplers=list(self.row_samplers), out=self.codes, logprobs_out=self.logprobs, report_out=self.report,
+                      row_positions=(list(self.pos), k))
         if self.L == 3:
             self.engine.sample3(self.slots, cond, self.n, **common)
         else:
@@ -390,9 +437,11 @@ class RollingSampler:
         idx = torch.as_tensor(done, dtype=torch.int64, device=self.codes[0].device)
         codes = [c.index_select(0, idx) for c in self.codes]
         logprobs = self.logprobs.index_select(0, idx) if self.logprobs is not None else None
+        report = None if self.report is None else [None if f is None else f.index_select(0, idx) for f in self.report]
         out = []
         for i, s in enumerate(done):
-            out.append((self.ticket[s], [c[i] for c in codes]) + ((logprobs[i],) if logprobs is not None else ()))
+            out.append((self.ticket[s], [c[i] for c in codes]) + ((logprobs[i],) if logprobs is not None else ())
+                       + ((DrawReport(*(None if f is None else f[i] for f in report)),) if report is not None else ()))
             self.ticket[s] = None
         self.free = sorted(self.free + done)
         return out
@@ -681,6 +730,10 @@ class _Step(NamedTuple):
     def wants_logprobs(self) -> bool:
         return bool(self.sample_kw.get('return_logprobs'))
 
+    def wants_report(self) -> bool:
+        """``return_report=N`` is a step setting like the sampler's: it is NOT among the free ones of ``settings``, so steps merge only when their N is equal."""
+        return self.sample_kw.get('return_report') is not None
+
     def prefix_len(self) -> int:
         """P of the step's ``prefix_codes`` (0: none)."""
         prefix = self.sample_kw.get('prefix_codes')
@@ -766,7 +819,9 @@ class InflightSampler:
         behind ``done_event``.  Steps of a merged pass need not agree on it: the pass computes the buffer if any of its steps asks, and only
         those steps get their rows.  ``guidance_scale`` / ``neg_cond`` (with the sampler keywords, as in ``sampling_ihqgpt``): a guided step; it
         merges with guided and unguided steps alike -- the pass carries one negative row per row of a guided step behind the rows of all steps
-        (``step_guidance``), which are neither decoded nor returned."""
+        (``step_guidance``), which are neither decoded nor returned.  ``return_report=N`` (with the sampler keywords, as in ``sampling_ihqgpt``): the step's
+        ``DrawReport`` as the last element, behind the log-probabilities; steps merge into one pass only when their N is equal (None included)."""
+        _report_n(self.model.stage2.spec, sample_kw.get('return_report'))      # refused here, before the step is queued or an engine is built
         if self.share_prompts:
             sample_kw.setdefault('share_prompts', True)
         if self.merge > 1:
@@ -842,12 +897,15 @@ class InflightSampler:
         if self.record_phases:
             phases = tuple(torch.cuda.Event(enable_timing=True) for _ in range(3))
             self.phase_log.append((phases, sum(sizes)))
-        ct, cb, px, ev, *lp = self._launch(sum(sizes) + len(mirrors), cond, keep_rows=sum(sizes), seed=seeds[0], max_seq_len=ref.max_seq_len, use_fp16=ref.use_fp16, decode=True,
+        ct, cb, px, ev, *more = self._launch(sum(sizes) + len(mirrors), cond, keep_rows=sum(sizes), seed=seeds[0], max_seq_len=ref.max_seq_len, use_fp16=ref.use_fp16, decode=True,
                                       precision=ref.precision, clamp01=ref.clamp01, use_graph=ref.use_graph,
                                       after=split_after if any(e.after is not None for e in q) else None, phase_events=phases,
                                       order_after_current=any(e.order_after_current for e in q), row_seeds=row_seeds, row_offsets=row_offsets, **kw)
+        lp = more.pop(0) if want_lp else None
+        report = more.pop(0) if ref.wants_report() else None
         for e, lo in zip(q, los):
-            e.pending.value = (*_rows(ct, cb, px, lo, e.num_candidates), ev) + ((lp[0][lo:lo + e.num_candidates],) if e.wants_logprobs() else ())
+            e.pending.value = ((*_rows(ct, cb, px, lo, e.num_candidates), ev) + ((lp[lo:lo + e.num_candidates],) if e.wants_logprobs() else ())
+                               + ((DrawReport(*(None if f is None else f[lo:lo + e.num_candidates] for f in report)),) if report is not None else ()))
 
     def _launch(self, num_candidates: int, cond, *, seed: Optional[int] = None, max_seq_len: int = 64, use_fp16: bool = True,
                 decode: bool = True, precision: Optional[str] = None, clamp01: bool = True, use_graph: bool = True,
@@ -858,6 +916,7 @@ class InflightSampler:
         # use_fp16 (sampling_ihqgpt's `precision`; the `precision` of this method is the DECODE arithmetic)
         ar_precision = sample_kw.pop('ar_precision', None)
         want_lp = bool(sample_kw.pop('return_logprobs', False))
+        want_report = sample_kw.get('return_report') is not None
         st = self.streams[lane]
         caller = torch.cuda.current_stream(self.device)
         # order the lane after whatever the caller's stream has queued (inputs; earlier direct use of lane 0's engine):
@@ -880,13 +939,14 @@ class InflightSampler:
             codes = sample_codes(self.model.stage2, num_candidates, cond, seed=seed, max_seq_len=max_seq_len, use_fp16=use_fp16,
                                  use_graph=use_graph, lane=lane, precision=ar_precision, return_logprobs=want_lp, **sample_kw)
             if keep_rows is not None and keep_rows < num_candidates:      # a merged pass's negative rows end here: not decoded, not returned
-                codes = [c[:keep_rows] for c in codes]
+                codes = [_first_rows(c, keep_rows) for c in codes]
+            report = codes.pop() if want_report else None      # (behind the log-probabilities)
             logprobs = codes.pop() if want_lp else None
             if phase_events is not None:
                 phase_events[1].record(ast)
         if ast is not st:
             st.wait_stream(ast)
-            for t in (*codes, logprobs):
+            for t in (*codes, logprobs, *(report or ())):
                 if t is not None:
                     t.record_stream(st)
         ct, cb = _public(codes)                      # the 4-tuple shape of the result, whatever the level count
@@ -902,10 +962,10 @@ class InflightSampler:
             ev.record(st)
         # the results were allocated on the lane's stream and will be read (and eventually freed) on the caller's: tell the
         # caching allocator, or it may hand the memory to the lane again while the caller's stream still reads it
-        for t in (*codes, px, logprobs):
+        for t in (*codes, px, logprobs, *(report or ())):
             if t is not None:
                 t.record_stream(caller)
-        return (ct, cb, px, ev) + ((logprobs,) if want_lp else ())
+        return (ct, cb, px, ev) + ((logprobs,) if want_lp else ()) + ((report,) if want_report else ())
 
     def release(self, batch: int, max_seq_len: int) -> None:
         """Back to the latency-oriented kernels on lane 0 (the engine direct ``sampling_ihqgpt`` calls use)."""

@@ -10,7 +10,7 @@ from typing import List, Optional
 import torch
 
 from ._lib import PRECISION_EXACT, PRECISION_FAST, PRECISIONS
-from .engine import check_keep, check_prefix, keep_leading_run
+from .engine import DrawReport, check_keep, check_prefix, check_report_n, keep_leading_run, new_draw_report
 from .text import pad_caption
 
 
@@ -188,7 +188,8 @@ def sampling_ihqgpt(model,
                     guidance=None,
                     keep_mask=None,
                     kept_codes=None,
-                    share_prompts: bool = False):
+                    share_prompts: bool = False,
+                    return_report: Optional[int] = None):
     """Returns ``(codes_top int64 [B, max_seq_len], codes_bot int64 [B, max_seq_len, 4])`` on the model's GPU; ``return_logprobs=True`` appends
     ``logprobs`` fp32 [B, max_seq_len, 5]: the log-probability of every code the call feeds forward (the drawn one; the given one where
     ``given_top_code`` forces the top level) under the raw logits of its draw -- temperature 1, no cut-off, so always finite; draw order top,
@@ -233,12 +234,17 @@ def sampling_ihqgpt(model,
     ``share_prompts=True`` (text models): identical prompts among the rows of the pass -- with ``guidance_scale`` the negative rows count, so one negative
     prompt for all is one group -- are prefilled once and handed to their rows (``prompt_groups_of``, ``hqt_set_prompt_groups``).  'exact' returns bit for bit
     what the call returns without it.  ValueError together with ``prefix_codes`` or ``keep_mask``.
+    ``return_report=N`` (0..16; None: no report): appends one ``DrawReport(entropy, rank, top_codes, top_logprobs)`` behind the log-probabilities -- per draw, laid out
+    [B, max_seq_len, 5] as they are, the entropy (nats) of the raw row the code was drawn from, the 0-based rank of the fed-forward code in it and, N >= 1, the N
+    most likely codes with their log-probabilities [..., N] (``hqt_set_draw_report``; T = 1, no cut-off, whatever settings drew the code).  N = 0: entropy and
+    rank only.  Positions below a prefix are NaN / -1.  The weights of the shipped configurations are synthetic: the mechanism and its arithmetic are claimed.
 
     The call is asynchronous and does not read the device's flags: 'split' passes above 256 rows SATURATE activations outside the fp16 range and
     only flag them, and a persistent FAST launch (up to 64 samples) that could not finish on a shared GPU only marks the handle -- call
     ``model.range_check()`` (``hqt_range_check``: raises ``HqtError``) once the codes are needed, as ``InflightSampler.drain`` and ``bench.py`` do.
     """
     spec = model.spec
+    top_n = _report_n(spec, return_report)           # refused here, before an engine is built
     B, cond = _batch_and_cond(model, num_candidates, cond)
     rows, cond, guidance, keep = _guided(model, B, cond, guidance_scale, neg_cond, guidance)
     if rows != B:                                    # the negative half repeats every per-row input of the positive one
@@ -266,12 +272,29 @@ def sampling_ihqgpt(model,
     eng = model.engine(B, max_seq_len, lane, max_prefix=_prefix_room(spec, prefix) or _keep_room(spec, kept, text_prefix))
     if seed is None and noise is None:
         seed = _seed_from_torch()
+    report = None if top_n is None else new_draw_report(B, max_seq_len, 5, top_n, eng.device)
     out = eng.sample(B, cond, max_seq_len, precision=_precision(precision, use_fp16),
                      top_k=(top_k_top, top_k_bot), top_p=(top_p_top, top_p_bot), temperature=softmax_temperature,
                      noise=noise, seed=seed or 0, sample_offset=sample_offset, force_top=force_top, use_graph=use_graph,
                      row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs,
-                     guidance=guidance, keep=kept, **({} if groups is None else {'prompt_groups': groups}))
-    return out if keep == B else tuple(t[:keep] for t in out)          # (codes and log-probabilities are [B, ...]: the positive half)
+                     guidance=guidance, keep=kept, report_out=report, **({} if groups is None else {'prompt_groups': groups}))
+    out = out if report is None else out + (report,)
+    return out if keep == B else tuple(_first_rows(t, keep) for t in out)          # (codes, log-probabilities and the report are [B, ...]: the positive half)
+
+
+def _report_n(spec, return_report) -> Optional[int]:
+    """``return_report`` of the samplers checked on the host: None, or N in [0, 16] and no more than the vocabulary holds."""
+    top_n = check_report_n(return_report)
+    if top_n is not None and top_n > spec.vocab_top:
+        raise ValueError(f'return_report: N={top_n} alternatives, the vocabulary has {spec.vocab_top} codes')
+    return top_n
+
+
+def _first_rows(t, keep: int):
+    """The first ``keep`` rows of a result [B, ...]; a ``DrawReport`` field by field."""
+    if isinstance(t, DrawReport):
+        return DrawReport(*(None if f is None else f[:keep] for f in t))
+    return t[:keep]
 
 
 def _prefix_room(spec, prefix) -> int:
@@ -332,7 +355,8 @@ def sampling_hqtransformer(model,
                            guidance=None,
                            keep_mask=None,
                            kept_codes=None,
-                           share_prompts: bool = False):
+                           share_prompts: bool = False,
+                           return_report: Optional[int] = None):
     """Counterpart of ``hqvae.utils.sampling.sampling_hqtransformer`` (sampling.py:240-307) for the three-level
     HQTransformer: returns ``[codes0 int64 [B, L], codes1 [B, L, 4], codes2 [B, L, 16]]`` on the model's GPU.
     ``top_k`` / ``top_p`` / ``softmax_temperature`` are per-level lists (None = no cut-off); ``cond`` as in
@@ -341,10 +365,12 @@ def sampling_hqtransformer(model,
     as in ``sampling_ihqgpt``), ``return_logprobs`` (appends fp32 [B, L, 21] to the list, as in ``sampling_ihqgpt``), ``guidance_scale`` (a float or
     three, one per level) / ``neg_cond`` / ``guidance`` (guided sampling over 2 B rows, the B positive ones returned, as in ``sampling_ihqgpt``),
     ``keep_mask`` [B, L] / ``kept_codes`` = ``[[B, L], [B, L, 4], [B, L, 16]]`` (kept positions, as in ``sampling_ihqgpt``),
-    ``share_prompts`` (identical prompts of the pass prefilled once, as in ``sampling_ihqgpt``)."""
+    ``share_prompts`` (identical prompts of the pass prefilled once, as in ``sampling_ihqgpt``), ``return_report=N`` (appends a ``DrawReport`` of
+    [B, L, 21(, N)] tensors behind the log-probabilities, as in ``sampling_ihqgpt``)."""
     spec = model.spec
     if spec.levels != 3:
         raise ValueError('sampling_hqtransformer needs the three-level HQTransformer (stage2.type multilevel-hq)')
+    top_n = _report_n(spec, return_report)
     B, cond = _batch_and_cond(model, num_candidates, cond)
     rows, cond, guidance, keep = _guided(model, B, cond, guidance_scale, neg_cond, guidance)
     if rows != B:
@@ -360,11 +386,13 @@ def sampling_hqtransformer(model,
     eng = model.engine(B, max_seq_len, lane, max_prefix=_prefix_room(spec, prefix) or _keep_room(spec, kept))
     if seed is None and noise is None:
         seed = _seed_from_torch()
+    report = None if top_n is None else new_draw_report(B, max_seq_len, 21, top_n, eng.device)
     out = eng.sample3(B, cond, max_seq_len, precision=_precision(precision, use_fp16), top_k=top_k, top_p=top_p,
                       temperature=softmax_temperature, noise=noise, seed=seed or 0, sample_offset=sample_offset, use_graph=use_graph,
                       row_seeds=row_seeds, row_offsets=row_offsets, row_samplers=row_samplers, prefix=prefix, return_logprobs=return_logprobs,
-                      guidance=guidance, keep=kept, **({} if groups is None else {'prompt_groups': groups}))
-    return list(out if keep == B else (t[:keep] for t in out))
+                      guidance=guidance, keep=kept, report_out=report, **({} if groups is None else {'prompt_groups': groups}))
+    out = out if report is None else out + (report,)
+    return list(out if keep == B else (_first_rows(t, keep) for t in out))
 
 
 def rearrange_levels(codes: List[torch.Tensor], top_resolution: int) -> tuple:

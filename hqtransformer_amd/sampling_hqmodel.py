@@ -58,6 +58,9 @@ def build_parser() -> argparse.ArgumentParser:
                         'resolution * G / top_resolution.  Needs --canvas-stride.  The mechanism is claimed, not the quality of the picture')
     p.add_argument('--canvas-stride', type=int, default=None, metavar='S', help='with --canvas-grid: cells the window moves by (1 <= S < top_resolution, (G - top_resolution) % S == 0)')
     p.add_argument('--negative-class', type=int, default=None, metavar='C', help='with --guidance-scale: the class id to push away from (required: there is no "null" class)')
+    p.add_argument('--report-top', type=int, default=None, metavar='N',
+                   help='also write report.npz: per draw the entropy of the distribution the code was drawn from, the rank of the code in it and the N most likely '
+                        'codes with their log-probabilities (0 .. 16; 0: entropy and rank only).  Plain sampling only; the other outputs do not change')
     return p
 
 
@@ -142,7 +145,11 @@ def sample_pixels(model: ImageGPT2, args, num_candidates: int, cond) -> np.ndarr
     if getattr(args, 'share_prompts', False):      # --share-prompts (text driver): identical prompts of the pass are prefilled once
         sampler['share_prompts'] = True
     best_of = getattr(args, 'best_of', 1)
-    if best_of > 1:                      # --best-of N: N x num_candidates per condition in one pass, the num_candidates most likely kept
+    report_top = getattr(args, 'report_top', None)
+    if report_top is not None:           # --report-top N: the report of every draw travels behind the codes and is collected for report.npz
+        codes = sample_codes(model.stage2, num_candidates, cond, return_report=report_top, **sampler)
+        args.reports = getattr(args, 'reports', []) + [codes.pop()]
+    elif best_of > 1:                      # --best-of N: N x num_candidates per condition in one pass, the num_candidates most likely kept
         codes, _ = sample_best_of(model.stage2, cond, best_of * num_candidates, num_candidates, **sampler)
     else:
         codes = sample_codes(model.stage2, num_candidates, cond, **sampler)
@@ -181,6 +188,11 @@ def main(argv=None):
             canvas_windows(args.canvas_grid, args.top_resolution, args.canvas_stride)
         except ValueError as e:
             raise SystemExit(f'--canvas-grid / --canvas-stride: {e}')
+    if args.report_top is not None:
+        if not 0 <= args.report_top <= 16:
+            raise SystemExit('--report-top must lie in [0, 16]')
+        if args.complete_from is not None or args.canvas_grid is not None:
+            raise SystemExit('--report-top reports plain sampling: not together with --complete-from or --canvas-grid')
     set_seed(args.seed)
     os.makedirs(args.result_path, exist_ok=True)
     model = load_model(args.model_path).eval()
@@ -192,6 +204,15 @@ def main(argv=None):
             pixels = sample_pixels(model, args, n, cls_idx)
             save_pickle(os.path.join(args.result_path, f'samples_({cls_idx + 1}_{num_batches}).pkl'), pixels)
             np.savez(os.path.join(args.result_path, f'targets_({cls_idx + 1}_{num_batches}).npz'), targets=targets.cpu().numpy())
+    write_report(args)
+
+
+def write_report(args) -> None:
+    """``--report-top``: report.npz beside the samples -- the ``DrawReport`` fields of all batches in the order they were sampled, [images, positions, draws(, N)]."""
+    reports = getattr(args, 'reports', None)
+    if reports:
+        fields = {f: torch.cat([getattr(r, f) for r in reports]).cpu().numpy() for f in reports[0]._fields if getattr(reports[0], f) is not None}
+        np.savez(os.path.join(args.result_path, 'report.npz'), **fields)
 
 
 if __name__ == '__main__':

@@ -226,6 +226,38 @@ int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler* rows);
  * "code_logprob").  Forcing every level to given codes makes the call a scorer of those codes, at the cost of its n_steps decode steps. */
 int hqt_set_logprob_out(hqt_handle* h, float* logprobs);
 
+/* hqt_set_draw_report -- no reference counterpart (LLM sampling APIs call the last two fields top_logprobs).  What the distribution behind every draw looked
+ * like, in a few numbers per draw where `logits_out` writes the whole row: how flat it was, where the fed-forward code stood in it, which codes were the
+ * alternatives.  All pointers are DEVICE pointers, each [B, n_steps, draws] as the hqt_set_logprob_out buffer (draws = 5, or 21 with three code levels; draw
+ * order as in `noise`), the two top arrays with top_n entries per draw; a NULL entropy / rank is not written, top_n = 0 writes no top arrays.  STAGED on the
+ * handle exactly like hqt_set_logprob_out (a lane from hqt_clone has its own): the next hqt_sample / hqt_sample_l3 / hqt_sample_prefix / hqt_sample_prefix_l3
+ * or hqt_score on that handle takes it and clears it, whether that call succeeds or not; r = NULL, or a struct with nothing to write (all pointers NULL,
+ * top_n = 0), clears.  HQT_ERR_INVALID, naming the field: a NULL handle, top_n outside [0, HQT_REPORT_MAX_TOP], top_n > 0 with top_codes or top_logprobs
+ * NULL, top_n = 0 with either of them set; the taking call fails with HQT_ERR_INVALID when its vocabulary is smaller than top_n.
+ * Over the RAW fp32 logits row l of the draw (with a guidance pair the guided row, equal in both rows), at T = 1 without cut-off whatever settings drew the
+ * code, with m = max l and S = sum_i expf(l_i - m) -- the m and S of the log-probability, from the same code in the same reduction order -- and c the code the
+ * call feeds forward (forced where a level is forced, clamped into the vocabulary):
+ *   top_codes[j]    the j-th index when indices are sorted by (l descending, index ascending); float compares, so -0.0 ties with +0.0 and the lower index wins
+ *   top_logprobs[j] (l[top_codes[j]] - m) - logf(S): bit for bit the hqt_set_logprob_out entry of a call that feeds top_codes[j] forward
+ *   rank            #{i : l_i > l_c} + #{i < c : l_i == l_c}, 0-based; rank < top_n implies top_codes[rank] == c
+ *   entropy         logf(S) - T / S in nats, T = sum_i expf(l_i - m) (l_i - m) reduced in the order of S (per thread a pairwise tree, the wave's xor
+ *                   butterfly, four wave sums as (w0 + w1) + (w2 + w3)); IEEE expf / logf and an IEEE division in every precision
+ * Every value depends on the row's bits and on V alone, never on B, the batch row, or eager versus replayed.  Entries are written exactly where a staged
+ * log-probability buffer is written and nowhere else: behind every draw, at kept positions and forced levels as there, not for positions < prefix_len, not for
+ * an idle row of a rolling pass.  One launch per draw in code_logprob's place (timing slot "draw_report"); with a log-probability buffer staged as well that
+ * one kernel writes both (no "code_logprob" launch; the log-probabilities keep their bits).  The pointers and top_n are part of the graph key; a call with
+ * nothing staged launches exactly what it launched before.  hqt_score writes the report of the GIVEN codes for all (pair, slot) rows of a depth chunk in one
+ * launch next to its log-probabilities.  Finite logits are assumed. */
+#define HQT_REPORT_MAX_TOP 16
+typedef struct {
+    float*   entropy;       /* device, fp32  [B, n_steps, draws]         or NULL */
+    int32_t* rank;          /* device, int32 [B, n_steps, draws]         or NULL */
+    int32_t  top_n;         /* 0 .. HQT_REPORT_MAX_TOP                            */
+    int32_t* top_codes;     /* device, int32 [B, n_steps, draws, top_n]  (top_n > 0) */
+    float*   top_logprobs;  /* device, fp32  [B, n_steps, draws, top_n]  (top_n > 0) */
+} hqt_draw_report;          /* 40 bytes */
+int hqt_set_draw_report(hqt_handle* h, const hqt_draw_report* r);
+
 /* hqt_set_guidance -- no reference counterpart: the reference trains without condition dropout and draws every image under one condition.  Guided sampling
  * runs an image under TWO conditions, as two rows of one pass (both count against max_batch), and draws every code of both rows from
  *   g = l_pos + (scale - 1) * (l_pos - l_neg)
@@ -441,7 +473,9 @@ int hqt_sample_prefix_l3(hqt_handle* h, int B, const int64_t* cond, const hqt_sa
  * Runs eagerly on `stream`; touches neither the graph cache nor its key, leaves the step state at (0, 0) and the K/V cache and the code
  * buffers overwritten: a sampling call afterwards draws what it drew before.  The handle needs hqt_set_max_prefix(h, >= n - 1) (n = 1: none).
  * HQT_ERR_STATE: not finalized, max_prefix too small, a precision whose layout the handle was built without, a staged row-sampler table,
- * pair table or log-probability buffer (they belong to a sampling call; hqt_score clears them).  HQT_ERR_INVALID: NULL logprobs / codes,
+ * pair table or log-probability buffer (they belong to a sampling call; hqt_score clears them).  A staged hqt_set_draw_report IS taken: entry
+ * (b, t, d) of the report describes the row of logprobs entry (b, t, d), c being the given code (timing slot "draw_report", one launch per
+ * level and chunk).  HQT_ERR_INVALID: NULL logprobs / codes, a staged report whose top_n exceeds the vocabulary,
  * B or n out of range, the 'top2mid2bot' head (21 causal sub-steps: score it stepwise, hqt_sample_l3 with forced codes), three code levels
  * with text conditioning.
  * hqt_set_score_chunk -- pairs per depth chunk, between hqt_create and hqt_finalize_weights (lanes inherit it): sizes the depth workspace
