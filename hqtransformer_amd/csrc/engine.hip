@@ -154,8 +154,11 @@ struct hqt_handle {
     size_t guide_room() const { return (size_t)std::max(1, cfg.max_batch / 2); }      // a row is in at most one pair
     unsigned char* keep_mask = nullptr;       // [max_batch * max_steps] mask of the current call
     int* group_of_row = nullptr;              // [max_batch] group table of the current call
-    int* row_pos = nullptr;                   // [2 * max_batch] rolling pass (hqt_set_row_positions): [0, max_batch) the position every row stands at, moved on by
-                                              // advance_rows between the steps of a call; [max_batch, 2 max_batch) the table as the call received it (what it copies out)
+    int* row_pos = nullptr;                   // [3 * max_batch] rolling pass (hqt_set_row_positions): [0, max_batch) the position every row stands at, moved on by
+                                              // advance_rows between the steps of a call; [max_batch, 2 max_batch) the table as the call received it (what it copies out);
+                                              // [2 max_batch, 3 max_batch) the join table of a text pass: 0 for a row that joins in this call, -1 for every other
+    int* row_pos_received() const { return row_pos + cfg.max_batch; }
+    int* row_pos_join() const { return row_pos + 2 * (size_t)cfg.max_batch; }
     // What the hqt_set_* calls leave for the next hqt_sample / hqt_sample_l3 (or prefix entry point) of this handle, which takes all of it
     struct Staged {
         std::vector<hqt_row_sampler> row_set;     // hqt_set_row_samplers: host table
@@ -176,12 +179,14 @@ struct hqt_handle {
     } staged;
     Staged take_staged() { Staged s = std::move(staged); staged = Staged(); return s; }
     void clear_staged() { staged = Staged(); }
-    // staging of a shared prefill, sized (grown) by hqt_set_prompt_groups and by nothing else: K and V of [n_layers][pg_cap][ctx_len_txt][D] at 4 bytes
-    // per element (any mode's activation type fits), and the [max_batch, D] fp32 rows the fan-out gathers for the depth head of position 0
+    // staging of a shared prefill, sized (grown) by hqt_set_prompt_groups and hqt_set_max_joins (reserve_prompt_staging) and by nothing else: K and V of
+    // [n_layers][pg_cap][ctx_len_txt][D] at 4 bytes per element (any mode's activation type fits), and the [max_batch, D] fp32 rows the fan-out gathers for
+    // the depth head of position 0
     void *pg_k = nullptr, *pg_v = nullptr;
     float* pg_x = nullptr;
     int pg_cap = 0;                           // prompts the staging holds
     size_t pg_bytes = 0;                      // bytes of pg_k (= pg_v)
+    int max_joins = 0;                        // hqt_set_max_joins: rows that may join a rolling pass of a text handle in one call (0: such a pass is refused)
     // the pass a segment stopped in: what a continuation must match, and `pos`, the position it goes on from (the step state says pos over t_live keys)
     struct Paused { bool live = false; int B = 0, n_steps = 0, levels = 0, precision = 0, pos = 0; } paused;
     // the rolling pass the last hqt_set_row_positions call left: what the next one must match, and per slot the position it draws next (-1: empty)
@@ -249,6 +254,35 @@ static int dev_alloc(hqt_handle* h, void** p, size_t bytes, bool workspace) {
     if (poison && workspace && bytes) HIPCHK(hipMemset(*p, 0xFF, bytes));
     h->owned.push_back(*p);
     if (workspace) h->workspace_bytes += bytes;
+    return HQT_OK;
+}
+
+// The one place that allocates the staging of a prompt prefill over fewer rows than the pass has (hqt_handle::pg_*): room for `n_groups` prompts, grown and never
+// shrunk (a larger need frees the old pair once the device has drained, a smaller one reuses it), and with the first need the gathered x rows.  Those start as
+// zeros: the join phase of a rolling pass writes only the joiners' rows and runs the depth head over all of them.  The caller has set the device.
+static int reserve_prompt_staging(hqt_handle* h, int n_groups) {
+    const hqt_config& c = h->cfg;
+    if (!h->pg_x) {
+        CHK(dev_alloc(h, (void**)&h->pg_x, (size_t)c.max_batch * c.embed_dim * 4, true));
+        HIPCHK(hipMemset(h->pg_x, 0, (size_t)c.max_batch * c.embed_dim * 4));
+        HIPCHK(hipDeviceSynchronize());          // (the calls that read it run on the caller's streams)
+    }
+    if (n_groups <= h->pg_cap) return HQT_OK;
+    if (h->pg_k) {
+        HIPCHK(hipDeviceSynchronize());          // an earlier call may still be reading the old pair
+        for (void** p : {&h->pg_k, &h->pg_v}) {
+            HIPCHK(hipFree(*p));
+            h->owned.erase(std::remove(h->owned.begin(), h->owned.end(), *p), h->owned.end());
+            h->workspace_bytes -= h->pg_bytes;
+            *p = nullptr;
+        }
+        h->pg_cap = 0;
+    }
+    const size_t bytes = (size_t)c.n_layers * n_groups * c.ctx_len_txt * c.embed_dim * 4;
+    CHK(dev_alloc(h, &h->pg_k, bytes, true));
+    CHK(dev_alloc(h, &h->pg_v, bytes, true));
+    h->pg_bytes = bytes;
+    h->pg_cap = n_groups;
     return HQT_OK;
 }
 
@@ -583,7 +617,7 @@ static int alloc_workspace(hqt_handle* hp) {
         CHK(dev_alloc(h.get(), (void**)&h->guide, h->guide_room() * sizeof(GuidePair), true));
         CHK(dev_alloc(h.get(), (void**)&h->keep_mask, B * (size_t)c.max_steps, true));
         CHK(dev_alloc(h.get(), (void**)&h->group_of_row, B * sizeof(int), true));
-        CHK(dev_alloc(h.get(), (void**)&h->row_pos, 2 * B * sizeof(int), true));
+        CHK(dev_alloc(h.get(), (void**)&h->row_pos, 3 * B * sizeof(int), true));
         CHK(dev_alloc(h.get(), (void**)&h->cond_buf, B * (size_t)std::max(1, c.cond_type == HQT_COND_TEXT ? c.ctx_len_txt : 1) * 8, true));
         CHK(dev_alloc(h.get(), (void**)&h->codes_top, B * (size_t)c.max_steps * 8, true));
         CHK(dev_alloc(h.get(), (void**)&h->codes_bot, B * (size_t)c.max_steps * 4 * 8, true));
@@ -671,7 +705,8 @@ extern "C" int hqt_clone(hqt_handle* src, hqt_handle** out) {
     h->pbody.d_phases = nullptr; h->pfull.d_phases = nullptr;      // phase tables hold workspace pointers: bound per handle (persist_bind)
     h->persist_used = false; h->persist_tripped = false; h->capture_persist = false; h->graph_has_persist = false;
     h->policy = HQT_POLICY_LATENCY;              // a lane's tile choice never depends on what the root ran when it was cloned
-    const int rc = alloc_workspace(h.get());
+    int rc = alloc_workspace(h.get());
+    if (rc == HQT_OK && h->max_joins > 0) rc = reserve_prompt_staging(h.get(), h->max_joins);      // (hqt_set_max_joins on the root: the lane joins as many, in a staging of its own)
     if (rc != HQT_OK) { for (void* p : h->owned) hipFree(p); return rc; }
     root->n_clones++;
     *out = h.release();
@@ -1198,9 +1233,24 @@ struct SampleCtx {
     int roll_k = 0;                              // ... and the steps the call runs (it then is positions [0, roll_k) of the launch loop: start = 0, stop = roll_k)
     const int* row_pos = nullptr;                // ... and its device copy (h->row_pos) that the launches of a rolling call read, NULL otherwise
     const int64_t* roll_prev[3] = {nullptr, nullptr, nullptr};   // ... and the caller's out_*: where the codes of position pos[b] - 1 of every continued row are read
+    int n_join = 0;                              // ... on a text handle: the rows with roll[b] == 0, whose prompt prefill (the join phase) draws position 0 in front of the steps
     hipStream_t st;
     Mode md;
 };
+
+// a text handle that has not opted in (hqt_set_max_joins): the sentence the rolling entry points have always refused it with, and where to go
+static const char ROLLING_TEXT_REFUSAL[] =
+    "hqt_set_row_positions: a rolling pass on a text-conditional handle is not built (a row that joins at position 0 needs a prompt prefill of its own)"
+    " unless the handle has sized one: hqt_set_max_joins(h, J > 0) allocates the staging for J joining rows per call";
+
+// What a rolling call leaves of the position a row presented (-1: an empty slot): where the slot stands behind it, -1 once its last position is drawn.  On a
+// text handle a joining row (position 0) is moved on by the join phase AND by the k steps: 1 + k.  The handle's record, what the next call must present and
+// the copy-out all follow this rule.
+static int rolled_to(const hqt_config& cf, int pos, int k, int n) {
+    if (pos < 0) return -1;
+    const int next = pos + k + (cf.cond_type == HQT_COND_TEXT && pos == 0 ? 1 : 0);
+    return next < n ? next : -1;
+}
 
 // State-dict key of a stage-2 tensor: the code below names tensors as iHQGPT does; the three-level HQTransformer keeps
 // the same roles under indexed names (hqtransformer.py:24-205).
@@ -1755,7 +1805,10 @@ static int run_decode_step(hqt_handle* h, const SampleCtx& c) {      // one KV-c
         if (dln_ok(h, c, h->body[0], c.B)) { e.xpk = h->xpk; e.pk_mb = packed_mb(c.B); h->nparts = 1; }
         HIPCHK(launch_embed_step(e, c.st));
     }
-    CHK(run_position(h, c, 1, 0, true));
+    // a rolling pass of a text handle: row b stands behind its prompt, at cache row ctx_len_txt - 1 + pos[b] -- where the plain text call's step state puts
+    // position pos[b]; the offset is a constant of the handle (an idle row stores at row ctx_len_txt - 1 of its own, dead slot and is read by nothing)
+    const int behind_prompt = c.row_pos && h->cfg.cond_type == HQT_COND_TEXT ? h->cfg.ctx_len_txt - 1 : 0;
+    CHK(run_position(h, c, 1, behind_prompt, true));
     if (c.row_pos) HIPCHK(launch_advance_rows(h->row_pos, c.B, c.n_steps, c.st));      // a rolling pass: every live row moves on; the step state is not read
     else HIPCHK(launch_advance_step(h->state, 1, c.st));
     return HQT_OK;
@@ -1771,7 +1824,7 @@ static_assert(alignof(RowKey) == 8 && alignof(RowSampler) == 4 && alignof(GuideP
 static RingSlot ring_slot(const hqt_handle* h, RowKey* base) {      // (base null: only `bytes`, what a slot needs)
     const size_t B = h->cfg.max_batch;
     const size_t samplers = B * sizeof(RowKey), pairs = samplers + B * sizeof(RowSampler), groups = pairs + h->guide_room() * sizeof(GuidePair),
-                 pos = groups + B * sizeof(int32_t), keep = pos + B * sizeof(int32_t);
+                 pos = groups + B * sizeof(int32_t), keep = pos + 3 * B * sizeof(int32_t);      // pos: the three tables of hqt_handle::row_pos, in its order
     RingSlot r{};
     r.bytes = keep + B * h->cfg.max_steps;
     if (!base) return r;
@@ -1861,8 +1914,7 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     }
     if (c.roll) {
         const int n = c.n_steps;
-        if (cf.cond_type == HQT_COND_TEXT)
-            return fail(HQT_ERR_INVALID, "hqt_set_row_positions: a rolling pass on a text-conditional handle is not built (a row that joins at position 0 needs a prompt prefill of its own)");
+        if (cf.cond_type == HQT_COND_TEXT && h->max_joins < 1) return fail(HQT_ERR_INVALID, "%s", ROLLING_TEXT_REFUSAL);      // (hqt_set_max_joins(0) behind the staging call)
         if (c.with_prefix) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: the staged positions were taken by a prefix entry point; a rolling pass with a code prefix is not built (hqt_sample / hqt_sample_l3 take the table)");
         if (c.seg) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged segment (hqt_set_segment) is not built: the k of the table is the call's span");
         if (c.keep) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged keep table (hqt_set_keep_mask) is not built");
@@ -1895,6 +1947,13 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
                                                     "overwritten its cache since): every entry must be 0 (join) or -1 (empty)", b, c.roll[b]);
             if (want < 0) return fail(HQT_ERR_STATE, "hqt_set_row_positions: row %d continues at position %d, but the slot is empty in the rolling pass (0 joins, -1 stays empty)", b, c.roll[b]);
             return fail(HQT_ERR_STATE, "hqt_set_row_positions: row %d continues at position %d, but the slot stands at position %d of the rolling pass", b, c.roll[b], want);
+        }
+        if (cf.cond_type == HQT_COND_TEXT) {     // the rows that join draw position 0 in a prompt prefill of their own, in front of the steps (sample_run)
+            for (int b = 0; b < B; ++b) c.n_join += c.roll[b] == 0;
+            if (c.n_join > h->max_joins)
+                return fail(HQT_ERR_INVALID, "hqt_set_row_positions: %d rows join at position 0 in this call, the handle's staging holds the prompts of max_joins=%d (hqt_set_max_joins)", c.n_join, h->max_joins);
+            if (c.n_join > h->pg_cap || (c.n_join && (!h->pg_k || !h->pg_v || !h->pg_x)))
+                return fail(HQT_ERR_STATE, "hqt_set_max_joins: the staging buffer holds %d prompts, %d rows join", h->pg_cap, c.n_join);
         }
         c.start = 0; c.stop = c.roll_k;
     }
@@ -1999,13 +2058,16 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
         for (int b = 0; b < B; ++b) any = any || c.roll[b] >= 0;
         if (any) {                               // (only empty slots: legal, draws nothing, launches nothing)
             CHK(sample_run(h, c));
-            for (int i = 0; i < c.levels; ++i)
-                HIPCHK(launch_copy_row_positions(codes[i], out[i], h->row_pos + cf.max_batch, B, c.n_steps, LEVEL_WIDTH[i], 0, c.roll_k, c.st));
+            for (int i = 0; i < c.levels; ++i) {
+                HIPCHK(launch_copy_row_positions(codes[i], out[i], h->row_pos_received(), B, c.n_steps, LEVEL_WIDTH[i], 0, c.roll_k, c.st));
+                // a joining row of a text pass drew positions [0, 1 + k): its last one through the join table (0 for the joiners, -1 for every other row)
+                if (c.n_join) HIPCHK(launch_copy_row_positions(codes[i], out[i], h->row_pos_join(), B, c.n_steps, LEVEL_WIDTH[i], c.roll_k, c.roll_k + 1, c.st));
+            }
         }
         hqt_handle::Rolling& r = h->rolling;
         r.live = true; r.B = B; r.n_steps = c.n_steps; r.levels = c.levels; r.precision = c.precision;
         r.next.assign(B, -1);
-        for (int b = 0; b < B; ++b) if (c.roll[b] >= 0 && c.roll[b] + c.roll_k < c.n_steps) r.next[b] = c.roll[b] + c.roll_k;
+        for (int b = 0; b < B; ++b) r.next[b] = rolled_to(cf, c.roll[b], c.roll_k, c.n_steps);
         r.live = std::any_of(r.next.begin(), r.next.end(), [](int32_t p) { return p >= 0; });      // every slot empty: the pass is over, nothing is left to match
         return HQT_OK;
     }
@@ -2095,8 +2157,8 @@ extern "C" int hqt_set_row_samplers(hqt_handle* h, int n, const hqt_row_sampler*
     return HQT_OK;
 }
 
-// The one place that allocates for shared prompts: the staging K/V of n_groups prompts (grown, never shrunk: a larger table frees the old pair once
-// the device has drained, a smaller one reuses it) and, with the first table, the gathered x rows.  A sampling call allocates nothing.
+// Stages the group table of a shared prefill and sizes the staging for its n_groups prompts (reserve_prompt_staging: grown, never shrunk).  A sampling call
+// allocates nothing.
 extern "C" int hqt_set_prompt_groups(hqt_handle* h, int B, int n_groups, const int32_t* group_of_row) {
     if (!h) return fail(HQT_ERR_INVALID, "null handle");
     h->staged.groups.clear();
@@ -2112,26 +2174,24 @@ extern "C" int hqt_set_prompt_groups(hqt_handle* h, int B, int n_groups, const i
             return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups: group_of_row[%d]=%d outside [0, n_groups=%d)", b, group_of_row[b], n_groups);
     if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
     ON_DEVICE(h);
-    if (!h->pg_x) CHK(dev_alloc(h, (void**)&h->pg_x, (size_t)c.max_batch * c.embed_dim * 4, true));
-    if (n_groups > h->pg_cap) {
-        if (h->pg_k) {
-            HIPCHK(hipDeviceSynchronize());      // an earlier call may still be reading the old pair
-            for (void** p : {&h->pg_k, &h->pg_v}) {
-                HIPCHK(hipFree(*p));
-                h->owned.erase(std::remove(h->owned.begin(), h->owned.end(), *p), h->owned.end());
-                h->workspace_bytes -= h->pg_bytes;
-                *p = nullptr;
-            }
-            h->pg_cap = 0;
-        }
-        const size_t bytes = (size_t)c.n_layers * n_groups * c.ctx_len_txt * c.embed_dim * 4;
-        CHK(dev_alloc(h, &h->pg_k, bytes, true));
-        CHK(dev_alloc(h, &h->pg_v, bytes, true));
-        h->pg_bytes = bytes;
-        h->pg_cap = n_groups;
-    }
+    CHK(reserve_prompt_staging(h, n_groups));
     h->staged.groups_G = n_groups;
     h->staged.groups.assign(group_of_row, group_of_row + B);
+    return HQT_OK;
+}
+
+// Opt-in sizing of rolling passes on a text handle: the staging that the prompt prefill of up to max_joins joining rows per call needs (the buffers of
+// hqt_set_prompt_groups, sized to the larger of the two needs).  0 switches rolling off again and frees nothing.
+extern "C" int hqt_set_max_joins(hqt_handle* h, int max_joins) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    const hqt_config& c = h->cfg;
+    if (!c.has_stage2 || c.cond_type != HQT_COND_TEXT)
+        return fail(HQT_ERR_INVALID, "hqt_set_max_joins: the handle is not text-conditional (cond_type %d): a row of any other model joins a rolling pass without a prefill", c.cond_type);
+    if (max_joins < 0 || max_joins > c.max_batch) return fail(HQT_ERR_INVALID, "hqt_set_max_joins: max_joins=%d outside [0, max_batch=%d]", max_joins, c.max_batch);
+    if (h->rolling.live) return fail(HQT_ERR_STATE, "hqt_set_max_joins: this handle holds a rolling pass (hqt_set_row_positions); finish it first");
+    ON_DEVICE(h);
+    if (max_joins > 0) CHK(reserve_prompt_staging(h, max_joins));
+    h->max_joins = max_joins;
     return HQT_OK;
 }
 
@@ -2142,8 +2202,7 @@ extern "C" int hqt_set_row_positions(hqt_handle* h, int B, const int32_t* pos, i
     if (B == 0 || !pos) return HQT_OK;
     const hqt_config& c = h->cfg;
     if (!c.has_stage2) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: the handle was created without stage 2");
-    if (c.cond_type == HQT_COND_TEXT)
-        return fail(HQT_ERR_INVALID, "hqt_set_row_positions: a rolling pass on a text-conditional handle is not built (a row that joins at position 0 needs a prompt prefill of its own)");
+    if (c.cond_type == HQT_COND_TEXT && h->max_joins < 1) return fail(HQT_ERR_INVALID, "%s", ROLLING_TEXT_REFUSAL);
     if (B < 1 || B > c.max_batch) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: B=%d outside [1, max_batch=%d]", B, c.max_batch);
     if (k < 1 || k > c.max_steps) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: k=%d outside [1, n_steps] (n_steps <= max_steps = %d)", k, c.max_steps);
     for (int b = 0; b < B; ++b)
@@ -2437,9 +2496,25 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         if (c.guide) CHK(ring_send(ring.pairs, c.guide, (size_t)c.n_guide, h->guide, c.st));
         if (c.keep) CHK(ring_send(ring.keep, c.keep, (size_t)B * c.n_steps, h->keep_mask, c.st));
         if (c.groups) CHK(ring_send(ring.groups, c.groups, (size_t)B, h->group_of_row, c.st));
-        if (c.roll) {             // the positions the rows stand at (moved on between the steps) and, behind them, the table as received (what sample_call copies out)
+        if (c.roll && !c.n_join) {      // the positions the rows stand at (moved on between the steps) and, behind them, the table as received (what sample_call copies out)
             CHK(ring_send(ring.pos, c.roll, (size_t)B, h->row_pos, c.st));
-            CHK(ring_send(ring.pos, (const int32_t*)nullptr, (size_t)B, h->row_pos + cf.max_batch, c.st));
+            CHK(ring_send(ring.pos, (const int32_t*)nullptr, (size_t)B, h->row_pos_received(), c.st));
+        } else if (c.roll) {
+            // a text pass with joining rows: the live table has them behind the join phase already (position 1; n_steps = 1: finished, idle in the steps), the
+            // join table says 0 for them and -1 for every other row, and the group table of the join's fan-out numbers them in ascending slot order
+            int32_t *live = ring.pos, *received = ring.pos + cf.max_batch, *join = ring.pos + 2 * (size_t)cf.max_batch;
+            int g = 0;
+            for (int b = 0; b < B; ++b) {
+                const bool joins = c.roll[b] == 0;
+                received[b] = c.roll[b];
+                live[b] = joins ? (c.n_steps > 1 ? 1 : -1) : c.roll[b];
+                join[b] = joins ? 0 : -1;
+                ring.groups[b] = joins ? g++ : -1;
+            }
+            CHK(ring_send(live, (const int32_t*)nullptr, (size_t)B, h->row_pos, c.st));
+            CHK(ring_send(received, (const int32_t*)nullptr, (size_t)B, h->row_pos_received(), c.st));
+            CHK(ring_send(join, (const int32_t*)nullptr, (size_t)B, h->row_pos_join(), c.st));
+            CHK(ring_send(ring.groups, (const int32_t*)nullptr, (size_t)B, h->group_of_row, c.st));
         }
         CHK(ring_sent(h, slot, c.st));
     }
@@ -2455,6 +2530,36 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         if (c.feed[i] == own[i]) HIPCHK(launch_copy_row_positions(c.roll_prev[i], c.out[i], h->row_pos + cf.max_batch, B, c.n_steps, LEVEL_WIDTH[i], -1, 0, c.st));
     if (c.start > 0) {
         // a continuation (hqt_set_segment): no prefill -- the cache holds the prompt rows and every position below start
+    } else if (c.roll) {
+        // A rolling pass runs no prefill over its rows; on a text handle the J rows that join run the JOIN PHASE, the shared-prompt block below with the
+        // joiners as the groups: their prompts (gathered from cond [B, T] through the group table) through the body blocks into the staging, the fan-out into
+        // the joiners' cache slots and gathered rows alone, then the depth head over all B gathered rows under the join table -- the joiners draw position 0 under
+        // their own key, sampler row and noise slice, every other row is idle there (it computes on the finite row it was left with and writes nothing).
+        // The steps below find the joiners at position 1 of the live table, behind ctx_len_txt cache rows (run_decode_step).
+        if (c.n_join) {
+            const int T = cf.ctx_len_txt, J = c.n_join, D = cf.embed_dim;
+            SampleCtx cg = c;
+            cg.B = J;
+            cg.row_pos = nullptr;                        // (the prefill of J prompts knows no positions)
+            HIPCHK(launch_embed_text_rows(c.cond, h->group_of_row, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, B, J, T, D, c.st, cf.vocab_txt));
+            const KvStage stage{h->pg_k, h->pg_v};
+            bool pfull = false;
+            CHK(run_body(h, cg, T, 0, false, false, &pfull, &stage));
+            CHK(fold_pending(h, cg, J * T));
+            {
+                Timed t(h, "prompt_fanout", c.st);
+                const FanoutArgs fa{h->pg_k, h->pg_v, h->kcache, h->vcache, h->x, h->pg_x, h->group_of_row, cf.n_layers, B, J, T, D,
+                                    D * (int)c.md.act_sz(), cf.max_batch, h->Tmax};
+                HIPCHK(launch_prompt_fanout(fa, c.st));
+            }
+            SampleCtx cj = c;
+            cj.row_pos = h->row_pos_join();
+            float* const x_body = h->x;
+            h->x = h->pg_x;
+            const int rc = run_depth_head(h, cj, 1, false);
+            h->x = x_body;
+            CHK(rc);
+        }
     } else if (cf.cond_type == HQT_COND_TEXT && c.groups) {
         const int T = cf.ctx_len_txt;
         // Shared prompts (hqt_set_prompt_groups; P = 0, checked by sample_call): the prompt rows of a sample depend on nothing but its prompt, so the

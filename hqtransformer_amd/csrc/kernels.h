@@ -34,7 +34,8 @@ struct EmbedArgs {
     const float* tok_l2;         // [V, D] tok_emb_levels.2
     const int64_t* codes_l2;     // [B, n_steps, 16]
     int V, n_classes;            // table sizes for the index clamp (0: unchecked)
-    const int* row_pos;          // rolling pass (embed_step only): sample b stands at row_live(row_pos, b) in place of state->step; NULL: the step state
+    const int* row_pos;          // rolling pass (embed_step only): sample b stands at row_live(row_pos, b) in place of state->step; NULL: the step state.
+                                 // An idle row (row_pos[b] < 0) gets a row of zeros: sos (NULL on a text handle), cond and the codes are not read for it
 };
 hipError_t launch_embed_step(const EmbedArgs& a, hipStream_t st);
 // prefix prefill: x[b * stride + row_off + j] = body input row step_off + j of sample b, j < rows (row 0: sos; row s: position s - 1's codes),
@@ -48,6 +49,11 @@ hipError_t launch_copy_kept(const int64_t* src, int64_t* dst, const unsigned cha
 // text prompt: x[b * rows_per_sample + t, :] = tok_emb_txt[cond[b, t]] + pos_emb_txt[t]
 hipError_t launch_embed_text(const int64_t* cond, const float* tok, const float* pos, float* x, int B, int T, int D,
                              hipStream_t st, int vocab = 0, int rows_per_sample = 0);      // rows_per_sample 0: T
+
+// the prompts of the rows that join a rolling pass: x[g * T + t, :] = tok_emb_txt[cond[b, t]] + pos_emb_txt[t] for every row b of cond [B, T] whose
+// g = group_of_row[b] (device, [B]) lies in [0, G); other rows are neither read nor written
+hipError_t launch_embed_text_rows(const int64_t* cond, const int* group_of_row, const float* tok, const float* pos, float* x, int B, int G, int T, int D,
+                                  hipStream_t st, int vocab);
 
 // Shared prompts (hqt_set_prompt_groups): the prefill ran over G distinct prompts into a staging K/V of [n_layers][G][T][row_bytes]; one launch hands
 // every row b of the pass the prompt of its group g = group_of_row[b] (device, B entries):

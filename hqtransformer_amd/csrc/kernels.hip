@@ -126,7 +126,9 @@ __global__ __launch_bounds__(256) void embed_step_kernel(EmbedArgs a) {
     __shared__ float red[4];
     const int b = blockIdx.x;
     float* x = a.x + (long long)b * a.D;
-    embed_row(a, b, step_of(a.state, a.row_pos, b), x);
+    // an idle row of a rolling pass (workgroup-uniform) has no input: zeros, without a read of sos (NULL on a text handle), cond or the codes
+    if (row_idle(a.row_pos, b)) { for (int d = threadIdx.x; d < a.D; d += blockDim.x) x[d] = 0.0f; }
+    else embed_row(a, b, step_of(a.state, a.row_pos, b), x);
     if (a.xpk) { __syncthreads(); emit_packed_row(x, b, a.D, a.xpk, a.pk_mb, a.parts, red); }
 }
 hipError_t launch_embed_step(const EmbedArgs& a, hipStream_t st) {
@@ -190,6 +192,23 @@ hipError_t launch_embed_text(const int64_t* cond, const float* tok, const float*
     if (rows_per_sample == 0) rows_per_sample = T;
     if (rows_per_sample < T) return hipErrorInvalidValue;
     embed_text_kernel<<<B * T, 256, 0, st>>>(cond, tok, pos, x, T, D, vocab, rows_per_sample);
+    return hipGetLastError();
+}
+
+// The sibling for the rows that join a rolling pass (hqt_set_max_joins): their prompts are not contiguous in cond [B, T].  `group_of_row` (device, [B]) is the
+// row list: row b with group g in [0, G) writes its T prompt rows to x[g * T + t]; every other row (group -1: mid-image, or an empty slot) reads and writes nothing.
+__global__ __launch_bounds__(256) void embed_text_rows_kernel(const int64_t* cond, const int* group_of_row, const float* tok, const float* pos,
+                                                              float* x, int G, int T, int D, int vocab) {
+    const int b = blockIdx.x / T, t = blockIdx.x % T;
+    const int g = group_of_row[b];
+    if (g < 0 || g >= G) return;
+    const long long id = clamp_idx(cond[blockIdx.x], vocab), row = (long long)g * T + t;
+    for (int d = threadIdx.x; d < D; d += blockDim.x) x[row * D + d] = tok[id * D + d] + pos[(long long)t * D + d];
+}
+hipError_t launch_embed_text_rows(const int64_t* cond, const int* group_of_row, const float* tok, const float* pos, float* x, int B, int G, int T, int D,
+                                  hipStream_t st, int vocab) {
+    if (B < 1 || G < 1 || G > B || T < 1 || D < 1 || !cond || !group_of_row || !x) return hipErrorInvalidValue;
+    embed_text_rows_kernel<<<B * T, 256, 0, st>>>(cond, group_of_row, tok, pos, x, G, T, D, vocab);
     return hipGetLastError();
 }
 

@@ -255,16 +255,19 @@ def check_segment(n_steps: int, segment, prefix=None, keep=None, prompt_groups=N
     return start, stop
 
 
-def check_row_positions(cond_type: int, batch: int, n_steps: int, row_positions, prefix=None, keep=None, prompt_groups=None, segment=None):
+def check_row_positions(cond_type: int, batch: int, n_steps: int, row_positions, prefix=None, keep=None, prompt_groups=None, segment=None, max_joins: int = 0):
     """A rolling call (``hqt_set_row_positions``) checked on the host, before any engine is touched: ``row_positions = (pos, k)`` with ``pos`` one integer per row of
-    the batch in [-1, n_steps - 1] (-1: an empty slot) and 1 <= k <= n_steps; not on a text-conditional model (a joining row needs a prompt prefill: not built) and
-    not together with ``prefix``, ``keep``, ``prompt_groups`` or ``segment``.  Returns (pos as a contiguous int32 numpy array, k); None stays None."""
+    the batch in [-1, n_steps - 1] (-1: an empty slot) and 1 <= k <= n_steps; on a text-conditional model only with ``max_joins`` > 0 (the engine has sized the
+    prompt prefill of its joining rows, ``hqt_set_max_joins``) and then with at most that many rows at position 0; not together with ``prefix``, ``keep``,
+    ``prompt_groups`` or ``segment``.  Returns (pos as a contiguous int32 numpy array, k); None stays None."""
     if row_positions is None:
         return None
     if not isinstance(row_positions, (list, tuple)) or len(row_positions) != 2:
         raise ValueError('row_positions: expected (pos, k)')
-    if int(cond_type) == 2:
-        raise ValueError('row_positions: a rolling pass on a text-conditional model is not built (a row that joins at position 0 needs a prompt prefill of its own)')
+    text = int(cond_type) == 2
+    if text and int(max_joins) < 1:
+        raise ValueError('row_positions: a rolling pass on a text-conditional model is not built (a row that joins at position 0 needs a prompt prefill of its own)'
+                         ' unless the engine has sized one: Engine(..., max_joins=J) / Engine.set_max_joins(J) with J > 0')
     for other, what in ((prefix, 'prefix'), (keep, 'keep'), (prompt_groups, 'prompt_groups'), (segment, 'segment')):
         if other is not None:
             raise ValueError(f'row_positions together with {what} is not built')
@@ -278,6 +281,9 @@ def check_row_positions(cond_type: int, batch: int, n_steps: int, row_positions,
     bad = np.nonzero((p < -1) | (p > int(n_steps) - 1))[0]
     if bad.size:
         raise ValueError(f'row_positions: pos[{int(bad[0])}]={int(p[bad[0]])} outside [-1, n_steps - 1 = {int(n_steps) - 1}] (-1: an empty slot)')
+    joins = int((p == 0).sum())
+    if text and joins > int(max_joins):
+        raise ValueError(f'row_positions: {joins} rows join at position 0 in this call, the engine has sized the prompt prefill of max_joins={int(max_joins)}')
     return p, int(k)
 
 
@@ -400,14 +406,16 @@ class Engine:
     """One libhqt handle on one GPU.  Not thread-safe; asynchronous on torch's current stream."""
 
     def __init__(self, s2: Optional[Stage2Spec], s1: Optional[Stage1Spec], device: torch.device, max_batch: int,
-                 max_steps: Optional[int] = None, ar_layouts: int = 0, max_prefix: int = 0, score_chunk: int = 0):
+                 max_steps: Optional[int] = None, ar_layouts: int = 0, max_prefix: int = 0, score_chunk: int = 0, max_joins: int = 0):
         """``ar_layouts``: bit mask of ``_lib.LAYOUT_*`` -- which derived layouts of the AR loop's weights ``finalize`` builds
         (``hqt_config.ar_layouts``; 0 = all).  A FAST-only replica passes ``_lib.LAYOUT_FAST`` and holds 5.2 instead of 9.1 GB for the
         ImageNet-12L model; a call in a precision the engine was built without raises HqtError (HQT_ERR_STATE).
         ``max_prefix``: longest code prefix ``sample(..., prefix=...)`` may pass (``hqt_set_max_prefix``, called right after ``hqt_create``; 0 = none, and the workspace
         is exactly what it is without the feature).
         ``score_chunk``: (sample, position) pairs per depth chunk of ``score`` (``hqt_set_score_chunk``, called right after ``hqt_create``; 0 = ``max_batch`` pairs,
-        and nothing is allocated for it)."""
+        and nothing is allocated for it).
+        ``max_joins``: rows that may join a rolling pass of a text-conditional model in one call (``hqt_set_max_joins``, called right after ``hqt_create``; 0 = rolling
+        passes on a text model stay refused, and nothing is allocated)."""
         self.lib = _lib.load()                      # raises HqtLibraryError when the HIP library is absent
         self.s2, self.s1 = s2, s1
         self.device = torch.device(device)
@@ -428,7 +436,18 @@ class Engine:
         if self.score_chunk:
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.hqt_set_score_chunk(self.h, self.score_chunk))
+        self.max_joins = 0
+        if int(max_joins):
+            self.set_max_joins(max_joins)
         self.policy = _lib.POLICY_LATENCY
+
+    def set_max_joins(self, max_joins: int) -> None:
+        """``hqt_set_max_joins``: sizes (grows, never shrinks) the staging of the prompt prefill that up to ``max_joins`` rows joining a rolling pass need in one call,
+        on a text-conditional engine; 0 switches rolling passes off again and frees nothing.  Raises HqtError on any other engine, outside [0, max_batch], or while
+        the engine holds a rolling pass."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.hqt_set_max_joins(self.h, int(max_joins)))
+        self.max_joins = int(max_joins)
 
     def clone(self) -> 'Engine':
         """A further lane over the same weights (``hqt_clone``): own KV cache / activations / graph cache, results
@@ -439,6 +458,7 @@ class Engine:
         e.lib, e.s2, e.s1, e.device = self.lib, self.s2, self.s1, self.device
         e.max_batch, e.max_steps, e.max_prefix, e.cfg = self.max_batch, self.max_steps, self.max_prefix, self.cfg
         e.score_chunk = self.score_chunk
+        e.max_joins = getattr(self, '_parent', self).max_joins     # hqt_clone gives the lane a staging of its own for as many joins as the root has sized
         h = C.c_void_p()
         _lib.check(self.lib.hqt_clone(self.h, C.byref(h)))
         e.h, e.finalized = h, True
@@ -608,7 +628,7 @@ class Engine:
         dev = self.device
         B, V, L = int(batch), self.s2.vocab_top, int(levels)
         segment = check_segment(n_steps, segment, prefix, keep, prompt_groups)
-        roll = check_row_positions(self.s2.cond, B, n_steps, row_positions, prefix, keep, prompt_groups, segment)
+        roll = check_row_positions(self.s2.cond, B, n_steps, row_positions, prefix, keep, prompt_groups, segment, max_joins=getattr(self, 'max_joins', 0))
         if roll is not None and out is None:
             raise ValueError('row_positions: a rolling call writes the positions its rows draw into out (and reads the codes in front of them there) -- pass the tensors the pass lives in')
         if segment is not None and segment[0] > 0 and out is None:
@@ -759,7 +779,9 @@ class Engine:
         (the tensors the pass lives in: the positions drawn are written there, the codes of pos[b] - 1 read from there); ``logits_out`` / ``logprobs_out`` are filled
         the same way, and nothing of an idle row is written.  A slot continues exactly where the engine's rolling pass left it, joins at 0 or is empty (HqtError
         otherwise); ``cond[b]`` is read where a row stands at 0, ``row_seeds`` / ``row_offsets`` / ``row_samplers`` give each slot its request's key and settings.
-        Not on text models, not together with ``prefix``, ``keep``, ``prompt_groups`` or ``segment``.
+        Text models: only on an engine with ``max_joins`` > 0 (``set_max_joins``), with at most that many rows at position 0 per call; ``cond`` is [B, ctx_len_txt], a
+        joining row's prompt prefill draws its position 0 in front of the k steps, so it advances by 1 + k in that call (every other row by k).
+        Not together with ``prefix``, ``keep``, ``prompt_groups`` or ``segment``.
         ``report_out`` (a ``DrawReport`` of caller-owned tensors, see ``check_report_out`` / ``new_draw_report``): the call writes entropy, rank and the top-N codes of the
         row behind every draw into them (``hqt_set_draw_report``), exactly where ``logprobs_out`` entries are written; nothing is appended to the returned values."""
         if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):

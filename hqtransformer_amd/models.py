@@ -159,23 +159,28 @@ class HQTransformerStage2(_Stage):
     def pos_emb_txt(self):
         return _Table(self._w['pos_emb_txt.weight'])
 
-    def engine(self, batch: int, n_steps: int, lane: int = 0, max_prefix: int = 0, score_chunk: Optional[int] = None) -> Engine:
+    def engine(self, batch: int, n_steps: int, lane: int = 0, max_prefix: int = 0, score_chunk: Optional[int] = None, max_joins: int = 0) -> Engine:
         """``max_prefix`` > 0: the engine must take code prefixes of that many positions (``hqt_set_max_prefix``); like ``batch`` it only
         ever grows, and a model that never completes a prefix keeps the workspace it always had.
         ``score_chunk``: pairs per depth chunk of ``Engine.score`` (``hqt_set_score_chunk``); None keeps what the engine has (0, i.e. ``max_batch`` pairs, for a
-        new one), another value than the engine's rebuilds it."""
+        new one), another value than the engine's rebuilds it.
+        ``max_joins`` > 0 (text models): the lane must take rolling calls in which that many rows join (``hqt_set_max_joins``); it grows the lane's staging in place
+        and never rebuilds the engine."""
         self._need_gpu()
         e = self._engine
         chunk = (e.score_chunk if e else 0) if score_chunk is None else int(score_chunk)
         if e is None or batch > e.max_batch or n_steps > e.max_steps or max_prefix > e.max_prefix or chunk != e.score_chunk:
             self._drop_engine()
             e = Engine(self.spec, None, self._device, max(batch, e.max_batch if e else 0), self.spec.ctx_len_img,
-                       max_prefix=max(int(max_prefix), e.max_prefix if e else 0), score_chunk=chunk)
+                       max_prefix=max(int(max_prefix), e.max_prefix if e else 0), score_chunk=chunk, max_joins=e.max_joins if e else 0)
             unused = stage2_unused(self.spec)
             e.load(stage2={k: v for k, v in self._w.items() if k not in unused})
             e.finalize()
             self._engine = e
-        return self._lane(e, lane)
+        le = self._lane(e, lane)
+        if int(max_joins) > le.max_joins:
+            le.set_max_joins(int(max_joins))
+        return le
 
     def sampling_step(self, sos, codes_t=None, codes_b=None, pos_codes=None, use_fp16: bool = True, top_k_top=None, top_p_top=None,
                       top_k_bot=None, top_p_bot=None, softmax_temperature=(1.0, 1.0), past=None, model_stage1=None, given_top_code=None, *,

@@ -359,20 +359,30 @@ class RollingSampler:
     slot -- in EXACT arithmetic, where a row's draws do not depend on the pass it sits in, what ``sampling_ihqgpt(stage2, 1, cond, max_seq_len=n, seed=seed)`` draws.
     The sampler holds the slot bookkeeping on the host (free list, positions, keys, conditions, the row-sampler table) and the code tensors of the pass on the
     device; one rolling pass at a time per engine lane (any other sampling or scoring call on the lane ends it, and the next ``step`` raises ``HqtError``).
-    Text models are refused: a row that joins at position 0 would need a prompt prefill of its own, which is not built."""
+    Text models need ``max_joins`` (1 <= max_joins <= slots): a row that joins at position 0 needs a prompt prefill of its own, whose staging the engine sizes for
+    that many joining rows per call (``hqt_set_max_joins``); without it they are refused.  ``submit(cond=...)`` then takes one prompt of ``ctx_len_txt`` token ids,
+    ``step`` admits at most ``max_joins`` requests per call, and a request that joins in a call advances by 1 + k in it -- the join draws position 0 in front of
+    the k steps --, every other by k."""
 
-    def __init__(self, stage2, slots: int, n: int, *, precision: Optional[str] = None, use_fp16: bool = True, use_graph: bool = True, lane: int = 0,
-                 return_logprobs: bool = False, return_report: Optional[int] = None):
+    def __init__(self, stage2, slots: int, n: int, max_joins: Optional[int] = None, *, precision: Optional[str] = None, use_fp16: bool = True, use_graph: bool = True,
+                 lane: int = 0, return_logprobs: bool = False, return_report: Optional[int] = None):
         top_n = _report_n(stage2.spec, return_report)
-        if stage2.use_txt_cond:
-            raise ValueError('RollingSampler: a rolling pass on a text-conditional model is not built (a row that joins at position 0 needs a prompt prefill of its own)')
+        self.text_cond = bool(stage2.use_txt_cond)
+        if self.text_cond and not max_joins:
+            raise ValueError('RollingSampler: a rolling pass on a text-conditional model is not built (a row that joins at position 0 needs a prompt prefill of its own)'
+                             ' unless max_joins= sizes one: RollingSampler(stage2, slots, n, max_joins=J) with 1 <= J <= slots')
+        if max_joins is not None and not self.text_cond:
+            raise ValueError('max_joins: only a text-conditional model prefills the rows that join (any other model joins without a prefill)')
+        if self.text_cond and (isinstance(max_joins, bool) or not 1 <= int(max_joins) <= int(slots)):
+            raise ValueError(f'max_joins={max_joins!r} outside [1, slots = {int(slots)}]')
+        self.max_joins = int(max_joins) if self.text_cond else None
         self.stage2, self.L, self.slots, self.n = stage2, int(stage2.spec.levels), int(slots), int(n)
         if self.slots < 1:
             raise ValueError(f'slots={self.slots}: a rolling pass needs at least one slot')
         if not 1 <= self.n <= stage2.spec.ctx_len_img:
             raise ValueError(f'n={self.n} outside [1, ctx_len_img={stage2.spec.ctx_len_img}]')
         self.precision, self.use_graph = _precision(precision, use_fp16), bool(use_graph)
-        self.engine = stage2.engine(self.slots, self.n, lane)
+        self.engine = stage2.engine(self.slots, self.n, lane, max_joins=self.max_joins) if self.text_cond else stage2.engine(self.slots, self.n, lane)
         dev = self.engine.device
         self.codes = [torch.full((self.slots, self.n) + ((4 ** l,) if l else ()), -1, dtype=torch.int64, device=dev) for l in range(self.L)]
         self.logprobs = torch.full((self.slots, self.n, (4 ** self.L - 1) // 3), float('nan'), dtype=torch.float32, device=dev) if return_logprobs else None
@@ -382,6 +392,8 @@ class RollingSampler:
         # per slot: the position it draws next (-1: empty), its request's ticket, condition, key and sampler settings
         self.pos, self.ticket = [-1] * self.slots, [None] * self.slots
         self.cond, self.row_seeds, self.row_offsets = [0] * self.slots, [0] * self.slots, [0] * self.slots
+        if self.text_cond:                           # per slot one prompt; an empty slot's row is never read (token 0 is inside every vocabulary)
+            self.cond = [[0] * int(stage2.spec.ctx_len_txt) for _ in range(self.slots)]
         self.row_samplers = [default] * self.slots
         self.free = list(range(self.slots))          # ascending: a request joins in the lowest free slot
         self.queue: list = []
@@ -401,6 +413,14 @@ class RollingSampler:
             if cond is None or isinstance(cond, bool) or not 0 <= int(cond) < self.stage2.spec.n_classes:
                 raise ValueError(f'cond={cond!r}: a class id in [0, {self.stage2.spec.n_classes}) is required')
             cond = int(cond)
+        elif self.text_cond:
+            T, V = int(self.stage2.spec.ctx_len_txt), int(self.stage2.spec.vocab_txt)
+            ids = None if cond is None else torch.as_tensor(cond).cpu()
+            if ids is None or ids.dtype.is_floating_point or ids.dtype == torch.bool or tuple(ids.shape) != (T,):
+                raise ValueError(f'cond: one prompt of ctx_len_txt = {T} token ids is required' + ('' if ids is None else f', got {ids.dtype} of shape {tuple(ids.shape)}'))
+            if int(ids.min()) < 0 or int(ids.max()) >= V:
+                raise ValueError(f'cond: token ids span [{int(ids.min())}, {int(ids.max())}], outside the text vocabulary [0, vocab_txt = {V})')
+            cond = [int(v) for v in ids.tolist()]
         elif cond is not None:
             raise ValueError('cond: an unconditional model takes None')
         entry = step_row_samplers(self.L, [1], [sampler])[0]
@@ -416,13 +436,15 @@ class RollingSampler:
         k = int(k)
         if not 1 <= k <= self.n:
             raise ValueError(f'step(k={k}): expected 1 <= k <= n = {self.n}')
-        while self.queue and self.free:
+        admitted = 0
+        while self.queue and self.free and (self.max_joins is None or admitted < self.max_joins):
+            admitted += 1
             slot = self.free.pop(0)
             self.ticket[slot], self.cond[slot], self.row_seeds[slot], self.row_offsets[slot], self.row_samplers[slot] = self.queue.pop(0)
             self.pos[slot] = 0
         if not self.live:
             return []
-        cond = torch.tensor(self.cond, dtype=torch.int64) if self.class_cond else None
+        cond = torch.tensor(self.cond, dtype=torch.int64) if self.class_cond or self.text_cond else None
         common = dict(precision=self.precision, seed=0, use_graph=self.use_graph, row_seeds=list(self.row_seeds), row_offsets=list(self.row_offsets),
                       row_samplers=list(self.row_samplers), out=self.codes, logprobs_out=self.logprobs, report_out=self.report,
                       row_positions=(list(self.pos), k))
@@ -430,8 +452,10 @@ class RollingSampler:
             self.engine.sample3(self.slots, cond, self.n, **common)
         else:
             self.engine.sample(self.slots, cond, self.n, **common)
-        done = [s for s in range(self.slots) if self.pos[s] >= 0 and self.pos[s] + k >= self.n]
-        self.pos = [-1 if p < 0 or p + k >= self.n else p + k for p in self.pos]
+        # the record the library keeps: a row of a text pass that joined in this call drew position 0 in its prompt prefill, in front of the k steps
+        moved = [p if p < 0 else p + k + (1 if self.text_cond and p == 0 else 0) for p in self.pos]
+        done = [s for s in range(self.slots) if self.pos[s] >= 0 and moved[s] >= self.n]
+        self.pos = [-1 if p < 0 or p >= self.n else p for p in moved]
         if not done:
             return []
         idx = torch.as_tensor(done, dtype=torch.int64, device=self.codes[0].device)

@@ -364,8 +364,8 @@ int hqt_select_rows(hqt_handle* h, int B_new, const int32_t* rows_from, void* st
  * settings and row tables; force_*, logits_out and a staged hqt_set_logprob_out buffer behave as in a plain call, all indexed by absolute position.  cond[b] is read
  * where a row stands at position 0; row_seeds / row_offsets give each slot its request's key.  The codes of position pos[b] - 1 are read from the caller's out_* (a
  * forced level: force_*), as a segment reads them.  Every depth head and every precision; a row's bits do not depend on where its neighbours stand.
- * Idle rows -- empty slots, and rows that have drawn position n - 1 in an earlier step of the call -- still occupy rows of the GEMMs: they compute as a row at
- * position 0 would, inside their own cache slot, and nothing the caller can see of them is written (out_*, logits_out, the log-probabilities).
+ * Idle rows -- empty slots, and rows that have drawn position n - 1 in an earlier step of the call -- still occupy rows of the GEMMs: they compute on an input row of
+ * zeros at position 0, inside their own (dead) cache slot, and nothing the caller can see of them is written (out_*, logits_out, the log-probabilities).
  * The handle records the ROLLING PASS: B, n, code levels, precision and per slot the next position; a slot whose row reached n becomes empty.  The taking call
  * checks every slot against the record and fails with HQT_ERR_STATE naming the row (the record is kept) unless pos[b] is -1 (vacate, or stay empty), 0 (join: always
  * allowed, the slot's old contents are dead) or exactly the recorded next position (continue); without a record every entry must be 0 or -1.  A B, n, level count or
@@ -376,11 +376,31 @@ int hqt_select_rows(hqt_handle* h, int B_new, const int32_t* rows_from, void* st
  * the steps per graph launch enter the graph key, calls that differ only in positions replay one graph.  Without a staged table a call launches exactly what it
  * launched before.
  * HQT_ERR_INVALID, with a message naming the cause: a NULL handle; B outside [1, max_batch] or different from the taking call's; k outside [1, n]; an entry outside
- * [-1, n - 1]; a text-conditional handle (a joining row needs a prompt prefill: not built); a prefix entry point; a staged segment, keep table or prompt-group table;
- * a hqt_set_guidance pair whose two rows stand at different positions or of which exactly one is empty.
- * Not built: text-conditional rolling passes; rolling together with segments, keep tables or prefixes; hqt_select_rows on a rolling pass (HQT_ERR_STATE: slots are
- * reused in place); a rolling form of the persistent launch. */
+ * [-1, n - 1]; a text-conditional handle that has not sized the prefill of its joining rows (hqt_set_max_joins, below), or more joining rows in one call than it
+ * sized; a prefix entry point; a staged segment, keep table or prompt-group table; a hqt_set_guidance pair whose two rows stand at different positions or of which
+ * exactly one is empty.
+ * TEXT-CONDITIONAL handles (after hqt_set_max_joins(h, J > 0)) differ in these points, and in nothing else.  cond is [B, ctx_len_txt]; row b of it is read only
+ * where pos[b] == 0.  Position 0 of a text row is not a decode step: the row's prompt prefill draws it.  A call whose table holds joining rows (pos[b] == 0) first
+ * runs the JOIN PHASE -- the prompts of the joining rows through the body into a staging buffer, from there into their cache slots, and the depth head, which draws
+ * position 0 under each joiner's own key, sampler row and noise slice (out_*[b, 0], logits_out, the log-probabilities and the draw report at position 0) -- and then
+ * the k steps, in all of which a joining row takes part at positions 1 .. k: it advances by 1 + k (clipped at n), every other row by k.  The handle's record, what
+ * the next call must present for the slot and the entries of every output that are written follow that rule.  With n == 1 a joining row is finished behind the
+ * join phase and idles in the steps.  The two rows of a guidance pair stand at one position, so they join together.  The join phase runs in front of the
+ * captured steps, as the prompt prefill of a plain call does, and allocates nothing.  In EXACT a request draws bit for bit what the plain call draws for it in its
+ * slot; in FAST and SPLIT the prefill of J prompts may be served by other GEMM kernels than the prefill of B, so the plain call that equals a join is the one
+ * that prefills the same J prompts (hqt_set_prompt_groups).
+ * Not built: rolling together with segments, keep tables, prefixes or prompt groups (a join prefills every joining row's prompt, equal or not); a depth pass
+ * over the joining rows alone (the join phase's depth head runs over all B rows); hqt_select_rows on a rolling pass (HQT_ERR_STATE: slots are reused in place);
+ * a rolling form of the persistent launch. */
 int hqt_set_row_positions(hqt_handle* h, int B, const int32_t* pos, int k);
+
+/* hqt_set_max_joins -- opt-in sizing of rolling passes on a text-conditional handle: allocates (grows, never shrinks) what the prompt prefill of up to max_joins
+ * joining rows per call needs -- the staging K/V of [n_layers][max_joins][ctx_len_txt][D] at 4 bytes per element and the gathered rows [max_batch][D] fp32.  These
+ * are the buffers of hqt_set_prompt_groups, sized to the larger of the two needs and counted by hqt_workspace_bytes; a sampling call allocates nothing.  A lane from
+ * hqt_clone of a handle with max_joins > 0 gets a staging of its own for as many.  max_joins == 0 switches rolling passes off again and frees nothing.  A text
+ * handle that never called it refuses hqt_set_row_positions as it always has.
+ * HQT_ERR_INVALID: a NULL handle, a handle that is not text-conditional, max_joins outside [0, max_batch].  HQT_ERR_STATE: the handle holds a rolling pass. */
+int hqt_set_max_joins(hqt_handle* h, int max_joins);
 
 /* hqt_sample -- replaces sampling_ihqgpt + iHQGPT.sampling_step (hqvae/utils/sampling.py:164-237,
  * hierarchical_ar.py:428-480, 482-563, 667-789) for a batch of B independent images.
