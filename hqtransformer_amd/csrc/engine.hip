@@ -179,9 +179,9 @@ struct hqt_handle {
     } staged;
     Staged take_staged() { Staged s = std::move(staged); staged = Staged(); return s; }
     void clear_staged() { staged = Staged(); }
-    // staging of a shared prefill, sized (grown) by hqt_set_prompt_groups and hqt_set_max_joins (reserve_prompt_staging) and by nothing else: K and V of
-    // [n_layers][pg_cap][ctx_len_txt][D] at 4 bytes per element (any mode's activation type fits), and the [max_batch, D] fp32 rows the fan-out gathers for
-    // the depth head of position 0
+    // staging of staged_prompt_prefill (shared prompts; the joiners of a rolling text pass), sized (grown) by hqt_set_prompt_groups and hqt_set_max_joins
+    // (reserve_prompt_staging) and by nothing else: K and V of [n_layers][pg_cap][ctx_len_txt][D] at 4 bytes per element (any mode's activation type fits), and
+    // the [max_batch, D] fp32 rows the fan-out gathers for the depth head of position 0
     void *pg_k = nullptr, *pg_v = nullptr;
     float* pg_x = nullptr;
     int pg_cap = 0;                           // prompts the staging holds
@@ -257,9 +257,9 @@ static int dev_alloc(hqt_handle* h, void** p, size_t bytes, bool workspace) {
     return HQT_OK;
 }
 
-// The one place that allocates the staging of a prompt prefill over fewer rows than the pass has (hqt_handle::pg_*): room for `n_groups` prompts, grown and never
-// shrunk (a larger need frees the old pair once the device has drained, a smaller one reuses it), and with the first need the gathered x rows.  Those start as
-// zeros: the join phase of a rolling pass writes only the joiners' rows and runs the depth head over all of them.  The caller has set the device.
+// The one place that allocates the staging of staged_prompt_prefill, the prompt prefill over fewer rows than the pass has (hqt_handle::pg_*): room for `n_groups`
+// prompts, grown and never shrunk (a larger need frees the old pair once the device has drained, a smaller one reuses it), and with the first need the gathered
+// x rows.  Those start as zeros: with joiners as the prompts the prefill writes only their rows and runs the depth head over all.  The caller has set the device.
 static int reserve_prompt_staging(hqt_handle* h, int n_groups) {
     const hqt_config& c = h->cfg;
     if (!h->pg_x) {
@@ -1529,7 +1529,7 @@ static int run_block(hqt_handle* h, const SampleCtx& c, const BlockW& bw, const 
 // The body blocks of one position over Tq_body rows: as ONE persistent launch up to the top logits (pfull: two code levels, 'parallel' -- persist_build
 // makes that program for no other head; dln0: sub-step 0 of the depth head takes the deferred-LayerNorm path), as one persistent launch of the body
 // alone (pbody), or as the launch chain.  *pfull: the whole-position launch ran.
-// `stage` (a shared prefill, hqt_set_prompt_groups): K/V go to the staging buffer of [n_layers][c.B][Tq_body][D] instead of the cache.
+// `stage` (staged_prompt_prefill: shared prompts, the joiners of a rolling text pass): K/V go to the staging buffer of [n_layers][c.B][Tq_body][D] instead of the cache.
 struct KvStage { void *k, *v; };
 static int run_body(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_base, bool body_tbase_from_state, bool dln0, bool* pfull,
                     const KvStage* stage = nullptr) {
@@ -1598,8 +1598,8 @@ static SubStep sub_step(const hqt_config& cf, int sub) {
     return {lv, 1, sub, lv ? LEVEL_WIDTH[lv] : 0, sub - first[lv]};
 }
 
-// The input rows of depth sub-step `sub` in xd (dln: with their packed copy and row statistics)
-static int run_depth_input(hqt_handle* h, const SampleCtx& c, int sub, bool dln, int Tq_body, bool fuse) {
+// The input rows of depth sub-step `sub` in xd (dln: with their packed copy and row statistics); sub-step 0 reads the last of the Tq_body rows per sample in x
+static int run_depth_input(hqt_handle* h, const SampleCtx& c, float* x, int sub, bool dln, int Tq_body, bool fuse) {
     const hqt_config& cf = h->cfg;
     const int D = cf.embed_dim, B = c.B, V = cf.vocab_top;
     const SubStep s = sub_step(cf, sub);
@@ -1607,7 +1607,7 @@ static int run_depth_input(hqt_handle* h, const SampleCtx& c, int sub, bool dln,
     bf16_t* xpk = dln ? h->xdpk : nullptr;
     if (sub == 0) {           // ln_f on the last token of each sample, + sos_depth (hierarchical_ar.py:561,684-686) -> depth input of level 0
         Timed t(h, "layernorm", c.st);
-        LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, B, D, Tq_body, Tq_body - 1, 1e-5f, DT_F32, 0,
+        LNArgs ln{x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, B, D, Tq_body, Tq_body - 1, 1e-5f, DT_F32, 0,
                   nullptr, 0, 0, nullptr, xpk, pk, h->partsd};
         take_pend(h, ln);
         HIPCHK(launch_layernorm(ln, c.st));
@@ -1633,10 +1633,10 @@ static int run_depth_input(hqt_handle* h, const SampleCtx& c, int sub, bool dln,
     return HQT_OK;
 }
 
+static const Lin& head_of(const hqt_handle* h, int lv) { return lv == 0 ? h->head_top : (lv == 1 ? h->head_bot : h->head_l2); }      // the head of code level lv
 // Sub-step `s` of the depth head takes the deferred-LayerNorm path (never the bidirectional head's single pass, which decides for itself)
 static bool depth_dln(hqt_handle* h, const SampleCtx& c, const SubStep& s) {
-    const Lin* heads[3] = {&h->head_top, &h->head_bot, &h->head_l2};
-    return h->cfg.depth_decoding != HQT_DEPTH_BIDIRECTIONAL && dln_ok(h, c, h->depth[0], c.B * s.Tq) && heads[s.lv]->wpk_ln;
+    return h->cfg.depth_decoding != HQT_DEPTH_BIDIRECTIONAL && dln_ok(h, c, h->depth[0], c.B * s.Tq) && head_of(h, s.lv).wpk_ln;
 }
 
 // The bidirectional head behind its input launch: one pass of the depth blocks over the depth_rows rows per sample in xd, then ln_top / ln_bot of the
@@ -1672,15 +1672,13 @@ static int fold_pending(hqt_handle* h, const SampleCtx& c, int M) {
 //    depth blocks over five rows per sample, [ln_f(h) + sos_depth, pos_emb_depth[0..3]], with full 5 x 5 attention and no cache carried to
 //    the next position; then the two 'parallel' sub-steps' heads and draws, top logits from row 0 (ln_top, head_top), bottom from rows 1..4
 //    (ln_bot, head_bot).  All five draws use temperature_top, top_k_bot and top_p_bot, as the reference does (:866-873).
-// The depth-head half of a position: ln_f on the last of the Tq_body rows per sample in h->x, the sub-steps and their draws.  pfull: the
-// whole-position persistent launch already computed sub-step 0 up to its logits (run_body).
-static int run_depth_head(hqt_handle* h, const SampleCtx& c, int Tq_body, bool pfull) {
+// The depth-head half of a position: ln_f on the last of the Tq_body rows per sample in x (h->x, or the rows a staged prompt prefill gathered; a pending split-K
+// fold rewrites them), the sub-steps and their draws.  pfull: the whole-position persistent launch already computed sub-step 0 up to its logits (run_body).
+static int run_depth_head(hqt_handle* h, const SampleCtx& c, float* x, int Tq_body, bool pfull) {
     const hqt_config& cf = h->cfg;
     const int D = cf.embed_dim, B = c.B, V = cf.vocab_top;
-    const Lin* heads[3] = {&h->head_top, &h->head_bot, &h->head_l2};
     const bool bidir = cf.depth_decoding == HQT_DEPTH_BIDIRECTIONAL, causal_head = cf.depth_decoding == HQT_DEPTH_TOP2MID2BOT;
     const int nsub = causal_head ? h->depth_rows : c.levels;       // 'top2mid2bot': one sub-step per depth token
-    auto dln_of = [&](const SubStep& s) { return depth_dln(h, c, s); };
     // the draw and the embedding lookup of the drawn code in one kernel: the two-level top sampler's workgroup of sample b also writes the
     // four input rows of depth sub-step 1 (HQT_NO_FUSED_EMBED=1: separate depth_embed_kernel, for A/B runs)
     static const bool fuse_env = !getenv("HQT_NO_FUSED_EMBED");
@@ -1692,7 +1690,7 @@ static int run_depth_head(hqt_handle* h, const SampleCtx& c, int Tq_body, bool p
         const bool dln = dln_ok(h, c, h->depth[0], M);
         {
             Timed t(h, "bidir_depth_input", c.st);
-            LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, B, D, Tq_body, Tq_body - 1, 1e-5f, DT_F32, 0,
+            LNArgs ln{x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, B, D, Tq_body, Tq_body - 1, 1e-5f, DT_F32, 0,
                       nullptr, 0, 0, nullptr, dln ? h->xdpk : nullptr, dln ? packed_mb(M) : 0, h->partsd};
             ln.fill = W(h, "pos_emb_depth.weight");
             take_pend(h, ln);
@@ -1705,13 +1703,13 @@ static int run_depth_head(hqt_handle* h, const SampleCtx& c, int Tq_body, bool p
     for (int sub = 0; sub < nsub; ++sub) {
         const SubStep s = sub_step(cf, sub);
         const int M = B * s.Tq;
-        const bool dln = dln_of(s), in_pfull = pfull && sub == 0;      // the whole-position launch computed sub-step 0 up to its logits
+        const bool dln = depth_dln(h, c, s), in_pfull = pfull && sub == 0;      // the whole-position launch computed sub-step 0 up to its logits
         if (!bidir && !in_pfull) {    // the bidirectional pass ran its depth blocks above
-            CHK(run_depth_input(h, c, sub, dln, Tq_body, fuse));
+            CHK(run_depth_input(h, c, x, sub, dln, Tq_body, fuse));
             h->npartsd = 1;
             CHK(run_depth(h, c, dln, s.Tq, s.tbase));
         }
-        if (!in_pfull) CHK(run_head(h, c, *heads[s.lv], s.lv, M, dln, normed[s.lv]));
+        if (!in_pfull) CHK(run_head(h, c, head_of(h, s.lv), s.lv, M, dln, normed[s.lv]));
         if (c.guide) {            // both rows of every pair become the guided row before anything reads the logits (the sampler, its logits_out copy, code_logprob)
             Timed t(h, "guide_logits", c.st);
             HIPCHK(launch_guide_logits(h->logits, h->guide, c.n_guide, V, s.Tq, s.lv, c.st));
@@ -1730,25 +1728,19 @@ static int run_depth_head(hqt_handle* h, const SampleCtx& c, int Tq_body, bool p
             if (c.keep) sa.keep = h->keep_mask;
             sa.row_pos = c.row_pos;
             if (fuse && sub == 0) {
-                const bool dln_next = dln_of(sub_step(cf, 1));
+                const bool dln_next = depth_dln(h, c, sub_step(cf, 1));
                 sa.emb_tok = W(h, "tok_emb_top_depth.weight"); sa.emb_pos = W(h, "pos_emb_depth.weight");
                 sa.emb_feed = c.feed[0] != c.out[0] ? c.feed[0] : nullptr;
                 sa.emb_x = h->xd; sa.emb_D = D;
                 sa.emb_xpk = dln_next ? h->xdpk : nullptr; sa.emb_pk_mb = dln_next ? packed_mb(4 * B) : 0; sa.emb_parts = h->partsd;
             }
             HIPCHK(launch_sampler(sa, c.st));
-            if (c.report.any()) {     // one launch per draw writes the report and, where a buffer is staged too, the log-probability: no code_logprob launch then
-                t.next("draw_report");
-                for (int slot = 0; slot < s.Tq; ++slot) {
-                    if (slot) t.next("draw_report");
-                    HIPCHK(launch_draw_report(sa, c.feed[s.lv], c.logprob_out, c.report, slot, c.st));
-                }
-            } else if (c.logprob_out) {      // one launch per draw of this sub-step, each under the timing slot of its own: the sampler's scope ends with the sampler
-                t.next("code_logprob");
-                for (int slot = 0; slot < s.Tq; ++slot) {
-                    if (slot) t.next("code_logprob");
-                    HIPCHK(launch_code_logprob(sa, c.feed[s.lv], c.logprob_out, slot, c.st));
-                }
+            // one launch per draw, each under a timing slot of its own (the sampler's ends here): the log-probability, or the report, which also writes that where a buffer is staged
+            const bool report = c.report.any();
+            for (int slot = 0; slot < (report || c.logprob_out ? s.Tq : 0); ++slot) {
+                t.next(report ? "draw_report" : "code_logprob");
+                if (report) HIPCHK(launch_draw_report(sa, c.feed[s.lv], c.logprob_out, c.report, slot, c.st));
+                else HIPCHK(launch_code_logprob(sa, c.feed[s.lv], c.logprob_out, slot, c.st));
             }
         }
     }
@@ -1759,7 +1751,7 @@ static int run_depth_head(hqt_handle* h, const SampleCtx& c, int Tq_body, bool p
 static int run_position(hqt_handle* h, const SampleCtx& c, int Tq_body, int body_t_base, bool body_tbase_from_state) {
     bool pfull = false;
     CHK(run_body(h, c, Tq_body, body_t_base, body_tbase_from_state, depth_dln(h, c, sub_step(h->cfg, 0)), &pfull));
-    return run_depth_head(h, c, Tq_body, pfull);
+    return run_depth_head(h, c, h->x, Tq_body, pfull);
 }
 
 // hqt_config.ar_layouts: a precision whose weight layout the handle was created without fails here, loudly (never a silent slower path)
@@ -1798,13 +1790,15 @@ static int embed_prefill(hqt_handle* h, const SampleCtx& c, const int64_t* const
     return HQT_OK;
 }
 
+static int embed_step(hqt_handle* h, const SampleCtx& c) {      // the body input row of a decode step, one per sample (with the packed copy where run_body wants it)
+    Timed t(h, "embed", c.st);
+    EmbedArgs e = embed_args(h, c, c.feed);
+    if (dln_ok(h, c, h->body[0], c.B)) { e.xpk = h->xpk; e.pk_mb = packed_mb(c.B); h->nparts = 1; }
+    HIPCHK(launch_embed_step(e, c.st));
+    return HQT_OK;
+}
 static int run_decode_step(hqt_handle* h, const SampleCtx& c) {      // one KV-cached position, Tq = 1
-    {
-        Timed t(h, "embed", c.st);
-        EmbedArgs e = embed_args(h, c, c.feed);
-        if (dln_ok(h, c, h->body[0], c.B)) { e.xpk = h->xpk; e.pk_mb = packed_mb(c.B); h->nparts = 1; }
-        HIPCHK(launch_embed_step(e, c.st));
-    }
+    CHK(embed_step(h, c));
     // a rolling pass of a text handle: row b stands behind its prompt, at cache row ctx_len_txt - 1 + pos[b] -- where the plain text call's step state puts
     // position pos[b]; the offset is a constant of the handle (an idle row stores at row ctx_len_txt - 1 of its own, dead slot and is read by nothing)
     const int behind_prompt = c.row_pos && h->cfg.cond_type == HQT_COND_TEXT ? h->cfg.ctx_len_txt - 1 : 0;
@@ -1864,136 +1858,117 @@ static int ring_sent(hqt_handle* h, int slot, hipStream_t st) {
     return HQT_OK;
 }
 
-// hqt_sample / hqt_sample_l3 after their null checks: `c` holds the call's options, sampler settings and forced codes (feed); validates them,
-// runs the call and copies the drawn codes of every level out
-static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t* const* out, void* stream) {
-    // what was staged belongs to THIS call and to no later one, whatever becomes of the call; `s` owns the host tables until it returns
-    const hqt_handle::Staged s = h->take_staged();
-    c.row_set = s.row_set.empty() ? nullptr : s.row_set.data();
-    c.logprob_out = s.logprob;
-    c.report = s.report;
-    c.guide = s.guide.empty() ? nullptr : s.guide.data();
-    c.n_guide = (int)s.guide.size();
-    c.keep = s.keep.empty() ? nullptr : s.keep.data();
-    for (int i = 0; i < 3; ++i) c.keep_codes[i] = s.keep_codes[i];
-    c.groups = s.groups.empty() ? nullptr : s.groups.data();
-    c.n_groups = c.groups ? s.groups_G : 0;
-    c.seg = s.seg;
-    c.start = c.seg ? s.seg_start : 0;
-    c.stop = c.seg ? s.seg_stop : c.n_steps;
-    c.roll = s.roll.empty() ? nullptr : s.roll.data();
-    c.roll_k = s.roll_k;
-    if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
-    const hqt_config& cf = h->cfg;
-    if (c.levels == 2 && !cf.has_stage2) return fail(HQT_ERR_STATE, "handle was created without stage 2");
-    if (c.levels == 2 && cf.code_levels == 3) return fail(HQT_ERR_STATE, "three-level model: use hqt_sample_l3");
-    if (c.levels == 3 && (!cf.has_stage2 || cf.code_levels != 3)) return fail(HQT_ERR_STATE, "handle does not hold a three-level stage 2");
-    const int B = c.B;
-    if (B < 1 || B > cf.max_batch) return fail(HQT_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cf.max_batch);
-    if (c.n_steps < 1 || c.n_steps > cf.max_steps) return fail(HQT_ERR_INVALID, "n_steps=%d outside [1, %d]", c.n_steps, cf.max_steps);
-    if (cf.cond_type != HQT_COND_NONE && !cond) return fail(HQT_ERR_INVALID, "cond is required for class/text conditioning");
-    if (c.report.top_n > cf.vocab_top)
-        return fail(HQT_ERR_INVALID, "hqt_set_draw_report staged top_n=%d, this model's vocabulary has %d codes", c.report.top_n, cf.vocab_top);
-    if (c.seg) {
-        if (c.start < 0 || c.stop <= c.start || c.stop > c.n_steps)
-            return fail(HQT_ERR_INVALID, "hqt_set_segment staged [%d, %d): a segment needs 0 <= start < stop <= n_steps = %d", c.start, c.stop, c.n_steps);
-        if (c.with_prefix) return fail(HQT_ERR_INVALID, "hqt_set_segment: the staged segment was taken by a prefix entry point; segments of a pass with a code prefix are not built (hqt_sample / hqt_sample_l3 take the segment)");
-        if (c.keep) return fail(HQT_ERR_INVALID, "hqt_set_segment together with a staged keep table (hqt_set_keep_mask) is not built");
-        if (c.groups && c.start > 0)
-            return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups together with a segment that starts at position %d: the prompt prefill belongs to the segment that starts at 0", c.start);
-        if (c.start > 0) {                       // a continuation: the cache and the step state must be those of THIS pass, stopped in front of `start`
-            const hqt_handle::Paused& p = h->paused;
-            if (!p.live) return fail(HQT_ERR_STATE, "hqt_set_segment: a segment that starts at position %d continues a paused pass, and this handle holds none "
-                                                    "(none was begun, the pass was finished, or another call has overwritten its cache since)", c.start);
-            if (p.B != B) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass has B=%d, this call has B=%d (hqt_select_rows changes the rows of a paused pass)", p.B, B);
-            if (p.n_steps != c.n_steps) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass has n_steps=%d, this call has n_steps=%d", p.n_steps, c.n_steps);
-            if (p.levels != c.levels) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass has %d code levels, this call has %d", p.levels, c.levels);
-            if (p.precision != c.precision) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass runs in precision %d, this call asks for precision %d (the cache holds that precision's type)", p.precision, c.precision);
-            if (p.pos != c.start) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass stands at position %d, this segment has start=%d", p.pos, c.start);
-        }
+// ---- what sample_call refuses, one function per staged feature (segment, row positions, prefix, keep table, prompt groups, row samplers, guidance), called in
+// this order: any two refusals speak in the order of the lines below.  `s` is what the call took off the handle (the sizes the tables were staged with), cf and
+// B the handle's config and the call's rows; what a check computes travels in `c`: start / stop and n_join, prefix_len of a keep table, top_p / row_top_p.
+static int check_segment(const hqt_handle* h, const SampleCtx& c, int B) {
+    if (c.start < 0 || c.stop <= c.start || c.stop > c.n_steps)
+        return fail(HQT_ERR_INVALID, "hqt_set_segment staged [%d, %d): a segment needs 0 <= start < stop <= n_steps = %d", c.start, c.stop, c.n_steps);
+    if (c.with_prefix) return fail(HQT_ERR_INVALID, "hqt_set_segment: the staged segment was taken by a prefix entry point; segments of a pass with a code prefix are not built (hqt_sample / hqt_sample_l3 take the segment)");
+    if (c.keep) return fail(HQT_ERR_INVALID, "hqt_set_segment together with a staged keep table (hqt_set_keep_mask) is not built");
+    if (c.groups && c.start > 0)
+        return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups together with a segment that starts at position %d: the prompt prefill belongs to the segment that starts at 0", c.start);
+    if (c.start > 0) {                       // a continuation: the cache and the step state must be those of THIS pass, stopped in front of `start`
+        const hqt_handle::Paused& p = h->paused;
+        if (!p.live) return fail(HQT_ERR_STATE, "hqt_set_segment: a segment that starts at position %d continues a paused pass, and this handle holds none "
+                                                "(none was begun, the pass was finished, or another call has overwritten its cache since)", c.start);
+        if (p.B != B) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass has B=%d, this call has B=%d (hqt_select_rows changes the rows of a paused pass)", p.B, B);
+        if (p.n_steps != c.n_steps) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass has n_steps=%d, this call has n_steps=%d", p.n_steps, c.n_steps);
+        if (p.levels != c.levels) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass has %d code levels, this call has %d", p.levels, c.levels);
+        if (p.precision != c.precision) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass runs in precision %d, this call asks for precision %d (the cache holds that precision's type)", p.precision, c.precision);
+        if (p.pos != c.start) return fail(HQT_ERR_STATE, "hqt_set_segment: the paused pass stands at position %d, this segment has start=%d", p.pos, c.start);
     }
-    if (c.roll) {
-        const int n = c.n_steps;
-        if (cf.cond_type == HQT_COND_TEXT && h->max_joins < 1) return fail(HQT_ERR_INVALID, "%s", ROLLING_TEXT_REFUSAL);      // (hqt_set_max_joins(0) behind the staging call)
-        if (c.with_prefix) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: the staged positions were taken by a prefix entry point; a rolling pass with a code prefix is not built (hqt_sample / hqt_sample_l3 take the table)");
-        if (c.seg) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged segment (hqt_set_segment) is not built: the k of the table is the call's span");
-        if (c.keep) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged keep table (hqt_set_keep_mask) is not built");
-        if (c.groups) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged prompt-group table (hqt_set_prompt_groups) is not built");
-        if ((int)s.roll.size() != B) return fail(HQT_ERR_INVALID, "hqt_set_row_positions staged a table of B=%d, this call has B=%d", (int)s.roll.size(), B);
-        if (c.roll_k < 1 || c.roll_k > n) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: k=%d outside [1, n_steps = %d]", c.roll_k, n);
-        for (int b = 0; b < B; ++b)
-            if (c.roll[b] < -1 || c.roll[b] > n - 1)
-                return fail(HQT_ERR_INVALID, "hqt_set_row_positions: pos[%d]=%d outside [-1, n_steps - 1 = %d] (-1: an empty slot)", b, c.roll[b], n - 1);
-        for (int i = 0; i < c.n_guide; ++i) {      // (rows outside [0, B) are refused below, by the pair checks of every call)
-            const hqt_guide_pair& p = c.guide[i];
-            if (p.pos_row < 0 || p.pos_row >= B || p.neg_row < 0 || p.neg_row >= B || c.roll[p.pos_row] == c.roll[p.neg_row]) continue;
-            if (c.roll[p.pos_row] < 0 || c.roll[p.neg_row] < 0)
-                return fail(HQT_ERR_INVALID, "guidance pair %d: exactly one of rows %d and %d is an empty slot of the rolling pass (positions %d and %d)", i, p.pos_row, p.neg_row, c.roll[p.pos_row], c.roll[p.neg_row]);
-            return fail(HQT_ERR_INVALID, "guidance pair %d: rows %d and %d stand at different positions of the rolling pass (%d and %d): both rows of a pair draw one position", i, p.pos_row, p.neg_row,
-                        c.roll[p.pos_row], c.roll[p.neg_row]);
-        }
-        // every slot against the rolling pass this handle holds: empty, a join at 0, or exactly where the slot stands
-        const hqt_handle::Rolling& r = h->rolling;
-        if (r.live) {
-            if (r.B != B) return fail(HQT_ERR_STATE, "hqt_set_row_positions: the rolling pass has B=%d, this call has B=%d", r.B, B);
-            if (r.n_steps != n) return fail(HQT_ERR_STATE, "hqt_set_row_positions: the rolling pass has n_steps=%d, this call has n_steps=%d", r.n_steps, n);
-            if (r.levels != c.levels) return fail(HQT_ERR_STATE, "hqt_set_row_positions: the rolling pass has %d code levels, this call has %d", r.levels, c.levels);
-            if (r.precision != c.precision) return fail(HQT_ERR_STATE, "hqt_set_row_positions: the rolling pass runs in precision %d, this call asks for precision %d (the cache holds that precision's type)", r.precision, c.precision);
-        }
-        for (int b = 0; b < B; ++b) {
-            const int want = r.live ? r.next[b] : -1;
-            if (c.roll[b] <= 0 || c.roll[b] == want) continue;
-            if (!r.live) return fail(HQT_ERR_STATE, "hqt_set_row_positions: row %d continues at position %d, and this handle holds no rolling pass (none was begun, or another call has "
-                                                    "overwritten its cache since): every entry must be 0 (join) or -1 (empty)", b, c.roll[b]);
-            if (want < 0) return fail(HQT_ERR_STATE, "hqt_set_row_positions: row %d continues at position %d, but the slot is empty in the rolling pass (0 joins, -1 stays empty)", b, c.roll[b]);
-            return fail(HQT_ERR_STATE, "hqt_set_row_positions: row %d continues at position %d, but the slot stands at position %d of the rolling pass", b, c.roll[b], want);
-        }
-        if (cf.cond_type == HQT_COND_TEXT) {     // the rows that join draw position 0 in a prompt prefill of their own, in front of the steps (sample_run)
-            for (int b = 0; b < B; ++b) c.n_join += c.roll[b] == 0;
-            if (c.n_join > h->max_joins)
-                return fail(HQT_ERR_INVALID, "hqt_set_row_positions: %d rows join at position 0 in this call, the handle's staging holds the prompts of max_joins=%d (hqt_set_max_joins)", c.n_join, h->max_joins);
-            if (c.n_join > h->pg_cap || (c.n_join && (!h->pg_k || !h->pg_v || !h->pg_x)))
-                return fail(HQT_ERR_STATE, "hqt_set_max_joins: the staging buffer holds %d prompts, %d rows join", h->pg_cap, c.n_join);
-        }
-        c.start = 0; c.stop = c.roll_k;
+    return HQT_OK;
+}
+static int check_rolling(const hqt_handle* h, SampleCtx& c, const hqt_handle::Staged& s, const hqt_config& cf, int B) {
+    const int n = c.n_steps;
+    if (cf.cond_type == HQT_COND_TEXT && h->max_joins < 1) return fail(HQT_ERR_INVALID, "%s", ROLLING_TEXT_REFUSAL);      // (hqt_set_max_joins(0) behind the staging call)
+    if (c.with_prefix) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: the staged positions were taken by a prefix entry point; a rolling pass with a code prefix is not built (hqt_sample / hqt_sample_l3 take the table)");
+    if (c.seg) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged segment (hqt_set_segment) is not built: the k of the table is the call's span");
+    if (c.keep) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged keep table (hqt_set_keep_mask) is not built");
+    if (c.groups) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged prompt-group table (hqt_set_prompt_groups) is not built");
+    if ((int)s.roll.size() != B) return fail(HQT_ERR_INVALID, "hqt_set_row_positions staged a table of B=%d, this call has B=%d", (int)s.roll.size(), B);
+    if (c.roll_k < 1 || c.roll_k > n) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: k=%d outside [1, n_steps = %d]", c.roll_k, n);
+    for (int b = 0; b < B; ++b)
+        if (c.roll[b] < -1 || c.roll[b] > n - 1)
+            return fail(HQT_ERR_INVALID, "hqt_set_row_positions: pos[%d]=%d outside [-1, n_steps - 1 = %d] (-1: an empty slot)", b, c.roll[b], n - 1);
+    for (int i = 0; i < c.n_guide; ++i) {      // (rows outside [0, B) are refused below, by the pair checks of every call)
+        const hqt_guide_pair& p = c.guide[i];
+        if (p.pos_row < 0 || p.pos_row >= B || p.neg_row < 0 || p.neg_row >= B || c.roll[p.pos_row] == c.roll[p.neg_row]) continue;
+        if (c.roll[p.pos_row] < 0 || c.roll[p.neg_row] < 0)
+            return fail(HQT_ERR_INVALID, "guidance pair %d: exactly one of rows %d and %d is an empty slot of the rolling pass (positions %d and %d)", i, p.pos_row, p.neg_row, c.roll[p.pos_row], c.roll[p.neg_row]);
+        return fail(HQT_ERR_INVALID, "guidance pair %d: rows %d and %d stand at different positions of the rolling pass (%d and %d): both rows of a pair draw one position", i, p.pos_row, p.neg_row,
+                    c.roll[p.pos_row], c.roll[p.neg_row]);
     }
+    // every slot against the rolling pass this handle holds: empty, a join at 0, or exactly where the slot stands
+    const hqt_handle::Rolling& r = h->rolling;
+    if (r.live) {
+        if (r.B != B) return fail(HQT_ERR_STATE, "hqt_set_row_positions: the rolling pass has B=%d, this call has B=%d", r.B, B);
+        if (r.n_steps != n) return fail(HQT_ERR_STATE, "hqt_set_row_positions: the rolling pass has n_steps=%d, this call has n_steps=%d", r.n_steps, n);
+        if (r.levels != c.levels) return fail(HQT_ERR_STATE, "hqt_set_row_positions: the rolling pass has %d code levels, this call has %d", r.levels, c.levels);
+        if (r.precision != c.precision) return fail(HQT_ERR_STATE, "hqt_set_row_positions: the rolling pass runs in precision %d, this call asks for precision %d (the cache holds that precision's type)", r.precision, c.precision);
+    }
+    for (int b = 0; b < B; ++b) {
+        const int want = r.live ? r.next[b] : -1;
+        if (c.roll[b] <= 0 || c.roll[b] == want) continue;
+        if (!r.live) return fail(HQT_ERR_STATE, "hqt_set_row_positions: row %d continues at position %d, and this handle holds no rolling pass (none was begun, or another call has "
+                                                "overwritten its cache since): every entry must be 0 (join) or -1 (empty)", b, c.roll[b]);
+        if (want < 0) return fail(HQT_ERR_STATE, "hqt_set_row_positions: row %d continues at position %d, but the slot is empty in the rolling pass (0 joins, -1 stays empty)", b, c.roll[b]);
+        return fail(HQT_ERR_STATE, "hqt_set_row_positions: row %d continues at position %d, but the slot stands at position %d of the rolling pass", b, c.roll[b], want);
+    }
+    if (cf.cond_type == HQT_COND_TEXT) {     // the rows that join draw position 0 in a prompt prefill of their own, in front of the steps (sample_run)
+        for (int b = 0; b < B; ++b) c.n_join += c.roll[b] == 0;
+        if (c.n_join > h->max_joins)
+            return fail(HQT_ERR_INVALID, "hqt_set_row_positions: %d rows join at position 0 in this call, the handle's staging holds the prompts of max_joins=%d (hqt_set_max_joins)", c.n_join, h->max_joins);
+        if (c.n_join > h->pg_cap || (c.n_join && (!h->pg_k || !h->pg_v || !h->pg_x)))
+            return fail(HQT_ERR_STATE, "hqt_set_max_joins: the staging buffer holds %d prompts, %d rows join", h->pg_cap, c.n_join);
+    }
+    c.start = 0; c.stop = c.roll_k;
+    return HQT_OK;
+}
+// (the group table is asked about a prefix here, where that test has always stood: behind the rolling table, in front of the prefix's own)
+static int check_prefix(const hqt_handle* h, const SampleCtx& c, const hqt_config& cf) {
     if (c.groups && c.with_prefix)
         return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups together with a code prefix (a prefix entry point) is not built: the prompt and the prefix are one prefill whose prefix rows differ per row");
-    if (c.with_prefix) {
-        if (cf.cond_type == HQT_COND_TEXT && c.levels == 3)
-            return fail(HQT_ERR_INVALID, "a code prefix with text conditioning and three code levels is not built (two code levels are)");
-        if (c.prefix_len < 1 || c.prefix_len >= c.n_steps)
-            return fail(HQT_ERR_INVALID, "prefix_len=%d outside [1, n_steps - 1 = %d]: at least one position must be left to draw", c.prefix_len, c.n_steps - 1);
-        if (c.prefix_len > h->max_prefix)
-            return fail(HQT_ERR_INVALID, "prefix_len=%d exceeds max_prefix=%d of this handle (hqt_set_max_prefix sizes the body workspace for the prefill's rows)", c.prefix_len, h->max_prefix);
-        for (int i = 0; i < c.levels; ++i) if (!c.prefix[i]) return fail(HQT_ERR_INVALID, "prefix codes of level %d are NULL", i);
+    if (!c.with_prefix) return HQT_OK;
+    if (cf.cond_type == HQT_COND_TEXT && c.levels == 3)
+        return fail(HQT_ERR_INVALID, "a code prefix with text conditioning and three code levels is not built (two code levels are)");
+    if (c.prefix_len < 1 || c.prefix_len >= c.n_steps)
+        return fail(HQT_ERR_INVALID, "prefix_len=%d outside [1, n_steps - 1 = %d]: at least one position must be left to draw", c.prefix_len, c.n_steps - 1);
+    if (c.prefix_len > h->max_prefix)
+        return fail(HQT_ERR_INVALID, "prefix_len=%d exceeds max_prefix=%d of this handle (hqt_set_max_prefix sizes the body workspace for the prefill's rows)", c.prefix_len, h->max_prefix);
+    for (int i = 0; i < c.levels; ++i) if (!c.prefix[i]) return fail(HQT_ERR_INVALID, "prefix codes of level %d are NULL", i);
+    return HQT_OK;
+}
+static int check_keep(const hqt_handle* h, SampleCtx& c, const hqt_handle::Staged& s, const hqt_config& cf, int B) {
+    if (c.with_prefix) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: the staged keep table was taken by a prefix entry point; a leading run of the mask is the prefix (hqt_sample / hqt_sample_l3 take the table)");
+    if (s.keep_B != B || s.keep_n != c.n_steps)
+        return fail(HQT_ERR_INVALID, "hqt_set_keep_mask staged a table of B=%d, n_steps=%d, this call has B=%d, n_steps=%d", s.keep_B, s.keep_n, B, c.n_steps);
+    static const char* const fname[2][3] = {{"force_top", "force_bot", ""}, {"force0", "force1", "force2"}};
+    for (int i = 0; i < c.levels; ++i)
+        if (c.feed[i]) return fail(HQT_ERR_INVALID, "%s together with a keep table is not built: put the forced codes into the kept codes (hqt_set_keep_mask)", fname[c.levels == 3][i]);
+    for (int i = 0; i < c.levels; ++i) if (!c.keep_codes[i]) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: kept codes of level %d are NULL", i);
+    // the leading run every row shares goes through the one-pass prefix prefill, where it is built (hqt_set_max_prefix; not text with three code levels)
+    int L = std::min(h->max_prefix, c.n_steps - 1);
+    if (cf.cond_type == HQT_COND_TEXT && c.levels == 3) L = 0;
+    for (int b = 0; b < B && L > 0; ++b) {
+        int run = 0;
+        while (run < L && c.keep[(size_t)b * c.n_steps + run]) ++run;
+        L = run;
     }
-    if (c.keep) {
-        if (c.with_prefix) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: the staged keep table was taken by a prefix entry point; a leading run of the mask is the prefix (hqt_sample / hqt_sample_l3 take the table)");
-        if (s.keep_B != B || s.keep_n != c.n_steps)
-            return fail(HQT_ERR_INVALID, "hqt_set_keep_mask staged a table of B=%d, n_steps=%d, this call has B=%d, n_steps=%d", s.keep_B, s.keep_n, B, c.n_steps);
-        static const char* const fname[2][3] = {{"force_top", "force_bot", ""}, {"force0", "force1", "force2"}};
-        for (int i = 0; i < c.levels; ++i)
-            if (c.feed[i]) return fail(HQT_ERR_INVALID, "%s together with a keep table is not built: put the forced codes into the kept codes (hqt_set_keep_mask)", fname[c.levels == 3][i]);
-        for (int i = 0; i < c.levels; ++i) if (!c.keep_codes[i]) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: kept codes of level %d are NULL", i);
-        // the leading run every row shares goes through the one-pass prefix prefill, where it is built (hqt_set_max_prefix; not text with three code levels)
-        int L = std::min(h->max_prefix, c.n_steps - 1);
-        if (cf.cond_type == HQT_COND_TEXT && c.levels == 3) L = 0;
-        for (int b = 0; b < B && L > 0; ++b) {
-            int run = 0;
-            while (run < L && c.keep[(size_t)b * c.n_steps + run]) ++run;
-            L = run;
-        }
-        c.prefix_len = L;
-    }
-    if (c.groups) {
-        if ((int)s.groups.size() != B) return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups staged a table of B=%d, this call has B=%d", (int)s.groups.size(), B);
-        if (c.prefix_len > 0)
-            return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups together with a code prefix or a keep table whose rows share a leading run (prefix_len=%d) is not built: "
-                                         "the prompt and the prefix are one prefill whose prefix rows differ per row", c.prefix_len);
-        // (the staging holds n_groups prompts: the table and the buffer were sized together by hqt_set_prompt_groups)
-        if (c.n_groups > h->pg_cap || !h->pg_k || !h->pg_v || !h->pg_x) return fail(HQT_ERR_STATE, "hqt_set_prompt_groups: the staging buffer holds %d prompts, the table has %d", h->pg_cap, c.n_groups);
-    }
+    c.prefix_len = L;
+    return HQT_OK;
+}
+static int check_groups(const hqt_handle* h, const SampleCtx& c, const hqt_handle::Staged& s, int B) {
+    if ((int)s.groups.size() != B) return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups staged a table of B=%d, this call has B=%d", (int)s.groups.size(), B);
+    if (c.prefix_len > 0)
+        return fail(HQT_ERR_INVALID, "hqt_set_prompt_groups together with a code prefix or a keep table whose rows share a leading run (prefix_len=%d) is not built: "
+                                     "the prompt and the prefix are one prefill whose prefix rows differ per row", c.prefix_len);
+    // (the staging holds n_groups prompts: the table and the buffer were sized together by hqt_set_prompt_groups)
+    if (c.n_groups > h->pg_cap || !h->pg_k || !h->pg_v || !h->pg_x) return fail(HQT_ERR_STATE, "hqt_set_prompt_groups: the staging buffer holds %d prompts, the table has %d", h->pg_cap, c.n_groups);
+    return HQT_OK;
+}
+static int check_samplers(SampleCtx& c, const hqt_handle::Staged& s, const hqt_config& cf, int B) {
     if (c.row_set) {                             // per-row settings replace the scalars of `opts`: those are neither checked nor part of the graph key
         if ((int)s.row_set.size() != B) return fail(HQT_ERR_INVALID, "hqt_set_row_samplers staged %d rows, this call has B=%d", (int)s.row_set.size(), B);
         for (int i = 0; i < 3; ++i) c.lv[i] = SamplerSet();
@@ -2006,40 +1981,100 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
         }
     if (c.top_p && cf.vocab_top > 8192) return fail(HQT_ERR_INVALID, "top-p needs vocab <= 8192");
     c.row_top_p = c.row_set && c.top_p;
-    if (c.guide) {
-        if (cf.cond_type == HQT_COND_NONE) return fail(HQT_ERR_INVALID, "guidance needs a conditional model: this handle has cond_type HQT_COND_NONE, its rows have no condition to differ in");
-        if ((c.row_seeds || c.row_offsets) && (!c.row_seeds || !c.row_offsets)) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
-        std::vector<char> paired(B, 0);
-        for (int i = 0; i < c.n_guide; ++i) {
-            const hqt_guide_pair& p = c.guide[i];
-            if (p.pos_row < 0 || p.pos_row >= B || p.neg_row < 0 || p.neg_row >= B)
-                return fail(HQT_ERR_INVALID, "guidance pair %d: rows (%d, %d) outside [0, B=%d)", i, p.pos_row, p.neg_row, B);
-            if (p.pos_row == p.neg_row) return fail(HQT_ERR_INVALID, "guidance pair %d: pos_row == neg_row == %d", i, p.pos_row);
-            if (paired[p.pos_row] || paired[p.neg_row])
-                return fail(HQT_ERR_INVALID, "guidance pair %d: row %d appears in more than one pair", i, paired[p.pos_row] ? p.pos_row : p.neg_row);
-            paired[p.pos_row] = paired[p.neg_row] = 1;
-            for (int l = 0; l < c.levels; ++l)
-                if (!std::isfinite(p.scale[l])) return fail(HQT_ERR_INVALID, "guidance pair %d: scale[%d] is not finite", i, l);
-            // both rows must draw the same code from the same (guided) logits: same settings, same Philox key
-            if (c.row_set && memcmp(&c.row_set[p.pos_row], &c.row_set[p.neg_row], sizeof(hqt_row_sampler)))
-                return fail(HQT_ERR_INVALID, "guidance pair %d: rows %d and %d have different sampler settings in the staged row-sampler table", i, p.pos_row, p.neg_row);
-            if (c.keep && memcmp(c.keep + (size_t)p.pos_row * c.n_steps, c.keep + (size_t)p.neg_row * c.n_steps, (size_t)c.n_steps))
-                return fail(HQT_ERR_INVALID, "guidance pair %d: rows %d and %d have different rows in the staged keep table (both rows of a pair keep the same positions)", i, p.pos_row, p.neg_row);
-            if (c.row_seeds && (c.row_seeds[p.pos_row] != c.row_seeds[p.neg_row] || c.row_offsets[p.pos_row] != c.row_offsets[p.neg_row]))
-                return fail(HQT_ERR_INVALID, "guidance pair %d: row_seeds / row_offsets give rows %d and %d different keys (both rows of a pair must draw with one key)", i, p.pos_row, p.neg_row);
-        }
+    return HQT_OK;
+}
+static int check_guidance(const SampleCtx& c, const hqt_config& cf, int B) {
+    if (cf.cond_type == HQT_COND_NONE) return fail(HQT_ERR_INVALID, "guidance needs a conditional model: this handle has cond_type HQT_COND_NONE, its rows have no condition to differ in");
+    if ((c.row_seeds || c.row_offsets) && (!c.row_seeds || !c.row_offsets)) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
+    std::vector<char> paired(B, 0);
+    for (int i = 0; i < c.n_guide; ++i) {
+        const hqt_guide_pair& p = c.guide[i];
+        if (p.pos_row < 0 || p.pos_row >= B || p.neg_row < 0 || p.neg_row >= B)
+            return fail(HQT_ERR_INVALID, "guidance pair %d: rows (%d, %d) outside [0, B=%d)", i, p.pos_row, p.neg_row, B);
+        if (p.pos_row == p.neg_row) return fail(HQT_ERR_INVALID, "guidance pair %d: pos_row == neg_row == %d", i, p.pos_row);
+        if (paired[p.pos_row] || paired[p.neg_row])
+            return fail(HQT_ERR_INVALID, "guidance pair %d: row %d appears in more than one pair", i, paired[p.pos_row] ? p.pos_row : p.neg_row);
+        paired[p.pos_row] = paired[p.neg_row] = 1;
+        for (int l = 0; l < c.levels; ++l)
+            if (!std::isfinite(p.scale[l])) return fail(HQT_ERR_INVALID, "guidance pair %d: scale[%d] is not finite", i, l);
+        // both rows must draw the same code from the same (guided) logits: same settings, same Philox key
+        if (c.row_set && memcmp(&c.row_set[p.pos_row], &c.row_set[p.neg_row], sizeof(hqt_row_sampler)))
+            return fail(HQT_ERR_INVALID, "guidance pair %d: rows %d and %d have different sampler settings in the staged row-sampler table", i, p.pos_row, p.neg_row);
+        if (c.keep && memcmp(c.keep + (size_t)p.pos_row * c.n_steps, c.keep + (size_t)p.neg_row * c.n_steps, (size_t)c.n_steps))
+            return fail(HQT_ERR_INVALID, "guidance pair %d: rows %d and %d have different rows in the staged keep table (both rows of a pair keep the same positions)", i, p.pos_row, p.neg_row);
+        if (c.row_seeds && (c.row_seeds[p.pos_row] != c.row_seeds[p.neg_row] || c.row_offsets[p.pos_row] != c.row_offsets[p.neg_row]))
+            return fail(HQT_ERR_INVALID, "guidance pair %d: row_seeds / row_offsets give rows %d and %d different keys (both rows of a pair must draw with one key)", i, p.pos_row, p.neg_row);
     }
+    return HQT_OK;
+}
+
+// What the hqt_set_* calls staged, as the call reads it: the host tables stay with `s`
+static void ctx_from_staged(SampleCtx& c, const hqt_handle::Staged& s) {
+    c.row_set = s.row_set.empty() ? nullptr : s.row_set.data();
+    c.logprob_out = s.logprob; c.report = s.report;
+    c.guide = s.guide.empty() ? nullptr : s.guide.data(); c.n_guide = (int)s.guide.size();
+    c.keep = s.keep.empty() ? nullptr : s.keep.data();
+    for (int i = 0; i < 3; ++i) c.keep_codes[i] = s.keep_codes[i];
+    c.groups = s.groups.empty() ? nullptr : s.groups.data(); c.n_groups = c.groups ? s.groups_G : 0;
+    c.seg = s.seg; c.start = c.seg ? s.seg_start : 0; c.stop = c.seg ? s.seg_stop : c.n_steps;
+    c.roll = s.roll.empty() ? nullptr : s.roll.data(); c.roll_k = s.roll_k;
+}
+// Behind a rolling call (`drew`: it ran steps; only empty slots draws and launches nothing): the positions drawn go to the caller's tensors, every slot's next one to the handle
+static int finish_rolling(hqt_handle* h, const SampleCtx& c, int64_t* const* out, bool drew) {
+    const int B = c.B;
+    for (int i = 0; i < (drew ? c.levels : 0); ++i) {
+        HIPCHK(launch_copy_row_positions(c.out[i], out[i], h->row_pos_received(), B, c.n_steps, LEVEL_WIDTH[i], 0, c.roll_k, c.st));
+        // a joining row of a text pass drew positions [0, 1 + k): its last one through the join table (0 for the joiners, -1 for every other row)
+        if (c.n_join) HIPCHK(launch_copy_row_positions(c.out[i], out[i], h->row_pos_join(), B, c.n_steps, LEVEL_WIDTH[i], c.roll_k, c.roll_k + 1, c.st));
+    }
+    hqt_handle::Rolling& r = h->rolling;
+    r.B = B; r.n_steps = c.n_steps; r.levels = c.levels; r.precision = c.precision;
+    r.next.assign(B, -1);
+    for (int b = 0; b < B; ++b) r.next[b] = rolled_to(h->cfg, c.roll[b], c.roll_k, c.n_steps);
+    r.live = std::any_of(r.next.begin(), r.next.end(), [](int32_t p) { return p >= 0; });      // every slot empty: the pass is over, nothing is left to match
+    return HQT_OK;
+}
+// Behind a segment: its positions go to the caller's tensors, and a pass that is not finished stays on the handle as the paused one
+static int finish_segment(hqt_handle* h, const SampleCtx& c, int64_t* const* out) {
+    for (int i = 0; i < c.levels; ++i) HIPCHK(launch_copy_positions(c.out[i], out[i], c.B, c.n_steps, LEVEL_WIDTH[i], c.start, c.stop, c.st));
+    if (c.stop < c.n_steps) h->paused = hqt_handle::Paused{true, c.B, c.n_steps, c.levels, c.precision, c.stop};
+    return HQT_OK;
+}
+static int copy_out(const SampleCtx& c, int64_t* const* out) {
+    for (int i = 0; i < c.levels; ++i) HIPCHK(hipMemcpyAsync(out[i], c.out[i], (size_t)c.B * c.n_steps * LEVEL_WIDTH[i] * 8, hipMemcpyDeviceToDevice, c.st));
+    return HQT_OK;
+}
+
+// hqt_sample / hqt_sample_l3 after their null checks: `c` holds the call's options, sampler settings and forced codes (feed); validates them,
+// runs the call and copies the drawn codes of every level out
+static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t* const* out, void* stream) {
+    // what was staged belongs to THIS call and to no later one, whatever becomes of the call; `s` owns the host tables until it returns
+    const hqt_handle::Staged s = h->take_staged();
+    ctx_from_staged(c, s);
+    if (!h->finalized) return fail(HQT_ERR_STATE, "hqt_finalize_weights has not run");
+    const hqt_config& cf = h->cfg;
+    if (c.levels == 2 && !cf.has_stage2) return fail(HQT_ERR_STATE, "handle was created without stage 2");
+    if (c.levels == 2 && cf.code_levels == 3) return fail(HQT_ERR_STATE, "three-level model: use hqt_sample_l3");
+    if (c.levels == 3 && (!cf.has_stage2 || cf.code_levels != 3)) return fail(HQT_ERR_STATE, "handle does not hold a three-level stage 2");
+    const int B = c.B;
+    if (B < 1 || B > cf.max_batch) return fail(HQT_ERR_INVALID, "B=%d outside [1, max_batch=%d]", B, cf.max_batch);
+    if (c.n_steps < 1 || c.n_steps > cf.max_steps) return fail(HQT_ERR_INVALID, "n_steps=%d outside [1, %d]", c.n_steps, cf.max_steps);
+    if (cf.cond_type != HQT_COND_NONE && !cond) return fail(HQT_ERR_INVALID, "cond is required for class/text conditioning");
+    if (c.report.top_n > cf.vocab_top)
+        return fail(HQT_ERR_INVALID, "hqt_set_draw_report staged top_n=%d, this model's vocabulary has %d codes", c.report.top_n, cf.vocab_top);
+    if (c.seg) CHK(check_segment(h, c, B));
+    if (c.roll) CHK(check_rolling(h, c, s, cf, B));
+    CHK(check_prefix(h, c, cf));
+    if (c.keep) CHK(check_keep(h, c, s, cf, B));
+    if (c.groups) CHK(check_groups(h, c, s, B));
+    CHK(check_samplers(c, s, cf, B));
+    if (c.guide) CHK(check_guidance(c, cf, B));
     ON_DEVICE(h);
-    // The launch sequence reads cond and writes the drawn codes in buffers owned by the handle, and takes the Philox seed
-    // and the global row offset from device memory: nothing that changes from call to call is baked into the captured
-    // graph, so a steady stream of batches replays ONE graph (no re-capture, no exec destroyed under pending launches).
+    // The launch sequence reads cond and writes the drawn codes in buffers owned by the handle, and takes the Philox seed and the global row offset from device memory: nothing
+    // that changes from call to call is baked into the captured graph, so a steady stream of batches replays ONE graph (no re-capture, no exec destroyed under pending launches).
     int64_t* codes[3] = {h->codes_top, h->codes_bot, h->codes_l2};
-    for (int i = 0; i < c.levels; ++i) {
-        if (!c.feed[i]) c.feed[i] = codes[i];
-        c.out[i] = codes[i];
-    }
-    c.cond = cond ? h->cond_buf : nullptr;
-    c.st = (hipStream_t)stream;
+    for (int i = 0; i < c.levels; ++i) { c.out[i] = codes[i]; if (!c.feed[i]) c.feed[i] = codes[i]; }
+    c.cond = cond ? h->cond_buf : nullptr; c.st = (hipStream_t)stream;
     CHK(mode_of(c.precision, false, &c.md));
     CHK(layout_check(h, c.md));
     // (a group table: cond is [n_groups, ctx_len_txt], n_groups <= B)
@@ -2054,36 +2089,16 @@ static int sample_call(hqt_handle* h, SampleCtx& c, const int64_t* cond, int64_t
     if (c.roll) {
         c.row_pos = h->row_pos;
         for (int i = 0; i < c.levels; ++i) c.roll_prev[i] = out[i];
-        bool any = false;
-        for (int b = 0; b < B; ++b) any = any || c.roll[b] >= 0;
-        if (any) {                               // (only empty slots: legal, draws nothing, launches nothing)
-            CHK(sample_run(h, c));
-            for (int i = 0; i < c.levels; ++i) {
-                HIPCHK(launch_copy_row_positions(codes[i], out[i], h->row_pos_received(), B, c.n_steps, LEVEL_WIDTH[i], 0, c.roll_k, c.st));
-                // a joining row of a text pass drew positions [0, 1 + k): its last one through the join table (0 for the joiners, -1 for every other row)
-                if (c.n_join) HIPCHK(launch_copy_row_positions(codes[i], out[i], h->row_pos_join(), B, c.n_steps, LEVEL_WIDTH[i], c.roll_k, c.roll_k + 1, c.st));
-            }
-        }
-        hqt_handle::Rolling& r = h->rolling;
-        r.live = true; r.B = B; r.n_steps = c.n_steps; r.levels = c.levels; r.precision = c.precision;
-        r.next.assign(B, -1);
-        for (int b = 0; b < B; ++b) r.next[b] = rolled_to(cf, c.roll[b], c.roll_k, c.n_steps);
-        r.live = std::any_of(r.next.begin(), r.next.end(), [](int32_t p) { return p >= 0; });      // every slot empty: the pass is over, nothing is left to match
-        return HQT_OK;
+        const bool any = std::any_of(c.roll, c.roll + B, [](int32_t p) { return p >= 0; });
+        if (any) CHK(sample_run(h, c));
+        return finish_rolling(h, c, out, any);
     }
     // a continuation reads the codes of position start - 1 where the caller holds them: a level that is not forced takes them from out_* (the caller may have
     // edited them, or gathered its rows along with hqt_select_rows)
     for (int i = 0; i < (c.start > 0 ? c.levels : 0); ++i)
         if (c.feed[i] == codes[i]) HIPCHK(launch_copy_positions(out[i], codes[i], B, c.n_steps, LEVEL_WIDTH[i], c.start - 1, c.start, c.st));
     CHK(sample_run(h, c));
-    if (!c.seg) {
-        for (int i = 0; i < c.levels; ++i)
-            HIPCHK(hipMemcpyAsync(out[i], codes[i], (size_t)B * c.n_steps * LEVEL_WIDTH[i] * 8, hipMemcpyDeviceToDevice, c.st));
-        return HQT_OK;
-    }
-    for (int i = 0; i < c.levels; ++i) HIPCHK(launch_copy_positions(codes[i], out[i], B, c.n_steps, LEVEL_WIDTH[i], c.start, c.stop, c.st));
-    if (c.stop < c.n_steps) h->paused = hqt_handle::Paused{true, B, c.n_steps, c.levels, c.precision, c.stop};
-    return HQT_OK;
+    return c.seg ? finish_segment(h, c, out) : copy_out(c, out);
 }
 
 // the options both entry points share
@@ -2315,18 +2330,11 @@ extern "C" int hqt_sample_prefix_l3(hqt_handle* h, int B, const int64_t* cond, c
 }
 
 // hqt_score: the log-probability of GIVEN codes in one teacher-forced pass (the reference's eval-mode forward, hierarchical_ar.py:246-426,
-// hqtransformer.py:226-407).  Body: the prefix prefill with P = n - 1 -- copy_prefix, embed_prefix (text: embed_text + the prefix rows), run_body with
-// t_base = 0 over n (text: T + n - 1) rows per sample, the classic LayerNorm path (a single row per sample, n = 1 without text, is the decode step's
-// embedding and may take the deferred one; never the persistent chain: the step state is not where t_base comes from).  Depth: a (sample, position) pair
-// p = b n + t is a depth "sample"; chunks of at most score_chunk pairs (default max_batch) run the sub-step schedule of run_position -- input rows,
-// run_depth with the chunk's pair count as batch, run_head, the log-probabilities -- with no sampler, no guidance and no draws.  Eager, no graph.
-extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_t* const* codes, int n, int precision, float* logprobs,
-                         float* const* logits_out, void* stream) {
-    if (!h) return fail(HQT_ERR_INVALID, "null handle");
-    // a staged table or buffer belongs to a sampling call: it must not wait for a later one behind this call
-    const bool staged = h->staged.holds_table();
-    const ReportOut report = h->staged.report;     // a staged draw report is this call's (hqt_set_draw_report); taken and cleared whatever becomes of the call
-    h->clear_staged();
+// hqtransformer.py:226-407).  Body (score_body): the prefix prefill with P = n - 1 -- copy_prefix, embed_prefix (text: embed_text + the prefix rows), run_body with t_base = 0
+// over n (text: T + n - 1) rows per sample, the classic LayerNorm path (a single row per sample, n = 1 without text, is the decode step's embedding and may take the deferred
+// one; never the persistent chain: the step state is not where t_base comes from).  Depth (score_depth_chunk): a (sample, position) pair p = b n + t is a depth "sample";
+// chunks of at most score_chunk pairs (default max_batch).  Eager, no graph.  score_check: what the call refuses, in this order.
+static int score_check(const hqt_handle* h, bool staged, int B, const int64_t* cond, const int64_t* const* codes, int n, const float* logprobs, const ReportOut& report) {
     if (staged) return fail(HQT_ERR_STATE, "hqt_score: a row-sampler table, guidance pair table, keep table, prompt-group table or log-probability buffer was staged on this handle "
                             "(hqt_set_row_samplers / hqt_set_guidance / hqt_set_logprob_out / hqt_set_keep_mask / hqt_set_prompt_groups): they belong to a sampling call and were cleared");
     if (!logprobs) return fail(HQT_ERR_INVALID, "hqt_score: logprobs is NULL");
@@ -2347,98 +2355,106 @@ extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_
         return fail(HQT_ERR_INVALID, "hqt_set_draw_report staged top_n=%d, this model's vocabulary has %d codes", report.top_n, cf.vocab_top);
     if (n - 1 > h->max_prefix)
         return fail(HQT_ERR_STATE, "hqt_score: n=%d positions need max_prefix >= %d, this handle has %d (hqt_set_max_prefix sizes the body workspace for the pass's rows)", n, n - 1, h->max_prefix);
+    return HQT_OK;
+}
+// hqt_score's body pass over the codes in the handle's buffers: n rows per sample (text: the T prompt rows, then the input rows of positions 1 .. n - 1); *Tq: those rows
+static int score_body(hqt_handle* h, const SampleCtx& c, int* Tq) {
+    if (h->cfg.cond_type == HQT_COND_TEXT || c.n_steps > 1) CHK(embed_prefill(h, c, c.feed, c.n_steps - 1, Tq));
+    else CHK(embed_step(h, c));                    // one row per sample (*Tq stays 1): the decode step's embedding at step 0
+    bool pfull = false;
+    CHK(run_body(h, c, *Tq, 0, false, false, &pfull));
+    return fold_pending(h, c, c.B * *Tq);
+}
+// The depth head over the np = cc.B pairs [p0, p0 + np) of the score pass (pair p = b n + t reads body row b Tq + row_off + t): the sub-step schedule of
+// run_depth_head -- input rows, run_depth with the pair count as batch, run_head, the log-probabilities -- with no sampler, no guidance and no draws
+static int score_depth_chunk(hqt_handle* h, const SampleCtx& cc, int p0, int Tq, int row_off, float* logprobs, float* const* logits_out, const ReportOut& report) {
+    const hqt_config& cf = h->cfg;
+    const int D = cf.embed_dim, V = cf.vocab_top, np = cc.B, n = cc.n_steps, draws = h->depth_rows;
+    const bool bidir = cf.depth_decoding == HQT_DEPTH_BIDIRECTIONAL;
+    const int dmul = cf.depth_decoding == HQT_DEPTH_PARALLEL_REDUCE ? 4 : 1;
+    // ln_f of every pair's body row + sos_depth -> the input rows of sub-step 0: M = np, or the bidirectional pass's 5 np, four rows behind each `fill`ed with the depth positions
+    auto depth_input = [&](bool dln, int M, const float* fill) {
+        Timed t(h, "score_depth_input", cc.st);
+        LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, np, D, 1, 0, 1e-5f, DT_F32, 0,
+                  nullptr, 0, 0, nullptr, dln ? h->xdpk : nullptr, dln ? packed_mb(M) : 0, h->partsd};
+        ln.fill = fill;
+        HIPCHK(launch_score_depth_input(ln, p0, n, Tq, row_off, cc.st));
+        h->npartsd = 1;
+        return (int)HQT_OK;
+    };
+    void* normed[3] = {nullptr, nullptr, nullptr};
+    if (bidir) {                  // one pass of the depth blocks over five rows per pair (run_depth_head)
+        const int M = np * h->depth_rows;
+        const bool dln = dln_ok(h, cc, h->depth[0], M);
+        CHK(depth_input(dln, M, W(h, "pos_emb_depth.weight")));
+        CHK(run_bidir_tail(h, cc, dln, normed));
+    }
+    for (int sub = 0; sub < cc.levels; ++sub) {
+        const SubStep s = sub_step(cf, sub);
+        const int M = np * s.Tq;
+        const bool dln = depth_dln(h, cc, s);
+        if (!bidir) {
+            bf16_t* xpk = dln ? h->xdpk : nullptr;
+            const int pk = dln ? packed_mb(M) : 0;
+            if (sub == 0) {
+                CHK(depth_input(dln, M, nullptr));
+            } else {
+                Timed t(h, "embed", cc.st);
+                if (sub == 1) HIPCHK(launch_score_depth_embed(cc.feed[0], p0, np, W(h, "tok_emb_top_depth.weight"), W(h, "pos_emb_depth.weight"), h->xd, D, xpk, pk, h->partsd, cc.st, V, dmul * D));
+                else HIPCHK(launch_score_depth_embed_l2(cc.feed[0], cc.feed[1], p0, np, cf.depth_decoding == HQT_DEPTH_PARALLEL_ADD ? W(h, "tok_emb_top_depth.weight") : nullptr,
+                                                        W(h, "tok_emb_depth_levels.1.weight"), W(h, "pos_emb_depths.1.weight"), h->xd, D, xpk, pk, h->partsd, cc.st, V, dmul * D));
+            }
+            h->npartsd = 1;
+            CHK(run_depth(h, cc, dln, s.Tq, s.tbase));
+        }
+        // the head GEMM writes the caller's buffer directly where one is given: rows of a level are contiguous over pairs
+        float* lg = (logits_out && logits_out[s.lv]) ? logits_out[s.lv] + (size_t)p0 * s.Tq * V : h->logits;
+        CHK(run_head(h, cc, head_of(h, s.lv), s.lv, M, dln, normed[s.lv], lg));
+        {
+            Timed t(h, "score_logprob", cc.st);
+            HIPCHK(launch_score_logprob(lg, cc.feed[s.lv] + (size_t)p0 * s.Tq, logprobs + (size_t)p0 * draws, np, V, s.Tq, s.tbase, draws, cc.st));
+        }
+        if (report.any()) {       // the chunk's (pair, slot) rows of this level in one launch, over the logits the log-probabilities were read from
+            Timed t(h, "draw_report", cc.st);
+            HIPCHK(launch_score_report(lg, cc.feed[s.lv] + (size_t)p0 * s.Tq, report, p0, np, V, s.Tq, s.tbase, draws, cc.st));
+        }
+    }
+    return HQT_OK;
+}
+
+extern "C" int hqt_score(hqt_handle* h, int B, const int64_t* cond, const int64_t* const* codes, int n, int precision, float* logprobs,
+                         float* const* logits_out, void* stream) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    // a staged table or buffer belongs to a sampling call: it must not wait for a later one behind this call
+    const bool staged = h->staged.holds_table();
+    const ReportOut report = h->staged.report;     // a staged draw report is this call's (hqt_set_draw_report); taken and cleared whatever becomes of the call
+    h->clear_staged();
+    CHK(score_check(h, staged, B, cond, codes, n, logprobs, report));
+    const hqt_config& cf = h->cfg;
+    const bool text = cf.cond_type == HQT_COND_TEXT;
     SampleCtx c{};
-    c.levels = levels; c.B = B; c.n_steps = n; c.precision = precision; c.st = (hipStream_t)stream;
+    c.levels = cf.code_levels == 3 ? 3 : 2; c.B = B; c.n_steps = n; c.precision = precision; c.st = (hipStream_t)stream;
     CHK(mode_of(precision, false, &c.md));
     CHK(layout_check(h, c.md));
     ON_DEVICE(h);
     int64_t* const own[3] = {h->codes_top, h->codes_bot, h->codes_l2};
     if (cond) HIPCHK(hipMemcpyAsync(h->cond_buf, cond, (size_t)B * (text ? cf.ctx_len_txt : 1) * 8, hipMemcpyDefault, c.st));
     c.cond = cond ? h->cond_buf : nullptr;
-    for (int i = 0; i < levels; ++i) {             // [B, n, width]: the handle's code buffers hold the pairs contiguously, pair p at index p
+    for (int i = 0; i < c.levels; ++i) {           // [B, n, width]: the handle's code buffers hold the pairs contiguously, pair p at index p
         HIPCHK(launch_copy_prefix(codes[i], own[i], B, n, n, LEVEL_WIDTH[i], cf.vocab_top, c.st));
         c.feed[i] = own[i]; c.out[i] = own[i];
     }
     h->paused.live = false;                        // the pass overwrites the body cache and the step state: a paused pass (hqt_set_segment) is over
     h->rolling.live = false;                       // ... and so is a rolling pass (hqt_set_row_positions)
     HIPCHK(launch_set_step(h->state, 0, 0, c.st));
-    // ---- body: n rows per sample (text: the T prompt rows, then the input rows of positions 1 .. n - 1)
-    const int D = cf.embed_dim, V = cf.vocab_top, T = text ? cf.ctx_len_txt : 0;
-    const int row_off = text ? T - 1 : 0;          // body row of pair (b, t): b Tq + row_off + t
     int Tq = 1;
-    if (text || n > 1) {
-        CHK(embed_prefill(h, c, own, n - 1, &Tq));
-    } else {                                       // one row per sample: the decode step's embedding at step 0 (with the packed copy where run_body wants it)
-        Timed t(h, "embed", c.st);
-        EmbedArgs e = embed_args(h, c, own);
-        if (dln_ok(h, c, h->body[0], B)) { e.xpk = h->xpk; e.pk_mb = packed_mb(B); h->nparts = 1; }
-        HIPCHK(launch_embed_step(e, c.st));
-    }
-    bool pfull = false;
-    CHK(run_body(h, c, Tq, 0, false, false, &pfull));
-    CHK(fold_pending(h, c, B * Tq));
-    // ---- depth: chunks of pairs
-    const Lin* heads[3] = {&h->head_top, &h->head_bot, &h->head_l2};
-    const int64_t* const feed[3] = {h->codes_top, h->codes_bot, h->codes_l2};
-    const bool bidir = cf.depth_decoding == HQT_DEPTH_BIDIRECTIONAL;
-    const int dmul = cf.depth_decoding == HQT_DEPTH_PARALLEL_REDUCE ? 4 : 1;
-    const int chunk = h->score_chunk > 0 ? h->score_chunk : cf.max_batch, total = B * n, draws = h->depth_rows;
+    CHK(score_body(h, c, &Tq));
+    // the depth head in chunks of pairs; body row of pair (b, t): b Tq + row_off + t
+    const int row_off = text ? cf.ctx_len_txt - 1 : 0, chunk = h->score_chunk > 0 ? h->score_chunk : cf.max_batch, total = B * n;
     SampleCtx cc = c;
     for (int p0 = 0; p0 < total; p0 += chunk) {
-        const int np = std::min(chunk, total - p0);
-        cc.B = np;
-        auto dln_of = [&](const SubStep& s) { return !bidir && dln_ok(h, cc, h->depth[0], np * s.Tq) && heads[s.lv]->wpk_ln; };
-        void* normed[3] = {nullptr, nullptr, nullptr};
-        if (bidir) {              // one pass of the depth blocks over five rows per pair (run_position)
-            const int M = np * h->depth_rows;
-            const bool dln = dln_ok(h, cc, h->depth[0], M);
-            {
-                Timed t(h, "score_depth_input", c.st);
-                LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, np, D, 1, 0, 1e-5f, DT_F32, 0,
-                          nullptr, 0, 0, nullptr, dln ? h->xdpk : nullptr, dln ? packed_mb(M) : 0, h->partsd};
-                ln.fill = W(h, "pos_emb_depth.weight");
-                HIPCHK(launch_score_depth_input(ln, p0, n, Tq, row_off, c.st));
-                h->npartsd = 1;
-            }
-            CHK(run_bidir_tail(h, cc, dln, normed));
-        }
-        for (int sub = 0; sub < levels; ++sub) {
-            const SubStep s = sub_step(cf, sub);
-            const int M = np * s.Tq;
-            const bool dln = dln_of(s);
-            if (!bidir) {
-                bf16_t* xpk = dln ? h->xdpk : nullptr;
-                const int pk = dln ? packed_mb(M) : 0;
-                if (sub == 0) {
-                    Timed t(h, "score_depth_input", c.st);
-                    LNArgs ln{h->x, W(h, "ln_f.weight"), W(h, "ln_f.bias"), W(h, "sos_depth"), h->xd, np, D, 1, 0, 1e-5f, DT_F32, 0,
-                              nullptr, 0, 0, nullptr, xpk, pk, h->partsd};
-                    HIPCHK(launch_score_depth_input(ln, p0, n, Tq, row_off, c.st));
-                } else if (sub == 1) {
-                    Timed t(h, "embed", c.st);
-                    HIPCHK(launch_score_depth_embed(feed[0], p0, np, W(h, "tok_emb_top_depth.weight"), W(h, "pos_emb_depth.weight"), h->xd, D, xpk, pk, h->partsd,
-                                                    c.st, V, dmul * D));
-                } else {
-                    Timed t(h, "embed", c.st);
-                    HIPCHK(launch_score_depth_embed_l2(feed[0], feed[1], p0, np, cf.depth_decoding == HQT_DEPTH_PARALLEL_ADD ? W(h, "tok_emb_top_depth.weight") : nullptr,
-                                                       W(h, "tok_emb_depth_levels.1.weight"), W(h, "pos_emb_depths.1.weight"), h->xd, D, xpk, pk, h->partsd,
-                                                       c.st, V, dmul * D));
-                }
-                h->npartsd = 1;
-                CHK(run_depth(h, cc, dln, s.Tq, s.tbase));
-            }
-            // the head GEMM writes the caller's buffer directly where one is given: rows of a level are contiguous over pairs
-            float* lg = (logits_out && logits_out[s.lv]) ? logits_out[s.lv] + (size_t)p0 * s.Tq * V : h->logits;
-            CHK(run_head(h, cc, *heads[s.lv], s.lv, M, dln, normed[s.lv], lg));
-            {
-                Timed t(h, "score_logprob", c.st);
-                HIPCHK(launch_score_logprob(lg, feed[s.lv] + (size_t)p0 * s.Tq, logprobs + (size_t)p0 * draws, np, V, s.Tq, s.tbase, draws, c.st));
-            }
-            if (report.any()) {       // the chunk's (pair, slot) rows of this level in one launch, over the logits the log-probabilities were read from
-                Timed t(h, "draw_report", c.st);
-                HIPCHK(launch_score_report(lg, feed[s.lv] + (size_t)p0 * s.Tq, report, p0, np, V, s.Tq, s.tbase, draws, c.st));
-            }
-        }
+        cc.B = std::min(chunk, total - p0);
+        CHK(score_depth_chunk(h, cc, p0, Tq, row_off, logprobs, logits_out, report));
     }
     return HQT_OK;
 }
@@ -2470,135 +2486,158 @@ struct PersistOrder {
     }
 };
 
+// The host tables of a call (B <= max_batch entries each) through ONE slot of the pinned ring to their device buffers.  Merged steps: per-row Philox keys and / or
+// sampler settings; a guided call: its pair table, and ALWAYS the keys -- the implicit ones (seed, sample_offset + b) are built here, the negative row of every pair taking its positive row's
+static int send_row_tables(hqt_handle* h, const SampleCtx& c) {
+    if (!(c.row_seeds || c.row_set || c.guide || c.keep || c.groups || c.roll)) return HQT_OK;
+    const int B = c.B;
+    int slot = 0;
+    RingSlot ring;
+    CHK(rows_ring_take(h, &slot, &ring));
+    if (c.row_seeds || c.guide) {
+        for (int b = 0; b < B; ++b) {
+            ring.keys[b].seed = c.row_seeds ? c.row_seeds[b] : c.seed;
+            ring.keys[b].global_row = c.row_offsets ? c.row_offsets[b] : c.sample_offset + b;
+        }
+        for (int i = 0; i < c.n_guide; ++i) ring.keys[c.guide[i].neg_row] = ring.keys[c.guide[i].pos_row];      // (explicit keys were checked to agree: sample_call)
+        CHK(ring_send(ring.keys, (const RowKey*)nullptr, (size_t)B, h->rows, c.st));
+    }
+    if (c.row_set) CHK(ring_send(ring.samplers, c.row_set, (size_t)B, h->row_set, c.st));
+    if (c.guide) CHK(ring_send(ring.pairs, c.guide, (size_t)c.n_guide, h->guide, c.st));
+    if (c.keep) CHK(ring_send(ring.keep, c.keep, (size_t)B * c.n_steps, h->keep_mask, c.st));
+    if (c.groups) CHK(ring_send(ring.groups, c.groups, (size_t)B, h->group_of_row, c.st));
+    if (c.roll) {
+        // the positions the rows stand at (moved on between the steps) and the table as received (what finish_rolling copies out by).  Joining rows of a text pass: the live
+        // table has them behind the join phase already (position 1; n_steps = 1: finished), the join table says 0 for them, -1 for the rest, the fan-out's groups number them
+        int32_t *live = ring.pos, *received = ring.pos + h->cfg.max_batch, *join = ring.pos + 2 * (size_t)h->cfg.max_batch;
+        int g = 0;
+        for (int b = 0; b < B; ++b) {
+            const bool joins = c.n_join && c.roll[b] == 0;
+            received[b] = c.roll[b];
+            live[b] = joins ? (c.n_steps > 1 ? 1 : -1) : c.roll[b];
+            join[b] = joins ? 0 : -1;
+            ring.groups[b] = joins ? g++ : -1;
+        }
+        CHK(ring_send(live, (const int32_t*)nullptr, (size_t)B, h->row_pos, c.st));
+        CHK(ring_send(received, (const int32_t*)nullptr, (size_t)B, h->row_pos_received(), c.st));
+        if (c.n_join) {
+            CHK(ring_send(join, (const int32_t*)nullptr, (size_t)B, h->row_pos_join(), c.st));
+            CHK(ring_send(ring.groups, (const int32_t*)nullptr, (size_t)B, h->group_of_row, c.st));
+        }
+    }
+    return ring_sent(h, slot, c.st);
+}
+
+// A prompt prefill over fewer rows than the pass has, through the staging (hqt_handle::pg_*): shared prompts (the n_prompts distinct prompts of cond [n_prompts, T]) and
+// the join phase of a rolling text pass (`gathered`: the joiners' prompts, read from cond [B, T] through the group table).  A sample's prompt rows depend on nothing but
+// its prompt, so the embedding and the body blocks run over the prompts alone, K/V into the staging buffer [n_layers][n_prompts][T][D] -- never cache slot g, the
+// destination of row g of the pass, which may carry another prompt --; ONE launch then copies the staged K/V of every row's prompt into its cache slot and gathers its last
+// prompt row of x (a negative group: neither); the depth head runs over the B gathered rows (one per sample) under `head_row_pos` and draws position 0.
+static int staged_prompt_prefill(hqt_handle* h, const SampleCtx& c, int n_prompts, bool gathered, const int* head_row_pos) {
+    const hqt_config& cf = h->cfg;
+    const int T = cf.ctx_len_txt, D = cf.embed_dim;
+    SampleCtx cg = c;
+    cg.B = n_prompts;
+    cg.row_pos = nullptr;                            // (the prefill of the prompts knows no positions)
+    if (gathered) HIPCHK(launch_embed_text_rows(c.cond, h->group_of_row, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, c.B, n_prompts, T, D, c.st, cf.vocab_txt));
+    else HIPCHK(launch_embed_text(c.cond, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, n_prompts, T, D, c.st, cf.vocab_txt, T));
+    const KvStage stage{h->pg_k, h->pg_v};
+    bool pfull = false;
+    CHK(run_body(h, cg, T, 0, false, false, &pfull, &stage));
+    CHK(fold_pending(h, cg, n_prompts * T));         // (the staged rows, before the fan-out gathers x)
+    {
+        Timed t(h, "prompt_fanout", c.st);
+        const FanoutArgs fa{h->pg_k, h->pg_v, h->kcache, h->vcache, h->x, h->pg_x, h->group_of_row, cf.n_layers, c.B, n_prompts, T, D,
+                            D * (int)c.md.act_sz(), cf.max_batch, h->Tmax};
+        HIPCHK(launch_prompt_fanout(fa, c.st));
+    }
+    SampleCtx ch = c;
+    ch.row_pos = head_row_pos;
+    return run_depth_head(h, ch, h->pg_x, 1, false);
+}
+
+// What a captured graph of G decode steps depends on: a call whose key equals the cached one replays the cached graph
+static std::vector<uint64_t> graph_key_of(const hqt_handle* h, const SampleCtx& c, int G) {
+    std::vector<uint64_t> key = {(uint64_t)G, (uint64_t)c.B, (uint64_t)(c.cond != nullptr), (uint64_t)c.noise, (uint64_t)c.logits_out, (uint64_t)c.logprob_out,
+                                 (uint64_t)c.precision, (uint64_t)c.n_steps, (uint64_t)c.levels, (uint64_t)h->policy + (c.roll ? 16 : 0),      // (+ 16: a rolling pass, never its positions)
+                                 (uint64_t)((h->persist_enabled && !h->persist_tripped ? 1 : 0) + (h->single_key ? 0 : 4) + (h->split_kslices ? 0 : 8))};
+    for (const int64_t* f : c.feed) key.push_back((uint64_t)f);
+    for (const SamplerSet& l : c.lv) {
+        uint32_t f[2];
+        memcpy(f, &l.top_p, 4); memcpy(f + 1, &l.temperature, 4);
+        key.push_back((uint64_t)l.top_k); key.push_back(f[0]); key.push_back(f[1]);
+    }
+    // a row table: that there is one (two sampler launches per draw where the pass dispatches) and whether a row uses top-p (the LDS of the general kernel) -- never its values, which the kernels read from device memory: a changed table replays the same graph
+    key.push_back((uint64_t)((c.row_set ? 1 : 0) + (c.row_top_p ? 2 : 0)));
+    // a pair table: that there is one (one more launch per sub-step) and its pair count (that launch's grid), never its rows or scales
+    key.push_back((uint64_t)c.n_guide);
+    // a keep table: that there is one (the samplers' guard) and the length of its prefill (the positions the graph covers), never its values
+    key.push_back(c.keep ? (uint64_t)c.prefix_len + 1 : 0);
+    // a draw report: its pointers and top_n (kernel arguments of the launches that take code_logprob's place)
+    for (const void* p : {(const void*)c.report.entropy, (const void*)c.report.rank, (const void*)c.report.top_codes, (const void*)c.report.top_logprobs}) key.push_back((uint64_t)p);
+    key.push_back((uint64_t)c.report.top_n);
+    return key;
+}
+static int capture_steps(hqt_handle* h, const SampleCtx& c, int G) {      // G decode steps captured on a stream of their own: the handle's graph, in place of the one it held
+    if (h->graph_exec) {                             // rare (options or test-only buffers changed): drain before destroying
+        HIPCHK(hipStreamSynchronize(c.st));
+        hipGraphExecDestroy(h->graph_exec);
+        h->graph_exec = nullptr;
+    }
+    SampleCtx cc = c;
+    HIPCHK(hipStreamCreateWithFlags(&cc.st, hipStreamNonBlocking));
+    h->capture_persist = false;
+    HIPCHK(hipStreamBeginCapture(cc.st, hipStreamCaptureModeThreadLocal));
+    int rc = HQT_OK;
+    for (int gi = 0; gi < G && rc == HQT_OK; ++gi) rc = run_decode_step(h, cc);
+    hipGraph_t graph = nullptr;
+    hipError_t e = hipStreamEndCapture(cc.st, &graph);
+    hipStreamDestroy(cc.st);
+    if (rc != HQT_OK) { if (graph) hipGraphDestroy(graph); return rc; }
+    HIPCHK(e);
+    HIPCHK(hipGraphInstantiate(&h->graph_exec, graph, nullptr, nullptr, 0));
+    hipGraphDestroy(graph);
+    h->graph_has_persist = h->capture_persist;
+    h->persist_used = false;                         // capturing queued nothing
+    return HQT_OK;
+}
+
 static int sample_run(hqt_handle* h, const SampleCtx& c) {
     const hqt_config& cf = h->cfg;
-    const int B = c.B;
     HIPCHK(sampler_configure(cf.vocab_top, c.top_p));
     CHK(persist_bind(h));
     if (c.start == 0) HIPCHK(launch_set_step(h->state, 0, 0, c.st));      // (a continuation goes on from the step state its pass stopped at)
     if ((c.row_seeds || c.row_offsets) && (!c.row_seeds || !c.row_offsets)) return fail(HQT_ERR_INVALID, "row_seeds and row_offsets come together");
-    // merged steps: per-row Philox keys and / or sampler settings (host arrays of B <= max_batch entries, through the pinned ring); a guided call: its pair
-    // table, and ALWAYS the keys -- the implicit ones (seed, sample_offset + b) are built here, the negative row of every pair taking its positive row's
-    if (c.row_seeds || c.row_set || c.guide || c.keep || c.groups || c.roll) {
-        int slot = 0;
-        RingSlot ring;
-        CHK(rows_ring_take(h, &slot, &ring));
-        RowKey* rk = ring.keys;
-        if (c.row_seeds || c.guide) {
-            for (int b = 0; b < B; ++b) {
-                rk[b].seed = c.row_seeds ? c.row_seeds[b] : c.seed;
-                rk[b].global_row = c.row_offsets ? c.row_offsets[b] : c.sample_offset + b;
-            }
-            for (int i = 0; i < c.n_guide; ++i) rk[c.guide[i].neg_row] = rk[c.guide[i].pos_row];      // (explicit keys were checked to agree: sample_call)
-            CHK(ring_send(rk, (const RowKey*)nullptr, (size_t)B, h->rows, c.st));
-        }
-        if (c.row_set) CHK(ring_send(ring.samplers, c.row_set, (size_t)B, h->row_set, c.st));
-        if (c.guide) CHK(ring_send(ring.pairs, c.guide, (size_t)c.n_guide, h->guide, c.st));
-        if (c.keep) CHK(ring_send(ring.keep, c.keep, (size_t)B * c.n_steps, h->keep_mask, c.st));
-        if (c.groups) CHK(ring_send(ring.groups, c.groups, (size_t)B, h->group_of_row, c.st));
-        if (c.roll && !c.n_join) {      // the positions the rows stand at (moved on between the steps) and, behind them, the table as received (what sample_call copies out)
-            CHK(ring_send(ring.pos, c.roll, (size_t)B, h->row_pos, c.st));
-            CHK(ring_send(ring.pos, (const int32_t*)nullptr, (size_t)B, h->row_pos_received(), c.st));
-        } else if (c.roll) {
-            // a text pass with joining rows: the live table has them behind the join phase already (position 1; n_steps = 1: finished, idle in the steps), the
-            // join table says 0 for them and -1 for every other row, and the group table of the join's fan-out numbers them in ascending slot order
-            int32_t *live = ring.pos, *received = ring.pos + cf.max_batch, *join = ring.pos + 2 * (size_t)cf.max_batch;
-            int g = 0;
-            for (int b = 0; b < B; ++b) {
-                const bool joins = c.roll[b] == 0;
-                received[b] = c.roll[b];
-                live[b] = joins ? (c.n_steps > 1 ? 1 : -1) : c.roll[b];
-                join[b] = joins ? 0 : -1;
-                ring.groups[b] = joins ? g++ : -1;
-            }
-            CHK(ring_send(live, (const int32_t*)nullptr, (size_t)B, h->row_pos, c.st));
-            CHK(ring_send(received, (const int32_t*)nullptr, (size_t)B, h->row_pos_received(), c.st));
-            CHK(ring_send(join, (const int32_t*)nullptr, (size_t)B, h->row_pos_join(), c.st));
-            CHK(ring_send(ring.groups, (const int32_t*)nullptr, (size_t)B, h->group_of_row, c.st));
-        }
-        CHK(ring_sent(h, slot, c.st));
-    }
+    CHK(send_row_tables(h, c));
     // the kept codes go into the handle's code buffers (outside any captured graph) behind the mask: every level's embeddings, the samplers' guard and
     // code_logprob read them there
     for (int i = 0; i < (c.keep ? c.levels : 0); ++i)
-        HIPCHK(launch_copy_kept(c.keep_codes[i], c.out[i], h->keep_mask, B, c.n_steps, LEVEL_WIDTH[i], cf.vocab_top, c.st));
-    if (!c.row_seeds && !c.guide) HIPCHK(launch_set_rows(h->rows, B, c.seed, c.sample_offset, c.st));
+        HIPCHK(launch_copy_kept(c.keep_codes[i], c.out[i], h->keep_mask, c.B, c.n_steps, LEVEL_WIDTH[i], cf.vocab_top, c.st));
+    if (!c.row_seeds && !c.guide) HIPCHK(launch_set_rows(h->rows, c.B, c.seed, c.sample_offset, c.st));
     int first = c.start;
-    const int64_t* const own[3] = {h->codes_top, h->codes_bot, h->codes_l2};
     // a rolling pass: every continued row reads the codes of its position pos[b] - 1 where the caller holds them, as a segment does (a forced level: force_*)
     for (int i = 0; i < (c.roll ? c.levels : 0); ++i)
-        if (c.feed[i] == own[i]) HIPCHK(launch_copy_row_positions(c.roll_prev[i], c.out[i], h->row_pos + cf.max_batch, B, c.n_steps, LEVEL_WIDTH[i], -1, 0, c.st));
-    if (c.start > 0) {
-        // a continuation (hqt_set_segment): no prefill -- the cache holds the prompt rows and every position below start
+        if (c.feed[i] == c.out[i]) HIPCHK(launch_copy_row_positions(c.roll_prev[i], c.out[i], h->row_pos_received(), c.B, c.n_steps, LEVEL_WIDTH[i], -1, 0, c.st));
+    if (c.start > 0) {                           // a continuation (hqt_set_segment): no prefill -- the cache holds the prompt rows and every position below start
     } else if (c.roll) {
-        // A rolling pass runs no prefill over its rows; on a text handle the J rows that join run the JOIN PHASE, the shared-prompt block below with the
-        // joiners as the groups: their prompts (gathered from cond [B, T] through the group table) through the body blocks into the staging, the fan-out into
-        // the joiners' cache slots and gathered rows alone, then the depth head over all B gathered rows under the join table -- the joiners draw position 0 under
-        // their own key, sampler row and noise slice, every other row is idle there (it computes on the finite row it was left with and writes nothing).
-        // The steps below find the joiners at position 1 of the live table, behind ctx_len_txt cache rows (run_decode_step).
-        if (c.n_join) {
-            const int T = cf.ctx_len_txt, J = c.n_join, D = cf.embed_dim;
-            SampleCtx cg = c;
-            cg.B = J;
-            cg.row_pos = nullptr;                        // (the prefill of J prompts knows no positions)
-            HIPCHK(launch_embed_text_rows(c.cond, h->group_of_row, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, B, J, T, D, c.st, cf.vocab_txt));
-            const KvStage stage{h->pg_k, h->pg_v};
-            bool pfull = false;
-            CHK(run_body(h, cg, T, 0, false, false, &pfull, &stage));
-            CHK(fold_pending(h, cg, J * T));
-            {
-                Timed t(h, "prompt_fanout", c.st);
-                const FanoutArgs fa{h->pg_k, h->pg_v, h->kcache, h->vcache, h->x, h->pg_x, h->group_of_row, cf.n_layers, B, J, T, D,
-                                    D * (int)c.md.act_sz(), cf.max_batch, h->Tmax};
-                HIPCHK(launch_prompt_fanout(fa, c.st));
-            }
-            SampleCtx cj = c;
-            cj.row_pos = h->row_pos_join();
-            float* const x_body = h->x;
-            h->x = h->pg_x;
-            const int rc = run_depth_head(h, cj, 1, false);
-            h->x = x_body;
-            CHK(rc);
-        }
+        // A rolling pass runs no prefill over its rows; on a text handle the rows that join run the JOIN PHASE, the staged prompt prefill with the joiners as the
+        // groups and the depth head under the join table: the joiners draw position 0 under their own key, sampler row and noise slice, every other row is idle
+        // (it computes on the finite row it was left with and writes nothing).  The steps below find the joiners at position 1, behind ctx_len_txt cache rows.
+        if (c.n_join) CHK(staged_prompt_prefill(h, c, c.n_join, true, h->row_pos_join()));
     } else if (cf.cond_type == HQT_COND_TEXT && c.groups) {
-        const int T = cf.ctx_len_txt;
-        // Shared prompts (hqt_set_prompt_groups; P = 0, checked by sample_call): the prompt rows of a sample depend on nothing but its prompt, so the
-        // embedding and the body blocks run over the G distinct prompts, K/V into the staging buffer [n_layers][G][T][D] -- never cache slot g, which
-        // is the destination of row g of the pass, a row that may carry another prompt --; ONE launch then copies the staged K/V of every row's
-        // prompt into its cache slot and gathers the last prompt row of x per row; the depth head runs over the B gathered rows and draws position 0.
-        // Afterwards the cache and the step state are what the unshared prefill leaves: the decode steps below are the same launches.
-        const int G = c.n_groups, D = cf.embed_dim;
-        SampleCtx cg = c;
-        cg.B = G;
-        HIPCHK(launch_embed_text(c.cond, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, G, T, D, c.st, cf.vocab_txt, T));
-        const KvStage stage{h->pg_k, h->pg_v};
-        bool pfull = false;
-        CHK(run_body(h, cg, T, 0, false, false, &pfull, &stage));
-        CHK(fold_pending(h, c, G * T));                  // (the G T staged rows, before the fan-out gathers x)
-        {
-            Timed t(h, "prompt_fanout", c.st);
-            const FanoutArgs fa{h->pg_k, h->pg_v, h->kcache, h->vcache, h->x, h->pg_x, h->group_of_row, cf.n_layers, B, G, T, D,
-                                D * (int)c.md.act_sz(), cf.max_batch, h->Tmax};
-            HIPCHK(launch_prompt_fanout(fa, c.st));
-        }
-        // the depth head reads its B input rows from h->x: the gathered rows stand in for it while its launches are issued (one row per sample)
-        float* const x_body = h->x;
-        h->x = h->pg_x;
-        const int rc = run_depth_head(h, c, 1, false);
-        h->x = x_body;
-        CHK(rc);
-        HIPCHK(launch_advance_step(h->state, T, c.st));
+        // shared prompts (P = 0, checked by sample_call): afterwards the cache and the step state are what the unshared prefill leaves
+        CHK(staged_prompt_prefill(h, c, c.n_groups, false, nullptr));
+        HIPCHK(launch_advance_step(h->state, cf.ctx_len_txt, c.st));
         first = 1;
     } else if (cf.cond_type == HQT_COND_TEXT || c.prefix_len) {
         // The prefill: the text prompt (64-token causal prefill: sampling.py:187-190, layers.py:107-111) and / or a code prefix of P positions as ONE pass
-        // over the rows embed_prefill lays out, read from the handle's code buffers.  All body blocks run causally over them -- K/V of all rows go to the
-        // cache --, ln_f and the depth head on the last row, which draws position P: the step state says (P, 0) while that pass runs (sampler keys, noise
-        // slice, where the codes go) and P + 1 over all the rows afterwards.  The pass takes the classic path (Tq_body > 1: run_body); the persistent chain
-        // first reads the step state in the decode steps below, behind the advance.  Text with P = 0: the plain prompt prefill.
+        // over the rows embed_prefill lays out, read from the handle's code buffers.  All body blocks run causally over them -- K/V of all rows go to the cache --, ln_f and
+        // the depth head on the last row, which draws position P: the step state says (P, 0) while that pass runs (sampler keys, noise slice, where the codes go) and P + 1 over
+        // all the rows afterwards.  The classic path (Tq_body > 1: run_body); the persistent chain first reads the step state in the decode steps below.  Text, P = 0: the plain prompt prefill.
         const int P = c.prefix_len;
         int rows = 0;
         if (P) HIPCHK(launch_set_step(h->state, P, 0, c.st));
-        CHK(embed_prefill(h, c, own, P, &rows));
+        CHK(embed_prefill(h, c, c.out, P, &rows));
         CHK(run_position(h, c, rows, 0, false));
         HIPCHK(launch_advance_step(h->state, rows, c.st));
         first = P + 1;
@@ -2611,49 +2650,10 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
         static const int gmax = getenv("HQT_GRAPH_POSITIONS") ? std::max(1, atoi(getenv("HQT_GRAPH_POSITIONS"))) : 16;
         int G = 1;
         for (int d = std::min(gmax, remaining); d >= 1; --d) if (remaining % d == 0) { G = d; break; }
-        std::vector<uint64_t> key = {(uint64_t)G, (uint64_t)B, (uint64_t)(c.cond != nullptr), (uint64_t)c.noise, (uint64_t)c.logits_out, (uint64_t)c.logprob_out,
-                                     (uint64_t)c.precision, (uint64_t)c.n_steps, (uint64_t)c.levels, (uint64_t)h->policy + (c.roll ? 16 : 0),      // (+ 16: a rolling pass, never its positions)
-                                     (uint64_t)((h->persist_enabled && !h->persist_tripped ? 1 : 0) + (h->single_key ? 0 : 4) + (h->split_kslices ? 0 : 8))};
-        for (const int64_t* f : c.feed) key.push_back((uint64_t)f);
-        for (const SamplerSet& l : c.lv) {
-            uint32_t f[2];
-            memcpy(f, &l.top_p, 4); memcpy(f + 1, &l.temperature, 4);
-            key.push_back((uint64_t)l.top_k); key.push_back(f[0]); key.push_back(f[1]);
-        }
-        // a row table: that there is one (two sampler launches per draw where the pass dispatches) and whether a row uses top-p (the LDS of the general
-        // kernel) -- never its values, which the kernels read from device memory: a changed table replays the same graph
-        key.push_back((uint64_t)((c.row_set ? 1 : 0) + (c.row_top_p ? 2 : 0)));
-        // a pair table: that there is one (one more launch per sub-step) and its pair count (that launch's grid), never its rows or scales
-        key.push_back((uint64_t)c.n_guide);
-        // a keep table: that there is one (the samplers' guard) and the length of its prefill (the positions the graph covers), never its values
-        key.push_back(c.keep ? (uint64_t)c.prefix_len + 1 : 0);
-        // a draw report: its pointers and top_n (kernel arguments of the launches that take code_logprob's place)
-        for (const void* p : {(const void*)c.report.entropy, (const void*)c.report.rank, (const void*)c.report.top_codes, (const void*)c.report.top_logprobs}) key.push_back((uint64_t)p);
-        key.push_back((uint64_t)c.report.top_n);
+        std::vector<uint64_t> key = graph_key_of(h, c, G);
         if (!h->graph_exec || key != h->graph_key) {
-            if (h->graph_exec) {                         // rare (options or test-only buffers changed): drain before destroying
-                HIPCHK(hipStreamSynchronize(c.st));
-                hipGraphExecDestroy(h->graph_exec);
-                h->graph_exec = nullptr;
-            }
-            hipStream_t cs;
-            HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-            SampleCtx cc = c;
-            cc.st = cs;
-            h->capture_persist = false;
-            HIPCHK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-            int rc = HQT_OK;
-            for (int gi = 0; gi < G && rc == HQT_OK; ++gi) rc = run_decode_step(h, cc);
-            hipGraph_t graph = nullptr;
-            hipError_t e = hipStreamEndCapture(cs, &graph);
-            hipStreamDestroy(cs);
-            if (rc != HQT_OK) { if (graph) hipGraphDestroy(graph); return rc; }
-            HIPCHK(e);
-            HIPCHK(hipGraphInstantiate(&h->graph_exec, graph, nullptr, nullptr, 0));
-            hipGraphDestroy(graph);
-            h->graph_key = key;
-            h->graph_has_persist = h->capture_persist;
-            h->persist_used = false;                     // capturing queued nothing
+            CHK(capture_steps(h, c, G));
+            h->graph_key = std::move(key);
         }
         PersistOrder order(h->device, c.st, h->graph_has_persist);
         if (h->graph_has_persist) h->persist_used = true;   // every replay queues the persistent launches the graph holds (hqt_range_check reads their mark)

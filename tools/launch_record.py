@@ -15,8 +15,10 @@ policy (tiled GEMM, split-K combine, K-sliced SPLIT GEMM); decode and encode in 
 upsampling conv and a nin_shortcut (planes-out, conv_out-direct, the halo conv's fused statistics), one decode with HQT_NO_FUSED_GN=1.
 
 The ``staged/*`` cases (``staged_cases``) cover the calls that stage something on the handle first -- code prefixes, kept positions, row samplers (six calls
-back to back through the four-slot pinned ring), guidance, shared prompts, segments with ``select_rows`` -- and ``score``, on the tiny spec; ``staged/refusals/*``
-record the code and text of refused raw-ABI calls and the hash of a plain call behind each.
+back to back through the four-slot pinned ring), guidance, shared prompts, segments with ``select_rows``, rolling passes (``row_positions``: a slot that joins late, rows that end at different calls, a call
+over empty slots alone; on a text engine with ``max_joins`` the join phase with two, one and no joiner), draw reports -- and ``score``, on the tiny spec;
+``staged/refusals/*`` record the code and text of refused raw-ABI calls (a wrong table, or two tables staged together: which test speaks first) and the
+hash of a plain call behind each.
 
 The ``surface/*`` cases record hashes only, with fixed seeds, of what the Python surface above the engine returns on the tiny configs:
 ``sampling_ihqgpt`` (class / text / bidirectional; every form of ``cond``, ``given_top_code``, ``row_seeds``, 'split', a seed drawn from
@@ -195,7 +197,7 @@ def flat_all(out):
 
 def staged_cases(rec, tiny):
     """``staged/*``: the calls that stage something on the handle first (row samplers, log-probabilities, guidance, prefixes, kept positions, shared prompts,
-    segments with select_rows) and ``score``, on the tiny spec with B = 4, n = 6, max_prefix = 5 and score_chunk = 5 (24 pairs: chunks of 5, 5, 5, 5, 4).
+    segments with select_rows, rolling passes, draw reports) and ``score``, on the tiny spec with B = 4, n = 6, max_prefix = 5 and score_chunk = 5 (24 pairs: chunks of 5, 5, 5, 5, 4).
     Draws are keyed (no ``noise``): the per-row keys travel with the tables.  ``staged/refusals/*``: refused raw-ABI calls, their code and text, and
     the hash of a plain call behind each -- nothing was left staged."""
     import ctypes as C
@@ -208,12 +210,13 @@ def staged_cases(rec, tiny):
     B, n, P, V = 4, 6, 2, tiny['vocab_top']
     specs = {'class': Stage2Spec(**tiny), 'text': Stage2Spec(**dict(tiny, cond=2, n_classes=0)),
              'l3_parallel_add': Stage2Spec(**tiny, levels=3, depth_decoding='parallel-add'), 'bidirectional': Stage2Spec(**tiny, depth_decoding='bidirectional')}
+    specs['text_joins'] = specs['text']              # the text model on an engine of its own, built with max_joins = 2 (rolling passes; 'text' stays without)
     engines = {}
 
     def engine(model):
         if model not in engines:
             spec = specs[model]
-            eng = engines[model] = Engine(spec, None, dev, B, spec.ctx_len_img, max_prefix=5, score_chunk=5)
+            eng = engines[model] = Engine(spec, None, dev, B, spec.ctx_len_img, max_prefix=5, score_chunk=5, max_joins=2 if model == 'text_joins' else 0)
             eng.load(stage2=synth.stage2_weights(spec, 60 + len(engines), 'fixture'))
             eng.finalize()
         return engines[model]
@@ -294,17 +297,64 @@ def staged_cases(rec, tiny):
         put('score', model, lambda p, g, m=model: [engine(m).score(B, cond_of(m), [c[:, :k].contiguous() for c in codes_of(m, 92)], precision=p, return_logits=True)
                                                    for k in (n, 1)], graph=False)
 
+    def rolling(case, model, tables, seed):
+        """A rolling pass (``row_positions``) of k = 2 steps per call on one set of ``out`` tensors, one call per table: a launch dict per call (and their sum, which
+        ``check_coverage`` reads) and the hash of ``out`` after every call, eager and graphed."""
+        eng, spec = engine(model), specs[model]
+
+        def calls(p, g, each):
+            outs = [torch.zeros((B, n) + ((4 ** l,) if l else ()), dtype=torch.int64, device=dev) for l in range(spec.levels)]
+            lp = torch.zeros((B, n, (4 ** spec.levels - 1) // 3), device=dev)
+            seen = []
+            for pos in tables:
+                each(lambda: fn_of(model)(B, cond_of(model), n, precision=p, use_graph=g, seed=seed, out=outs, logprobs_out=lp, row_positions=(pos, 2)))
+                torch.cuda.synchronize()
+                seen += [digest(t) for t in outs + [lp]]
+            return seen
+        for prec in ('exact', 'fast'):
+            per_call = []
+            eager = calls(_lib.PRECISIONS[prec], False, lambda call: per_call.append(timed(eng, call)[0]))
+            graph = calls(_lib.PRECISIONS[prec], True, lambda call: call())
+            eng.range_check()
+            total = {}
+            for counts in per_call:
+                for slot, v in counts.items():
+                    total[slot] = total.get(slot, 0) + v
+            rec[f'staged/{case}/{model}/{prec}'] = {'launches': total, 'launches_per_call': per_call, 'eager': eager, 'graph': graph}
+
+    # a slot joins late (slot 2, in call 2), rows end at different calls (slots 0, 1, 3 in call 3; slot 2 is left at position 4), and a call over empty slots alone
+    for k, model in enumerate(('class', 'l3_parallel_add', 'bidirectional')):
+        rolling('rolling', model, [[0, 0, -1, 0], [2, 2, 0, 2], [4, 4, 2, 4], [-1, -1, -1, -1]], 94 + k)
+    # text, max_joins = 2: a joiner draws position 0 in its prompt prefill and then the k steps, so it stands at 1 + k = 3 behind its first call.  Two joiners; ONE
+    # joiner next to two continuing rows; no joiner (slots 0 and 1 draw their last position, 5, in the first step and idle in the second)
+    # and a last call in which slot 2 draws position 5: the pass is over, as behind the all-empty call above (the next precision begins a pass of its own)
+    rolling('rolling_txt', 'text_joins', [[0, 0, -1, -1], [3, 3, 0, -1], [5, 5, 3, -1], [-1, -1, 5, -1]], 97)
+
+    def report(model, p, g, score=False):
+        from hqtransformer_amd.engine import new_draw_report
+        eng, draws = engine(model), 5
+        if score:
+            rep = new_draw_report(B, n, draws, 3, dev)
+            return [eng.score(B, cond_of(model), codes_of(model, 92), precision=p, report_out=rep), list(rep)]
+        reps = [new_draw_report(B, n, draws, 3, dev) for _ in range(2)]
+        return [eng.sample(B, cond_of(model), n, precision=p, use_graph=g, seed=98, report_out=reps[0]), list(reps[0]),
+                eng.sample(B, cond_of(model), n, precision=p, use_graph=g, seed=98, report_out=reps[1], return_logprobs=True), list(reps[1])]
+    for model in ('class', 'bidirectional'):
+        put('report', model, lambda p, g, m=model: report(m, p, g))
+    put('report_score', 'class', lambda p, g: report('class', p, g, score=True), graph=False)
+
     # ---- refusals, through the C ABI: what the Python surface checks first never reaches the library
     def ptr(t):
         return C.c_void_p(t.data_ptr())
 
-    def raw_sample(eng, model, rows=B, prefix_len=None, opts=True):
+    def raw_sample(eng, model, rows=B, prefix_len=None, opts=True, force_top=False):
         o = _lib.hqt_sample_opts()
         o.precision, o.n_steps, o.temperature_top, o.temperature_bot, o.seed = _lib.PRECISION_EXACT, n, 1.0, 1.0, 5
         cond = cond_of(model, rows).to(dev)
         outs = [torch.zeros((rows, n), dtype=torch.int64, device=dev), torch.zeros((rows, n, 4), dtype=torch.int64, device=dev)]
+        forced = torch.zeros((rows, n), dtype=torch.int64, device=dev)
         head = [eng.h, rows, ptr(cond), C.byref(o) if opts else None, None]
-        tail = [None, None, None, ptr(outs[0]), ptr(outs[1]), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)]
+        tail = [ptr(forced) if force_top else None, None, None, ptr(outs[0]), ptr(outs[1]), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)]
         if prefix_len is None:
             return eng.lib.hqt_sample(*head, *tail)
         px = [torch.zeros((rows, prefix_len), dtype=torch.int64, device=dev), torch.zeros((rows, prefix_len, 4), dtype=torch.int64, device=dev)]
@@ -316,9 +366,16 @@ def staged_cases(rec, tiny):
         return eng.lib.hqt_score(eng.h, B, ptr(cond), (C.c_void_p * 3)(*[c.data_ptr() for c in codes]), n, _lib.PRECISION_EXACT, ptr(lp), None,
                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
 
-    def set_rows(eng, rows):
-        t = row_sampler_table(2, table[:rows])
+    def set_rows(eng, rows, entries=table):
+        t = row_sampler_table(2, entries[:rows])
         return eng.lib.hqt_set_row_samplers(eng.h, rows, t.ctypes.data_as(C.POINTER(_lib.hqt_row_sampler)))
+
+    def set_pos(eng, pos, k=2):
+        p = np.asarray(pos, dtype=np.int32)
+        return eng.lib.hqt_set_row_positions(eng.h, len(p), p.ctypes.data_as(C.c_void_p), k)
+
+    def set_pair(eng, pos_row, neg_row):
+        return eng.lib.hqt_set_guidance(eng.h, 1, guide_pair_table(2, [(pos_row, neg_row, 1.5)]))
 
     def set_keep(eng, rows):
         m = np.ones((rows, n), dtype=np.uint8)
@@ -347,6 +404,25 @@ def staged_cases(rec, tiny):
         ('score_behind_logprob_and_segment', 'class', lambda e: set_logprob(e) or e.lib.hqt_set_segment(e.h, 0, 2), lambda e: raw_score(e, 'class')),
         # not a refusal: a segment alone is cleared by hqt_score without one, and the plain call behind it runs all n positions
         ('score_behind_segment_alone', 'class', lambda e: e.lib.hqt_set_segment(e.h, 0, 2), lambda e: raw_score(e, 'class')),
+        # two things staged together, or a wrong one: which of sample_call's tests speaks first.  (No case of a draw report whose top_n exceeds the
+        # vocabulary: top_n is at most HQT_REPORT_MAX_TOP = 16 and the tiny spec has 512 codes.)
+        ('segment_with_keep', 'class', lambda e: e.lib.hqt_set_segment(e.h, 0, 2) or set_keep(e, B), lambda e: raw_sample(e, 'class')),
+        ('later_segment_with_groups', 'text', lambda e: e.lib.hqt_set_segment(e.h, 2, 4) or set_groups(e, [0, 1, 1, 0]), lambda e: raw_sample(e, 'text')),
+        ('positions_with_segment', 'class', lambda e: set_pos(e, [0, 0, 0, 0]) or e.lib.hqt_set_segment(e.h, 0, 2), lambda e: raw_sample(e, 'class')),
+        ('positions_with_keep', 'class', lambda e: set_pos(e, [0, 0, 0, 0]) or set_keep(e, B), lambda e: raw_sample(e, 'class')),
+        ('positions_with_groups', 'text_joins', lambda e: set_pos(e, [0, 0, -1, -1]) or set_groups(e, [0, 1, 1, 0]), lambda e: raw_sample(e, 'text_joins')),
+        ('positions_wrong_B', 'class', lambda e: set_pos(e, [0, 0, 0]), lambda e: raw_sample(e, 'class')),
+        ('positions_k_beyond_n', 'class', lambda e: set_pos(e, [0, 0, 0, 0], k=n + 1), lambda e: raw_sample(e, 'class')),
+        ('positions_pair_with_empty_slot', 'class', lambda e: set_pos(e, [0, -1, 0, 0]) or set_pair(e, 0, 1), lambda e: raw_sample(e, 'class')),
+        # (the pair speaks before the slot bookkeeping: position 3 continues nothing on this handle)
+        ('positions_pair_apart', 'class', lambda e: set_pos(e, [0, 3, 0, 0]) or set_pair(e, 0, 1), lambda e: raw_sample(e, 'class')),
+        ('positions_continue_without_pass', 'class', lambda e: set_pos(e, [3, 0, 0, 0]), lambda e: raw_sample(e, 'class')),
+        # refused where it is staged (staged_rc != 0): nothing is staged, and the call behind it is a plain one
+        ('positions_on_text_without_max_joins', 'text', lambda e: set_pos(e, [0, 0, -1, -1]), lambda e: raw_sample(e, 'text')),
+        ('positions_three_joiners', 'text_joins', lambda e: set_pos(e, [0, 0, 0, -1]), lambda e: raw_sample(e, 'text_joins')),
+        ('positions_on_prefix_entry', 'class', lambda e: set_pos(e, [0, 0, 0, 0]), lambda e: raw_sample(e, 'class', prefix_len=P)),
+        ('keep_with_force_top', 'class', lambda e: set_keep(e, B), lambda e: raw_sample(e, 'class', force_top=True)),
+        ('row_table_temperature_0', 'class', lambda e: set_rows(e, B, [((0.0, 1.0), None, None)] + table[1:]), lambda e: raw_sample(e, 'class')),
     ]
     for name, model, stage, call in refusals:
         eng = engine(model)
@@ -402,14 +478,29 @@ COVERAGE = {
     'staged/score/text/fast': ('score_logprob', 'embed_prefix'),
     'staged/score/bidirectional/fast': ('score_logprob', 'bidir_head_ln'),
     'staged/score/l3_parallel_add/exact': ('score_logprob',),
+    # rolling passes: the decode steps under per-row positions with their log-probabilities (a rolling call runs no prefill ...)
+    'staged/rolling/class/exact': ('sampler', 'code_logprob', '!embed_prefix'),
+    'staged/rolling/class/fast': ('sampler', 'code_logprob'),
+    'staged/rolling/l3_parallel_add/exact': ('sampler', 'code_logprob'),
+    'staged/rolling/bidirectional/fast': ('bidir_sampler_top', 'bidir_head_ln'),
+    # ... but the join phase of a text pass: the joiners' prompts through the staging and the fan-out
+    'staged/rolling_txt/text_joins/exact': ('prompt_fanout',),
+    'staged/rolling_txt/text_joins/fast': ('prompt_fanout',),
+    # a draw report takes code_logprob's place, also where log-probabilities are asked for
+    'staged/report/class/exact': ('draw_report', '!code_logprob'),
+    'staged/report/class/fast': ('draw_report', '!code_logprob'),
+    'staged/report/bidirectional/exact': ('draw_report', '!code_logprob'),
+    'staged/report_score/class/exact': ('draw_report', 'score_logprob'),
 }
 
 
 def check_coverage(rec: dict) -> list:
+    """A needle names a slot the case must have launched; '!needle' one it must not have."""
     miss = []
     for case, needles in COVERAGE.items():
         slots = ' '.join(rec[case]['launches'])
-        miss += [f'{case}: no slot matching {n!r}' for n in needles if n not in slots]
+        miss += [f'{case}: no slot matching {n!r}' for n in needles if not n.startswith('!') and n not in slots]
+        miss += [f'{case}: a slot matching {n[1:]!r}' for n in needles if n.startswith('!') and n[1:] in slots]
     return miss
 
 
