@@ -13,8 +13,12 @@ from typing import List, Optional
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libhqt.so')
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['engine.hip', 'kernels.hip', 'attention.hip', 'fast_kernels.hip', 'persist.hip', 'tile_gemm.hip', 'exact_gemm.hip', 'mfma_gemm.hip', 'split_conv.hip', 'split_stream_conv.hip']
+SOURCES = ['engine.hip', 'kernels.hip', 'attention.hip', 'fast_kernels.hip', 'persist.hip', 'tile_gemm.hip', 'exact_gemm.hip', 'mfma_gemm.hip', 'split_conv.hip', 'split_stream_conv.hip', 'switches.hip']
 ABI_VERSION = 9
+# libhqt.so exports the C ABI (hqt_*) and nothing else, but for these C++ launchers of csrc/kernels.h that tests/test_gpu_draw_report.py calls on a row no
+# head can produce: csrc/libhqt.map lists them (as _Z*<name>*) and tests/test_abi.py holds the map, this list and the dynamic symbol table together
+TEST_EXPORTS = ['launch_score_report', 'launch_score_logprob']
+VERSION_SCRIPT = os.path.join(CSRC, 'libhqt.map')
 
 PRECISION_EXACT, PRECISION_FAST, PRECISION_SPLIT = 0, 1, 2
 PRECISIONS = {'exact': PRECISION_EXACT, 'fast': PRECISION_FAST, 'split': PRECISION_SPLIT}
@@ -151,8 +155,9 @@ _lib: Optional[C.CDLL] = None
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile libhqt.so for gfx950 in-tree with hipcc (cross-compiles without a GPU): one object per source, the stale
     ones in parallel, then one link.  "Stale" is decided by CONTENT, not by file times: every object carries a stamp = SHA-256 of its
-    source, every header, the flags and `hipcc --version` (build/<name>.stamp), and libhqt.so one over the objects' stamps -- an object or
-    a library shipped from another checkout, or left behind by an older source with a newer mtime, is rebuilt instead of loaded."""
+    source, every header, the flags and `hipcc --version` (build/<name>.stamp), and libhqt.so one over the objects' stamps, the link flags and the
+    version script (csrc/libhqt.map: everything but the C ABI and TEST_EXPORTS stays local to the library) -- an object or a library shipped
+    from another checkout, or left behind by an older source with a newer mtime, is rebuilt instead of loaded."""
     import hashlib
     from concurrent.futures import ThreadPoolExecutor
     hdrs = sorted([os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')] + [os.path.join(os.path.dirname(HERE), 'include', 'hqt.h')])
@@ -202,10 +207,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
         built = list(pool.map(compile_one, SOURCES))
         audit.result()                               # raises HqtLibraryError: no library without a valid audit of the ISA it contains
     objs = [o for o, _ in built]
-    lib_want = hashlib.sha256('\n'.join(st for _, st in built).encode()).hexdigest()
+    link_flags = ['--offload-arch=gfx950', '-shared', '-fPIC']
+    with open(VERSION_SCRIPT, 'rb') as fp:                # (the script's text, not its path: the stamp holds in a checkout elsewhere)
+        lib_want = hashlib.sha256('\n'.join([st for _, st in built] + link_flags + ['--version-script']).encode() + b'\0' + fp.read()).hexdigest()
     lib_stamp = os.path.join(objdir, 'libhqt.stamp')
     if force or not os.path.exists(LIB_PATH) or read(lib_stamp) != lib_want:
-        cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB_PATH] + objs
+        cmd = [hipcc] + link_flags + ['-Wl,--version-script=' + VERSION_SCRIPT, '-o', LIB_PATH] + objs
         if verbose:
             print(' '.join(cmd), flush=True)
         proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

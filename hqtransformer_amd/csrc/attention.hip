@@ -11,6 +11,7 @@
 // kernels' V^T gather, score tile and output store.  The equalities the copies promise are held by tests/test_gpu_attention_paths.py.
 #include "kernels.h"
 #include "gemm_generic.h"
+#include "switches.h"
 #include <type_traits>
 
 template <typename T> using raw_t = typename std::conditional<sizeof(T) == 2, uint4, float4>::type;      // 16-B vector of the cache dtype
@@ -658,10 +659,9 @@ AttnKernel attention_choice(const AttnArgs& a) {
     if (a.head_dim % 8 != 0 || chunks > 64 || (chunks & (chunks - 1)) != 0) return ATTN_INVALID;
     // few queries over a cache known on the host to fit one pass (depth sub-steps): one wave per (sample, head), see attention_fewq_kernel
     if (a.Tq > 1 && a.Tq <= 16 && !a.t_base_dev && !a.dbg && a.t_base + a.Tq <= 2 * (64 / chunks)) {
-        static const bool off = getenv("HQT_NO_FEWQ_ATTN") != nullptr;          // A/B switch
-        if (!off) {
+        if (!switch_value(SW_NO_FEWQ_ATTN)) {                                   // A/B switch
             // head size 64, <= 4 queries over <= 8 keys, 64+ samples: eight heads per wave (attention_fewq8_kernel; HQT_NO_FEWQ8=1: A/B switch)
-            static const bool off8 = getenv("HQT_NO_FEWQ8") != nullptr;
+            const bool off8 = switch_value(SW_NO_FEWQ8);
             if (!off8 && a.head_dim == 64 && a.Tq <= 4 && a.t_base + a.Tq <= 8 && a.B >= 64) return ATTN_FEWQ8;
             return a.t_base + a.Tq <= 64 / chunks ? ATTN_FEWQ1 : ATTN_FEWQ2;
         }
@@ -670,9 +670,9 @@ AttnKernel attention_choice(const AttnArgs& a) {
     // per (sample, head) with the whole problem in registers, above that one wave per 32-query tile (attention_prefill_tiled_kernel).
     // HQT_PREFILL_TILED=1 (test hook, read per launch so that one process can compare the two): the tiled kernel from 5 rows on
     const bool prefill = a.causal && a.dtype == DT_BF16 && a.head_dim == 64 && a.Tq > 4 && a.t_base == 0 && !a.t_base_dev && !a.dbg && (a.n_heads * 64) % 8 == 0;
-    if (prefill) return a.Tq > 64 || getenv("HQT_PREFILL_TILED") != nullptr ? ATTN_PREFILL_TILED : ATTN_PREFILL_MFMA;      // (MFMA: 4 < Tq <= 64)
+    if (prefill) return a.Tq > 64 || switch_value(SW_PREFILL_TILED) ? ATTN_PREFILL_TILED : ATTN_PREFILL_MFMA;      // (MFMA: 4 < Tq <= 64)
     // one query per sample, head size 64 (the decode steps of a merged FAST pass): eight heads per wave (HQT_NO_HEADS8=1: A/B switch)
-    static const bool no_h8 = getenv("HQT_NO_HEADS8") != nullptr;
+    const bool no_h8 = switch_value(SW_NO_HEADS8);
     // FAST only, from 256 samples: below that the launch is a handful of waves and the chunk-by-chunk walk loses to attention_kernel's
     // single round trip from 32 keys on (64 samples x 64 keys: 19.1 vs 9.3 us); EXACT keeps ONE kernel for every row count, so that a
     // row's draws do not depend on the pass it sits in (hqt.h: merged steps).

@@ -5,6 +5,7 @@
 #include "fast_kernels.h"
 #include "split_kernels.h"
 #include "persist.h"
+#include "switches.h"
 
 #include <algorithm>
 #include <cmath>
@@ -250,7 +251,7 @@ static int dev_alloc(hqt_handle* h, void** p, size_t bytes, bool workspace) {
     HIPCHK(hipMalloc(p, bytes ? bytes : 16));
     // test hook: HQT_POISON_WORKSPACE=1 fills every workspace buffer with 0xFF (NaN as fp32 / bf16, -1 as int64) so that
     // a read of something no kernel wrote shows up instead of passing on freshly zeroed memory
-    const bool poison = getenv("HQT_POISON_WORKSPACE") != nullptr;       // read per allocation: tests switch it on around one engine
+    const bool poison = switch_value(SW_POISON_WORKSPACE);                // read per allocation: tests switch it on around one engine
     if (poison && workspace && bytes) HIPCHK(hipMemset(*p, 0xFF, bytes));
     h->owned.push_back(*p);
     if (workspace) h->workspace_bytes += bytes;
@@ -443,11 +444,12 @@ extern "C" int hqt_create(const hqt_config* cfg, int device, hqt_handle** out) {
     DeviceGuard dg(device);
     if (!dg.ok) return fail(HQT_ERR_HIP, "hipSetDevice(%d) failed", device);
     std::unique_ptr<hqt_handle> h(new hqt_handle());
-    // every environment switch of the per-call path is read HERE, once per handle (hqt_set_switch changes them afterwards)
-    h->tile_gemm = getenv("HQT_NO_TILE_GEMM") == nullptr;
-    { const char* e = getenv("HQT_PERSIST"); h->persist_enabled = !(e && atoi(e) == 0); }
-    h->single_key = getenv("HQT_NO_SINGLE_KEY") == nullptr;
-    h->split_kslices = getenv("HQT_SPLIT_KSLICES_OFF") == nullptr;
+    // the per-handle switches take their defaults from the environment HERE, once per handle (hqt_set_switch changes them afterwards); the other
+    // switches of the call path are read where they act, once per process or per launch as their row of switches.h says
+    h->tile_gemm = !switch_value(SW_NO_TILE_GEMM);
+    h->persist_enabled = switch_value(SW_PERSIST);
+    h->single_key = !switch_value(SW_NO_SINGLE_KEY);
+    h->split_kslices = !switch_value(SW_SPLIT_KSLICES_OFF);
     h->cfg = *cfg;
     h->layouts = (cfg->ar_layouts & HQT_LAYOUT_ALL) ? (cfg->ar_layouts & HQT_LAYOUT_ALL) : HQT_LAYOUT_ALL;
     h->device = device;
@@ -641,7 +643,7 @@ static int alloc_workspace(hqt_handle* hp) {
             const size_t out_e = out_r * out_r * (size_t)(l.kind == 4 ? 0 : l.cout);
             per_img = std::max(per_img, std::max(in_e, out_e));
         }
-        h->dec_chunk = std::max(1, std::min<int>(c.max_batch, getenv("HQT_DEC_CHUNK") ? atoi(getenv("HQT_DEC_CHUNK")) : 64));     // images per decode pass.  Decoder alone 64 -> 128 -> 256: 2047 -> 2090 -> 2102 images/s (SPLIT), but in the pipeline 128 measured 0.4 % slower (1275 vs 1280 images/s, same box)
+        h->dec_chunk = std::max(1, std::min<int>(c.max_batch, switch_value(SW_DEC_CHUNK)));     // images per decode pass.  Decoder alone 64 -> 128 -> 256: 2047 -> 2090 -> 2102 images/s (SPLIT), but in the pipeline 128 measured 0.4 % slower (1275 vs 1280 images/s, same box)
         h->act_elems = per_img * h->dec_chunk;
         for (int i = 0; i < 3; ++i) CHK(dev_alloc(h.get(), &h->act[i], h->act_elems * 4, true));
         CHK(dev_alloc(h.get(), &h->act[3], h->act_elems * 4, true));     // bf16 copy (FAST) or fp16 hi / lo planes (SPLIT)
@@ -1112,7 +1114,7 @@ static void lin_args(const hqt_handle* h, GemmArgs& g, const Lin& l, bool split_
 struct SlotName {
     char s[64];
     SlotName(const char* tag, int rows) {
-        static const bool by_rows = getenv("HQT_TIMING_BY_ROWS") != nullptr;
+        const bool by_rows = switch_value(SW_TIMING_BY_ROWS);
         snprintf(s, sizeof s, by_rows ? "%s@%d" : "%s", tag, rows);
     }
 };
@@ -1322,7 +1324,7 @@ static int persist_build_one(hqt_handle* h, PersistProg& pr, const std::vector<P
 static int persist_build(hqt_handle* h) {
     const hqt_config& c = h->cfg;
     h->pbody = PersistProg(); h->pfull = PersistProg();
-    if (!c.has_stage2 || !(h->layouts & HQT_LAYOUT_FAST) || getenv("HQT_PERSIST_BUILD_OFF")) return HQT_OK;
+    if (!c.has_stage2 || !(h->layouts & HQT_LAYOUT_FAST) || switch_value(SW_PERSIST_BUILD_OFF)) return HQT_OK;
     HIPCHK(hipDeviceGetAttribute(&h->ncu, hipDeviceAttributeMultiprocessorCount, h->device));
     // one 576-thread workgroup with its whole LDS ring must fit a compute unit, or the grid barrier can never complete: no program then (launch chain)
     HIPCHK(persist_configure());
@@ -1428,8 +1430,7 @@ static int run_persist(hqt_handle* h, const SampleCtx& c, const PersistProg& pr,
     a.counters = h->persist_counters; a.err = h->persist_err; a.x32 = x32; a.slabs = h->persist_slabs;
     a.D = h->cfg.embed_dim; a.M = c.B; a.MB = packed_mb(c.B); a.n_heads = h->cfg.n_heads; a.head_dim = h->cfg.embed_dim / h->cfg.n_heads;
     a.t_base = 0; a.t_base_dev = t_dev; a.write_back = write_back;
-    static const bool nt = !(getenv("HQT_PERSIST_NT") && atoi(getenv("HQT_PERSIST_NT")) == 0);
-    a.nt_weights = nt ? 1 : 0;
+    a.nt_weights = switch_value(SW_PERSIST_NT);
     persist_default_fill(a);
     HIPCHK(launch_persist(a, h->ncu, c.st));
     h->persist_used = true;
@@ -1458,8 +1459,7 @@ static int run_ln(hqt_handle* h, hipStream_t st, float* x, const float* g, const
 struct Resid { float* x; bf16_t* xpk; float* parts; int* nparts; };
 
 static bool dln_ok(hqt_handle* h, const SampleCtx& c, const BlockW& bw, int M) {
-    static const bool off = getenv("HQT_NO_DLN") != nullptr;      // debugging / A-B switch: classic LayerNorm kernels
-    if (off) return false;
+    if (switch_value(SW_NO_DLN)) return false;                    // debugging / A-B switch: classic LayerNorm kernels
     return c.md.fast && M <= PACKED_MAX_ROWS && bw.qkv.wpk_ln && bw.fc1.wpk_ln && bw.proj.wpk && bw.fc2.wpk && h->cfg.embed_dim % 32 == 0;
 }
 
@@ -1681,8 +1681,7 @@ static int run_depth_head(hqt_handle* h, const SampleCtx& c, float* x, int Tq_bo
     const int nsub = causal_head ? h->depth_rows : c.levels;       // 'top2mid2bot': one sub-step per depth token
     // the draw and the embedding lookup of the drawn code in one kernel: the two-level top sampler's workgroup of sample b also writes the
     // four input rows of depth sub-step 1 (HQT_NO_FUSED_EMBED=1: separate depth_embed_kernel, for A/B runs)
-    static const bool fuse_env = !getenv("HQT_NO_FUSED_EMBED");
-    const bool fuse = fuse_env && c.levels == 2 && !bidir;
+    const bool fuse = !switch_value(SW_NO_FUSED_EMBED) && c.levels == 2 && !bidir;
     void* normed[3] = {nullptr, nullptr, nullptr};
     SamplerSet bidir_set;
     if (bidir) {                  // one pass over all depth rows
@@ -2647,7 +2646,7 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
     if (c.use_graph && !h->timing) {
         // positions per captured graph: the largest divisor of the remaining positions up to HQT_GRAPH_POSITIONS (default 16):
         // one graph launch then covers G positions (fewer host launches and graph-to-graph hand-overs on the device)
-        static const int gmax = getenv("HQT_GRAPH_POSITIONS") ? std::max(1, atoi(getenv("HQT_GRAPH_POSITIONS"))) : 16;
+        const int gmax = switch_value(SW_GRAPH_POSITIONS);
         int G = 1;
         for (int d = std::min(gmax, remaining); d >= 1; --d) if (remaining % d == 0) { G = d; break; }
         std::vector<uint64_t> key = graph_key_of(h, c, G);
@@ -2813,7 +2812,7 @@ static int s1_conv(S1Ctx& c, GemmArgs g, S1Operand a, const Lin& l, int c_dt, co
         if (h->timing) count_variant(h, conv_halo_ok(g, c_dt) ? "variant:halo_conv:%s" : "variant:mfma_gemm:%s", tag);
         // a 3x3 halo conv also leaves per-tile GroupNorm statistics of its output
         if (g.conv_taps == 9 && g.store == STORE_ROWS && h->gn_tiles && conv_halo_ok(g, c_dt) && conv_halo_stats_ok(g.N, 32) &&
-            !getenv("HQT_NO_FUSED_GN")) {
+            !switch_value(SW_NO_FUSED_GN)) {
             g.gn_part_out = h->gn_tiles; g.gn_out_groups = 32;
             c.gn_ready = {g.C, conv_halo_tiles_per_image(g), false};
         }

@@ -18,6 +18,7 @@
 // (tests/test_gpu_timed_schedule.py compares the logits of a 64-row call with the same rows of a 512 / 2048-row pass bit for bit).
 #include "gemm_generic.h"
 #include "kernels.h"
+#include "switches.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(256) void exact_mfma_gemm_kernel(GemmArgs g, int TM
 // plain fp32 row-major operands, K in whole chunks, the AR loop's store modes (gemm_store handles bias / act / resid / row remap / QKV split)
 bool exact_mfma_small(const GemmArgs& g);
 bool exact_mfma_ok(const GemmArgs& g) {
-    static const bool off = getenv("HQT_NO_EXACT_MFMA") != nullptr;                // A/B switch: the 64 x 64 vector-ALU tile kernel for everything
+    const bool off = switch_value(SW_NO_EXACT_MFMA);                               // A/B switch: the 64 x 64 vector-ALU tile kernel for everything
     if (off || !g.k_quarters || g.conv_taps || g.a_packed_mb || g.a_rows_per_group || g.batch > 1 || g.gn_stats) return false;
     if (g.K % 32 != 0 || g.K < 32 || g.lda % 4 != 0 || g.ldb % 4 != 0) return false;
     return (g.store == STORE_ROWS || g.store == STORE_QKV) && exact_mfma_small(g);

@@ -1,6 +1,7 @@
 // Small kernels of the HQ-Transformer sampling path: embeddings, LayerNorm, the fused sampler, codebook
 // gather, GroupNorm statistics (KV-cache attention: attention.hip).  gfx950 only (wave = 64).
 #include "kernels.h"
+#include "switches.h"
 #include <mutex>
 #include "gemm_generic.h"
 #include <type_traits>
@@ -1147,7 +1148,7 @@ hipError_t launch_sampler(const SamplerArgs& args, hipStream_t st) {
     if (smem > 160 * 1024) return hipErrorInvalidValue;               // sampler_configure(V, top_p) ran in sample_run for this call's options
     // FAST, no cut-offs, V <= 8192: the register-resident kernel (HQT_NO_PLAIN_SAMPLER=1: A/B switch).  With a row table it runs over every row in front of the
     // general kernel and each of the two leaves the other one's rows alone (row_dispatch): two launches whatever the table holds.
-    static const bool no_plain = getenv("HQT_NO_PLAIN_SAMPLER") != nullptr;
+    const bool no_plain = switch_value(SW_NO_PLAIN_SAMPLER);
     const bool plain_v = !no_plain && a.fast_math && a.V % 4 == 0 && a.V <= 8192 && a.V >= 1024;
     a.row_dispatch = table && plain_v ? 1 : 0;
     if (plain_v && (table || sampler_row_plain(a.top_k, a.top_p, a.V))) {

@@ -14,6 +14,7 @@
 // different rows fall on 16 different 16-B bank slots (conflict-free ds_read_b128).
 #include "fast_kernels.h"
 #include "gemm_generic.h"
+#include "switches.h"
 #include <cstdlib>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -732,10 +733,9 @@ bool conv_halo_stats_ok(int N, int groups) {
 }
 // 16-row tiles when the grid still fills the chip twice over (two workgroups per CU x 256 CUs), else 8-row tiles
 int conv_halo_tile_rows(const GemmArgs& g) {
-    const char* fe = getenv("HQT_HALO_TY");                                          // tuning / test hook (read per launch): 8 or 16
-    const int forced = fe ? atoi(fe) : 0;
     if (g.H % 16 != 0) return 8;
-    if (forced == 8 || forced == 16) return forced;
+    const int forced = switch_value(SW_HALO_TY);                                     // tuning / test hook (read per launch): 8 or 16, 0 = not forced
+    if (forced) return forced;
     const long long tiles16 = (long long)(g.M / 256) * ((g.N + 127) / 128);
     return tiles16 >= 1024 ? 16 : 8;
 }
@@ -785,13 +785,14 @@ static hipError_t launch_t(const GemmArgs& g, int c_dt, hipStream_t st) {
 
 static bool big_tile_shape(const GemmArgs& g) {
     const long long tiles128 = (long long)((g.M + 127) / 128) * ((g.N + 127) / 128) * (g.batch > 0 ? g.batch : 1);
-    static const bool force128 = getenv("HQT_FORCE_TILE128") != nullptr;          // test hook: exercise the big-tile kernels on tiny shapes
     const bool narrow = g.N < 32 && g.M >= 4096 && glds_ok(g);       // conv_out (N = 3): one zero-padded 128-wide n-tile
-    return narrow || (g.N >= 128 && g.M >= 128 && (tiles128 >= 96 || force128));      // 96: the 1024-row x 1536-column GEMMs of the third code level
+    // 96: the 1024-row x 1536-column GEMMs of the third code level.  HQT_FORCE_TILE128: test hook (read per launch, and only for shapes of fewer tiles):
+    // exercise the big-tile kernels on tiny shapes
+    return narrow || (g.N >= 128 && g.M >= 128 && (tiles128 >= 96 || switch_value(SW_FORCE_TILE128)));
 }
 // true when launch_mfma_gemm will run the halo-tile kernel for g (the engine asks before requesting fused statistics)
 bool conv_halo_ok(const GemmArgs& g, int c_dt) {
-    const bool no_halo = getenv("HQT_NO_HALO") != nullptr;                    // A/B switch (read per launch): generic implicit GEMM for the 3x3 convs too
+    const bool no_halo = switch_value(SW_NO_HALO);                            // A/B switch (read per launch): generic implicit GEMM for the 3x3 convs too
     return big_tile_shape(g) && !no_halo && halo_ok(g, c_dt);
 }
 
@@ -804,7 +805,7 @@ hipError_t launch_mfma_gemm(const GemmArgs& g, int a_dt, int b_dt, int c_dt, hip
 #define LAUNCH_HALO(TC, NCHW_)                                                                              \
             if (ty == 16) conv3x3_halo_kernel<TC, NCHW_, 16><<<grid, 256, halo_lds(16), st>>>(g);           \
             else conv3x3_halo_kernel<TC, NCHW_, 8><<<grid, 256, halo_lds(8), st>>>(g);
-            const bool no_narrow = getenv("HQT_NO_NARROW_OUT") != nullptr;   // A/B switch (read per launch)
+            const bool no_narrow = switch_value(SW_NO_NARROW_OUT);   // A/B switch (read per launch)
             if (g.store == STORE_NCHW && g.N <= 32 && c_dt == DT_F32 && !no_narrow) {   // conv_out: 32-channel tiles instead of 3 padded to 128
                 if (ty == 16) conv3x3_halo_kernel<float, true, 16, 0, 32><<<grid, 256, halo_lds(16, 32), st>>>(g);
                 else conv3x3_halo_kernel<float, true, 8, 0, 32><<<grid, 256, halo_lds(8, 32), st>>>(g);
@@ -823,7 +824,7 @@ hipError_t launch_mfma_gemm(const GemmArgs& g, int a_dt, int b_dt, int c_dt, hip
             const long long t128 = (long long)grid.x * grid.y * grid.z;
             // (latency policy only: with several steps in flight the 128 x 128 tiles cost fewer CU-microseconds -- level-3 config,
             // 3 lanes: 594 vs 576 images/s; one lane: AR 158.7 vs 169.1 ms)
-            if (t128 < 192 && g.M >= 256 && !g.conv_taps && g.store == STORE_ROWS && g.tune == 0 && !getenv("HQT_NO_TILE64")) {
+            if (t128 < 192 && g.M >= 256 && !g.conv_taps && g.store == STORE_ROWS && g.tune == 0 && !switch_value(SW_NO_TILE64)) {
                 const dim3 grid64((g.N + 127) / 128, (g.M + 63) / 64, grid.z);
                 const size_t smem64 = (size_t)2 * (64 + 128) * 128;
                 if (g.rows_per_group == 0) {

@@ -24,6 +24,7 @@
 #include "split_kernels.h"
 #include "split_ring.h"
 #include "gemm_generic.h"
+#include "switches.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -520,7 +521,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_out16_kernel(GemmArgs g)
 
 // can the conv's epilogue emit operand planes (GemmArgs::out_split)?  Only conv3x3_split_ring16_kernel does: g must take that kernel.
 bool split_conv3_emits_planes(const GemmArgs& g) {
-    static const bool off = getenv("HQT_SPLIT_PLANES_OUT") && atoi(getenv("HQT_SPLIT_PLANES_OUT")) == 0;        // A/B switch: 0 = fp32 tensor + operand pass
+    const bool off = !switch_value(SW_SPLIT_PLANES_OUT);        // A/B switch: 0 = fp32 tensor + operand pass
     return !off && split_stream_ok(g) && g.store == STORE_ROWS && !g.upsample && g.ldc == g.N && g.N % 8 == 0;
 }
 bool split_stream_ok(const GemmArgs& g) {
@@ -533,7 +534,7 @@ bool split_stream_ok(const GemmArgs& g) {
 }
 // upsampling conv as four 2x2 phase convolutions on the low-resolution image (conv2x2_split_up16_kernel)
 static bool split_up_shape(const GemmArgs& g) {
-    static const bool off = getenv("HQT_SPLIT_UP") && atoi(getenv("HQT_SPLIT_UP")) == 0;              // A/B switch: 0 = nine taps on the upsampled image
+    const bool off = !switch_value(SW_SPLIT_UP);              // A/B switch: 0 = nine taps on the upsampled image
     return !off && g.upsample == 1 && g.Bw_up16 && g.store == STORE_ROWS && (g.H / 2) % R_TY == 0 && (g.W / 2) % R_TX == 0 && g.N % 128 == 0;
 }
 int split_stream_tiles_per_image(const GemmArgs& g) { return split_up_shape(g) ? 4 * (g.H / 2 / R_TY) * (g.W / 2 / R_TX) : (g.H / R_TY) * (g.W / R_TX); }
@@ -663,7 +664,7 @@ __global__ __launch_bounds__(256, 3) void conv_out_direct_kernel(GemmArgs g) {
 }
 
 bool conv_out_direct_ok(const GemmArgs& g) {
-    static const bool off = getenv("HQT_CONV_OUT_DIRECT") && atoi(getenv("HQT_CONV_OUT_DIRECT")) == 0;        // A/B switch: 0 = operand pass + conv3x3_split_out16_kernel
+    const bool off = !switch_value(SW_CONV_OUT_DIRECT);        // A/B switch: 0 = operand pass + conv3x3_split_out16_kernel
     return !off && g.conv_taps == 9 && g.store == STORE_NCHW && g.N >= 1 && g.N <= 4 && g.Cin % O_CH == 0 && g.H % O_T == 0 && g.W % O_T == 0 &&
            !g.upsample && !g.conv_stride2 && !g.resid && g.gn_stats && g.gn_groups > 0 && g.Cin % g.gn_groups == 0 &&
            (long long)g.H * g.W * g.Cin < (1ll << 31);

@@ -451,7 +451,8 @@ class Engine:
 
     def clone(self) -> 'Engine':
         """A further lane over the same weights (``hqt_clone``): own KV cache / activations / graph cache, results
-        bit-identical to this engine's.  Lanes on different streams keep several batches in flight on one GPU."""
+        bit-identical to this engine's.  Lanes on different streams keep several batches in flight on one GPU.  The lane takes this engine's root's
+        ``set_persist`` / ``set_single_key`` / ``set_split_kslices`` values as they are now; a later ``set_*`` call changes only the engine it is called on."""
         if not self.finalized:
             raise _lib.HqtError(-1, 'clone() needs a finalized engine')
         e = Engine.__new__(Engine)
@@ -476,21 +477,24 @@ class Engine:
 
     def set_persist(self, on: bool) -> None:
         """``hqt_set_switch(HQT_SWITCH_PERSIST)``: False = the launch chain instead of the persistent AR launch (FAST sampling of up to 64
-        rows); True also re-arms a handle that fell back to the chain after a launch gave up.  Part of the graph key."""
+        rows); True also re-arms a handle that fell back to the chain after a launch gave up.  Part of the graph key.  Per handle, as every
+        ``hqt_set_switch`` value: this engine only, not the lanes cloned from it before (a lane copies its root's values in ``clone()``)."""
         _lib.check(self.lib.hqt_set_switch(self.h, _lib.SWITCH_PERSIST, int(bool(on))))
 
     def set_persist_fault(self, cu_plus_one: int) -> None:
         """Test hook ``hqt_set_switch(HQT_SWITCH_PERSIST_FAULT)``: compute unit ``cu_plus_one - 1`` withholds its first grid-barrier signal in
-        every later persistent launch (0 = none), cached graphs included."""
+        every later persistent launch (0 = none), cached graphs included.  This engine only (per handle)."""
         with torch.cuda.device(self.device):
             _lib.check(self.lib.hqt_set_switch(self.h, _lib.SWITCH_PERSIST_FAULT, int(cu_plus_one)))
 
     def set_split_kslices(self, on: bool) -> None:
-        """``hqt_set_switch(HQT_SWITCH_SPLIT_KSLICES)``: False = the SPLIT AR GEMMs are never K-sliced (one fp32 summation order at every row count)."""
+        """``hqt_set_switch(HQT_SWITCH_SPLIT_KSLICES)``: False = the SPLIT AR GEMMs are never K-sliced (one fp32 summation order at every row count).
+        Per handle: lanes that exist keep their value (the merged passes run on lanes: call it on each), a lane cloned afterwards copies its root's."""
         _lib.check(self.lib.hqt_set_switch(self.h, _lib.SWITCH_SPLIT_KSLICES, int(bool(on))))
 
     def set_single_key(self, on: bool) -> None:
-        """``hqt_set_switch(HQT_SWITCH_SINGLE_KEY)``: False = depth sub-step 0 the long way round (A/B runs and tests; bit-identical results)."""
+        """``hqt_set_switch(HQT_SWITCH_SINGLE_KEY)``: False = depth sub-step 0 the long way round (A/B runs and tests; bit-identical results).  Per handle: this engine
+        only, not the lanes cloned from it before."""
         _lib.check(self.lib.hqt_set_switch(self.h, _lib.SWITCH_SINGLE_KEY, int(bool(on))))
 
     def _note_split(self, precision: int, stream: int, ar_rows: int = 0) -> None:

@@ -172,7 +172,8 @@ int hqt_finalize_weights(hqt_handle* h);
  * latency-bound kernels that leaves most of an MI355X idle, so the harness here keeps several batches in flight,
  * one lane and one HIP stream each (independent chains interleave on the GPU).  The clone shares every weight
  * buffer of `src` and owns only its workspace (KV cache, activations, step state, graph cache); results of a lane
- * are bit-identical to the parent's.  Destroy clones before their parent (hqt_destroy(parent) fails otherwise). */
+ * are bit-identical to the parent's.  The lane starts with the root's hqt_set_switch values as they are at this call (and with the LATENCY
+ * policy); later changes on either side stay there.  Destroy clones before their parent (hqt_destroy(parent) fails otherwise). */
 int hqt_clone(hqt_handle* src, hqt_handle** out);
 
 /* hqt_set_policy -- kernel selection for the AR loop.  LATENCY (default): tile shapes that finish one batch soonest
@@ -185,6 +186,9 @@ int hqt_set_policy(hqt_handle* h, int policy);
 
 /* hqt_set_switch -- two choices of launch sequence that do not change what is computed beyond fp32 summation order (no reference
  * counterpart; A/B runs and tests).  Both are part of the graph key: the next hqt_sample re-captures if one changed.
+ * SCOPE: the handle it is called on, and no other.  A lane copies its root's values when hqt_clone makes it; a later hqt_set_switch on the root
+ * does not reach the lanes that exist, nor one on a lane its root or its siblings: call it on every handle that is to change.  (The environment
+ * variables named below only set the values a ROOT handle starts with.)
  *   HQT_SWITCH_PERSIST     1 (default): FAST hqt_sample of up to 64 rows on a root handle runs a top position as ONE persistent launch
  *                          (csrc/persist.h); 0: the launch chain.  The default is 0 when HQT_PERSIST=0 was in the environment at hqt_create
  *                          -- the environment is read there, once, never per call.  A handle whose persistent launch gave up

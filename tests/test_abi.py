@@ -25,6 +25,29 @@ def test_header_symbols_are_exported_and_bound(lib):
         assert getattr(lib, name) is not None
 
 
+def test_library_exports_the_abi_and_nothing_else(lib):
+    """The dynamic symbol table holds the functions include/hqt.h declares and the launchers of _lib.TEST_EXPORTS (csrc/libhqt.map), nothing else:
+    no kernel handle, no launcher, no member of hqt_handle, no C++ library instantiation for another object of the process to bind to."""
+    import subprocess
+    hdr = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'hqt.h')).read(), flags=re.S)
+    declared = set(re.findall(r'\b(hqt_[a-z0-9_]+)\s*\(', hdr))
+    nm = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], check=True, stdout=subprocess.PIPE, text=True).stdout
+    exported = [line.split()[-1] for line in nm.splitlines() if line.strip()]
+    assert len(exported) == len(set(exported))
+    launchers = {}
+    for sym in set(exported) - declared:
+        m = re.fullmatch(r'_Z(\d+)(\w+)', sym)                  # a mangled free function: _Z<length><name><parameters>
+        base = m and m.group(2)[:int(m.group(1))]
+        assert base in _lib.TEST_EXPORTS, f'libhqt.so exports {sym}'
+        launchers[base] = sym
+    assert declared <= set(exported), declared - set(exported)
+    assert sorted(launchers) == sorted(_lib.TEST_EXPORTS)
+    # the version script lists exactly these
+    script = re.sub(r'/\*.*?\*/', '', open(_lib.VERSION_SCRIPT).read(), flags=re.S)
+    glob = re.search(r'global:(.*?)local:\s*\*;', script, re.S).group(1).split(';')
+    assert sorted(p.strip() for p in glob if p.strip()) == sorted(['hqt_*'] + [f'_Z*{n}*' for n in _lib.TEST_EXPORTS])
+
+
 def test_abi_version_and_error_paths_without_gpu(lib):
     assert lib.hqt_abi_version() == _lib.ABI_VERSION
     assert lib.hqt_create(None, 0, None) == -1

@@ -361,6 +361,11 @@ def test_decode_fast_tolerance():
         gate(f'decode_fast.{name}.mean', d.mean(), 1e-2)
 
 
+def _launches(eng, kernel):
+    """Launches the engine counted under `variant:<kernel>:*` since the last timing_reset(): {slot tag: count}, slots at 0 left out."""
+    return {k.split(':', 2)[2]: v[0] for k, v in eng.timing_report().items() if k.startswith(f'variant:{kernel}:') and v[0] > 0}
+
+
 def test_decode_fast_big_tile_kernels_vs_oracle():
     """FAST decode on a config wide enough (Cin % 64 == 0, Cout >= 128) for the LDS-DMA 128x128x64 MFMA conv
     kernel; HQT_FORCE_TILE128 makes the dispatcher pick it even though the grid is small.  Same tolerance as
@@ -375,10 +380,13 @@ def test_decode_fast_big_tile_kernels_vs_oracle():
     os.environ['HQT_FORCE_TILE128'] = '1'
     try:
         eng = engine_s1(spec, weights, 3)
+        eng.timing(True)
         got = np_(eng.decode(torch.from_numpy(ct), torch.from_numpy(cb), precision=PRECISION_FAST))
+        halo = _launches(eng, 'halo_conv')
         exact = np_(eng.decode(torch.from_numpy(ct), torch.from_numpy(cb), precision=PRECISION_EXACT))
     finally:
         del os.environ['HQT_FORCE_TILE128']
+    assert halo.get('conv3x3', 0) > 0, f'the hook did not take effect: no 3x3 conv of the body ran the halo-tile kernel ({halo})'
     assert np.abs(exact - want).max() <= PIXEL_TOL
     d = np.abs(got - want)
     gate('decode_fast_big_tile.max', d.max(), 0.06)
@@ -397,12 +405,15 @@ def test_decode_fast_halo_conv_matches_generic_implicit_gemm():
     r = np.random.default_rng(42)
     ct, cb = r.integers(0, 256, (5, 8, 8)), r.integers(0, 256, (5, 16, 16))
     os.environ['HQT_FORCE_TILE128'] = '1'
-    halo = {}
+    halo, ran = {}, {}
     try:
         eng = engine_s1(spec, weights, 5)
+        eng.timing(True)
         for ty in ('8', '16'):                      # 8 x 16 and 16 x 16 pixel tiles (the latter: single patch buffer, two-half epilogue)
             os.environ['HQT_HALO_TY'] = ty
+            eng.timing_reset()
             halo[ty] = np_(eng.decode(torch.from_numpy(ct), torch.from_numpy(cb), precision=PRECISION_FAST))
+            ran[ty] = (_launches(eng, 'halo_conv'), _launches(eng, 'mfma_gemm'))
             os.environ['HQT_NO_NARROW_OUT'] = '1'   # conv_out through the 128-channel tiles instead of the 32-channel variant
             wide_out = np_(eng.decode(torch.from_numpy(ct), torch.from_numpy(cb), precision=PRECISION_FAST))
             del os.environ['HQT_NO_NARROW_OUT']
@@ -410,10 +421,19 @@ def test_decode_fast_halo_conv_matches_generic_implicit_gemm():
         os.environ['HQT_NO_FUSED_GN'] = '1'         # statistics by the separate pass instead of the conv epilogue
         unfused = np_(eng.decode(torch.from_numpy(ct), torch.from_numpy(cb), precision=PRECISION_FAST))
         os.environ['HQT_NO_HALO'] = '1'
+        eng.timing_reset()
         generic = np_(eng.decode(torch.from_numpy(ct), torch.from_numpy(cb), precision=PRECISION_FAST))
+        ran['generic'] = (_launches(eng, 'halo_conv'), _launches(eng, 'mfma_gemm'))
     finally:
         for k in ('HQT_NO_HALO', 'HQT_HALO_TY', 'HQT_NO_FUSED_GN', 'HQT_FORCE_TILE128', 'HQT_NO_NARROW_OUT'):
             os.environ.pop(k, None)
+    # the two sides of the comparison ran the kernels they are named for: the halo-tile kernel while the hook is set, and under HQT_NO_HALO not one launch of
+    # it -- every conv it served is counted under the generic MFMA kernel instead
+    for ty in ('8', '16'):
+        assert ran[ty][0].get('conv3x3', 0) > 0, f'the hook did not take effect: no 3x3 conv of the body ran the halo-tile kernel ({ran[ty]})'
+    assert ran['8'] == ran['16']
+    assert not ran['generic'][0], f"halo-tile launches under HQT_NO_HALO: {ran['generic'][0]}"
+    assert sum(ran['generic'][1].values()) == sum(ran['16'][1].values()) + sum(ran['16'][0].values()), ran
     want = O.OracleStage1(spec, weights).decode_code(ct, cb)
     eg = np.abs(generic - want)
     for ty, px in list(halo.items()) + [('16, separate GroupNorm statistics', unfused)]:
@@ -425,6 +445,40 @@ def test_decode_fast_halo_conv_matches_generic_implicit_gemm():
         gate(f'halo_conv.vs_generic_kernel.mean({ty})', d.mean(), 8e-3)
     if not np.array_equal(halo['8'], halo['16']):
         gate('halo_conv.tile_heights_8_vs_16.max', np.abs(halo['8'] - halo['16']).max(), 0.06)
+
+
+def test_force_tile128_is_read_per_call():
+    """HQT_FORCE_TILE128 is read at every launch (csrc/switches.h: live), not once per process by whichever FAST conv comes first: three FAST decodes
+    on ONE engine, without, with and again without the hook.  The body's 3x3 convs (128 output channels, 24 tiles of 128 x 128: far below the 96 at
+    which the dispatcher takes the big tiles by itself) run the halo-tile kernel exactly while the hook is set.  conv_out is the one halo launch the hook
+    does not decide: 3 output channels over 3 x 64 x 64 = 12288 rows are the dispatcher's 'narrow' big-tile shape (N < 32, M >= 4096) at any setting,
+    so it is counted once in all three decodes."""
+    import os
+    assert 'HQT_FORCE_TILE128' not in os.environ and 'HQT_NO_HALO' not in os.environ
+    spec = Stage1Spec(ch=64, ch_mult=[1, 2], num_res_blocks=1, attn_resolutions=[16], resolution=64, z_channels=64,
+                      embed_dim=32, n_embed=256)
+    eng = engine_s1(spec, synth.stage1_weights(spec, 31, 'fixture'), 3)
+    r = np.random.default_rng(32)
+    ct, cb = torch.from_numpy(r.integers(0, 256, (3, 8, 8))), torch.from_numpy(r.integers(0, 256, (3, 16, 16)))
+    eng.timing(True)
+    halo, px = [], []
+    try:
+        for hook in (False, True, False):
+            if hook:
+                os.environ['HQT_FORCE_TILE128'] = '1'
+            else:
+                os.environ.pop('HQT_FORCE_TILE128', None)
+            eng.timing_reset()
+            px.append(np_(eng.decode(ct, cb, precision=PRECISION_FAST)))
+            halo.append(_launches(eng, 'halo_conv'))
+    finally:
+        os.environ.pop('HQT_FORCE_TILE128', None)
+    print('halo-tile launches without / with / without the hook:', halo)
+    assert halo[0] == {'conv_out': 1}, halo
+    assert halo[1].get('conv3x3', 0) > 0 and halo[1].get('conv_out') == 1, halo
+    assert halo[2] == halo[0], halo
+    assert np.array_equal(px[0], px[2])
+    gate('force_tile128_per_call.halo_vs_small_tiles.max', np.abs(px[1] - px[0]).max(), 0.06)      # (the gate of the halo test: summation order only)
 
 
 def test_decode_batch_chunking_and_ragged():
@@ -598,12 +652,13 @@ def test_encode_exact_vs_reference_fixture(name):
 
 def test_encode_wide_config_exact_and_fast_vs_oracle():
     """A config wide enough for the MFMA kernels (64..128 channels; HQT_FORCE_TILE128 makes the dispatcher pick the LDS-DMA kernel
-    with its stride-2 taps for Downsample).  EXACT: codes equal the oracle's except where the oracle's own float64 distance gap is
+    with its stride-2 taps for Downsample: the first level is 128 wide, because that kernel takes no GEMM of fewer than 128 columns, hook or not --
+    with ch_mult [1, 2] the Downsample conv has 64 and ran the vector-ALU kernel, whatever the test was named).  EXACT: codes equal the oracle's except where the oracle's own float64 distance gap is
     within 1e-4 (argmin ties under a different fp32 summation order), feature map within 1e-4.  FAST (bf16 convolutions,
     fp32 distance GEMM): every chosen code is the nearest one for the device's own quantiser input (up to 1e-4 ties), the
     feature map within 0.15 (2 % of its range) of the fp32 one, >= 60 % of the codes identical to the fp32 choice."""
     import os
-    spec = Stage1Spec(ch=64, ch_mult=[1, 2], num_res_blocks=1, attn_resolutions=[16], resolution=64, z_channels=64,
+    spec = Stage1Spec(ch=64, ch_mult=[2, 2], num_res_blocks=1, attn_resolutions=[16], resolution=64, z_channels=64,
                       embed_dim=32, n_embed=256)
     weights = synth.stage1_weights(spec, 81, 'fixture', encoder=True)
     x = _synth_images(82, 5, 64)
@@ -613,9 +668,13 @@ def test_encode_wide_config_exact_and_fast_vs_oracle():
     try:
         eng = engine_s1(spec, weights, 5)
         ex = eng.encode(torch.from_numpy(x), precision=PRECISION_EXACT, want_resid=True)
+        eng.timing(True)
         fa = eng.encode(torch.from_numpy(x), precision=PRECISION_FAST, want_resid=True)
+        down = {k: _launches(eng, k).get('conv_down', 0) for k in ('mfma_gemm', 'gemm_generic_bf16')}
     finally:
         del os.environ['HQT_FORCE_TILE128']
+    # the stride-2 Downsample conv (s1_layer's tag 'conv_down') ran the LDS-DMA MFMA kernel, which only a big-tile shape takes: the hook was in effect
+    assert down['mfma_gemm'] > 0 and down['gemm_generic_bf16'] == 0, down
     assert np.abs(np_(ex['resid'][0]) - want['resid'][0]).max() <= PIXEL_TOL
     for l in range(2):
         got = np_(ex['codes'][l])

@@ -1,5 +1,5 @@
 """AR-loop time of one merged pass (rows = merge x 64) of the ImageNet-12L model, graphed, one lane -- and, un-graphed with the
-per-launch timers, where it goes.  For A/B runs of the GEMM planner (HQT_TILE_FORCE, HQT_NO_TILE_GEMM).
+per-launch timers, where it goes.  For A/B runs of the GEMM planner (HQT_NO_TILE_GEMM, read at hqt_create).
     python tools/ar_pass_time.py --rows 512 1280 [--policy 1] [--breakdown]"""
 import argparse
 import json

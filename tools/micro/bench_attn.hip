@@ -2,6 +2,7 @@
 // runs them), by number of cached keys -- achieved bytes/s against the K/V bytes the launch must read.  Also a head-major cache layout
 // ([b][head][t][hs]: one (sample, head)'s keys contiguous) through the same arithmetic, to price the layout.
 #include "../../hqtransformer_amd/csrc/attention.hip"
+#include "../../hqtransformer_amd/csrc/switches.hip"
 #include <cstdio>
 #include <vector>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)

@@ -3,6 +3,7 @@
 #include "../../hqtransformer_amd/csrc/fast_kernels.hip"
 #include "../../hqtransformer_amd/csrc/kernels.hip"
 #include "../../hqtransformer_amd/csrc/attention.hip"
+#include "../../hqtransformer_amd/csrc/switches.hip"
 #include <cstdio>
 #include <vector>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)

@@ -1,6 +1,7 @@
 // Micro-benchmark: the LDS-DMA implicit-GEMM conv kernel on the HQ-VAE decoder's layer shapes (batch 64), with
 // ablations that separate the epilogue, the DMA/address generation and the MFMA/LDS-read loop.
 #include "../../hqtransformer_amd/csrc/mfma_gemm.hip"
+#include "../../hqtransformer_amd/csrc/switches.hip"
 #include <cstdio>
 #include <vector>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)

@@ -2,6 +2,7 @@
 // per wave (MT), cold weights (8 rotating copies: 300-600 MB, beyond the Infinity Cache).
 //   hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/micro/bench_exact.hip -o tools/micro/bench_exact
 #include "../../hqtransformer_amd/csrc/exact_gemm.hip"
+#include "../../hqtransformer_amd/csrc/switches.hip"
 #include <cstdio>
 #include <vector>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)

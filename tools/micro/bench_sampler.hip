@@ -1,6 +1,7 @@
 // Micro-benchmark: the fused sampler at merged-pass row counts (V = 8192), plain / top-k / top-k + top-p, and a row table (hqt_set_row_samplers)
 // that mixes them: FAST runs both kernels over the pass, each leaving the other one's rows at once.
 #include "../../hqtransformer_amd/csrc/kernels.hip"
+#include "../../hqtransformer_amd/csrc/switches.hip"
 #include <cstdio>
 #include <vector>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)

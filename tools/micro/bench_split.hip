@@ -3,6 +3,7 @@
 //   hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/micro/bench_split.hip -o tools/micro/bench_split
 #include "../../hqtransformer_amd/csrc/split_conv.hip"
 #include "../../hqtransformer_amd/csrc/split_stream_conv.hip"
+#include "../../hqtransformer_amd/csrc/switches.hip"
 #include <cstdio>
 #include <cstring>
 #include <vector>

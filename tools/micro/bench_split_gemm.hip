@@ -4,6 +4,7 @@
 #define HQT_SPLIT_GEMM_STAMPS 1
 #include "../../hqtransformer_amd/csrc/split_conv.hip"
 #include "../../hqtransformer_amd/csrc/split_stream_conv.hip"
+#include "../../hqtransformer_amd/csrc/switches.hip"
 #include <cstdio>
 #include <cstring>
 #include <vector>
