@@ -126,6 +126,7 @@ SYMBOLS = {
     'hqt_select_rows': (C.c_int, [_VP, C.c_int, _VP, _VP]),
     'hqt_set_row_positions': (C.c_int, [_VP, C.c_int, _VP, C.c_int]),
     'hqt_set_max_joins': (C.c_int, [_VP, C.c_int]),
+    'hqt_set_join_run': (C.c_int, [_VP, C.c_int, C.c_int]),
     'hqt_sample': (C.c_int, [_VP, C.c_int, _I64P, C.POINTER(hqt_sample_opts), _F32P, _I64P, _I64P, _F32P, _I64P, _I64P, _VP]),
     'hqt_set_max_prefix': (C.c_int, [_VP, C.c_int]),
     'hqt_sample_prefix': (C.c_int, [_VP, C.c_int, _I64P, C.POINTER(hqt_sample_opts), _F32P, C.c_int, _I64P, _I64P, _I64P, _I64P, _F32P, _I64P, _I64P, _VP]),

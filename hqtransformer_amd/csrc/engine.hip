@@ -180,14 +180,18 @@ struct hqt_handle {
     } staged;
     Staged take_staged() { Staged s = std::move(staged); staged = Staged(); return s; }
     void clear_staged() { staged = Staged(); }
-    // staging of staged_prompt_prefill (shared prompts; the joiners of a rolling text pass), sized (grown) by hqt_set_prompt_groups and hqt_set_max_joins
-    // (reserve_prompt_staging) and by nothing else: K and V of [n_layers][pg_cap][ctx_len_txt][D] at 4 bytes per element (any mode's activation type fits), and
-    // the [max_batch, D] fp32 rows the fan-out gathers for the depth head of position 0
+    // staging of staged_prompt_prefill (shared prompts; the joiners of a rolling pass), sized (grown) by hqt_set_prompt_groups, hqt_set_max_joins and hqt_set_join_run
+    // (reserve_prompt_staging) and by nothing else: K and V of [n_layers][prompts][rows][D] at 4 bytes per element (any mode's activation type fits) for the largest
+    // prompts * rows asked for (rows: ctx_len_txt, with hqt_set_join_run + max_run, 1 + max_run without text), and the [max_batch, D] fp32 rows the fan-out gathers
+    // for the depth head of the position behind the prefill
     void *pg_k = nullptr, *pg_v = nullptr;
     float* pg_x = nullptr;
-    int pg_cap = 0;                           // prompts the staging holds
+    int pg_cap = 0;                           // prompts (of ctx_len_txt rows or more) the staging holds
     size_t pg_bytes = 0;                      // bytes of pg_k (= pg_v)
     int max_joins = 0;                        // hqt_set_max_joins: rows that may join a rolling pass of a text handle in one call (0: such a pass is refused)
+    int join_run = -1;                        // hqt_set_join_run: a rolling call may take a keep table, and joining rows prefill a shared leading kept run of up to this
+                                              // many positions in the join phase, max_joins of them per call (-1: not opted in, such a call is refused)
+    int staging_rows(int run) const { return (cfg.cond_type == HQT_COND_TEXT ? cfg.ctx_len_txt : 1) + run; }      // body rows of one joiner in the join phase
     // the pass a segment stopped in: what a continuation must match, and `pos`, the position it goes on from (the step state says pos over t_live keys)
     struct Paused { bool live = false; int B = 0, n_steps = 0, levels = 0, precision = 0, pos = 0; } paused;
     // the rolling pass the last hqt_set_row_positions call left: what the next one must match, and per slot the position it draws next (-1: empty)
@@ -261,14 +265,17 @@ static int dev_alloc(hqt_handle* h, void** p, size_t bytes, bool workspace) {
 // The one place that allocates the staging of staged_prompt_prefill, the prompt prefill over fewer rows than the pass has (hqt_handle::pg_*): room for `n_groups`
 // prompts, grown and never shrunk (a larger need frees the old pair once the device has drained, a smaller one reuses it), and with the first need the gathered
 // x rows.  Those start as zeros: with joiners as the prompts the prefill writes only their rows and runs the depth head over all.  The caller has set the device.
-static int reserve_prompt_staging(hqt_handle* h, int n_groups) {
+static int reserve_prompt_staging(hqt_handle* h, int n_groups, int rows = 0) {      // rows per prompt; 0: ctx_len_txt
     const hqt_config& c = h->cfg;
+    if (rows == 0) rows = c.ctx_len_txt;
     if (!h->pg_x) {
         CHK(dev_alloc(h, (void**)&h->pg_x, (size_t)c.max_batch * c.embed_dim * 4, true));
         HIPCHK(hipMemset(h->pg_x, 0, (size_t)c.max_batch * c.embed_dim * 4));
         HIPCHK(hipDeviceSynchronize());          // (the calls that read it run on the caller's streams)
     }
-    if (n_groups <= h->pg_cap) return HQT_OK;
+    const size_t bytes = (size_t)c.n_layers * n_groups * rows * c.embed_dim * 4;
+    if (bytes <= h->pg_bytes) { h->pg_cap = std::max(h->pg_cap, n_groups); return HQT_OK; }      // (rows >= ctx_len_txt: as many prompts fit)
+    const int held = h->pg_cap;                  // (the larger pair holds them too)
     if (h->pg_k) {
         HIPCHK(hipDeviceSynchronize());          // an earlier call may still be reading the old pair
         for (void** p : {&h->pg_k, &h->pg_v}) {
@@ -277,13 +284,12 @@ static int reserve_prompt_staging(hqt_handle* h, int n_groups) {
             h->workspace_bytes -= h->pg_bytes;
             *p = nullptr;
         }
-        h->pg_cap = 0;
+        h->pg_cap = 0; h->pg_bytes = 0;
     }
-    const size_t bytes = (size_t)c.n_layers * n_groups * c.ctx_len_txt * c.embed_dim * 4;
     CHK(dev_alloc(h, &h->pg_k, bytes, true));
     CHK(dev_alloc(h, &h->pg_v, bytes, true));
     h->pg_bytes = bytes;
-    h->pg_cap = n_groups;
+    h->pg_cap = std::max(held, n_groups);
     return HQT_OK;
 }
 
@@ -708,7 +714,9 @@ extern "C" int hqt_clone(hqt_handle* src, hqt_handle** out) {
     h->persist_used = false; h->persist_tripped = false; h->capture_persist = false; h->graph_has_persist = false;
     h->policy = HQT_POLICY_LATENCY;              // a lane's tile choice never depends on what the root ran when it was cloned
     int rc = alloc_workspace(h.get());
-    if (rc == HQT_OK && h->max_joins > 0) rc = reserve_prompt_staging(h.get(), h->max_joins);      // (hqt_set_max_joins on the root: the lane joins as many, in a staging of its own)
+    // (hqt_set_max_joins / hqt_set_join_run on the root: the lane joins as many rows over as long a run, in a staging of its own; without text and a run there is none)
+    if (rc == HQT_OK && h->max_joins > 0 && (h->cfg.cond_type == HQT_COND_TEXT || h->join_run > 0))
+        rc = reserve_prompt_staging(h.get(), h->max_joins, h->staging_rows(std::max(h->join_run, 0)));
     if (rc != HQT_OK) { for (void* p : h->owned) hipFree(p); return rc; }
     root->n_clones++;
     *out = h.release();
@@ -1235,7 +1243,8 @@ struct SampleCtx {
     int roll_k = 0;                              // ... and the steps the call runs (it then is positions [0, roll_k) of the launch loop: start = 0, stop = roll_k)
     const int* row_pos = nullptr;                // ... and its device copy (h->row_pos) that the launches of a rolling call read, NULL otherwise
     const int64_t* roll_prev[3] = {nullptr, nullptr, nullptr};   // ... and the caller's out_*: where the codes of position pos[b] - 1 of every continued row are read
-    int n_join = 0;                              // ... on a text handle: the rows with roll[b] == 0, whose prompt prefill (the join phase) draws position 0 in front of the steps
+    int n_join = 0;                              // ... where a join phase runs (a text handle; a kept run to prefill): the rows with roll[b] == 0, which it draws position join_len for in front of the steps
+    int join_len = 0;                            // ... and the leading kept run those rows share and prefill there (0 without a keep table)
     hipStream_t st;
     Mode md;
 };
@@ -1245,12 +1254,12 @@ static const char ROLLING_TEXT_REFUSAL[] =
     "hqt_set_row_positions: a rolling pass on a text-conditional handle is not built (a row that joins at position 0 needs a prompt prefill of its own)"
     " unless the handle has sized one: hqt_set_max_joins(h, J > 0) allocates the staging for J joining rows per call";
 
-// What a rolling call leaves of the position a row presented (-1: an empty slot): where the slot stands behind it, -1 once its last position is drawn.  On a
-// text handle a joining row (position 0) is moved on by the join phase AND by the k steps: 1 + k.  The handle's record, what the next call must present and
-// the copy-out all follow this rule.
-static int rolled_to(const hqt_config& cf, int pos, int k, int n) {
+// What a rolling call leaves of the position a row presented (-1: an empty slot): where the slot stands behind it, -1 once its last position is drawn.  A row
+// that joins (position 0) through a join phase (`join_phase`: a text handle, or a kept run of join_len > 0 to prefill) is moved on by the phase, which covers
+// positions [0, join_len], AND by the k steps: join_len + 1 + k.  The handle's record, what the next call must present and the copy-out all follow this rule.
+static int rolled_to(int pos, int k, int n, bool join_phase, int join_len) {
     if (pos < 0) return -1;
-    const int next = pos + k + (cf.cond_type == HQT_COND_TEXT && pos == 0 ? 1 : 0);
+    const int next = pos + k + (join_phase && pos == 0 ? join_len + 1 : 0);
     return next < n ? next : -1;
 }
 
@@ -1879,12 +1888,34 @@ static int check_segment(const hqt_handle* h, const SampleCtx& c, int B) {
     }
     return HQT_OK;
 }
+// The join phase of a rolling call (sample_run): which rows it takes and the kept run it prefills.  The rows that join (position 0) share
+// L = min(smallest leading run of ones of their mask rows, max_run of hqt_set_join_run, n_steps - 1), 0 without a keep table; the phase runs on a text handle (the
+// joiners' prompts) and wherever L > 0, and draws position L.  Without it (no text, L == 0) a joining row's position 0 is an ordinary step.
+static int check_joins(const hqt_handle* h, SampleCtx& c, const hqt_config& cf, int B) {
+    const bool text = cf.cond_type == HQT_COND_TEXT;
+    int joiners = 0, L = c.keep ? std::min(std::max(h->join_run, 0), c.n_steps - 1) : 0;
+    for (int b = 0; b < B; ++b) {
+        if (c.roll[b] != 0) continue;
+        ++joiners;
+        int run = 0;
+        while (run < L && c.keep[(size_t)b * c.n_steps + run]) ++run;
+        L = run;
+    }
+    if (!joiners || (!text && L == 0)) return HQT_OK;
+    c.n_join = joiners; c.join_len = L;
+    if (c.n_join > h->max_joins)
+        return fail(HQT_ERR_INVALID, "hqt_set_row_positions: %d rows join at position 0 in this call, the handle's staging holds the prompts of max_joins=%d (hqt_set_max_joins)", c.n_join, h->max_joins);
+    const size_t need = (size_t)cf.n_layers * c.n_join * h->staging_rows(L) * cf.embed_dim * 4;
+    if (need > h->pg_bytes || !h->pg_k || !h->pg_v || !h->pg_x)
+        return fail(HQT_ERR_STATE, "hqt_set_max_joins: the staging buffer holds %d prompts, %d rows join", h->pg_cap, c.n_join);
+    return HQT_OK;
+}
 static int check_rolling(const hqt_handle* h, SampleCtx& c, const hqt_handle::Staged& s, const hqt_config& cf, int B) {
     const int n = c.n_steps;
     if (cf.cond_type == HQT_COND_TEXT && h->max_joins < 1) return fail(HQT_ERR_INVALID, "%s", ROLLING_TEXT_REFUSAL);      // (hqt_set_max_joins(0) behind the staging call)
     if (c.with_prefix) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: the staged positions were taken by a prefix entry point; a rolling pass with a code prefix is not built (hqt_sample / hqt_sample_l3 take the table)");
     if (c.seg) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged segment (hqt_set_segment) is not built: the k of the table is the call's span");
-    if (c.keep) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged keep table (hqt_set_keep_mask) is not built");
+    if (c.keep && h->join_run < 0) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged keep table (hqt_set_keep_mask) is not built");      // (unless hqt_set_join_run opted in)
     if (c.groups) return fail(HQT_ERR_INVALID, "hqt_set_row_positions together with a staged prompt-group table (hqt_set_prompt_groups) is not built");
     if ((int)s.roll.size() != B) return fail(HQT_ERR_INVALID, "hqt_set_row_positions staged a table of B=%d, this call has B=%d", (int)s.roll.size(), B);
     if (c.roll_k < 1 || c.roll_k > n) return fail(HQT_ERR_INVALID, "hqt_set_row_positions: k=%d outside [1, n_steps = %d]", c.roll_k, n);
@@ -1915,15 +1946,8 @@ static int check_rolling(const hqt_handle* h, SampleCtx& c, const hqt_handle::St
         if (want < 0) return fail(HQT_ERR_STATE, "hqt_set_row_positions: row %d continues at position %d, but the slot is empty in the rolling pass (0 joins, -1 stays empty)", b, c.roll[b]);
         return fail(HQT_ERR_STATE, "hqt_set_row_positions: row %d continues at position %d, but the slot stands at position %d of the rolling pass", b, c.roll[b], want);
     }
-    if (cf.cond_type == HQT_COND_TEXT) {     // the rows that join draw position 0 in a prompt prefill of their own, in front of the steps (sample_run)
-        for (int b = 0; b < B; ++b) c.n_join += c.roll[b] == 0;
-        if (c.n_join > h->max_joins)
-            return fail(HQT_ERR_INVALID, "hqt_set_row_positions: %d rows join at position 0 in this call, the handle's staging holds the prompts of max_joins=%d (hqt_set_max_joins)", c.n_join, h->max_joins);
-        if (c.n_join > h->pg_cap || (c.n_join && (!h->pg_k || !h->pg_v || !h->pg_x)))
-            return fail(HQT_ERR_STATE, "hqt_set_max_joins: the staging buffer holds %d prompts, %d rows join", h->pg_cap, c.n_join);
-    }
     c.start = 0; c.stop = c.roll_k;
-    return HQT_OK;
+    return c.keep ? HQT_OK : check_joins(h, c, cf, B);      // (a keep table: behind its own checks, check_keep)
 }
 // (the group table is asked about a prefix here, where that test has always stood: behind the rolling table, in front of the prefix's own)
 static int check_prefix(const hqt_handle* h, const SampleCtx& c, const hqt_config& cf) {
@@ -1947,6 +1971,8 @@ static int check_keep(const hqt_handle* h, SampleCtx& c, const hqt_handle::Stage
     for (int i = 0; i < c.levels; ++i)
         if (c.feed[i]) return fail(HQT_ERR_INVALID, "%s together with a keep table is not built: put the forced codes into the kept codes (hqt_set_keep_mask)", fname[c.levels == 3][i]);
     for (int i = 0; i < c.levels; ++i) if (!c.keep_codes[i]) return fail(HQT_ERR_INVALID, "hqt_set_keep_mask: kept codes of level %d are NULL", i);
+    // a rolling call: no prefill over all rows; the run its joining rows share goes through the join phase (hqt_set_join_run)
+    if (c.roll) return check_joins(h, c, cf, B);
     // the leading run every row shares goes through the one-pass prefix prefill, where it is built (hqt_set_max_prefix; not text with three code levels)
     int L = std::min(h->max_prefix, c.n_steps - 1);
     if (cf.cond_type == HQT_COND_TEXT && c.levels == 3) L = 0;
@@ -2023,13 +2049,13 @@ static int finish_rolling(hqt_handle* h, const SampleCtx& c, int64_t* const* out
     const int B = c.B;
     for (int i = 0; i < (drew ? c.levels : 0); ++i) {
         HIPCHK(launch_copy_row_positions(c.out[i], out[i], h->row_pos_received(), B, c.n_steps, LEVEL_WIDTH[i], 0, c.roll_k, c.st));
-        // a joining row of a text pass drew positions [0, 1 + k): its last one through the join table (0 for the joiners, -1 for every other row)
-        if (c.n_join) HIPCHK(launch_copy_row_positions(c.out[i], out[i], h->row_pos_join(), B, c.n_steps, LEVEL_WIDTH[i], c.roll_k, c.roll_k + 1, c.st));
+        // a row that joined through the join phase passed positions [0, L + 1 + k): those behind the first k through the join table (L for the joiners, -1 for every other row)
+        if (c.n_join) HIPCHK(launch_copy_row_positions(c.out[i], out[i], h->row_pos_join(), B, c.n_steps, LEVEL_WIDTH[i], c.roll_k - c.join_len, c.roll_k + 1, c.st));
     }
     hqt_handle::Rolling& r = h->rolling;
     r.B = B; r.n_steps = c.n_steps; r.levels = c.levels; r.precision = c.precision;
     r.next.assign(B, -1);
-    for (int b = 0; b < B; ++b) r.next[b] = rolled_to(h->cfg, c.roll[b], c.roll_k, c.n_steps);
+    for (int b = 0; b < B; ++b) r.next[b] = rolled_to(c.roll[b], c.roll_k, c.n_steps, c.n_join > 0, c.join_len);
     r.live = std::any_of(r.next.begin(), r.next.end(), [](int32_t p) { return p >= 0; });      // every slot empty: the pass is over, nothing is left to match
     return HQT_OK;
 }
@@ -2206,6 +2232,28 @@ extern "C" int hqt_set_max_joins(hqt_handle* h, int max_joins) {
     ON_DEVICE(h);
     if (max_joins > 0) CHK(reserve_prompt_staging(h, max_joins));
     h->max_joins = max_joins;
+    return HQT_OK;
+}
+
+// Opt-in sizing of rolling calls that take a keep table (hqt_set_keep_mask): up to max_joins rows per call join through the join phase, which prefills a leading kept
+// run of up to max_run positions that they share (hqt_set_max_prefix has sized the body workspace for such a pass).  Grows the staging of staged_prompt_prefill to
+// max_joins * ((ctx_len_txt | 1) + max_run) rows; without text and with max_run == 0 no join phase ever runs and nothing is allocated.  On a text handle it is also
+// hqt_set_max_joins(h, max_joins).  0 joins switch the opt-in off again and free nothing.
+extern "C" int hqt_set_join_run(hqt_handle* h, int max_joins, int max_run) {
+    if (!h) return fail(HQT_ERR_INVALID, "null handle");
+    const hqt_config& c = h->cfg;
+    const bool text = c.cond_type == HQT_COND_TEXT;
+    if (!c.has_stage2) return fail(HQT_ERR_INVALID, "hqt_set_join_run: the handle was created without stage 2");
+    if (max_joins < 0 || max_joins > c.max_batch) return fail(HQT_ERR_INVALID, "hqt_set_join_run: max_joins=%d outside [0, max_batch=%d]", max_joins, c.max_batch);
+    if (max_run < 0 || max_run > h->max_prefix)
+        return fail(HQT_ERR_INVALID, "hqt_set_join_run: max_run=%d outside [0, max_prefix=%d] of this handle (hqt_set_max_prefix sizes the body workspace for the prefill's rows)", max_run, h->max_prefix);
+    if (max_run > 0 && text && c.code_levels == 3)
+        return fail(HQT_ERR_INVALID, "hqt_set_join_run: max_run=%d with text conditioning and three code levels is not built (the prefix prefill is not; max_run = 0 is)", max_run);
+    if (h->rolling.live) return fail(HQT_ERR_STATE, "hqt_set_join_run: this handle holds a rolling pass (hqt_set_row_positions); finish it first");
+    ON_DEVICE(h);
+    if (max_joins > 0 && (text || max_run > 0)) CHK(reserve_prompt_staging(h, max_joins, h->staging_rows(max_run)));
+    h->join_run = max_joins > 0 ? max_run : -1;
+    h->max_joins = max_joins;                    // (a text handle: hqt_set_max_joins(h, max_joins) as well; any other reads it in the join phase only)
     return HQT_OK;
 }
 
@@ -2506,15 +2554,15 @@ static int send_row_tables(hqt_handle* h, const SampleCtx& c) {
     if (c.keep) CHK(ring_send(ring.keep, c.keep, (size_t)B * c.n_steps, h->keep_mask, c.st));
     if (c.groups) CHK(ring_send(ring.groups, c.groups, (size_t)B, h->group_of_row, c.st));
     if (c.roll) {
-        // the positions the rows stand at (moved on between the steps) and the table as received (what finish_rolling copies out by).  Joining rows of a text pass: the live
-        // table has them behind the join phase already (position 1; n_steps = 1: finished), the join table says 0 for them, -1 for the rest, the fan-out's groups number them
+        // the positions the rows stand at (moved on between the steps) and the table as received (what finish_rolling copies out by).  Rows that join through a join phase: the live
+        // table has them behind it already (position L + 1 behind a kept run of L; past the last position: finished), the join table says L for them, -1 for the rest, the fan-out's groups number them
         int32_t *live = ring.pos, *received = ring.pos + h->cfg.max_batch, *join = ring.pos + 2 * (size_t)h->cfg.max_batch;
         int g = 0;
         for (int b = 0; b < B; ++b) {
             const bool joins = c.n_join && c.roll[b] == 0;
             received[b] = c.roll[b];
-            live[b] = joins ? (c.n_steps > 1 ? 1 : -1) : c.roll[b];
-            join[b] = joins ? 0 : -1;
+            live[b] = joins ? (c.join_len + 1 < c.n_steps ? c.join_len + 1 : -1) : c.roll[b];
+            join[b] = joins ? c.join_len : -1;
             ring.groups[b] = joins ? g++ : -1;
         }
         CHK(ring_send(live, (const int32_t*)nullptr, (size_t)B, h->row_pos, c.st));
@@ -2527,19 +2575,26 @@ static int send_row_tables(hqt_handle* h, const SampleCtx& c) {
     return ring_sent(h, slot, c.st);
 }
 
-// A prompt prefill over fewer rows than the pass has, through the staging (hqt_handle::pg_*): shared prompts (the n_prompts distinct prompts of cond [n_prompts, T]) and
-// the join phase of a rolling text pass (`gathered`: the joiners' prompts, read from cond [B, T] through the group table).  A sample's prompt rows depend on nothing but
-// its prompt, so the embedding and the body blocks run over the prompts alone, K/V into the staging buffer [n_layers][n_prompts][T][D] -- never cache slot g, the
-// destination of row g of the pass, which may carry another prompt --; ONE launch then copies the staged K/V of every row's prompt into its cache slot and gathers its last
-// prompt row of x (a negative group: neither); the depth head runs over the B gathered rows (one per sample) under `head_row_pos` and draws position 0.
-static int staged_prompt_prefill(hqt_handle* h, const SampleCtx& c, int n_prompts, bool gathered, const int* head_row_pos) {
+// A prefill over fewer rows than the pass has, through the staging (hqt_handle::pg_*): shared prompts (the n_prompts distinct prompts of cond [n_prompts, T]) and
+// the join phase of a rolling pass (`gathered`: the joiners' rows, read from cond [B, .] and the handle's code buffers through the group table -- their prompts on a text
+// handle, their sos / class row otherwise, then the input rows of the `run` leading kept positions they share, the layout of embed_prefill).  A sample's prompt rows depend
+// on nothing but its prompt, so the embedding and the body blocks run over the prompts alone, K/V into the staging buffer [n_layers][n_prompts][T][D] -- never cache slot g,
+// the destination of row g of the pass, which may carry another prompt --; ONE launch then copies the staged K/V of every row's prompt into its cache slot and gathers its last
+// row of x (a negative group: neither); the depth head runs over the B gathered rows (one per sample) under `head_row_pos` and draws position `run` (0 without a kept run).
+static int staged_prompt_prefill(hqt_handle* h, const SampleCtx& c, int n_prompts, bool gathered, const int* head_row_pos, int run = 0) {
     const hqt_config& cf = h->cfg;
-    const int T = cf.ctx_len_txt, D = cf.embed_dim;
+    const bool text = cf.cond_type == HQT_COND_TEXT;
+    const int Tp = text ? cf.ctx_len_txt : 0, T = (text ? Tp : 1) + run, D = cf.embed_dim;      // Tp prompt rows, T rows per prompt in all
+    if (!gathered && (!text || run)) return fail(HQT_ERR_INVALID, "staged_prompt_prefill: only the join phase of a rolling pass prefills a kept run or rows without a prompt");
     SampleCtx cg = c;
     cg.B = n_prompts;
     cg.row_pos = nullptr;                            // (the prefill of the prompts knows no positions)
-    if (gathered) HIPCHK(launch_embed_text_rows(c.cond, h->group_of_row, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, c.B, n_prompts, T, D, c.st, cf.vocab_txt));
-    else HIPCHK(launch_embed_text(c.cond, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, n_prompts, T, D, c.st, cf.vocab_txt, T));
+    if (!text || run) {                              // the sos / class row and the rows of the kept run, as embed_prefill lays them out: (text) `run` rows behind the prompt, at step offset 1
+        Timed t(h, "embed_prefix", c.st);
+        HIPCHK(launch_embed_prefix_rows(embed_args(h, c, c.out), h->group_of_row, n_prompts, T - Tp, T, Tp, text ? 1 : 0, c.st));
+    }
+    if (text && gathered) HIPCHK(launch_embed_text_rows(c.cond, h->group_of_row, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, c.B, n_prompts, Tp, D, c.st, cf.vocab_txt, T));
+    else if (text) HIPCHK(launch_embed_text(c.cond, W(h, "tok_emb_txt.weight"), W(h, "pos_emb_txt.weight"), h->x, n_prompts, Tp, D, c.st, cf.vocab_txt, T));
     const KvStage stage{h->pg_k, h->pg_v};
     bool pfull = false;
     CHK(run_body(h, cg, T, 0, false, false, &pfull, &stage));
@@ -2610,19 +2665,24 @@ static int sample_run(hqt_handle* h, const SampleCtx& c) {
     CHK(send_row_tables(h, c));
     // the kept codes go into the handle's code buffers (outside any captured graph) behind the mask: every level's embeddings, the samplers' guard and
     // code_logprob read them there
-    for (int i = 0; i < (c.keep ? c.levels : 0); ++i)
+    for (int i = 0; i < (c.keep && !c.roll ? c.levels : 0); ++i)
         HIPCHK(launch_copy_kept(c.keep_codes[i], c.out[i], h->keep_mask, c.B, c.n_steps, LEVEL_WIDTH[i], cf.vocab_top, c.st));
     if (!c.row_seeds && !c.guide) HIPCHK(launch_set_rows(h->rows, c.B, c.seed, c.sample_offset, c.st));
     int first = c.start;
     // a rolling pass: every continued row reads the codes of its position pos[b] - 1 where the caller holds them, as a segment does (a forced level: force_*)
     for (int i = 0; i < (c.roll ? c.levels : 0); ++i)
         if (c.feed[i] == c.out[i]) HIPCHK(launch_copy_row_positions(c.roll_prev[i], c.out[i], h->row_pos_received(), c.B, c.n_steps, LEVEL_WIDTH[i], -1, 0, c.st));
+    // ... and with a keep table every row takes the kept codes of the span it passes in this call, [pos[b], pos[b] + k) and, joining through the join phase, the run in front
+    for (int i = 0; i < (c.roll && c.keep ? c.levels : 0); ++i)
+        HIPCHK(launch_copy_kept_rows(c.keep_codes[i], c.out[i], h->keep_mask, h->row_pos_received(), c.B, c.n_steps, LEVEL_WIDTH[i], c.roll_k,
+                                     c.roll_k + (c.n_join ? c.join_len + 1 : 0), cf.vocab_top, c.st));
     if (c.start > 0) {                           // a continuation (hqt_set_segment): no prefill -- the cache holds the prompt rows and every position below start
     } else if (c.roll) {
-        // A rolling pass runs no prefill over its rows; on a text handle the rows that join run the JOIN PHASE, the staged prompt prefill with the joiners as the
-        // groups and the depth head under the join table: the joiners draw position 0 under their own key, sampler row and noise slice, every other row is idle
-        // (it computes on the finite row it was left with and writes nothing).  The steps below find the joiners at position 1, behind ctx_len_txt cache rows.
-        if (c.n_join) CHK(staged_prompt_prefill(h, c, c.n_join, true, h->row_pos_join()));
+        // A rolling pass runs no prefill over its rows; the rows that join a text handle, or join behind a leading kept run L > 0 (check_joins), run the JOIN PHASE, the
+        // staged prompt prefill with the joiners as the groups and the depth head under the join table: the joiners draw position L (kept itself: the samplers' guard) under
+        // their own key, sampler row and noise slice, every other row is idle (it computes on the finite row it was left with and writes nothing).  The steps below find the
+        // joiners at position L + 1, behind (ctx_len_txt | 1) + L cache rows.
+        if (c.n_join) CHK(staged_prompt_prefill(h, c, c.n_join, true, h->row_pos_join(), c.join_len));
     } else if (cf.cond_type == HQT_COND_TEXT && c.groups) {
         // shared prompts (P = 0, checked by sample_call): afterwards the cache and the step state are what the unshared prefill leaves
         CHK(staged_prompt_prefill(h, c, c.n_groups, false, nullptr));

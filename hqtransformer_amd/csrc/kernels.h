@@ -45,17 +45,25 @@ hipError_t launch_embed_prefix(const EmbedArgs& a, int rows, int stride, int row
 hipError_t launch_copy_prefix(const int64_t* src, int64_t* dst, int B, int P, int n_steps, int width, int V, hipStream_t st);
 // The masked sibling (hqt_set_keep_mask): dst[b, t, :] = clamp(src[b, t, :]) where keep[b * n_steps + t] != 0, both [B, n_steps, width]; other entries of dst are left alone
 hipError_t launch_copy_kept(const int64_t* src, int64_t* dst, const unsigned char* keep, int B, int n_steps, int width, int V, hipStream_t st);
+// The per-row-span sibling (a rolling pass with a keep table): row b takes only the kept positions of [pos[b], pos[b] + (pos[b] == 0 ? k0 : k)) clipped to n_steps
+// (pos: device, [B], the table as received; k0 >= k); rows with pos[b] < 0 and positions outside the span are neither read nor written
+hipError_t launch_copy_kept_rows(const int64_t* src, int64_t* dst, const unsigned char* keep, const int* pos, int B, int n_steps, int width, int k, int k0, int V,
+                                 hipStream_t st);
+// The gathered sibling of launch_embed_prefix (the join phase of a rolling pass): row b of the pass whose g = group_of_row[b] (device, [a.B]) lies in [0, G) writes
+// x[g * stride + row_off + j] = its body input row step_off + j, j < rows; other rows are neither read nor written
+hipError_t launch_embed_prefix_rows(const EmbedArgs& a, const int* group_of_row, int G, int rows, int stride, int row_off, int step_off, hipStream_t st);
 
 // text prompt: x[b * rows_per_sample + t, :] = tok_emb_txt[cond[b, t]] + pos_emb_txt[t]
 hipError_t launch_embed_text(const int64_t* cond, const float* tok, const float* pos, float* x, int B, int T, int D,
                              hipStream_t st, int vocab = 0, int rows_per_sample = 0);      // rows_per_sample 0: T
 
-// the prompts of the rows that join a rolling pass: x[g * T + t, :] = tok_emb_txt[cond[b, t]] + pos_emb_txt[t] for every row b of cond [B, T] whose
+// the prompts of the rows that join a rolling pass: x[g * rows_per_sample + t, :] = tok_emb_txt[cond[b, t]] + pos_emb_txt[t] for every row b of cond [B, T] whose
 // g = group_of_row[b] (device, [B]) lies in [0, G); other rows are neither read nor written
 hipError_t launch_embed_text_rows(const int64_t* cond, const int* group_of_row, const float* tok, const float* pos, float* x, int B, int G, int T, int D,
-                                  hipStream_t st, int vocab);
+                                  hipStream_t st, int vocab, int rows_per_sample = 0);      // rows_per_sample 0: T
 
-// Shared prompts (hqt_set_prompt_groups): the prefill ran over G distinct prompts into a staging K/V of [n_layers][G][T][row_bytes]; one launch hands
+// Shared prompts (hqt_set_prompt_groups) and the join phase of a rolling pass (T = the rows per joiner: prompt or sos row, then its kept run): the prefill ran
+// over G distinct prompts into a staging K/V of [n_layers][G][T][row_bytes]; one launch hands
 // every row b of the pass the prompt of its group g = group_of_row[b] (device, B entries):
 //   cache slot b, tokens 0 .. T - 1 of every layer <- staging rows of g (K and V; the cache is [n_layers][cache_slots][Tcache][row_bytes]),
 //   x_out[b, :] <- x_src[g * T + T - 1, :] (fp32 [., D]: the last prompt row of the residual stream; x_out must not overlap x_src)

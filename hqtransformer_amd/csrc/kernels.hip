@@ -153,6 +153,23 @@ hipError_t launch_embed_prefix(const EmbedArgs& a, int rows, int stride, int row
     return hipGetLastError();
 }
 
+// The gathered sibling (the join phase of a rolling pass: hqt_set_join_run): only the rows that join take part, and their body rows are packed by group.  Row b with
+// g = group_of_row[b] in [0, G) writes x[g * stride + row_off + j] = embed_row(b, step_off + j), reading cond[b] and the codes of ITS row of a.codes_*; every other row
+// (group -1: mid-image, or an empty slot) reads and writes nothing.
+__global__ __launch_bounds__(256) void embed_prefix_rows_kernel(EmbedArgs a, const int* group_of_row, int G, int rows, int stride, int row_off, int step_off) {
+    const int b = blockIdx.x / rows, j = blockIdx.x - b * rows;
+    if (b >= a.B) return;
+    const int g = group_of_row[b];
+    if (g < 0 || g >= G) return;
+    embed_row(a, b, step_off + j, a.x + ((long long)g * stride + row_off + j) * a.D);
+}
+hipError_t launch_embed_prefix_rows(const EmbedArgs& a, const int* group_of_row, int G, int rows, int stride, int row_off, int step_off, hipStream_t st) {
+    if (a.B < 1 || G < 1 || G > a.B || !group_of_row || !a.x) return hipErrorInvalidValue;
+    if (rows < 1 || row_off < 0 || step_off < 0 || row_off + rows > stride || step_off + rows > a.n_steps || a.xpk) return hipErrorInvalidValue;
+    embed_prefix_rows_kernel<<<a.B * rows, 256, 0, st>>>(a, group_of_row, G, rows, stride, row_off, step_off);
+    return hipGetLastError();
+}
+
 // The prefix codes of one level, [B, P, width], into the first P positions of the handle's [B, n_steps, width] code buffer (clamped into
 // the vocabulary like every index that arrives from the caller)
 __global__ __launch_bounds__(256) void copy_prefix_kernel(const int64_t* src, int64_t* dst, long long n, int per_sample, int dst_per_sample, int V) {
@@ -181,6 +198,42 @@ hipError_t launch_copy_kept(const int64_t* src, int64_t* dst, const unsigned cha
     return hipGetLastError();
 }
 
+// The per-row-span sibling (a rolling pass that takes a keep table: hqt_set_join_run): row b scatters only the kept positions of the span it advances over in this
+// call, [pos[b], pos[b] + (pos[b] == 0 ? k0 : k)) clipped to n_steps -- k0 >= k: a row that joins through a join phase passes its prefilled run too.  `pos` is the table
+// as the call received it (device, [B]); a row with pos[b] < 0 (an empty slot) and every position outside the span are neither read nor written, in mask, src or dst.
+// One thread per unit of UNIT codes of a (row, span position): two (one 16-byte vector) where the width is even and both pointers are 16-byte aligned, else one.
+template <int UNIT>
+__global__ __launch_bounds__(256) void copy_kept_rows_kernel(const int64_t* src, int64_t* dst, const unsigned char* keep, const int* pos, long long n, int k, int k0,
+                                                             int width, int n_steps, int V) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int units = width / UNIT;
+    const long long per_row = (long long)k0 * units;
+    const long long b = i / per_row, r = i - b * per_row;
+    const int j = (int)(r / units), u = (int)(r - (long long)j * units);
+    const int p0 = pos[b];
+    if (p0 < 0 || j >= (p0 == 0 ? k0 : k)) return;
+    const int p = p0 + j;
+    if (p >= n_steps || !keep[b * n_steps + p]) return;
+    const long long at = (b * n_steps + p) * width + (long long)u * UNIT;
+    if (UNIT == 2) {
+        const longlong2 v = *reinterpret_cast<const longlong2*>(src + at);
+        *reinterpret_cast<longlong2*>(dst + at) = make_longlong2(clamp_idx(v.x, V), clamp_idx(v.y, V));
+    } else {
+        dst[at] = clamp_idx(src[at], V);
+    }
+}
+hipError_t launch_copy_kept_rows(const int64_t* src, int64_t* dst, const unsigned char* keep, const int* pos, int B, int n_steps, int width, int k, int k0, int V,
+                                 hipStream_t st) {
+    if (B < 1 || n_steps < 1 || width < 1 || k < 1 || k0 < k || !src || !dst || !keep || !pos) return hipErrorInvalidValue;
+    const bool vec = width % 2 == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+    const long long n = (long long)B * k0 * (width / (vec ? 2 : 1));
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    if (vec) copy_kept_rows_kernel<2><<<grid, 256, 0, st>>>(src, dst, keep, pos, n, k, k0, width, n_steps, V);
+    else copy_kept_rows_kernel<1><<<grid, 256, 0, st>>>(src, dst, keep, pos, n, k, k0, width, n_steps, V);
+    return hipGetLastError();
+}
+
 // The T prompt rows of every sample, x[b * rows_per_sample + t] (rows_per_sample > T: a code prefix's rows follow, embed_prefix_kernel)
 __global__ __launch_bounds__(256) void embed_text_kernel(const int64_t* cond, const float* tok, const float* pos,
                                                          float* x, int T, int D, int vocab, int rows_per_sample) {
@@ -197,19 +250,21 @@ hipError_t launch_embed_text(const int64_t* cond, const float* tok, const float*
 }
 
 // The sibling for the rows that join a rolling pass (hqt_set_max_joins): their prompts are not contiguous in cond [B, T].  `group_of_row` (device, [B]) is the
-// row list: row b with group g in [0, G) writes its T prompt rows to x[g * T + t]; every other row (group -1: mid-image, or an empty slot) reads and writes nothing.
+// row list: row b with group g in [0, G) writes its T prompt rows to x[g * rows_per_sample + t] (rows_per_sample > T: the rows of a kept run follow,
+// embed_prefix_rows_kernel); every other row (group -1: mid-image, or an empty slot) reads and writes nothing.
 __global__ __launch_bounds__(256) void embed_text_rows_kernel(const int64_t* cond, const int* group_of_row, const float* tok, const float* pos,
-                                                              float* x, int G, int T, int D, int vocab) {
+                                                              float* x, int G, int T, int D, int vocab, int rows_per_sample) {
     const int b = blockIdx.x / T, t = blockIdx.x % T;
     const int g = group_of_row[b];
     if (g < 0 || g >= G) return;
-    const long long id = clamp_idx(cond[blockIdx.x], vocab), row = (long long)g * T + t;
+    const long long id = clamp_idx(cond[blockIdx.x], vocab), row = (long long)g * rows_per_sample + t;
     for (int d = threadIdx.x; d < D; d += blockDim.x) x[row * D + d] = tok[id * D + d] + pos[(long long)t * D + d];
 }
 hipError_t launch_embed_text_rows(const int64_t* cond, const int* group_of_row, const float* tok, const float* pos, float* x, int B, int G, int T, int D,
-                                  hipStream_t st, int vocab) {
-    if (B < 1 || G < 1 || G > B || T < 1 || D < 1 || !cond || !group_of_row || !x) return hipErrorInvalidValue;
-    embed_text_rows_kernel<<<B * T, 256, 0, st>>>(cond, group_of_row, tok, pos, x, G, T, D, vocab);
+                                  hipStream_t st, int vocab, int rows_per_sample) {
+    if (rows_per_sample == 0) rows_per_sample = T;
+    if (B < 1 || G < 1 || G > B || T < 1 || D < 1 || rows_per_sample < T || !cond || !group_of_row || !x) return hipErrorInvalidValue;
+    embed_text_rows_kernel<<<B * T, 256, 0, st>>>(cond, group_of_row, tok, pos, x, G, T, D, vocab, rows_per_sample);
     return hipGetLastError();
 }
 

@@ -255,11 +255,13 @@ def check_segment(n_steps: int, segment, prefix=None, keep=None, prompt_groups=N
     return start, stop
 
 
-def check_row_positions(cond_type: int, batch: int, n_steps: int, row_positions, prefix=None, keep=None, prompt_groups=None, segment=None, max_joins: int = 0):
+def check_row_positions(cond_type: int, batch: int, n_steps: int, row_positions, prefix=None, keep=None, prompt_groups=None, segment=None, max_joins: int = 0,
+                        rolling_keep: bool = False):
     """A rolling call (``hqt_set_row_positions``) checked on the host, before any engine is touched: ``row_positions = (pos, k)`` with ``pos`` one integer per row of
     the batch in [-1, n_steps - 1] (-1: an empty slot) and 1 <= k <= n_steps; on a text-conditional model only with ``max_joins`` > 0 (the engine has sized the
-    prompt prefill of its joining rows, ``hqt_set_max_joins``) and then with at most that many rows at position 0; not together with ``prefix``, ``keep``,
-    ``prompt_groups`` or ``segment``.  Returns (pos as a contiguous int32 numpy array, k); None stays None."""
+    prompt prefill of its joining rows, ``hqt_set_max_joins``) and then with at most that many rows at position 0; not together with ``prefix``,
+    ``prompt_groups`` or ``segment``, and with ``keep`` only where ``rolling_keep`` says that the engine has opted in (``hqt_set_join_run``).  Returns (pos as a
+    contiguous int32 numpy array, k); None stays None."""
     if row_positions is None:
         return None
     if not isinstance(row_positions, (list, tuple)) or len(row_positions) != 2:
@@ -268,7 +270,7 @@ def check_row_positions(cond_type: int, batch: int, n_steps: int, row_positions,
     if text and int(max_joins) < 1:
         raise ValueError('row_positions: a rolling pass on a text-conditional model is not built (a row that joins at position 0 needs a prompt prefill of its own)'
                          ' unless the engine has sized one: Engine(..., max_joins=J) / Engine.set_max_joins(J) with J > 0')
-    for other, what in ((prefix, 'prefix'), (keep, 'keep'), (prompt_groups, 'prompt_groups'), (segment, 'segment')):
+    for other, what in ((prefix, 'prefix'), (None if rolling_keep else keep, 'keep'), (prompt_groups, 'prompt_groups'), (segment, 'segment')):
         if other is not None:
             raise ValueError(f'row_positions together with {what} is not built')
     pos, k = row_positions
@@ -406,7 +408,8 @@ class Engine:
     """One libhqt handle on one GPU.  Not thread-safe; asynchronous on torch's current stream."""
 
     def __init__(self, s2: Optional[Stage2Spec], s1: Optional[Stage1Spec], device: torch.device, max_batch: int,
-                 max_steps: Optional[int] = None, ar_layouts: int = 0, max_prefix: int = 0, score_chunk: int = 0, max_joins: int = 0):
+                 max_steps: Optional[int] = None, ar_layouts: int = 0, max_prefix: int = 0, score_chunk: int = 0, max_joins: int = 0,
+                 join_run: Optional[Tuple[int, int]] = None):
         """``ar_layouts``: bit mask of ``_lib.LAYOUT_*`` -- which derived layouts of the AR loop's weights ``finalize`` builds
         (``hqt_config.ar_layouts``; 0 = all).  A FAST-only replica passes ``_lib.LAYOUT_FAST`` and holds 5.2 instead of 9.1 GB for the
         ImageNet-12L model; a call in a precision the engine was built without raises HqtError (HQT_ERR_STATE).
@@ -415,7 +418,8 @@ class Engine:
         ``score_chunk``: (sample, position) pairs per depth chunk of ``score`` (``hqt_set_score_chunk``, called right after ``hqt_create``; 0 = ``max_batch`` pairs,
         and nothing is allocated for it).
         ``max_joins``: rows that may join a rolling pass of a text-conditional model in one call (``hqt_set_max_joins``, called right after ``hqt_create``; 0 = rolling
-        passes on a text model stay refused, and nothing is allocated)."""
+        passes on a text model stay refused, and nothing is allocated).
+        ``join_run`` = (J, R): rolling calls may take ``keep`` (``hqt_set_join_run``, see ``set_join_run``); None = they stay refused."""
         self.lib = _lib.load()                      # raises HqtLibraryError when the HIP library is absent
         self.s2, self.s1 = s2, s1
         self.device = torch.device(device)
@@ -439,6 +443,9 @@ class Engine:
         self.max_joins = 0
         if int(max_joins):
             self.set_max_joins(max_joins)
+        self.join_run = None
+        if join_run is not None:
+            self.set_join_run(*join_run)
         self.policy = _lib.POLICY_LATENCY
 
     def set_max_joins(self, max_joins: int) -> None:
@@ -448,6 +455,17 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.hqt_set_max_joins(self.h, int(max_joins)))
         self.max_joins = int(max_joins)
+
+    def set_join_run(self, max_joins: int, max_run: int) -> None:
+        """``hqt_set_join_run``: after it a rolling call (``row_positions=``) may take ``keep``; up to ``max_joins`` rows per call join through a join phase that
+        prefills a shared leading kept run of up to ``max_run`` positions (``max_run`` <= ``max_prefix`` of the engine; 0 on a text model with three code levels).
+        On a text-conditional engine it is also ``set_max_joins(max_joins)``.  Grows, never shrinks, the staging; ``max_joins`` = 0 switches the opt-in off again.
+        Raises HqtError outside those ranges or while the engine holds a rolling pass."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.hqt_set_join_run(self.h, int(max_joins), int(max_run)))
+        self.join_run = (int(max_joins), int(max_run)) if int(max_joins) > 0 else None
+        if self.s2 is not None and self.s2.cond == 2:
+            self.max_joins = int(max_joins)
 
     def clone(self) -> 'Engine':
         """A further lane over the same weights (``hqt_clone``): own KV cache / activations / graph cache, results
@@ -460,6 +478,7 @@ class Engine:
         e.max_batch, e.max_steps, e.max_prefix, e.cfg = self.max_batch, self.max_steps, self.max_prefix, self.cfg
         e.score_chunk = self.score_chunk
         e.max_joins = getattr(self, '_parent', self).max_joins     # hqt_clone gives the lane a staging of its own for as many joins as the root has sized
+        e.join_run = getattr(getattr(self, '_parent', self), 'join_run', None)      # ... and over as long a run
         h = C.c_void_p()
         _lib.check(self.lib.hqt_clone(self.h, C.byref(h)))
         e.h, e.finalized = h, True
@@ -632,7 +651,8 @@ class Engine:
         dev = self.device
         B, V, L = int(batch), self.s2.vocab_top, int(levels)
         segment = check_segment(n_steps, segment, prefix, keep, prompt_groups)
-        roll = check_row_positions(self.s2.cond, B, n_steps, row_positions, prefix, keep, prompt_groups, segment, max_joins=getattr(self, 'max_joins', 0))
+        roll = check_row_positions(self.s2.cond, B, n_steps, row_positions, prefix, keep, prompt_groups, segment, max_joins=getattr(self, 'max_joins', 0),
+                                   rolling_keep=getattr(self, 'join_run', None) is not None)
         if roll is not None and out is None:
             raise ValueError('row_positions: a rolling call writes the positions its rows draw into out (and reads the codes in front of them there) -- pass the tensors the pass lives in')
         if segment is not None and segment[0] > 0 and out is None:
@@ -649,7 +669,8 @@ class Engine:
                 if f is not None:
                     raise ValueError(f'{what} together with keep is not built: put the forced codes into the kept codes')
             # the leading run every row shares runs as the prefix prefill; its rows of the logits / log-probabilities are not written, as with a prefix
-            P = keep_leading_run(keep[0], self.max_prefix, text_l3=self.s2.cond == 2 and L == 3)
+            # (a rolling call prefills no run over all rows: which rows of the buffers it writes follows the positions, and the buffers are the caller's)
+            P = 0 if roll is not None else keep_leading_run(keep[0], self.max_prefix, text_l3=self.s2.cond == 2 and L == 3)
         draws = (4 ** L - 1) // 3                   # one draw per code of a position: 1 + 4 (+ 16)
         report = check_report_out(report_out, B, n_steps, draws, dev, V)
         shapes = [(B, n_steps) + ((4 ** l,) if l else ()) for l in range(L)]

@@ -17,6 +17,7 @@ from __future__ import annotations
 
 from typing import Any, Callable, List, NamedTuple, Optional, Tuple
 
+import numpy as np
 import torch
 
 from ._lib import POLICY_LATENCY, POLICY_THROUGHPUT
@@ -362,10 +363,15 @@ class RollingSampler:
     Text models need ``max_joins`` (1 <= max_joins <= slots): a row that joins at position 0 needs a prompt prefill of its own, whose staging the engine sizes for
     that many joining rows per call (``hqt_set_max_joins``); without it they are refused.  ``submit(cond=...)`` then takes one prompt of ``ctx_len_txt`` token ids,
     ``step`` admits at most ``max_joins`` requests per call, and a request that joins in a call advances by 1 + k in it -- the join draws position 0 in front of
-    the k steps --, every other by k."""
+    the k steps --, every other by k.
+    ``join_run=R`` (``hqt_set_join_run``; the stage-2 engine must be built with ``max_prefix`` >= R) lets a request bring cells that are GIVEN:
+    ``submit(..., keep_mask=[n] bool, kept_codes=[[n], [n, 4][, [n, 16]]])``.  Kept cells are returned verbatim and everything else is drawn around them.  The
+    requests that join in one call prefill the leading kept run they share, clipped to min(run, R, n - 1), in the call's join phase and advance by run + 1 + k in
+    it; a kept cell behind the run is an ordinary step whose draw is discarded.  Admission stays in submission order: the head of the queue decides the run of
+    the call, and admission stops at the first queued request whose clipped run differs -- it joins in the next call."""
 
     def __init__(self, stage2, slots: int, n: int, max_joins: Optional[int] = None, *, precision: Optional[str] = None, use_fp16: bool = True, use_graph: bool = True,
-                 lane: int = 0, return_logprobs: bool = False, return_report: Optional[int] = None):
+                 lane: int = 0, return_logprobs: bool = False, return_report: Optional[int] = None, join_run: Optional[int] = None):
         top_n = _report_n(stage2.spec, return_report)
         self.text_cond = bool(stage2.use_txt_cond)
         if self.text_cond and not max_joins:
@@ -382,9 +388,22 @@ class RollingSampler:
         if not 1 <= self.n <= stage2.spec.ctx_len_img:
             raise ValueError(f'n={self.n} outside [1, ctx_len_img={stage2.spec.ctx_len_img}]')
         self.precision, self.use_graph = _precision(precision, use_fp16), bool(use_graph)
-        self.engine = stage2.engine(self.slots, self.n, lane, max_joins=self.max_joins) if self.text_cond else stage2.engine(self.slots, self.n, lane)
+        if join_run is not None and (isinstance(join_run, bool) or not isinstance(join_run, (int, np.integer)) or not 0 <= int(join_run) <= self.n - 1):
+            raise ValueError(f'join_run={join_run!r} outside [0, n - 1 = {self.n - 1}]')
+        self.join_run = None if join_run is None else int(join_run)
+        if self.join_run and self.text_cond and self.L == 3:
+            raise ValueError(f'join_run={self.join_run}: a kept run is not prefilled on a text-conditional model with three code levels (join_run=0 is built)')
+        extra = {} if not self.join_run else {'max_prefix': self.join_run}
+        self.engine = stage2.engine(self.slots, self.n, lane, max_joins=self.max_joins, **extra) if self.text_cond else stage2.engine(self.slots, self.n, lane, **extra)
         dev = self.engine.device
+        if self.join_run is not None:
+            if int(getattr(self.engine, 'max_prefix', 0)) < self.join_run:
+                raise ValueError(f'join_run={self.join_run} exceeds max_prefix={int(getattr(self.engine, "max_prefix", 0))} of the stage-2 engine')
+            self.engine.set_join_run(self.max_joins if self.text_cond else self.slots, self.join_run)
         self.codes = [torch.full((self.slots, self.n) + ((4 ** l,) if l else ()), -1, dtype=torch.int64, device=dev) for l in range(self.L)]
+        # the pass's keep table: the mask on the host, the kept codes in device tensors shaped like the codes (an empty or plain slot: nothing kept)
+        self.keep_mask = np.zeros((self.slots, self.n), dtype=bool)
+        self.kept = [torch.zeros_like(c) for c in self.codes] if self.join_run is not None else None
         self.logprobs = torch.full((self.slots, self.n, (4 ** self.L - 1) // 3), float('nan'), dtype=torch.float32, device=dev) if return_logprobs else None
         self.report = None if top_n is None else new_draw_report(self.slots, self.n, (4 ** self.L - 1) // 3, top_n, dev)
         self.class_cond = bool(stage2.spec.cond == 1)
@@ -403,12 +422,51 @@ class RollingSampler:
     def live(self) -> int:
         return sum(p >= 0 for p in self.pos)
 
-    def submit(self, cond, seed: int, sample_offset: int = 0, **sampler) -> int:
+    def _check_kept(self, keep_mask, kept_codes):
+        """``keep_mask`` / ``kept_codes`` of one request: (mask as a bool numpy array [n], the levels as int64 host tensors), or None without a mask."""
+        if keep_mask is None and kept_codes is None:
+            return None
+        if self.join_run is None:
+            raise ValueError('keep_mask / kept_codes: this rolling pass takes no given cells; build it with RollingSampler(..., join_run=R)')
+        if keep_mask is None or kept_codes is None:
+            raise ValueError('keep_mask and kept_codes come together')
+        m = torch.as_tensor(keep_mask).cpu()
+        if tuple(m.shape) != (self.n,) or m.dtype.is_floating_point:
+            raise ValueError(f'keep_mask: expected bool of shape ({self.n},), got {m.dtype} of shape {tuple(m.shape)}')
+        m = (m != 0).numpy().astype(bool)
+        if not isinstance(kept_codes, (list, tuple)) or len(kept_codes) != self.L:
+            raise ValueError(f'kept_codes: expected the {self.L} code levels as one list, coarse to fine')
+        levels, V = [], int(self.stage2.spec.vocab_top)
+        for l, c in enumerate(kept_codes):
+            t = torch.as_tensor(c).cpu()
+            want = (self.n,) + ((4 ** l,) if l else ())
+            if tuple(t.shape) != want or t.dtype.is_floating_point or t.dtype == torch.bool:
+                raise ValueError(f'kept_codes[{l}]: expected integer codes of shape {want}, got {t.dtype} of shape {tuple(t.shape)}')
+            t = t.to(torch.int64)
+            if m.any():
+                sel = t[torch.from_numpy(m)]
+                lo, hi = int(sel.min()), int(sel.max())
+                if lo < 0 or hi >= V:
+                    raise IndexError(f'kept_codes[{l}]: index out of range (values span [{lo}, {hi}], table has {V} rows)')
+            levels.append(t)
+        return m, levels
+
+    def _run_of(self, kept) -> int:
+        """The leading kept run a request prefills when it joins: its count of leading ones clipped to min(join_run, n - 1); 0 without given cells."""
+        if kept is None or not self.join_run:
+            return 0
+        m = kept[0]
+        run = self.n if m.all() else int(np.argmin(m))
+        return min(run, self.join_run, self.n - 1)
+
+    def submit(self, cond, seed: int, sample_offset: int = 0, keep_mask=None, kept_codes=None, **sampler) -> int:
         """Queues one request and returns its ticket.  ``sampler``: the sampler keywords of ``sampling_ihqgpt`` / ``sampling_hqtransformer``; they travel as the
-        ``row_samplers`` entry of the slot the request is admitted to."""
+        ``row_samplers`` entry of the slot the request is admitted to.  ``keep_mask`` [n] bool and ``kept_codes`` (one tensor per level: [n], [n, 4][, [n, 16]]; read
+        where the mask is set, IndexError outside the vocabulary there): the cells of the request that are given (a pass built with ``join_run=``)."""
         unknown = set(sampler) - set(SAMPLER_KEYS)
         if unknown:
             raise TypeError(f'submit: unexpected keywords {sorted(unknown)} (sampler settings travel here)')
+        kept = self._check_kept(keep_mask, kept_codes)
         if self.class_cond:
             if cond is None or isinstance(cond, bool) or not 0 <= int(cond) < self.stage2.spec.n_classes:
                 raise ValueError(f'cond={cond!r}: a class id in [0, {self.stage2.spec.n_classes}) is required')
@@ -425,7 +483,7 @@ class RollingSampler:
             raise ValueError('cond: an unconditional model takes None')
         entry = step_row_samplers(self.L, [1], [sampler])[0]
         ticket, self.tickets = self.tickets, self.tickets + 1
-        self.queue.append((ticket, cond or 0, int(seed), int(sample_offset), entry))
+        self.queue.append((ticket, cond or 0, int(seed), int(sample_offset), entry, kept))
         return ticket
 
     def step(self, k: int = 1) -> list:
@@ -436,24 +494,34 @@ class RollingSampler:
         k = int(k)
         if not 1 <= k <= self.n:
             raise ValueError(f'step(k={k}): expected 1 <= k <= n = {self.n}')
-        admitted = 0
+        admitted, run = 0, 0                         # the joiners of one call share one clipped leading run: the queue's head decides it
         while self.queue and self.free and (self.max_joins is None or admitted < self.max_joins):
+            if admitted and self._run_of(self.queue[0][5]) != run:
+                break                                # (it joins in the next call, as the head of the queue)
+            run = self._run_of(self.queue[0][5])
             admitted += 1
             slot = self.free.pop(0)
-            self.ticket[slot], self.cond[slot], self.row_seeds[slot], self.row_offsets[slot], self.row_samplers[slot] = self.queue.pop(0)
+            self.ticket[slot], self.cond[slot], self.row_seeds[slot], self.row_offsets[slot], self.row_samplers[slot], kept = self.queue.pop(0)
             self.pos[slot] = 0
+            if self.kept is not None:
+                self.keep_mask[slot] = kept[0] if kept is not None else False
+                for dst, src in zip(self.kept, kept[1] if kept is not None else ()):
+                    dst[slot] = src.to(dst.device)
         if not self.live:
             return []
         cond = torch.tensor(self.cond, dtype=torch.int64) if self.class_cond or self.text_cond else None
         common = dict(precision=self.precision, seed=0, use_graph=self.use_graph, row_seeds=list(self.row_seeds), row_offsets=list(self.row_offsets),
                       row_samplers=list(self.row_samplers), out=self.codes, logprobs_out=self.logprobs, report_out=self.report,
                       row_positions=(list(self.pos), k))
+        if self.kept is not None:                    # every call of the pass stages the table: the captured steps stay the same whether a live request keeps cells or not
+            common['keep'] = (torch.from_numpy(self.keep_mask.copy()), self.kept)
         if self.L == 3:
             self.engine.sample3(self.slots, cond, self.n, **common)
         else:
             self.engine.sample(self.slots, cond, self.n, **common)
-        # the record the library keeps: a row of a text pass that joined in this call drew position 0 in its prompt prefill, in front of the k steps
-        moved = [p if p < 0 else p + k + (1 if self.text_cond and p == 0 else 0) for p in self.pos]
+        # the record the library keeps: a row that joined through a join phase (a text pass; a kept run to prefill) drew position `run` there, in front of the k steps
+        joined = run + 1 if admitted and (self.text_cond or run > 0) else 0
+        moved = [p if p < 0 else p + k + (joined if p == 0 else 0) for p in self.pos]
         done = [s for s in range(self.slots) if self.pos[s] >= 0 and moved[s] >= self.n]
         self.pos = [-1 if p < 0 or p >= self.n else p for p in moved]
         if not done:
@@ -467,6 +535,7 @@ class RollingSampler:
             out.append((self.ticket[s], [c[i] for c in codes]) + ((logprobs[i],) if logprobs is not None else ())
                        + ((DrawReport(*(None if f is None else f[i] for f in report)),) if report is not None else ()))
             self.ticket[s] = None
+            self.keep_mask[s] = False
         self.free = sorted(self.free + done)
         return out
 
@@ -585,21 +654,55 @@ def grids_to_sequences(grids: list) -> list:
     return out
 
 
+def _roll_images(rolling: 'RollingSampler', stage2, B: int, n: int, cond, mask: torch.Tensor, kept: list, sampler: dict) -> list:
+    """``rolling=`` of ``complete_images`` / ``regenerate_region``: image b is ONE request of the rolling pass -- its condition, the key (seed, b) a plain call
+    gives row b, its row of ``mask`` [B, n] and of ``kept`` -- and the pass is drained; -> the codes as the plain call returns them, [B, n], [B, n, 4][, ...].
+    ``sampler`` may hold ``seed``, the sampler settings of ``RollingSampler.submit`` and ``steps_per_call`` (default 16); precision, graphs and the engine are the
+    pass's own."""
+    if not isinstance(rolling, RollingSampler) or rolling.stage2 is not stage2:
+        raise ValueError('rolling: expected a RollingSampler over this model\'s stage 2')
+    if rolling.n != int(n):
+        raise ValueError(f'rolling: the pass has n={rolling.n} positions, the images have {int(n)}')
+    if rolling.queue or rolling.live:
+        raise ValueError('rolling: the pass holds requests of its own; drain it first (the images are submitted and drained together)')
+    sampler = dict(sampler)
+    sampler.pop('text_prefix', None)
+    seed, k = sampler.pop('seed', None), int(sampler.pop('steps_per_call', 16))
+    unknown = set(sampler) - set(SAMPLER_KEYS)
+    if unknown:
+        raise ValueError(f'rolling: {sorted(unknown)} belong to the RollingSampler the images join (its precision, graphs and lane), not to the call')
+    seed = _seed_from_torch() if seed is None else int(seed)
+    _, cond = _batch_and_cond(stage2, B, cond)
+    kept = [c.cpu() for c in kept]
+    tickets = [rolling.submit(None if cond is None else (cond[b] if cond.dim() == 2 else int(cond[b])), seed, sample_offset=b, keep_mask=mask[b],
+                              kept_codes=[c[b] for c in kept], **sampler) for b in range(B)]
+    done = {d[0]: d[1] for d in rolling.drain(max(1, min(k, rolling.n)))}
+    return [torch.stack([done[t][l] for t in tickets]) for l in range(rolling.L)]
+
+
 def complete_images(model, images: torch.Tensor, keep_rows: int, cond=None, encode_precision: Optional[str] = None,
-                    decode_precision: Optional[str] = None, **sampler) -> Tuple[torch.Tensor, list]:
+                    decode_precision: Optional[str] = None, rolling: Optional['RollingSampler'] = None, **sampler) -> Tuple[torch.Tensor, list]:
     """Keep the first ``keep_rows`` rows of every image's top code grid and sample the rest: ``images`` fp32 [B, 3, R, R] in [-1, 1] (what
     ``stage1.get_codes`` takes) -> ``stage1`` codes -> the codes of the first ``P = keep_rows * top_resolution`` positions on every level (the
     bottom / middle grids cut at the matching rows) as ``prefix_codes`` of one sampler call over all ``top_resolution ** 2`` positions ->
     ``decode_codes``.  ``cond``: class ids as in ``sampling_ihqgpt``, or text prompts [B, ctx_len_txt] (two code levels: the prompt and the
     prefix then share one prefill, ``text_prefix=True`` of ``sampling_ihqgpt``); ``sampler``: further keywords of that sampler (cut-offs,
     temperatures, seed, precision ...).  Returns ``(pixels fp32 [B, 3, R, R] in [0, 1], codes)`` with ``codes`` the full-length code list, coarse to fine;
-    its positions < P are the image's own codes."""
+    its positions < P are the image's own codes.
+    ``rolling=RollingSampler(stage2, slots, K K, join_run=R)``: every image joins that rolling pass as one request (key (seed, b), as row b of the plain call) and
+    the pass is drained, instead of the one call: the images prefill min(P, R) of their kept positions in the join phase and may share the pass with other work
+    between calls.  ``sampler`` then holds only ``seed``, sampler settings and ``steps_per_call``."""
     grids = list(model.stage1.code_grids(images, precision=encode_precision))
     K = int(grids[0].shape[-1])
     if not 1 <= int(keep_rows) < K:
         raise ValueError(f'keep_rows={keep_rows} outside [1, {K - 1}]: at least one row of the {K} x {K} top grid is kept and one is left to sample')
     P = int(keep_rows) * K
     prefix = [s[:, :P].contiguous() for s in grids_to_sequences(grids)]
+    if rolling is not None:
+        mask = torch.zeros((int(images.shape[0]), K * K), dtype=torch.bool)
+        mask[:, :P] = True
+        codes = _roll_images(rolling, model.stage2, int(images.shape[0]), K * K, cond, mask, grids_to_sequences(grids), sampler)
+        return decode_codes(model.stage1, codes, decode_precision), codes
     if model.stage2.use_txt_cond and model.stage2.spec.levels == 2:
         sampler['text_prefix'] = True
     codes = sample_codes(model.stage2, int(images.shape[0]), cond, max_seq_len=K * K, prefix_codes=prefix, **sampler)
@@ -618,16 +721,19 @@ def box_keep_mask(K: int, box) -> torch.Tensor:
 
 
 def regenerate_region(model, images: torch.Tensor, box, cond=None, encode_precision: Optional[str] = None,
-                      decode_precision: Optional[str] = None, **sampler) -> Tuple[torch.Tensor, list]:
+                      decode_precision: Optional[str] = None, rolling: Optional['RollingSampler'] = None, **sampler) -> Tuple[torch.Tensor, list]:
     """Draw a box of every image again and keep everything around it: ``images`` fp32 [B, 3, R, R] in [-1, 1] -> ``stage1`` codes -> one sampler call
     over all ``top_resolution ** 2`` positions that keeps every cell outside ``box = (r0, r1, c0, c1)`` (half-open, in top-grid cells) on every code
     level (``keep_mask`` / ``kept_codes`` of the samplers) and draws the inside, each position given everything before it in raster order -- the kept
     cells to the right of and below the box are not seen by the draws, as in any raster-order model -> ``decode_codes``.  ``cond`` and ``sampler`` as in
     ``complete_images``.  Returns ``(pixels fp32 [B, 3, R, R] in [0, 1], codes)``, the codes in the sampler's layout.  What is claimed is the mechanism,
-    not the quality of the seam."""
+    not the quality of the seam.  ``rolling=``: as in ``complete_images`` -- every image one request of that rolling pass, drained."""
     grids = list(model.stage1.code_grids(images, precision=encode_precision))
     B, K = int(images.shape[0]), int(grids[0].shape[-1])
     mask = box_keep_mask(K, box).unsqueeze(0).expand(B, K * K)
+    if rolling is not None:
+        codes = _roll_images(rolling, model.stage2, B, K * K, cond, mask, grids_to_sequences(grids), sampler)
+        return decode_codes(model.stage1, codes, decode_precision), codes
     if model.stage2.use_txt_cond and model.stage2.spec.levels == 2:
         sampler['text_prefix'] = True
     codes = sample_codes(model.stage2, B, cond, max_seq_len=K * K, keep_mask=mask, kept_codes=grids_to_sequences(grids), **sampler)

@@ -302,8 +302,9 @@ int hqt_set_guidance(hqt_handle* h, int n_pairs, const hqt_guide_pair* pairs);
  * staged" and L enter the graph key; the mask lives in device memory: a changed table with the same L replays the same graph.  Every depth head and every precision.
  * The taking call fails with HQT_ERR_INVALID (and a message naming the cause) when B or n_steps differ from the table's, a level pointer is NULL, force_* is given
  * (refused by name: the caller puts forced codes into the kept codes), the call is a prefix entry point (the leading run IS the prefix), or the two rows of a
- * hqt_set_guidance pair keep different positions.  Keeping some levels of a position and not others is not built.  Without a staged table a call launches exactly
- * what it launched before. */
+ * hqt_set_guidance pair keep different positions.  Not built: keeping some levels of a position and not others.  A rolling call (hqt_set_row_positions) takes the
+ * table only on a handle that has opted in with hqt_set_join_run, and reads it per row, by the rules given there; without the opt-in it is refused.  Without a
+ * staged table a call launches exactly what it launched before. */
 int hqt_set_keep_mask(hqt_handle* h, int B, int n_steps, const uint8_t* keep, const int64_t* const* codes);
 
 /* hqt_set_prompt_groups -- no reference counterpart: the reference prefills the text prompt of every row (sampling.py:187-190), also where the rows are candidates of
@@ -393,7 +394,22 @@ int hqt_select_rows(hqt_handle* h, int B_new, const int32_t* rows_from, void* st
  * captured steps, as the prompt prefill of a plain call does, and allocates nothing.  In EXACT a request draws bit for bit what the plain call draws for it in its
  * slot; in FAST and SPLIT the prefill of J prompts may be served by other GEMM kernels than the prefill of B, so the plain call that equals a join is the one
  * that prefills the same J prompts (hqt_set_prompt_groups).
- * Not built: rolling together with segments, keep tables, prefixes or prompt groups (a join prefills every joining row's prompt, equal or not); a depth pass
+ * KEEP TABLES (after hqt_set_join_run(h, J > 0, R), below; without it a staged keep table is refused as it always was).  The table is [B, n] with one device pointer
+ * per level, exactly as hqt_set_keep_mask stages it; row b of it is read only inside the positions row b passes in this call.  Before the steps, outside the
+ * captured graph, the kept codes of row b go into out_* only at kept positions inside the span row b advances over in this call; empty slots and positions outside
+ * the span are neither read nor written.  Every kept position that is not prefilled is an ordinary step of the row, as in a plain keep call: the draw is spent and
+ * discarded, the kept code is what out_* holds and what is fed forward, and logits_out, the log-probabilities and the draw report are written for it.  JOIN RUN:
+ * among the rows with pos[b] == 0 in the call, L = min(smallest leading run of ones of their mask rows, R, n - 1); L is 0 without a table and when no row joins.  The
+ * join phase runs iff the handle is text-conditional or L > 0: the joiners' body input rows -- the prompt rows (text) or the sos / class row, then the L input rows of
+ * positions 1 .. L, read from their kept codes -- go through the body over the joiners alone into the staging buffer, ONE launch hands every joiner its (ctx_len_txt
+ * | 1) + L rows of K/V and its last row of x, and the depth head draws position L (which may itself be kept) under the join table.  The steps then find the joiners
+ * at L + 1: a row that joins through a join phase advances by L + 1 + k (clipped at n), every other row by k (L = 0 on a text handle: the 1 + k above).  Rows of
+ * positions < L of logits_out, the log-probabilities and the report are not written, as in hqt_sample_prefix.  Without a join phase (no text, L == 0) the call
+ * launches what it launched before plus the scatter and the samplers' guard.  Only "rolling" and "a keep table is staged" enter the graph key -- never positions,
+ * mask or L.  HQT_ERR_INVALID in the taking call: no opt-in; the table's B or n differ from the call's; a NULL level pointer; force_* with a table; more rows
+ * joining through a join phase than max_joins; the two rows of a guidance pair keep different positions.
+ * Not built: rolling together with segments, prefixes or prompt groups (a join prefills every joining row's prompt, equal or not); per-row join runs in one prefill
+ * (the joiners of a call share L); a kept run prefilled on text handles with three code levels; a depth pass
  * over the joining rows alone (the join phase's depth head runs over all B rows); hqt_select_rows on a rolling pass (HQT_ERR_STATE: slots are reused in place);
  * a rolling form of the persistent launch. */
 int hqt_set_row_positions(hqt_handle* h, int B, const int32_t* pos, int k);
@@ -405,6 +421,18 @@ int hqt_set_row_positions(hqt_handle* h, int B, const int32_t* pos, int k);
  * handle that never called it refuses hqt_set_row_positions as it always has.
  * HQT_ERR_INVALID: a NULL handle, a handle that is not text-conditional, max_joins outside [0, max_batch].  HQT_ERR_STATE: the handle holds a rolling pass. */
 int hqt_set_max_joins(hqt_handle* h, int max_joins);
+
+/* hqt_set_join_run -- opt-in sizing of rolling calls that take a keep table (hqt_set_row_positions, KEEP TABLES): after hqt_set_join_run(h, J >= 1, R >= 0) such a
+ * call is taken, up to J rows per call join through a join phase, and R is the longest leading kept run they prefill there in one pass.  R <= max_prefix of the
+ * handle (hqt_set_max_prefix has sized the body workspace for such a pass); R == 0 with text conditioning and three code levels, where the prefix prefill is not
+ * built.  On a text-conditional handle the call also counts as hqt_set_max_joins(h, J).  Grows, never shrinks, the staging K/V to [n_layers][J][rows][D] at 4 bytes
+ * per element, rows = ctx_len_txt + R on a text handle and 1 + R otherwise, and the gathered rows [max_batch][D] fp32: the buffers of hqt_set_prompt_groups /
+ * hqt_set_max_joins, sized to the largest need and counted by hqt_workspace_bytes.  A handle without text conditioning and with R == 0 needs none (no join phase
+ * ever runs there).  A sampling call allocates nothing.  A lane from hqt_clone inherits the setting and gets a staging of its own.  max_joins == 0 switches the
+ * opt-in off again and frees nothing.
+ * HQT_ERR_INVALID: a NULL handle, a handle without stage 2, max_joins outside [0, max_batch], max_run outside [0, max_prefix], max_run > 0 on a text handle with
+ * three code levels.  HQT_ERR_STATE: the handle holds a rolling pass. */
+int hqt_set_join_run(hqt_handle* h, int max_joins, int max_run);
 
 /* hqt_sample -- replaces sampling_ihqgpt + iHQGPT.sampling_step (hqvae/utils/sampling.py:164-237,
  * hierarchical_ar.py:428-480, 482-563, 667-789) for a batch of B independent images.
