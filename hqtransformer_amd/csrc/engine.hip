@@ -1145,10 +1145,10 @@ static int ar_linear(hqt_handle* h, const Mode& md, GemmArgs g, const Lin& l, in
                 if (g.ln_parts) g.bias = l.bias_ln;
                 HIPCHK(launch_tile_gemm(g, g.ln_parts ? l.wpk_ln : l.wpk, a_dt, c_dt, tp, h->splitk, st));
                 if (tp.S > 1) {
-                    count_variant(h, "variant:tile_gemm_%dx%d_splitk%d:%s", tp.bm, tp.bn, tp.S, slot.s);
+                    count_variant(h, "variant:tile_gemm_%dx%d%s_splitk%d:%s", tp.bm, tp.bn, tile_geom_suffix(tp.geom), tp.S, slot.s);
                     t.next(SlotName("gemm_combine", g.M).s);
                     HIPCHK(launch_resid_combine(g, h->splitk, tp.S, st));
-                } else count_variant(h, "variant:tile_gemm_%dx%d%s:%s", tp.bm, tp.bn, g.ln_parts ? "_dln" : "", slot.s);
+                } else count_variant(h, "variant:tile_gemm_%dx%d%s%s:%s", tp.bm, tp.bn, tile_geom_suffix(tp.geom), g.ln_parts ? "_dln" : "", slot.s);
                 if (resid_nparts) *resid_nparts = tp.S > 1 ? 1 : g.N / tp.bn;
                 return HQT_OK;
             }

@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "kernels.h"
+#include "tile_plan.h"
 
 hipError_t launch_f32_to_bf16(const float* src, bf16_t* dst, size_t n, hipStream_t st);
 // [O][I][taps] -> [O][taps][I]
@@ -24,7 +25,6 @@ hipError_t launch_stream_gemm(const GemmArgs& g, const bf16_t* wpk, int a_dt, in
 // ---- LDS-tiled MFMA GEMM of the merged AR passes (tile_gemm.hip): same operands and store modes as the streaming GEMM, 512+ rows.
 // S > 1 (STORE_RESID only): fp32 partial slabs [S][32 * a_packed_mb][N], finished by launch_resid_combine (x += bias + sum of
 // slabs, bf16 packed copy, whole-row statistics as ONE part).
-struct TilePlan { int geom; int bm, bn; int S; };    // geom < 0: not taken; S: split-K factor
 constexpr int TILE_CTR_MAX = 4096;          // output tiles of one TS_FUSED launch (GemmArgs.tile_ctr; tools/micro/bench_tile only: measured and lost, tile_gemm.hip)
 bool tile_gemm_ok(const GemmArgs& g, int a_dt, int c_dt);
 TilePlan tile_gemm_plan(const GemmArgs& g);

@@ -20,7 +20,7 @@
 #define SWITCH_TABLE(X)                                                                                                                              \
     /* per-handle values, taken at hqt_create (hqt_set_switch changes the three behind HQT_SWITCH_* afterwards) */                                   \
     X(NO_TILE_GEMM, "HQT_NO_TILE_GEMM", SWP_PRESENT, 0, SWR_LIVE, "merged passes through the streaming GEMMs instead of the tiled ones",             \
-      "tools/fast_tile_error.py, tools/ar_pass_time.py")                                                                                             \
+      "tools/fast_tile_error.py, tools/ar_pass_time.py, tests/test_gpu_merged_rows.py")                                                              \
     X(PERSIST, "HQT_PERSIST", SWP_ZERO_OFF, 1, SWR_LIVE, "0: the launch chain instead of the persistent AR launch (default of HQT_SWITCH_PERSIST)",  \
       "bench.py, tests/test_gpu_dist.py, tests/dist_gpu_worker.py, tests/test_gpu_persist.py, tools/collect_round_evidence.sh")                      \
     X(NO_SINGLE_KEY, "HQT_NO_SINGLE_KEY", SWP_PRESENT, 0, SWR_LIVE, "depth sub-step 0 the long way round (default of HQT_SWITCH_SINGLE_KEY)",        \

@@ -22,6 +22,7 @@
 //     its bf16 copy and partial row statistics, or raw fp32 split-K slabs that resid_combine_kernel finishes.
 #include "fast_kernels.h"
 #include "gemm_generic.h"
+#include "tile_plan.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -37,32 +38,6 @@ typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 #ifndef HQT_TILE_STAGGER
 #define HQT_TILE_STAGGER 1
 #endif
-
-// NLOAD_ > 0 (round 6): NLOAD_ further waves do nothing but the LDS-DMA of the ring (loader waves), the WGM x WGN waves only read fragments and
-// multiply: a `buffer_load ... lds` piece costs its wave 60 .. 180 ISSUE cycles (the texture path takes 64 B/clk), and a wave issues in order -- in the
-// all-consumer form every stage opens with CPW such pieces in front of the matrix instructions of the wave that issues them.
-template <int WGM_, int WGN_, int MBW_, int NT_, int KU_, int NSTAGE_, int NLOAD_ = 0>
-struct TileGeom {
-    static constexpr int WGM = WGM_, WGN = WGN_, MBW = MBW_, NT = NT_, KU = KU_, NSTAGE = NSTAGE_, NLOAD = NLOAD_;
-    static constexpr int NC = WGM * WGN;                       // consumer waves (wave tile (32 MBW) x (32 NT))
-    static constexpr int NW = NC + NLOAD;                      // waves per workgroup
-    static constexpr int NDMA = NLOAD ? NLOAD : NC;            // waves that issue the ring's DMA
-    static constexpr int BM = 32 * MBW * WGM, BN = 32 * NT * WGN;
-    static constexpr int ACH = BM / 32, WCH = BN / 32;         // 1-KiB fragments per k-step
-    static constexpr int CPS = ACH + WCH;
-    static constexpr int CH_STAGE = KU * CPS;
-    static constexpr int CPW = CH_STAGE / NDMA;                // LDS-DMA instructions per issuing wave per stage
-    static constexpr int STAGE_BYTES = CH_STAGE * 1024;
-    static constexpr int RING_BYTES = NSTAGE * STAGE_BYTES;
-    static constexpr int GR = NC * 64 / BM;                    // threads per row in the statistics prologue (consumer waves)
-    // after the ring: (mean, rstd) per row, (bias, colsum) per column, prologue scratch
-    static constexpr int AUX_BYTES = BM * 8 + BN * 8 + GR * BM * 8;
-    static constexpr int LDS_BYTES = RING_BYTES + AUX_BYTES;
-    static constexpr int WG_PER_CU = NW == 4 ? (160 * 1024 / LDS_BYTES < 4 ? 160 * 1024 / LDS_BYTES : 4) : (LDS_BYTES <= 80 * 1024 ? 2 : 1);   // by LDS; 4-wave workgroups up to 4 per CU
-    static_assert(CH_STAGE % NDMA == 0, "every issuing wave issues the same number of DMA pieces per stage");
-    static_assert(NC * 64 % BM == 0 && GR >= 1, "statistics prologue: whole thread groups per row");
-    static_assert(WGN * BM * 8 <= RING_BYTES, "residual epilogue: per-wave partial statistics fit the dead ring");
-};
 
 // GELU (erf form, stage2/layers.py: nn.GELU()) for bf16 outputs: erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, far below the
 // bf16 rounding of the result) -- one v_rcp, one v_exp and 8 FMAs instead of erff's ~40 instructions; 128 of them per lane made
@@ -86,37 +61,6 @@ template <int ACT> __device__ __forceinline__ float tile_act(float v) {
 template <int N> __device__ __forceinline__ void wait_vmcnt() {
     static_assert(N >= 0 && N < 64, "vmcnt immediate");
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// Workgroup id -> (split-K slice, row tile, column tile).  Workgroups b and b + 8 share an XCD (MI355X_MICROARCH.md), and an XCD runs ~32 of
-// them at a time; what its L2 has to pull over the fabric is one K-long fragment stream per DISTINCT row tile and column tile among its
-// workgroups (tools/micro/bench_fill: a CU fills at ~135 GB/s from a hot L2 whatever the path, at ~27 GB/s when every CU pulls from beyond it).
-// Each XCD therefore gets a contiguous run of a grouped order (bands of GM row tiles, walked column by column): a compact block of tiles, not a
-// 32 x 1 column (which made every XCD pull the whole activation panel every k-step: fabric-bound at 4096+ rows).
-//   * GM: up to 12 row tiles make ONE band (an XCD then owns whole columns: the weights cross the fabric once, the small activation panel
-//     eight times; bands of 8 left 2 of 10 row tiles at 640 rows to the last XCDs, which pulled two thirds of the weight matrix each);
-//     more row tiles are cut into equal bands of at most 8.
-//   * split-K: with S | 8 slices, XCD x works on slice x % S only (S = 8: every XCD streams ITS eighth of K of both operands, once).
-__device__ __forceinline__ void tile_of(int b, int total, int S, int TM, int TN, int& z, int& tm, int& tn) {
-    int t;
-    if (S > 1 && (8 % S) == 0) {
-        const int xcd = b & 7, G = 8 / S, xg = xcd / S;
-        z = xcd - xg * S;
-        const int q = total / G, r = total - q * G;
-        t = (xg < r ? xg * (q + 1) : r * (q + 1) + (xg - r) * q) + (b >> 3);
-    } else {
-        z = b / total;
-        const int id = b - z * total;
-        const int q = total >> 3, r = total & 7, xcd = id & 7;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-    }
-    const int nb = TM <= 12 ? 1 : (TM + 7) >> 3;
-    const int GM = (TM + nb - 1) / nb;
-    const int per_group = GM * TN;
-    const int group = t / per_group, in_group = t - group * per_group;
-    const int first = group * GM, rows = min(TM - first, GM);
-    tn = in_group / rows;
-    tm = first + in_group - tn * rows;
 }
 
 template <class G, int STORE, bool DLN, typename TC, int ACT = ACT_NONE>
@@ -666,26 +610,7 @@ __global__ __launch_bounds__(NT) void resid_combine_kernel(float* __restrict__ x
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-// 128 x 128, 4 waves of 64 x 64, 3 stages of 32 k: 48 KiB ring, THREE workgroups per CU.  What the shapes of the AR loop want
-// (tools/micro/bench_tile, in-kernel stamps): a workgroup spends about half of its life outside the main loop (ring fill,
-// epilogue stores at ~10 B/clk/CU, slot turnover), so throughput comes from co-resident workgroups covering each other --
-// with three per CU the matrix pipe is busy 93 % of a main loop.  256 x 256 (one per CU, 71 % busy loop, 20 us of exposed
-// prologue + epilogue per 32 us loop) and 256 x 128 tiles measured 5-30 % slower in the dependent chain of the AR loop
-// at 512 .. 5120 rows (profiles/r03_micro_tile_gemm.txt); they live on in tools/micro/bench_tile.hip.
-typedef TileGeom<2, 2, 2, 2, 2, 3> Tile128;
-// 64 x 128, 4 waves of 32 x 64, 36 KiB ring, FOUR workgroups per CU: the 512-row passes.  A 512 x 6144 output is only 192 tiles of
-// 128 x 128 (qkv: 144) -- fewer workgroups than the chip has CUs, each walking K alone on its CU at the latency-bound pace of a single
-// ring; halving the row tile doubles the workgroups for 1.5x the LDS-DMA bytes per FLOP, which these shapes have to spare.
-typedef TileGeom<2, 2, 1, 2, 2, 3> Tile64;
-// 64 x 128 with EIGHT waves (32 x 32 each), stages of 64 k (24 KiB), two workgroups per CU: launches of about one workgroup per CU
-// (640-row passes: 360 tiles).  In-kernel stamps put a lone 4-wave workgroup's stage at ~650 cycles against 128-256 of MFMA work whatever
-// the ring depth (6 stages in flight instead of 2 measured within 1 %: profiles/r04_tile_variants.txt) -- what paces it is the ISSUE of its
-// LDS-DMA pieces, ~150 cycles per 1-KiB piece and wave; eight waves issue the same pieces twice as fast.
-typedef TileGeom<2, 4, 1, 1, 4, 3> Tile64W8;
-// 128 x 128 with FOUR loader waves beside the four multiplying waves (round 6): 4 stages of 32 k (64 KiB ring, two workgroups per CU)
-typedef TileGeom<2, 2, 2, 2, 2, 4, 4> Tile128PC;
-typedef TileGeom<2, 2, 1, 1, 4, 3> Tile64x64;     // 64 x 64, 4 waves of 32 x 32, stages of 64 k: 48 KiB ring, three workgroups per CU (proj at 640 rows: tile_gemm_plan)
-
+// (the geometries Tile128 .. Tile128PC, the plan and the tile order: tile_plan.h)
 template <class G, int STORE, bool DLN, typename TC, int ACT = ACT_NONE>
 static hipError_t launch_tile_t(const GemmArgs& g, const bf16_t* wpk, int S, float* slabs, hipStream_t st) {
     const int TM = (g.M + G::BM - 1) / G::BM, TN = (g.N + G::BN - 1) / G::BN;
@@ -722,66 +647,17 @@ static hipError_t launch_tile_g(const GemmArgs& g, const bf16_t* wpk, int c_dt, 
 // modes with 16-byte row segments; STORE_QKV parts aligned to the column tile.
 bool tile_gemm_ok(const GemmArgs& g, int a_dt, int c_dt) {
     if (!(g.a_packed_mb >= 16 && a_dt == DT_BF16 && !g.conv_taps && g.batch <= 1 && g.M >= 512)) return false;
-    if (g.N % 128 != 0 || g.K % 32 != 0 || g.K < 256 || g.ldc % 8 != 0 || g.resid) return false;
+    if (!tile_shape_ok(g.M, g.N, g.K, g.store, g.ln_parts != nullptr) || g.ldc % 8 != 0 || g.resid) return false;
     if (g.act != ACT_NONE && g.store != STORE_PACKED) return false;
     if (g.store == STORE_QKV) return c_dt == DT_BF16 && g.qkv_D % 128 == 0 && g.rows_per_group > 0;
     if (g.store == STORE_PACKED) return c_dt == DT_BF16 && g.c_packed_mb > 0;
-    // (proj, K = D: one short K loop over 48 column-tile rows.  Below 640 rows the streaming kernel's 64-row tiles win (23.5 vs 25.2 us at 512 rows); from 640
-    //  rows the 8-wave 64 x 128 tiles do (27.8 -> 24.9 us at 640, 30.0 -> 26.8 at 768, 37.5 -> 29.3 at 1024))
-    if (g.store == STORE_RESID) return c_dt == DT_F32 && g.c_packed_mb > 0 && !g.ln_parts && g.resid_pk && g.resid_parts && g.N == g.ldc && (g.K >= 3072 || g.M >= 640);
+    if (g.store == STORE_RESID) return c_dt == DT_F32 && g.c_packed_mb > 0 && g.resid_pk && g.resid_parts && g.N == g.ldc;      // (rows and K: tile_shape_ok)
     if (g.store == STORE_ROWS) return g.rows_per_group == 0 && g.act == ACT_NONE;      // (the activation is a template parameter, instantiated for STORE_PACKED only)
     return false;
 }
 
-// Split-K factor: only the residual producers with a long K (fc2: K = 4 D) whose tiles would leave most of the 768 resident
-// slots empty; the slices leave fp32 slabs that resid_combine_kernel finishes (one extra launch: not worth it at K = D).
-TilePlan tile_gemm_plan(const GemmArgs& g) {
-    constexpr int max_s = 8;
-    TilePlan p{0, Tile128::BM, Tile128::BN, 1};
-    const int KS = g.K / 16, tiles = ((g.M + p.bm - 1) / p.bm) * (g.N / p.bn);
-    // the narrow residual producer (proj: N = K = D) at the driver's 640 rows: 240 tiles of 64 x 64 (4 waves, three workgroups per CU) instead of 120 of 64 x 128 --
-    // every CU gets one, half the matrix work per workgroup: 18.9 -> 16.5 ms per pass (1024 rows: 384 such tiles lose to 192 of 64 x 128, 21.4 vs 19.4)
-    if (g.store == STORE_RESID && g.K < 3072 && ((g.M + 63) / 64) * (g.N / 64) <= 256 && KS % Tile64x64::KU == 0 && KS / Tile64x64::KU >= 2 * Tile64x64::NSTAGE)
-        return TilePlan{3, 64, 64, 1};
-    // one round of 128 x 128 tiles that fills most of the chip (640 rows: qkv 180, fc1 240 tiles): the loader-wave geometry -- in-kernel stamps at 640 rows
-    // (profiles/r06_micro_tile_gemm.txt): main loop 18.4 k cycles against 28.9 k for the all-consumer 128 x 128 tile, workgroup life 13.5-14 us against the
-    // 8-wave 64 x 128 tiles' grid span of 16.5-17 us (360 / 480 workgroups: two rounds on part of the chip)
-    if (g.store != STORE_RESID && tiles >= 160 && tiles <= 256 && KS % Tile128PC::KU == 0 && KS / Tile128PC::KU >= 2 * Tile128PC::NSTAGE)
-        return TilePlan{4, Tile128PC::BM, Tile128PC::BN, 1};
-    if (g.store != STORE_RESID && tiles < 256 && KS / Tile64::KU >= Tile64::NSTAGE) {
-        const int t64 = ((g.M + Tile64::BM - 1) / Tile64::BM) * (g.N / Tile64::BN);
-        if (t64 <= 512 && KS % Tile64W8::KU == 0 && KS / Tile64W8::KU >= 2 * Tile64W8::NSTAGE) return TilePlan{2, Tile64::BM, Tile64::BN, 1};
-        return TilePlan{1, Tile64::BM, Tile64::BN, 1};
-    }
-    if (g.store == STORE_RESID && g.K < 3072 && tiles < 256 && KS % Tile64W8::KU == 0 && KS / Tile64W8::KU >= 2 * Tile64W8::NSTAGE)
-        return TilePlan{2, Tile64::BM, Tile64::BN, 1};
-    // the wide-K residual producer when its 128 x 128 tiles are ONE round over most of the chip (fc2 at 2560 rows: 240 tiles): the loader-wave geometry without split-K --
-    // grid span 46 us against 60-69 for 480 tiles of 64 x 128 (profiles/r06_micro_tile_gemm.txt: main loop 73 k cycles against 115 k for the all-consumer 128 x 128 tile)
-    if (g.store == STORE_RESID && g.K >= 3072 && tiles >= 160 && tiles <= 256 && KS % Tile128PC::KU == 0 && KS / Tile128PC::KU >= 2 * Tile128PC::NSTAGE)
-        return TilePlan{4, Tile128PC::BM, Tile128PC::BN, 1};
-    if (g.store == STORE_RESID && g.K >= 3072 && tiles < 256) {
-        // The wide-K residual producer (fc2).  Measured per (geometry, S) at the row counts the schedules produce (profiles/r04_fc2_plans.txt; GEMM + combine,
-        // ms per pass): what counts is whole ROUNDS of workgroups (128 x 128: one per CU, 8-wave 64 x 128: two) and the slab traffic of the combine.
-        //   * 8-wave 64 x 128 tiles without split-K when they fill the chip evenly (at most one or close to two per CU): 1024 rows 53.4 -> 47.5, 2560 rows 20.2 -> 18.4;
-        //   * S = 4 when 4 x tiles is one round or a whole number of rounds: 512 rows 36.4 -> 34.7, 640 rows 38.0 -> 35.9, 2048 rows 80.9 -> 74.0 (was S = 8 / 8 / 3);
-        //   * else the largest S that keeps the grid under 2.25 rounds.
-        const int t64 = ((g.M + Tile64::BM - 1) / Tile64::BM) * (g.N / Tile64::BN);
-        if (((t64 >= 176 && t64 <= 208) || (t64 >= 448 && t64 <= 512)) && KS % Tile64W8::KU == 0 && KS / Tile64W8::KU >= 2 * Tile64W8::NSTAGE)
-            return TilePlan{2, Tile64::BM, Tile64::BN, 1};
-        if ((tiles * 4 <= 256 || tiles % 64 == 0) && KS % (Tile128::KU * 4) == 0 && KS / 4 / Tile128::KU >= 2 * Tile128::NSTAGE) {
-            p.S = 4;
-            // one round (640 rows: 60 tiles x 4 slices = 240 workgroups): the loader-wave geometry (fc2 at 640 rows, GEMM + combine: 29.2 -> 26.6 us).
-            // Finishing the slices INSIDE the launch (TS_FUSED: write-through slabs, the tile's last arriver sums them) was built and measured in round 6 and LOSES:
-            // 47.1 us (59.1 on this geometry) against 26.6 -- 256 KB of dependent sc1 reads by one workgroup per tile behind 64 KB of write-through stores per workgroup
-            // (profiles/r06_micro_tile_fused.txt); the product never selects it, tools/micro/bench_tile still times and checks it.
-            if (tiles * 4 <= 256 && KS / 4 / Tile128PC::KU >= 2 * Tile128PC::NSTAGE) p.geom = 4;
-            return p;
-        }
-        for (int S : {8, 6, 4, 3, 2})
-            if (S <= max_s && tiles * S <= 576 && KS % (Tile128::KU * S) == 0 && KS / S / Tile128::KU >= 2 * Tile128::NSTAGE) { p.S = S; break; }
-    }
-    return p;
-}
+static_assert(TPS_ROWS == STORE_ROWS && TPS_QKV == STORE_QKV && TPS_PACKED == STORE_PACKED && TPS_RESID == STORE_RESID, "tile_plan.h restates the store modes");
+TilePlan tile_gemm_plan(const GemmArgs& g) { return tile_plan(g.M, g.N, g.K, g.store, g.ln_parts != nullptr); }
 
 hipError_t launch_tile_gemm(const GemmArgs& g, const bf16_t* wpk, int a_dt, int c_dt, const TilePlan& p, float* slabs, hipStream_t st) {
     (void)a_dt;
